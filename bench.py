@@ -9,12 +9,14 @@ sequence of C-ABI calls the product driver (indelminer_amd/host, run_pipeline) i
   im_dev_realign_n     every candidate: K1-K4, evidence slots (a2-a11)
   im_dev_flush_groupby every READCHUNK flush point + the end-of-contig flush (a12, node selection) and the split-read clusters of
                        all flushes (a12) in three chip-wide launches (IM_BENCH_FLUSH=seq: the one-workgroup flush list + four group-by launches)
-After the timed region every buffer set is checked against the pass run alone and the depths against the pileup rule;
-at N > 1 (or IM_BENCH_FORCE_COMM=1) the product CLI is also run on all ranks (end_to_end_multi_gpu).
+A plain run sets up, warms up, times exactly --steps steps, writes what the last step computed if --dump-outputs DIR is
+given, and prints the line.  With --full, after the timed region every buffer set is checked against the pass run alone and
+the depths against the pileup rule, the region is repeated for its spread, the roofline and the CPU / whole-program legs are
+measured; at N > 1 (or IM_BENCH_FORCE_COMM=1) the product CLI is also run on all ranks (end_to_end_multi_gpu).
 Inputs (reference, the records as the BAM file holds them) are resident in HBM before the timed region
 starts; `value` counts the records the timed kernels read -- all of them.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): synthetic 1 Mb contig, 100 bp PE reads at
@@ -40,8 +42,9 @@ from indelminer_amd import capi, rawrec, synth  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 PIPELINE_DEPTH = int(os.environ.get("IM_BENCH_DEPTH", "4"))   # sets of realign output buffers in flight
-MIN_TIMED_S = 0.12              # the --steps long region is repeated until at least this much time has been measured (and at least
-MIN_REGIONS, MAX_REGIONS = 5, 400   # MIN_REGIONS times): ms_per_step is the MEDIAN region's, the spread is reported beside it
+MIN_TIMED_S = 0.12              # --full: the --steps long region is repeated until at least this much time has been measured (and at
+MIN_REGIONS, MAX_REGIONS = 5, 400   # least MIN_REGIONS times); the median and spread of the regions are reported beside ms_per_step
+DUMP_LIMIT_BYTES = 60_000_000   # --dump-outputs: at most this much array data (a fixed, seeded sample of the rows beyond it): < 64 MB with the headers
 BRACKET_STEPS = 96              # after the timed regions: this many overlapped steps of which every fourth has ONE launch bracketed by HIP
                                 # events on its stream (realign / triage alternating); those steps are issued call by call, not as a graph
 FLUSH_WIDE = os.environ.get("IM_BENCH_FLUSH", "wide") == "wide"   # im_dev_flush_groupby (3 chip-wide launches) or the sequential flush list + 4 group-by launches
@@ -306,6 +309,59 @@ class PipeStep:
         p = self.last["pipe"]
         c = p.fetch_counts()
         return c, p.d_res.download(capi.RESULT_DTYPE, max(int(c[0]), 1))[:int(c[0])], p.d_counts.download(np.int32, 2)
+
+
+def step_outputs(ps, clen, n_query=2000, seed=5):
+    """What the last step handed its caller, as float64 arrays (every value is an int32 / uint32, exact in float64): per
+    candidate read its record and the realign record (status, bands, alignment ops, evidence), per evidence slot the flush
+    that consumed it, the split-read clusters in key order (the group-by's table order is not part of its answer) and DP= range
+    sums of the contig over fixed seeded ranges.  Fields a record leaves undefined (bands of a read that aborted, ops and
+    evidence of a read without evidence, entries beyond n_band / n_ops / n_ev) are written as 0."""
+    cur = ps.last
+    p = cur["pipe"]
+    nc = int(p.fetch_counts()[0])
+    res = p.d_res.download(capi.RESULT_DTYPE, max(nc, 1))[:nc]
+    st = res["status"]
+    has_bands, has_ev = st >= 0, st == 1
+    n_band = np.where(has_bands, res["n_band"], 0)
+    n_ops = np.where(has_ev, res["n_ops"], 0)
+    n_ev = np.where(has_ev, res["n_ev"], 0)
+    band = np.stack([res["band"][f] for f in res.dtype["band"].base.names], axis=-1).astype(np.float64)
+    band *= (np.arange(2)[None, :] < n_band[:, None])[:, :, None]
+    ops = res["ops"].astype(np.float64) * (np.arange(capi.MAX_OPS)[None, :] < n_ops[:, None])
+    ev = np.stack([res["ev"][f] for f in res.dtype["ev"].base.names], axis=-1).astype(np.float64)
+    ev *= (np.arange(capi.MAX_EV)[None, :] < n_ev[:, None])[:, :, None]
+    cons = p.d_consumed.download(np.int32, p.n_slots)
+    key, first, count, order = p.clusters()
+    srt = np.lexsort(key.T[::-1]) if len(key) else np.zeros(0, np.int64)
+    members = np.concatenate([order[first[i]:first[i] + count[i]] for i in srt]) if len(srt) else np.zeros(0, np.int32)
+    rng = np.random.default_rng(seed)
+    beg = rng.integers(0, clen - 1, n_query).astype(np.int32)
+    end = np.minimum(beg + rng.integers(1, 2000, n_query), clen).astype(np.int32)
+    tid = (ps.k - 1) % len(ps.sets)           # buffer set k works on contig k
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    return {"candidate_record": f64(p.d_cand_rec.download(np.int32, max(nc, 1))[:nc]),
+            "candidate_status": f64(st), "candidate_n_band": f64(n_band), "candidate_band": band,
+            "candidate_ref_start": f64(np.where(has_ev, res["ref_start"], 0)), "candidate_n_ops": f64(n_ops), "candidate_ops": ops,
+            "candidate_n_ev": f64(n_ev), "candidate_evidence": ev,
+            "slot_flush": f64(np.concatenate([cons[:nc * capi.MAX_EV], cons[p.cap_cand * capi.MAX_EV:p.cap_cand * capi.MAX_EV + p.n_pe]])),
+            "cluster_key": f64(key[srt]), "cluster_count": f64(count[srt]), "cluster_members": f64(members),
+            "depth_range_beg": f64(beg), "depth_range_end": f64(end), "depth_range_sum": f64(ps.ctx.depth_query_tid(tid, beg, end))}
+
+
+def dump_outputs(out, out_dir, limit=DUMP_LIMIT_BYTES, seed=7):
+    """DIR/<name>.npy for every array of `out`.  Beyond `limit` bytes in all, every array keeps the same fraction of its rows,
+    chosen with a fixed seed and written beside it as <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes + 8 * len(a) for a in out.values())
+    frac = min(1.0, limit / max(total, 1))
+    rng = np.random.default_rng(seed)
+    for name, a in out.items():
+        if frac < 1.0:
+            rows = np.sort(rng.choice(len(a), int(len(a) * frac), replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def copy_peak_gbs(ctx, nbytes=1 << 30, reps=5):
@@ -905,6 +961,11 @@ def main():
     ap.add_argument("--no-shard3", action="store_true", help="skip the config-3 per-GPU shard measurement (N=1 only)")
     ap.add_argument("--no-config3", action="store_true", help="skip the whole-program leg on BASELINE configs[2] at full size (N=1 only, about a minute)")
     ap.add_argument("--no-config5", action="store_true", help="skip the tumour / normal leg (BASELINE configs[4]: discovery + annotate mode, N=1 only, about a minute and a half)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: repeated timed regions and their spread, the overlap / depth self-checks, the roofline, "
+                         "the CPU baselines and the whole-program legs (the --no-* options thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float64, at most 64 MB in all")
     args = ap.parse_args()
 
     # stdout carries ONE JSON line and nothing else: gloo ("[Gloo] Rank 0 is connected ...") and librccl (its
@@ -939,11 +1000,11 @@ def main():
 
     # ---- no data-path collective in the timed step: contigs (and pieces of contigs) are independent on the device; the product's
     # exchanges -- one all-gather of the ranks' logs before the walk, one sum of the depth arrays when pieces of a contig were
-    # walked by several ranks -- happen once per RUN and are measured where they happen, in end_to_end_multi_gpu ----
+    # walked by several ranks -- happen once per RUN and are measured where they happen, in end_to_end_multi_gpu (--full) ----
     ps.step(); ps.sync()
     c0, res0, counts0 = ps.results()
     assert int(c0[0]) == n_cand and int(c0[3]) == 0 and int(c0[4]) == 0, (c0, n_cand)
-    digest0 = ps.digest(ps.last)           # the pass on its own, nothing else on the device
+    digest0 = ps.digest(ps.last) if args.full else None     # the pass on its own, nothing else on the device
     collective = "none in the timed step (shards are independent); the product's per-run exchanges are in end_to_end_multi_gpu"
 
     def barrier():
@@ -957,9 +1018,9 @@ def main():
         ps.step()
     barrier()
 
-    # ---- the timed region: EXACTLY --steps steps between barrier + device sync on both sides, max over ranks.  A region of 20 steps
-    # is 1.3 ms, so the region is repeated (same bracket every time) until MIN_TIMED_S have been measured; the line carries the
-    # MEDIAN region and the spread.  Nothing but graph launches is issued inside a region.
+    # ---- the timed region: EXACTLY --steps steps between barrier + device sync on both sides, max over ranks.  Nothing but graph
+    # launches is issued inside a region.  With --full the region is repeated (same bracket every time) until MIN_TIMED_S have
+    # been measured, and the median and spread of the regions go beside the first one's ms_per_step.
     def region():
         barrier()
         t0 = time.perf_counter()
@@ -976,7 +1037,65 @@ def main():
             e = float(t[0])
         return e
 
-    regions = [region()]
+    elapsed = region()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(ps, len(refs[0])), args.dump_outputs)
+    if dist is not None:
+        tot = torch.tensor([n_reads, n_cand], dtype=torch.int64)
+        dist.all_reduce(tot, op=dist.ReduceOp.SUM)
+        total_reads, total_cand = int(tot[0]), int(tot[1])
+    else:
+        total_reads, total_cand = n_reads, n_cand
+    ms_per_step = elapsed / args.steps * 1e3
+    value = total_reads * args.steps / elapsed
+    line = {
+        "metric": "reads/sec through split-read realign+cluster; VCF diff-clean vs reference",
+        "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "ms_per_step_is": "one timed region of exactly --steps steps, divided by --steps",
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u8/int32", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: synthetic %.1f Mb contig per GPU, 100 bp PE reads at %gx, seeded "
+                               "1-50 bp indels every ~2 kb, BWA-like S/I/D emission; -k 6 -g 0 -s 1000 -n 10 -q 10"
+                               % (args.ref_len / 1e6, args.coverage),
+                   "reads_per_step": total_reads, "candidates_per_step": total_cand,
+                   "record_bytes_per_step_rank0": ps.record_bytes,
+                   "flushes_per_step": len(ps.flushes),
+                   "candidates_per_s": total_cand * args.steps / elapsed,
+                   "pipeline_depth": PIPELINE_DEPTH, "hip_graph": os.environ.get("IM_BENCH_GRAPH", "1") == "1",
+                   "parallelism": "contig-sharded x%d" % world, "collective": collective,
+                   "timed_region": "the product driver's device pass over EVERY delivered record of the shard: triage "
+                                   "(candidate rules, base decode, CIGAR evidence, pileup depth scatter) -> depth scan of the contig -> realign -> "
+                                   "one flush cut per READCHUNK flush point -> split-read group-by; BGZF inflate and the pair table stay on the host "
+                                   "(north_star) and are in end_to_end (--full), not here"},
+        "full": bool(args.full),
+    }
+    if args.dump_outputs:
+        line["outputs_dumped"] = "rank 0's last timed step, as .npy files under --dump-outputs"
+    checks = {"candidates_counted_on_the_device_equal_the_simulator": True}     # asserted above
+    if args.full:
+        full_legs(args, line, checks, ps, ctx, refs, rd, cand, region, elapsed, digest0, L, rank, world, local_rank, dist)
+    if rank == 0:
+        # every self-check of the line in one place; the process exits non-zero when one of them is not true
+        line["self_checks"] = checks
+        line["self_checks_all_true"] = all(checks.values())
+        sys.stdout.flush()
+        os.write(real_stdout, (json.dumps(line) + "\n").encode())
+        failed = not line["self_checks_all_true"]
+    if dist is not None:
+        dist.destroy_process_group()
+    ctx.close()
+    if rank == 0 and failed:
+        sys.stderr.write("bench.py: a self-check of the line is not true: %s\n" % [k for k, v in line["self_checks"].items() if not v])
+        sys.exit(1)
+
+
+def full_legs(args, line, checks, ps, ctx, refs, rd, cand, region, elapsed, digest0, L, rank, world, local_rank, dist):
+    """--full: everything beside the headline, added to `line` and `checks` -- the repeated timed regions and their spread, the
+    overlap / depth self-checks, the roofline, the CPU baselines and the whole-program legs"""
+    if dist is not None:
+        import torch
+    n_reads, n_cand = rd.n, len(cand["index"])
+    regions = [elapsed]
     n_regions = int(min(MAX_REGIONS, max(MIN_REGIONS, np.ceil(MIN_TIMED_S / max(regions[0], 1e-6)))))
     if dist is not None:
         t = torch.tensor([n_regions], dtype=torch.int64)
@@ -985,13 +1104,7 @@ def main():
     for _ in range(n_regions - 1):
         regions.append(region())
     regions = np.array(regions)
-    elapsed = float(np.median(regions))
-    if dist is not None:
-        tot = torch.tensor([n_reads, n_cand], dtype=torch.int64)
-        dist.all_reduce(tot, op=dist.ReduceOp.SUM)
-        total_reads, total_cand = int(tot[0]), int(tot[1])
-    else:
-        total_reads, total_cand = n_reads, n_cand
+    median = float(np.median(regions))
 
     # ---- outside the timing: overlapped steps with ONE launch of every fourth step bracketed by HIP events on its stream
     timers = []
@@ -1027,177 +1140,145 @@ def main():
             e2e_mg = end_to_end_multi(rank, world, local_rank, dist)
         except Exception as ex:                 # plumbing; never hides the kernel numbers
             e2e_mg = {"error": str(ex)}
-    if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        value = total_reads * args.steps / elapsed
-        cpu = None
-        cpu_port = None
-        parity = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu, ref_out = cpu_reference_baseline(refs[0], cand, L, n_reads)
-            if ref_out is not None:
-                m = len(ref_out)
-                st = res["status"][:m]
-                ok = (np.where(st == 1, res["n_ev"][:m], 0) == ref_out[:, 0])
-                has = ref_out[:, 0] > 0
-                ev0 = res["ev"][:m, 0]
-                ok &= ~has | ((ev0["cls"] == ref_out[:, 1]) & (ev0["b1"] == ref_out[:, 2]) & (ev0["b2"] == ref_out[:, 3]))
-                parity = "identical to the reference on %d sampled reads" % m if bool(ok.all()) else \
-                    "MISMATCH on %d of %d sampled reads" % (int((~ok).sum()), m)
-                try:
-                    cpu_port = cpu_port_baseline(refs[0], cand, L, n_reads, min(m, 20000))
-                except Exception as ex:
-                    cpu_port = {"error": str(ex)}
-        e2e = None
-        if world == 1 and not args.no_cpu_baseline:
+    if rank != 0:
+        return
+    cpu = None
+    cpu_port = None
+    parity = None
+    if world == 1 and not args.no_cpu_baseline:
+        cpu, ref_out = cpu_reference_baseline(refs[0], cand, L, n_reads)
+        if ref_out is not None:
+            m = len(ref_out)
+            st = res["status"][:m]
+            ok = (np.where(st == 1, res["n_ev"][:m], 0) == ref_out[:, 0])
+            has = ref_out[:, 0] > 0
+            ev0 = res["ev"][:m, 0]
+            ok &= ~has | ((ev0["cls"] == ref_out[:, 1]) & (ev0["b1"] == ref_out[:, 2]) & (ev0["b2"] == ref_out[:, 3]))
+            parity = "identical to the reference on %d sampled reads" % m if bool(ok.all()) else \
+                "MISMATCH on %d of %d sampled reads" % (int((~ok).sum()), m)
             try:
-                e2e = end_to_end(refs, rd)
-            except Exception as ex:              # plumbing; never hides the kernel numbers
-                e2e = {"error": str(ex)}
+                cpu_port = cpu_port_baseline(refs[0], cand, L, n_reads, min(m, 20000))
+            except Exception as ex:
+                cpu_port = {"error": str(ex)}
+    e2e = None
+    if world == 1 and not args.no_cpu_baseline:
         try:
-            peak_measured = copy_peak_gbs(ctx)
-        except Exception:
-            peak_measured = None
+            e2e = end_to_end(refs, rd)
+        except Exception as ex:              # plumbing; never hides the kernel numbers
+            e2e = {"error": str(ex)}
+    try:
+        peak_measured = copy_peak_gbs(ctx)
+    except Exception:
+        peak_measured = None
+    try:
+        h2d = h2d_pinned_gbs(ctx)
+    except Exception:
+        h2d = None
+    try:
+        s_pcie = ps.measure_with_uploads(min(max(args.steps, 50), 400))
+    except Exception as ex:
+        s_pcie = None
+        sys.stderr.write("measure_with_uploads: %s\n" % ex)
+    line["timed_regions"] = {"n": int(len(regions)), "timed_s_in_total": float(regions.sum()),
+                             "ms_per_step_median": median / args.steps * 1e3,
+                             "ms_per_step_min": float(regions.min() / args.steps * 1e3), "ms_per_step_max": float(regions.max() / args.steps * 1e3),
+                             "spread_iqr_over_median": float((np.percentile(regions, 75) - np.percentile(regions, 25)) / median),
+                             "spread_range_over_median": float((regions.max() - regions.min()) / median)}
+    line["config"].update({
+        "h2d_pinned_gbs": h2d,
+        "reads_per_s_with_the_records_crossing_pcie": (n_reads / s_pcie) if s_pcie else None,
+        "reads_per_s_with_the_records_crossing_pcie_note": "MEASURED: every step uploads its records from pinned host memory on its stream, "
+                                                           "then runs the pass; 4 streams overlap copies and kernels as the product's walkers do",
+        "ms_per_step_with_the_records_crossing_pcie": s_pcie * 1e3 if s_pcie else None,
+        "evidence_nodes_per_step_rank0": nodes, "clusters_per_step_rank0": ncl,
+        "band_alignments_per_s": n_band * world * args.steps / elapsed,
+        "gcups": 2.0 * L * n_band * world * args.steps / elapsed / 1e9,
+        "parity": parity,
+        "overlapped_passes_equal_the_pass_alone": overlap_ok,
+        "depth_range_sums_equal_the_pileup_rule": depth_ok,
+        "pass_digest": {"candidates": digest0[0], "clusters": digest0[1], "md5": digest0[2],
+                        "of_each_buffer_set_after_the_timed_region": [dg[2] for dg in digests]}})
+    line["roofline"] = {"bound": "hbm", "kernel": "realign_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic()[0],
+                        "longest_stage_of_the_step": "realign_kernel" if q_realign >= q_triage else "triage (classify + emit + decode, three launches)",
+                        "traffic_source": "%s: PMC passes of an EARLIER run of this command (FETCH_SIZE x 2 + WRITE_SIZE per launch), not measured in this run" % measured_traffic()[1],
+                        "issue": measured_issue(),
+                        "issue_note": "what binds this kernel: its reference windows come out of L2 (traffic is a fraction of the algorithmic bytes), the time goes "
+                                      "into instruction issue and LDS round trips -- valu/salu/lds instructions per candidate read, VALU issue cycles over "
+                                      "the SIMDs' cycles, LDS bank-conflict cycles over LDS-active cycles, from the same committed counter passes as `traffic`",
+                        "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": q_realign,
+                        "avg_launch_ms_note": "HIP events around the realign launch on its stream with nothing else on the device (the kernel's own "
+                                              "duration, what rocprofv3 --kernel-trace reports for it); inside the timed region's overlapped steps the same "
+                                              "bracket also holds the wait for a dispatch slot behind the other streams' launches",
+                        "avg_launch_ms_inside_the_overlapped_steps": float(realign_ms.mean()) if len(realign_ms) else None, "launches_timed_inside": int(len(realign_ms)),
+                        "min_launch_ms_inside": float(realign_ms.min()) if len(realign_ms) else None,
+                        "peak_measured_copy_gbs": peak_measured,
+                        "frac_of_measured_copy": (achieved / peak_measured) if peak_measured else None,
+                        "triage": {"algorithmic_bytes_per_launch": int(tri_bytes), "avg_ms_3_launches": q_triage,
+                                   "avg_ms_inside_the_overlapped_steps": float(triage_ms.mean()) if len(triage_ms) else None,
+                                   "achieved_gbs": tri_bytes / (q_triage * 1e-3) / 1e9}}
+    line["cpu_baseline"] = cpu
+    line["cpu_baseline_hoisted"] = cpu_port
+    line["end_to_end"] = e2e
+    line["end_to_end_multi_gpu"] = e2e_mg
+    if world == 1 and not args.no_shard3:
         try:
-            h2d = h2d_pinned_gbs(ctx)
-        except Exception:
-            h2d = None
-        try:
-            s_pcie = ps.measure_with_uploads(min(max(args.steps, 50), 400))
+            line["shard_config3"] = shard3_measure(0 if os.environ.get("IM_BENCH_ONE_DEVICE") == "1" else local_rank)
         except Exception as ex:
-            s_pcie = None
-            sys.stderr.write("measure_with_uploads: %s\n" % ex)
-        line = {
-            "metric": "reads/sec through split-read realign+cluster; VCF diff-clean vs reference",
-            "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "ms_per_step_is": "the median of %d timed regions of --steps steps each" % len(regions),
-            "timed_regions": {"n": int(len(regions)), "timed_s_in_total": float(regions.sum()),
-                              "ms_per_step_min": float(regions.min() / args.steps * 1e3), "ms_per_step_max": float(regions.max() / args.steps * 1e3),
-                              "spread_iqr_over_median": float((np.percentile(regions, 75) - np.percentile(regions, 25)) / elapsed),
-                              "spread_range_over_median": float((regions.max() - regions.min()) / elapsed)},
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8/int32", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: synthetic %.1f Mb contig per GPU, 100 bp PE reads at %gx, seeded "
-                                   "1-50 bp indels every ~2 kb, BWA-like S/I/D emission; -k 6 -g 0 -s 1000 -n 10 -q 10"
-                                   % (args.ref_len / 1e6, args.coverage),
-                       "reads_per_step": total_reads, "candidates_per_step": total_cand,
-                       "record_bytes_per_step_rank0": ps.record_bytes,
-                       "h2d_pinned_gbs": h2d,
-                       "reads_per_s_with_the_records_crossing_pcie": (n_reads / s_pcie) if s_pcie else None,
-                       "reads_per_s_with_the_records_crossing_pcie_note": "MEASURED: every step uploads its records from pinned host memory on its stream, "
-                                                                          "then runs the pass; 4 streams overlap copies and kernels as the product's walkers do",
-                       "ms_per_step_with_the_records_crossing_pcie": s_pcie * 1e3 if s_pcie else None,
-                       "flushes_per_step": len(ps.flushes), "evidence_nodes_per_step_rank0": nodes, "clusters_per_step_rank0": ncl,
-                       "candidates_per_s": total_cand * args.steps / elapsed,
-                       "band_alignments_per_s": n_band * world * args.steps / elapsed,
-                       "gcups": 2.0 * L * n_band * world * args.steps / elapsed / 1e9,
-                       "pipeline_depth": PIPELINE_DEPTH, "hip_graph": os.environ.get("IM_BENCH_GRAPH", "1") == "1",
-                       "parallelism": "contig-sharded x%d" % world, "collective": collective,
-                       "timed_region": "the product driver's device pass over EVERY delivered record of the shard: triage "
-                                       "(candidate rules, base decode, CIGAR evidence, pileup depth scatter) -> depth scan of the contig -> realign -> "
-                                       "one flush cut per READCHUNK flush point -> split-read group-by; BGZF inflate and the pair table stay on the host "
-                                       "(north_star) and are in end_to_end, not here",
-                       "parity": parity,
-                       "overlapped_passes_equal_the_pass_alone": overlap_ok,
-                       "depth_range_sums_equal_the_pileup_rule": depth_ok,
-                       "pass_digest": {"candidates": digest0[0], "clusters": digest0[1], "md5": digest0[2],
-                                       "of_each_buffer_set_after_the_timed_region": [dg[2] for dg in digests]}},
-            "roofline": {"bound": "hbm", "kernel": "realign_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic()[0],
-                         "longest_stage_of_the_step": "realign_kernel" if q_realign >= q_triage else "triage (classify + emit + decode, three launches)",
-                         "traffic_source": "%s: PMC passes of an EARLIER run of this command (FETCH_SIZE x 2 + WRITE_SIZE per launch), not measured in this run" % measured_traffic()[1],
-                         "issue": measured_issue(),
-                         "issue_note": "what binds this kernel: its reference windows come out of L2 (traffic is a fraction of the algorithmic bytes), the time goes "
-                                       "into instruction issue and LDS round trips -- valu/salu/lds instructions per candidate read, VALU issue cycles over "
-                                       "the SIMDs' cycles, LDS bank-conflict cycles over LDS-active cycles, from the same committed counter passes as `traffic`",
-                         "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": q_realign,
-                         "avg_launch_ms_note": "HIP events around the realign launch on its stream with nothing else on the device (the kernel's own "
-                                               "duration, what rocprofv3 --kernel-trace reports for it); inside the timed region's overlapped steps the same "
-                                               "bracket also holds the wait for a dispatch slot behind the other streams' launches",
-                         "avg_launch_ms_inside_the_overlapped_steps": float(realign_ms.mean()) if len(realign_ms) else None, "launches_timed_inside": int(len(realign_ms)),
-                         "min_launch_ms_inside": float(realign_ms.min()) if len(realign_ms) else None,
-                         "peak_measured_copy_gbs": peak_measured,
-                         "frac_of_measured_copy": (achieved / peak_measured) if peak_measured else None,
-                         "triage": {"algorithmic_bytes_per_launch": int(tri_bytes), "avg_ms_3_launches": q_triage,
-                                    "avg_ms_inside_the_overlapped_steps": float(triage_ms.mean()) if len(triage_ms) else None,
-                                    "achieved_gbs": tri_bytes / (q_triage * 1e-3) / 1e9}},
-            "cpu_baseline": cpu,
-            "cpu_baseline_hoisted": cpu_port,
-            "end_to_end": e2e,
-            "end_to_end_multi_gpu": e2e_mg,
-        }
-        if world == 1 and not args.no_shard3:
-            try:
-                line["shard_config3"] = shard3_measure(0 if os.environ.get("IM_BENCH_ONE_DEVICE") == "1" else local_rank)
-            except Exception as ex:
-                line["shard_config3"] = {"error": str(ex)}
-        if world == 1 and not args.no_shard3:
-            try:
-                line["long_reads_2x300"] = long_reads_measure(0 if os.environ.get("IM_BENCH_ONE_DEVICE") == "1" else local_rank)
-            except Exception as ex:
-                line["long_reads_2x300"] = {"error": str(ex)}
-        if world == 1 and not args.no_shard3:
-            try:
-                line["other_parameters"] = other_parameters_measure(0 if os.environ.get("IM_BENCH_ONE_DEVICE") == "1" else local_rank)
-            except Exception as ex:
-                line["other_parameters"] = {"error": str(ex)}
-            try:
-                line["triage_with_aligner_tags"] = triage_with_aligner_tags(0 if os.environ.get("IM_BENCH_ONE_DEVICE") == "1" else local_rank, rd, refs[0].tobytes())
-            except Exception as ex:
-                line["triage_with_aligner_tags"] = {"error": str(ex)}
-        if world == 1 and not args.no_cpu_baseline and not args.no_config3:
-            try:
-                line["end_to_end_config3"] = end_to_end_config3()
-            except Exception as ex:
-                line["end_to_end_config3"] = {"error": str(ex)}
-        if world == 1 and not args.no_cpu_baseline and not args.no_config5:
-            try:
-                line["end_to_end_config5"] = end_to_end_config5()
-            except Exception as ex:
-                line["end_to_end_config5"] = {"error": str(ex)}
-        # every self-check of the line in one place; the process exits non-zero when one of them is not true
-        checks = {"candidates_counted_on_the_device_equal_the_simulator": True,      # asserted above
-                  "overlapped_passes_equal_the_pass_alone": overlap_ok is True,
-                  "depth_range_sums_equal_the_pileup_rule": depth_ok is True}
-        if parity is not None:
-            checks["realign_identical_to_the_reference_on_the_sample"] = parity.startswith("identical")
-        if isinstance(e2e, dict):
-            checks["end_to_end_ran"] = "error" not in e2e and e2e.get("product_rc") == 0
-            if "vcf_identical_to_reference" in e2e:
-                checks["end_to_end_vcf_identical_to_reference"] = e2e["vcf_identical_to_reference"] is True
-        if isinstance(e2e_mg, dict):
-            checks["multi_gpu_all_ranks_ok"] = e2e_mg.get("all_ranks_ok") is True
-            checks["multi_gpu_vcf_identical_to_single_process"] = e2e_mg.get("vcf_identical_to_single_process") is True
-            for k_, v_ in (e2e_mg.get("strong") or {}).items():
-                if isinstance(v_, dict) and "vcf_identical_to_single_process" in v_:
-                    checks["multi_gpu_strong_%s_vcf_identical" % k_] = v_["vcf_identical_to_single_process"] is True
-        if isinstance(line.get("shard_config3"), dict):
-            checks["shard_config3_ran"] = "error" not in line["shard_config3"]
-        if isinstance(line.get("end_to_end_config3"), dict):
-            c3 = line["end_to_end_config3"]
-            checks["end_to_end_config3_md5_is_the_references"] = c3.get("product_md5_is_the_references") is True
-        if isinstance(line.get("long_reads_2x300"), dict):
-            checks["long_reads_identical_to_the_oracle"] = line["long_reads_2x300"].get("identical_to_the_oracle_on_the_sample") is True
-            if isinstance(line.get("triage_with_aligner_tags"), dict):
-                checks["aligner_tags_leave_the_classes_as_they_are"] = line["triage_with_aligner_tags"].get("same_classes_and_candidates") is True
-            if isinstance(line.get("other_parameters"), dict):
-                checks["other_parameters_identical_to_the_oracle"] = line["other_parameters"].get("identical_to_the_oracle_on_the_samples") is True
-            if isinstance(line["long_reads_2x300"].get("with_gaps"), dict):
-                checks["long_reads_with_gaps_identical_to_the_oracle"] = line["long_reads_2x300"]["with_gaps"].get("identical_to_the_oracle_on_the_sample") is True
-        if isinstance(line.get("end_to_end_config5"), dict):
-            checks["end_to_end_config5_md5s_are_the_references"] = line["end_to_end_config5"].get("product_md5s_are_the_references") is True
-        line["self_checks"] = checks
-        line["self_checks_all_true"] = all(checks.values())
-        sys.stdout.flush()
-        os.write(real_stdout, (json.dumps(line) + "\n").encode())
-        failed = not line["self_checks_all_true"]
-    if dist is not None:
-        dist.destroy_process_group()
-    ctx.close()
-    if rank == 0 and failed:
-        sys.stderr.write("bench.py: a self-check of the line is not true: %s\n" % [k for k, v in line["self_checks"].items() if not v])
-        sys.exit(1)
-
+            line["shard_config3"] = {"error": str(ex)}
+    if world == 1 and not args.no_shard3:
+        try:
+            line["long_reads_2x300"] = long_reads_measure(0 if os.environ.get("IM_BENCH_ONE_DEVICE") == "1" else local_rank)
+        except Exception as ex:
+            line["long_reads_2x300"] = {"error": str(ex)}
+    if world == 1 and not args.no_shard3:
+        try:
+            line["other_parameters"] = other_parameters_measure(0 if os.environ.get("IM_BENCH_ONE_DEVICE") == "1" else local_rank)
+        except Exception as ex:
+            line["other_parameters"] = {"error": str(ex)}
+        try:
+            line["triage_with_aligner_tags"] = triage_with_aligner_tags(0 if os.environ.get("IM_BENCH_ONE_DEVICE") == "1" else local_rank, rd, refs[0].tobytes())
+        except Exception as ex:
+            line["triage_with_aligner_tags"] = {"error": str(ex)}
+    if world == 1 and not args.no_cpu_baseline and not args.no_config3:
+        try:
+            line["end_to_end_config3"] = end_to_end_config3()
+        except Exception as ex:
+            line["end_to_end_config3"] = {"error": str(ex)}
+    if world == 1 and not args.no_cpu_baseline and not args.no_config5:
+        try:
+            line["end_to_end_config5"] = end_to_end_config5()
+        except Exception as ex:
+            line["end_to_end_config5"] = {"error": str(ex)}
+    checks["overlapped_passes_equal_the_pass_alone"] = overlap_ok is True
+    checks["depth_range_sums_equal_the_pileup_rule"] = depth_ok is True
+    if parity is not None:
+        checks["realign_identical_to_the_reference_on_the_sample"] = parity.startswith("identical")
+    if isinstance(e2e, dict):
+        checks["end_to_end_ran"] = "error" not in e2e and e2e.get("product_rc") == 0
+        if "vcf_identical_to_reference" in e2e:
+            checks["end_to_end_vcf_identical_to_reference"] = e2e["vcf_identical_to_reference"] is True
+    if isinstance(e2e_mg, dict):
+        checks["multi_gpu_all_ranks_ok"] = e2e_mg.get("all_ranks_ok") is True
+        checks["multi_gpu_vcf_identical_to_single_process"] = e2e_mg.get("vcf_identical_to_single_process") is True
+        for k_, v_ in (e2e_mg.get("strong") or {}).items():
+            if isinstance(v_, dict) and "vcf_identical_to_single_process" in v_:
+                checks["multi_gpu_strong_%s_vcf_identical" % k_] = v_["vcf_identical_to_single_process"] is True
+    if isinstance(line.get("shard_config3"), dict):
+        checks["shard_config3_ran"] = "error" not in line["shard_config3"]
+    if isinstance(line.get("end_to_end_config3"), dict):
+        c3 = line["end_to_end_config3"]
+        checks["end_to_end_config3_md5_is_the_references"] = c3.get("product_md5_is_the_references") is True
+    if isinstance(line.get("long_reads_2x300"), dict):
+        checks["long_reads_identical_to_the_oracle"] = line["long_reads_2x300"].get("identical_to_the_oracle_on_the_sample") is True
+        if isinstance(line.get("triage_with_aligner_tags"), dict):
+            checks["aligner_tags_leave_the_classes_as_they_are"] = line["triage_with_aligner_tags"].get("same_classes_and_candidates") is True
+        if isinstance(line.get("other_parameters"), dict):
+            checks["other_parameters_identical_to_the_oracle"] = line["other_parameters"].get("identical_to_the_oracle_on_the_samples") is True
+        if isinstance(line["long_reads_2x300"].get("with_gaps"), dict):
+            checks["long_reads_with_gaps_identical_to_the_oracle"] = line["long_reads_2x300"]["with_gaps"].get("identical_to_the_oracle_on_the_sample") is True
+    if isinstance(line.get("end_to_end_config5"), dict):
+        checks["end_to_end_config5_md5s_are_the_references"] = line["end_to_end_config5"].get("product_md5s_are_the_references") is True
 
 if __name__ == "__main__":
     main()

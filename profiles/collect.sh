@@ -10,8 +10,8 @@ set -e
 TAG=$1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/collect; mkdir -p $O
-python3 bench.py > $O/${TAG}_bench.json 2> $O/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-shard3 > $O/${TAG}_bench_under_rocprof.json 2> $O/err.log
+python3 bench.py --full > $O/${TAG}_bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-shard3 > $O/${TAG}_bench_under_rocprof.json 2> $O/err.log
 cp "$(ls $O/stats/*/*kernel_stats.csv | head -1)" $O/${TAG}_kernel_stats.csv; rm -rf $O/stats
 : > $O/${TAG}_pmc_summary.txt
 i=0
