@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define IM_ABI_VERSION 2
+#define IM_ABI_VERSION 3
 
 /* ---- return codes ------------------------------------------------------ */
 #define IM_OK             0
@@ -153,7 +153,11 @@ int im_realign_batch(im_ctx* ctx, const im_params* params,
 /* The split-read part of process_evidence (src/indelminer.c:117-209 with the
  * SR rule of add_node, src/graph.c:122-127): evidence arrives as parallel
  * arrays in ARRIVAL order; it is sorted by (b1,b2), cut at the first
- * b2 >= marker, and grouped by identical (cls,b1,b2).
+ * b2 >= marker, and grouped by identical (cls,b1,b2).  For identical (b1,b2)
+ * every record has the same class by construction (insertions have b1 == b2,
+ * deletions b2 > b1), so the groups are the reference's runs in sorted order.
+ * cls is a split-read class (0 or 1).  One im_dev_flush_cut over [0, n) and
+ * one im_dev_cluster_groupby; the host orders the clusters.
  *   order[n]     evidence indices, cluster after cluster, clusters ascending
  *                in (b1,b2); members ascending in arrival (tie_desc = 0, what
  *                glibc's stable qsort yields) or descending (tie_desc = 1, the
@@ -213,7 +217,7 @@ typedef struct im_dev_batch {
     im_read_result* out;        /* n   */
     /* optional evidence SLOT arrays, n * IM_MAX_EV entries each (NULL = not wanted):
      * slot i*IM_MAX_EV+k carries evidence k of read i, cls = -1 marks an empty slot.
-     * Slot order is arrival order, so the arrays feed im_dev_cluster_slots directly. */
+     * Slot order is arrival order, so the arrays feed im_dev_cluster_groupby directly. */
     int32_t* ev_cls;
     int32_t* ev_b1;
     int32_t* ev_b2;
@@ -242,64 +246,6 @@ int im_expect_read_length(im_ctx* ctx, int32_t max_len);
  * receives the number of packed records.  n_dev: device-resident batch size (NULL: n).  Asynchronous. */
 int im_dev_compact_results(im_ctx* ctx, const im_read_result* res, int32_t n, const int32_t* n_dev,
                            int32_t* status, int32_t* slot, im_read_result* compact, int32_t* count, void* stream);
-
-/* Bytes of device scratch im_dev_cluster_sr needs for n evidence records. */
-size_t im_dev_cluster_scratch_bytes(int32_t n);
-
-/* Device form of im_cluster_sr.  The record count is read from device memory
- * (*n_dev, e.g. the n_out of im_dev_gather_evidence) so that no host round trip
- * sits between the stages; n_cap is the capacity the arrays and the scratch
- * were sized for.  n_clusters is a device int32.  Asynchronous. */
-int im_dev_cluster_sr(im_ctx* ctx, int32_t n_cap, const int32_t* n_dev,
-                      const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                      int32_t marker, int32_t tie_desc,
-                      int32_t* order, int32_t* cl_first, int32_t* cl_count,
-                      uint8_t* used, int32_t* n_clusters,
-                      void* scratch, size_t scratch_bytes, void* stream);
-
-/* Single-launch form for evidence SLOT arrays (see im_dev_batch): compacts the live
- * slots (cls >= 0) in arrival order and clusters them in one workgroup.  Holds up
- * to im_dev_cluster_slots_max() live records (a READCHUNK flush of the reference is
- * a few thousand); with more, counts[0] is set to -1 and the caller takes the
- * im_dev_gather_evidence + im_dev_cluster_sr path instead.  order[] lists slot
- * indices; used[] (n_slots, may be NULL) marks slots that became graph nodes;
- * counts (device int32[2]) = {clusters, live records}.  Asynchronous. */
-int im_dev_cluster_slots(im_ctx* ctx, int32_t n_slots,
-                         const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                         int32_t marker, int32_t tie_desc,
-                         int32_t* order, int32_t* cl_first, int32_t* cl_count,
-                         uint8_t* used, int32_t* counts, void* stream);
-int im_dev_cluster_slots_max(void);
-
-/* Breakpoint-histogram form (the default for evidence SLOT arrays): hash the live slots into
- * a table of distinct (b1,b2,class) breakpoints with their support, sort only the distinct
- * breakpoints, drop every record into its cluster's slice and order the slice by arrival.
- * Four launches, any n_slots.  Same outputs as im_dev_cluster_slots.  Limits: 8192 distinct
- * breakpoints and 1024 records per breakpoint per call; beyond them counts[0] = -1 and the
- * caller takes the im_dev_gather_evidence + im_dev_cluster_sr path (after a distinct-key
- * overflow the scratch must be re-initialised).  scratch: im_dev_cluster_hist_scratch_bytes(n_slots)
- * bytes, prepared ONCE with im_dev_cluster_hist_init; every call leaves it clean.  The scratch is laid out for
- * the n_slots it was prepared with: call with THAT n_slots every time (pad the slot arrays with cls = -1), or prepare it
- * again.  Asynchronous. */
-size_t im_dev_cluster_hist_scratch_bytes(int32_t n_slots);
-int im_dev_cluster_hist_init(im_ctx* ctx, int32_t n_slots, void* scratch, size_t scratch_bytes, void* stream);
-int im_dev_cluster_hist(im_ctx* ctx, int32_t n_slots,
-                        const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                        int32_t marker, int32_t tie_desc,
-                        int32_t* order, int32_t* cl_first, int32_t* cl_count,
-                        uint8_t* used, int32_t* counts,
-                        void* scratch, size_t scratch_bytes, void* stream);
-
-/* Gather the evidence records of a realigned batch into dense SoA arrays
- * (arrival order = read order, then segment order), the input format of
- * im_dev_cluster_sr.  n_out is a device int32 (number of records written);
- * src[] receives read_index*IM_MAX_EV + k for each record.  cap = capacity of
- * the output arrays.  Asynchronous. */
-int im_dev_gather_evidence(im_ctx* ctx, const im_read_result* res, int32_t n,
-                           int32_t* cls, int32_t* b1, int32_t* b2, int32_t* src,
-                           int32_t cap, int32_t* n_out, void* scratch, size_t scratch_bytes,
-                           void* stream);
-size_t im_dev_gather_scratch_bytes(int32_t n);
 
 /* ---- seam 0: record triage -- fetch_func's candidate rules on the device ------- */
 
@@ -517,15 +463,6 @@ int  im_comm_allreduce_sum_i32(im_comm* comm, int32_t* buf_dev, size_t count, vo
 int  im_comm_exchange(im_comm* comm, int32_t n, const int32_t* dir, const int32_t* peer, void* const* dev, const size_t* bytes, void* stream);
 void im_comm_destroy(im_comm* comm);
 const char* im_comm_last_error(void);
-
-/* One 16-byte record per cluster, the unit that is gathered: {tid, b1, b2, cls<<24 | support}.
- * recs[0] = {n_clusters, n_live_evidence, tid, 0}; cluster c at recs[1 + c]; cap = records the
- * buffer holds (clusters beyond cap-1 are dropped and recs[0].w is set to 1).  counts = the
- * device int32[2] written by im_dev_cluster_slots / n_clusters of im_dev_cluster_sr. */
-int im_dev_cluster_records(im_ctx* ctx, int32_t tid, const int32_t* counts,
-                           const int32_t* order, const int32_t* cl_first, const int32_t* cl_count,
-                           const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                           int32_t* recs, int32_t cap, void* stream);
 
 /* ---- device memory / timing plumbing for callers without a HIP binding --- */
 

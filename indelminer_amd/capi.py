@@ -120,30 +120,12 @@ def lib():
         L.im_dev_realign.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(DevBatch), C.c_void_p]
         L.im_expect_read_length.argtypes = [C.c_void_p, C.c_int32]
         L.im_dev_compact_results.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.im_dev_cluster_scratch_bytes.restype = C.c_size_t
-        L.im_dev_cluster_scratch_bytes.argtypes = [C.c_int32]
-        L.im_dev_gather_scratch_bytes.restype = C.c_size_t
-        L.im_dev_gather_scratch_bytes.argtypes = [C.c_int32]
-        L.im_dev_cluster_sr.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_size_t, C.c_void_p]
-        L.im_dev_gather_evidence.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.im_dev_cluster_slots.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.im_dev_cluster_records.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_void_p]
         L.im_comm_unique_id.argtypes = [C.c_void_p]
         L.im_comm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.im_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_comm_destroy.argtypes = [C.c_void_p]
         L.im_comm_destroy.restype = None
         L.im_comm_last_error.restype = C.c_char_p
-        L.im_dev_cluster_hist_scratch_bytes.restype = C.c_size_t
-        L.im_dev_cluster_hist_scratch_bytes.argtypes = [C.c_int32]
-        L.im_dev_cluster_hist_init.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.im_dev_cluster_hist.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_depth_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.im_depth_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_support_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 #include <unordered_map>
 #include <mutex>
@@ -800,81 +801,6 @@ int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64
     return IM_OK;
 }
 
-size_t im_dev_cluster_scratch_bytes(int32_t n) { return im::cluster_scratch_bytes(n); }
-size_t im_dev_gather_scratch_bytes(int32_t n) { return im::gather_scratch_bytes(n); }
-
-int im_dev_cluster_sr(im_ctx* ctx, int32_t n_cap, const int32_t* n_dev,
-                      const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                      int32_t marker, int32_t tie_desc,
-                      int32_t* order, int32_t* cl_first, int32_t* cl_count, uint8_t* used, int32_t* n_clusters,
-                      void* scratch, size_t scratch_bytes, void* stream)
-{
-    if (!ctx) return IM_E_ARG;
-    if (n_cap < 0 || !n_dev) { set_err(ctx, "bad evidence count arguments"); return IM_E_ARG; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_cluster_sr(n_cap, n_dev, cls, b1, b2, marker, tie_desc, order, cl_first, cl_count, used, n_clusters,
-                                       scratch, scratch_bytes, (hipStream_t)stream));
-    return IM_OK;
-}
-
-int im_dev_cluster_slots_max(void) { return im::cluster_small_max(); }
-
-int im_dev_cluster_records(im_ctx* ctx, int32_t tid, const int32_t* counts,
-                           const int32_t* order, const int32_t* cl_first, const int32_t* cl_count,
-                           const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                           int32_t* recs, int32_t cap, void* stream)
-{
-    if (!ctx || cap < 1) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_cluster_records(tid, counts, order, cl_first, cl_count, cls, b1, b2, recs, cap, (hipStream_t)stream));
-    return IM_OK;
-}
-
-int im_dev_cluster_slots(im_ctx* ctx, int32_t n_slots, const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                         int32_t marker, int32_t tie_desc,
-                         int32_t* order, int32_t* cl_first, int32_t* cl_count, uint8_t* used, int32_t* counts, void* stream)
-{
-    if (!ctx) return IM_E_ARG;
-    if (n_slots < 0 || !counts) { set_err(ctx, "bad slot arguments"); return IM_E_ARG; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_cluster_small(n_slots, nullptr, cls, b1, b2, marker, tie_desc, order, cl_first, cl_count,
-                                          used, counts, (hipStream_t)stream));
-    return IM_OK;
-}
-
-size_t im_dev_cluster_hist_scratch_bytes(int32_t n_slots) { return im::cluster_hist_scratch_bytes(n_slots); }
-
-int im_dev_cluster_hist_init(im_ctx* ctx, int32_t n_slots, void* scratch, size_t scratch_bytes, void* stream)
-{
-    if (!ctx) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_cluster_hist_init(n_slots, scratch, scratch_bytes, (hipStream_t)stream));
-    return IM_OK;
-}
-
-int im_dev_cluster_hist(im_ctx* ctx, int32_t n_slots, const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                        int32_t marker, int32_t tie_desc,
-                        int32_t* order, int32_t* cl_first, int32_t* cl_count, uint8_t* used, int32_t* counts,
-                        void* scratch, size_t scratch_bytes, void* stream)
-{
-    if (!ctx) return IM_E_ARG;
-    if (n_slots < 0 || !counts) { set_err(ctx, "bad slot arguments"); return IM_E_ARG; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_cluster_hist(n_slots, cls, b1, b2, marker, tie_desc, order, cl_first, cl_count, used, counts,
-                                         scratch, scratch_bytes, (hipStream_t)stream));
-    return IM_OK;
-}
-
-int im_dev_gather_evidence(im_ctx* ctx, const im_read_result* res, int32_t n,
-                           int32_t* cls, int32_t* b1, int32_t* b2, int32_t* src,
-                           int32_t cap, int32_t* n_out, void* scratch, size_t scratch_bytes, void* stream)
-{
-    if (!ctx) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_gather_evidence(res, n, cls, b1, b2, src, cap, n_out, scratch, scratch_bytes, (hipStream_t)stream));
-    return IM_OK;
-}
-
 int im_cluster_sr(im_ctx* ctx, int32_t n, const int32_t* cls, const int32_t* b1, const int32_t* b2,
                   int32_t marker, int32_t tie_desc,
                   int32_t* order, int32_t* cl_first, int32_t* cl_count, uint8_t* used, int32_t* n_clusters)
@@ -884,51 +810,58 @@ int im_cluster_sr(im_ctx* ctx, int32_t n, const int32_t* cls, const int32_t* b1,
     *n_clusters = 0;
     if (n == 0) return IM_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // one flush (id 1) over slots [0, n), then the group-by of what it consumed.  Workspace and pinned staging share one
+    // layout for the arrays that travel: cls, b1, b2 up in one copy; order, first, count, consumed and counts down in one.
     const size_t a32 = up256(sizeof(int32_t) * (size_t)n);
-    const size_t scratch = im::cluster_scratch_bytes(n);
-    const size_t hist_bytes = im::cluster_hist_scratch_bytes(n);
-    int rc = ensure_ws(ctx, 6 * a32 + up256((size_t)n) + 256 + up256(scratch) + hist_bytes);
+    const size_t up_bytes = 3 * a32, down_bytes = 4 * a32 + 256;
+    const size_t gb_bytes = im::groupby_scratch_bytes(n);
+    int rc = ensure_ws(ctx, up_bytes + down_bytes + up256(16 * (size_t)n) + 256 + gb_bytes);
+    if (!rc) rc = ensure_pin(ctx, up_bytes + down_bytes);
     if (rc) return rc;
     char* w = static_cast<char*>(ctx->ws);
-    int32_t* d_cls = (int32_t*)w; w += a32;
-    int32_t* d_b1 = (int32_t*)w; w += a32;
-    int32_t* d_b2 = (int32_t*)w; w += a32;
-    int32_t* d_order = (int32_t*)w; w += a32;
-    int32_t* d_first = (int32_t*)w; w += a32;
-    int32_t* d_count = (int32_t*)w; w += a32;
-    uint8_t* d_used = (uint8_t*)w; w += up256((size_t)n);
-    int32_t* d_ncl = (int32_t*)w; w += 128;
-    int32_t* d_n = (int32_t*)w; w += 128;
-    void* d_scratch = w; w += up256(scratch);
-    void* d_hist = w;
-    HIP_TRY(ctx, hipMemcpyAsync(d_cls, cls, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_b1, b1, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_b2, b2, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_n, &n, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    {
-        // breakpoint-histogram path: every record is a live slot
-        HIP_TRY(ctx, im::launch_cluster_hist_init(n, d_hist, hist_bytes, ctx->stream));
-        HIP_TRY(ctx, im::launch_cluster_hist(n, d_cls, d_b1, d_b2, marker, tie_desc, d_order, d_first, d_count, d_used, d_ncl,
-                                             d_hist, hist_bytes, ctx->stream));
-        int32_t got = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&got, d_ncl, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (got < 0) {      // more distinct breakpoints / deeper clusters than the histogram holds: radix path
-            rc = im_dev_cluster_sr(ctx, n, d_n, d_cls, d_b1, d_b2, marker, tie_desc, d_order, d_first, d_count, d_used, d_ncl,
-                                   d_scratch, scratch, ctx->stream);
-            if (rc) return rc;
-        }
+    char* h = static_cast<char*>(ctx->pin);
+    auto arr = [&](char* base, int k) { return (int32_t*)(base + (size_t)k * a32); };
+    int32_t *d_cls = arr(w, 0), *d_b1 = arr(w, 1), *d_b2 = arr(w, 2);
+    char* d_down = w + up_bytes;
+    int32_t *d_order = arr(d_down, 0), *d_first = arr(d_down, 1), *d_count = arr(d_down, 2), *d_consumed = arr(d_down, 3);
+    int32_t* d_counts = arr(d_down, 4);
+    int32_t* d_key = (int32_t*)(d_down + down_bytes);
+    uint64_t* d_cut = (uint64_t*)(d_down + down_bytes + up256(16 * (size_t)n));
+    void* d_gb = (char*)d_cut + 256;
+    memcpy(arr(h, 0), cls, sizeof(int32_t) * (size_t)n);
+    memcpy(arr(h, 1), b1, sizeof(int32_t) * (size_t)n);
+    memcpy(arr(h, 2), b2, sizeof(int32_t) * (size_t)n);
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(w, h, up_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(d_consumed, 0, sizeof(int32_t) * (size_t)n, st));
+    HIP_TRY(ctx, hipMemsetAsync(d_cut, 0xFF, sizeof(uint64_t), st));
+    HIP_TRY(ctx, im::launch_flush_cut(d_cls, d_b1, d_b2, d_consumed, 0, n, 0, 0, marker, 1, d_cut, nullptr, nullptr, 0, st));
+    HIP_TRY(ctx, im::launch_groupby_init(n, d_gb, st));
+    HIP_TRY(ctx, im::launch_groupby(n, n, nullptr, d_cls, d_b1, d_b2, d_consumed, tie_desc, d_order, d_key, d_first, d_count,
+                                    d_counts, d_gb, st));
+    HIP_TRY(ctx, hipMemcpyAsync(h + up_bytes, d_down, down_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    char* h_down = h + up_bytes;
+    const int32_t *h_order = arr(h_down, 0), *h_first = arr(h_down, 1), *h_count = arr(h_down, 2), *h_consumed = arr(h_down, 3);
+    const int32_t ncl = arr(h_down, 4)[0];
+    // The clusters come back in table order.  Their keys are the host's own (b1, b2, cls) of a member: clusters ascending in
+    // (b1, b2) (class is a function of (b1, b2), so the tie-break never decides), order[] rebuilt to match.
+    struct Cl { uint64_t b12; int32_t cls, c; };
+    std::vector<Cl> by(ncl);
+    for (int32_t c = 0; c < ncl; c++) {
+        const int32_t r = h_order[h_first[c]];
+        by[c] = Cl{(uint64_t)((uint32_t)b1[r] ^ 0x80000000u) << 32 | ((uint32_t)b2[r] ^ 0x80000000u), cls[r], c};
     }
-    HIP_TRY(ctx, hipMemcpyAsync(n_clusters, d_ncl, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const int32_t ncl = *n_clusters;
-    HIP_TRY(ctx, hipMemcpyAsync(order, d_order, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(used, d_used, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (ncl > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(cl_first, d_first, sizeof(int32_t) * (size_t)ncl, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(cl_count, d_count, sizeof(int32_t) * (size_t)ncl, hipMemcpyDeviceToHost, ctx->stream));
+    std::sort(by.begin(), by.end(), [](const Cl& x, const Cl& y) { return x.b12 != y.b12 ? x.b12 < y.b12 : x.cls < y.cls; });
+    int32_t pos = 0;
+    for (int32_t k = 0; k < ncl; k++) {
+        const int32_t c = by[k].c;
+        cl_first[k] = pos; cl_count[k] = h_count[c];
+        memcpy(order + pos, h_order + h_first[c], sizeof(int32_t) * (size_t)h_count[c]);
+        pos += h_count[c];
     }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int32_t i = 0; i < n; i++) used[i] = h_consumed[i] != 0;
+    *n_clusters = ncl;
     return IM_OK;
 }
 

@@ -79,7 +79,7 @@ hipError_t launch_depth_scan_tiled(int32_t* depth, int64_t n, int32_t* sums, hip
 hipError_t launch_depth_query_tiled(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* depth, const int32_t* sums,
                                     int64_t clen, uint32_t* out, uint32_t* out_max, hipStream_t stream);
 
-// launchers (im_realign.hip / im_cluster.hip)
+// im_realign.hip
 hipError_t launch_pack_reference(const uint8_t* ascii, uint64_t* pk, int64_t n_bases_padded,
                                  hipStream_t stream);
 hipError_t launch_realign(const RealignArgs& a, int n_cu, hipStream_t stream);
@@ -98,37 +98,6 @@ hipError_t launch_realign_any(const RealignArgs& a, const int32_t* list, int32_t
 // im_results.hip
 hipError_t launch_compact_results(const im_read_result* res, int32_t n_cap, const int32_t* n_dev, int32_t* status, int32_t* slot,
                                   im_read_result* compact, int32_t* count, int n_cu, hipStream_t stream);
-
-size_t cluster_scratch_bytes(int32_t n);
-hipError_t launch_cluster_sr(int32_t n_cap, const int32_t* n_dev,
-                             const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                             int32_t marker, int32_t tie_desc,
-                             int32_t* order, int32_t* cl_first, int32_t* cl_count,
-                             uint8_t* used, int32_t* n_clusters,
-                             void* scratch, size_t scratch_bytes, hipStream_t stream);
-
-hipError_t launch_cluster_records(int32_t tid, const int32_t* counts, const int32_t* order, const int32_t* cl_first,
-                                  const int32_t* cl_count, const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                                  int32_t* recs, int32_t cap, hipStream_t stream);
-int cluster_small_max();
-size_t cluster_hist_scratch_bytes(int32_t n_slots);
-hipError_t launch_cluster_hist_init(int32_t n_slots, void* scratch, size_t scratch_bytes, hipStream_t stream);
-hipError_t launch_cluster_hist(int32_t n_slots, const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                               int32_t marker, int32_t tie_desc,
-                               int32_t* order, int32_t* cl_first, int32_t* cl_count,
-                               uint8_t* used, int32_t* out_counts,
-                               void* scratch, size_t scratch_bytes, hipStream_t stream);
-hipError_t launch_cluster_small(int32_t n_slots, const int32_t* n_slots_dev,
-                                const int32_t* cls, const int32_t* b1, const int32_t* b2,
-                                int32_t marker, int32_t tie_desc,
-                                int32_t* order, int32_t* cl_first, int32_t* cl_count,
-                                uint8_t* used, int32_t* out_counts, hipStream_t stream);
-
-size_t gather_scratch_bytes(int32_t n);
-hipError_t launch_gather_evidence(const im_read_result* res, int32_t n,
-                                  int32_t* cls, int32_t* b1, int32_t* b2, int32_t* src,
-                                  int32_t cap, int32_t* n_out, void* scratch, size_t scratch_bytes,
-                                  hipStream_t stream);
 
 hipError_t launch_depth_build(int64_t clen, int32_t n_seg, const int32_t* seg_start, const int32_t* seg_len,
                               int32_t* depth, int32_t* sums, hipStream_t stream);

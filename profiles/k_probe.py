@@ -12,7 +12,7 @@ import numpy as np  # noqa: E402
 from indelminer_amd import capi, synth  # noqa: E402
 import bench  # noqa: E402,F401
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import legacy_shard  # noqa: E402
+import cand_batch  # noqa: E402
 
 KS = [int(a) for a in sys.argv[1:]] or [4, 5, 6, 7, 8, 10, 12, 15]
 refs, rd = synth.simulate(seed=1, ref_len=1_000_000, coverage=30)
@@ -23,7 +23,7 @@ n_all = len(cand["index"])
 n = 4 * n_all
 L = capi.lib()
 sub = {k: (np.concatenate([v] * 4)[:n] if isinstance(v, np.ndarray) and v.shape[:1] == (n_all,) else v) for k, v in cand.items()}
-sh = legacy_shard.Shard(ctx, refs[0], sub, 100)
+sh = cand_batch.CandBatch(ctx, sub, 100)
 for k in KS:
     P = capi.params(klength=k)
     t = capi.Timer(ctx)

@@ -1,11 +1,12 @@
-"""Host-side twin of im_dev_cluster_records and of the merge of all-gathered record buffers (test helper for
-tests/test_gpu_cluster.py::test_cluster_records_and_rccl_allgather_world1; the product's multi-rank path is
+"""The 16-byte cluster records that ranks all-gather, packed on the host, and the merge of the gathered buffers (test helper
+for tests/test_gpu_cluster.py::test_cluster_records_and_rccl_allgather_world1; the product's multi-rank path is
 indelminer_amd/host/host_multirank.c, covered by tests/test_multi_rank_driver.py)."""
 import numpy as np
 
 
 def pack_records(tid, keys_b1, keys_b2, cls, support, n_live, cap):
-    """Host-side twin of im_dev_cluster_records: int32 [cap,4] buffer."""
+    """int32 [cap,4] buffer: recs[0] = {n_clusters, n_live, tid, truncated}, cluster c at recs[1 + c] = {tid, b1, b2,
+    cls << 24 | support}; clusters beyond cap - 1 are dropped and recs[0][3] is set to 1."""
     recs = np.zeros((cap, 4), dtype=np.int32)
     n = len(keys_b1)
     lim = min(n, cap - 1)

@@ -24,7 +24,7 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(L, s), "missing export: " + s
     version = int(re.search(r"#define IM_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "indelminer_amd.h")).read()).group(1))
-    assert L.im_abi_version() == version == 2
+    assert L.im_abi_version() == version == 3
 
 
 def test_result_record_layout():

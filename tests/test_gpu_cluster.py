@@ -62,12 +62,47 @@ def test_cluster_sortedness_and_grouping_large(gpu_ctx):
     assert np.array_equal(heads[1:], ~same)
 
 
-@pytest.mark.parametrize("path", ["slots", "hist"])
-def test_cluster_slots_matches_oracle(gpu_ctx, path):
-    """Slot form (empty slots = cls -1) through im_dev_cluster_slots (one workgroup) and
-    im_dev_cluster_hist (breakpoint histogram): same clusters as the oracle on the compacted
-    records, order[] in slot indices; the histogram scratch must come back clean (3 rounds)."""
-    import ctypes as C
+def _cut_and_group(ctx, n_slots, d, marker, tie):
+    """One flush (id 1) over slots [0, n_slots) through im_dev_flush_cut, then im_dev_cluster_groupby (asynchronous)."""
+    from indelminer_amd import capi
+    L = capi.lib()
+    st = ctx.stream
+    ctx._check(L.im_dev_memset(ctx.h, d["consumed"].ptr, 0, 4 * n_slots, st))
+    ctx._check(L.im_dev_memset(ctx.h, d["cut"].ptr, 0xFF, 8, st))
+    ctx._check(L.im_dev_flush_cut(ctx.h, d["cls"].ptr, d["b1"].ptr, d["b2"].ptr, d["consumed"].ptr, 0, n_slots, 0, 0, marker, 1,
+                                  d["cut"].ptr, st))
+    ctx._check(L.im_dev_cluster_groupby(ctx.h, n_slots, d["cls"].ptr, d["b1"].ptr, d["b2"].ptr, d["consumed"].ptr, tie,
+                                        d["order"].ptr, d["key"].ptr, d["first"].ptr, d["count"].ptr, d["counts"].ptr,
+                                        d["gs"].ptr, d["gs_bytes"], st))
+
+
+def _slot_buffers(ctx, cls, b1, b2):
+    from indelminer_amd import capi
+    L = capi.lib()
+    n = len(cls)
+    d = {k: capi.DevBuf(ctx, 4 * n).upload(np.ascontiguousarray(v, np.int32)) for k, v in (("cls", cls), ("b1", b1), ("b2", b2))}
+    for k in ("consumed", "order", "first", "count"):
+        d[k] = capi.DevBuf(ctx, 4 * n)
+    d["key"] = capi.DevBuf(ctx, 16 * n); d["counts"] = capi.DevBuf(ctx, 64); d["cut"] = capi.DevBuf(ctx, 64)
+    d["gs_bytes"] = L.im_dev_groupby_scratch_bytes(n)
+    d["gs"] = capi.DevBuf(ctx, d["gs_bytes"])
+    ctx._check(L.im_dev_groupby_scratch_init(ctx.h, n, d["gs"].ptr, d["gs_bytes"], ctx.stream))
+    return d
+
+
+def _clusters_by_key(d):
+    """counts, and the group-by's clusters ordered by (b1, b2, cls): keys [k, 4], firsts, counts"""
+    counts = d["counts"].download(np.int32, 2)
+    k = int(counts[0])
+    key = d["key"].download(np.int32, 4 * k).reshape(k, 4)
+    perm = np.lexsort((key[:, 1], key[:, 3], key[:, 2]))
+    return counts, key[perm], d["first"].download(np.int32, k)[perm], d["count"].download(np.int32, k)[perm]
+
+
+def test_cluster_slots_matches_oracle(gpu_ctx):
+    """Slot form (empty slots = cls -1) through im_dev_flush_cut + im_dev_cluster_groupby: same clusters as the oracle
+    on the compacted records once ordered by key, order[] in slot indices, used[] from consumed[]; the group-by scratch
+    must come back clean (3 calls, then a replay from a captured launch graph)."""
     from indelminer_amd import capi
     L = capi.lib()
     for seed, n_slots, live_frac, marker, tie in [(1, 4000, 0.5, 2**31 - 1, 0), (2, 30000, 0.25, 2**31 - 1, 1),
@@ -79,69 +114,45 @@ def test_cluster_slots_matches_oracle(gpu_ctx, path):
         cls_s = np.where(live, cls, -1).astype(np.int32)
         idx = np.nonzero(live)[0]
         o_order, o_first, o_count, o_used, o_k = _cluster_oracle(cls[idx], b1[idx], b2[idx], marker, tie)
-        bufs = {}
-        for name, arr in (("cls", cls_s), ("b1", b1), ("b2", b2)):
-            bufs[name] = capi.DevBuf(gpu_ctx, 4 * n_slots).upload(arr)
-        d_order = capi.DevBuf(gpu_ctx, 4 * n_slots); d_first = capi.DevBuf(gpu_ctx, 4 * n_slots)
-        d_count = capi.DevBuf(gpu_ctx, 4 * n_slots); d_used = capi.DevBuf(gpu_ctx, n_slots); d_counts = capi.DevBuf(gpu_ctx, 64)
-        if path == "slots":
-            gpu_ctx._check(L.im_dev_cluster_slots(gpu_ctx.h, n_slots, bufs["cls"].ptr, bufs["b1"].ptr, bufs["b2"].ptr, marker, tie,
-                                                  d_order.ptr, d_first.ptr, d_count.ptr, d_used.ptr, d_counts.ptr, gpu_ctx.stream))
-            gpu_ctx._check(L.im_stream_sync(gpu_ctx.h, gpu_ctx.stream))
-            counts = d_counts.download(np.int32, 2)
-            if len(idx) > L.im_dev_cluster_slots_max():
-                assert counts[0] == -1 and counts[1] == len(idx)
-                continue
-        else:
-            hb = L.im_dev_cluster_hist_scratch_bytes(n_slots)
-            d_hs = capi.DevBuf(gpu_ctx, hb)
-            gpu_ctx._check(L.im_dev_cluster_hist_init(gpu_ctx.h, n_slots, d_hs.ptr, hb, gpu_ctx.stream))
-            for _round in range(3):     # the table cleans itself: identical answers call after call
-                gpu_ctx._check(L.im_dev_cluster_hist(gpu_ctx.h, n_slots, bufs["cls"].ptr, bufs["b1"].ptr, bufs["b2"].ptr, marker, tie,
-                                                     d_order.ptr, d_first.ptr, d_count.ptr, d_used.ptr, d_counts.ptr,
-                                                     d_hs.ptr, hb, gpu_ctx.stream))
-            # ... and once more replayed from a captured launch graph (im_capture_* / im_graph_launch)
-            with capi.Graph.capture(gpu_ctx) as g:
-                gpu_ctx._check(L.im_dev_cluster_hist(gpu_ctx.h, n_slots, bufs["cls"].ptr, bufs["b1"].ptr, bufs["b2"].ptr, marker, tie,
-                                                     d_order.ptr, d_first.ptr, d_count.ptr, d_used.ptr, d_counts.ptr,
-                                                     d_hs.ptr, hb, gpu_ctx.stream))
-            g.launch()
-            gpu_ctx._check(L.im_stream_sync(gpu_ctx.h, gpu_ctx.stream))
-            g.close()
-            counts = d_counts.download(np.int32, 2)
-            n_keys = len(np.unique(np.stack([cls[idx], b1[idx], b2[idx]]), axis=1).T)
-            if n_keys > 8192:           # more distinct breakpoints than the table lists: refused, caller takes the radix path
-                assert counts[0] == -1
-                continue
-        assert counts[1] == len(idx) and counts[0] == o_k
+        d = _slot_buffers(gpu_ctx, cls_s, b1, b2)
+        for _round in range(3):     # the table cleans itself: identical answers call after call
+            _cut_and_group(gpu_ctx, n_slots, d, marker, tie)
+        # ... and once more replayed from a captured launch graph (im_capture_* / im_graph_launch)
+        with capi.Graph.capture(gpu_ctx) as g:
+            _cut_and_group(gpu_ctx, n_slots, d, marker, tie)
+        g.launch()
+        gpu_ctx._check(L.im_stream_sync(gpu_ctx.h, gpu_ctx.stream))
+        g.close()
+        counts, key, first, count = _clusters_by_key(d)
         m = int(o_used.sum())
-        assert np.array_equal(d_order.download(np.int32, n_slots)[:m], idx[o_order[:m]])
-        assert np.array_equal(d_first.download(np.int32, n_slots)[:o_k], o_first)
-        assert np.array_equal(d_count.download(np.int32, n_slots)[:o_k], o_count)
-        used = d_used.download(np.uint8, n_slots)
-        want = np.zeros(n_slots, np.uint8); want[idx[o_used.astype(bool)]] = 1
+        assert counts[0] == o_k and counts[1] == m
+        order = d["order"].download(np.int32, n_slots)
+        got = np.concatenate([order[f:f + c] for f, c in zip(first, count)]) if o_k else np.zeros(0, np.int32)
+        assert np.array_equal(got, idx[o_order[:m]])
+        assert np.array_equal(np.cumsum(count) - count, o_first)
+        assert np.array_equal(count, o_count)
+        used = d["consumed"].download(np.int32, n_slots) != 0
+        want = np.zeros(n_slots, bool); want[idx[o_used.astype(bool)]] = True
         assert np.array_equal(used, want)
 
 
 def test_cluster_records_and_rccl_allgather_world1(gpu_ctx):
-    """The gathered unit (16 B cluster records) and the RCCL all-gather entry point with one rank."""
-    import ctypes as C
+    """The gathered unit (16 B cluster records, packed on the host from the group-by's clusters) and the RCCL
+    all-gather entry point with one rank."""
     from indelminer_amd import capi
     from tests.support import gathered as shard
     L = capi.lib()
     n = 3000
     cls, b1, b2 = _random_evidence(77, n, 40000)
     o_order, o_first, o_count, o_used, o_k = _cluster_oracle(cls, b1, b2, 2**31 - 1, 0)
-    d = {k: capi.DevBuf(gpu_ctx, 4 * n).upload(v) for k, v in (("cls", cls), ("b1", b1), ("b2", b2))}
-    d_order = capi.DevBuf(gpu_ctx, 4 * n); d_first = capi.DevBuf(gpu_ctx, 4 * n); d_count = capi.DevBuf(gpu_ctx, 4 * n)
-    d_counts = capi.DevBuf(gpu_ctx, 64)
+    d = _slot_buffers(gpu_ctx, cls, b1, b2)
+    _cut_and_group(gpu_ctx, n, d, 2**31 - 1, 0)
+    gpu_ctx._check(L.im_stream_sync(gpu_ctx.h, gpu_ctx.stream))
+    counts, key, _, count = _clusters_by_key(d)
     cap = 4096
-    d_recs = capi.DevBuf(gpu_ctx, 16 * cap); d_all = capi.DevBuf(gpu_ctx, 16 * cap)
+    recs = shard.pack_records(3, key[:, 2], key[:, 3], key[:, 1], count, int(counts[1]), cap)
+    d_recs = capi.DevBuf(gpu_ctx, 16 * cap).upload(recs); d_all = capi.DevBuf(gpu_ctx, 16 * cap)
     st = gpu_ctx.stream
-    gpu_ctx._check(L.im_dev_cluster_slots(gpu_ctx.h, n, d["cls"].ptr, d["b1"].ptr, d["b2"].ptr, 2**31 - 1, 0,
-                                          d_order.ptr, d_first.ptr, d_count.ptr, None, d_counts.ptr, st))
-    gpu_ctx._check(L.im_dev_cluster_records(gpu_ctx.h, 3, d_counts.ptr, d_order.ptr, d_first.ptr, d_count.ptr,
-                                            d["cls"].ptr, d["b1"].ptr, d["b2"].ptr, d_recs.ptr, cap, st))
     comm = capi.Comm(gpu_ctx, capi.comm_unique_id(), 0, 1)
     comm.allgather(d_recs.ptr, d_all.ptr, 16 * cap, st)
     gpu_ctx._check(L.im_stream_sync(gpu_ctx.h, st))
