@@ -440,6 +440,33 @@ int im_depth_query_max_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* b
  * reference has no counterpart (calculate_cov_params re-reads the file per variant, src/shared.c:178-212).  Synchronous. */
 int im_depth_allreduce(im_ctx* ctx, im_comm* comm);
 
+/* ---- seam 5: reference-spanning read counts, for genotype calls (-G) --------------- */
+
+/* Replaces nothing in the reference: it prints NS= (reads that support the indel) and has no count of the reads that support the
+ * REFERENCE allele at the same breakpoint (DP= is a mean pileup depth over a window and holds the NS= reads too).  The statistic:
+ * a record is eligible iff its flag has none of 0x4 / 0x100 / 0x200 / 0x400 (the pileup's mask), its tid names a contig and its
+ * mapping quality is >= min_mapq.  A RUN is a maximal sequence of consecutive M / = / X operations of its CIGAR, covering contig
+ * positions [s, e) clipped to [0, length); D and N advance the position and end a run, every other operation ends a run without
+ * advancing.  span[p], 0 <= p <= length, is the number of runs of eligible records with s <= p - flank and p + flank <= e: the
+ * run holds `flank` matched bases on each side of the boundary in front of base p.
+ *
+ * Genome-wide form, beside seam 3's: im_span_enable allocates one int32 per reference position for all contigs (4 bytes per base
+ * of HBM, on this call only; flank >= 1) and fixes flank and min_mapq; im_dev_span_scatter adds a chunk of delivered records (the
+ * chunk im_dev_triage takes; a launch of its own, asynchronous) to the difference array; im_span_scan turns contig tid into
+ * counts once all its records have been through the scatter (the depth array's tiled scan); im_span_reset puts contig tid's run
+ * back to zeros; im_span_query_tid returns per query the MINIMUM of span[p] over [beg, end] INCLUSIVE, clipped to
+ * [0, length] (0 for an interval that is empty after the clip). */
+int im_span_enable(im_ctx* ctx, int32_t flank, int32_t min_mapq);
+int im_dev_span_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream);
+int im_span_scan(im_ctx* ctx, int32_t tid, void* stream);
+int im_span_reset(im_ctx* ctx, int32_t tid, void* stream);
+int im_span_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out);
+/* Host-buffer form, beside im_depth_build / im_depth_query: once per contig the runs (contig start, length) of its eligible
+ * records -- the caller applies the record rule and forms the runs -- leave span[] of that contig resident on the device;
+ * im_span_query answers like im_span_query_tid.  Synchronous. */
+int im_span_build(im_ctx* ctx, int64_t contig_len, int32_t n_run, const int32_t* run_start, const int32_t* run_len, int32_t flank);
+int im_span_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

@@ -187,6 +187,13 @@ def lib():
         L.im_depth_scan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.im_depth_reset.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.im_depth_query_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_span_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.im_dev_span_scatter.argtypes = [C.c_void_p, C.POINTER(DevRecords), C.c_void_p]
+        L.im_span_scan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.im_span_reset.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.im_span_query_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_span_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+        L.im_span_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_capture_begin.argtypes = [C.c_void_p, C.c_void_p]
@@ -424,6 +431,40 @@ class Context:
         end = np.ascontiguousarray(end, dtype=np.int32)
         out = np.zeros(max(len(beg), 1), dtype=np.uint32)
         self._check(lib().im_depth_query_tid(self.h, tid, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
+        return out[:len(beg)]
+
+    def span_enable(self, flank, min_mapq):
+        """the genome-wide array of reference-spanning read counts (the genotype columns), 4 bytes per reference base"""
+        self._check(lib().im_span_enable(self.h, int(flank), int(min_mapq)))
+
+    def span_scatter(self, recs, stream=None):
+        """recs: a DevRecords chunk, as im_dev_triage takes it (asynchronous)"""
+        self._check(lib().im_dev_span_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
+
+    def span_scan(self, tid, stream=None):
+        self._check(lib().im_span_scan(self.h, tid, self.stream if stream is None else stream))
+
+    def span_reset(self, tid, stream=None):
+        self._check(lib().im_span_reset(self.h, tid, self.stream if stream is None else stream))
+
+    def span_query_tid(self, tid, beg, end):
+        """per query the minimum of span[p] over [beg, end] inclusive"""
+        beg = np.ascontiguousarray(beg, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        out = np.zeros(max(len(beg), 1), dtype=np.uint32)
+        self._check(lib().im_span_query_tid(self.h, tid, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
+        return out[:len(beg)]
+
+    def span_build(self, contig_len, run_start, run_len, flank):
+        run_start = np.ascontiguousarray(run_start, dtype=np.int32)
+        run_len = np.ascontiguousarray(run_len, dtype=np.int32)
+        self._check(lib().im_span_build(self.h, contig_len, len(run_start), _ptr(run_start), _ptr(run_len), int(flank)))
+
+    def span_query(self, beg, end):
+        beg = np.ascontiguousarray(beg, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        out = np.zeros(max(len(beg), 1), dtype=np.uint32)
+        self._check(lib().im_span_query(self.h, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
         return out[:len(beg)]
 
     def cluster_sr(self, cls, b1, b2, marker=2**31 - 1, tie_desc=0):

@@ -46,6 +46,14 @@ struct im_ctx {
     // genome-wide depth / difference array (im_depth_enable): one int32 per byte of ref_ascii
     int32_t* gdepth = nullptr;
     int32_t* gdepth_sums = nullptr;
+    // genome-wide reference-spanning counts (im_span_enable): the depth array's layout, allocated on that call only
+    int32_t* gspan = nullptr;
+    int32_t* gspan_sums = nullptr;
+    int32_t span_flank = 0, span_min_mapq = 0;
+    // resident span array of the current contig (im_span_build)
+    int32_t* span = nullptr;
+    int32_t* span_sums = nullptr;
+    int64_t span_cap = 0, span_len = -1;
     std::mutex gb_mu;
     std::unordered_map<void*, int32_t> gb_layout;   // group-by scratch -> the slot count it was initialised (and is carved) for
     std::unordered_map<void*, std::pair<int32_t, int32_t>> fg_layout;   // flush + group-by scratch -> (slots, flushes) it is carved for
@@ -126,6 +134,9 @@ void free_reference(im_ctx* ctx)
     if (ctx->gdepth) (void)hipFree(ctx->gdepth);
     if (ctx->gdepth_sums) (void)hipFree(ctx->gdepth_sums);
     ctx->gdepth = nullptr; ctx->gdepth_sums = nullptr;
+    if (ctx->gspan) (void)hipFree(ctx->gspan);
+    if (ctx->gspan_sums) (void)hipFree(ctx->gspan_sums);
+    ctx->gspan = nullptr; ctx->gspan_sums = nullptr;
     ctx->h_asc_off.clear(); ctx->h_len.clear(); ctx->ref_total = 0;
 }
 
@@ -173,6 +184,8 @@ void im_ctx_destroy(im_ctx* ctx)
     if (ctx->ws) (void)hipFree(ctx->ws);
     if (ctx->depth) (void)hipFree(ctx->depth);
     if (ctx->depth_sums) (void)hipFree(ctx->depth_sums);
+    if (ctx->span) (void)hipFree(ctx->span);
+    if (ctx->span_sums) (void)hipFree(ctx->span_sums);
     if (ctx->rg_blob) (void)hipFree(ctx->rg_blob);
     if (ctx->any_list) (void)hipFree(ctx->any_list);
     if (ctx->any_counters) (void)hipFree(ctx->any_counters);
@@ -762,6 +775,124 @@ int im_depth_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* en
     HIP_TRY(ctx, hipMemcpyAsync(sum_out, d_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return IM_OK;
+}
+
+// ---- reference-spanning read counts (the genotype columns) ------------------------------------
+
+int im_span_enable(im_ctx* ctx, int32_t flank, int32_t min_mapq)
+{
+    if (!ctx) return IM_E_ARG;
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    if (flank < 1) { set_err(ctx, "im_span_enable: flank %d, must be >= 1", flank); return IM_E_ARG; }
+    if (ctx->gspan) {
+        if (flank != ctx->span_flank || min_mapq != ctx->span_min_mapq) { set_err(ctx, "im_span_enable: already enabled with flank %d, min_mapq %d", ctx->span_flank, ctx->span_min_mapq); return IM_E_ARG; }
+        return IM_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // each contig's run of tile sums lies where im_depth_enable puts the depth array's (the two arrays share the layout)
+    int64_t tiles = 0;
+    std::vector<int64_t> sums_off;
+    for (int32_t l : ctx->h_len) { sums_off.push_back(tiles); tiles += im::depth_sums_ints(l); }
+    ctx->h_sums_off = sums_off;
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->gspan, (size_t)ctx->ref_total * sizeof(int32_t)));
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->gspan_sums, (size_t)(tiles + 1) * sizeof(int32_t)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->gspan, 0, (size_t)ctx->ref_total * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->gspan_sums, 0, (size_t)(tiles + 1) * sizeof(int32_t), ctx->stream));       // the arrival counters start at zero
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->span_flank = flank; ctx->span_min_mapq = min_mapq;
+    return IM_OK;
+}
+
+int im_dev_span_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
+{
+    if (!ctx || !recs) return IM_E_ARG;
+    if (!ctx->gspan) { set_err(ctx, "im_span_enable has not been called"); return IM_E_ARG; }
+    if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    im::RefDev ref;
+    ref.ascii = ctx->ref_ascii; ref.pk = reinterpret_cast<const uint8_t*>(ctx->ref_pk);
+    ref.asc_off = ctx->d_asc_off; ref.pk_off = ctx->d_pk_off; ref.len = ctx->d_len; ref.n_contigs = ctx->n_contigs;
+    HIP_TRY(ctx, im::launch_span_scatter(ref, ctx->span_flank, ctx->span_min_mapq, *recs, ctx->gspan, (hipStream_t)stream));
+    return IM_OK;
+}
+
+int im_span_scan(im_ctx* ctx, int32_t tid, void* stream)
+{
+    if (!ctx || !ctx->gspan || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, im::launch_depth_scan_tiled(ctx->gspan + ctx->h_asc_off[tid], (int64_t)ctx->h_len[tid] + 1, ctx->gspan_sums + ctx->h_sums_off[tid], (hipStream_t)stream));
+    return IM_OK;
+}
+
+int im_span_reset(im_ctx* ctx, int32_t tid, void* stream)
+{
+    if (!ctx || !ctx->gspan || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->gspan + ctx->h_asc_off[tid], 0, ((size_t)ctx->h_len[tid] + 1) * sizeof(int32_t), (hipStream_t)stream));
+    return IM_OK;
+}
+
+// the queries' trip: [beg][end] in, [min] out through the context's workspace and stream
+static int span_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums, int64_t clen, uint32_t* min_out)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = up256(sizeof(int32_t) * (size_t)n);
+    int rc = ensure_ws(ctx, 3 * sb);
+    if (rc) return rc;
+    int32_t* d_beg = (int32_t*)ctx->ws;
+    int32_t* d_end = (int32_t*)((char*)ctx->ws + sb);
+    uint32_t* d_out = (uint32_t*)((char*)ctx->ws + 2 * sb);
+    HIP_TRY(ctx, hipMemcpyAsync(d_beg, beg, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_end, end, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, im::launch_span_query(n, d_beg, d_end, span, sums, clen, d_out, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(min_out, d_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+int im_span_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
+{
+    if (!ctx || n < 0 || !ctx->gspan || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    if (n == 0) return IM_OK;
+    if (!beg || !end || !min_out) return IM_E_ARG;
+    return span_query(ctx, n, beg, end, ctx->gspan + ctx->h_asc_off[tid], ctx->gspan_sums + ctx->h_sums_off[tid], ctx->h_len[tid], min_out);
+}
+
+int im_span_build(im_ctx* ctx, int64_t contig_len, int32_t n_run, const int32_t* run_start, const int32_t* run_len, int32_t flank)
+{
+    if (!ctx || contig_len < 0 || contig_len > 0x7fffff00LL || n_run < 0 || (n_run > 0 && (!run_start || !run_len))) return IM_E_ARG;
+    if (flank < 1) { set_err(ctx, "im_span_build: flank %d, must be >= 1", flank); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (contig_len + 1 > ctx->span_cap) {
+        if (ctx->span) { HIP_TRY(ctx, hipFree(ctx->span)); ctx->span = nullptr; }
+        if (ctx->span_sums) { HIP_TRY(ctx, hipFree(ctx->span_sums)); ctx->span_sums = nullptr; }
+        ctx->span_cap = 0; ctx->span_len = -1;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->span, (size_t)(contig_len + 1) * sizeof(int32_t)));
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->span_sums, (size_t)(im::depth_tiles(contig_len) + 1) * sizeof(int32_t)));
+        ctx->span_cap = contig_len + 1;
+    }
+    const size_t sb = up256(sizeof(int32_t) * (size_t)(n_run ? n_run : 1));
+    int rc = ensure_ws(ctx, 2 * sb);
+    if (rc) return rc;
+    int32_t* d_start = (int32_t*)ctx->ws;
+    int32_t* d_len = (int32_t*)((char*)ctx->ws + sb);
+    if (n_run > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_start, run_start, sizeof(int32_t) * (size_t)n_run, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_len, run_len, sizeof(int32_t) * (size_t)n_run, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(ctx, im::launch_span_build(contig_len, n_run, d_start, d_len, flank, ctx->span, ctx->span_sums, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->span_len = contig_len;
+    return IM_OK;
+}
+
+int im_span_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
+{
+    if (!ctx || n < 0) return IM_E_ARG;
+    if (ctx->span_len < 0) { set_err(ctx, "im_span_build has not been called"); return IM_E_ARG; }
+    if (n == 0) return IM_OK;
+    if (!beg || !end || !min_out) return IM_E_ARG;
+    return span_query(ctx, n, beg, end, ctx->span, nullptr, ctx->span_len, min_out);
 }
 
 int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64_t* t_off,

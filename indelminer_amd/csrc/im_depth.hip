@@ -236,6 +236,7 @@ hipError_t launch_depth_scan(int32_t* depth, int64_t n, int32_t* sums, hipStream
     return hipGetLastError();
 }
 
+int64_t depth_tile_positions() { return kScanTile; }
 int64_t depth_tiles(int64_t clen) { return (clen + 1 + kScanTile - 1) / kScanTile; }
 // ints of a contig's run of tile sums in the genome-wide form: the tiles' totals, the arrival counter of the groups, one arrival counter per group
 int64_t depth_sums_ints(int64_t clen) { const int64_t t = depth_tiles(clen); return t + 1 + (t + kScanGroup - 1) / kScanGroup; }

@@ -105,6 +105,15 @@ int64_t depth_tiles(int64_t clen);
 int64_t depth_sums_ints(int64_t clen);
 hipError_t launch_depth_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* depth, int64_t clen,
                               uint32_t* out, hipStream_t stream);
+int64_t depth_tile_positions();     // positions per tile of launch_depth_scan_tiled (a tile's offset lies at sums[p / that])
+
+// im_span.hip: reference-spanning read counts (the genotype columns); the array has the depth array's layout and scans
+hipError_t launch_span_scatter(const RefDev& ref, int32_t flank, int32_t min_mapq, const im_dev_records& recs, int32_t* diff, hipStream_t stream);
+hipError_t launch_span_build(int64_t clen, int32_t n_run, const int32_t* run_start, const int32_t* run_len, int32_t flank,
+                             int32_t* span, int32_t* sums, hipStream_t stream);
+// minimum over [beg, end] inclusive; sums: the tile offsets of launch_depth_scan_tiled, or null for an array of whole prefix sums
+hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
+                             int64_t clen, uint32_t* out, hipStream_t stream);
 
 // tasks within IM_MAX_SW_TARGET / IM_MAX_READ run in the LDS form; when the batch holds longer ones (big_grid > 0) a second launch
 // with its boundary rows in big_scratch (support_big_scratch_bytes) takes those

@@ -327,6 +327,8 @@ typedef struct {
     /* match segments of the contig's pileup-eligible records, for the device depth array */
     int32_t *seg_start, *seg_len; int64_t n_seg, cap_seg;
     int depth_tid;              /* contig whose depth array is resident on the device, -1 = none */
+    /* -G, record-at-a-time path: the M/=/X runs of the contig's eligible records, for the device span array (im_span_build) */
+    int32_t *run_start, *run_len; int64_t n_run, cap_run;
     int pipe_mode;              /* device pipeline: depth queries go to the genome-wide array */
     int marker_floor;           /* multi-GPU: smallest start of a stale pair-table entry of an earlier contig on another rank */
     /* live entries of the pair table (find_marker walks these) */
@@ -899,6 +901,40 @@ static uint32_t region_depth_from_bam(driver* d, int32_t tid, int32_t start, int
     return (uint32_t)floor((uint32_t)covsum * 1.0 / (uint32_t)(stop - start));
 }
 
+/* -G: POS, END and BP_END of a variant as print_vcf_output prints them */
+static void vcf_coordinates(const variant_t* v, int* pos, int* endpos, int* bp_end)
+{
+    *pos = (int)(v->start - v->lw);
+    if (v->type == CLS_DELETION) {
+        const int reflength = (int)(v->stop + v->rw) - (int)(v->start - v->lw - 1);
+        const int altlength = (int)(v->start + v->rw) - (int)(v->start - v->lw - 1);
+        *endpos = *pos + reflength - altlength + 1;
+    } else *endpos = *pos + 1;
+    *bp_end = (int)(v->stop + v->rw + 1);
+}
+
+/* -G: the sample column.  Genotype from (RS = reads that span the breakpoint on the reference allele, NS = reads that support
+ * the indel) in 64-bit integers, thousandths of a phred: a read of the wrong allele costs E (error 0.01), a read of the right one
+ * C, either read under a heterozygote H.  GT = the cheapest of 0/0, 0/1, 1/1 (the lower index wins a tie), GQ = the distance to
+ * the second cheapest, rounded to whole phreds, at most 99.  No reference counterpart. */
+static void print_genotype(const variant_t* v)
+{
+    if (v->evdnctype == EV_PAIRED_READ || !v->rs_valid) {           /* no precise breakpoint to count spanning reads at */
+        printf("\tGT:AD:GQ\t./.:.,%u:.", v->support);
+        return;
+    }
+    const int64_t E = 20000, C = 44, H = 3010;
+    const int64_t ns = (int64_t)v->support, rs = (int64_t)v->rs_cached;
+    int64_t L[3] = { ns * E + rs * C, (ns + rs) * H, ns * C + rs * E };
+    int best = 0;
+    for (int g = 1; g < 3; g++) if (L[g] < L[best]) best = g;
+    int64_t second = -1;
+    for (int g = 0; g < 3; g++) if (g != best && (second < 0 || L[g] - L[best] < second)) second = L[g] - L[best];
+    int64_t gq = (second + 500) / 1000;
+    if (gq > 99) gq = 99;
+    printf("\tGT:AD:GQ\t%s:%u,%u:%d", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", v->rs_cached, v->support, (int)gq);
+}
+
 /* print_vcf_output (src/variant.c:115-311) */
 static void print_vcf_output(driver* d, const variant_t* v)
 {
@@ -971,6 +1007,7 @@ static void print_vcf_output(driver* d, const variant_t* v)
            v->dp_valid ? (int)v->dp_cached
                        : (int)region_depth(d, v->tid, (int32_t)(v->start - v->lw - 1), (int32_t)(v->stop + v->rw + 1)));
     printf(";BF=%d,%d", lflank, rflank);
+    if (g_genotype) print_genotype(v);
     printf("\n");
     free(taildistances);
 }
@@ -1196,6 +1233,34 @@ static void print_variants(driver* d, variant_list* vs)
             }
         }
         free(beg); free(end); free(sum); free(deepest); free(who);
+    }
+    /* ... -G: their reference support the same way: per variant the thinnest reference-spanning depth over the positions its
+     * breakpoint can lie at, POS .. POS + (BP_END - END) ... */
+    if (g_genotype && out.n > 0) {
+        int32_t* beg = xmalloc(sizeof(int32_t) * (size_t)out.n);
+        int32_t* end = xmalloc(sizeof(int32_t) * (size_t)out.n);
+        uint32_t* rs = xmalloc(sizeof(uint32_t) * (size_t)out.n);
+        int* who = xmalloc(sizeof(int) * (size_t)out.n);
+        int m = 0;
+        for (int i = 0; i < out.n; i++) {
+            variant_t* v = out.v[i];
+            v->rs_valid = 0;
+            if (v->evdnctype == EV_PAIRED_READ) continue;
+            int pos, endpos, bp_end;
+            vcf_coordinates(v, &pos, &endpos, &bp_end);
+            if (bp_end < endpos) continue;
+            beg[m] = pos; end[m] = pos + (bp_end - endpos); who[m] = i; m++;
+        }
+        if (m > 0) {
+            gpu_wait(d);
+            pthread_mutex_lock(&g_query_mu);
+            /* all printed variants of a flush lie on one contig */
+            const int qrc = d->pipe_mode ? im_span_query_tid(d->gpu, out.v[who[0]]->tid, m, beg, end, rs) : im_span_query(d->gpu, m, beg, end, rs);
+            pthread_mutex_unlock(&g_query_mu);
+            if (qrc != IM_OK) fatalf("im_span_query: %s", im_last_error(d->gpu));
+            for (int q = 0; q < m; q++) { out.v[who[q]]->rs_cached = rs[q]; out.v[who[q]]->rs_valid = 1; }
+        }
+        free(beg); free(end); free(rs); free(who);
     }
     /* ... and out they go */
     for (int i = 0; i < out.n; i++) emit_variant(d, out.v[i]);

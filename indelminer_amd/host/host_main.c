@@ -33,6 +33,7 @@ static void print_help(FILE* file)
     fprintf(file, "\t-f, number of differences allowed in an alignment[6]\n");
     fprintf(file, "\t-b, require at least one read with these bases on \n");
     fprintf(file, "\t    either side of the indel[30]\n");
+    fprintf(file, "\t-G, add genotype columns (FORMAT GT:AD:GQ) to the vcf output\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -75,7 +76,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:G")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -99,6 +100,7 @@ int main(int argc, char** argv)
         case 'q': if (sscanf(optarg, "%d", &O.qthreshold) != 1) fatalf("incorrect option for -q: %s\n", optarg); break;
         case 'a': O.call_all_indels = 1; break;
         case 'b': if (sscanf(optarg, "%u", &O.minbalance) != 1) fatalf("incorrect option for -b: %s\n", optarg); break;
+        case 'G': g_genotype = 1; break;                            /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -126,6 +128,16 @@ int main(int argc, char** argv)
     const char* bam_name = ++ptr;
     g_sample_name = samplename;
     if (g_vcfname != NULL) O.ethreshold_vcfcheck = 0;   /* src/indelminer.c:1074 */
+    if (g_genotype) {
+        /* what -G does not do, said in one line */
+        const char* ws_ = getenv("WORLD_SIZE");
+        if (g_vcfname != NULL) { fprintf(stderr, "indelminer: -G is not available with a VCF argument (annotate mode)\n"); return EXIT_FAILURE; }
+        if ((ws_ && atoi(ws_) > 1) || getenv("INDELMINER_FORCE_MGPU")) { fprintf(stderr, "indelminer: -G is not available with more than one rank\n"); return EXIT_FAILURE; }
+        if (!im_span_enable || !im_dev_span_scatter || !im_span_scan || !im_span_query_tid || !im_span_build || !im_span_query) {
+            fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
+        }
+        if (strcmp(O.outputformat, "detailed") == 0) g_genotype = 0;    /* -o detailed has no columns to add to */
+    }
 
     fprintf(stderr, "Reference fasta file: %s\n", fasta_reference);
     fprintf(stderr, "Chromosomal region  : %s\n", O.region == NULL ? "ALL" : O.region);

@@ -188,6 +188,8 @@ static void pipe_global_init(driver* d)
     if (im_set_insert_ranges(d->gpu, g_rg_n, g_rg_name, rmax) != IM_OK) fatalf("im_set_insert_ranges: %s", im_last_error(d->gpu));
     free(rmax);
     if (im_depth_enable(d->gpu) != IM_OK) fatalf("im_depth_enable: %s", im_last_error(d->gpu));
+    /* -G: the second genome-wide array, only then */
+    if (g_genotype && im_span_enable(d->gpu, (int32_t)O.ethreshold, O.qthreshold) != IM_OK) fatalf("im_span_enable: %s", im_last_error(d->gpu));
 }
 
 /* one walker's buffers (with_chunks: the pinned chunk ring a walk delivers records through; the main thread's stage pipeline
@@ -404,6 +406,7 @@ static void pipe_submit(ppipe* P, pgroup* G)
     out.cand_rec = P->cand_rec; out.counters = P->counters; out.rec_class = c->d_class;
     out.cap_cand = P->cap_cand; out.cap_bases = P->cap_bases; out.consumed = NULL;     /* cleared once per group in pipe_run_group */
     GPU(im_dev_triage(g, &P->tp, &recs, &out, c->d_scratch, c->scratch_bytes, P->stream));
+    if (g_genotype) GPU(im_dev_span_scatter(g, &recs, P->stream));      /* -G: a launch of its own behind the triage, in front of the chunk's event */
     GPU(im_dev_download_async(g, c->h_cnt, P->counters, 32, P->stream));
     GPU(im_event_record(c->done, P->stream));
     c->busy = 1; P->n_busy++;

@@ -34,7 +34,13 @@ static void print_output_header(void)
     if (strncmp(O.outputformat, "vcf", 3) == 0) print_vcf_preamble();
     if (g_vcfname != NULL)
         printf("##INFO=<ID=%s,Number=0,Type=Flag,Description=\"The variant is also present in this sample\">\n", g_sample_name);
-    if (strncmp(O.outputformat, "vcf", 3) == 0) printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
+    if (g_genotype) {
+        /* -G: no reference counterpart */
+        printf("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype, the most likely of 0/0, 0/1, 1/1 given AD\">\n");
+        printf("##FORMAT=<ID=AD,Number=2,Type=Integer,Description=\"Read support of the reference and the alternative allele: the smallest number, over the positions POS .. POS+(BP_END-END) the breakpoint can lie at, of alignments that match the reference for the -n distance on both sides of it (an upper bound of the reads spanning the whole interval, exact when the interval is one position), and NS\">\n");
+        printf("##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred-scaled distance to the second most likely genotype, at most 99\">\n");
+        printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", g_sample_name);
+    } else if (strncmp(O.outputformat, "vcf", 3) == 0) printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
     fflush(OUT);
 }
 /* One pass without a config file: the reference prints its header after its estimation pass and the FASTA read -- a run it ends
@@ -300,7 +306,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
     bam_region_iter it;
     bam_record b; memset(&b, 0, sizeof b);
     if (bam_region_begin(&it, r, d->idx, tid, beg, end) != 0) fatalf("cannot seek in %s", d->bam_name);
-    d->n_seg = 0;
+    d->n_seg = 0; d->n_run = 0;
     const int whole = (beg <= 0 && end >= d->hdr->target_len[tid]);
     volatile int died = 0;              /* a record the reference dies on ended the pass: the flushes in front of it are still to print */
     t_is_main_thread_of_passA = 1;
@@ -324,6 +330,30 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
                 } else if (op == OP_D || op == OP_N) x += len;
             }
         }
+        if (g_genotype && b.tid >= 0 && !(b.flag & (0x4 | 0x100 | 0x200 | 0x400)) && (int)b.mapq >= O.qthreshold) {
+            /* -G: the maximal M/=/X runs of the record (D and N advance and end a run, every other operation ends it) */
+            const uint8_t* cig = BAMR_CIGAR(&b);
+            int64_t x = b.pos, rs = 0;
+            int in_run = 0;
+            for (int kk = 0; kk <= b.n_cigar; kk++) {
+                const int op = kk < b.n_cigar ? CIG_OP(bamr_cigar_at(cig, kk)) : OP_S, len = kk < b.n_cigar ? CIG_LEN(bamr_cigar_at(cig, kk)) : 0;
+                if (op == OP_M || op == OP_EQ || op == OP_X) { if (!in_run) { rs = x; in_run = 1; } x += len; continue; }
+                if (in_run) {
+                    /* clipped to what an int32 start and length hold (the device clips to the contig) */
+                    int64_t a = rs < 0 ? 0 : rs, e = x > INT32_MAX ? INT32_MAX : x;
+                    if (e > a) {
+                        if (d->n_run == d->cap_run) {
+                            d->cap_run = d->cap_run ? d->cap_run * 2 : (1 << 16);
+                            d->run_start = xrealloc(d->run_start, sizeof(int32_t) * (size_t)d->cap_run);
+                            d->run_len = xrealloc(d->run_len, sizeof(int32_t) * (size_t)d->cap_run);
+                        }
+                        d->run_start[d->n_run] = (int32_t)a; d->run_len[d->n_run] = (int32_t)(e - a); d->n_run++;
+                    }
+                    in_run = 0;
+                }
+                if (op == OP_D || op == OP_N) x += len;
+            }
+        }
         dispatch_record(d, &b);
     }
     g_passA_armed = 0;
@@ -337,6 +367,13 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
         d->depth_tid = tid;
     }
     phase_time("depth array (device)");
+    if (g_genotype) {
+        gpu_wait(d);
+        if (d->n_run > INT32_MAX) fatalf("more than 2^31 alignment runs on one contig");
+        if (im_span_build(d->gpu, d->seqlen[tid], (int32_t)d->n_run, d->run_start, d->run_len, (int32_t)O.ethreshold) != IM_OK)
+            fatalf("im_span_build: %s", im_last_error(d->gpu));
+        phase_time("span array (device)");
+    }
 
     im_read_result* res = NULL;
     if (d->cb.n > 0) {

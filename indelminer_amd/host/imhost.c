@@ -106,6 +106,16 @@ static __thread FILE* t_out;
 #define OUT (t_out ? t_out : stdout)
 #define printf(...) fprintf(OUT, __VA_ARGS__)
 static pthread_mutex_t g_query_mu = PTHREAD_MUTEX_INITIALIZER;     /* depth queries share the context's workspace and stream */
+/* -G: genotype columns (FORMAT GT:AD:GQ) from the device's reference-spanning read counts.  The reference has no such option
+ * (its getopt string has no G).  The entry points are referenced weakly: an implementation of the C ABI without them (the CPU
+ * stand-in the host tests link this driver against) still links, and -G then says what it needs. */
+static int g_genotype = 0;
+extern int im_span_enable(im_ctx*, int32_t, int32_t) __attribute__((weak));
+extern int im_dev_span_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
+extern int im_span_scan(im_ctx*, int32_t, void*) __attribute__((weak));
+extern int im_span_query_tid(im_ctx*, int32_t, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
+extern int im_span_build(im_ctx*, int64_t, int32_t, const int32_t*, const int32_t*, int32_t) __attribute__((weak));
+extern int im_span_query(im_ctx*, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that

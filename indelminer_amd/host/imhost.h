@@ -71,6 +71,9 @@ typedef struct {
     /* DP= of the variant when print_variants asked the device for a whole flush at once */
     int32_t   dp_cached;
     int       dp_valid;
+    /* -G: reference support of the variant (reads that span its breakpoint interval), asked for in the same way */
+    uint32_t  rs_cached;
+    int       rs_valid;
 } variant_t;
 
 typedef struct {
