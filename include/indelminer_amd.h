@@ -200,6 +200,44 @@ int im_support_batch(im_ctx* ctx, int32_t n,
                      const uint8_t* targets, const int64_t* t_off,
                      const uint8_t* queries, const int64_t* q_off, int32_t* out);
 
+/* ---- seam 4, counting form: "how many reads support this known indel?" (-A) ------ */
+
+/* check_for_indel's rule (src/variant.c:1427-1573) for EVERY read that overlaps a known variant, not up to the first that
+ * passes (is_indel_supported, 1561-1573, stops there): the read counts for and against each known indel of an annotate run.
+ * No reference counterpart for the counts; the per-read rule is the reference's.
+ * One call takes the tasks of many variants.  A task names its variant and the stretch [rstart, rstop) of the contig its read
+ * covers, widened by the indel's size and clipped to the contig by the caller (1259-1263); the kernel reads the window through
+ * the splice from the resident reference (im_set_reference) and the variant's ALT bytes -- the caller builds no window:
+ *     deletion   ref[rstart, start) + ref[stop-1, rstop)          insertion   ref[rstart, start) + ALT[1..] + ref[start, rstop)
+ * (raw bytes: the score compares upper-cased bytes, the substitution count raw ones), runs im_support_batch's Smith-Waterman of
+ * queries[q_off, q_off + q_len) against it and applies the verdict subs <= own_subs, indels <= own_indels, aligned >= own_aligned.
+ * IM_SC_DIRECT: the read's CIGAR carries the indel itself, it supports without an alignment.  Per variant the call returns
+ *     counts[3v]     N_all  supporting tasks
+ *     counts[3v+1]   AS     ... that have IM_SC_MAPQ_OK
+ *     counts[3v+2]   DC     ... that have IM_SC_MAPQ_OK and IM_SC_SPANS (reads seam 5's array has counted for the reference)
+ * Integer adds: the result does not depend on the order of the tasks.  Windows beyond IM_MAX_SW_TARGET and queries beyond
+ * IM_MAX_READ (up to 2^20 bases) are counted too, by a second launch.  Stream-ordered on the context's stream, one
+ * synchronisation when the counts come back. */
+#define IM_SC_DIRECT   1
+#define IM_SC_MAPQ_OK  2
+#define IM_SC_SPANS    4
+typedef struct {
+    int32_t tid;                /* contig of im_set_reference                          */
+    int32_t start, stop;        /* POS and END of the VCF record, used as the reference uses them (0-based indices) */
+    int32_t type;               /* IM_CLS_*                                            */
+    int32_t alt_off, alt_len;   /* the ALT string in alts[]                            */
+} im_known_variant;
+typedef struct {
+    int32_t variant;            /* index into variants[]                               */
+    int32_t rstart, rstop;      /* 0 <= rstart <= rstop <= contig length               */
+    int32_t q_off, q_len;       /* the aligned part of the read in queries[]           */
+    int32_t own_subs, own_indels, own_aligned;      /* of the read's own alignment     */
+    int32_t flags;              /* IM_SC_*                                             */
+} im_count_task;
+int im_support_count(im_ctx* ctx, int32_t n_variants, const im_known_variant* variants, const uint8_t* alts, int64_t alt_bytes,
+                     int32_t n_tasks, const im_count_task* tasks, const uint8_t* queries, int64_t query_bytes,
+                     int32_t* counts /* n_variants x 3 */);
+
 /* ---- device-resident level --------------------------------------------- */
 
 /* Device buffers of one realign batch.  All pointers are device pointers owned

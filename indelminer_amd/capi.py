@@ -84,6 +84,24 @@ class DevCands(C.Structure):
                 ("cap_cand", C.c_int32), ("cap_bases", C.c_int64), ("consumed", C.c_void_p)]
 
 
+class KnownVariant(C.Structure):
+    _fields_ = [("tid", C.c_int32), ("start", C.c_int32), ("stop", C.c_int32), ("type", C.c_int32),
+                ("alt_off", C.c_int32), ("alt_len", C.c_int32)]
+
+
+class CountTask(C.Structure):
+    _fields_ = [("variant", C.c_int32), ("rstart", C.c_int32), ("rstop", C.c_int32), ("q_off", C.c_int32), ("q_len", C.c_int32),
+                ("own_subs", C.c_int32), ("own_indels", C.c_int32), ("own_aligned", C.c_int32), ("flags", C.c_int32)]
+
+
+assert C.sizeof(KnownVariant) == 24 and C.sizeof(CountTask) == 36
+KNOWN_VARIANT_DTYPE = np.dtype([("tid", "<i4"), ("start", "<i4"), ("stop", "<i4"), ("type", "<i4"), ("alt_off", "<i4"), ("alt_len", "<i4")])
+COUNT_TASK_DTYPE = np.dtype([("variant", "<i4"), ("rstart", "<i4"), ("rstop", "<i4"), ("q_off", "<i4"), ("q_len", "<i4"),
+                             ("own_subs", "<i4"), ("own_indels", "<i4"), ("own_aligned", "<i4"), ("flags", "<i4")])
+assert KNOWN_VARIANT_DTYPE.itemsize == 24 and COUNT_TASK_DTYPE.itemsize == 36
+CLS_INSERTION, CLS_DELETION = 0, 1
+SC_DIRECT, SC_MAPQ_OK, SC_SPANS = 1, 2, 4
+
 REC_SKIP, REC_COUNTED, REC_CAND_UNMAPPED, REC_CAND_PROPER, REC_PE = 0, 1, 2, 3, 4
 
 
@@ -129,6 +147,8 @@ def lib():
         L.im_depth_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.im_depth_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_support_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_support_count.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.im_dev_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.im_dev_free.argtypes = [C.c_void_p, C.c_void_p]
         L.im_dev_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -412,6 +432,18 @@ class Context:
         out = np.zeros((max(n, 1), 4), dtype=np.int32)
         self._check(lib().im_support_batch(self.h, n, _ptr(t), _ptr(to), _ptr(q), _ptr(qo), _ptr(out)))
         return out[:n]
+
+    def support_count(self, variants, alts, tasks, queries):
+        """variants: KNOWN_VARIANT_DTYPE array, alts: bytes, tasks: COUNT_TASK_DTYPE array, queries: bytes.
+        Returns int32 [n_variants, 3]: N_all, AS, DC."""
+        variants = np.ascontiguousarray(variants, dtype=KNOWN_VARIANT_DTYPE)
+        tasks = np.ascontiguousarray(tasks, dtype=COUNT_TASK_DTYPE)
+        a = np.frombuffer(bytes(alts) + b"\0" * 8, dtype=np.uint8).copy()
+        q = np.frombuffer(bytes(queries) + b"\0" * 8, dtype=np.uint8).copy()
+        out = np.zeros((max(len(variants), 1), 3), dtype=np.int32)
+        self._check(lib().im_support_count(self.h, len(variants), _ptr(variants), _ptr(a), len(alts),
+                                           len(tasks), _ptr(tasks), _ptr(q), len(queries), _ptr(out)))
+        return out[:len(variants)]
 
     def set_insert_ranges(self, names, range_max):
         """names in the order they entered the reference's insert-length table; range_max = range[1] of each."""

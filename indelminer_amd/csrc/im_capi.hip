@@ -54,6 +54,7 @@ struct im_ctx {
     int32_t* span = nullptr;
     int32_t* span_sums = nullptr;
     int64_t span_cap = 0, span_len = -1;
+    bool support_count_attr = false;    // im_support_count: its kernel's LDS attribute has been set on this context's device
     std::mutex gb_mu;
     std::unordered_map<void*, int32_t> gb_layout;   // group-by scratch -> the slot count it was initialised (and is carved) for
     std::unordered_map<void*, std::pair<int32_t, int32_t>> fg_layout;   // flush + group-by scratch -> (slots, flushes) it is carved for
@@ -929,6 +930,84 @@ int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int32_t i = 0; i < n; i++)
         if (out[4 * i + 3] == IM_ST_UNSUPPORTED) { set_err(ctx, "support task %d: target or query longer than the kernel holds", i); return IM_E_UNSUPPORTED; }
+    return IM_OK;
+}
+
+int im_support_count(im_ctx* ctx, int32_t n_variants, const im_known_variant* variants, const uint8_t* alts, int64_t alt_bytes,
+                     int32_t n_tasks, const im_count_task* tasks, const uint8_t* queries, int64_t query_bytes, int32_t* counts)
+{
+    if (!ctx || n_variants < 0 || n_tasks < 0 || alt_bytes < 0 || query_bytes < 0) return IM_E_ARG;
+    if (n_variants == 0) { if (n_tasks > 0) { set_err(ctx, "im_support_count: tasks without variants"); return IM_E_ARG; } return IM_OK; }
+    if (!variants || !counts || (n_tasks > 0 && !tasks) || (alt_bytes > 0 && !alts) || (query_bytes > 0 && !queries)) return IM_E_ARG;
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    if (alt_bytes > 0x7fffffffLL || query_bytes > 0x7fffffffLL) { set_err(ctx, "im_support_count: more than 2^31 bytes in one call"); return IM_E_ARG; }
+    memset(counts, 0, sizeof(int32_t) * 3 * (size_t)n_variants);
+    if (n_tasks == 0) return IM_OK;
+    // every index the kernels follow is checked here, once
+    for (int32_t v = 0; v < n_variants; v++) {
+        const im_known_variant& k = variants[v];
+        if (k.tid < 0 || k.tid >= ctx->n_contigs || k.start < 0 || k.stop < 0 || (k.type != IM_CLS_DELETION && k.type != IM_CLS_INSERTION) ||
+            k.alt_off < 0 || k.alt_len < 0 || (int64_t)k.alt_off + k.alt_len > alt_bytes) {
+            set_err(ctx, "im_support_count: variant %d is not a variant of this reference", v); return IM_E_ARG;
+        }
+    }
+    std::vector<int32_t> big_idx;
+    std::vector<int64_t> big_toff(1, 0);
+    int64_t max_short = 0, max_big_t = 0, max_big_q = 0;
+    for (int32_t i = 0; i < n_tasks; i++) {
+        const im_count_task& t = tasks[i];
+        if (t.variant < 0 || t.variant >= n_variants) { set_err(ctx, "im_support_count: task %d names variant %d of %d", i, t.variant, n_variants); return IM_E_ARG; }
+        if (t.flags & IM_SC_DIRECT) continue;
+        const im_known_variant& k = variants[t.variant];
+        if (t.rstart < 0 || t.rstop < t.rstart || t.rstop > ctx->h_len[k.tid] || t.q_off < 0 || t.q_len < 0 || (int64_t)t.q_off + t.q_len > query_bytes) {
+            set_err(ctx, "im_support_count: task %d reaches outside its contig or the query bytes", i); return IM_E_ARG;
+        }
+        if (t.q_len > im::support_count_max_query()) { set_err(ctx, "support task %d: query longer than the kernel holds", i); return IM_E_UNSUPPORTED; }
+        const int64_t w = im::support_count_window(k, t.rstart, t.rstop);
+        if (!im::support_count_is_big(w, t.q_len)) { if (w > max_short) max_short = w; continue; }
+        big_idx.push_back(i);
+        big_toff.push_back(big_toff.back() + w);
+        if (w > max_big_t) max_big_t = w;
+        if (t.q_len > max_big_q) max_big_q = t.q_len;
+    }
+    const int32_t n_big = (int32_t)big_idx.size();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int32_t big_grid = 0;
+    const size_t rowb = n_big ? up256(im::support_big_scratch_bytes(max_big_t, max_big_q, n_big, &big_grid)) : 0;
+    const size_t vb = up256(sizeof(im_known_variant) * (size_t)n_variants), ab = up256((size_t)alt_bytes + 16);
+    const size_t kb = up256(sizeof(im_count_task) * (size_t)n_tasks), qb = up256((size_t)query_bytes + 16);
+    const size_t cb = up256(sizeof(int32_t) * 3 * (size_t)n_variants);
+    const size_t bib = up256(sizeof(int32_t) * (size_t)(n_big + 1)), bob = up256(sizeof(int64_t) * (size_t)(n_big + 1));
+    const size_t bwb = up256((size_t)big_toff.back() + 16);
+    int rc = ensure_ws(ctx, vb + ab + kb + qb + cb + bib + bob + bwb + rowb);
+    if (rc) return rc;
+    char* w = static_cast<char*>(ctx->ws);
+    im_known_variant* d_v = (im_known_variant*)w; w += vb;
+    uint8_t* d_a = (uint8_t*)w; w += ab;
+    im_count_task* d_k = (im_count_task*)w; w += kb;
+    uint8_t* d_q = (uint8_t*)w; w += qb;
+    int32_t* d_c = (int32_t*)w; w += cb;
+    int32_t* d_bi = (int32_t*)w; w += bib;
+    int64_t* d_bo = (int64_t*)w; w += bob;
+    uint8_t* d_bw = (uint8_t*)w; w += bwb;
+    void* d_rows = (void*)w;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(d_v, variants, sizeof(im_known_variant) * (size_t)n_variants, hipMemcpyHostToDevice, st));
+    if (alt_bytes > 0) HIP_TRY(ctx, hipMemcpyAsync(d_a, alts, (size_t)alt_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_k, tasks, sizeof(im_count_task) * (size_t)n_tasks, hipMemcpyHostToDevice, st));
+    if (query_bytes > 0) HIP_TRY(ctx, hipMemcpyAsync(d_q, queries, (size_t)query_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(d_c, 0, sizeof(int32_t) * 3 * (size_t)n_variants, st));
+    if (n_big > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_bi, big_idx.data(), sizeof(int32_t) * (size_t)n_big, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_bo, big_toff.data(), sizeof(int64_t) * (size_t)(n_big + 1), hipMemcpyHostToDevice, st));
+    }
+    im::RefDev ref;
+    ref.ascii = ctx->ref_ascii; ref.pk = reinterpret_cast<const uint8_t*>(ctx->ref_pk);
+    ref.asc_off = ctx->d_asc_off; ref.pk_off = ctx->d_pk_off; ref.len = ctx->d_len; ref.n_contigs = ctx->n_contigs;
+    HIP_TRY(ctx, im::launch_support_count(n_tasks, d_k, d_v, d_a, ref, d_q, d_c, max_short, n_big, d_bi, d_bo, d_bw, max_big_t, d_rows, big_grid,
+                                          &ctx->support_count_attr, st));
+    HIP_TRY(ctx, hipMemcpyAsync(counts, d_c, sizeof(int32_t) * 3 * (size_t)n_variants, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));      // the one synchronisation: big_idx / big_toff are read by then too
     return IM_OK;
 }
 

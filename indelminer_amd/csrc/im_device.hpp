@@ -122,4 +122,16 @@ hipError_t launch_support(int32_t n_tasks, const uint8_t* targets, const int64_t
                           const uint8_t* queries, const int64_t* q_off, int32_t* out, int64_t max_target, int64_t max_query,
                           void* big_scratch, int32_t big_grid, int n_cu, hipStream_t stream);
 
+
+// the counting form (im_support_count): the windows come through the splice from the resident reference.  The caller lists the
+// tasks beyond the LDS form (support_count_is_big) with the offsets of their windows in big_win (support_count_window bytes each);
+// attr_set: the context's "function attribute has been set" flag
+int64_t support_count_window(const im_known_variant& v, int32_t rstart, int32_t rstop);
+bool support_count_is_big(int64_t window, int64_t query);
+int64_t support_count_max_query();
+hipError_t launch_support_count(int32_t n_tasks, const im_count_task* tasks, const im_known_variant* vars, const uint8_t* alts, const RefDev& ref,
+                                const uint8_t* queries, int32_t* counts, int64_t max_short_target,
+                                int32_t n_big, const int32_t* big_idx, const int64_t* big_toff, uint8_t* big_win, int64_t max_big_target,
+                                void* big_scratch, int32_t big_grid, bool* attr_set, hipStream_t stream);
+
 }  // namespace im

@@ -94,6 +94,80 @@ __device__ __forceinline__ uint64_t stat_xor(uint64_t v, int o)
     return ((uint64_t)hi << 32) | lo;
 }
 
+// The skewed sweep with carried statistics, shared by every kernel of this file: the packed statistics of the traced path from
+// the first strictly-greatest cell (0 when no cell is positive).  s.t1 holds the len1 target bytes, q the len2 query bytes; the
+// whole workgroup (one wave) calls it, and passes a barrier per 64-row block.
+template <bool BIG>
+__device__ __forceinline__ typename SwStat<BIG>::T sw_sweep(const SwRow<typename SwStat<BIG>::T>& s, const uint8_t* __restrict__ q,
+                                                            const int len1, const int len2, const int lane)
+{
+    typedef SwStat<BIG> St;
+    typedef typename St::T stat_t;
+    constexpr stat_t kStAligned = St::kAligned, kStIndel = St::kIndel, kStSub = St::kSub;
+    int g_best = 0; stat_t g_stats = 0;              // max_score starts at 0: an all-nonpositive matrix traces nothing
+    for (int i0 = 0; i0 < len2; i0 += 64) {
+        const int i = i0 + 1 + lane;                    // this lane's row (1-based)
+        const bool row_ok = i <= len2;
+        const uint32_t qc_raw = row_ok ? q[i - 1] : 0u;
+        const uint32_t qc = up8(qc_raw);
+        // own previous cell (i, j-1): column 0 to start with (1297-1303)
+        int v_left = -4 - i, e_left = 0; stat_t s_left = 0;
+        // what the lane below produced one and two steps ago
+        int v_out = 0, f_out = 0; stat_t s_out = 0;     // this lane's newest cell
+        int v_diag_in = -4 - (i - 1);                   // (i-1, 0)
+        stat_t s_diag_in = 0;
+        int best_v = 0; stat_t best_s = 0;
+        const int steps = len1 + 63;
+        for (int t = 0; t < steps; t++) {
+            // neighbours from the lane below: its newest cell is (i-1, j)
+            int v_up = sw_shr1(0, v_out), f_up = sw_shr1(0, f_out);
+            stat_t s_up = stat_shr1(s_out);
+            const int j = t - lane + 1;
+            if (lane == 0) {
+                if (j >= 1 && j <= len1) {
+                    if (i0 == 0) { v_up = -4 - j; f_up = 0; s_up = 0; }          // row 0 (1301-1303), F zero-filled (1307)
+                    else { v_up = s.rowV[j]; f_up = s.rowF[j]; s_up = s.rowS[j]; }
+                }
+            }
+            const bool act = row_ok && j >= 1 && j <= len1;
+            if (act) {
+                const uint32_t tc_raw = s.t1[j - 1];
+                const int sub = v_diag_in + ((up8(tc_raw) == qc) ? 2 : -1);
+                const int ins = max(f_up, v_up - 4) - 1;
+                const int del = max(e_left, v_left - 4) - 1;
+                const int indel = max(ins, del);
+                int v = sub;
+                stat_t st = (v_diag_in > 0 ? s_diag_in : (stat_t)0) + kStAligned + ((tc_raw != qc_raw) ? kStSub : (stat_t)0);
+                if (v < indel) {
+                    v = indel;
+                    if (ins >= del) st = (v_up > 0 ? s_up : (stat_t)0) + kStIndel + kStAligned;
+                    else            st = (v_left > 0 ? s_left : (stat_t)0) + kStIndel;
+                }
+                if (v > best_v) { best_v = v; best_s = st; }
+                // becomes "left" for the next column and "up" for the lane above
+                v_left = v; e_left = del; s_left = st;
+                v_out = v; f_out = ins; s_out = st;
+                if (lane == 63) { s.rowV[j] = v; s.rowF[j] = ins; s.rowS[j] = st; }
+            }
+            // the cell above-left of the next column is the cell above of this one
+            v_diag_in = (j >= 1 && j <= len1) ? v_up : v_diag_in;
+            s_diag_in = (j >= 1 && j <= len1) ? s_up : s_diag_in;
+            if (j == 0) { v_diag_in = -4 - (i - 1); s_diag_in = 0; }
+            if (lane == 0 && j >= 1 && j <= len1 && i0 > 0) { /* boundary row diag comes from LDS too */ }
+        }
+        // block maximum: larger score, then smaller row (rows ascend with the lane)
+        int bv = best_v; stat_t bs = best_s; int bl = lane;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int ov = __shfl_xor(bv, o); const stat_t os = stat_xor(bs, o); const int ol = __shfl_xor(bl, o);
+            if (ov > bv || (ov == bv && ol < bl)) { bv = ov; bs = os; bl = ol; }
+        }
+        if (bv > g_best) { g_best = bv; g_stats = bs; }
+        __syncthreads();
+    }
+    return g_stats;
+}
+
 template <bool BIG>
 __global__ __launch_bounds__(64) void support_kernel(int32_t n_tasks,
                                                     const uint8_t* __restrict__ targets, const int64_t* __restrict__ t_off,
@@ -104,7 +178,6 @@ __global__ __launch_bounds__(64) void support_kernel(int32_t n_tasks,
 {
     typedef SwStat<BIG> St;
     typedef typename St::T stat_t;
-    constexpr stat_t kStAligned = St::kAligned, kStIndel = St::kIndel, kStSub = St::kSub;
     extern __shared__ __align__(16) unsigned char smem_raw[];
     SwRow<stat_t> s;
     if constexpr (BIG) {
@@ -138,67 +211,7 @@ __global__ __launch_bounds__(64) void support_kernel(int32_t n_tasks,
         }
         __syncthreads();
 
-        int g_best = 0; stat_t g_stats = 0;              // max_score starts at 0: an all-nonpositive matrix traces nothing
-        for (int i0 = 0; i0 < len2; i0 += 64) {
-            const int i = i0 + 1 + lane;                    // this lane's row (1-based)
-            const bool row_ok = i <= len2;
-            const uint32_t qc_raw = row_ok ? queries[qo + i - 1] : 0u;
-            const uint32_t qc = up8(qc_raw);
-            // own previous cell (i, j-1): column 0 to start with (1297-1303)
-            int v_left = -4 - i, e_left = 0; stat_t s_left = 0;
-            // what the lane below produced one and two steps ago
-            int v_out = 0, f_out = 0; stat_t s_out = 0;     // this lane's newest cell
-            int v_diag_in = -4 - (i - 1);                   // (i-1, 0)
-            stat_t s_diag_in = 0;
-            int best_v = 0; stat_t best_s = 0;
-            const int steps = len1 + 63;
-            for (int t = 0; t < steps; t++) {
-                // neighbours from the lane below: its newest cell is (i-1, j)
-                int v_up = sw_shr1(0, v_out), f_up = sw_shr1(0, f_out);
-                stat_t s_up = stat_shr1(s_out);
-                const int j = t - lane + 1;
-                if (lane == 0) {
-                    if (j >= 1 && j <= len1) {
-                        if (i0 == 0) { v_up = -4 - j; f_up = 0; s_up = 0; }          // row 0 (1301-1303), F zero-filled (1307)
-                        else { v_up = s.rowV[j]; f_up = s.rowF[j]; s_up = s.rowS[j]; }
-                    }
-                }
-                const bool act = row_ok && j >= 1 && j <= len1;
-                if (act) {
-                    const uint32_t tc_raw = s.t1[j - 1];
-                    const int sub = v_diag_in + ((up8(tc_raw) == qc) ? 2 : -1);
-                    const int ins = max(f_up, v_up - 4) - 1;
-                    const int del = max(e_left, v_left - 4) - 1;
-                    const int indel = max(ins, del);
-                    int v = sub;
-                    stat_t st = (v_diag_in > 0 ? s_diag_in : (stat_t)0) + kStAligned + ((tc_raw != qc_raw) ? kStSub : (stat_t)0);
-                    if (v < indel) {
-                        v = indel;
-                        if (ins >= del) st = (v_up > 0 ? s_up : (stat_t)0) + kStIndel + kStAligned;
-                        else            st = (v_left > 0 ? s_left : (stat_t)0) + kStIndel;
-                    }
-                    if (v > best_v) { best_v = v; best_s = st; }
-                    // becomes "left" for the next column and "up" for the lane above
-                    v_left = v; e_left = del; s_left = st;
-                    v_out = v; f_out = ins; s_out = st;
-                    if (lane == 63) { s.rowV[j] = v; s.rowF[j] = ins; s.rowS[j] = st; }
-                }
-                // the cell above-left of the next column is the cell above of this one
-                v_diag_in = (j >= 1 && j <= len1) ? v_up : v_diag_in;
-                s_diag_in = (j >= 1 && j <= len1) ? s_up : s_diag_in;
-                if (j == 0) { v_diag_in = -4 - (i - 1); s_diag_in = 0; }
-                if (lane == 0 && j >= 1 && j <= len1 && i0 > 0) { /* boundary row diag comes from LDS too */ }
-            }
-            // block maximum: larger score, then smaller row (rows ascend with the lane)
-            int bv = best_v; stat_t bs = best_s; int bl = lane;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const int ov = __shfl_xor(bv, o); const stat_t os = stat_xor(bs, o); const int ol = __shfl_xor(bl, o);
-                if (ov > bv || (ov == bv && ol < bl)) { bv = ov; bs = os; bl = ol; }
-            }
-            if (bv > g_best) { g_best = bv; g_stats = bs; }
-            __syncthreads();
-        }
+        const stat_t g_stats = sw_sweep<BIG>(s, queries + qo, len1, len2, lane);
         if (lane == 0) {
             out[4 * task]     = St::subs(g_stats);
             out[4 * task + 1] = St::indels(g_stats);
@@ -209,7 +222,158 @@ __global__ __launch_bounds__(64) void support_kernel(int32_t n_tasks,
     }
 }
 
+// ---- counting form (im_support_count): every read of every known variant, verdict on the device ----------------------------
+//
+// check_for_indel's rule (src/variant.c:1427-1556) applied to ALL overlapping reads of a known variant instead of up to the first
+// that passes.  A task names its variant and the clipped reference stretch [rstart, rstop) of its read; the window is never
+// built by the caller: the three pieces of the splice (1259-1272) are read from the resident reference and the ALT string,
+//     deletion   ref[rstart, start) + ref[stop-1, rstop)
+//     insertion  ref[rstart, start) + ALT[1..] + ref[start, rstop)
+// raw bytes, straight into LDS.  Same sweep, then the verdict (subs <= own, indels <= own, aligned >= own) and three integer adds
+// into the variant's counters {N_all, AS, DC}: the result does not depend on the order the tasks run in.
+
+struct Splice { int na, nm, nb, b_src; };      // bytes of ref[rstart..), of ALT[1..], of ref[b_src..)
+__host__ __device__ inline Splice splice_of(const im_known_variant& v, int rstart, int rstop)
+{
+    Splice p;
+    const int a_end = v.start < rstop ? v.start : rstop;
+    p.na = a_end > rstart ? a_end - rstart : 0;
+    if (v.type == IM_CLS_DELETION) {
+        p.nm = 0; p.b_src = v.stop - 1;
+        p.nb = (rstop > p.b_src && p.b_src >= 0) ? rstop - p.b_src : 0;
+    } else {
+        p.nm = v.alt_len > 1 ? v.alt_len - 1 : 0; p.b_src = a_end;
+        p.nb = rstop > a_end ? rstop - a_end : 0;
+    }
+    return p;
+}
+__device__ __forceinline__ uint8_t splice_byte(const Splice& p, const uint8_t* __restrict__ refc, const uint8_t* __restrict__ alt, int rstart, int64_t j)
+{
+    if (j < p.na) return refc[rstart + j];
+    j -= p.na;
+    if (j < p.nm) return alt[1 + j];
+    return refc[p.b_src + (j - p.nm)];
+}
+
+template <bool BIG>
+__device__ __forceinline__ void count_verdict(typename SwStat<BIG>::T st, const im_count_task& T, int32_t* __restrict__ counts, int lane, bool direct)
+{
+    typedef SwStat<BIG> St;
+    const bool ok = direct || (St::subs(st) <= T.own_subs && St::indels(st) <= T.own_indels && St::aligned(st) + 1 >= T.own_aligned);
+    if (ok && lane == 0) {
+        int32_t* c = counts + 3 * (size_t)T.variant;
+        atomicAdd(c, 1);
+        if (T.flags & IM_SC_MAPQ_OK) {
+            atomicAdd(c + 1, 1);
+            if (T.flags & IM_SC_SPANS) atomicAdd(c + 2, 1);
+        }
+    }
+}
+
+// LDS form: one wave per task; DIRECT tasks are counted without a sweep, tasks beyond the LDS form are left to the second launch
+__global__ __launch_bounds__(64) void support_count_kernel(int32_t n_tasks, const im_count_task* __restrict__ tasks,
+                                                          const im_known_variant* __restrict__ vars, const uint8_t* __restrict__ alts,
+                                                          RefDev ref, const uint8_t* __restrict__ queries, int32_t* __restrict__ counts, int cap)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const SwRow<uint32_t> s = sw_carve(smem_raw, cap);
+    const int lane = threadIdx.x;
+    for (int task = blockIdx.x; task < n_tasks; task += gridDim.x) {
+        const im_count_task T = tasks[task];
+        if (T.flags & IM_SC_DIRECT) { count_verdict<false>(0u, T, counts, lane, true); continue; }
+        const im_known_variant V = vars[T.variant];
+        const Splice p = splice_of(V, T.rstart, T.rstop);
+        const int64_t l1 = (int64_t)p.na + p.nm + p.nb;
+        if (l1 > kSwMaxTarget || T.q_len > IM_MAX_READ || l1 >= cap) continue;
+        const int len1 = (int)l1;
+        const uint8_t* refc = ref.ascii + ref.asc_off[V.tid];
+        const uint8_t* alt = alts + V.alt_off;
+        for (int j = lane; j < len1; j += 64) smem_raw[j] = splice_byte(p, refc, alt, T.rstart, j);
+        __syncthreads();
+        const uint32_t st = sw_sweep<false>(s, queries + T.q_off, len1, T.q_len, lane);
+        count_verdict<false>(st, T, counts, lane, false);
+        __syncthreads();
+    }
+}
+
+// the tasks beyond the LDS form: their windows written out once ...
+__global__ __launch_bounds__(256) void support_splice_kernel(int32_t n_big, const int32_t* __restrict__ big_idx, const int64_t* __restrict__ big_toff,
+                                                            const im_count_task* __restrict__ tasks, const im_known_variant* __restrict__ vars,
+                                                            const uint8_t* __restrict__ alts, RefDev ref, uint8_t* __restrict__ win)
+{
+    for (int b = blockIdx.x; b < n_big; b += gridDim.x) {
+        const im_count_task T = tasks[big_idx[b]];
+        const im_known_variant V = vars[T.variant];
+        const Splice p = splice_of(V, T.rstart, T.rstop);
+        const int64_t l1 = (int64_t)p.na + p.nm + p.nb, to = big_toff[b];
+        if (l1 != big_toff[b + 1] - to) continue;           // the host sized the stretch with the same splice_of
+        const uint8_t* refc = ref.ascii + ref.asc_off[V.tid];
+        const uint8_t* alt = alts + V.alt_off;
+        for (int64_t j = threadIdx.x; j < l1; j += 256) win[to + j] = splice_byte(p, refc, alt, T.rstart, j);
+    }
+}
+// ... and swept with the boundary row in device memory, as support_kernel<true> does
+__global__ __launch_bounds__(64) void support_count_big_kernel(int32_t n_big, const int32_t* __restrict__ big_idx, const int64_t* __restrict__ big_toff,
+                                                              const uint8_t* __restrict__ win, const im_count_task* __restrict__ tasks,
+                                                              const uint8_t* __restrict__ queries, int32_t* __restrict__ counts, int cap,
+                                                              unsigned char* __restrict__ big_rows)
+{
+    SwRow<uint64_t> s;
+    unsigned char* mine = big_rows + (size_t)blockIdx.x * sw_big_row_bytes(cap);
+    s.rowS = reinterpret_cast<uint64_t*>(mine);
+    s.rowV = reinterpret_cast<int32_t*>(mine + (size_t)cap * 8);
+    s.rowF = s.rowV + cap;
+    const int lane = threadIdx.x;
+    for (int b = blockIdx.x; b < n_big; b += gridDim.x) {
+        const im_count_task T = tasks[big_idx[b]];
+        const int64_t to = big_toff[b], l1 = big_toff[b + 1] - to;
+        if (l1 < 0 || l1 >= cap || T.q_len < 0 || T.q_len > kSwBigMaxQuery) continue;      // im_support_count has refused such a batch
+        s.t1 = win + to;
+        const uint64_t st = sw_sweep<true>(s, queries + T.q_off, (int)l1, T.q_len, lane);
+        count_verdict<true>(st, T, counts, lane, false);
+        __syncthreads();
+    }
+}
+
 }  // namespace
+
+int64_t support_count_window(const im_known_variant& v, int32_t rstart, int32_t rstop)
+{
+    const Splice p = splice_of(v, rstart, rstop);
+    return (int64_t)p.na + p.nm + p.nb;
+}
+bool support_count_is_big(int64_t window, int64_t query) { return window > kSwMaxTarget || query > IM_MAX_READ; }
+int64_t support_count_max_query() { return kSwBigMaxQuery; }
+
+hipError_t launch_support_count(int32_t n_tasks, const im_count_task* tasks, const im_known_variant* vars, const uint8_t* alts, const RefDev& ref,
+                                const uint8_t* queries, int32_t* counts, int64_t max_short_target,
+                                int32_t n_big, const int32_t* big_idx, const int64_t* big_toff, uint8_t* big_win, int64_t max_big_target,
+                                void* big_scratch, int32_t big_grid, bool* attr_set, hipStream_t stream)
+{
+    if (n_tasks <= 0) return hipSuccess;
+    if (max_short_target < 0) max_short_target = 0;
+    if (max_short_target > kSwMaxTarget) return hipErrorInvalidValue;
+    const int cap = (int)((max_short_target + 1 + 3) & ~(int64_t)3);
+    const size_t lds = sw_lds_bytes(cap);
+    if (!*attr_set) {                       // once per context (the caller keeps the flag), for the largest LDS form
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(support_count_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sw_lds_bytes((kSwMaxTarget + 4) & ~3));
+        if (e != hipSuccess) return e;
+        *attr_set = true;
+    }
+    const int grid = n_tasks < (1 << 20) ? n_tasks : (1 << 20);
+    hipLaunchKernelGGL(support_count_kernel, dim3(grid), dim3(64), lds, stream, n_tasks, tasks, vars, alts, ref, queries, counts, cap);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || n_big <= 0) return e;
+    if (big_grid <= 0 || max_big_target >= 0x7ffffff0LL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(support_splice_kernel, dim3(n_big < 4096 ? n_big : 4096), dim3(256), 0, stream, n_big, big_idx, big_toff, tasks, vars, alts, ref, big_win);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int big_cap = (int)((max_big_target + 1 + 3) & ~(int64_t)3);
+    hipLaunchKernelGGL(support_count_big_kernel, dim3(big_grid), dim3(64), 0, stream, n_big, big_idx, big_toff, big_win, tasks, queries, counts, big_cap,
+                       static_cast<unsigned char*>(big_scratch));
+    return hipGetLastError();
+}
 
 size_t support_big_scratch_bytes(int64_t max_target, int64_t max_query, int32_t n_tasks, int32_t* grid_out)
 {

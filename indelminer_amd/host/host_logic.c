@@ -917,14 +917,9 @@ static void vcf_coordinates(const variant_t* v, int* pos, int* endpos, int* bp_e
  * the indel) in 64-bit integers, thousandths of a phred: a read of the wrong allele costs E (error 0.01), a read of the right one
  * C, either read under a heterozygote H.  GT = the cheapest of 0/0, 0/1, 1/1 (the lower index wins a tie), GQ = the distance to
  * the second cheapest, rounded to whole phreds, at most 99.  No reference counterpart. */
-static void print_genotype(const variant_t* v)
+static void genotype_of(int64_t rs, int64_t ns, int* best_out, int* gq_out)
 {
-    if (v->evdnctype == EV_PAIRED_READ || !v->rs_valid) {           /* no precise breakpoint to count spanning reads at */
-        printf("\tGT:AD:GQ\t./.:.,%u:.", v->support);
-        return;
-    }
     const int64_t E = 20000, C = 44, H = 3010;
-    const int64_t ns = (int64_t)v->support, rs = (int64_t)v->rs_cached;
     int64_t L[3] = { ns * E + rs * C, (ns + rs) * H, ns * C + rs * E };
     int best = 0;
     for (int g = 1; g < 3; g++) if (L[g] < L[best]) best = g;
@@ -932,7 +927,17 @@ static void print_genotype(const variant_t* v)
     for (int g = 0; g < 3; g++) if (g != best && (second < 0 || L[g] - L[best] < second)) second = L[g] - L[best];
     int64_t gq = (second + 500) / 1000;
     if (gq > 99) gq = 99;
-    printf("\tGT:AD:GQ\t%s:%u,%u:%d", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", v->rs_cached, v->support, (int)gq);
+    *best_out = best; *gq_out = (int)gq;
+}
+static void print_genotype(const variant_t* v)
+{
+    if (v->evdnctype == EV_PAIRED_READ || !v->rs_valid) {           /* no precise breakpoint to count spanning reads at */
+        printf("\tGT:AD:GQ\t./.:.,%u:.", v->support);
+        return;
+    }
+    int best, gq;
+    genotype_of((int64_t)v->rs_cached, (int64_t)v->support, &best, &gq);
+    printf("\tGT:AD:GQ\t%s:%u,%u:%d", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", v->rs_cached, v->support, gq);
 }
 
 /* print_vcf_output (src/variant.c:115-311) */
@@ -1429,9 +1434,15 @@ typedef struct {
     uint32_t support, stop, bpstop;
     char*    addntlinfo;
     int      diffsample_support;
+    /* -A (known_counts_run): supporting reads, those of them with mapping quality >= -q, those of them the span array has
+     * counted for the reference; the first read the reference would die on, if it got that far */
+    int32_t  n_all, n_as, n_dc;
+    int32_t  n_before_fatal;        /* supporting reads in front of that read */
+    char*    fatal_msg; int fatal_is_assert;
+    uint32_t rs; int rs_valid;      /* span minimum over [POS, POS + (BP_END - END)], as queried for the print call */
 } knownvariant_t;
 
-typedef struct { knownvariant_t** v; int n, cap; int next; } known_list;
+typedef struct { knownvariant_t** v; int n, cap; int next; int counted; } known_list;
 
 static const char* g_vcfname = NULL;
 static const char* g_sample_name = NULL;
@@ -1441,7 +1452,7 @@ static void read_variants(const char* vcfname, int32_t tid, const char* chromnam
 {
     size_t cap = 2;
     char* line = xmalloc(cap);
-    out->n = 0; out->next = 0;
+    out->n = 0; out->next = 0; out->counted = 0;
     FILE* fp = fopen(vcfname, "r");
     if (!fp) fatalf("error in opening the file %s", vcfname);
     const size_t big = (size_t)O.maxpedelsize + 16;
@@ -1485,7 +1496,7 @@ static void read_variants(const char* vcfname, int32_t tid, const char* chromnam
 
 static void known_free(known_list* l)
 {
-    for (int i = 0; i < l->n; i++) { free(l->v[i]->reference); free(l->v[i]->alternate); free(l->v[i]->addntlinfo); free(l->v[i]); }
+    for (int i = 0; i < l->n; i++) { free(l->v[i]->reference); free(l->v[i]->alternate); free(l->v[i]->addntlinfo); free(l->v[i]->fatal_msg); free(l->v[i]); }
     l->n = 0; l->next = 0;
 }
 
@@ -1498,6 +1509,69 @@ static void print_vcf_line(const driver* d, const knownvariant_t* k)
     else if (k->evdnctype == EV_PAIRED_READ) printf("PAIRED_READ;");
     else if (k->evdnctype == EV_COMPOSITE) printf("COMPOSITE;");
     printf("NS=%d;END=%d;BP_END=%d;%s", (int)k->support, (int)k->stop, (int)k->bpstop, k->addntlinfo);
+}
+
+/* What check_for_indel's bookkeeping (src/variant.c:1427-1556) makes of one read against one known variant: nothing (KR_SKIP),
+ * a supporter by its CIGAR alone (KR_DIRECT), a Smith-Waterman task (KR_ALIGN: the clipped reference stretch, the query and the
+ * read's own counts), or a read the reference dies on (KR_FATAL).  defer = 0 dies there and then, as the early-exit loop does;
+ * defer = 1 (-A visits every read) hands the message back: whether it is fatal depends on the reads in front. */
+enum { KR_SKIP = 0, KR_DIRECT, KR_ALIGN, KR_FATAL };
+typedef struct { int rstart, rstop, qstart, qlen, subs, indels, aligned; char msg[256]; int is_assert; } known_read;
+#define KR_ASSERT(e) do { if (!(e)) { if (!defer) forceassert(e); \
+        snprintf(out->msg, sizeof out->msg, "Assertion failed: %s file %s line %d", #e, __FILE__, __LINE__); out->is_assert = 1; return KR_FATAL; } } while (0)
+static int known_read_task(const knownvariant_t* k, const bam_record* b, const seglist* rln, const char* seq, int64_t seqlen, int defer, known_read* out)
+{
+    int aln1subs = 0, aln1indels = 0, aln1aligned = 0, overlaps = 0, qstart = -1, qstop = -1, readindx = 0;
+    int refpos = rln->ref_start;
+    for (int sgi = 0; sgi < rln->n; sgi++) {
+        const int op = CIG_OP(rln->ops[sgi]), len = CIG_LEN(rln->ops[sgi]);
+        const int sstart = refpos;
+        const int send = (op == OP_M || op == OP_EQ || op == OP_X || op == OP_D) ? refpos + len : refpos;
+        if (!(send < (int)k->start || sstart > (int)k->stop)) overlaps = 1;
+        switch (op) {
+        case OP_S:
+            if (sgi == rln->n - 1) qstop = readindx;
+            readindx += len;
+            break;
+        case OP_I:
+            if (qstart == -1) qstart = readindx;
+            if (k->type == CLS_INSERTION && sstart == (int)k->start) return KR_DIRECT;
+            readindx += len; aln1indels += len; aln1aligned += len;
+            break;
+        case OP_D:
+            if (k->type == CLS_DELETION && sstart == (int)k->start && send == (int)k->stop - 1) return KR_DIRECT;
+            aln1indels += len;
+            break;
+        case OP_M:
+            if (qstart == -1) qstart = readindx;
+            for (int i = 0, j = sstart; i < len; i++, j++) if (rln->bases[readindx + i] != seq[j]) aln1subs++;
+            readindx += len; aln1aligned += len;
+            break;
+        default:
+            if (!defer) fatalf("Unhandled CIGAR op: %d", op);
+            snprintf(out->msg, sizeof out->msg, "Unhandled CIGAR op: %d", op); out->is_assert = 0;
+            return KR_FATAL;
+        }
+        refpos = send;
+    }
+    if (qstop == -1) qstop = aln1aligned + qstart;
+    KR_ASSERT(aln1aligned == (qstop - qstart));
+    if (!overlaps) return KR_SKIP;
+    const int indelsize = abs((int)strlen(k->alternate) - (int)strlen(k->reference));
+    int rstart = b->pos, rstop = bam_record_end(b);
+    if ((uint32_t)rstop < k->bpstop) return KR_SKIP;
+    KR_ASSERT(qstart != -1 && qstop != -1);
+    rstart -= indelsize; rstop += indelsize;
+    /* the fake reference with the variant in it (1259-1272); reads beyond the contig's ends
+     * stop at its terminator there, here they are clipped */
+    if (rstart < 0) rstart = 0;
+    if (rstop > seqlen) rstop = (int)seqlen;
+    /* query = read[qstart, qstop) of the record's stored bases */
+    int qlen = qstop - qstart;
+    if ((int)strlen(rln->bases + qstart) < qlen) qlen = (int)strlen(rln->bases + qstart);
+    out->rstart = rstart; out->rstop = rstop; out->qstart = qstart; out->qlen = qlen;
+    out->subs = aln1subs; out->indels = aln1indels; out->aligned = aln1aligned;
+    return KR_ALIGN;
 }
 
 /* is_indel_supported (src/variant.c:1561-1573) = check_for_indel (1427-1556) over the reads that
@@ -1521,50 +1595,11 @@ static int is_indel_supported(driver* d, knownvariant_t* k)
             if (b.flag & 0x4) continue;
             if (b.flag & (0x100 | 0x200 | 0x400 | 0x800)) continue;
             seglist rln = seglist_from_record(&b);
-            int aln1subs = 0, aln1indels = 0, aln1aligned = 0, overlaps = 0, qstart = -1, qstop = -1, readindx = 0;
-            int refpos = rln.ref_start, done = 0;
-            for (int sgi = 0; sgi < rln.n && !done; sgi++) {
-                const int op = CIG_OP(rln.ops[sgi]), len = CIG_LEN(rln.ops[sgi]);
-                const int sstart = refpos;
-                const int send = (op == OP_M || op == OP_EQ || op == OP_X || op == OP_D) ? refpos + len : refpos;
-                if (!(send < (int)k->start || sstart > (int)k->stop)) overlaps = 1;
-                switch (op) {
-                case OP_S:
-                    if (sgi == rln.n - 1) qstop = readindx;
-                    readindx += len;
-                    break;
-                case OP_I:
-                    if (qstart == -1) qstart = readindx;
-                    if (k->type == CLS_INSERTION && sstart == (int)k->start) { k->diffsample_support = 1; done = 1; break; }
-                    readindx += len; aln1indels += len; aln1aligned += len;
-                    break;
-                case OP_D:
-                    if (k->type == CLS_DELETION && sstart == (int)k->start && send == (int)k->stop - 1) { k->diffsample_support = 1; done = 1; break; }
-                    aln1indels += len;
-                    break;
-                case OP_M:
-                    if (qstart == -1) qstart = readindx;
-                    for (int i = 0, j = sstart; i < len; i++, j++) if (rln.bases[readindx + i] != seq[j]) aln1subs++;
-                    readindx += len; aln1aligned += len;
-                    break;
-                default:
-                    fatalf("Unhandled CIGAR op: %d", op);
-                }
-                refpos = send;
-            }
-            if (done) { seglist_free(&rln); break; }
-            if (qstop == -1) qstop = aln1aligned + qstart;
-            forceassert(aln1aligned == (qstop - qstart));
-            if (!overlaps) { seglist_free(&rln); continue; }
-            const int indelsize = abs((int)strlen(k->alternate) - (int)strlen(k->reference));
-            int rstart = b.pos, rstop = bam_record_end(&b);
-            if ((uint32_t)rstop < k->bpstop) { seglist_free(&rln); continue; }
-            forceassert(qstart != -1 && qstop != -1);
-            rstart -= indelsize; rstop += indelsize;
-            /* the fake reference with the variant in it (1259-1272); reads beyond the contig's ends
-             * stop at its terminator there, here they are clipped */
-            if (rstart < 0) rstart = 0;
-            if (rstop > seqlen) rstop = (int)seqlen;
+            known_read kr;
+            const int kind = known_read_task(k, &b, &rln, seq, seqlen, 0, &kr);
+            if (kind == KR_DIRECT) { k->diffsample_support = 1; seglist_free(&rln); break; }
+            if (kind == KR_SKIP) { seglist_free(&rln); continue; }
+            const int rstart = kr.rstart, rstop = kr.rstop;
             const size_t alen = strlen(k->alternate);
             size_t need = (size_t)(rstop - rstart) + alen + 8;
             if (tg_len + need > tg_cap) { tg_cap = (tg_cap + need) * 2; tg = xrealloc(tg, tg_cap); }
@@ -1583,14 +1618,12 @@ static int is_indel_supported(driver* d, knownvariant_t* k)
                 if (alen > 1) { memcpy(t + tl, k->alternate + 1, alen - 1); tl += alen - 1; }
                 if (rstop > a_end) { memcpy(t + tl, seq + a_end, (size_t)(rstop - a_end)); tl += (size_t)(rstop - a_end); }
             }
-            /* query = read[qstart, qstop) of the record's stored bases */
-            int qlen = qstop - qstart;
-            if ((int)strlen(rln.bases + qstart) < qlen) qlen = (int)strlen(rln.bases + qstart);
+            const int qlen = kr.qlen;
             if (qs_len + (size_t)qlen + 8 > qs_cap) { qs_cap = (qs_cap + (size_t)qlen + 8) * 2; qs = xrealloc(qs, qs_cap); }
-            memcpy(qs + qs_len, rln.bases + qstart, (size_t)qlen);
+            memcpy(qs + qs_len, rln.bases + kr.qstart, (size_t)qlen);
             if (nt + 2 > capt) { capt = capt ? capt * 2 : 64; to = xrealloc(to, sizeof(int64_t) * (size_t)(capt + 1)); qo = xrealloc(qo, sizeof(int64_t) * (size_t)(capt + 1)); own = xrealloc(own, sizeof(int32_t) * 3 * (size_t)capt); }
             to[nt] = (int64_t)tg_len; qo[nt] = (int64_t)qs_len;
-            own[3 * nt] = aln1subs; own[3 * nt + 1] = aln1indels; own[3 * nt + 2] = aln1aligned;
+            own[3 * nt] = kr.subs; own[3 * nt + 1] = kr.indels; own[3 * nt + 2] = kr.aligned;
             tg_len += tl; qs_len += (size_t)qlen; nt++;
             to[nt] = (int64_t)tg_len; qo[nt] = (int64_t)qs_len;
             seglist_free(&rln);
@@ -1616,54 +1649,278 @@ static int is_indel_supported(driver* d, knownvariant_t* k)
     return k->diffsample_support;
 }
 
+/* ---- -A: read counts for and against every known indel (no reference counterpart) ---------------------------
+ * known_counts_run: once per contig, before its first known variant is printed.  Every read bam_region_begin(tid, start, stop)
+ * delivers for a SPLIT_READ or COMPOSITE variant goes through known_read_task; the tasks of all variants travel to the device in
+ * bounded batches (im_support_count), which answers {N_all, AS, DC} per variant.  A read the reference would die on splits its
+ * variant's tasks in two counter slots, in front of it and behind: it is fatal only if nothing in front supported (known_die_if). */
+#define KNOWN_BATCH_TASKS 32768
+typedef struct {
+    im_known_variant* kv; int* slot_ki; int* slot_front; int nv, capv;
+    im_count_task* tk; int nt, capt;
+    uint8_t* qs; size_t qs_len, qs_cap;
+    uint8_t* alts; size_t alt_len, alt_cap;
+} known_batch;
+
+static void known_batch_send(driver* d, known_list* kl, known_batch* B)
+{
+    if (B->nv == 0) return;
+    int32_t* counts = xmalloc(sizeof(int32_t) * 3 * (size_t)B->nv);
+    gpu_wait(d);
+    const int64_t t0 = wall_ns();
+    pthread_mutex_lock(&g_query_mu);
+    const int rc = im_support_count(d->gpu, B->nv, B->kv, B->alts, (int64_t)B->alt_len, B->nt, B->tk, B->qs, (int64_t)B->qs_len, counts);
+    pthread_mutex_unlock(&g_query_mu);
+    if (rc != IM_OK) fatalf("im_support_count: %s", im_last_error(d->gpu));
+    if (g_timing) { g_kc_ns += wall_ns() - t0; g_kc_calls++; g_kc_tasks += B->nt; for (int i = 0; i < B->nt; i++) g_kc_direct += (B->tk[i].flags & IM_SC_DIRECT) != 0; }
+    for (int s = 0; s < B->nv; s++) {
+        knownvariant_t* k = kl->v[B->slot_ki[s]];
+        k->n_all += counts[3 * s]; k->n_as += counts[3 * s + 1]; k->n_dc += counts[3 * s + 2];
+        if (B->slot_front[s]) k->n_before_fatal += counts[3 * s];
+    }
+    free(counts);
+    B->nv = 0; B->nt = 0; B->qs_len = 0; B->alt_len = 0;
+}
+
+/* eligible by -G's span rule apart from the mapping quality (the caller has that), with one M/=/X run [s, e) clipped to the
+ * contig that the span array has counted at every position of [b0, b1]: s <= b0 - m and b1 + m <= e */
+static int read_spans_interval(const seglist* rln, int64_t seqlen, int64_t b0, int64_t b1, int64_t m)
+{
+    int64_t x = rln->ref_start, rs = 0;
+    int in_run = 0;
+    for (int kk = 0; kk <= rln->n; kk++) {
+        const int op = kk < rln->n ? CIG_OP(rln->ops[kk]) : OP_S, len = kk < rln->n ? CIG_LEN(rln->ops[kk]) : 0;
+        if (op == OP_M || op == OP_EQ || op == OP_X) { if (!in_run) { rs = x; in_run = 1; } x += len; continue; }
+        if (in_run) {
+            const int64_t a = rs < 0 ? 0 : rs, e = x > seqlen ? seqlen : x;
+            if (e - a >= 2 * m && a <= b0 - m && b1 + m <= e) return 1;
+            in_run = 0;
+        }
+        if (op == OP_D || op == OP_N) x += len;
+    }
+    return 0;
+}
+
+static void known_counts_run(driver* d, known_list* kl)
+{
+    if (kl->counted) return;
+    kl->counted = 1;
+    const int64_t t0 = wall_ns();
+    bgzf_reader* r = bgzf_open(d->bam_name);
+    if (!r) fatalf("error in opening the file %s", d->bam_name);
+    bam_header* h = bam_header_load(r);
+    bam_record b; memset(&b, 0, sizeof b);
+    known_batch B; memset(&B, 0, sizeof B);
+    for (int ki = 0; h && ki < kl->n; ki++) {
+        knownvariant_t* k = kl->v[ki];
+        if (k->evdnctype != EV_SPLIT_READ && k->evdnctype != EV_COMPOSITE) continue;
+        const char* seq = d->sequences[k->tid];
+        const int64_t seqlen = d->seqlen[k->tid];
+        const int64_t b0 = k->start, b1 = k->bpstop >= k->stop ? (int64_t)k->start + (k->bpstop - k->stop) : b0;
+        bam_region_iter it;
+        if (bam_region_begin(&it, r, d->idx, k->tid, (int32_t)k->start, (int32_t)k->stop) != 0) continue;
+        int slot = -1, front = 1;
+        while (bam_region_next(&it, &b) == 1) {
+            if (b.flag & 0x4) continue;
+            if (b.flag & (0x100 | 0x200 | 0x400 | 0x800)) continue;
+            /* new_readaln's own refusals (check_like_new_readaln) come before the bookkeeping, deferred like its */
+            const char* refused = NULL;
+            for (int ci = 0; ci < b.n_cigar && !refused; ci++) {
+                const int op = CIG_OP(bamr_cigar_at(BAMR_CIGAR(&b), ci));
+                refused = op == OP_N ? "Implement new_readseg_bam:164" : op == OP_H ? "Implement new_readseg_bam:176" : op == OP_P ? "Implement new_readseg_bam:179" :
+                          op > OP_X ? "Unhandled cigar operation" : NULL;
+            }
+            if (refused) {
+                if (!k->fatal_msg) { k->fatal_msg = xstrdup(refused); k->fatal_is_assert = 0; front = 0; slot = -1; }
+                continue;
+            }
+            seglist rln = seglist_from_record(&b);
+            known_read kr;
+            const int kind = known_read_task(k, &b, &rln, seq, seqlen, 1, &kr);
+            if (kind == KR_SKIP) { seglist_free(&rln); continue; }
+            if (kind == KR_FATAL) {
+                /* the first such read decides; the ones behind it are left out of the counts like it */
+                if (!k->fatal_msg) { k->fatal_msg = xstrdup(kr.msg); k->fatal_is_assert = kr.is_assert; front = 0; slot = -1; }
+                seglist_free(&rln); continue;
+            }
+            if (slot < 0) {
+                if (B.nv == B.capv) {
+                    B.capv = B.capv ? B.capv * 2 : 256;
+                    B.kv = xrealloc(B.kv, sizeof(im_known_variant) * (size_t)B.capv);
+                    B.slot_ki = xrealloc(B.slot_ki, sizeof(int) * (size_t)B.capv); B.slot_front = xrealloc(B.slot_front, sizeof(int) * (size_t)B.capv);
+                }
+                const size_t alen = strlen(k->alternate);
+                if (B.alt_len + alen + 8 > B.alt_cap) { B.alt_cap = (B.alt_cap + alen + 8) * 2; B.alts = xrealloc(B.alts, B.alt_cap); }
+                memcpy(B.alts + B.alt_len, k->alternate, alen);
+                slot = B.nv++;
+                B.kv[slot] = (im_known_variant){ k->tid, (int32_t)k->start, (int32_t)k->stop, k->type == CLS_DELETION ? IM_CLS_DELETION : IM_CLS_INSERTION, (int32_t)B.alt_len, (int32_t)alen };
+                B.slot_ki[slot] = ki; B.slot_front[slot] = front;
+                B.alt_len += alen;
+            }
+            if (B.nt == B.capt) { B.capt = B.capt ? B.capt * 2 : 4096; B.tk = xrealloc(B.tk, sizeof(im_count_task) * (size_t)B.capt); }
+            im_count_task* T = &B.tk[B.nt++];
+            memset(T, 0, sizeof *T);
+            T->variant = slot;
+            if ((int)b.mapq >= O.qthreshold) {
+                T->flags |= IM_SC_MAPQ_OK;
+                if (b.tid >= 0 && read_spans_interval(&rln, seqlen, b0, b1, (int64_t)O.ethreshold)) T->flags |= IM_SC_SPANS;
+            }
+            if (kind == KR_DIRECT) T->flags |= IM_SC_DIRECT;
+            else {
+                if (B.qs_len + (size_t)kr.qlen + 8 > B.qs_cap) { B.qs_cap = (B.qs_cap + (size_t)kr.qlen + 8) * 2; B.qs = xrealloc(B.qs, B.qs_cap); }
+                memcpy(B.qs + B.qs_len, rln.bases + kr.qstart, (size_t)kr.qlen);
+                T->rstart = kr.rstart; T->rstop = kr.rstop; T->q_off = (int32_t)B.qs_len; T->q_len = kr.qlen;
+                T->own_subs = kr.subs; T->own_indels = kr.indels; T->own_aligned = kr.aligned;
+                B.qs_len += (size_t)kr.qlen;
+            }
+            seglist_free(&rln);
+            if (B.nt >= KNOWN_BATCH_TASKS || B.qs_len > ((size_t)1 << 30)) { known_batch_send(d, kl, &B); slot = -1; }
+        }
+    }
+    free(b.data);
+    if (h) bam_header_free(h);
+    bgzf_close(r);
+    known_batch_send(d, kl, &B);
+    if (g_timing) g_kc_wall_ns += wall_ns() - t0;       /* region fetches + bookkeeping + the calls */
+    free(B.kv); free(B.slot_ki); free(B.slot_front); free(B.tk); free(B.qs); free(B.alts);
+}
+
+/* the discovered variant that re-finds a known one (src/variant.c:1590-1655); *ui_out == vars->n: none overlaps the rule */
+static int known_match(const knownvariant_t* k, const variant_list* vars, int* ui_out)
+{
+    int is_found = 0;
+    const uint32_t kstart = k->start, kstop = k->stop;
+    int ui;
+    for (ui = 0; ui < vars->n; ui++) {
+        const variant_t* u = vars->v[ui];
+        const uint32_t ustart = u->start - u->lw;
+        uint32_t ustop = 0;
+        const int reflength = (int)(u->stop + u->rw) - (int)(u->start - u->lw - 1);
+        forceassert(reflength >= 1);
+        if (u->type == CLS_DELETION) {
+            const int altlength = (int)(u->start + u->rw) - (int)(u->start - u->lw - 1);
+            forceassert(altlength >= 1);
+            ustop = u->start - u->lw + (uint32_t)reflength - (uint32_t)altlength + 1;
+        } else if (u->type == CLS_INSERTION) ustop = ustart + 1;
+        forceassert(ustop != 0);
+        if (kstart >= ustop) { }
+        else if (ustart >= kstop) { }
+        else {
+            if ((k->evdnctype == EV_SPLIT_READ || k->evdnctype == EV_COMPOSITE) && u->evdnctype == EV_SPLIT_READ) {
+                if (kstart == ustart && kstop == ustop) { is_found = 1; break; }
+            } else if (((k->evdnctype == EV_SPLIT_READ || k->evdnctype == EV_COMPOSITE) && u->evdnctype == EV_PAIRED_READ) ||
+                       (k->evdnctype == EV_PAIRED_READ && u->evdnctype == EV_SPLIT_READ) ||
+                       (k->evdnctype == EV_PAIRED_READ && u->evdnctype == EV_PAIRED_READ)) {
+                const uint32_t sx = k->start > u->start ? k->start : u->start;
+                const uint32_t ex = k->bpstop < u->stop ? k->bpstop : u->stop;
+                uint32_t olap = 0;
+                if (ex >= sx) olap = ex - sx;
+                if ((olap * 100.00 / (k->bpstop - k->start)) > 50) { is_found = 1; break; }
+            }
+        }
+    }
+    *ui_out = ui;
+    return is_found;
+}
+
+/* -A: the sample column of a known variant.  RS = the thinnest reference-spanning depth over [POS, POS + (BP_END - END)] less the
+ * supporting reads that array has counted at every position of it (DC); AS = the supporting reads with mapping quality >= -q;
+ * GT and GQ from (RS, AS) by print_genotype's rule. */
+static void print_known_genotype(const knownvariant_t* k)
+{
+    if (k->evdnctype == EV_PAIRED_READ) { printf("\tGT:AD:GQ\t./.:.,.:."); return; }     /* no precise breakpoint */
+    int64_t rs = k->rs_valid ? (int64_t)k->rs : 0;
+    /* a DC read adds one at every position of the interval, so the minimum holds them all -- where the walk has delivered them:
+     * a region run (-c) scatters the records of its stretch only */
+    if (O.region != NULL && rs < k->n_dc) rs = k->n_dc;
+    forceassert(rs >= k->n_dc);
+    rs -= k->n_dc;
+    if (rs + k->n_as == 0) { printf("\tGT:AD:GQ\t./.:0,0:."); return; }
+    int best, gq;
+    genotype_of(rs, (int64_t)k->n_as, &best, &gq);
+    printf("\tGT:AD:GQ\t%s:%d,%d:%d", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", (int)rs, (int)k->n_as, gq);
+}
+
+/* -A: known variants [from, to) of the list go out; found[ki - from] says which of them the discovery pass re-found (NULL: none).
+ * Their span minima travel as one query.  A read the reference dies on ends the run where the reference would have met it: the
+ * variant was not re-found and no read in front of that one supports it (is_indel_supported stops at the first that does). */
+static void print_known_counted(driver* d, known_list* kl, int from, int to, const uint8_t* found)
+{
+    if (to <= from) return;
+    known_counts_run(d, kl);
+    const int n = to - from;
+    int32_t* beg = xmalloc(sizeof(int32_t) * (size_t)n);
+    int32_t* end = xmalloc(sizeof(int32_t) * (size_t)n);
+    uint32_t* rs = xmalloc(sizeof(uint32_t) * (size_t)n);
+    int* who = xmalloc(sizeof(int) * (size_t)n);
+    int m = 0;
+    for (int ki = from; ki < to; ki++) {
+        knownvariant_t* k = kl->v[ki];
+        k->rs_valid = 0;
+        if (k->evdnctype != EV_SPLIT_READ && k->evdnctype != EV_COMPOSITE) continue;
+        beg[m] = (int32_t)k->start; end[m] = (int32_t)(k->bpstop >= k->stop ? k->start + (k->bpstop - k->stop) : k->start); who[m] = ki; m++;
+    }
+    if (m > 0) {
+        gpu_wait(d);
+        pthread_mutex_lock(&g_query_mu);
+        const int qrc = d->pipe_mode ? im_span_query_tid(d->gpu, kl->v[who[0]]->tid, m, beg, end, rs) : im_span_query(d->gpu, m, beg, end, rs);
+        pthread_mutex_unlock(&g_query_mu);
+        if (qrc != IM_OK) fatalf("im_span_query: %s", im_last_error(d->gpu));
+        for (int q = 0; q < m; q++) { kl->v[who[q]]->rs = rs[q]; kl->v[who[q]]->rs_valid = 1; }
+    }
+    free(beg); free(end); free(rs); free(who);
+    for (int ki = from; ki < to; ki++) {
+        knownvariant_t* k = kl->v[ki];
+        const int is_found = found ? found[ki - from] : 0;
+        print_vcf_line(d, k);
+        if (!is_found && k->evdnctype == EV_SPLIT_READ && k->fatal_msg && k->n_before_fatal == 0) {
+            if (!k->fatal_is_assert) fatalf("%s", k->fatal_msg);
+            walker_bails_out(); end_lock(); out_flush_on_exit();
+            fprintf(stderr, "%s\n", k->fatal_msg);
+            exit(EXIT_FAILURE);
+        }
+        if (is_found || (k->evdnctype == EV_SPLIT_READ && k->n_all > 0)) printf(";%s", g_sample_name);
+        print_known_genotype(k);
+        printf("\n");
+    }
+}
+
+/* what print_knownvariants left over at the end of a contig (src/indelminer.c:839-847) */
+static void print_known_rest(driver* d, known_list* kl)
+{
+    if (g_known_counts) print_known_counted(d, kl, kl->next, kl->n, NULL);
+    else
+        for (int ki = kl->next; ki < kl->n; ki++) {
+            knownvariant_t* k = kl->v[ki];
+            print_vcf_line(d, k);
+            if (k->evdnctype == EV_SPLIT_READ && is_indel_supported(d, k)) printf(";%s", g_sample_name);
+            printf("\n");
+        }
+    kl->next = kl->n;
+}
+
 /* print_knownvariants (src/variant.c:1577-1692): known variants from kl->next on; stops at the
  * first known variant that lies behind the last discovered one (1661-1666) */
 static void print_knownvariants(driver* d, known_list* kl, const variant_list* vars)
 {
     if (vars->n == 0) return;
     int ki = kl->next;
+    uint8_t* found = g_known_counts ? xmalloc((size_t)(kl->n - ki + 1)) : NULL;     /* -A: the records go out together */
     for (; ki < kl->n; ki++) {
         knownvariant_t* k = kl->v[ki];
-        int is_found = 0;
-        const uint32_t kstart = k->start, kstop = k->stop;
         int ui;
-        for (ui = 0; ui < vars->n; ui++) {
-            const variant_t* u = vars->v[ui];
-            const uint32_t ustart = u->start - u->lw;
-            uint32_t ustop = 0;
-            const int reflength = (int)(u->stop + u->rw) - (int)(u->start - u->lw - 1);
-            forceassert(reflength >= 1);
-            if (u->type == CLS_DELETION) {
-                const int altlength = (int)(u->start + u->rw) - (int)(u->start - u->lw - 1);
-                forceassert(altlength >= 1);
-                ustop = u->start - u->lw + (uint32_t)reflength - (uint32_t)altlength + 1;
-            } else if (u->type == CLS_INSERTION) ustop = ustart + 1;
-            forceassert(ustop != 0);
-            if (kstart >= ustop) { }
-            else if (ustart >= kstop) { }
-            else {
-                if ((k->evdnctype == EV_SPLIT_READ || k->evdnctype == EV_COMPOSITE) && u->evdnctype == EV_SPLIT_READ) {
-                    if (kstart == ustart && kstop == ustop) { is_found = 1; break; }
-                } else if (((k->evdnctype == EV_SPLIT_READ || k->evdnctype == EV_COMPOSITE) && u->evdnctype == EV_PAIRED_READ) ||
-                           (k->evdnctype == EV_PAIRED_READ && u->evdnctype == EV_SPLIT_READ) ||
-                           (k->evdnctype == EV_PAIRED_READ && u->evdnctype == EV_PAIRED_READ)) {
-                    const uint32_t sx = k->start > u->start ? k->start : u->start;
-                    const uint32_t ex = k->bpstop < u->stop ? k->bpstop : u->stop;
-                    uint32_t olap = 0;
-                    if (ex >= sx) olap = ex - sx;
-                    if ((olap * 100.00 / (k->bpstop - k->start)) > 50) { is_found = 1; break; }
-                }
-            }
-        }
+        const int is_found = known_match(k, vars, &ui);
         if (ui == vars->n) {
             const variant_t* last = vars->v[vars->n - 1];
-            if (last->start < kstart) break;
+            if (last->start < k->start) break;
         }
+        if (found) { found[ki - kl->next] = (uint8_t)is_found; continue; }
         print_vcf_line(d, k);
         if (is_found) printf(";%s", g_sample_name);
         else if (k->evdnctype == EV_SPLIT_READ && is_indel_supported(d, k)) printf(";%s", g_sample_name);
         printf("\n");
     }
+    if (found) { print_known_counted(d, kl, kl->next, ki, found); free(found); }
     kl->next = ki;
 }
 

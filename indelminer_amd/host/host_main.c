@@ -34,6 +34,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t-b, require at least one read with these bases on \n");
     fprintf(file, "\t    either side of the indel[30]\n");
     fprintf(file, "\t-G, add genotype columns (FORMAT GT:AD:GQ) to the vcf output\n");
+    fprintf(file, "\t-A, with indels.vcf: genotype the known indels in this sample\n");
+    fprintf(file, "\t    (FORMAT GT:AD:GQ from the reads for and against each)\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -76,7 +78,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:G")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GA")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -101,6 +103,7 @@ int main(int argc, char** argv)
         case 'a': O.call_all_indels = 1; break;
         case 'b': if (sscanf(optarg, "%u", &O.minbalance) != 1) fatalf("incorrect option for -b: %s\n", optarg); break;
         case 'G': g_genotype = 1; break;                            /* not an option of the reference */
+        case 'A': g_known_counts = 1; break;                        /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -116,6 +119,7 @@ int main(int argc, char** argv)
 
     const char* fasta_reference = argv[optind++];
     char* ptr = argv[optind++];
+    if (g_known_counts && strchr(ptr, '=') != NULL) { fprintf(stderr, "indelminer: -A needs a VCF argument (annotate mode)\n"); return EXIT_FAILURE; }
     if (strchr(ptr, '=') == NULL) {                 /* a VCF: tag its indels only (src/indelminer.c:1046-1053) */
         g_vcfname = ptr;
         O.minsupport = 1;
@@ -137,6 +141,14 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
         if (strcmp(O.outputformat, "detailed") == 0) g_genotype = 0;    /* -o detailed has no columns to add to */
+    }
+
+    if (g_known_counts) {
+        const char* ws_ = getenv("WORLD_SIZE");
+        if ((ws_ && atoi(ws_) > 1) || getenv("INDELMINER_FORCE_MGPU")) { fprintf(stderr, "indelminer: -A is not available with more than one rank\n"); return EXIT_FAILURE; }
+        if (!im_support_count || !im_span_enable || !im_dev_span_scatter || !im_span_scan || !im_span_query_tid || !im_span_build || !im_span_query) {
+            fprintf(stderr, "indelminer: genotyping known indels (-A) needs the device library\n"); return EXIT_FAILURE;
+        }
     }
 
     fprintf(stderr, "Reference fasta file: %s\n", fasta_reference);

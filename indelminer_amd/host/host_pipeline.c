@@ -189,7 +189,7 @@ static void pipe_global_init(driver* d)
     free(rmax);
     if (im_depth_enable(d->gpu) != IM_OK) fatalf("im_depth_enable: %s", im_last_error(d->gpu));
     /* -G: the second genome-wide array, only then */
-    if (g_genotype && im_span_enable(d->gpu, (int32_t)O.ethreshold, O.qthreshold) != IM_OK) fatalf("im_span_enable: %s", im_last_error(d->gpu));
+    if (SPAN_ON && im_span_enable(d->gpu, (int32_t)O.ethreshold, O.qthreshold) != IM_OK) fatalf("im_span_enable: %s", im_last_error(d->gpu));
 }
 
 /* one walker's buffers (with_chunks: the pinned chunk ring a walk delivers records through; the main thread's stage pipeline
@@ -406,7 +406,7 @@ static void pipe_submit(ppipe* P, pgroup* G)
     out.cand_rec = P->cand_rec; out.counters = P->counters; out.rec_class = c->d_class;
     out.cap_cand = P->cap_cand; out.cap_bases = P->cap_bases; out.consumed = NULL;     /* cleared once per group in pipe_run_group */
     GPU(im_dev_triage(g, &P->tp, &recs, &out, c->d_scratch, c->scratch_bytes, P->stream));
-    if (g_genotype) GPU(im_dev_span_scatter(g, &recs, P->stream));      /* -G: a launch of its own behind the triage, in front of the chunk's event */
+    if (SPAN_ON) GPU(im_dev_span_scatter(g, &recs, P->stream));      /* -G, -A: a launch of its own behind the triage, in front of the chunk's event */
     GPU(im_dev_download_async(g, c->h_cnt, P->counters, 32, P->stream));
     GPU(im_event_record(c->done, P->stream));
     c->busy = 1; P->n_busy++;
@@ -1177,15 +1177,7 @@ static void group_replay(driver* d, pgroup* G)
             for (int64_t i = 0; i < n_used; i++) evidence_free(used[i]);
             free(used);
         }
-        if (g_vcfname != NULL && cg->last) {
-            for (int ki = g_known.next; ki < g_known.n; ki++) {
-                knownvariant_t* k = g_known.v[ki];
-                print_vcf_line(d, k);
-                if (k->evdnctype == EV_SPLIT_READ && is_indel_supported(d, k)) printf(";%s", g_sample_name);
-                printf("\n");
-            }
-            g_known.next = g_known.n;
-        }
+        if (g_vcfname != NULL && cg->last) print_known_rest(d, &g_known);
     }
     /* evidence objects that were built with their candidate but belong to slots no flush of this group consumed (they are still
      * pending: a later piece builds them again from the candidate) */

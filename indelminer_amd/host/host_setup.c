@@ -34,7 +34,13 @@ static void print_output_header(void)
     if (strncmp(O.outputformat, "vcf", 3) == 0) print_vcf_preamble();
     if (g_vcfname != NULL)
         printf("##INFO=<ID=%s,Number=0,Type=Flag,Description=\"The variant is also present in this sample\">\n", g_sample_name);
-    if (g_genotype) {
+    if (g_known_counts) {
+        /* -A: no reference counterpart */
+        printf("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype, the most likely of 0/0, 0/1, 1/1 given AD\">\n");
+        printf("##FORMAT=<ID=AD,Number=2,Type=Integer,Description=\"Read support of the reference and the alternative allele in this sample: the smallest number, over the positions POS .. POS+(BP_END-END) the breakpoint can lie at, of alignments that match the reference for the -n distance on both sides of it, less those of them that support the indel; and the reads with mapping quality of at least -q that support the indel, by their CIGAR or by aligning at least as well against the reference with the indel applied\">\n");
+        printf("##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred-scaled distance to the second most likely genotype, at most 99\">\n");
+        printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", g_sample_name);
+    } else if (g_genotype) {
         /* -G: no reference counterpart */
         printf("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype, the most likely of 0/0, 0/1, 1/1 given AD\">\n");
         printf("##FORMAT=<ID=AD,Number=2,Type=Integer,Description=\"Read support of the reference and the alternative allele: the smallest number, over the positions POS .. POS+(BP_END-END) the breakpoint can lie at, of alignments that match the reference for the -n distance on both sides of it (an upper bound of the reads spanning the whole interval, exact when the interval is one position), and NS\">\n");
@@ -330,7 +336,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
                 } else if (op == OP_D || op == OP_N) x += len;
             }
         }
-        if (g_genotype && b.tid >= 0 && !(b.flag & (0x4 | 0x100 | 0x200 | 0x400)) && (int)b.mapq >= O.qthreshold) {
+        if (SPAN_ON && b.tid >= 0 && !(b.flag & (0x4 | 0x100 | 0x200 | 0x400)) && (int)b.mapq >= O.qthreshold) {
             /* -G: the maximal M/=/X runs of the record (D and N advance and end a run, every other operation ends it) */
             const uint8_t* cig = BAMR_CIGAR(&b);
             int64_t x = b.pos, rs = 0;
@@ -367,7 +373,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
         d->depth_tid = tid;
     }
     phase_time("depth array (device)");
-    if (g_genotype) {
+    if (SPAN_ON) {
         gpu_wait(d);
         if (d->n_run > INT32_MAX) fatalf("more than 2^31 alignment runs on one contig");
         if (im_span_build(d->gpu, d->seqlen[tid], (int32_t)d->n_run, d->run_start, d->run_len, (int32_t)O.ethreshold) != IM_OK)
@@ -408,14 +414,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
     flush_variants(d, tid, INT_MAX);        /* end of contig (src/indelminer.c:806-823) */
     phase_time("pass B (cluster, merge, print)");
     if (g_vcfname != NULL) {
-        /* what print_knownvariants left over (src/indelminer.c:839-847) */
-        for (int ki = g_known.next; ki < g_known.n; ki++) {
-            knownvariant_t* k = g_known.v[ki];
-            print_vcf_line(d, k);
-            if (k->evdnctype == EV_SPLIT_READ && is_indel_supported(d, k)) printf(";%s", g_sample_name);
-            printf("\n");
-        }
-        g_known.next = g_known.n;
+        print_known_rest(d, &g_known);       /* what print_knownvariants left over (src/indelminer.c:839-847) */
     }
 }
 

@@ -777,7 +777,7 @@ static void run_pipeline(driver* d, walkpool_t* o)
         for (int k = 0; k < n_held; k++)
             for (int cj = 0; cj < held[k]->n_ctg; cj++)
                 if (held[k]->ctg[cj].last && g_region_tid < 0) GPU2(d, im_depth_scan(d->gpu, held[k]->ctg[cj].tid, S.stream));
-        if (g_genotype)                          /* -G: the span array too, region runs included */
+        if (SPAN_ON)                             /* -G, -A: the span array too, region runs included */
             for (int k = 0; k < n_held; k++)
                 for (int cj = 0; cj < held[k]->n_ctg; cj++)
                     if (held[k]->ctg[cj].last) GPU2(d, im_span_scan(d->gpu, held[k]->ctg[cj].tid, S.stream));

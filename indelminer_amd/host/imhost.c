@@ -116,6 +116,11 @@ extern int im_span_scan(im_ctx*, int32_t, void*) __attribute__((weak));
 extern int im_span_query_tid(im_ctx*, int32_t, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
 extern int im_span_build(im_ctx*, int64_t, int32_t, const int32_t*, const int32_t*, int32_t) __attribute__((weak));
 extern int im_span_query(im_ctx*, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
+/* -A: annotate mode with read counts for and against every known indel (GT:AD:GQ per record), from the device's counting form
+ * of the annotate-mode Smith-Waterman and the same span array.  Not an option of the reference either; referenced weakly too. */
+static int g_known_counts = 0;
+extern int im_support_count(im_ctx*, int32_t, const im_known_variant*, const uint8_t*, int64_t, int32_t, const im_count_task*, const uint8_t*, int64_t, int32_t*) __attribute__((weak));
+#define SPAN_ON (g_genotype || g_known_counts)     /* the walk scatters the span array */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that
@@ -232,9 +237,12 @@ static __thread int64_t t_cpu_dev_ns, t_wall_dev_ns;      /* a walker's processo
 static int64_t thread_cpu_ns(void) { struct timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); return (int64_t)ts.tv_sec * 1000000000LL + ts.tv_nsec; }
 static int64_t wall_ns(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (int64_t)ts.tv_sec * 1000000000LL + ts.tv_nsec; }
 static int64_t g_sw_ns, g_sw_calls, g_sw_tasks, g_sw_cells;      /* annotate mode: im_support_batch calls, their tasks and DP cells */
+static int64_t g_kc_ns, g_kc_calls, g_kc_tasks, g_kc_direct, g_kc_wall_ns;     /* -A: im_support_count calls and the whole of known_counts_run */
 static void cpu_report(void)
 {
     if (!g_timing) return;
+    if (g_kc_calls) fprintf(stderr, "[timing] annotate mode -A: %ld im_support_count calls, %ld tasks (%ld by their CIGAR alone), %.3f s in the calls (copies + kernels), %.3f s in region fetches and CIGAR bookkeeping\n",
+                            (long)g_kc_calls, (long)g_kc_tasks, (long)g_kc_direct, g_kc_ns / 1e9, (g_kc_wall_ns - g_kc_ns) / 1e9);
     if (g_sw_calls) fprintf(stderr, "[timing] annotate mode: %ld im_support_batch calls, %ld tasks, %ld cells, %.3f s in the calls (launch + copies + kernel)\n",
                             (long)g_sw_calls, (long)g_sw_tasks, (long)g_sw_cells, g_sw_ns / 1e9);
     struct timespec ts; clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &ts);
