@@ -10,6 +10,7 @@
 //   K4  find_best_del_candidate / count_matches  src/alignment.c:219-339
 //   a10 update_readsegs  src/readaln.c:348-458     final segment list
 //   a11 new_evidence     src/evidence.c:4-34       evidence record
+// K4, a10, a11 and the control logic between the steps live in im_realign_plan.hpp, shared with the other realign kernels.
 //
 // Work shape.  A workgroup is ONE wavefront (64 lanes) and owns one read at a
 // time; the grid is a few workgroups per CU that stride over the batch, with
@@ -26,6 +27,7 @@
 
 #include "im_device.hpp"
 #include "im_wave.hpp"
+#include "im_realign_plan.hpp"
 
 // Diagnostic build only (-DIM_STAMPS, `python indelminer_amd/build.py --stamps`): per-phase
 // shader-cycle sums over all waves, read back through im_debug_stamps_read.  The product
@@ -682,15 +684,9 @@ __device__ __forceinline__ void realign_one(WaveLds& s, const RealignArgs& A, in
     if (lane < 4) s.rd[64 + lane] = 0u;
     wave_lds_sync();
 
-    // window geometry (src/alignment.c:774-783)
-    int distance = R;
-    const int left1  = anchor >= distance ? anchor - distance : 0;
-    const int right1 = clen < (anchor + distance) ? clen : anchor + distance;
-    distance = R + (int)A.P.maxdelsize;
-    const int left2  = anchor >= distance ? anchor - distance : 0;
-    const int right2 = clen < (anchor + distance) ? clen : anchor + distance;
-    if (!(anchor >= left1 && anchor >= left2 && anchor <= right1 && anchor <= right2 &&
-          left2 >= 0 && right2 > 0)) { finish(out, IM_ST_ABORT, 0, lane); return; }      // 548-553
+    const Windows win = realign_windows(anchor, R, A.P.maxdelsize, clen);
+    if (!win.ok) { finish(out, IM_ST_ABORT, 0, lane); return; }
+    const int left1 = win.left1, right1 = win.right1;
 
     // piece 1: the whole read in [left1,right1) (557-566)
     IM_STAMP(0);
@@ -704,173 +700,28 @@ __device__ __forceinline__ void realign_one(WaveLds& s, const RealignArgs& A, in
     if (q1 == q2) { finish(out, IM_ST_NONE, 1, lane); return; }                          // 568-572
     if (q1 == 0 && q2 == L) { finish(out, IM_ST_NONE, 1, lane); return; }                // 575-582: no I/D op at g = 0
 
-    // piece 2: the rest of the read in the extended window, four cases (605-717)
-    const uint32_t uL = (uint32_t)L, f = (uint32_t)a1.f, l = (uint32_t)a1.l;
-    uint32_t w0, w1, anc, p0, p1; bool want_tail;
-    if (r1 > anchor) {
-        if (q1 == 0) {
-            if (!(uL > f)) { finish(out, IM_ST_ABORT, 1, lane); return; }
-            if ((uL - f) < eth || ((uint32_t)right2 - (uint32_t)r1 - f) < eth) { finish(out, IM_ST_NONE, 1, lane); return; }
-            w0 = (uint32_t)r1 + f; w1 = (uint32_t)right2; anc = (uint32_t)r1; p0 = f; p1 = uL; want_tail = true;
-        } else if (q2 == L) {
-            if (!(uL > l)) { finish(out, IM_ST_ABORT, 1, lane); return; }
-            if ((uL - l) < eth || ((uint32_t)r2 - l - (uint32_t)anchor) < eth) { finish(out, IM_ST_NONE, 1, lane); return; }
-            w0 = (uint32_t)anchor; w1 = (uint32_t)r2 - l; anc = (uint32_t)r2; p0 = 0; p1 = uL - l; want_tail = false;
-        } else { finish(out, IM_ST_NONE, 1, lane); return; }
-    } else if (r1 < anchor) {
-        if (r2 >= anchor) { finish(out, IM_ST_NONE, 1, lane); return; }
-        if (q1 == 0) {
-            if (!(uL > f)) { finish(out, IM_ST_ABORT, 1, lane); return; }
-            if ((uL - f) < eth || ((uint32_t)anchor - (uint32_t)r1 - f) < eth) { finish(out, IM_ST_NONE, 1, lane); return; }
-            w0 = (uint32_t)r1 + f; w1 = (uint32_t)anchor; anc = (uint32_t)r1; p0 = f; p1 = uL; want_tail = true;
-        } else if (q2 == L) {
-            if (!(uL > l)) { finish(out, IM_ST_ABORT, 1, lane); return; }
-            if ((uL - l) < eth || ((uint32_t)r2 - l - (uint32_t)left2) < eth) { finish(out, IM_ST_NONE, 1, lane); return; }
-            w0 = (uint32_t)left2; w1 = (uint32_t)r2 - l; anc = (uint32_t)r2; p0 = 0; p1 = uL - l; want_tail = false;
-        } else { finish(out, IM_ST_NONE, 1, lane); return; }
-    } else { finish(out, IM_ST_NONE, 1, lane); return; }                                  // r1 == anchor (712-717)
-    if ((int32_t)(w1 - w0) <= 0) { finish(out, IM_ST_ABORT, 1, lane); return; }
+    const Piece2Plan pl = plan_piece2(r1, r2, q1, q2, (uint32_t)a1.f, (uint32_t)a1.l, L, anchor, win.left2, win.right2, eth);
+    if (pl.st != kStGoOn) { finish(out, pl.st, 1, lane); return; }
+    const uint32_t w0 = pl.w0, w1 = pl.w1, p0 = pl.p0, p1 = pl.p1;
 
     IM_STAMP(7);
-    const Band b2 = band_search<KT, DIRECT>(s, pk, contig, w0, w1, anc, p0, p1, k, g, lane, read_pk8, codes IM_STAMP_PASS(8));
+    const Band b2 = band_search<KT, DIRECT>(s, pk, contig, w0, w1, pl.anc, p0, p1, k, g, lane, read_pk8, codes IM_STAMP_PASS(8));
     if (b2.st) { finish(out, b2.st, 2, lane); return; }
     const Aln a2 = diag_scan<false>(s, contig, w0, w1, p0, p1, b2.low, lane);
     store_band(out, 1, b2, a2, lane);
     IM_STAMP(13);
     if (a2.st) { finish(out, a2.st, 2, lane); return; }
     const int r3 = a2.r1, r4 = a2.r2, q3 = a2.q1, q4 = a2.q2;
-    if (want_tail) { if (q4 != L || q3 == q4) { finish(out, IM_ST_NONE, 2, lane); return; } }   // 623-627, 679-683
-    else           { if (q3 != 0 || q3 == q4) { finish(out, IM_ST_NONE, 2, lane); return; } }   // 645-649, 701-705
-    if (!(q1 < q2 && q3 < q4)) { finish(out, IM_ST_ABORT, 2, lane); return; }             // 720-721
-
-    // combine (723-754).  "A" = the piece that starts at read offset 0, "B" = the one that ends at L.
-    uint32_t wa, wb;                    // Aln::eqbits of the A / B piece
-    int qa2, rA, qb1, rB;               // A = read[0,qa2) at contig rA.. ; B = read[qb1,L) at contig rB..
-    bool split;                         // true: overlapping pieces, choose the split point (K4)
-    if (q1 > q3 && q1 <= q4)        { wa = a2.eqbits; qa2 = q4; rA = r3; wb = a1.eqbits; qb1 = q1; rB = r1; split = true;  }
-    else if (q3 > q1 && q3 <= q2)   { wa = a1.eqbits; qa2 = q2; rA = r1; wb = a2.eqbits; qb1 = q3; rB = r3; split = true;  }
-    else if (q1 > q4 && r1 == r4)   { wa = a2.eqbits; qa2 = q4; rA = r3; wb = a1.eqbits; qb1 = q1; rB = r1; split = false; }
-    else if (q3 > q2 && r2 == r3)   { wa = a1.eqbits; qa2 = q2; rA = r1; wb = a2.eqbits; qb1 = q3; rB = r3; split = false; }
-    else { finish(out, IM_ST_NONE, 2, lane); return; }
-    // find_best_del_candidate asserts its first piece starts at read offset 0 (314-315)
-    // (holds by the accept conditions above: the A piece has q == 0)
-
-    // per-position match flags of A on [0,qa2) and B on [qb1,L)
-    const int x0 = 4 * lane;
-    int fa[4], fb[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int x = x0 + j;
-        fa[j] = (x < qa2) ? (int)((wa >> j) & 1u) : 0;
-        fb[j] = (x >= qb1 && x < L) ? (int)((wb >> j) & 1u) : 0;
-    }
-    const int ta = fa[0] + fa[1] + fa[2] + fa[3], tb = fb[0] + fb[1] + fb[2] + fb[3];
-    const int iab = wave_scan_add(ta | (tb << 16), lane);          // both counts in one scan: each stays below 2^15
-    const int tot = __builtin_amdgcn_readlane(iab, 63);
-    const int ia = iab & 0xFFFF, ib = iab >> 16;
-    const int totA = tot & 0xFFFF, totB = tot >> 16;
-    int pa[4], pb[4];                   // exclusive prefix counts at x
-    pa[0] = ia - ta; pb[0] = ib - tb;
-#pragma unroll
-    for (int j = 1; j < 4; j++) { pa[j] = pa[j - 1] + fa[j - 1]; pb[j] = pb[j - 1] + fb[j - 1]; }
-
-    int index, nextindex, matches;
-    if (split) {
-        // count_matches(i) = '=' of A in read[0,i) + '=' of B in read[i,L); X counts are
-        // L - that, so "max matches, then min mismatches, first wins" is the first maximum.
-        // one reduction for both: (matches << 8) | (255 - x), largest wins -- matches and x stay below 256
-        int bk = -1;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int x = x0 + j;
-            if (x >= qb1 && x <= qa2) bk = max(bk, ((pa[j] + (totB - pb[j])) << 8) | (255 - x));
-        }
-        bk = wave_max(bk);
-        if (bk < 0) { finish(out, IM_ST_ABORT, 2, lane); return; }                         // forceassert(index != -1)
-        index = 255 - (bk & 255);
-        nextindex = index;
-        matches = bk >> 8;
-    } else {
-        index = qa2; nextindex = qb1;
-        matches = totA + totB;
-    }
-
-    // update_readsegs (src/readaln.c:348-458) in closed form: A's runs over [0,index),
-    // an I of nextindex-index bases if the pieces leave read bases uncovered, a D if
-    // the reference positions leave a gap, then B's runs over [nextindex,L).
-    const int refindx = rA + index;
-    const int rindex  = rB + (nextindex - qb1);
-    const bool hasI = nextindex > index;
-    const bool hasD = refindx < rindex;
-    if (!hasI && !hasD) { finish(out, IM_ST_NONE, 2, lane); return; }                      // no D/I segment -> NULL
-
-    // run-length encode the final per-position classes
-    int cls[4]; bool bnd[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int x = x0 + j;
-        cls[j] = (x >= L) ? -1 : (x < index) ? (fa[j] ? IM_OP_EQ : IM_OP_X)
-                 : (x < nextindex) ? IM_OP_I : (fb[j] ? IM_OP_EQ : IM_OP_X);
-    }
-    const int prevc = dpp_mov<kDppWaveShr1>(-2, cls[3]);      // lane 0 keeps -2
-    int nb = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int x = x0 + j;
-        const int pc = (j == 0) ? prevc : cls[j - 1];
-        bnd[j] = (x < L) && (x == 0 || x == index || x == nextindex || cls[j] != pc);
-        nb += bnd[j] ? 1 : 0;
-    }
-    const int inb = wave_scan_add(nb, lane);
-    const int total_b = __builtin_amdgcn_readlane(inb, 63);
-    const int n_ops = total_b + (hasD ? 1 : 0);
-    if (n_ops > IM_MAX_OPS) { finish(out, IM_ST_OVERFLOW, 2, lane); return; }
-    // run length = distance to the next boundary: boundary k leaves its position in LDS
-    // (the vote histogram is idle by now), run k ends where boundary k+1 starts
-    int32_t* bpos = reinterpret_cast<int32_t*>(s.diag);
-    {
-        int k = inb - nb;
-#pragma unroll
-        for (int j = 0; j < 4; j++) if (bnd[j]) bpos[k++] = x0 + j;
-        if (lane == 0) bpos[total_b] = L;
-    }
-    wave_lds_sync();
-    int slot = inb - nb;                 // boundaries before this lane
-    int seg_indel = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int x = x0 + j;
-        if (bnd[j]) {
-            const int sl = slot + ((hasD && x >= nextindex) ? 1 : 0);
-            out->ops[sl] = ((uint32_t)(bpos[slot + 1] - x) << 4) | (uint32_t)cls[j];
-            if (x == index) seg_indel = slot;       // the I run itself, or the run the D op goes in front of
-            slot++;
-        }
-    }
-    seg_indel = __builtin_amdgcn_readlane(seg_indel, index >> 2);     // the lane that owns read position `index` set it
-    if (lane == 0) {
-        if (hasD) out->ops[seg_indel] = ((uint32_t)(rindex - refindx) << 4) | IM_OP_D;
-        im_evidence* e = &out->ev[0];
-        if (hasD) {
-            e->cls = IM_CLS_DELETION; e->b1 = refindx; e->b2 = rindex;
-            e->lflank = index; e->rflank = L - nextindex;
-        } else {
-            e->cls = IM_CLS_INSERTION; e->b1 = refindx; e->b2 = refindx;
-            e->lflank = index; e->rflank = L - nextindex;
-        }
-        e->seg = seg_indel;
-        e->read_off = index;
-        // X bases left in aln1 + aln3: aligned bases minus '=' bases
-        const int aligned = index + (L - nextindex);
-        e->nd_print = aligned - matches;
-        e->nd_filter = aligned - matches;
-        out->ref_start = rA;
-        out->n_ops = n_ops;
-        out->n_ev = 1;
-        out->status = IM_ST_EVIDENCE;
-        out->n_band = 2;
-    }
-    write_slots(A, c, 1, hasD ? IM_CLS_DELETION : IM_CLS_INSERTION, refindx, hasD ? rindex : refindx, lane);
+    const int acc = accept_piece2(pl.want_tail, q1, q2, q3, q4, L);
+    if (acc != kStGoOn) { finish(out, acc, 2, lane); return; }
+    const Pieces pc = choose_pieces(q1, q2, q3, q4, r1, r2, r3, r4);
+    if (!pc.ok) { finish(out, IM_ST_NONE, 2, lane); return; }
+    // find_best_del_candidate asserts its first piece starts at read offset 0 (314-315): not tested here, it holds by
+    // accept_piece2 (the A piece has q == 0); the band and the one-lane-per-read kernels test it.
+    // The boundary positions go where the vote histogram was (idle by now).
+    const int st = merge_pieces<4>(pc.a_is_second ? a2.eqbits : a1.eqbits, pc.a_is_second ? a1.eqbits : a2.eqbits,
+                                   pc.qa2, pc.rA, pc.qb1, pc.rB, pc.split, L, reinterpret_cast<int32_t*>(s.diag), out, A, c, lane);
+    if (st != IM_ST_EVIDENCE) { finish(out, st, 2, lane); return; }
     IM_STAMP(14);
 }
 
@@ -1647,6 +1498,7 @@ __global__ __launch_bounds__(64, 5) void realign_band_kernel(RealignArgs A)
     const uint32_t k = A.P.klength, g = A.P.numgaps, eth = A.P.ethreshold;
     const int n_reads = A.n_dev ? min(*A.n_dev, A.batch.n) : A.batch.n;
     for (int c = blockIdx.x; c < n_reads; c += gridDim.x) {
+        IM_STAMP_DECL
         im_read_result* out = &A.batch.out[c];
         const int64_t off = uni64(A.batch.base_off[c]);
         const int64_t Lraw = uni(A.batch.read_len[c]);
@@ -1675,15 +1527,9 @@ __global__ __launch_bounds__(64, 5) void realign_band_kernel(RealignArgs A)
         }
         wave_lds_sync();
         const uint8_t* rd = reinterpret_cast<const uint8_t*>(s.rd);
-        int distance = R;
-        const int left1  = anchor >= distance ? anchor - distance : 0;
-        const int right1 = clen < (anchor + distance) ? clen : anchor + distance;
-        distance = R + (int)A.P.maxdelsize;
-        const int left2  = anchor >= distance ? anchor - distance : 0;
-        const int right2 = clen < (anchor + distance) ? clen : anchor + distance;
-        if (!(anchor >= left1 && anchor >= left2 && anchor <= right1 && anchor <= right2 && left2 >= 0 && right2 > 0)) {
-            finish(out, IM_ST_ABORT, 0, lane); continue;
-        }
+        const Windows win = realign_windows(anchor, R, A.P.maxdelsize, clen);
+        if (!win.ok) { finish(out, IM_ST_ABORT, 0, lane); continue; }
+        const int left1 = win.left1, right1 = win.right1;
         // piece 1: the whole read in [left1, right1)
         const Band b1 = band_search<0, DIRECT>(s, pk, contig, (uint32_t)left1, (uint32_t)right1, (uint32_t)anchor, 0u, (uint32_t)L, k, g, lane, 0u, nullptr IM_STAMP_PASS(16));
         if (b1.st) { finish(out, b1.st, 1, lane); continue; }
@@ -1716,35 +1562,11 @@ __global__ __launch_bounds__(64, 5) void realign_band_kernel(RealignArgs A)
             if (i1 >= 0 && (c1[i1] & 15u) == IM_OP_EQ) l = c1[i1] >> 4;
             f = (uint32_t)uni((int)f); l = (uint32_t)uni((int)l);
         }
-        const uint32_t uL = (uint32_t)L;
-        uint32_t w0 = 0, w1 = 0, anc = 0, p0 = 0, p1 = 0; bool want_tail = false; int none = 0, abortc = 0;
-        if (r1 > anchor) {
-            if (q1 == 0) {
-                if (!(uL > f)) abortc = 1;
-                else if ((uL - f) < eth || ((uint32_t)right2 - (uint32_t)r1 - f) < eth) none = 1;
-                w0 = (uint32_t)r1 + f; w1 = (uint32_t)right2; anc = (uint32_t)r1; p0 = f; p1 = uL; want_tail = true;
-            } else if (q2 == L) {
-                if (!(uL > l)) abortc = 1;
-                else if ((uL - l) < eth || ((uint32_t)r2 - l - (uint32_t)anchor) < eth) none = 1;
-                w0 = (uint32_t)anchor; w1 = (uint32_t)r2 - l; anc = (uint32_t)r2; p0 = 0; p1 = uL - l;
-            } else none = 1;
-        } else if (r1 < anchor) {
-            if (r2 >= anchor) none = 1;
-            else if (q1 == 0) {
-                if (!(uL > f)) abortc = 1;
-                else if ((uL - f) < eth || ((uint32_t)anchor - (uint32_t)r1 - f) < eth) none = 1;
-                w0 = (uint32_t)r1 + f; w1 = (uint32_t)anchor; anc = (uint32_t)r1; p0 = f; p1 = uL; want_tail = true;
-            } else if (q2 == L) {
-                if (!(uL > l)) abortc = 1;
-                else if ((uL - l) < eth || ((uint32_t)r2 - l - (uint32_t)left2) < eth) none = 1;
-                w0 = (uint32_t)left2; w1 = (uint32_t)r2 - l; anc = (uint32_t)r2; p0 = 0; p1 = uL - l;
-            } else none = 1;
-        } else none = 1;
-        if (abortc) { finish(out, IM_ST_ABORT, 1, lane); continue; }
-        if (none) { finish(out, IM_ST_NONE, 1, lane); continue; }
-        if ((int32_t)(w1 - w0) <= 0) { finish(out, IM_ST_ABORT, 1, lane); continue; }
+        const Piece2Plan pl = plan_piece2(r1, r2, q1, q2, f, l, L, anchor, win.left2, win.right2, eth);
+        if (pl.st != kStGoOn) { finish(out, pl.st, 1, lane); continue; }
+        const uint32_t w0 = pl.w0, w1 = pl.w1, p0 = pl.p0, p1 = pl.p1; const bool want_tail = pl.want_tail;
         // piece 2
-        const Band b2 = band_search<0, DIRECT>(s, pk, contig, w0, w1, anc, p0, p1, k, g, lane, 0u, nullptr IM_STAMP_PASS(21));
+        const Band b2 = band_search<0, DIRECT>(s, pk, contig, w0, w1, pl.anc, p0, p1, k, g, lane, 0u, nullptr IM_STAMP_PASS(21));
         if (b2.st) { finish(out, b2.st, 2, lane); continue; }
         const int up2 = ((p1 - p0) < k) ? b2.low : b2.low + (int)g;
         const BandAln a2 = band_alignment(G, contig, rd, (int)p0, (int)(p1 - p0), (int)w0, (int)(w1 - w0), b2.low, up2, 1, lane);
@@ -1757,10 +1579,11 @@ __global__ __launch_bounds__(64, 5) void realign_band_kernel(RealignArgs A)
         if (st == 0) {
             const int r3 = a2.r1, r4 = a2.r2, q3 = a2.q1, q4 = a2.q2;
             uint32_t* c2 = G.ops[1]; int n2 = uni(G.nops[1]);
-            st = -100;                                      // "go on to combine"
-            if (want_tail) { if (q4 != L || q3 == q4) st = IM_ST_NONE; }
-            else           { if (q3 != 0 || q3 == q4) st = IM_ST_NONE; }
-            if (st == -100) {
+            // the verdict on the second alignment; its abort (720-721) waits behind the soft clips, whose own failures come
+            // first here as in the reference's order of statements (the numgaps == 0 kernels have no clips)
+            const int acc = accept_piece2(want_tail, q1, q2, q3, q4, L);
+            st = acc == IM_ST_NONE ? IM_ST_NONE : kStGoOn;
+            if (st == kStGoOn) {
                 // add_prefix_soft_clip / add_suffix_soft_clip (src/alignment.c:478-532)
                 if (want_tail && f > 0) {
                     if (n2 > 0 && (c2[0] & 15u) == IM_OP_S) { if (lane == 0) c2[0] = (((c2[0] >> 4) + f) << 4) | IM_OP_S; }
@@ -1780,22 +1603,26 @@ __global__ __launch_bounds__(64, 5) void realign_band_kernel(RealignArgs A)
                 }
                 wave_lds_sync();
             }
-            if (st == -100) {
-                if (!(q1 < q2 && q3 < q4)) { BFAIL(G, 103); st = IM_ST_ABORT; }
+            if (st == kStGoOn) {
+                if (acc == IM_ST_ABORT) { BFAIL(G, 103); st = IM_ST_ABORT; }
                 else {
-                    int index = -1;
-                    const uint32_t bits2 = band_piece_bits(G, 1, (int)p0, (int)(p1 - p0), lane);
-                    // find_best_del_candidate asserts that its first piece starts at read offset 0 (314-315); its second piece
-                    // ends at L by the accept conditions above
-                    if (q1 > q3 && q1 <= q4) {
-                        st = (q3 != 0 || q2 != L) ? IM_ST_ABORT : band_best_split(G, bits2, q4, bits1, q1, L, lane, &index);
-                        if (st == 0) st = band_build_result(out, G, r3, c2, n2, index, q1, r1, c1, n1, lane, A, c);
-                    } else if (q3 > q1 && q3 <= q2) {
-                        st = (q1 != 0 || q4 != L) ? IM_ST_ABORT : band_best_split(G, bits1, q2, bits2, q3, L, lane, &index);
-                        if (st == 0) st = band_build_result(out, G, r1, c1, n1, index, q3, r3, c2, n2, lane, A, c);
-                    } else if (q1 > q4 && r1 == r4) st = band_build_result(out, G, r3, c2, n2, q4, q1, r1, c1, n1, lane, A, c);
-                    else if (q3 > q2 && r2 == r3) st = band_build_result(out, G, r1, c1, n1, q2, q3, r3, c2, n2, lane, A, c);
-                    else st = IM_ST_NONE;
+                    const Pieces pc = choose_pieces(q1, q2, q3, q4, r1, r2, r3, r4);
+                    if (!pc.ok) st = IM_ST_NONE;
+                    else {
+                        const uint32_t bits2 = band_piece_bits(G, 1, (int)p0, (int)(p1 - p0), lane);
+                        const bool as = pc.a_is_second;
+                        const uint32_t* cA = as ? c2 : c1; const uint32_t* cB = as ? c1 : c2;
+                        const int nA = as ? n2 : n1, nB = as ? n1 : n2;
+                        int index = pc.qa2;
+                        st = 0;
+                        if (pc.split) {
+                            // find_best_del_candidate asserts that its first piece starts at read offset 0 (314-315); that its second
+                            // piece ends at L is this kernel's own test (neither is tested by the numgaps == 0 kernels)
+                            st = ((as ? q3 : q1) != 0 || (as ? q2 : q4) != L) ? IM_ST_ABORT
+                                 : band_best_split(G, as ? bits2 : bits1, pc.qa2, as ? bits1 : bits2, pc.qb1, L, lane, &index);
+                        }
+                        if (st == 0) st = band_build_result(out, G, pc.rA, cA, nA, index, pc.qb1, pc.rB, cB, nB, lane, A, c);
+                    }
                 }
             }
         }

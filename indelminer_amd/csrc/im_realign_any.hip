@@ -20,12 +20,17 @@
 //   a10 update_readsegs          src/readaln.c:348-458
 //   a11 new_evidence             src/evidence.c:4-34 (+ the reductions of src/variant.c:217-290,704-775)
 //
+// Shared with the laid-out kernels (im_realign_plan.hpp, run per lane here): the windows, the plan and the verdict for the
+// second piece, the choice of the A / B pieces.  This file's own: the band searches, the dynamic programs, the soft clips,
+// the split search over CIGARs (any_best_split) and the merge of pieces with inner I / D ops (any_build_result).
+//
 // Two launches: any_pick_kernel lists the reads the other kernels left (or, for numgaps > 60, every read) with the largest
 // read and window among them; the host sizes the arena from those and realign_any_kernel works the list off, every lane
 // of a wave claiming a read per round.  The result record's own bounds (IM_MAX_OPS segments, IM_MAX_EV indels per read) stay.
 
 #include "im_device.hpp"
 #include "im_wave.hpp"
+#include "im_realign_plan.hpp"
 
 namespace im {
 namespace {
@@ -776,16 +781,10 @@ __device__ void any_step_begin(const RealignArgs& R, int c, AnyRead& X)
     im_read_result* out = &R.batch.out[c];
     X.c = c; X.L = R.batch.read_len[c]; X.tid = R.batch.tid[c]; X.anchor = R.batch.anchor[c];
     const int range = R.batch.range_max[c], clen = R.ref.len[X.tid], anchor = X.anchor;
-    int distance = range;                                                             // 774-783
-    X.left1  = anchor >= distance ? anchor - distance : 0;
-    X.right1 = clen < (anchor + distance) ? clen : anchor + distance;
-    distance = range + (int)R.P.maxdelsize;
-    X.left2  = anchor >= distance ? anchor - distance : 0;
-    X.right2 = clen < (anchor + distance) ? clen : anchor + distance;
+    const Windows win = realign_windows(anchor, range, R.P.maxdelsize, clen);
+    X.left1 = win.left1; X.right1 = win.right1; X.left2 = win.left2; X.right2 = win.right2;
     X.stage = 1;
-    if (!(anchor >= X.left1 && anchor >= X.left2 && anchor <= X.right1 && anchor <= X.right2 && X.left2 >= 0 && X.right2 > 0)) {
-        any_finish(out, IM_ST_ABORT, 0); X.stage = 0;                                 // 548-553
-    }
+    if (!win.ok) { any_finish(out, IM_ST_ABORT, 0); X.stage = 0; }
 }
 
 // behind band search 1: the first alignment, the geometric case, the second search's window and piece
@@ -820,34 +819,9 @@ __device__ void any_step_middle(const AR& a, const AnyLayout& Y, const RealignAr
         l = (uint32_t)j;
     }
     X.f = f; X.l = l;
-    // piece 2 by the four geometric cases; the guards in unsigned arithmetic as written (605-717)
-    const uint32_t uL = (uint32_t)L;
-    const int right2 = X.right2, left2 = X.left2;
-    uint32_t w0, w1, anc, p0, p1; bool want_tail;
-    if (r1 > anchor) {
-        if (q1 == 0) {
-            if (!(uL > f)) { any_finish(out, IM_ST_ABORT, 1); return; }
-            if ((uL - f) < eth || ((uint32_t)right2 - (uint32_t)r1 - f) < eth) { any_finish(out, IM_ST_NONE, 1); return; }
-            w0 = (uint32_t)r1 + f; w1 = (uint32_t)right2; anc = (uint32_t)r1; p0 = f; p1 = uL; want_tail = true;
-        } else if (q2 == L) {
-            if (!(uL > l)) { any_finish(out, IM_ST_ABORT, 1); return; }
-            if ((uL - l) < eth || ((uint32_t)r2 - l - (uint32_t)anchor) < eth) { any_finish(out, IM_ST_NONE, 1); return; }
-            w0 = (uint32_t)anchor; w1 = (uint32_t)r2 - l; anc = (uint32_t)r2; p0 = 0; p1 = uL - l; want_tail = false;
-        } else { any_finish(out, IM_ST_NONE, 1); return; }
-    } else if (r1 < anchor) {
-        if (r2 >= anchor) { any_finish(out, IM_ST_NONE, 1); return; }
-        if (q1 == 0) {
-            if (!(uL > f)) { any_finish(out, IM_ST_ABORT, 1); return; }
-            if ((uL - f) < eth || ((uint32_t)anchor - (uint32_t)r1 - f) < eth) { any_finish(out, IM_ST_NONE, 1); return; }
-            w0 = (uint32_t)r1 + f; w1 = (uint32_t)anchor; anc = (uint32_t)r1; p0 = f; p1 = uL; want_tail = true;
-        } else if (q2 == L) {
-            if (!(uL > l)) { any_finish(out, IM_ST_ABORT, 1); return; }
-            if ((uL - l) < eth || ((uint32_t)r2 - l - (uint32_t)left2) < eth) { any_finish(out, IM_ST_NONE, 1); return; }
-            w0 = (uint32_t)left2; w1 = (uint32_t)r2 - l; anc = (uint32_t)r2; p0 = 0; p1 = uL - l; want_tail = false;
-        } else { any_finish(out, IM_ST_NONE, 1); return; }
-    } else { any_finish(out, IM_ST_NONE, 1); return; }                                // r1 == anchor (712-717)
-    if ((int32_t)(w1 - w0) <= 0) { any_finish(out, IM_ST_ABORT, 1); return; }
-    X.w0 = w0; X.w1 = w1; X.anc = anc; X.p0 = p0; X.p1 = p1; X.want_tail = want_tail;
+    const Piece2Plan pl = plan_piece2(r1, r2, q1, q2, f, l, L, anchor, X.left2, X.right2, eth);
+    if (pl.st != kStGoOn) { any_finish(out, pl.st, 1); return; }
+    X.w0 = pl.w0; X.w1 = pl.w1; X.anc = pl.anc; X.p0 = pl.p0; X.p1 = pl.p1; X.want_tail = pl.want_tail;
     X.stage = 2;
 }
 
@@ -868,8 +842,10 @@ __device__ void any_step_end(const AR& a, const AnyLayout& Y, const RealignArgs&
     any_store_band(out, 1, X.b2, a2, (int)(w1 - w0), (int)(p1 - p0));
     if (a2.st) { any_finish(out, a2.st, 2); return; }
     const int r3 = a2.r1, r4 = a2.r2, q3 = a2.q1, q4 = a2.q2; int n2 = a2.n_ops;
-    if (want_tail) { if (q4 != L || q3 == q4) { any_finish(out, IM_ST_NONE, 2); return; } }
-    else           { if (q3 != 0 || q3 == q4) { any_finish(out, IM_ST_NONE, 2); return; } }
+    // the verdict on the second alignment; its abort (720-721) waits behind the soft clips, whose own failures come first
+    // here as in the reference's order of statements
+    const int acc = accept_piece2(want_tail, q1, q2, q3, q4, L);
+    if (acc == IM_ST_NONE) { any_finish(out, IM_ST_NONE, 2); return; }
     // add_prefix_soft_clip / add_suffix_soft_clip (478-532)
     if (want_tail && f > 0) {
         const uint32_t w = a.atu(Y.o_ops1, 0);
@@ -883,17 +859,17 @@ __device__ void any_step_end(const AR& a, const AnyLayout& Y, const RealignArgs&
         else if (n2 >= IM_MAX_OPS) { any_finish(out, IM_ST_OVERFLOW, 2); return; }
         else { a.atu(Y.o_ops1, n2) = (l << 4) | IM_OP_S; n2++; }
     }
-    if (!(q1 < q2 && q3 < q4)) { any_finish(out, IM_ST_ABORT, 2); return; }           // 720-721
-    int st, index = -1;
-    if (q1 > q3 && q1 <= q4) {                                                        // 724-731
-        st = any_best_split(a, q3, q4, Y.o_ops1, n2, q1, q2, Y.o_ops0, n1, L, &index);
-        if (st == 0) st = any_build_result(a, Y, out, R, c, r3, Y.o_ops1, n2, index, q1, r1, Y.o_ops0, n1);
-    } else if (q3 > q1 && q3 <= q2) {                                                 // 732-739
-        st = any_best_split(a, q1, q2, Y.o_ops0, n1, q3, q4, Y.o_ops1, n2, L, &index);
-        if (st == 0) st = any_build_result(a, Y, out, R, c, r1, Y.o_ops0, n1, index, q3, r3, Y.o_ops1, n2);
-    } else if (q1 > q4 && r1 == r4) st = any_build_result(a, Y, out, R, c, r3, Y.o_ops1, n2, q4, q1, r1, Y.o_ops0, n1);       // 740-744
-    else if (q3 > q2 && r2 == r3) st = any_build_result(a, Y, out, R, c, r1, Y.o_ops0, n1, q2, q3, r3, Y.o_ops1, n2);         // 745-749
-    else st = IM_ST_NONE;
+    if (acc == IM_ST_ABORT) { any_finish(out, IM_ST_ABORT, 2); return; }
+    const Pieces pc = choose_pieces(q1, q2, q3, q4, r1, r2, r3, r4);
+    if (!pc.ok) { any_finish(out, IM_ST_NONE, 2); return; }
+    const bool as = pc.a_is_second;
+    const int32_t oA = as ? Y.o_ops1 : Y.o_ops0, oB = as ? Y.o_ops0 : Y.o_ops1;
+    const int nA = as ? n2 : n1, nB = as ? n1 : n2;
+    int st = 0, index = pc.qa2;
+    // find_best_del_candidate (306-339) tests that its first piece starts at read offset 0 (the band kernel also tests that
+    // the second ends at L, the numgaps == 0 kernels neither)
+    if (pc.split) st = any_best_split(a, as ? q3 : q1, pc.qa2, oA, nA, pc.qb1, as ? q2 : q4, oB, nB, L, &index);
+    if (st == 0) st = any_build_result(a, Y, out, R, c, pc.rA, oA, nA, index, pc.qb1, pc.rB, oB, nB);
     any_finish(out, st, 2);
 }
 

@@ -1,9 +1,15 @@
 // im_realign_long.hip -- split-read realignment of reads of 256 .. IM_MAX_READ bases (numgaps == 0).
 //
 // The same reference path as im_realign.hip (attempt_pe_alignment, src/alignment.c:764-799, with the band one
-// diagonal wide) in a second lane layout: lane l owns the SIXTEEN read positions 16l .. 16l+15, the k-mer table
-// stores 16-bit read offsets, the diagonal histogram counts in 16 bits (a 300-base read puts up to 295 votes on
-// its diagonal), and the per-position match flags of the two band alignments live in LDS instead of a register.
+// diagonal wide).
+//
+// Shared with the other realign kernels (im_realign_plan.hpp): the windows, the plan and the verdict for the second
+// piece, the choice of the A / B pieces, and the whole merge (merge_pieces<16>: split search, segment list, evidence).
+//
+// This file's own: the band search and the diagonal scan in a second lane layout.  Lane l owns the SIXTEEN read
+// positions 16l .. 16l+15, the k-mer table stores 16-bit read offsets, the diagonal histogram counts in 16 bits (a
+// 300-base read puts up to 295 votes on its diagonal), and the per-position match flags of the two band alignments
+// live in LDS instead of a register.
 // One wavefront per read, 23.3 KiB of LDS per wave.  The launch follows realign_kernel on the same stream when the
 // context was told that such reads occur (im_expect_read_length); reads of up to 255 bases are left to that kernel,
 // whose four-positions-per-lane layout is the fast one for them.
@@ -17,6 +23,7 @@
 
 #include "im_device.hpp"
 #include "im_wave.hpp"
+#include "im_realign_plan.hpp"
 
 namespace im {
 namespace {
@@ -301,15 +308,9 @@ __device__ void realign_long_one(LongLds& s, const RealignArgs& A, int c, int L,
     }
     wave_lds_sync();
 
-    // window geometry (src/alignment.c:774-783)
-    int distance = R;
-    const int left1  = anchor >= distance ? anchor - distance : 0;
-    const int right1 = clen < (anchor + distance) ? clen : anchor + distance;
-    distance = R + (int)A.P.maxdelsize;
-    const int left2  = anchor >= distance ? anchor - distance : 0;
-    const int right2 = clen < (anchor + distance) ? clen : anchor + distance;
-    if (!(anchor >= left1 && anchor >= left2 && anchor <= right1 && anchor <= right2 &&
-          left2 >= 0 && right2 > 0)) { finish(out, IM_ST_ABORT, 0, lane); return; }      // 548-553
+    const Windows win = realign_windows(anchor, R, A.P.maxdelsize, clen);
+    if (!win.ok) { finish(out, IM_ST_ABORT, 0, lane); return; }
+    const int left1 = win.left1, right1 = win.right1;
 
     // piece 1: the whole read in [left1,right1) (557-566)
     const LBand b1 = band_search_long<DIRECT>(s, pk, (uint32_t)left1, (uint32_t)right1, (uint32_t)anchor, 0u, (uint32_t)L, k, lane);
@@ -321,165 +322,34 @@ __device__ void realign_long_one(LongLds& s, const RealignArgs& A, int c, int L,
     if (q1 == q2) { finish(out, IM_ST_NONE, 1, lane); return; }                          // 568-572
     if (q1 == 0 && q2 == L) { finish(out, IM_ST_NONE, 1, lane); return; }                // 575-582: no I/D op without gaps
 
-    // piece 2: the rest of the read in the extended window, four cases (605-717)
-    const uint32_t uL = (uint32_t)L, f = (uint32_t)a1.f, l = (uint32_t)a1.l;
-    uint32_t w0, w1, anc, p0, p1; bool want_tail;
-    if (r1 > anchor) {
-        if (q1 == 0) {
-            if (!(uL > f)) { finish(out, IM_ST_ABORT, 1, lane); return; }
-            if ((uL - f) < eth || ((uint32_t)right2 - (uint32_t)r1 - f) < eth) { finish(out, IM_ST_NONE, 1, lane); return; }
-            w0 = (uint32_t)r1 + f; w1 = (uint32_t)right2; anc = (uint32_t)r1; p0 = f; p1 = uL; want_tail = true;
-        } else if (q2 == L) {
-            if (!(uL > l)) { finish(out, IM_ST_ABORT, 1, lane); return; }
-            if ((uL - l) < eth || ((uint32_t)r2 - l - (uint32_t)anchor) < eth) { finish(out, IM_ST_NONE, 1, lane); return; }
-            w0 = (uint32_t)anchor; w1 = (uint32_t)r2 - l; anc = (uint32_t)r2; p0 = 0; p1 = uL - l; want_tail = false;
-        } else { finish(out, IM_ST_NONE, 1, lane); return; }
-    } else if (r1 < anchor) {
-        if (r2 >= anchor) { finish(out, IM_ST_NONE, 1, lane); return; }
-        if (q1 == 0) {
-            if (!(uL > f)) { finish(out, IM_ST_ABORT, 1, lane); return; }
-            if ((uL - f) < eth || ((uint32_t)anchor - (uint32_t)r1 - f) < eth) { finish(out, IM_ST_NONE, 1, lane); return; }
-            w0 = (uint32_t)r1 + f; w1 = (uint32_t)anchor; anc = (uint32_t)r1; p0 = f; p1 = uL; want_tail = true;
-        } else if (q2 == L) {
-            if (!(uL > l)) { finish(out, IM_ST_ABORT, 1, lane); return; }
-            if ((uL - l) < eth || ((uint32_t)r2 - l - (uint32_t)left2) < eth) { finish(out, IM_ST_NONE, 1, lane); return; }
-            w0 = (uint32_t)left2; w1 = (uint32_t)r2 - l; anc = (uint32_t)r2; p0 = 0; p1 = uL - l; want_tail = false;
-        } else { finish(out, IM_ST_NONE, 1, lane); return; }
-    } else { finish(out, IM_ST_NONE, 1, lane); return; }                                  // r1 == anchor (712-717)
-    if ((int32_t)(w1 - w0) <= 0) { finish(out, IM_ST_ABORT, 1, lane); return; }
+    const Piece2Plan pl = plan_piece2(r1, r2, q1, q2, (uint32_t)a1.f, (uint32_t)a1.l, L, anchor, win.left2, win.right2, eth);
+    if (pl.st != kStGoOn) { finish(out, pl.st, 1, lane); return; }
+    const uint32_t w0 = pl.w0, w1 = pl.w1, p0 = pl.p0, p1 = pl.p1;
 
-    const LBand b2 = band_search_long<DIRECT>(s, pk, w0, w1, anc, p0, p1, k, lane);
+    const LBand b2 = band_search_long<DIRECT>(s, pk, w0, w1, pl.anc, p0, p1, k, lane);
     if (b2.st) { finish(out, b2.st, 2, lane); return; }
     const LAln a2 = diag_scan_long(s, 1, contig, w0, w1, p0, p1, b2.low, lane);
     store_band_long(out, 1, b2, a2, lane);
     if (a2.st) { finish(out, a2.st, 2, lane); return; }
     const int r3 = a2.r1, r4 = a2.r2, q3 = a2.q1, q4 = a2.q2;
-    if (want_tail) { if (q4 != L || q3 == q4) { finish(out, IM_ST_NONE, 2, lane); return; } }   // 623-627, 679-683
-    else           { if (q3 != 0 || q3 == q4) { finish(out, IM_ST_NONE, 2, lane); return; } }   // 645-649, 701-705
-    if (!(q1 < q2 && q3 < q4)) { finish(out, IM_ST_ABORT, 2, lane); return; }             // 720-721
+    const int acc = accept_piece2(pl.want_tail, q1, q2, q3, q4, L);
+    if (acc != kStGoOn) { finish(out, acc, 2, lane); return; }
+    const Pieces pc = choose_pieces(q1, q2, q3, q4, r1, r2, r3, r4);
+    if (!pc.ok) { finish(out, IM_ST_NONE, 2, lane); return; }
+    // find_best_del_candidate's assert that its first piece starts at read offset 0 (314-315) is not tested, as in
+    // realign_kernel: it holds by accept_piece2.
 
-    // combine (723-754).  "A" = the piece that starts at read offset 0, "B" = the one that ends at L.
-    int wa, wb;                         // which s.eq[] holds the A / B piece
-    int qa2, rA, qb1, rB;               // A = read[0,qa2) at contig rA.. ; B = read[qb1,L) at contig rB..
-    bool split;                         // true: overlapping pieces, choose the split point (K4)
-    if (q1 > q3 && q1 <= q4)        { wa = 1; qa2 = q4; rA = r3; wb = 0; qb1 = q1; rB = r1; split = true;  }
-    else if (q3 > q1 && q3 <= q2)   { wa = 0; qa2 = q2; rA = r1; wb = 1; qb1 = q3; rB = r3; split = true;  }
-    else if (q1 > q4 && r1 == r4)   { wa = 1; qa2 = q4; rA = r3; wb = 0; qb1 = q1; rB = r1; split = false; }
-    else if (q3 > q2 && r2 == r3)   { wa = 0; qa2 = q2; rA = r1; wb = 1; qb1 = q3; rB = r3; split = false; }
-    else { finish(out, IM_ST_NONE, 2, lane); return; }
-
-    // per-position match flags of A on [0,qa2) and B on [qb1,L), as bit masks of this lane's sixteen positions
-    const int x0 = kLB * lane;
-    uint32_t fa = 0, fb = 0;
+    // this lane's sixteen '=' flags of the A / B piece as bit masks, from s.eq[]
+    uint32_t eqA = 0, eqB = 0;
     {
         uint8_t ea[kLB], eb[kLB];
-        __builtin_memcpy(ea, &s.eq[wa][x0], kLB);
-        __builtin_memcpy(eb, &s.eq[wb][x0], kLB);
+        __builtin_memcpy(ea, &s.eq[pc.a_is_second ? 1 : 0][kLB * lane], kLB);
+        __builtin_memcpy(eb, &s.eq[pc.a_is_second ? 0 : 1][kLB * lane], kLB);
 #pragma unroll
-        for (int j = 0; j < kLB; j++) {
-            const int x = x0 + j;
-            fa |= (x < qa2 && ea[j]) ? 1u << j : 0u;
-            fb |= (x >= qb1 && x < L && eb[j]) ? 1u << j : 0u;
-        }
+        for (int j = 0; j < kLB; j++) { eqA |= ea[j] ? 1u << j : 0u; eqB |= eb[j] ? 1u << j : 0u; }
     }
-    const int ta = __popc(fa), tb = __popc(fb);
-    const int ia = wave_scan_add(ta, lane), ib = wave_scan_add(tb, lane);
-    const int totA = __builtin_amdgcn_readlane(ia, 63), totB = __builtin_amdgcn_readlane(ib, 63);
-    const int ea0 = ia - ta, eb0 = ib - tb;             // '=' of A / B in front of x0
-
-    int index, nextindex, matches;
-    if (split) {
-        // count_matches(i) = '=' of A in read[0,i) + '=' of B in read[i,L); X counts are L - that, so "max matches,
-        // then min mismatches, first wins" is the first maximum.
-        int bs = -1, bx = INT_MAX;
-#pragma unroll
-        for (int j = 0; j < kLB; j++) {
-            const int x = x0 + j;
-            if (x >= qb1 && x <= qa2) {
-                const uint32_t below = (1u << j) - 1u;
-                const int sc = ea0 + __popc(fa & below) + (totB - eb0 - __popc(fb & below));
-                if (sc > bs) { bs = sc; bx = x; }
-            }
-        }
-        const int best = wave_max(bs);
-        index = wave_min(bs == best ? bx : INT_MAX);
-        if (best < 0 || index == INT_MAX) { finish(out, IM_ST_ABORT, 2, lane); return; }   // forceassert(index != -1)
-        nextindex = index;
-        matches = best;
-    } else {
-        index = qa2; nextindex = qb1;
-        matches = totA + totB;
-    }
-
-    // update_readsegs (src/readaln.c:348-458) in closed form: A's runs over [0,index), an I of nextindex-index bases if
-    // the pieces leave read bases uncovered, a D if the reference positions leave a gap, then B's runs over [nextindex,L).
-    const int refindx = rA + index;
-    const int rindex  = rB + (nextindex - qb1);
-    const bool hasI = nextindex > index;
-    const bool hasD = refindx < rindex;
-    if (!hasI && !hasD) { finish(out, IM_ST_NONE, 2, lane); return; }                      // no D/I segment -> NULL
-
-    // run-length encode the final per-position classes
-    int cls[kLB];
-#pragma unroll
-    for (int j = 0; j < kLB; j++) {
-        const int x = x0 + j;
-        cls[j] = (x >= L) ? -1 : (x < index) ? (((fa >> j) & 1u) ? IM_OP_EQ : IM_OP_X)
-                 : (x < nextindex) ? IM_OP_I : (((fb >> j) & 1u) ? IM_OP_EQ : IM_OP_X);
-    }
-    const int prevc = dpp_mov<kDppWaveShr1>(-2, cls[kLB - 1]);      // lane 0 keeps -2
-    uint32_t bnd = 0;
-#pragma unroll
-    for (int j = 0; j < kLB; j++) {
-        const int x = x0 + j;
-        const int pc = (j == 0) ? prevc : cls[j - 1];
-        if ((x < L) && (x == 0 || x == index || x == nextindex || cls[j] != pc)) bnd |= 1u << j;
-    }
-    const int nb = __popc(bnd);
-    const int inb = wave_scan_add(nb, lane);
-    const int total_b = __builtin_amdgcn_readlane(inb, 63);
-    const int n_ops = total_b + (hasD ? 1 : 0);
-    if (n_ops > IM_MAX_OPS) { finish(out, IM_ST_OVERFLOW, 2, lane); return; }
-    // run length = distance to the next boundary
-    {
-        int kk = inb - nb;
-#pragma unroll
-        for (int j = 0; j < kLB; j++) if ((bnd >> j) & 1u) s.bpos[kk++] = x0 + j;
-        if (lane == 0) s.bpos[total_b] = L;
-    }
-    wave_lds_sync();
-    int slot = inb - nb;                 // boundaries before this lane
-    int seg_indel = 0;
-#pragma unroll
-    for (int j = 0; j < kLB; j++) {
-        const int x = x0 + j;
-        if ((bnd >> j) & 1u) {
-            const int sl = slot + ((hasD && x >= nextindex) ? 1 : 0);
-            out->ops[sl] = ((uint32_t)(s.bpos[slot + 1] - x) << 4) | (uint32_t)cls[j];
-            if (x == index) seg_indel = slot;       // the I run itself, or the run the D op goes in front of
-            slot++;
-        }
-    }
-    seg_indel = wave_max(seg_indel);     // only one lane set it (others 0); slot >= 1 there
-    if (lane == 0) {
-        if (hasD) out->ops[seg_indel] = ((uint32_t)(rindex - refindx) << 4) | IM_OP_D;
-        im_evidence* e = &out->ev[0];
-        e->cls = hasD ? IM_CLS_DELETION : IM_CLS_INSERTION;
-        e->b1 = refindx; e->b2 = hasD ? rindex : refindx;
-        e->lflank = index; e->rflank = L - nextindex;
-        e->seg = seg_indel;
-        e->read_off = index;
-        // X bases left in aln1 + aln3: aligned bases minus '=' bases
-        const int aligned = index + (L - nextindex);
-        e->nd_print = aligned - matches;
-        e->nd_filter = aligned - matches;
-        out->ref_start = rA;
-        out->n_ops = n_ops;
-        out->n_ev = 1;
-        out->status = IM_ST_EVIDENCE;
-        out->n_band = 2;
-    }
-    write_slots(A, c, 1, hasD ? IM_CLS_DELETION : IM_CLS_INSERTION, refindx, hasD ? rindex : refindx, lane);
+    const int st = merge_pieces<kLB>(eqA, eqB, pc.qa2, pc.rA, pc.qb1, pc.rB, pc.split, L, s.bpos, out, A, c, lane);
+    if (st != IM_ST_EVIDENCE) { finish(out, st, 2, lane); return; }
     wave_lds_sync();
 }
 
