@@ -14,6 +14,14 @@
 #include <mutex>
 #include <atomic>
 
+// One contig's difference array of the record-at-a-time path (im_depth_build, im_span_build): cap ints of data and the sums
+// im::depth_sums_ints gives for cap - 1 positions (it grows with the contig, so they serve every shorter one); len < 0: not built
+struct ContigArray {
+    int32_t* data = nullptr;
+    int32_t* sums = nullptr;
+    int64_t cap = 0, len = -1;
+};
+
 struct im_ctx {
     int device = -1;
     int n_cu = 0;
@@ -35,10 +43,8 @@ struct im_ctx {
     size_t pin_bytes = 0;
     hipStream_t copy_stream = nullptr, back_stream = nullptr;     // host -> device, device -> host
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_k[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    // resident depth array of the current contig (im_depth_build)
-    int32_t* depth = nullptr;
-    int32_t* depth_sums = nullptr;
-    int64_t depth_cap = 0, depth_len = -1;
+    // resident depth and span arrays of the current contig (im_depth_build, im_span_build)
+    ContigArray depth, span;
     // host copies of the reference layout
     std::vector<int64_t> h_asc_off;
     std::vector<int32_t> h_len;
@@ -50,10 +56,6 @@ struct im_ctx {
     int32_t* gspan = nullptr;
     int32_t* gspan_sums = nullptr;
     int32_t span_flank = 0, span_min_mapq = 0;
-    // resident span array of the current contig (im_span_build)
-    int32_t* span = nullptr;
-    int32_t* span_sums = nullptr;
-    int64_t span_cap = 0, span_len = -1;
     bool support_count_attr = false;    // im_support_count: its kernel's LDS attribute has been set on this context's device
     std::mutex gb_mu;
     std::unordered_map<void*, int32_t> gb_layout;   // group-by scratch -> the slot count it was initialised (and is carved) for
@@ -141,6 +143,81 @@ void free_reference(im_ctx* ctx)
     ctx->h_asc_off.clear(); ctx->h_len.clear(); ctx->ref_total = 0;
 }
 
+void free_array(ContigArray& a)
+{
+    if (a.data) (void)hipFree(a.data);
+    if (a.sums) (void)hipFree(a.sums);
+    a = ContigArray();
+}
+
+// im_depth_build / im_span_build behind their argument checks: grow, stage the intervals, memset + scatter + scan (one launcher,
+// im_depth.hip), wait
+int build_array(im_ctx* ctx, ContigArray& a, int64_t clen, int32_t n, const int32_t* start, const int32_t* len, int32_t lo, int32_t hi)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    a.len = -1;
+    if (clen + 1 > a.cap) {
+        free_array(a);
+        HIP_TRY(ctx, hipMalloc((void**)&a.data, (size_t)(clen + 1) * sizeof(int32_t)));
+        HIP_TRY(ctx, hipMalloc((void**)&a.sums, (size_t)im::depth_sums_ints(clen) * sizeof(int32_t)));     // zeroed by every build
+        a.cap = clen + 1;
+    }
+    const size_t sb = up256(sizeof(int32_t) * (size_t)(n ? n : 1));
+    int rc = ensure_ws(ctx, 2 * sb);
+    if (rc) return rc;
+    int32_t* d_start = (int32_t*)ctx->ws;
+    int32_t* d_len = (int32_t*)((char*)ctx->ws + sb);
+    if (n > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_start, start, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_len, len, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(ctx, im::launch_depth_build(clen, n, d_start, d_len, lo, hi, a.data, a.sums, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    a.len = clen;
+    return IM_OK;
+}
+
+// the queries' trip through the context's workspace and stream, n > 0: [beg][end] in, one launch on a scanned array, out back.
+// minimum: the span query (out = the minimum over [beg, end]); otherwise the depth query (out = the sum over [beg, end), and
+// max_out, where not null, the deepest position of [beg - 1, end])
+int query_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, const int32_t* data, const int32_t* sums, int64_t clen,
+                bool minimum, uint32_t* out, uint32_t* max_out)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = up256(sizeof(int32_t) * (size_t)n);
+    int rc = ensure_ws(ctx, 4 * sb);
+    if (rc) return rc;
+    int32_t* d_beg = (int32_t*)ctx->ws;
+    int32_t* d_end = (int32_t*)((char*)ctx->ws + sb);
+    uint32_t* d_out = (uint32_t*)((char*)ctx->ws + 2 * sb);
+    uint32_t* d_max = max_out ? (uint32_t*)((char*)ctx->ws + 3 * sb) : nullptr;
+    HIP_TRY(ctx, hipMemcpyAsync(d_beg, beg, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_end, end, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if (minimum) HIP_TRY(ctx, im::launch_span_query(n, d_beg, d_end, data, sums, clen, d_out, ctx->stream));
+    else HIP_TRY(ctx, im::launch_depth_query_tiled(n, d_beg, d_end, data, sums, clen, d_out, d_max, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (max_out) HIP_TRY(ctx, hipMemcpyAsync(max_out, d_max, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+// im_depth_enable / im_span_enable: a genome-wide array (one int32 per byte of ref_ascii) and its sums, zeroed.  Each contig has
+// its own run of sums (scans of different contigs may be in flight on different streams), at the same place in both arrays
+int enable_genome_array(im_ctx* ctx, int32_t** data, int32_t** sums)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int64_t ints = 0;
+    std::vector<int64_t> sums_off;
+    for (int32_t l : ctx->h_len) { sums_off.push_back(ints); ints += im::depth_sums_ints(l); }
+    ctx->h_sums_off = sums_off;
+    HIP_TRY(ctx, hipMalloc((void**)data, (size_t)ctx->ref_total * sizeof(int32_t)));
+    HIP_TRY(ctx, hipMalloc((void**)sums, (size_t)(ints + 1) * sizeof(int32_t)));
+    HIP_TRY(ctx, hipMemsetAsync(*data, 0, (size_t)ctx->ref_total * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(*sums, 0, (size_t)(ints + 1) * sizeof(int32_t), ctx->stream));      // the arrival counters start at zero
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -183,10 +260,8 @@ void im_ctx_destroy(im_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     free_reference(ctx);
     if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->depth) (void)hipFree(ctx->depth);
-    if (ctx->depth_sums) (void)hipFree(ctx->depth_sums);
-    if (ctx->span) (void)hipFree(ctx->span);
-    if (ctx->span_sums) (void)hipFree(ctx->span_sums);
+    free_array(ctx->depth);
+    free_array(ctx->span);
     if (ctx->rg_blob) (void)hipFree(ctx->rg_blob);
     if (ctx->any_list) (void)hipFree(ctx->any_list);
     if (ctx->any_counters) (void)hipFree(ctx->any_counters);
@@ -548,16 +623,7 @@ int im_depth_enable(im_ctx* ctx)
     if (!ctx) return IM_E_ARG;
     if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
     if (ctx->gdepth) return IM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int64_t tiles = 0;
-    ctx->h_sums_off.clear();
-    for (int32_t l : ctx->h_len) { ctx->h_sums_off.push_back(tiles); tiles += im::depth_sums_ints(l); }
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->gdepth, (size_t)ctx->ref_total * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->gdepth_sums, (size_t)(tiles + 1) * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->gdepth, 0, (size_t)ctx->ref_total * sizeof(int32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->gdepth_sums, 0, (size_t)(tiles + 1) * sizeof(int32_t), ctx->stream));      // the arrival counters start at zero
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return IM_OK;
+    return enable_genome_array(ctx, &ctx->gdepth, &ctx->gdepth_sums);
 }
 
 int im_depth_scan(im_ctx* ctx, int32_t tid, void* stream)
@@ -596,21 +662,7 @@ int im_depth_query_max_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* b
 {
     if (!ctx || n < 0 || !ctx->gdepth || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
     if (n == 0) return IM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = up256(sizeof(int32_t) * (size_t)n);
-    int rc = ensure_ws(ctx, 4 * sb);
-    if (rc) return rc;
-    int32_t* d_beg = (int32_t*)ctx->ws;
-    int32_t* d_end = (int32_t*)((char*)ctx->ws + sb);
-    uint32_t* d_out = (uint32_t*)((char*)ctx->ws + 2 * sb);
-    uint32_t* d_max = max_out ? (uint32_t*)((char*)ctx->ws + 3 * sb) : nullptr;
-    HIP_TRY(ctx, hipMemcpyAsync(d_beg, beg, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_end, end, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, im::launch_depth_query_tiled(n, d_beg, d_end, ctx->gdepth + ctx->h_asc_off[tid], ctx->gdepth_sums + ctx->h_sums_off[tid], ctx->h_len[tid], d_out, d_max, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(sum_out, d_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (max_out) HIP_TRY(ctx, hipMemcpyAsync(max_out, d_max, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return IM_OK;
+    return query_array(ctx, n, beg, end, ctx->gdepth + ctx->h_asc_off[tid], ctx->gdepth_sums + ctx->h_sums_off[tid], ctx->h_len[tid], false, sum_out, max_out);
 }
 
 int im_depth_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out)
@@ -735,47 +787,15 @@ int im_realign_batch(im_ctx* ctx, const im_params* params, const im_read_batch* 
 int im_depth_build(im_ctx* ctx, int64_t contig_len, int32_t n_seg, const int32_t* seg_start, const int32_t* seg_len)
 {
     if (!ctx || contig_len < 0 || n_seg < 0) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (contig_len + 1 > ctx->depth_cap) {
-        if (ctx->depth) { HIP_TRY(ctx, hipFree(ctx->depth)); ctx->depth = nullptr; }
-        if (ctx->depth_sums) { HIP_TRY(ctx, hipFree(ctx->depth_sums)); ctx->depth_sums = nullptr; }
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->depth, (size_t)(contig_len + 1) * sizeof(int32_t)));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->depth_sums, (size_t)(im::depth_tiles(contig_len) + 1) * sizeof(int32_t)));
-        ctx->depth_cap = contig_len + 1;
-    }
-    const size_t sb = up256(sizeof(int32_t) * (size_t)(n_seg ? n_seg : 1));
-    int rc = ensure_ws(ctx, 2 * sb);
-    if (rc) return rc;
-    int32_t* d_start = (int32_t*)ctx->ws;
-    int32_t* d_len = (int32_t*)((char*)ctx->ws + sb);
-    if (n_seg > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(d_start, seg_start, sizeof(int32_t) * (size_t)n_seg, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_len, seg_len, sizeof(int32_t) * (size_t)n_seg, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(ctx, im::launch_depth_build(contig_len, n_seg, d_start, d_len, ctx->depth, ctx->depth_sums, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->depth_len = contig_len;
-    return IM_OK;
+    return build_array(ctx, ctx->depth, contig_len, n_seg, seg_start, seg_len, 0, 0);
 }
 
 int im_depth_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out)
 {
     if (!ctx || n < 0) return IM_E_ARG;
-    if (ctx->depth_len < 0) { set_err(ctx, "im_depth_build has not been called"); return IM_E_ARG; }
+    if (ctx->depth.len < 0) { set_err(ctx, "im_depth_build has not been called"); return IM_E_ARG; }
     if (n == 0) return IM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = up256(sizeof(int32_t) * (size_t)n);
-    int rc = ensure_ws(ctx, 3 * sb);
-    if (rc) return rc;
-    int32_t* d_beg = (int32_t*)ctx->ws;
-    int32_t* d_end = (int32_t*)((char*)ctx->ws + sb);
-    uint32_t* d_out = (uint32_t*)((char*)ctx->ws + 2 * sb);
-    HIP_TRY(ctx, hipMemcpyAsync(d_beg, beg, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_end, end, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, im::launch_depth_query(n, d_beg, d_end, ctx->depth, ctx->depth_len, d_out, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(sum_out, d_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return IM_OK;
+    return query_array(ctx, n, beg, end, ctx->depth.data, ctx->depth.sums, ctx->depth.len, false, sum_out, nullptr);
 }
 
 // ---- reference-spanning read counts (the genotype columns) ------------------------------------
@@ -789,17 +809,8 @@ int im_span_enable(im_ctx* ctx, int32_t flank, int32_t min_mapq)
         if (flank != ctx->span_flank || min_mapq != ctx->span_min_mapq) { set_err(ctx, "im_span_enable: already enabled with flank %d, min_mapq %d", ctx->span_flank, ctx->span_min_mapq); return IM_E_ARG; }
         return IM_OK;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // each contig's run of tile sums lies where im_depth_enable puts the depth array's (the two arrays share the layout)
-    int64_t tiles = 0;
-    std::vector<int64_t> sums_off;
-    for (int32_t l : ctx->h_len) { sums_off.push_back(tiles); tiles += im::depth_sums_ints(l); }
-    ctx->h_sums_off = sums_off;
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->gspan, (size_t)ctx->ref_total * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->gspan_sums, (size_t)(tiles + 1) * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->gspan, 0, (size_t)ctx->ref_total * sizeof(int32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->gspan_sums, 0, (size_t)(tiles + 1) * sizeof(int32_t), ctx->stream));       // the arrival counters start at zero
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    int rc = enable_genome_array(ctx, &ctx->gspan, &ctx->gspan_sums);
+    if (rc) return rc;
     ctx->span_flank = flank; ctx->span_min_mapq = min_mapq;
     return IM_OK;
 }
@@ -833,67 +844,28 @@ int im_span_reset(im_ctx* ctx, int32_t tid, void* stream)
     return IM_OK;
 }
 
-// the queries' trip: [beg][end] in, [min] out through the context's workspace and stream
-static int span_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums, int64_t clen, uint32_t* min_out)
-{
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = up256(sizeof(int32_t) * (size_t)n);
-    int rc = ensure_ws(ctx, 3 * sb);
-    if (rc) return rc;
-    int32_t* d_beg = (int32_t*)ctx->ws;
-    int32_t* d_end = (int32_t*)((char*)ctx->ws + sb);
-    uint32_t* d_out = (uint32_t*)((char*)ctx->ws + 2 * sb);
-    HIP_TRY(ctx, hipMemcpyAsync(d_beg, beg, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_end, end, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, im::launch_span_query(n, d_beg, d_end, span, sums, clen, d_out, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(min_out, d_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return IM_OK;
-}
-
 int im_span_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
 {
     if (!ctx || n < 0 || !ctx->gspan || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
     if (n == 0) return IM_OK;
     if (!beg || !end || !min_out) return IM_E_ARG;
-    return span_query(ctx, n, beg, end, ctx->gspan + ctx->h_asc_off[tid], ctx->gspan_sums + ctx->h_sums_off[tid], ctx->h_len[tid], min_out);
+    return query_array(ctx, n, beg, end, ctx->gspan + ctx->h_asc_off[tid], ctx->gspan_sums + ctx->h_sums_off[tid], ctx->h_len[tid], true, min_out, nullptr);
 }
 
 int im_span_build(im_ctx* ctx, int64_t contig_len, int32_t n_run, const int32_t* run_start, const int32_t* run_len, int32_t flank)
 {
     if (!ctx || contig_len < 0 || contig_len > 0x7fffff00LL || n_run < 0 || (n_run > 0 && (!run_start || !run_len))) return IM_E_ARG;
     if (flank < 1) { set_err(ctx, "im_span_build: flank %d, must be >= 1", flank); return IM_E_ARG; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (contig_len + 1 > ctx->span_cap) {
-        if (ctx->span) { HIP_TRY(ctx, hipFree(ctx->span)); ctx->span = nullptr; }
-        if (ctx->span_sums) { HIP_TRY(ctx, hipFree(ctx->span_sums)); ctx->span_sums = nullptr; }
-        ctx->span_cap = 0; ctx->span_len = -1;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->span, (size_t)(contig_len + 1) * sizeof(int32_t)));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->span_sums, (size_t)(im::depth_tiles(contig_len) + 1) * sizeof(int32_t)));
-        ctx->span_cap = contig_len + 1;
-    }
-    const size_t sb = up256(sizeof(int32_t) * (size_t)(n_run ? n_run : 1));
-    int rc = ensure_ws(ctx, 2 * sb);
-    if (rc) return rc;
-    int32_t* d_start = (int32_t*)ctx->ws;
-    int32_t* d_len = (int32_t*)((char*)ctx->ws + sb);
-    if (n_run > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(d_start, run_start, sizeof(int32_t) * (size_t)n_run, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_len, run_len, sizeof(int32_t) * (size_t)n_run, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(ctx, im::launch_span_build(contig_len, n_run, d_start, d_len, flank, ctx->span, ctx->span_sums, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->span_len = contig_len;
-    return IM_OK;
+    return build_array(ctx, ctx->span, contig_len, n_run, run_start, run_len, flank, flank - 1);
 }
 
 int im_span_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
 {
     if (!ctx || n < 0) return IM_E_ARG;
-    if (ctx->span_len < 0) { set_err(ctx, "im_span_build has not been called"); return IM_E_ARG; }
+    if (ctx->span.len < 0) { set_err(ctx, "im_span_build has not been called"); return IM_E_ARG; }
     if (n == 0) return IM_OK;
     if (!beg || !end || !min_out) return IM_E_ARG;
-    return span_query(ctx, n, beg, end, ctx->span, nullptr, ctx->span_len, min_out);
+    return query_array(ctx, n, beg, end, ctx->span.data, ctx->span.sums, ctx->span.len, true, min_out, nullptr);
 }
 
 int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64_t* t_off,

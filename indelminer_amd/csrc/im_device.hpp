@@ -74,8 +74,16 @@ hipError_t launch_flush_groupby(int32_t n_slots_layout, int32_t n_fl_layout, con
                                 const int32_t* cand_rec, const int32_t* n_cand_dev, int32_t cand_cap, int32_t pe_base, int32_t pe_count,
                                 int32_t tie_desc, int32_t* order, int32_t* cl_key, int32_t* cl_first, int32_t* cl_count, int32_t* counts,
                                 void* scratch, hipStream_t stream);
-hipError_t launch_depth_scan(int32_t* depth, int64_t n, int32_t* sums, hipStream_t stream);
+
+// im_depth.hip: a contig's difference array (clen + 1 ints: the depth array, the span array) and its tile sums; the file's header
+// has the one rule for sums.  After the scan the array is tile-local: the value at p is data[p] + sums[p / kScanTile].
+constexpr int kScanTile = 8192;
+int64_t depth_sums_ints(int64_t clen);
 hipError_t launch_depth_scan_tiled(int32_t* depth, int64_t n, int32_t* sums, hipStream_t stream);
+// memset + interval scatter (+1 at a + lo, -1 at b - hi of every clipped [a, b) with a + lo < b - hi) + scan; zeroes sums itself
+hipError_t launch_depth_build(int64_t clen, int32_t n_seg, const int32_t* seg_start, const int32_t* seg_len, int32_t lo, int32_t hi,
+                              int32_t* data, int32_t* sums, hipStream_t stream);
+// sum over [beg, end); out_max (may be null): the deepest position of [beg - 1, end]
 hipError_t launch_depth_query_tiled(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* depth, const int32_t* sums,
                                     int64_t clen, uint32_t* out, uint32_t* out_max, hipStream_t stream);
 
@@ -99,19 +107,9 @@ hipError_t launch_realign_any(const RealignArgs& a, const int32_t* list, int32_t
 hipError_t launch_compact_results(const im_read_result* res, int32_t n_cap, const int32_t* n_dev, int32_t* status, int32_t* slot,
                                   im_read_result* compact, int32_t* count, int n_cu, hipStream_t stream);
 
-hipError_t launch_depth_build(int64_t clen, int32_t n_seg, const int32_t* seg_start, const int32_t* seg_len,
-                              int32_t* depth, int32_t* sums, hipStream_t stream);
-int64_t depth_tiles(int64_t clen);
-int64_t depth_sums_ints(int64_t clen);
-hipError_t launch_depth_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* depth, int64_t clen,
-                              uint32_t* out, hipStream_t stream);
-int64_t depth_tile_positions();     // positions per tile of launch_depth_scan_tiled (a tile's offset lies at sums[p / that])
-
-// im_span.hip: reference-spanning read counts (the genotype columns); the array has the depth array's layout and scans
+// im_span.hip: reference-spanning read counts (the genotype columns); the array has the depth array's layout, build and scan
 hipError_t launch_span_scatter(const RefDev& ref, int32_t flank, int32_t min_mapq, const im_dev_records& recs, int32_t* diff, hipStream_t stream);
-hipError_t launch_span_build(int64_t clen, int32_t n_run, const int32_t* run_start, const int32_t* run_len, int32_t flank,
-                             int32_t* span, int32_t* sums, hipStream_t stream);
-// minimum over [beg, end] inclusive; sums: the tile offsets of launch_depth_scan_tiled, or null for an array of whole prefix sums
+// minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);
 

@@ -10,9 +10,10 @@
 //   front of base p.  As a difference array a run with e - s >= 2 m adds +1 at s + m and -1 at e - m + 1 (<= clen as m >= 1).
 // The array has the depth array's layout (im_depth.hip): per contig clen + 1 entries, scanned by the same tiled scan.
 //   span_scatter   one lane per delivered record: runs -> events, gathered in an LDS window, written out with vector atomics
-//   (scan)         launch_depth_scan_tiled / launch_depth_scan, as they are
+//   (scan)         launch_depth_scan_tiled, as it is
 //   span_query     one wave per query: minimum of span[p] over [beg, end] inclusive
-//   span_scatter_runs   the same events from host-given (start, length) runs, for the record-at-a-time path
+// The record-at-a-time path hands over (start, length) runs instead of records: launch_depth_build(lo = m, hi = m - 1) makes the
+// same events from them.
 
 #include "im_device.hpp"
 
@@ -148,24 +149,10 @@ __global__ __launch_bounds__(kSpanBlock) void span_scatter_kernel(SpanArgs A)
     }
 }
 
-// host-given runs [start, start + len) of one contig (the record-at-a-time path)
-__global__ __launch_bounds__(256) void span_scatter_runs_kernel(int32_t n_run, const int32_t* __restrict__ start, const int32_t* __restrict__ len,
-                                                               int64_t clen, int64_t m, int32_t* __restrict__ diff)
-{
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_run; i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t a = start[i], b = (int64_t)start[i] + len[i];
-        if (a < 0) a = 0;
-        if (b > clen) b = clen;
-        if (b - a < 2 * m) continue;
-        atomicAdd(&diff[a + m], 1);
-        atomicAdd(&diff[b - m + 1], -1);
-    }
-}
-
 // One wave per query: the minimum of span[p] over [beg, end] INCLUSIVE, clipped to [0, clen]; an interval that is empty after
-// the clip answers 0.  sums: the tile offsets of the tiled scan (null: the array holds whole prefix sums).
+// the clip answers 0.  sums: the tile offsets of the tiled scan.
 __global__ __launch_bounds__(256) void span_query_kernel(int32_t nq, const int32_t* __restrict__ beg, const int32_t* __restrict__ end,
-                                                        const int32_t* __restrict__ span, const int32_t* __restrict__ sums, int32_t tile,
+                                                        const int32_t* __restrict__ span, const int32_t* __restrict__ sums,
                                                         int64_t clen, uint32_t* __restrict__ out)
 {
     const int lane = threadIdx.x & 63;
@@ -176,10 +163,7 @@ __global__ __launch_bounds__(256) void span_query_kernel(int32_t nq, const int32
         if (a < 0) a = 0;
         if (b > clen) b = clen;
         uint32_t mn = 0xFFFFFFFFu;
-        for (int64_t p = a + lane; p <= b; p += 64) {
-            const uint32_t v = (uint32_t)(span[p] + (sums ? sums[p / tile] : 0));
-            mn = min(mn, v);
-        }
+        for (int64_t p = a + lane; p <= b; p += 64) mn = min(mn, (uint32_t)(span[p] + sums[p / kScanTile]));
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, o));
         if (lane == 0) out[q] = a <= b ? mn : 0u;
@@ -199,27 +183,13 @@ hipError_t launch_span_scatter(const RefDev& ref, int32_t flank, int32_t min_map
     return hipGetLastError();
 }
 
-hipError_t launch_span_build(int64_t clen, int32_t n_run, const int32_t* run_start, const int32_t* run_len, int32_t flank,
-                             int32_t* span /* clen + 1 */, int32_t* sums /* tiles */, hipStream_t stream)
-{
-    const int64_t n = clen + 1;
-    hipError_t e = hipMemsetAsync(span, 0, (size_t)n * sizeof(int32_t), stream);
-    if (e != hipSuccess) return e;
-    if (n_run > 0) {
-        int64_t b = ((int64_t)n_run + 255) / 256;
-        if (b > 4096) b = 4096;
-        hipLaunchKernelGGL(span_scatter_runs_kernel, dim3((int)b), dim3(256), 0, stream, n_run, run_start, run_len, clen, (int64_t)flank, span);
-    }
-    return launch_depth_scan(span, n, sums, stream);
-}
-
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream)
 {
     if (nq <= 0) return hipSuccess;
     int b = (nq + 3) / 4;
     if (b > 2048) b = 2048;
-    hipLaunchKernelGGL(span_query_kernel, dim3(b), dim3(256), 0, stream, nq, beg, end, span, sums, (int32_t)depth_tile_positions(), clen, out);
+    hipLaunchKernelGGL(span_query_kernel, dim3(b), dim3(256), 0, stream, nq, beg, end, span, sums, clen, out);
     return hipGetLastError();
 }
 

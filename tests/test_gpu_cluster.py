@@ -185,6 +185,49 @@ def test_depth_matches_numpy(gpu_ctx):
         assert np.array_equal(got, want)
 
 
+def _depth_case(ctx, rng, clen, nseg):
+    """one im_depth_build on ctx against numpy: every position, the whole contig, and range sums clipped at both ends"""
+    start = rng.integers(-50, clen + 20, nseg).astype(np.int32)
+    ln = rng.integers(1, 101, nseg).astype(np.int32)
+    ctx.depth_build(clen, start, ln)
+    diff = np.zeros(clen + 1, np.int64)
+    a = np.clip(start.astype(np.int64), 0, clen); b = np.clip(start.astype(np.int64) + ln, 0, clen)
+    ok = a < b
+    np.add.at(diff, a[ok], 1); np.add.at(diff, b[ok], -1)
+    depth = np.cumsum(diff)[:clen]
+    csum = np.concatenate([[0], np.cumsum(depth)])
+    p = np.arange(clen, dtype=np.int32)
+    assert np.array_equal(ctx.depth_query(p, p + 1), depth.astype(np.uint32)), clen
+    qb = np.concatenate([rng.integers(-300, clen + 300, 500), [-5, -40, 0, clen - 1, clen, clen + 3, -9]])
+    qe = np.concatenate([qb[:500] + rng.integers(0, 1200, 500), [clen + 7, 30, clen, clen + 1, clen + 50, clen + 90, -2]])
+    ca, cb = np.clip(qb, 0, clen), np.clip(qe, 0, clen)
+    want = np.where(ca < cb, csum[cb] - csum[ca], 0).astype(np.uint32)
+    assert np.array_equal(ctx.depth_query(qb.astype(np.int32), qe.astype(np.int32)), want), clen
+    return start, ln, depth
+
+
+def test_depth_build_contigs_in_sequence_and_tile_edges():
+    """im_depth_build call after call on ONE context, exact against numpy: contigs that grow, shrink and grow again (the array is
+    reallocated, and a shorter contig's arrival counters lie where a longer one's tile offsets were), clen + 1 a multiple of the
+    scan's 8192-position tile, 32 / 33 / 1025 tiles (the edges of the two-level arrival count and of the 1024-wide offset pass),
+    an empty build, and the same build three times over."""
+    from indelminer_amd import capi
+    rng = np.random.default_rng(12)
+    ctx = capi.Context(0)
+    try:
+        for clen, nseg in ((5000, 800), (3_000_000, 900_000), (100, 40), (3_000_001, 900_000),
+                           (8191, 3000), (32 * 8192 - 1, 80_000), (32 * 8192, 80_000), (1024 * 8192, 1_200_000), (70_000, 0)):
+            _depth_case(ctx, rng, clen, nseg)
+        clen = 33 * 8192 - 1
+        start, ln, depth = _depth_case(ctx, rng, clen, 90_000)
+        p = np.arange(clen, dtype=np.int32)
+        for _again in range(3):
+            ctx.depth_build(clen, start, ln)
+            assert np.array_equal(ctx.depth_query(p, p + 1), depth.astype(np.uint32))
+    finally:
+        ctx.close()
+
+
 def test_support_sw_matches_oracle(gpu_ctx):
     """Annotate-mode SW (K7): forward-carried path statistics vs the oracle's full-matrix DP +
     traceback on random target/query pairs (planted indels, substitutions, lengths up to 255 x 1500)."""

@@ -355,6 +355,57 @@ def test_span_host_segments_form():
         ctx.close()
 
 
+def span_of_run_arrays(start, length, clen, m):
+    """span_of_runs on arrays (the large contigs below); the test checks it against span_of_runs itself first"""
+    a = np.clip(start.astype(np.int64), 0, clen); b = np.clip(start.astype(np.int64) + length, 0, clen)
+    ok = b - a >= 2 * m
+    d = np.zeros(clen + 2, np.int64)
+    np.add.at(d, a[ok] + m, 1); np.add.at(d, b[ok] - m + 1, -1)
+    return np.cumsum(d)[:clen + 1]
+
+
+def _span_case(ctx, rng, clen, nrun, m):
+    """one im_span_build on ctx: every position, intervals clipped at both ends, intervals that are empty after the clip"""
+    start = rng.integers(-50, clen + 20, nrun).astype(np.int32)
+    length = rng.choice([19, 20, 21, 50, 70, 100, 250], nrun).astype(np.int32)
+    want = span_of_run_arrays(start, length, clen, m)
+    ctx.span_build(clen, start, length, m)
+    p = np.arange(clen + 1, dtype=np.int32)
+    assert np.array_equal(ctx.span_query(p, p).astype(np.int64), want), (clen, m)
+    beg, end = interval_queries(rng, clen)
+    beg = np.concatenate([beg, [-1, -70, -3, -100]]).astype(np.int32); end = np.concatenate([end, [5, 90, clen + 4, clen + 100]]).astype(np.int32)
+    assert np.array_equal(ctx.span_query(beg, end).astype(np.int64), interval_minima(want, beg, end, clen)), (clen, m)
+    beg = np.array([clen + 1, clen + 5, -9, 40, -3], np.int32); end = np.array([clen + 9, clen + 5, -2, 39, -3], np.int32)
+    assert not ctx.span_query(beg, end).any(), (clen, m)
+    return start, length, want
+
+
+def test_span_build_contigs_in_sequence_and_tile_edges():
+    """im_span_build call after call on ONE context, as test_depth_build_contigs_in_sequence_and_tile_edges does for the depth
+    array: contigs that grow, shrink and grow again, clen + 1 a multiple of the scan's 8192-position tile, 32 / 33 / 1025 tiles,
+    an empty build, the same build three times over"""
+    from indelminer_amd import capi
+    rng = np.random.default_rng(22)
+    runs = [(int(s), int(s) + int(l)) for s, l in zip(rng.integers(-30, 5000, 900), rng.choice([19, 20, 21, 100], 900))]
+    st = np.array([s for s, e in runs], np.int32); ln = np.array([e - s for s, e in runs], np.int32)
+    for m in (1, 10):
+        assert np.array_equal(span_of_run_arrays(st, ln, 5000, m), span_of_runs(runs, 5000, m))
+    ctx = capi.Context(0)
+    try:
+        for clen, nrun, m in ((5000, 800, 10), (3_000_000, 900_000, 10), (100, 40, 1), (3_000_001, 900_000, 25),
+                              (8191, 3000, 10), (32 * 8192 - 1, 80_000, 10), (32 * 8192, 80_000, 1), (1024 * 8192, 1_200_000, 10),
+                              (70_000, 0, 3)):
+            _span_case(ctx, rng, clen, nrun, m)
+        clen = 33 * 8192 - 1
+        start, length, want = _span_case(ctx, rng, clen, 90_000, 10)
+        p = np.arange(clen + 1, dtype=np.int32)
+        for _again in range(3):
+            ctx.span_build(clen, start, length, 10)
+            assert np.array_equal(ctx.span_query(p, p).astype(np.int64), want)
+    finally:
+        ctx.close()
+
+
 def _depth_of(ctx, capi, clens, raw, off):
     """the pileup depth of every position from the same chunk: the triage's depth scatter, scanned and read back"""
     ctx.set_insert_ranges(["generic"], [700])
