@@ -505,6 +505,33 @@ int im_span_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, c
 int im_span_build(im_ctx* ctx, int64_t contig_len, int32_t n_run, const int32_t* run_start, const int32_t* run_len, int32_t flank);
 int im_span_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out);
 
+/* Concordant pairs, for the records without a precise breakpoint (PAIRED_READ; -P).  Replaces nothing in the reference either.
+ * With m = flank >= 1, q = min_mapq and range_max = range[1] of the record's read group (its RG:Z tag, "generic" without one:
+ * the look-up of fetch_func, through the table of im_set_insert_ranges), a record is a CONCORDANT LEFT MATE iff
+ *   flag & 0x1 is set and none of 0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800;
+ *   0 <= tid < n_contigs and mtid == tid;
+ *   ((flag >> 4) & 1) != ((flag >> 5) & 1), the orientation test of the discordant rule;
+ *   isize > 0;  pos < mpos, or pos == mpos and flag & 0x40 (each pair once);  mapq >= q (the record's own);
+ *   its read group is in the table and isize <= range_max, the complement of the evidence rule abs(isize) > range[1] (a record
+ *   whose group is not in the table is skipped here: the triage of the same chunk ends the run on it).
+ * Its FRAGMENT is [a, b) = [pos, pos + isize) clipped to [0, length).  pspan[p], 0 <= p <= length, counts the fragments with
+ * a + m <= p and p + m <= b; as a difference array a fragment with b - a >= 2 m adds +1 at a + m and -1 at b - m + 1 -- the
+ * shape of span[], scanned and queried by the same kernels.  The minimum of pspan[] over [POS, max(END, BP_END)] is the thinnest
+ * concordant-fragment depth between the two breakpoints of a deletion: a lower bound of the pairs of the reference allele.
+ *
+ * The entries mirror seam 5's, with the same contracts: im_pairspan_enable allocates a SECOND array of one int32 per reference
+ * position (4 more bytes per base of HBM, on this call only); im_dev_pairspan_scatter (a launch of its own, asynchronous) needs
+ * im_set_insert_ranges and answers IM_E_ARG without it; scan, reset and query_tid as for span[].  im_pairspan_build takes the
+ * fragments (start, length) of one contig's concordant left mates -- the caller applies the record rule -- and leaves pspan[] of
+ * that contig resident beside, and independent of, what im_span_build made; im_pairspan_query answers like im_span_query. */
+int im_pairspan_enable(im_ctx* ctx, int32_t flank, int32_t min_mapq);
+int im_dev_pairspan_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream);
+int im_pairspan_scan(im_ctx* ctx, int32_t tid, void* stream);
+int im_pairspan_reset(im_ctx* ctx, int32_t tid, void* stream);
+int im_pairspan_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out);
+int im_pairspan_build(im_ctx* ctx, int64_t contig_len, int32_t n_frag, const int32_t* frag_start, const int32_t* frag_len, int32_t flank);
+int im_pairspan_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

@@ -214,6 +214,13 @@ def lib():
         L.im_span_query_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_span_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         L.im_span_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_pairspan_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.im_dev_pairspan_scatter.argtypes = [C.c_void_p, C.POINTER(DevRecords), C.c_void_p]
+        L.im_pairspan_scan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.im_pairspan_reset.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.im_pairspan_query_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_pairspan_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+        L.im_pairspan_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_capture_begin.argtypes = [C.c_void_p, C.c_void_p]
@@ -497,6 +504,40 @@ class Context:
         end = np.ascontiguousarray(end, dtype=np.int32)
         out = np.zeros(max(len(beg), 1), dtype=np.uint32)
         self._check(lib().im_span_query(self.h, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
+        return out[:len(beg)]
+
+    def pairspan_enable(self, flank, min_mapq):
+        """a second genome-wide array: concordant pairs whose fragment spans a position (PAIRED_READ genotypes), 4 bytes per base"""
+        self._check(lib().im_pairspan_enable(self.h, int(flank), int(min_mapq)))
+
+    def pairspan_scatter(self, recs, stream=None):
+        """recs: a DevRecords chunk, as im_dev_triage takes it (asynchronous); needs set_insert_ranges"""
+        self._check(lib().im_dev_pairspan_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
+
+    def pairspan_scan(self, tid, stream=None):
+        self._check(lib().im_pairspan_scan(self.h, tid, self.stream if stream is None else stream))
+
+    def pairspan_reset(self, tid, stream=None):
+        self._check(lib().im_pairspan_reset(self.h, tid, self.stream if stream is None else stream))
+
+    def pairspan_query_tid(self, tid, beg, end):
+        """per query the minimum of pspan[p] over [beg, end] inclusive"""
+        beg = np.ascontiguousarray(beg, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        out = np.zeros(max(len(beg), 1), dtype=np.uint32)
+        self._check(lib().im_pairspan_query_tid(self.h, tid, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
+        return out[:len(beg)]
+
+    def pairspan_build(self, contig_len, frag_start, frag_len, flank):
+        frag_start = np.ascontiguousarray(frag_start, dtype=np.int32)
+        frag_len = np.ascontiguousarray(frag_len, dtype=np.int32)
+        self._check(lib().im_pairspan_build(self.h, contig_len, len(frag_start), _ptr(frag_start), _ptr(frag_len), int(flank)))
+
+    def pairspan_query(self, beg, end):
+        beg = np.ascontiguousarray(beg, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        out = np.zeros(max(len(beg), 1), dtype=np.uint32)
+        self._check(lib().im_pairspan_query(self.h, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
         return out[:len(beg)]
 
     def cluster_sr(self, cls, b1, b2, marker=2**31 - 1, tie_desc=0):

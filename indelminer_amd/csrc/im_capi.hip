@@ -14,7 +14,7 @@
 #include <mutex>
 #include <atomic>
 
-// One contig's difference array of the record-at-a-time path (im_depth_build, im_span_build): cap ints of data and the sums
+// One contig's difference array of the record-at-a-time path (im_depth_build, im_span_build, im_pairspan_build): cap ints of data and the sums
 // im::depth_sums_ints gives for cap - 1 positions (it grows with the contig, so they serve every shorter one); len < 0: not built
 struct ContigArray {
     int32_t* data = nullptr;
@@ -43,8 +43,8 @@ struct im_ctx {
     size_t pin_bytes = 0;
     hipStream_t copy_stream = nullptr, back_stream = nullptr;     // host -> device, device -> host
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_k[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    // resident depth and span arrays of the current contig (im_depth_build, im_span_build)
-    ContigArray depth, span;
+    // resident depth, span and pair-span arrays of the current contig (im_depth_build, im_span_build, im_pairspan_build)
+    ContigArray depth, span, pair;
     // host copies of the reference layout
     std::vector<int64_t> h_asc_off;
     std::vector<int32_t> h_len;
@@ -56,6 +56,10 @@ struct im_ctx {
     int32_t* gspan = nullptr;
     int32_t* gspan_sums = nullptr;
     int32_t span_flank = 0, span_min_mapq = 0;
+    // genome-wide concordant-pair counts (im_pairspan_enable): a further array of that layout, allocated on that call only
+    int32_t* gpair = nullptr;
+    int32_t* gpair_sums = nullptr;
+    int32_t pair_flank = 0, pair_min_mapq = 0;
     bool support_count_attr = false;    // im_support_count: its kernel's LDS attribute has been set on this context's device
     std::mutex gb_mu;
     std::unordered_map<void*, int32_t> gb_layout;   // group-by scratch -> the slot count it was initialised (and is carved) for
@@ -140,6 +144,9 @@ void free_reference(im_ctx* ctx)
     if (ctx->gspan) (void)hipFree(ctx->gspan);
     if (ctx->gspan_sums) (void)hipFree(ctx->gspan_sums);
     ctx->gspan = nullptr; ctx->gspan_sums = nullptr;
+    if (ctx->gpair) (void)hipFree(ctx->gpair);
+    if (ctx->gpair_sums) (void)hipFree(ctx->gpair_sums);
+    ctx->gpair = nullptr; ctx->gpair_sums = nullptr;
     ctx->h_asc_off.clear(); ctx->h_len.clear(); ctx->ref_total = 0;
 }
 
@@ -150,7 +157,7 @@ void free_array(ContigArray& a)
     a = ContigArray();
 }
 
-// im_depth_build / im_span_build behind their argument checks: grow, stage the intervals, memset + scatter + scan (one launcher,
+// im_depth_build / im_span_build / im_pairspan_build behind their argument checks: grow, stage the intervals, memset + scatter + scan (one launcher,
 // im_depth.hip), wait
 int build_array(im_ctx* ctx, ContigArray& a, int64_t clen, int32_t n, const int32_t* start, const int32_t* len, int32_t lo, int32_t hi)
 {
@@ -201,7 +208,7 @@ int query_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, 
     return IM_OK;
 }
 
-// im_depth_enable / im_span_enable: a genome-wide array (one int32 per byte of ref_ascii) and its sums, zeroed.  Each contig has
+// im_depth_enable / im_span_enable / im_pairspan_enable: a genome-wide array (one int32 per byte of ref_ascii) and its sums, zeroed.  Each contig has
 // its own run of sums (scans of different contigs may be in flight on different streams), at the same place in both arrays
 int enable_genome_array(im_ctx* ctx, int32_t** data, int32_t** sums)
 {
@@ -262,6 +269,7 @@ void im_ctx_destroy(im_ctx* ctx)
     if (ctx->ws) (void)hipFree(ctx->ws);
     free_array(ctx->depth);
     free_array(ctx->span);
+    free_array(ctx->pair);
     if (ctx->rg_blob) (void)hipFree(ctx->rg_blob);
     if (ctx->any_list) (void)hipFree(ctx->any_list);
     if (ctx->any_counters) (void)hipFree(ctx->any_counters);
@@ -866,6 +874,77 @@ int im_span_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end
     if (n == 0) return IM_OK;
     if (!beg || !end || !min_out) return IM_E_ARG;
     return query_array(ctx, n, beg, end, ctx->span.data, ctx->span.sums, ctx->span.len, true, min_out, nullptr);
+}
+
+// ---- concordant-pair counts (the genotype columns of PAIRED_READ records) ----------------------
+
+int im_pairspan_enable(im_ctx* ctx, int32_t flank, int32_t min_mapq)
+{
+    if (!ctx) return IM_E_ARG;
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    if (flank < 1) { set_err(ctx, "im_pairspan_enable: flank %d, must be >= 1", flank); return IM_E_ARG; }
+    if (ctx->gpair) {
+        if (flank != ctx->pair_flank || min_mapq != ctx->pair_min_mapq) { set_err(ctx, "im_pairspan_enable: already enabled with flank %d, min_mapq %d", ctx->pair_flank, ctx->pair_min_mapq); return IM_E_ARG; }
+        return IM_OK;
+    }
+    int rc = enable_genome_array(ctx, &ctx->gpair, &ctx->gpair_sums);
+    if (rc) return rc;
+    ctx->pair_flank = flank; ctx->pair_min_mapq = min_mapq;
+    return IM_OK;
+}
+
+int im_dev_pairspan_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
+{
+    if (!ctx || !recs) return IM_E_ARG;
+    if (!ctx->gpair) { set_err(ctx, "im_pairspan_enable has not been called"); return IM_E_ARG; }
+    if (!ctx->rg_blob) { set_err(ctx, "im_set_insert_ranges has not been called"); return IM_E_ARG; }
+    if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    im::RefDev ref;
+    ref.ascii = ctx->ref_ascii; ref.pk = reinterpret_cast<const uint8_t*>(ctx->ref_pk);
+    ref.asc_off = ctx->d_asc_off; ref.pk_off = ctx->d_pk_off; ref.len = ctx->d_len; ref.n_contigs = ctx->n_contigs;
+    HIP_TRY(ctx, im::launch_pair_scatter(ref, ctx->rg, ctx->pair_flank, ctx->pair_min_mapq, *recs, ctx->gpair, (hipStream_t)stream));
+    return IM_OK;
+}
+
+int im_pairspan_scan(im_ctx* ctx, int32_t tid, void* stream)
+{
+    if (!ctx || !ctx->gpair || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, im::launch_depth_scan_tiled(ctx->gpair + ctx->h_asc_off[tid], (int64_t)ctx->h_len[tid] + 1, ctx->gpair_sums + ctx->h_sums_off[tid], (hipStream_t)stream));
+    return IM_OK;
+}
+
+int im_pairspan_reset(im_ctx* ctx, int32_t tid, void* stream)
+{
+    if (!ctx || !ctx->gpair || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->gpair + ctx->h_asc_off[tid], 0, ((size_t)ctx->h_len[tid] + 1) * sizeof(int32_t), (hipStream_t)stream));
+    return IM_OK;
+}
+
+int im_pairspan_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
+{
+    if (!ctx || n < 0 || !ctx->gpair || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    if (n == 0) return IM_OK;
+    if (!beg || !end || !min_out) return IM_E_ARG;
+    return query_array(ctx, n, beg, end, ctx->gpair + ctx->h_asc_off[tid], ctx->gpair_sums + ctx->h_sums_off[tid], ctx->h_len[tid], true, min_out, nullptr);
+}
+
+int im_pairspan_build(im_ctx* ctx, int64_t contig_len, int32_t n_frag, const int32_t* frag_start, const int32_t* frag_len, int32_t flank)
+{
+    if (!ctx || contig_len < 0 || contig_len > 0x7fffff00LL || n_frag < 0 || (n_frag > 0 && (!frag_start || !frag_len))) return IM_E_ARG;
+    if (flank < 1) { set_err(ctx, "im_pairspan_build: flank %d, must be >= 1", flank); return IM_E_ARG; }
+    return build_array(ctx, ctx->pair, contig_len, n_frag, frag_start, frag_len, flank, flank - 1);
+}
+
+int im_pairspan_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
+{
+    if (!ctx || n < 0) return IM_E_ARG;
+    if (ctx->pair.len < 0) { set_err(ctx, "im_pairspan_build has not been called"); return IM_E_ARG; }
+    if (n == 0) return IM_OK;
+    if (!beg || !end || !min_out) return IM_E_ARG;
+    return query_array(ctx, n, beg, end, ctx->pair.data, ctx->pair.sums, ctx->pair.len, true, min_out, nullptr);
 }
 
 int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64_t* t_off,

@@ -109,6 +109,8 @@ hipError_t launch_compact_results(const im_read_result* res, int32_t n_cap, cons
 
 // im_span.hip: reference-spanning read counts (the genotype columns); the array has the depth array's layout, build and scan
 hipError_t launch_span_scatter(const RefDev& ref, int32_t flank, int32_t min_mapq, const im_dev_records& recs, int32_t* diff, hipStream_t stream);
+// concordant left mates -> fragment events in a difference array of the same layout (rg: the table of im_set_insert_ranges)
+hipError_t launch_pair_scatter(const RefDev& ref, const RgTable& rg, int32_t flank, int32_t min_mapq, const im_dev_records& recs, int32_t* diff, hipStream_t stream);
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);

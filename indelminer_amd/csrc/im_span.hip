@@ -14,8 +14,21 @@
 //   span_query     one wave per query: minimum of span[p] over [beg, end] inclusive
 // The record-at-a-time path hands over (start, length) runs instead of records: launch_depth_build(lo = m, hi = m - 1) makes the
 // same events from them.
+//
+// Concordant pairs (-P), a second array of the same shape for the records without a precise breakpoint (PAIRED_READ).  With
+// m = flank >= 1, q = min_mapq and range_max = range[1] of the record's read group (its RG:Z tag, "generic" without one: the
+// look-up of fetch_func), a record is a CONCORDANT LEFT MATE iff
+//   flag & 0x1, none of 0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800;  0 <= tid < n_contigs and mtid == tid;
+//   ((flag >> 4) & 1) != ((flag >> 5) & 1)  (the orientation test of the discordant rule);  isize > 0;
+//   pos < mpos, or pos == mpos and flag & 0x40  (each pair once);  mapq >= q;
+//   its read group is in the table and isize <= range_max  (the complement of the evidence rule abs(isize) > range[1]; a record
+//   whose group is not in the table is skipped: the triage of the same chunk ends the run on it).
+// Its FRAGMENT is [a, b) = [pos, pos + isize) clipped to [0, clen).  pspan[p], 0 <= p <= clen, counts the fragments with
+// a + m <= p and p + m <= b: a fragment with b - a >= 2 m adds +1 at a + m and -1 at b - m + 1.  Scan and query as for span[].
+//   pair_scatter   one lane per delivered record: the core decides first, the survivors find RG:Z and look the group up (im_rg.hpp)
 
 #include "im_device.hpp"
+#include "im_rg.hpp"
 
 namespace im {
 namespace {
@@ -23,8 +36,6 @@ namespace {
 constexpr int kSpanBlock = 256;
 constexpr int kSpanWin = 4096;      // positions of the difference array a workgroup gathers in LDS before it touches memory
 constexpr int kSpanHead = 4;        // CIGAR words a lane keeps in registers; the rest come from memory
-
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 
 // What the scatter needs of a record (the 32-byte core; layout as in include/indelminer_amd.h, im_dev_records)
 struct SpanRec {
@@ -68,28 +79,65 @@ struct SpanArgs {
     int32_t* diff;              // the genome-wide difference array
 };
 
-// one event of a run: into the LDS window when it lies there, to memory otherwise
-__device__ __forceinline__ void span_event(int32_t* s_win, int32_t* __restrict__ diff, int64_t base, bool here, int64_t win_pos, int64_t at, int32_t v)
+// The LDS window of a scatter workgroup: kSpanWin positions of one contig's difference array, from the position of the first
+// record of the workgroup that has events to add.  A coordinate-sorted BAM puts the 256 records of a workgroup within a few
+// hundred positions of each other: their events become LDS adds and a few whole-line atomic instructions (the depth events of
+// im_triage.hip's classify kernel take the same road).  Events outside the window or on another contig go to memory directly.
+struct SpanWin { int32_t* lds; int32_t pos, tid; };
+
+__device__ __forceinline__ void win_clear(int32_t* s_win, int t)
 {
-    const int64_t rel = at - win_pos;
-    if (here && rel >= 0 && rel < kSpanWin) atomicAdd(&s_win[rel], v);
+    int4* z = reinterpret_cast<int4*>(s_win);
+#pragma unroll
+    for (int k = 0; k < kSpanWin / 4 / kSpanBlock; k++) z[t + k * kSpanBlock] = make_int4(0, 0, 0, 0);
+}
+
+// each wave names its first record that adds events (records are sorted inside a contig); a __syncthreads, then win_open
+__device__ __forceinline__ void win_propose(int32_t* s_wpos, int32_t* s_wtid, bool adds, int32_t pos, int32_t tid, int lane, int wave)
+{
+    const uint64_t mp = __ballot(adds);
+    const int first = mp ? (int)__builtin_ctzll(mp) : 0;
+    const int fp = __shfl(pos, first), ft = __shfl(tid, first);
+    if (lane == 0) { s_wpos[wave] = fp < 0 ? 0 : fp; s_wtid[wave] = mp ? ft : -1; }
+}
+
+// the first wave with such a record decides; tid < 0: no record of the workgroup adds anything
+__device__ __forceinline__ SpanWin win_open(int32_t* s_win, const int32_t* s_wpos, const int32_t* s_wtid)
+{
+    SpanWin W; W.lds = s_win; W.pos = 0; W.tid = -1;
+#pragma unroll
+    for (int wv = kSpanBlock / 64 - 1; wv >= 0; wv--) if (s_wtid[wv] >= 0) { W.tid = s_wtid[wv]; W.pos = s_wpos[wv]; }
+    return W;
+}
+
+// one event on contig tid (base: the start of its run in diff): into the window when it lies there, to memory otherwise
+__device__ __forceinline__ void win_event(const SpanWin& W, int32_t* __restrict__ diff, int64_t base, int32_t tid, int64_t at, int32_t v)
+{
+    const int64_t rel = at - W.pos;
+    if (tid == W.tid && rel >= 0 && rel < kSpanWin) atomicAdd(&W.lds[rel], v);
     else atomicAdd(&diff[base + at], v);
+}
+
+// the gathered window out, behind a __syncthreads: consecutive lanes hold consecutive positions, only non-zero entries touch memory
+__device__ __forceinline__ void win_out(const SpanWin& W, int32_t* __restrict__ diff, const int64_t* asc_off, const int32_t* len, int t)
+{
+    int32_t* dst = diff + asc_off[W.tid] + W.pos;
+    const int64_t room = (int64_t)len[W.tid] + 1 - W.pos;          // the contig's run has len + 1 entries
+#pragma unroll 4
+    for (int k = 0; k < kSpanWin / kSpanBlock; k++) {
+        const int idx = t + k * kSpanBlock;
+        const int32_t v = W.lds[idx];
+        if (v != 0 && idx < room) atomicAdd(&dst[idx], v);
+    }
 }
 
 __global__ __launch_bounds__(kSpanBlock) void span_scatter_kernel(SpanArgs A)
 {
-    // A coordinate-sorted BAM puts the 256 records of a workgroup within a few hundred positions of each other: their events
-    // become LDS adds and a few whole-line atomic instructions (the depth events of im_triage.hip's classify kernel take the
-    // same road).  Events outside the window or on another contig go to memory directly.
     __shared__ int32_t s_win[kSpanWin];
     __shared__ int32_t s_wpos[kSpanBlock / 64], s_wtid[kSpanBlock / 64];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int64_t i = (int64_t)blockIdx.x * kSpanBlock + t;
-    {
-        int4* z = reinterpret_cast<int4*>(s_win);
-#pragma unroll
-        for (int k = 0; k < kSpanWin / 4 / kSpanBlock; k++) z[t + k * kSpanBlock] = make_int4(0, 0, 0, 0);
-    }
+    win_clear(s_win, t);
     SpanRec r; r.ok = false; r.tid = -1; r.pos = 0; r.flag = 0; r.mapq = 0; r.n_cigar = 0; r.o_cigar = 0; r.p = A.recs.raw;
     if (i < A.recs.n) r = span_record(A.recs.raw, A.recs.rec_off[i], A.recs.rec_off[i + 1]);
     if (r.ok) {
@@ -98,23 +146,14 @@ __global__ __launch_bounds__(kSpanBlock) void span_scatter_kernel(SpanArgs A)
         for (int k = 0; k < kSpanHead; k++) r.cig[k] = ld_u32(r.p + r.o_cigar + 4u * k);
     }
     const bool counts = r.ok && r.tid >= 0 && r.tid < A.n_contigs && !(r.flag & (0x4u | 0x100u | 0x200u | 0x400u)) && (int32_t)r.mapq >= A.min_mapq;
-    // the window starts at the first eligible record of the workgroup (records are sorted inside a contig)
-    {
-        const uint64_t mp = __ballot(counts);
-        const int first = mp ? (int)__builtin_ctzll(mp) : 0;
-        const int fp = __shfl(r.pos, first), ft = __shfl(r.tid, first);
-        if (lane == 0) { s_wpos[wave] = fp < 0 ? 0 : fp; s_wtid[wave] = mp ? ft : -1; }
-    }
+    win_propose(s_wpos, s_wtid, counts, r.pos, r.tid, lane, wave);
     __syncthreads();
-    int32_t win_pos = 0, win_tid = -1;
-#pragma unroll
-    for (int wv = kSpanBlock / 64 - 1; wv >= 0; wv--) if (s_wtid[wv] >= 0) { win_tid = s_wtid[wv]; win_pos = s_wpos[wv]; }
-    if (win_tid < 0) return;                                        // nothing eligible in the whole workgroup
+    const SpanWin W = win_open(s_win, s_wpos, s_wtid);
+    if (W.tid < 0) return;                                          // nothing eligible in the whole workgroup
 
     if (counts) {
         const int64_t base = A.asc_off[r.tid];
         const int64_t clen = A.len[r.tid], m = A.flank;
-        const bool here = r.tid == win_tid;
         int64_t x = r.pos, rs = 0;
         bool in_run = false;
         for (uint32_t k = 0; k <= r.n_cigar; k++) {
@@ -129,8 +168,8 @@ __global__ __launch_bounds__(kSpanBlock) void span_scatter_kernel(SpanArgs A)
             if (in_run) {
                 const int64_t a = rs < 0 ? 0 : rs, b = x > clen ? clen : x;
                 if (b - a >= 2 * m) {
-                    span_event(s_win, A.diff, base, here, win_pos, a + m, 1);
-                    span_event(s_win, A.diff, base, here, win_pos, b - m + 1, -1);
+                    win_event(W, A.diff, base, r.tid, a + m, 1);
+                    win_event(W, A.diff, base, r.tid, b - m + 1, -1);
                 }
                 in_run = false;
             }
@@ -138,15 +177,77 @@ __global__ __launch_bounds__(kSpanBlock) void span_scatter_kernel(SpanArgs A)
         }
     }
     __syncthreads();
-    // the gathered window out: consecutive lanes hold consecutive positions, only non-zero entries touch memory
-    int32_t* dst = A.diff + A.asc_off[win_tid] + win_pos;
-    const int64_t room = (int64_t)A.len[win_tid] + 1 - win_pos;    // the contig's run has len + 1 entries
-#pragma unroll 4
-    for (int k = 0; k < kSpanWin / kSpanBlock; k++) {
-        const int idx = t + k * kSpanBlock;
-        const int32_t v = s_win[idx];
-        if (v != 0 && idx < room) atomicAdd(&dst[idx], v);
+    win_out(W, A.diff, A.asc_off, A.len, t);
+}
+
+struct PairArgs {
+    im_dev_records recs;
+    const int64_t* asc_off;     // [n_contigs] start of a contig's run in the array
+    const int32_t* len;         // [n_contigs]
+    int32_t n_contigs;
+    int32_t flank, min_mapq;
+    RgTable rg;                 // read group -> range[1] (im_set_insert_ranges)
+    int32_t* diff;              // the genome-wide difference array of the pair counts
+};
+
+__global__ __launch_bounds__(kSpanBlock) void pair_scatter_kernel(PairArgs A)
+{
+    // A fragment's closing event lies up to range_max behind its opening one: with inserts of a few hundred bases most of them
+    // still fall into the window, and the rest are the plain device atomics the window is there to thin out, not a corner case.
+    __shared__ int32_t s_win[kSpanWin];
+    __shared__ int32_t s_wpos[kSpanBlock / 64], s_wtid[kSpanBlock / 64];
+    __shared__ uint32_t s_aux[kSpanBlock][kAuxWin / 4];
+    __shared__ uint32_t s_rg[kRgLds / 4];
+    __shared__ int32_t s_generic[2];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t i = (int64_t)blockIdx.x * kSpanBlock + t;
+    win_clear(s_win, t);
+    RecView r; r.ok = false; r.flag = 0; r.tid = -1; r.pos = 0; r.mtid = -1; r.mpos = 0; r.isize = 0; r.mapq = 0; r.p = A.recs.raw; r.len = 0; r.o_aux = 0;
+    if (i < A.recs.n) r = view_record(A.recs.raw, A.recs.rec_off[i], A.recs.rec_off[i + 1]);
+    // what the core decides: about half of the records of a paired library are left mates, and only they walk their tags
+    const uint32_t f = r.flag;
+    const bool left = r.ok && (f & 0x1u) && !(f & (0x4u | 0x8u | 0x100u | 0x200u | 0x400u | 0x800u)) &&
+                      r.tid >= 0 && r.tid < A.n_contigs && r.mtid == r.tid && (((f >> 4) ^ (f >> 5)) & 1u) && r.isize > 0 &&
+                      (r.pos < r.mpos || (r.pos == r.mpos && (f & 0x40u))) && (int32_t)r.mapq >= A.min_mapq;
+    if (left) {
+        // the aux window, as the classify kernel loads it: as many dwords as the record's aux area has
+        const uint32_t aux_bytes = r.len - r.o_aux;
+#pragma unroll
+        for (int k = 0; k < kAuxWin / 4; k++) if (4u * k < aux_bytes) s_aux[t][k] = ld_u32(r.p + r.o_aux + 4u * k);
     }
+    // the window starts at the first left mate of the workgroup (nearly all of them are concordant and count)
+    win_propose(s_wpos, s_wtid, left, r.pos, r.tid, lane, wave);
+    const bool rg_lds = A.rg.bytes <= kRgLds;
+    if (rg_lds) for (int k = t; 4 * k < A.rg.bytes; k += kSpanBlock) s_rg[k] = reinterpret_cast<const uint32_t*>(A.rg.blob)[k];
+    __syncthreads();
+    const SpanWin W = win_open(s_win, s_wpos, s_wtid);
+    if (W.tid < 0) return;                                          // no left mate in the whole workgroup
+    const RgView T = rg_view(rg_lds ? reinterpret_cast<const uint8_t*>(s_rg) : A.rg.blob, A.rg.n);
+    if (t == 0) {
+        int32_t rm = 0;
+        const bool ok = rg_lookup(T, [](uint32_t k) { return (uint32_t)("generic"[k]); }, 7u, rm);
+        s_generic[0] = ok ? 1 : 0; s_generic[1] = rm;
+    }
+    __syncthreads();
+
+    if (left) {
+        AuxWin w; w.lds = s_aux[t]; w.o0 = r.o_aux;
+        uint32_t o_rg, o_mq;
+        find_rg_mq(r, w, o_rg, o_mq);
+        int32_t range_max = s_generic[1];
+        const bool known = o_rg ? rg_tag_range(r, w, o_rg, T, range_max) : s_generic[0] != 0;
+        if (known && r.isize <= range_max) {
+            const int64_t base = A.asc_off[r.tid];
+            const int64_t clen = A.len[r.tid], m = A.flank;
+            const int64_t a = r.pos < 0 ? 0 : r.pos, e = (int64_t)r.pos + r.isize, b = e > clen ? clen : e;
+            if (b - a >= 2 * m) {
+                win_event(W, A.diff, base, r.tid, a + m, 1);
+                win_event(W, A.diff, base, r.tid, b - m + 1, -1);
+            }
+        }
+    }
+    __syncthreads();
+    win_out(W, A.diff, A.asc_off, A.len, t);
 }
 
 // One wave per query: the minimum of span[p] over [beg, end] INCLUSIVE, clipped to [0, clen]; an interval that is empty after
@@ -180,6 +281,17 @@ hipError_t launch_span_scatter(const RefDev& ref, int32_t flank, int32_t min_map
     A.flank = flank; A.min_mapq = min_mapq; A.diff = diff;
     const int blocks = (recs.n + kSpanBlock - 1) / kSpanBlock;
     hipLaunchKernelGGL(span_scatter_kernel, dim3(blocks), dim3(kSpanBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_pair_scatter(const RefDev& ref, const RgTable& rg, int32_t flank, int32_t min_mapq, const im_dev_records& recs, int32_t* diff, hipStream_t stream)
+{
+    if (recs.n <= 0) return hipSuccess;
+    PairArgs A;
+    A.recs = recs; A.asc_off = ref.asc_off; A.len = ref.len; A.n_contigs = ref.n_contigs;
+    A.flank = flank; A.min_mapq = min_mapq; A.rg = rg; A.diff = diff;
+    const int blocks = (recs.n + kSpanBlock - 1) / kSpanBlock;
+    hipLaunchKernelGGL(pair_scatter_kernel, dim3(blocks), dim3(kSpanBlock), 0, stream, A);
     return hipGetLastError();
 }
 

@@ -24,6 +24,7 @@
 // slots) per candidate out + 1 B class per record.
 
 #include "im_device.hpp"
+#include "im_rg.hpp"
 
 namespace im {
 namespace {
@@ -32,122 +33,14 @@ constexpr int kTriBlock = 256;
 constexpr int kTriGroup = 32;           // workgroups that count their publication into one word (see the classify kernel's tail)
 constexpr int kTriGroupsMax = 2048;
 
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 __device__ __forceinline__ uint32_t ld_u16(const uint8_t* p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
 
-struct RecView {
-    const uint8_t* p;       // record start (the 32-byte core)
-    uint32_t len;           // bytes of the record
-    int32_t tid, pos, mtid, mpos, isize, l_seq;
-    uint32_t l_qname, mapq, n_cigar, flag;
-    uint32_t o_cigar, o_seq, o_aux;
-    uint32_t cig[4];        // the first four CIGAR words, loaded together with the aux window
-    bool ok;
-};
-
-constexpr int kAuxWin = 24;     // bytes of the aux area a lane holds in LDS at a time: the tag walk slides the window along (aux_slide); more LDS
-                                // would cost the kernel its sixth workgroup per CU
-
-__device__ __forceinline__ RecView view_record(const uint8_t* raw, uint32_t off, uint32_t end)
-{
-    RecView r;
-    r.p = raw + off; r.len = end - off; r.ok = false;
-    r.tid = r.pos = r.mtid = r.mpos = r.isize = r.l_seq = 0;
-    r.l_qname = r.mapq = r.n_cigar = r.flag = 0; r.o_cigar = r.o_seq = r.o_aux = 0;
-    r.cig[0] = r.cig[1] = r.cig[2] = r.cig[3] = 0;
-    if (end < off || r.len < 32u) return r;
-    const uint32_t* c = reinterpret_cast<const uint32_t*>(r.p);     // 4-byte aligned by contract
-    r.tid = (int32_t)c[0]; r.pos = (int32_t)c[1];
-    const uint32_t w2 = c[2], w3 = c[3];
-    r.l_qname = w2 & 255u; r.mapq = (w2 >> 8) & 255u;
-    r.n_cigar = w3 & 0xFFFFu; r.flag = w3 >> 16;
-    r.l_seq = (int32_t)c[4]; r.mtid = (int32_t)c[5]; r.mpos = (int32_t)c[6]; r.isize = (int32_t)c[7];
-    if (r.l_seq < 0) return r;
-    r.o_cigar = 32u + r.l_qname;
-    r.o_seq = r.o_cigar + 4u * r.n_cigar;
-    // a record delivered without its base qualities says so in its bin field (include/indelminer_amd.h, im_dev_records)
-    const bool no_qual = (w2 >> 16) == 0xFFFFu;
-    const uint64_t o_aux = (uint64_t)r.o_seq + (((uint64_t)r.l_seq + 1u) >> 1) + (no_qual ? 0ull : (uint64_t)r.l_seq);
-    if (o_aux > r.len) return r;
-    r.o_aux = (uint32_t)o_aux;
-    r.ok = true;
-    return r;
-}
+// RecView, the aux window, find_rg_mq and the read-group table: im_rg.hpp
 
 // CIGAR word k: the first four travel in registers (one round trip with the aux window), the rest come from memory
 __device__ __forceinline__ uint32_t cigar_word(const RecView& r, uint32_t k)
 {
     return k == 0u ? r.cig[0] : k == 1u ? r.cig[1] : k == 2u ? r.cig[2] : k == 3u ? r.cig[3] : ld_u32(r.p + r.o_cigar + 4u * k);
-}
-
-__device__ __forceinline__ int aux_size(uint32_t t)
-{
-    switch (t) {
-    case 'A': case 'c': case 'C': return 1;
-    case 's': case 'S': return 2;
-    case 'i': case 'I': case 'f': return 4;
-    case 'd': return 8;
-    default: return 0;
-    }
-}
-
-// a byte of the record at offset o: the lane's aux window (LDS) when it covers o, memory otherwise
-struct AuxWin { uint32_t* lds; uint32_t o0; };
-__device__ __forceinline__ uint32_t rec_byte(const RecView& r, const AuxWin& w, uint32_t o)
-{
-    const uint32_t d = o - w.o0;
-    return d < (uint32_t)kAuxWin ? reinterpret_cast<const uint8_t*>(w.lds)[d] : r.p[o];
-}
-// The window moved to offset o: six dword loads by the lane that needs them.  What an aligner writes in front of RG and MQ
-// (NM MD AS XS MC ...: 30-100 bytes) used to be walked through memory byte by byte behind the first 24 -- every byte a 64-line
-// gather: records with such fields took classify from 25 to 77 us per 300 000 (profiles/r04_m_*).  Reads past the record stay
-// inside the chunk buffer (>= 64 spare bytes behind the last record).
-__device__ __forceinline__ void aux_slide(const RecView& r, AuxWin& w, uint32_t o)
-{
-    w.o0 = o;
-#pragma unroll
-    for (int k = 0; k < kAuxWin / 4; k++) w.lds[k] = ld_u32(r.p + o + 4u * k);
-}
-// the byte at o for a walk that only moves forward: the window follows
-__device__ __forceinline__ uint32_t walk_byte(const RecView& r, AuxWin& w, uint32_t o)
-{
-    if (o - w.o0 >= (uint32_t)kAuxWin) aux_slide(r, w, o);
-    return reinterpret_cast<const uint8_t*>(w.lds)[o - w.o0];
-}
-// [o, o + need) inside the window (need <= kAuxWin)
-__device__ __forceinline__ void aux_cover(const RecView& r, AuxWin& w, uint32_t o, uint32_t need)
-{
-    if (!(o >= w.o0 && o + need <= w.o0 + (uint32_t)kAuxWin)) aux_slide(r, w, o);
-}
-
-// bam_aux_get for RG and MQ in one walk (bam_aux.c:27-54): offsets of the TYPE byte of the first
-// occurrence, 0 = absent.  The walk stops where samtools' would (unknown type, truncated B array).
-__device__ __forceinline__ void find_rg_mq(const RecView& r, AuxWin& w, uint32_t& o_rg, uint32_t& o_mq)
-{
-    o_rg = 0; o_mq = 0;
-    uint32_t s = r.o_aux;
-    const uint32_t end = r.len;
-    while (s + 4u <= end) {      // a tail of < 4 bytes is alignment padding (include/indelminer_amd.h, im_dev_records)
-        aux_cover(r, w, s, 8u);  // tag, type and what a B array's header takes
-        const uint32_t t0 = rec_byte(r, w, s), t1 = rec_byte(r, w, s + 1), type = rec_byte(r, w, s + 2);
-        if (t0 == 'R' && t1 == 'G' && !o_rg) o_rg = s + 2u;
-        if (t0 == 'M' && t1 == 'Q' && !o_mq) o_mq = s + 2u;
-        if (o_rg && o_mq) return;
-        s += 3u;
-        if (type == 'Z' || type == 'H') { while (s < end && walk_byte(r, w, s)) s++; s++; }
-        else if (type == 'B') {
-            if (s + 5u > end) return;
-            const int sz = aux_size(rec_byte(r, w, s));
-            const uint32_t cnt = rec_byte(r, w, s + 1) | (rec_byte(r, w, s + 2) << 8) | (rec_byte(r, w, s + 3) << 16) | (rec_byte(r, w, s + 4) << 24);
-            const uint64_t ns = (uint64_t)s + 5u + (uint64_t)sz * cnt;
-            if (ns > end) return;
-            s = (uint32_t)ns;
-        } else {
-            const int sz = aux_size(type);
-            if (sz == 0) return;
-            s += (uint32_t)sz;
-        }
-    }
 }
 
 // bam_aux2i (bam_aux.c:163-174)
@@ -167,41 +60,6 @@ __device__ __forceinline__ int32_t aux_int(const RecView& r, const AuxWin& w, ui
     }
 }
 
-// The insert-length table as one blob (LDS copy when it is small, else the device original):
-// [bin_start 17][name_off n][name_len n][range_max n][names]
-struct RgView {
-    const int32_t* bin_start; const int32_t* name_off; const int32_t* name_len; const int32_t* range_max; const uint8_t* names;
-};
-__device__ __forceinline__ RgView rg_view(const uint8_t* blob, int32_t n)
-{
-    RgView v;
-    const int32_t* w = reinterpret_cast<const int32_t*>(blob);
-    const int32_t m = n > 0 ? n : 1;
-    v.bin_start = w; v.name_off = w + 20; v.name_len = w + 20 + m; v.range_max = w + 20 + 2 * m;
-    v.names = blob + 4 * (20 + 3 * m);
-    return v;
-}
-
-// must_find_hashtable(insertlengths, rgname, strlen(rgname)) (src/indelminer.c:374-376): DJB2 over the
-// bytes back to front (src/hashfunc.c:23-30), 16 bins, the chain walked head to tail, strncmp prefix
-// match, LAST hit wins (src/hashtable.c:62-81).  Returns false when the reference would exit.
-template <typename NameAt>
-__device__ __forceinline__ bool rg_lookup(const RgView& T, NameAt name_at, uint32_t len, int32_t& range_max)
-{
-    uint32_t h = 5381u;
-    for (int i = (int)len - 1; i >= 0; i--) h += (h << 5) + (uint32_t)(int32_t)(int8_t)name_at((uint32_t)i);
-    const uint32_t bin = h & 15u;
-    bool hit = false;
-    for (int32_t e = T.bin_start[bin]; e < T.bin_start[bin + 1]; e++) {
-        const uint32_t el = (uint32_t)T.name_len[e];
-        if (el < len) continue;                      // the stored name ends first: strncmp sees NUL != byte
-        const uint8_t* en = T.names + T.name_off[e];
-        bool same = true;
-        for (uint32_t i = 0; i < len && same; i++) same = en[i] == name_at(i);
-        if (same) { hit = true; range_max = T.range_max[e]; }
-    }
-    return hit;
-}
 
 // new_readaln (src/readaln.c:186-240) runs for aligned proper pairs whose mate is aligned (src/indelminer.c:425), after
 // the filters of 348-366: whether this record gets that far, from the core alone
@@ -333,21 +191,7 @@ __device__ __forceinline__ Verdict classify(const RecView& r, AuxWin w, const im
         if (!generic_ok) { v.cls = IM_REC_ERR_RG; return v; }
         v.range_max = generic_range;
     } else {
-        const uint32_t type = rec_byte(r, w, o_rg);
-        bool ok = type == 'Z' || type == 'H';                                  // else bam_aux2Z returns NULL: strlen(NULL)
-        if (ok) {
-            // the name's length; a name that runs out of the window brings the window to the tag (names of up to 22 bytes then lie in it)
-            uint32_t len = 0;
-            while (o_rg + 1u + len < r.len) {
-                const uint32_t o = o_rg + 1u + len;
-                if (o - w.o0 >= (uint32_t)kAuxWin && w.o0 != o_rg) aux_slide(r, w, o_rg);
-                if (!rec_byte(r, w, o)) break;
-                len++;
-            }
-            const uint32_t o_name = o_rg + 1u;
-            ok = rg_lookup(T, [&](uint32_t k) { return rec_byte(r, w, o_name + k); }, len, v.range_max);
-        }
-        if (!ok) { v.cls = IM_REC_ERR_RG; return v; }
+        if (!rg_tag_range(r, w, o_rg, T, v.range_max)) { v.cls = IM_REC_ERR_RG; return v; }
     }
 
     if (aligned && !mate_aligned) return v;                                    // 384-385
@@ -424,7 +268,6 @@ struct TriageArgs {
 
 __device__ __forceinline__ uint32_t padded4(int32_t l) { return ((uint32_t)l + 3u) & ~3u; }
 
-constexpr int kRgLds = 2048;        // an insert-length table up to this size is copied to LDS
 constexpr int kDepthWin = 4096;     // positions of the depth difference array a workgroup gathers in LDS before it touches memory
 
 __global__ __launch_bounds__(kTriBlock, 6) void triage_classify_kernel(TriageArgs A)

@@ -329,6 +329,8 @@ typedef struct {
     int depth_tid;              /* contig whose depth array is resident on the device, -1 = none */
     /* -G, record-at-a-time path: the M/=/X runs of the contig's eligible records, for the device span array (im_span_build) */
     int32_t *run_start, *run_len; int64_t n_run, cap_run;
+    /* -P, record-at-a-time path: the fragments of the contig's concordant left mates, for the device pair-span array (im_pairspan_build) */
+    int32_t *frag_start, *frag_len; int64_t n_frag, cap_frag;
     int pipe_mode;              /* device pipeline: depth queries go to the genome-wide array */
     int marker_floor;           /* multi-GPU: smallest start of a stale pair-table entry of an earlier contig on another rank */
     /* live entries of the pair table (find_marker walks these) */
@@ -524,6 +526,25 @@ static const int32_t* record_range(driver* d, const bam_record* b)
         d->rg_tmp_val = rb->val;
     } else d->rg_tmp_val = d->rg_last_val;
     return d->rg_tmp_val;
+}
+
+/* -P: the record rule of the device's pair scatter (include/indelminer_amd.h), for the record-at-a-time path: the left mate of
+ * a pair the evidence rule of discordant_pair does NOT take (isize <= range[1]), each pair once.  A record whose read group is not
+ * in the table does not count. */
+static int concordant_left_mate(driver* d, const bam_record* b)
+{
+    const int flag = b->flag;
+    if (!(flag & 0x1) || (flag & (0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800))) return 0;
+    if (b->tid < 0 || b->tid >= d->hdr->n_targets || b->mtid != b->tid) return 0;
+    if (((flag >> 4) & 1) == ((flag >> 5) & 1)) return 0;
+    if (b->isize <= 0) return 0;
+    if (!(b->pos < b->mpos || (b->pos == b->mpos && (flag & 0x40)))) return 0;
+    if ((int)b->mapq < O.qthreshold) return 0;
+    const uint8_t* rg = bam_aux_find(b, "RG");
+    if (rg && !(rg[0] == 'Z' || rg[0] == 'H')) return 0;
+    const char* rgname = rg ? bam_aux_str(rg) : "generic";
+    qbin* rb = qhash_lookup(d->insertlengths, rgname, (int)strlen(rgname));
+    return rb && b->isize <= ((const int32_t*)rb->val)[1];
 }
 
 /* fetch_func (src/indelminer.c:339-673) for one record, pass A part */
@@ -931,7 +952,9 @@ static void genotype_of(int64_t rs, int64_t ns, int* best_out, int* gq_out)
 }
 static void print_genotype(const variant_t* v)
 {
-    if (v->evdnctype == EV_PAIRED_READ || !v->rs_valid) {           /* no precise breakpoint to count spanning reads at */
+    /* a PAIRED_READ record has no precise breakpoint to count spanning reads at; with -P its rs_cached is RP, the thinnest depth
+     * of concordant fragments over [POS, max(END, BP_END)] */
+    if ((v->evdnctype == EV_PAIRED_READ && !g_pair_counts) || !v->rs_valid) {
         printf("\tGT:AD:GQ\t./.:.,%u:.", v->support);
         return;
     }
@@ -1246,11 +1269,11 @@ static void print_variants(driver* d, variant_list* vs)
         int32_t* end = xmalloc(sizeof(int32_t) * (size_t)out.n);
         uint32_t* rs = xmalloc(sizeof(uint32_t) * (size_t)out.n);
         int* who = xmalloc(sizeof(int) * (size_t)out.n);
-        int m = 0;
+        int m = 0, np = 0;
         for (int i = 0; i < out.n; i++) {
             variant_t* v = out.v[i];
             v->rs_valid = 0;
-            if (v->evdnctype == EV_PAIRED_READ) continue;
+            if (v->evdnctype == EV_PAIRED_READ) { np += g_pair_counts; continue; }
             int pos, endpos, bp_end;
             vcf_coordinates(v, &pos, &endpos, &bp_end);
             if (bp_end < endpos) continue;
@@ -1263,6 +1286,23 @@ static void print_variants(driver* d, variant_list* vs)
             const int qrc = d->pipe_mode ? im_span_query_tid(d->gpu, out.v[who[0]]->tid, m, beg, end, rs) : im_span_query(d->gpu, m, beg, end, rs);
             pthread_mutex_unlock(&g_query_mu);
             if (qrc != IM_OK) fatalf("im_span_query: %s", im_last_error(d->gpu));
+            for (int q = 0; q < m; q++) { out.v[who[q]]->rs_cached = rs[q]; out.v[who[q]]->rs_valid = 1; }
+        }
+        /* ... -P: the PAIRED_READ ones from the pair-span array, over everything between their two breakpoints */
+        if (np > 0) {
+            m = 0;
+            for (int i = 0; i < out.n; i++) {
+                variant_t* v = out.v[i];
+                if (v->evdnctype != EV_PAIRED_READ) continue;
+                int pos, endpos, bp_end;
+                vcf_coordinates(v, &pos, &endpos, &bp_end);
+                beg[m] = pos; end[m] = bp_end > endpos ? bp_end : endpos; who[m] = i; m++;
+            }
+            gpu_wait(d);
+            pthread_mutex_lock(&g_query_mu);
+            const int qrc = d->pipe_mode ? im_pairspan_query_tid(d->gpu, out.v[who[0]]->tid, m, beg, end, rs) : im_pairspan_query(d->gpu, m, beg, end, rs);
+            pthread_mutex_unlock(&g_query_mu);
+            if (qrc != IM_OK) fatalf("im_pairspan_query: %s", im_last_error(d->gpu));
             for (int q = 0; q < m; q++) { out.v[who[q]]->rs_cached = rs[q]; out.v[who[q]]->rs_valid = 1; }
         }
         free(beg); free(end); free(rs); free(who);
@@ -1440,6 +1480,7 @@ typedef struct {
     int32_t  n_before_fatal;        /* supporting reads in front of that read */
     char*    fatal_msg; int fatal_is_assert;
     uint32_t rs; int rs_valid;      /* span minimum over [POS, POS + (BP_END - END)], as queried for the print call */
+    uint32_t ap;                    /* -P, PAIRED_READ: the support of the discovered variant that re-finds it (known_match), or 0 */
 } knownvariant_t;
 
 typedef struct { knownvariant_t** v; int n, cap; int next; int counted; } known_list;
@@ -1828,7 +1869,16 @@ static int known_match(const knownvariant_t* k, const variant_list* vars, int* u
  * GT and GQ from (RS, AS) by print_genotype's rule. */
 static void print_known_genotype(const knownvariant_t* k)
 {
-    if (k->evdnctype == EV_PAIRED_READ) { printf("\tGT:AD:GQ\t./.:.,.:."); return; }     /* no precise breakpoint */
+    if (k->evdnctype == EV_PAIRED_READ) {
+        if (!g_pair_counts || !k->rs_valid) { printf("\tGT:AD:GQ\t./.:.,.:."); return; }     /* no precise breakpoint */
+        /* -P: RP = the thinnest depth of concordant fragments over [POS, max(END, BP_END)], AP = the pairs the discovery pass
+         * clustered into the variant that re-finds this one */
+        if (k->rs + k->ap == 0) { printf("\tGT:AD:GQ\t./.:0,0:."); return; }
+        int best, gq;
+        genotype_of((int64_t)k->rs, (int64_t)k->ap, &best, &gq);
+        printf("\tGT:AD:GQ\t%s:%u,%u:%d", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", k->rs, k->ap, gq);
+        return;
+    }
     int64_t rs = k->rs_valid ? (int64_t)k->rs : 0;
     /* a DC read adds one at every position of the interval, so the minimum holds them all -- where the walk has delivered them:
      * a region run (-c) scatters the records of its stretch only */
@@ -1867,6 +1917,23 @@ static void print_known_counted(driver* d, known_list* kl, int from, int to, con
         pthread_mutex_unlock(&g_query_mu);
         if (qrc != IM_OK) fatalf("im_span_query: %s", im_last_error(d->gpu));
         for (int q = 0; q < m; q++) { kl->v[who[q]]->rs = rs[q]; kl->v[who[q]]->rs_valid = 1; }
+    }
+    if (g_pair_counts) {
+        /* -P: the PAIRED_READ ones from the pair-span array */
+        m = 0;
+        for (int ki = from; ki < to; ki++) {
+            knownvariant_t* k = kl->v[ki];
+            if (k->evdnctype != EV_PAIRED_READ) continue;
+            beg[m] = (int32_t)k->start; end[m] = (int32_t)(k->bpstop > k->stop ? k->bpstop : k->stop); who[m] = ki; m++;
+        }
+        if (m > 0) {
+            gpu_wait(d);
+            pthread_mutex_lock(&g_query_mu);
+            const int qrc = d->pipe_mode ? im_pairspan_query_tid(d->gpu, kl->v[who[0]]->tid, m, beg, end, rs) : im_pairspan_query(d->gpu, m, beg, end, rs);
+            pthread_mutex_unlock(&g_query_mu);
+            if (qrc != IM_OK) fatalf("im_pairspan_query: %s", im_last_error(d->gpu));
+            for (int q = 0; q < m; q++) { kl->v[who[q]]->rs = rs[q]; kl->v[who[q]]->rs_valid = 1; }
+        }
     }
     free(beg); free(end); free(rs); free(who);
     for (int ki = from; ki < to; ki++) {
@@ -1914,7 +1981,11 @@ static void print_knownvariants(driver* d, known_list* kl, const variant_list* v
             const variant_t* last = vars->v[vars->n - 1];
             if (last->start < k->start) break;
         }
-        if (found) { found[ki - kl->next] = (uint8_t)is_found; continue; }
+        if (found) {
+            found[ki - kl->next] = (uint8_t)is_found;
+            k->ap = is_found ? vars->v[ui]->support : 0;
+            continue;
+        }
         print_vcf_line(d, k);
         if (is_found) printf(";%s", g_sample_name);
         else if (k->evdnctype == EV_SPLIT_READ && is_indel_supported(d, k)) printf(";%s", g_sample_name);

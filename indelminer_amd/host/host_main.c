@@ -36,6 +36,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t-G, add genotype columns (FORMAT GT:AD:GQ) to the vcf output\n");
     fprintf(file, "\t-A, with indels.vcf: genotype the known indels in this sample\n");
     fprintf(file, "\t    (FORMAT GT:AD:GQ from the reads for and against each)\n");
+    fprintf(file, "\t-P, with -G or -A: genotype PAIRED_READ records too, from the\n");
+    fprintf(file, "\t    concordant pairs whose fragment spans the deletion\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -78,7 +80,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GA")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAP")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -104,6 +106,7 @@ int main(int argc, char** argv)
         case 'b': if (sscanf(optarg, "%u", &O.minbalance) != 1) fatalf("incorrect option for -b: %s\n", optarg); break;
         case 'G': g_genotype = 1; break;                            /* not an option of the reference */
         case 'A': g_known_counts = 1; break;                        /* not an option of the reference */
+        case 'P': g_pair_counts = 1; break;                         /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -137,15 +140,27 @@ int main(int argc, char** argv)
         const char* ws_ = getenv("WORLD_SIZE");
         if (g_vcfname != NULL) { fprintf(stderr, "indelminer: -G is not available with a VCF argument (annotate mode)\n"); return EXIT_FAILURE; }
         if ((ws_ && atoi(ws_) > 1) || getenv("INDELMINER_FORCE_MGPU")) { fprintf(stderr, "indelminer: -G is not available with more than one rank\n"); return EXIT_FAILURE; }
-        if (!im_span_enable || !im_dev_span_scatter || !im_span_scan || !im_span_query_tid || !im_span_build || !im_span_query) {
-            fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
-        }
-        if (strcmp(O.outputformat, "detailed") == 0) g_genotype = 0;    /* -o detailed has no columns to add to */
     }
 
     if (g_known_counts) {
         const char* ws_ = getenv("WORLD_SIZE");
         if ((ws_ && atoi(ws_) > 1) || getenv("INDELMINER_FORCE_MGPU")) { fprintf(stderr, "indelminer: -A is not available with more than one rank\n"); return EXIT_FAILURE; }
+    }
+
+    /* -P: behind the refusals of -G and -A, in front of what the three need of the library (the newest entry points first) */
+    if (g_pair_counts) {
+        if (!g_genotype && !g_known_counts) { fprintf(stderr, "indelminer: -P needs -G or -A\n"); return EXIT_FAILURE; }
+        if (!im_pairspan_enable || !im_dev_pairspan_scatter || !im_pairspan_scan || !im_pairspan_query_tid || !im_pairspan_build || !im_pairspan_query) {
+            fprintf(stderr, "indelminer: genotyping paired-read records (-P) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
+    if (g_genotype) {
+        if (!im_span_enable || !im_dev_span_scatter || !im_span_scan || !im_span_query_tid || !im_span_build || !im_span_query) {
+            fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
+        }
+        if (strcmp(O.outputformat, "detailed") == 0) g_genotype = g_pair_counts = 0;    /* -o detailed has no columns to add to */
+    }
+    if (g_known_counts) {
         if (!im_support_count || !im_span_enable || !im_dev_span_scatter || !im_span_scan || !im_span_query_tid || !im_span_build || !im_span_query) {
             fprintf(stderr, "indelminer: genotyping known indels (-A) needs the device library\n"); return EXIT_FAILURE;
         }
@@ -230,6 +245,7 @@ int main(int argc, char** argv)
                 const char* op = getenv("INDELMINER_ONEPASS");          /* INDELMINER_ONEPASS=0: the pre-pass of the reference's layout */
                 /* several ranks: always the one walk (run_pipeline: the ranks exchange what their walks logged) */
                 g_onepass = O.configfile == NULL && g_vcfname == NULL && chromid == -1 && (g_mg || !(op && strcmp(op, "0") == 0));
+                if (PAIR_ON) g_onepass = 0;             /* -P: the first chunk's scatter looks read groups up in the finished table */
             }
             pool = walkpool_start(&d);
         }

@@ -39,12 +39,14 @@ static void print_output_header(void)
         printf("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype, the most likely of 0/0, 0/1, 1/1 given AD\">\n");
         printf("##FORMAT=<ID=AD,Number=2,Type=Integer,Description=\"Read support of the reference and the alternative allele in this sample: the smallest number, over the positions POS .. POS+(BP_END-END) the breakpoint can lie at, of alignments that match the reference for the -n distance on both sides of it, less those of them that support the indel; and the reads with mapping quality of at least -q that support the indel, by their CIGAR or by aligning at least as well against the reference with the indel applied\">\n");
         printf("##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred-scaled distance to the second most likely genotype, at most 99\">\n");
+        if (g_pair_counts) printf("##pairedReadAD=\"PAIRED_READ records: AD = concordant pairs spanning the deletion with -n bases on each side (lower bound), pairs supporting it\"\n");
         printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", g_sample_name);
     } else if (g_genotype) {
         /* -G: no reference counterpart */
         printf("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype, the most likely of 0/0, 0/1, 1/1 given AD\">\n");
         printf("##FORMAT=<ID=AD,Number=2,Type=Integer,Description=\"Read support of the reference and the alternative allele: the smallest number, over the positions POS .. POS+(BP_END-END) the breakpoint can lie at, of alignments that match the reference for the -n distance on both sides of it (an upper bound of the reads spanning the whole interval, exact when the interval is one position), and NS\">\n");
         printf("##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred-scaled distance to the second most likely genotype, at most 99\">\n");
+        if (g_pair_counts) printf("##pairedReadAD=\"PAIRED_READ records: AD = concordant pairs spanning the deletion with -n bases on each side (lower bound), pairs supporting it\"\n");
         printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", g_sample_name);
     } else if (strncmp(O.outputformat, "vcf", 3) == 0) printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
     fflush(OUT);
@@ -312,7 +314,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
     bam_region_iter it;
     bam_record b; memset(&b, 0, sizeof b);
     if (bam_region_begin(&it, r, d->idx, tid, beg, end) != 0) fatalf("cannot seek in %s", d->bam_name);
-    d->n_seg = 0; d->n_run = 0;
+    d->n_seg = 0; d->n_run = 0; d->n_frag = 0;
     const int whole = (beg <= 0 && end >= d->hdr->target_len[tid]);
     volatile int died = 0;              /* a record the reference dies on ended the pass: the flushes in front of it are still to print */
     t_is_main_thread_of_passA = 1;
@@ -361,6 +363,19 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
             }
         }
         dispatch_record(d, &b);
+        if (PAIR_ON && concordant_left_mate(d, &b)) {
+            /* -P: the fragment [pos, pos + isize) of the pair, clipped to what an int32 start and length hold (the device clips
+             * to the contig).  Behind dispatch_record: a read group that is not in the table has ended the run there. */
+            const int64_t a = b.pos < 0 ? 0 : b.pos, e = (int64_t)b.pos + b.isize > INT32_MAX ? INT32_MAX : (int64_t)b.pos + b.isize;
+            if (e > a) {
+                if (d->n_frag == d->cap_frag) {
+                    d->cap_frag = d->cap_frag ? d->cap_frag * 2 : (1 << 16);
+                    d->frag_start = xrealloc(d->frag_start, sizeof(int32_t) * (size_t)d->cap_frag);
+                    d->frag_len = xrealloc(d->frag_len, sizeof(int32_t) * (size_t)d->cap_frag);
+                }
+                d->frag_start[d->n_frag] = (int32_t)a; d->frag_len[d->n_frag] = (int32_t)(e - a); d->n_frag++;
+            }
+        }
     }
     g_passA_armed = 0;
     free(b.data);
@@ -379,6 +394,13 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
         if (im_span_build(d->gpu, d->seqlen[tid], (int32_t)d->n_run, d->run_start, d->run_len, (int32_t)O.ethreshold) != IM_OK)
             fatalf("im_span_build: %s", im_last_error(d->gpu));
         phase_time("span array (device)");
+    }
+    if (PAIR_ON) {
+        gpu_wait(d);
+        if (d->n_frag > INT32_MAX) fatalf("more than 2^31 concordant pairs on one contig");
+        if (im_pairspan_build(d->gpu, d->seqlen[tid], (int32_t)d->n_frag, d->frag_start, d->frag_len, (int32_t)O.ethreshold) != IM_OK)
+            fatalf("im_pairspan_build: %s", im_last_error(d->gpu));
+        phase_time("pair-span array (device)");
     }
 
     im_read_result* res = NULL;

@@ -781,6 +781,10 @@ static void run_pipeline(driver* d, walkpool_t* o)
             for (int k = 0; k < n_held; k++)
                 for (int cj = 0; cj < held[k]->n_ctg; cj++)
                     if (held[k]->ctg[cj].last) GPU2(d, im_span_scan(d->gpu, held[k]->ctg[cj].tid, S.stream));
+        if (PAIR_ON)                             /* -P: and the pair-span array */
+            for (int k = 0; k < n_held; k++)
+                for (int cj = 0; cj < held[k]->n_ctg; cj++)
+                    if (held[k]->ctg[cj].last) GPU2(d, im_pairspan_scan(d->gpu, held[k]->ctg[cj].tid, S.stream));
         GPU2(d, im_stream_sync(d->gpu, S.stream));
         if (nrep) {
             pthread_mutex_lock(&o->mu);

@@ -1,0 +1,681 @@
+"""Genotype columns of PAIRED_READ records (-P): the concordant-pair counts of im_span.hip's pair_scatter_kernel and what the host
+driver makes of them.
+
+The yardstick is the plain restatement in this file (fragment_of / pspan_of / genotype_of), written from the definition in
+include/indelminer_amd.h and DESIGN.md section 4.5c, not the code under test.  With m = -n (>= 1), q = -q and range_max = range[1]
+of the record's read group (its RG:Z tag, "generic" without one):
+
+  * a record is a concordant left mate iff flag & 0x1, none of 0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800, 0 <= tid < contigs,
+    mtid == tid, bit 0x10 != bit 0x20, isize > 0, pos < mpos or (pos == mpos and flag & 0x40), mapq >= q, its group is in the
+    table and isize <= range_max;
+  * its fragment is [pos, pos + isize) clipped to [0, clen);
+  * pspan[p], 0 <= p <= clen, counts the fragments [a, b) with a + m <= p and p + m <= b;
+  * RP of a PAIRED_READ record = min(pspan[p] for p in POS .. max(END, BP_END)); GT / GQ from (RP, NS) in integers.
+
+The group names used here are never a prefix of one another, so the table look-up is a plain dictionary.
+"""
+import importlib.util
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+
+EXCLUDED = 0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800
+
+
+# ------------------------------------------------------------------------------------------ the restatement
+# a record: (tid, pos, mapq, flag, mtid, mpos, isize, group name or None)
+
+def fragment_of(rec, n_contigs, q, table):
+    """(tid, a, b) of a concordant left mate, unclipped; None for every other record"""
+    tid, pos, mapq, flag, mtid, mpos, isize, rg = rec[:8]
+    if not flag & 0x1 or flag & EXCLUDED:
+        return None
+    if not 0 <= tid < n_contigs or mtid != tid:
+        return None
+    if ((flag >> 4) & 1) == ((flag >> 5) & 1):
+        return None
+    if isize <= 0:
+        return None
+    if not (pos < mpos or (pos == mpos and flag & 0x40)):
+        return None
+    if mapq < q:
+        return None
+    name = "generic" if rg is None else rg
+    if name not in table or isize > table[name]:
+        return None
+    return tid, pos, pos + isize
+
+
+def pspan_of_fragments(frags, clen, m):
+    """frags: [(a, b)] of one contig -> pspan[0 .. clen] through a difference array"""
+    d = np.zeros(clen + 2, np.int64)
+    for a, b in frags:
+        a, b = max(a, 0), min(b, clen)
+        if b - a >= 2 * m:
+            d[a + m] += 1          # first p with a + m <= p
+            d[b - m + 1] -= 1      # one past the last p with p + m <= b
+    return np.cumsum(d)[:clen + 1]
+
+
+def pspan_of(records, clens, m, q, table):
+    per = [[] for _ in clens]
+    for rec in records:
+        f = fragment_of(rec, len(clens), q, table)
+        if f is not None:
+            per[f[0]].append((f[1], f[2]))
+    return [pspan_of_fragments(per[t], clens[t], m) for t in range(len(clens))]
+
+
+def pspan_brute(records, clen, tid_want, m, q, table, n_contigs):
+    """the definition itself, position by position (small contigs): checks the restatement above"""
+    out = np.zeros(clen + 1, np.int64)
+    for rec in records:
+        f = fragment_of(rec, n_contigs, q, table)
+        if f is None or f[0] != tid_want:
+            continue
+        a, b = max(f[1], 0), min(f[2], clen)
+        for p in range(clen + 1):
+            if a + m <= p and p + m <= b:
+                out[p] += 1
+    return out
+
+
+def genotype_of(rs, ns):
+    """(GT, GQ) in thousandths of a phred, integers only"""
+    E, C, H = 20000, 44, 3010
+    L = [ns * E + rs * C, (ns + rs) * H, ns * C + rs * E]
+    lo = min(L)
+    L = [x - lo for x in L]
+    best = L.index(0)                       # the lower index wins a tie
+    second = sorted(L[:best] + L[best + 1:])[0]
+    return ("0/0", "0/1", "1/1")[best], min(99, (second + 500) // 1000)
+
+
+# ------------------------------------------------------------------------------------------ records
+
+def rg_tag(name):
+    return b"RGZ" + name.encode() + b"\0"
+
+
+# about 300 bytes of what an aligner writes in front of RG, a B array among them: the kernel's 24-byte tag window has to move
+LONG_AUX = (b"NMi" + struct.pack("<i", 3) + b"MDZ" + b"10A20C30G38" * 9 + b"\0" + b"ZBBS" + struct.pack("<I", 40) + bytes(range(80)) +
+            b"ASc\x64" + b"XAZ" + b"chr9,+1234,100M,2;" * 5 + b"\0" + b"MQC\x3c")
+assert 290 <= len(LONG_AUX) <= 330
+
+
+def raw_records(records):
+    """[(tid, pos, mapq, flag, mtid, mpos, isize, rg[, aux bytes in front of RG])] -> the device layout (raw uint8, rec_off
+    uint32[n + 1]): core with the mate fields, qname, CIGAR 100M, packed bases, qualities, aux tags; 4-byte aligned starts"""
+    blob, off = bytearray(), [0]
+    for i, rec in enumerate(records):
+        tid, pos, mapq, flag, mtid, mpos, isize, rg = rec[:8]
+        aux = (rec[8] if len(rec) > 8 else b"") + (rg_tag(rg) if rg is not None else b"")
+        qname = b"p%d\0" % i
+        l_seq = 100
+        core = struct.pack("<iiBBHHHiiii", tid, pos, len(qname), mapq, 4680, 1, flag, l_seq, mtid, mpos, isize)
+        body = core + qname + struct.pack("<I", (100 << 4) | 0) + b"\x11" * ((l_seq + 1) // 2) + b"\x28" * l_seq + aux
+        blob += body + b"\0" * (-len(body) % 4)
+        off.append(len(blob))
+    return np.frombuffer(bytes(blob), np.uint8).copy(), np.array(off, np.uint32)
+
+
+def aux_group(aux):
+    """the value of the first RG tag of an aux area (None without one), walking the fields as samtools does"""
+    size = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4, "d": 8}
+    p = 0
+    while p + 4 <= len(aux):
+        tag, typ = aux[p:p + 2], chr(aux[p + 2])
+        p += 3
+        if typ in "ZH":
+            e = aux.index(b"\0", p)
+            if tag == b"RG":
+                return aux[p:e].decode()
+            p = e + 1
+        elif typ == "B":
+            p += 5 + size[chr(aux[p])] * struct.unpack_from("<I", aux, p + 1)[0]
+        elif typ in size:
+            p += size[typ]
+        else:
+            break
+    return None
+
+
+def parse_record(b, o, end):
+    """one record with its base qualities at b[o:end] -> (tid, pos, mapq, flag, mtid, mpos, isize, rg, reference length)"""
+    tid, pos, l_qname, mapq, _bin, n_cig, flag, l_seq, mtid, mpos, isize = struct.unpack_from("<iiBBHHHiiii", b, o)
+    cw = struct.unpack_from("<%dI" % n_cig, b, o + 32 + l_qname)
+    reflen = sum(c >> 4 for c in cw if (c & 15) in (0, 2, 3, 7, 8))
+    o_aux = o + 32 + l_qname + 4 * n_cig + (l_seq + 1) // 2 + l_seq
+    return tid, pos, mapq, flag, mtid, mpos, isize, aux_group(b[o_aux:end]), reflen
+
+
+def parse_raw(raw, off):
+    b = raw.tobytes()
+    return [parse_record(b, int(off[i]), int(off[i + 1])) for i in range(len(off) - 1)]
+
+
+def read_bam_records(path):
+    """(contigs [(name, length)], records) of a BAM file"""
+    from tests.support import bamlite
+    raw = bytes(bamlite.bgzf_decompress(path))
+    assert raw[:4] == b"BAM\1"
+    p = 8 + struct.unpack_from("<i", raw, 4)[0]
+    n_ref = struct.unpack_from("<i", raw, p)[0]; p += 4
+    refs = []
+    for _ in range(n_ref):
+        l_name = struct.unpack_from("<i", raw, p)[0]; p += 4
+        name = raw[p:p + l_name - 1].decode(); p += l_name
+        refs.append((name, struct.unpack_from("<i", raw, p)[0])); p += 4
+    recs = []
+    while p < len(raw):
+        bs = struct.unpack_from("<i", raw, p)[0]; p += 4
+        recs.append(parse_record(raw, p, p + bs))
+        p += bs
+    return refs, recs
+
+
+# ------------------------------------------------------------------------------------------ device level
+
+class Device:
+    """one context with the genome-wide pair-span array enabled for (m, q) over contigs of the given lengths"""
+
+    def __init__(self, clens, m, q, table=None, seed=3):
+        from indelminer_amd import capi
+        self.capi = capi
+        rng = np.random.default_rng(seed)
+        self.clens = list(clens)
+        self.ctx = capi.Context(0)
+        self.ctx.set_reference([bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), n)) for n in clens])
+        if table is not None:
+            self.ctx.set_insert_ranges(list(table), [table[k] for k in table])
+        self.ctx.pairspan_enable(m, q)
+        self.keep = []
+
+    def scatter(self, raw, off):
+        capi = self.capi
+        d_raw = capi.DevBuf(self.ctx, len(raw) + 64).upload(raw)
+        d_off = capi.DevBuf(self.ctx, 4 * len(off)).upload(off)
+        self.keep += [d_raw, d_off]
+        self.ctx.pairspan_scatter(capi.DevRecords(len(off) - 1, d_raw.ptr, d_off.ptr, 0))
+
+    def scan(self):
+        for t in range(len(self.clens)):
+            self.ctx.pairspan_scan(t)
+        self.ctx._check(self.capi.lib().im_stream_sync(self.ctx.h, self.ctx.stream))
+
+    def every_position(self, tid):
+        p = np.arange(self.clens[tid] + 1, dtype=np.int32)
+        return self.ctx.pairspan_query_tid(tid, p, p).astype(np.int64)
+
+    def close(self):
+        for b in self.keep:
+            b.free()
+        self.ctx.close()
+
+
+def interval_queries(rng, clen, n=400):
+    """whole intervals: short, longer than a wave's 64 lanes, reaching out of the contig on both sides, the whole contig"""
+    beg = rng.integers(-50, clen + 1, n)
+    ln = np.concatenate([rng.integers(0, 8, n // 2), rng.integers(60, 700, n - n // 2)])
+    end = beg + ln
+    beg = np.concatenate([beg, [0, -5, clen, clen - 1]]); end = np.concatenate([end, [clen, clen + 40, clen, clen + 9]])
+    return beg.astype(np.int32), end.astype(np.int32)
+
+
+def interval_minima(span, beg, end, clen):
+    out = []
+    for a, b in zip(beg, end):
+        a, b = max(int(a), 0), min(int(b), clen)
+        out.append(int(span[a:b + 1].min()) if a <= b else 0)
+    return np.array(out, np.int64)
+
+
+def check_device(dev, want, rng):
+    for tid, clen in enumerate(dev.clens):
+        got = dev.every_position(tid)
+        bad = np.nonzero(got != want[tid])[0]
+        assert len(bad) == 0, (tid, bad[:10], got[bad[:10]], want[tid][bad[:10]])
+        beg, end = interval_queries(rng, clen)
+        assert np.array_equal(dev.ctx.pairspan_query_tid(tid, beg, end).astype(np.int64), interval_minima(want[tid], beg, end, clen)), tid
+
+
+CLENS = [150_000, 5_000]
+TABLE = {"generic": 700, "rgB": 400}
+LONG_NAME = "read_group_%03d_of_a_library_with_a_long_name"
+BIG_TABLE = dict([("generic", 700)] + [(LONG_NAME % i, 450 + i) for i in range(150)] + [("rgB", 400)] +
+                 [(LONG_NAME % i, 450 + i) for i in range(150, 300)])
+F = 0x1 | 0x2 | 0x20 | 0x40                    # paired, proper, forward with the mate reverse, first in pair
+
+
+def left(tid, pos, isize, flag=F, mapq=60, rg=None, mtid=None, mpos=None, aux=b""):
+    return (tid, pos, mapq, flag, tid if mtid is None else mtid, pos + max(1, isize - 100) if mpos is None else mpos, isize, rg, aux)
+
+
+def hand_made(m, q=10):
+    c0, c1 = CLENS
+    R = [
+        left(0, 1000, 500),                                         # the workgroup's first counted record: the LDS window starts here
+        left(0, 1010, 2 * m),                                       # a fragment of exactly 2 m: one position
+        left(0, 1020, 2 * m - 1),                                   # one base short: none
+        left(0, 1030, 700), left(0, 1031, 701),                     # isize == range_max counts, range_max + 1 does not: generic
+        left(0, 1040, 400, rg="rgB"), left(0, 1041, 401, rg="rgB"),     # the same for the second group
+        left(0, 1050, 450, rg="nobody"),                            # a group that is not in the table: skipped, no error
+        left(0, 1060, 400, rg="rgB", aux=LONG_AUX), left(0, 1061, 401, rg="rgB", aux=LONG_AUX),    # RG behind ~300 bytes of tags
+        left(0, 1062, 650, aux=LONG_AUX),                           # the same tags and no RG at all: generic
+    ]
+    R += [left(0, 1070 + k, 480, flag=F | bit) for k, bit in enumerate((0x4, 0x8, 0x100, 0x200, 0x400, 0x800))]
+    R += [
+        left(0, 1080, 480, flag=F & ~0x1),                          # not paired
+        left(0, 1081, 480, flag=0x1 | 0x2 | 0x40),                  # both mates forward
+        left(0, 1082, 480, flag=0x1 | 0x2 | 0x10 | 0x20 | 0x40),    # both mates reverse
+        left(0, 1083, 480, flag=0x1 | 0x2 | 0x10 | 0x40),           # reverse with the mate forward, still the left one: counts
+        left(0, 1084, 480, mtid=1),                                 # the mate on another contig, isize plausible
+        left(0, 1085, -480, mpos=1500),                             # isize < 0
+        left(0, 1086, 480, mpos=900),                               # isize > 0 and pos > mpos
+        left(0, 1090, 300, mpos=1090, flag=0x1 | 0x2 | 0x20 | 0x40),    # pos == mpos: the first in pair counts ...
+        left(0, 1090, 300, mpos=1090, flag=0x1 | 0x2 | 0x10 | 0x80),    # ... the second does not (its strand bits differ too)
+        left(0, 1100, 480, mapq=q - 1), left(0, 1101, 480, mapq=q),
+        left(-1, 1102, 480), left(7, 1103, 480),                    # no contig, a contig that does not exist
+        left(0, c0 - 300, 600),                                     # reaches past clen: clipped
+        left(0, c0 - 2 * m + 1, 300),                               # what is left of it inside the contig is one base short
+        left(0, 0, 500),                                            # starts at position 0 (in front of the window)
+        left(1, 200, 450), left(1, c1 - 200, 500, rg="rgB"),        # a second contig inside the same workgroup; rgB takes 400 only
+        left(1, c1 - 200, 400, rg="rgB"),
+        left(0, 101_000, 520), left(0, 101_040, 690),               # 100 kb from the workgroup's first record: outside the window
+        left(0, 4800, 700),                                         # opens inside the window (1000 .. 5095), closes outside it
+        left(0, 5090, 300),                                         # opens on the window's last positions
+        left(0, 1200, 480),                                         # and back again (unsorted input is legal for the scatter)
+    ]
+    return R
+
+
+def check_hand_made_against_definition(recs, m, table):
+    want = pspan_of(recs, CLENS, m, 10, table)
+    # the restatement against the definition, where that is affordable
+    assert np.array_equal(want[1], pspan_brute(recs, CLENS[1], 1, m, 10, table, len(CLENS)))
+    one = lambda r: pspan_of([r], CLENS, m, 10, table)[0]
+    assert one(recs[1]).sum() == 1 and one(recs[2]).sum() == 0
+    assert one(recs[3]).max() == 1 and one(recs[4]).max() == 0 and one(recs[5]).max() == 1 and one(recs[6]).max() == 0
+    assert one(recs[7]).max() == 0 and one(recs[8]).max() == 1 and one(recs[9]).max() == 0 and one(recs[10]).max() == 1
+    pos_eq = [r for r in recs if r[1] == 1090]
+    assert [int(pspan_of([r], CLENS, m, 10, table)[0].max()) for r in pos_eq] == [1, 0]
+    assert want[0][CLENS[0] - m] >= 1 and want[0][CLENS[0] - m + 1] == 0 and want[1][CLENS[1] - m] == 1 and want[1][300] == 1
+    return want
+
+
+@pytest.mark.parametrize("m", [10, 25])
+def test_pairspan_hand_made_records_every_position(m):
+    recs = hand_made(m)
+    want = check_hand_made_against_definition(recs, m, TABLE)
+    dev = Device(CLENS, m, 10, TABLE)
+    try:
+        raw, off = raw_records(recs)
+        assert parse_raw(raw, off) == [r[:8] + (100,) for r in recs]        # the packer and the parser agree
+        dev.scatter(raw, off)
+        dev.scan()
+        check_device(dev, want, np.random.default_rng(m))
+    finally:
+        dev.close()
+
+
+def test_pairspan_table_beyond_lds():
+    """a table of 302 groups with long names (about 19 KB: read from memory, not through LDS), rgB in the middle of it; records of
+    long-named groups on both sides of their own range_max"""
+    m = 10
+    recs = hand_made(m)
+    for i in (0, 149, 150, 299):
+        recs += [left(0, 2000 + i, 450 + i, rg=LONG_NAME % i), left(0, 2000 + i, 451 + i, rg=LONG_NAME % i),
+                 left(0, 2300 + i, 450 + i, rg=LONG_NAME % i, aux=LONG_AUX)]
+    recs.append(left(0, 2600, 450, rg=LONG_NAME % 300))             # one more than the table holds
+    want = check_hand_made_against_definition(recs, m, BIG_TABLE)
+    assert want[0][2100:2400].max() >= 2
+    dev = Device(CLENS, m, 10, BIG_TABLE)
+    try:
+        raw, off = raw_records(recs)
+        dev.scatter(raw, off)
+        dev.scan()
+        check_device(dev, want, np.random.default_rng(7))
+    finally:
+        dev.close()
+
+
+def test_pairspan_synthetic_chunk_every_position():
+    """a chunk at the density of the 30x benchmark input (two contigs, so that workgroups straddle the contig boundary), scattered
+    in two calls, with the hand-made records on top"""
+    from indelminer_amd import rawrec, synth
+    refs, rd = synth.simulate(seed=11, ref_len=150_000, coverage=30, n_contigs=2, big_every=9)
+    clens = [len(r) for r in refs]
+    raw, off = rawrec.records(rd)
+    half = rd.n // 2
+    m, q = 10, 10
+    dev = Device(clens, m, q, TABLE)
+    try:
+        for lo, hi in ((0, half), (half, rd.n)):
+            r, o = rawrec.records(rd, lo, hi)
+            dev.scatter(r, o)
+        extra = [x for x in hand_made(m) if x[0] != 1 or x[1] < 1000]
+        hr, ho = raw_records(extra)
+        dev.scatter(hr, ho)
+        dev.scan()
+        recs = parse_raw(raw, off) + extra
+        assert len(recs) == rd.n + len(extra)
+        want = pspan_of(recs, clens, m, q, TABLE)
+        # 30x of 100-base reads with 500-base inserts: about 70 fragments over a position
+        assert np.median(want[0]) > 50 and np.median(want[1]) > 50
+        check_device(dev, want, np.random.default_rng(5))
+    finally:
+        dev.close()
+
+
+def test_pairspan_records_without_qualities_and_reset():
+    """the layout the product's walkers deliver (no base qualities); im_pairspan_reset + a second pass gives the same array"""
+    from indelminer_amd import rawrec, synth
+    refs, rd = synth.simulate(seed=12, ref_len=60_000, coverage=20)
+    clens = [len(r) for r in refs]
+    raw, off = rawrec.records(rd, qual=False, rg="rgB", aux_prefix=LONG_AUX[:-4])
+    full_raw, full_off = rawrec.records(rd, rg="rgB", aux_prefix=LONG_AUX[:-4])
+    assert len(raw) < len(full_raw)
+    table = {"generic": 700, "rgB": 520}                            # about two thirds of the pairs are within rgB's range
+    want = pspan_of(parse_raw(full_raw, full_off), clens, 12, 10, table)
+    assert 3 < np.median(want[0]) < np.median(pspan_of(parse_raw(full_raw, full_off), clens, 12, 10, {"rgB": 700})[0])
+    dev = Device(clens, 12, 10, table)
+    try:
+        dev.scatter(raw, off)
+        dev.scan()
+        assert np.array_equal(dev.every_position(0), want[0])
+        dev.ctx.pairspan_reset(0)
+        dev.scatter(raw, off)
+        dev.scan()
+        assert np.array_equal(dev.every_position(0), want[0])
+    finally:
+        dev.close()
+
+
+def pspan_of_arrays(start, length, clen, m):
+    """pspan_of_fragments on arrays; the tests check it against pspan_of_fragments itself first"""
+    a = np.clip(start.astype(np.int64), 0, clen); b = np.clip(start.astype(np.int64) + length, 0, clen)
+    ok = b - a >= 2 * m
+    d = np.zeros(clen + 2, np.int64)
+    np.add.at(d, a[ok] + m, 1); np.add.at(d, b[ok] - m + 1, -1)
+    return np.cumsum(d)[:clen + 1]
+
+
+def test_pairspan_host_fragments_form_and_tile_edge():
+    """im_pairspan_build / im_pairspan_query on host-given fragments: 30 000 random ones, then a contig whose clen + 1 is a
+    multiple of the scan's 8192-position tile"""
+    from indelminer_amd import capi
+    rng = np.random.default_rng(21)
+    ctx = capi.Context(0)
+    try:
+        for clen, m in ((90_000, 10), (90_000, 25), (33 * 8192 - 1, 10)):
+            start = rng.integers(-300, clen + 50, 30_000).astype(np.int32)
+            length = rng.choice([19, 20, 21, 49, 50, 51, 300, 480, 500, 700], 30_000).astype(np.int32)
+            want = pspan_of_arrays(start, length, clen, m)
+            if clen == 90_000:
+                assert np.array_equal(want, pspan_of_fragments([(int(s), int(s) + int(l)) for s, l in zip(start, length)], clen, m))
+            assert want.max() > 20
+            ctx.pairspan_build(clen, start, length, m)
+            p = np.arange(clen + 1, dtype=np.int32)
+            assert np.array_equal(ctx.pairspan_query(p, p).astype(np.int64), want), (clen, m)
+            beg, end = interval_queries(rng, clen)
+            assert np.array_equal(ctx.pairspan_query(beg, end).astype(np.int64), interval_minima(want, beg, end, clen)), (clen, m)
+        ctx.pairspan_build(100, np.zeros(0, np.int32), np.zeros(0, np.int32), 3)
+        assert not ctx.pairspan_query(np.arange(101, dtype=np.int32), np.arange(101, dtype=np.int32)).any()
+    finally:
+        ctx.close()
+
+
+def test_pairspan_build_and_span_build_keep_their_own_arrays():
+    """-G -P on the record-at-a-time path holds both: im_span_build, then im_pairspan_build, then each query answers its own"""
+    from indelminer_amd import capi
+    rng = np.random.default_rng(23)
+    clen = 40_000
+    rs = rng.integers(0, clen, 9000).astype(np.int32); rl = rng.choice([40, 100], 9000).astype(np.int32)
+    fs = rng.integers(0, clen, 4000).astype(np.int32); fl = rng.choice([300, 500, 650], 4000).astype(np.int32)
+    span, pspan = pspan_of_arrays(rs, rl, clen, 10), pspan_of_arrays(fs, fl, clen, 10)
+    assert not np.array_equal(span, pspan)
+    p = np.arange(clen + 1, dtype=np.int32)
+    ctx = capi.Context(0)
+    try:
+        ctx.span_build(clen, rs, rl, 10)
+        ctx.pairspan_build(clen, fs, fl, 10)
+        assert np.array_equal(ctx.span_query(p, p).astype(np.int64), span)
+        assert np.array_equal(ctx.pairspan_query(p, p).astype(np.int64), pspan)
+        ctx.span_build(clen // 2, rs, rl, 10)                       # and the other way round, on another length
+        assert np.array_equal(ctx.pairspan_query(p, p).astype(np.int64), pspan)
+        assert np.array_equal(ctx.span_query(p[:clen // 2 + 1], p[:clen // 2 + 1]).astype(np.int64), pspan_of_arrays(rs, rl, clen // 2, 10))
+    finally:
+        ctx.close()
+
+
+def test_pairspan_scatter_without_insert_ranges_is_an_error():
+    dev = Device([5000], 10, 10, table=None)
+    try:
+        raw, off = raw_records([left(0, 100, 500)])
+        d_raw = dev.capi.DevBuf(dev.ctx, len(raw) + 64).upload(raw)
+        d_off = dev.capi.DevBuf(dev.ctx, 4 * len(off)).upload(off)
+        dev.keep += [d_raw, d_off]
+        recs = dev.capi.DevRecords(1, d_raw.ptr, d_off.ptr, 0)
+        import ctypes as C
+        rc = dev.capi.lib().im_dev_pairspan_scatter(dev.ctx.h, C.byref(recs), dev.ctx.stream)
+        assert rc != 0
+        assert b"im_set_insert_ranges" in dev.capi.lib().im_last_error(dev.ctx.h)
+    finally:
+        dev.close()
+
+
+# ------------------------------------------------------------------------------------------ the product
+
+META = '##pairedReadAD="PAIRED_READ records: AD = concordant pairs spanning the deletion with -n bases on each side (lower bound), pairs supporting it"'
+
+
+def _product():
+    from indelminer_amd import build
+    build.build()
+    return build.build_host()
+
+
+def _run(binary, flags, cwd, env=None, vcf=None, sample="sample"):
+    e = dict(os.environ)
+    e.update(env or {})
+    return subprocess.run([binary] + flags + ["ref.fa"] + ([vcf] if vcf else []) + [sample + "=aln.bam"], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e)
+
+
+def _ok(r):
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    return r.stdout
+
+
+def records_of(out):
+    """the record lines of a VCF as column lists"""
+    return [ln.split("\t") for ln in out.decode().split("\n") if ln and not ln.startswith("#")]
+
+
+def is_paired(cols):
+    return "PAIRED_READ" in cols[7].split(";")
+
+
+def strip_columns(out):
+    """a -G -P VCF without what the two options add: the ##FORMAT lines, the ##pairedReadAD line, the last two columns"""
+    lines = []
+    for ln in out.decode().split("\n"):
+        if ln.startswith("##FORMAT=") or ln.startswith("##pairedReadAD="):
+            continue
+        if ln and not ln.startswith("##"):
+            cols = ln.split("\t")
+            assert len(cols) == 10, ln
+            ln = "\t".join(cols[:8])
+        lines.append(ln)
+    return "\n".join(lines).encode()
+
+
+def check_header(out):
+    text = out.decode().split("\n")
+    fmt = [i for i, ln in enumerate(text) if ln.startswith("##FORMAT=")]
+    assert len(fmt) == 3 and fmt == list(range(fmt[0], fmt[0] + 3))
+    assert text[fmt[2] + 1] == META and text[fmt[2] + 2].startswith("#CHROM")
+    assert sum(1 for ln in text if ln.startswith("##pairedReadAD")) == 1
+
+
+def rp_of(pspan, names, cols):
+    info = dict(kv.split("=") for kv in cols[7].split(";") if "=" in kv)
+    pos, end, bp_end = int(cols[1]), int(info["END"]), int(info["BP_END"])
+    return int(pspan[names.index(cols[0])][pos:max(end, bp_end) + 1].min()), int(info["NS"])
+
+
+def pspan_of_bam(bam, m, q, table, region=None):
+    """region = (tid, beg, end): a -c run sees the records bam_fetch delivers for the stretch (those that overlap it)"""
+    refs, recs = read_bam_records(bam)
+    if region is not None:
+        rt, rb, re_ = region
+        recs = [r for r in recs if r[0] == rt and r[1] < re_ and r[1] + max(r[8], 1) > rb]
+    return [n for n, _ in refs], pspan_of(recs, [l for _, l in refs], m, q, table)
+
+
+def check_paired_columns(out, names, pspan):
+    """every PAIRED_READ line's GT:RP,NS:GQ against the restatement; returns [(RP, NS, GT)]"""
+    seen = []
+    for cols in records_of(out):
+        assert cols[8] == "GT:AD:GQ", cols
+        if not is_paired(cols):
+            continue
+        rp, ns = rp_of(pspan, names, cols)
+        gt, gq = genotype_of(rp, ns)
+        assert cols[9] == "%s:%d,%d:%d" % (gt, rp, ns, gq), (cols, rp)
+        seen.append((rp, ns, gt))
+    return seen
+
+
+def others(out):
+    return ["\t".join(c) for c in records_of(out) if not is_paired(c)]
+
+
+GENERIC = {"generic": 700}
+
+
+def test_product_paired_read_genotypes_homozygous(tmp_path):
+    """every read of the simulator's sample carries every deletion, and all nine PAIRED_READ deletions are at least 494 bases --
+    more than range_max - isize_min = 400, so no fragment of the deletion allele looks concordant: RP = 0 and 1/1, through the
+    restatement"""
+    prod = _product()
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(GOLD, "make_golden.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    d = str(tmp_path)
+    mg.write_dataset(d, mg.SYNTH_E2E["synth_2ctg_composite"])
+    bam = os.path.join(d, "aln.bam")
+    base = ["-i", "cfg.txt", "-s", "100"]
+    plain = _ok(_run(prod, base, d))
+    g = _ok(_run(prod, base + ["-G"], d))
+    gp = _ok(_run(prod, base + ["-G", "-P"], d))
+    check_header(gp)
+    assert strip_columns(gp) == plain
+    assert others(gp) == others(g) and len(others(g)) > 100
+    names, pspan = pspan_of_bam(bam, 10, 10, GENERIC)
+    seen = check_paired_columns(gp, names, pspan)
+    assert len(seen) >= 5
+    assert all(rp == 0 and gt == "1/1" for rp, ns, gt in seen), seen
+    for env in ({"INDELMINER_PIPELINE": "host"}, {"INDELMINER_PIECE_BYTES": "60000", "INDELMINER_WALKERS": "3"}):
+        assert _ok(_run(prod, base + ["-G", "-P"], d, env=env)) == gp, env
+    # a stretch of it
+    rflags = base + ["-c", "ctg0:1-100000"]
+    rg = _ok(_run(prod, rflags + ["-G"], d))
+    rgp = _ok(_run(prod, rflags + ["-G", "-P"], d))
+    assert strip_columns(rgp) == _ok(_run(prod, rflags, d)) and others(rgp) == others(rg)
+    rnames, rpspan = pspan_of_bam(bam, 10, 10, GENERIC, region=(0, 0, 100_000))
+    assert len(check_paired_columns(rgp, rnames, rpspan)) >= 1
+    # -o detailed ignores -P as it ignores -G; -n and -q move the flank and the gate
+    d0 = _ok(_run(prod, base + ["-o", "detailed"], d))
+    assert _ok(_run(prod, base + ["-o", "detailed", "-G", "-P"], d)) == d0 and len(d0) > 0
+    r2 = _ok(_run(prod, base + ["-n", "25", "-q", "30", "-G", "-P"], d))
+    names2, pspan2 = pspan_of_bam(bam, 25, 30, GENERIC)
+    assert len(check_paired_columns(r2, names2, pspan2)) >= 5
+
+
+@pytest.fixture(scope="module")
+def het_sample(tmp_path_factory):
+    """reads of two simulated samples with the same genome, one of them with large deletions, in one BAM: the deletions are on
+    about half the reads.  One contig: with more, big_every shifts the genome stream of the later ones."""
+    from indelminer_amd import bamwrite, synth
+    tmp = tmp_path_factory.mktemp("pairspan_het")
+    kw = dict(seed=6, ref_len=200_000, coverage=15, n_contigs=1)
+    refs, a = synth.simulate(big_every=4, **kw)
+    refs_b, b = synth.simulate(read_seed=77, big_every=0, **kw)
+    assert all(np.array_equal(x, y) for x, y in zip(refs, refs_b))
+    rd = synth.Reads()
+    order = np.lexsort((np.concatenate([a.pos, b.pos]), np.concatenate([a.tid, b.tid])))
+    for k in ("tid", "pos", "flag", "mpos", "isize", "seq", "cig_op", "cig_len", "ncig", "mate_first"):
+        setattr(rd, k, np.concatenate([getattr(a, k), getattr(b, k)])[order])
+    rd.pair_id = np.concatenate([a.pair_id, b.pair_id + int(a.pair_id.max()) + 1])[order]
+    rd.n, rd.read_len, rd.range_max, rd.mapq = a.n + b.n, a.read_len, a.range_max, a.mapq
+    contigs = [("ctg%d" % i, len(r)) for i, r in enumerate(refs)]
+    bamwrite.write_fasta(str(tmp / "ref.fa"), contigs, refs)
+    bamwrite.write_bam(str(tmp / "aln.bam"), contigs, rd)
+    (tmp / "cfg.txt").write_text("IL generic 300 700\n")
+    names, pspan = pspan_of_bam(str(tmp / "aln.bam"), 10, 10, GENERIC)
+    return str(tmp), names, pspan
+
+
+def test_product_paired_read_genotypes_heterozygous(het_sample):
+    d, names, pspan = het_sample
+    prod = _product()
+    base = ["-i", "cfg.txt", "-s", "100"]
+    plain = _ok(_run(prod, base, d))
+    g = _ok(_run(prod, base + ["-G"], d))
+    gp = _ok(_run(prod, base + ["-G", "-P"], d))
+    check_header(gp)
+    assert strip_columns(gp) == plain and others(gp) == others(g)
+    seen = check_paired_columns(gp, names, pspan)
+    assert len(seen) >= 8
+    assert sum(1 for rp, ns, gt in seen if rp >= 5 and gt == "0/1") >= 8, seen
+    for env in ({"INDELMINER_PIPELINE": "host"}, {"INDELMINER_PIECE_BYTES": "60000", "INDELMINER_WALKERS": "3"}):
+        assert _ok(_run(prod, base + ["-G", "-P"], d, env=env)) == gp, env
+    # without -P: the columns -G has always printed for these records, and no meta line
+    paired = [c for c in records_of(g) if is_paired(c)]
+    assert len(paired) == len(seen)
+    for c in paired:
+        ns = dict(kv.split("=") for kv in c[7].split(";") if "=" in kv)["NS"]
+        assert c[9] == "./.:.,%s:." % ns, c
+    assert b"pairedReadAD" not in g
+
+
+def test_product_paired_read_genotypes_annotate(het_sample):
+    """annotate mode on the sample's own calls: RP from the same query, AP = the support of the discovered variant that re-finds
+    the known one (the lines with the ;sample tag), GT / GQ by the integer rule on the printed pair"""
+    d, names, pspan = het_sample
+    prod = _product()
+    base = ["-i", "cfg.txt", "-s", "100"]
+    open(os.path.join(d, "calls.vcf"), "wb").write(_ok(_run(prod, base, d)))
+    a = _ok(_run(prod, base + ["-A", "-e", "1"], d, vcf="calls.vcf"))
+    ap = _ok(_run(prod, base + ["-A", "-P", "-e", "1"], d, vcf="calls.vcf"))
+    check_header(ap)
+    assert others(ap) == others(a) and len(others(a)) > 50
+    assert [c[:8] for c in records_of(ap)] == [c[:8] for c in records_of(a)]
+    n = tagged = 0
+    for cols in records_of(ap):
+        if not is_paired(cols):
+            continue
+        assert cols[8] == "GT:AD:GQ"
+        rp, _ns = rp_of(pspan, names, cols)
+        gt, ad, gq = cols[9].split(":")
+        got_rp, got_ap = (int(x) for x in ad.split(","))
+        assert got_rp == rp, (cols, rp)
+        if cols[7].split(";")[-1] == "sample":
+            assert got_ap > 0, cols
+            tagged += 1
+        if got_rp + got_ap == 0:
+            assert (gt, gq) == ("./.", "."), cols
+        else:
+            assert (gt, int(gq)) == genotype_of(got_rp, got_ap), cols
+        n += 1
+    assert n >= 8 and tagged >= 8
+    assert all(c[9] == "./.:.,.:." for c in records_of(a) if is_paired(c))
+    assert _ok(_run(prod, base + ["-A", "-P", "-e", "1"], d, vcf="calls.vcf", env={"INDELMINER_PIPELINE": "host"})) == ap
