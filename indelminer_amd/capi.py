@@ -417,17 +417,32 @@ class Context:
         self._check(rc, allow=allow)
         return rc, out
 
-    def depth_build(self, contig_len, seg_start, seg_len):
-        seg_start = np.ascontiguousarray(seg_start, dtype=np.int32)
-        seg_len = np.ascontiguousarray(seg_len, dtype=np.int32)
-        self._check(lib().im_depth_build(self.h, contig_len, len(seg_start), _ptr(seg_start), _ptr(seg_len)))
+    # one body per operation of the counted arrays (depth, span, pair-span); fn is the library function of the member
+    def _scan(self, fn, tid, stream):
+        self._check(fn(self.h, tid, self.stream if stream is None else stream))
 
-    def depth_query(self, beg, end):
+    _reset = _scan
+
+    def _build(self, fn, contig_len, start, length, *flank):
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        self._check(fn(self.h, contig_len, len(start), _ptr(start), _ptr(length), *[int(f) for f in flank]))
+
+    def _query(self, fn, beg, end, *tid):
         beg = np.ascontiguousarray(beg, dtype=np.int32)
         end = np.ascontiguousarray(end, dtype=np.int32)
         out = np.zeros(max(len(beg), 1), dtype=np.uint32)
-        self._check(lib().im_depth_query(self.h, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
+        self._check(fn(self.h, *tid, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
         return out[:len(beg)]
+
+    def _query_tid(self, fn, tid, beg, end):
+        return self._query(fn, beg, end, tid)
+
+    def depth_build(self, contig_len, seg_start, seg_len):
+        self._build(lib().im_depth_build, contig_len, seg_start, seg_len)
+
+    def depth_query(self, beg, end):
+        return self._query(lib().im_depth_query, beg, end)
 
     def support_batch(self, targets, queries):
         """targets / queries: lists of bytes.  Returns int32 [n,4]: subs, indels, aligned, status."""
@@ -463,14 +478,10 @@ class Context:
         self._check(lib().im_depth_enable(self.h))
 
     def depth_scan(self, tid, stream=None):
-        self._check(lib().im_depth_scan(self.h, tid, self.stream if stream is None else stream))
+        self._scan(lib().im_depth_scan, tid, stream)
 
     def depth_query_tid(self, tid, beg, end):
-        beg = np.ascontiguousarray(beg, dtype=np.int32)
-        end = np.ascontiguousarray(end, dtype=np.int32)
-        out = np.zeros(max(len(beg), 1), dtype=np.uint32)
-        self._check(lib().im_depth_query_tid(self.h, tid, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
-        return out[:len(beg)]
+        return self._query_tid(lib().im_depth_query_tid, tid, beg, end)
 
     def span_enable(self, flank, min_mapq):
         """the genome-wide array of reference-spanning read counts (the genotype columns), 4 bytes per reference base"""
@@ -481,30 +492,20 @@ class Context:
         self._check(lib().im_dev_span_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
 
     def span_scan(self, tid, stream=None):
-        self._check(lib().im_span_scan(self.h, tid, self.stream if stream is None else stream))
+        self._scan(lib().im_span_scan, tid, stream)
 
     def span_reset(self, tid, stream=None):
-        self._check(lib().im_span_reset(self.h, tid, self.stream if stream is None else stream))
+        self._reset(lib().im_span_reset, tid, stream)
 
     def span_query_tid(self, tid, beg, end):
         """per query the minimum of span[p] over [beg, end] inclusive"""
-        beg = np.ascontiguousarray(beg, dtype=np.int32)
-        end = np.ascontiguousarray(end, dtype=np.int32)
-        out = np.zeros(max(len(beg), 1), dtype=np.uint32)
-        self._check(lib().im_span_query_tid(self.h, tid, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
-        return out[:len(beg)]
+        return self._query_tid(lib().im_span_query_tid, tid, beg, end)
 
     def span_build(self, contig_len, run_start, run_len, flank):
-        run_start = np.ascontiguousarray(run_start, dtype=np.int32)
-        run_len = np.ascontiguousarray(run_len, dtype=np.int32)
-        self._check(lib().im_span_build(self.h, contig_len, len(run_start), _ptr(run_start), _ptr(run_len), int(flank)))
+        self._build(lib().im_span_build, contig_len, run_start, run_len, flank)
 
     def span_query(self, beg, end):
-        beg = np.ascontiguousarray(beg, dtype=np.int32)
-        end = np.ascontiguousarray(end, dtype=np.int32)
-        out = np.zeros(max(len(beg), 1), dtype=np.uint32)
-        self._check(lib().im_span_query(self.h, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
-        return out[:len(beg)]
+        return self._query(lib().im_span_query, beg, end)
 
     def pairspan_enable(self, flank, min_mapq):
         """a second genome-wide array: concordant pairs whose fragment spans a position (PAIRED_READ genotypes), 4 bytes per base"""
@@ -515,30 +516,20 @@ class Context:
         self._check(lib().im_dev_pairspan_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
 
     def pairspan_scan(self, tid, stream=None):
-        self._check(lib().im_pairspan_scan(self.h, tid, self.stream if stream is None else stream))
+        self._scan(lib().im_pairspan_scan, tid, stream)
 
     def pairspan_reset(self, tid, stream=None):
-        self._check(lib().im_pairspan_reset(self.h, tid, self.stream if stream is None else stream))
+        self._reset(lib().im_pairspan_reset, tid, stream)
 
     def pairspan_query_tid(self, tid, beg, end):
         """per query the minimum of pspan[p] over [beg, end] inclusive"""
-        beg = np.ascontiguousarray(beg, dtype=np.int32)
-        end = np.ascontiguousarray(end, dtype=np.int32)
-        out = np.zeros(max(len(beg), 1), dtype=np.uint32)
-        self._check(lib().im_pairspan_query_tid(self.h, tid, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
-        return out[:len(beg)]
+        return self._query_tid(lib().im_pairspan_query_tid, tid, beg, end)
 
     def pairspan_build(self, contig_len, frag_start, frag_len, flank):
-        frag_start = np.ascontiguousarray(frag_start, dtype=np.int32)
-        frag_len = np.ascontiguousarray(frag_len, dtype=np.int32)
-        self._check(lib().im_pairspan_build(self.h, contig_len, len(frag_start), _ptr(frag_start), _ptr(frag_len), int(flank)))
+        self._build(lib().im_pairspan_build, contig_len, frag_start, frag_len, flank)
 
     def pairspan_query(self, beg, end):
-        beg = np.ascontiguousarray(beg, dtype=np.int32)
-        end = np.ascontiguousarray(end, dtype=np.int32)
-        out = np.zeros(max(len(beg), 1), dtype=np.uint32)
-        self._check(lib().im_pairspan_query(self.h, len(beg), _ptr(beg), _ptr(end), _ptr(out)))
-        return out[:len(beg)]
+        return self._query(lib().im_pairspan_query, beg, end)
 
     def cluster_sr(self, cls, b1, b2, marker=2**31 - 1, tie_desc=0):
         n = len(cls)

@@ -22,6 +22,14 @@ struct ContigArray {
     int64_t cap = 0, len = -1;
 };
 
+// One genome-wide array of that layout (im_depth_enable, im_span_enable, im_pairspan_enable): one int32 per byte of ref_ascii and every contig's own run
+// of tile sums, allocated on that call only; flank and min_mapq are what its scatter counts by (the depth array has neither)
+struct GenomeArray {
+    int32_t* data = nullptr;
+    int32_t* sums = nullptr;
+    int32_t flank = 0, min_mapq = 0;
+};
+
 struct im_ctx {
     int device = -1;
     int n_cu = 0;
@@ -49,17 +57,8 @@ struct im_ctx {
     std::vector<int64_t> h_asc_off;
     std::vector<int32_t> h_len;
     int64_t ref_total = 0;
-    // genome-wide depth / difference array (im_depth_enable): one int32 per byte of ref_ascii
-    int32_t* gdepth = nullptr;
-    int32_t* gdepth_sums = nullptr;
-    // genome-wide reference-spanning counts (im_span_enable): the depth array's layout, allocated on that call only
-    int32_t* gspan = nullptr;
-    int32_t* gspan_sums = nullptr;
-    int32_t span_flank = 0, span_min_mapq = 0;
-    // genome-wide concordant-pair counts (im_pairspan_enable): a further array of that layout, allocated on that call only
-    int32_t* gpair = nullptr;
-    int32_t* gpair_sums = nullptr;
-    int32_t pair_flank = 0, pair_min_mapq = 0;
+    // genome-wide depth / difference array, reference-spanning counts and concordant-pair counts
+    GenomeArray all_depth, all_span, all_pair;
     bool support_count_attr = false;    // im_support_count: its kernel's LDS attribute has been set on this context's device
     std::mutex gb_mu;
     std::unordered_map<void*, int32_t> gb_layout;   // group-by scratch -> the slot count it was initialised (and is carved) for
@@ -138,15 +137,11 @@ void free_reference(im_ctx* ctx)
     if (ctx->d_len) (void)hipFree(ctx->d_len);
     ctx->ref_ascii = nullptr; ctx->ref_pk = nullptr; ctx->d_asc_off = nullptr; ctx->d_pk_off = nullptr; ctx->d_len = nullptr;
     ctx->n_contigs = 0;
-    if (ctx->gdepth) (void)hipFree(ctx->gdepth);
-    if (ctx->gdepth_sums) (void)hipFree(ctx->gdepth_sums);
-    ctx->gdepth = nullptr; ctx->gdepth_sums = nullptr;
-    if (ctx->gspan) (void)hipFree(ctx->gspan);
-    if (ctx->gspan_sums) (void)hipFree(ctx->gspan_sums);
-    ctx->gspan = nullptr; ctx->gspan_sums = nullptr;
-    if (ctx->gpair) (void)hipFree(ctx->gpair);
-    if (ctx->gpair_sums) (void)hipFree(ctx->gpair_sums);
-    ctx->gpair = nullptr; ctx->gpair_sums = nullptr;
+    for (GenomeArray* g : {&ctx->all_depth, &ctx->all_span, &ctx->all_pair}) {
+        if (g->data) (void)hipFree(g->data);
+        if (g->sums) (void)hipFree(g->sums);
+        g->data = nullptr; g->sums = nullptr;
+    }
     ctx->h_asc_off.clear(); ctx->h_len.clear(); ctx->ref_total = 0;
 }
 
@@ -157,10 +152,17 @@ void free_array(ContigArray& a)
     a = ContigArray();
 }
 
-// im_depth_build / im_span_build / im_pairspan_build behind their argument checks: grow, stage the intervals, memset + scatter + scan (one launcher,
-// im_depth.hip), wait
-int build_array(im_ctx* ctx, ContigArray& a, int64_t clen, int32_t n, const int32_t* start, const int32_t* len, int32_t lo, int32_t hi)
+// The helpers below serve one member of either family each; `family` ("im_depth", "im_span", "im_pairspan") names it in the messages, and
+// flank is null for the depth arrays, which count whole intervals.
+
+// im_depth_build / im_span_build / im_pairspan_build: check, grow, stage the intervals, memset + scatter + scan (one launcher, im_depth.hip), wait
+int build_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* family, int64_t clen, int32_t n, const int32_t* start, const int32_t* len,
+                const int32_t* flank)
 {
+    if (!ctx || clen < 0 || clen > 0x7fffff00LL || n < 0 || (n > 0 && (!start || !len))) return IM_E_ARG;
+    if (flank && *flank < 1) { set_err(ctx, "%s_build: flank %d, must be >= 1", family, *flank); return IM_E_ARG; }
+    const int32_t lo = flank ? *flank : 0, hi = flank ? *flank - 1 : 0;
+    ContigArray& a = ctx->*which;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     a.len = -1;
     if (clen + 1 > a.cap) {
@@ -208,21 +210,80 @@ int query_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, 
     return IM_OK;
 }
 
-// im_depth_enable / im_span_enable / im_pairspan_enable: a genome-wide array (one int32 per byte of ref_ascii) and its sums, zeroed.  Each contig has
-// its own run of sums (scans of different contigs may be in flight on different streams), at the same place in both arrays
-int enable_genome_array(im_ctx* ctx, int32_t** data, int32_t** sums)
+// im_depth_query / im_span_query / im_pairspan_query
+int query_contig_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* family, int32_t n, const int32_t* beg, const int32_t* end, bool minimum,
+                       uint32_t* out)
 {
+    if (!ctx || n < 0) return IM_E_ARG;
+    const ContigArray& a = ctx->*which;
+    if (a.len < 0) { set_err(ctx, "%s_build has not been called", family); return IM_E_ARG; }
+    if (n == 0) return IM_OK;
+    if (!beg || !end || !out) return IM_E_ARG;
+    return query_array(ctx, n, beg, end, a.data, a.sums, a.len, minimum, out, nullptr);
+}
+
+// im_depth_enable / im_span_enable / im_pairspan_enable: a genome-wide array and its sums, zeroed.  Each contig has its own run of sums (scans of
+// different contigs may be in flight on different streams), at the same place in every array
+int enable_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, const char* family, const int32_t* flank, int32_t min_mapq)
+{
+    if (!ctx) return IM_E_ARG;
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    if (flank && *flank < 1) { set_err(ctx, "%s_enable: flank %d, must be >= 1", family, *flank); return IM_E_ARG; }
+    GenomeArray& g = ctx->*which;
+    if (g.data) {
+        if (flank && (*flank != g.flank || min_mapq != g.min_mapq)) { set_err(ctx, "%s_enable: already enabled with flank %d, min_mapq %d", family, g.flank, g.min_mapq); return IM_E_ARG; }
+        return IM_OK;
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int64_t ints = 0;
     std::vector<int64_t> sums_off;
     for (int32_t l : ctx->h_len) { sums_off.push_back(ints); ints += im::depth_sums_ints(l); }
     ctx->h_sums_off = sums_off;
-    HIP_TRY(ctx, hipMalloc((void**)data, (size_t)ctx->ref_total * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMalloc((void**)sums, (size_t)(ints + 1) * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMemsetAsync(*data, 0, (size_t)ctx->ref_total * sizeof(int32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(*sums, 0, (size_t)(ints + 1) * sizeof(int32_t), ctx->stream));      // the arrival counters start at zero
+    HIP_TRY(ctx, hipMalloc((void**)&g.data, (size_t)ctx->ref_total * sizeof(int32_t)));
+    HIP_TRY(ctx, hipMalloc((void**)&g.sums, (size_t)(ints + 1) * sizeof(int32_t)));
+    HIP_TRY(ctx, hipMemsetAsync(g.data, 0, (size_t)ctx->ref_total * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(g.sums, 0, (size_t)(ints + 1) * sizeof(int32_t), ctx->stream));      // the arrival counters start at zero
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (flank) { g.flank = *flank; g.min_mapq = min_mapq; }
     return IM_OK;
+}
+
+// im_depth_scan / im_span_scan / im_pairspan_scan: one launch, tile-local sums + exclusive tile offsets (the queries add them)
+int scan_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, void* stream)
+{
+    if (!ctx || !(ctx->*which).data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    const GenomeArray& g = ctx->*which;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, im::launch_depth_scan_tiled(g.data + ctx->h_asc_off[tid], (int64_t)ctx->h_len[tid] + 1, g.sums + ctx->h_sums_off[tid], (hipStream_t)stream));
+    return IM_OK;
+}
+
+// im_depth_reset / im_span_reset / im_pairspan_reset
+int reset_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, void* stream)
+{
+    if (!ctx || !(ctx->*which).data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemsetAsync((ctx->*which).data + ctx->h_asc_off[tid], 0, ((size_t)ctx->h_len[tid] + 1) * sizeof(int32_t), (hipStream_t)stream));
+    return IM_OK;
+}
+
+// im_depth_query_max_tid / im_span_query_tid / im_pairspan_query_tid
+int query_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, bool minimum,
+                       uint32_t* out, uint32_t* max_out)
+{
+    if (!ctx || n < 0 || !(ctx->*which).data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    if (n == 0) return IM_OK;
+    if (!beg || !end || !out) return IM_E_ARG;
+    const GenomeArray& g = ctx->*which;
+    return query_array(ctx, n, beg, end, g.data + ctx->h_asc_off[tid], g.sums + ctx->h_sums_off[tid], ctx->h_len[tid], minimum, out, max_out);
+}
+
+im::RefDev ref_dev(const im_ctx* ctx)
+{
+    im::RefDev ref;
+    ref.ascii = ctx->ref_ascii; ref.pk = reinterpret_cast<const uint8_t*>(ctx->ref_pk);
+    ref.asc_off = ctx->d_asc_off; ref.pk_off = ctx->d_pk_off; ref.len = ctx->d_len; ref.n_contigs = ctx->n_contigs;
+    return ref;
 }
 
 }  // namespace
@@ -393,9 +454,7 @@ static int dev_realign(im_ctx* ctx, const im_params* params, const im_dev_batch*
     if (batch->n < 0) { set_err(ctx, "negative batch size"); return IM_E_ARG; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     im::RealignArgs a;
-    a.ref.ascii = ctx->ref_ascii; a.ref.pk = reinterpret_cast<const uint8_t*>(ctx->ref_pk);
-    a.ref.asc_off = ctx->d_asc_off; a.ref.pk_off = ctx->d_pk_off; a.ref.len = ctx->d_len;
-    a.ref.n_contigs = ctx->n_contigs;
+    a.ref = ref_dev(ctx);
     a.batch = *batch;
     a.P = *params;
     a.keep_slots = keep;
@@ -497,12 +556,9 @@ int im_dev_triage(im_ctx* ctx, const im_triage_params* tp, const im_dev_records*
     if (!ctx->rg_blob) { set_err(ctx, "im_set_insert_ranges has not been called"); return IM_E_ARG; }
     if (recs->n < 0 || !out->counters || !out->cand_rec) { set_err(ctx, "bad triage arguments"); return IM_E_ARG; }
     if (scratch_bytes < im::triage_scratch_bytes(recs->n)) { set_err(ctx, "triage scratch too small"); return IM_E_ARG; }
-    if (tp->want_depth && !ctx->gdepth) { set_err(ctx, "want_depth without im_depth_enable"); return IM_E_ARG; }
+    if (tp->want_depth && !ctx->all_depth.data) { set_err(ctx, "want_depth without im_depth_enable"); return IM_E_ARG; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    im::RefDev ref;
-    ref.ascii = ctx->ref_ascii; ref.pk = reinterpret_cast<const uint8_t*>(ctx->ref_pk);
-    ref.asc_off = ctx->d_asc_off; ref.pk_off = ctx->d_pk_off; ref.len = ctx->d_len; ref.n_contigs = ctx->n_contigs;
-    HIP_TRY(ctx, im::launch_triage(ref, ctx->rg, ctx->gdepth, *tp, *recs, *out, scratch, (hipStream_t)stream));
+    HIP_TRY(ctx, im::launch_triage(ref_dev(ctx), ctx->rg, ctx->all_depth.data, *tp, *recs, *out, scratch, (hipStream_t)stream));
     return IM_OK;
 }
 
@@ -626,57 +682,30 @@ int im_dev_cluster_groupby_n(im_ctx* ctx, int32_t n_slots_cap, const int32_t* n_
 
 // ---- seam 3, genome-wide form ------------------------------------------------------------------
 
-int im_depth_enable(im_ctx* ctx)
-{
-    if (!ctx) return IM_E_ARG;
-    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
-    if (ctx->gdepth) return IM_OK;
-    return enable_genome_array(ctx, &ctx->gdepth, &ctx->gdepth_sums);
-}
-
-int im_depth_scan(im_ctx* ctx, int32_t tid, void* stream)
-{
-    if (!ctx || !ctx->gdepth || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // one launch: tile-local depths + exclusive tile offsets (im_depth_query_tid adds them)
-    HIP_TRY(ctx, im::launch_depth_scan_tiled(ctx->gdepth + ctx->h_asc_off[tid], (int64_t)ctx->h_len[tid] + 1, ctx->gdepth_sums + ctx->h_sums_off[tid], (hipStream_t)stream));
-    return IM_OK;
-}
-
-int im_depth_reset(im_ctx* ctx, int32_t tid, void* stream)
-{
-    if (!ctx || !ctx->gdepth || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->gdepth + ctx->h_asc_off[tid], 0, ((size_t)ctx->h_len[tid] + 1) * sizeof(int32_t), (hipStream_t)stream));
-    return IM_OK;
-}
+int im_depth_enable(im_ctx* ctx) { return enable_genome_array(ctx, &im_ctx::all_depth, "im_depth", nullptr, 0); }
+int im_depth_scan(im_ctx* ctx, int32_t tid, void* stream) { return scan_genome_array(ctx, &im_ctx::all_depth, tid, stream); }
+int im_depth_reset(im_ctx* ctx, int32_t tid, void* stream) { return reset_genome_array(ctx, &im_ctx::all_depth, tid, stream); }
 
 int im_depth_allreduce(im_ctx* ctx, im_comm* comm)
 {
     if (!ctx || !comm) return IM_E_ARG;
-    if (!ctx->gdepth) { set_err(ctx, "im_depth_enable has not been called"); return IM_E_ARG; }
+    if (!ctx->all_depth.data) { set_err(ctx, "im_depth_enable has not been called"); return IM_E_ARG; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const size_t total = (size_t)ctx->ref_total, step = (size_t)1 << 28;           // 1 GiB of int32 per call
     for (size_t at = 0; at < total; at += step) {
         const size_t n = total - at < step ? total - at : step;
-        if (im_comm_allreduce_sum_i32(comm, ctx->gdepth + at, n, ctx->stream) != IM_OK) { set_err(ctx, "%s", im_comm_last_error()); return IM_E_HIP; }
+        if (im_comm_allreduce_sum_i32(comm, ctx->all_depth.data + at, n, ctx->stream) != IM_OK) { set_err(ctx, "%s", im_comm_last_error()); return IM_E_HIP; }
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return IM_OK;
 }
 
 int im_depth_query_max_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out, uint32_t* max_out)
-{
-    if (!ctx || n < 0 || !ctx->gdepth || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    if (n == 0) return IM_OK;
-    return query_array(ctx, n, beg, end, ctx->gdepth + ctx->h_asc_off[tid], ctx->gdepth_sums + ctx->h_sums_off[tid], ctx->h_len[tid], false, sum_out, max_out);
-}
+{ return query_genome_array(ctx, &im_ctx::all_depth, tid, n, beg, end, false, sum_out, max_out); }
 
 int im_depth_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out)
-{
-    return im_depth_query_max_tid(ctx, tid, n, beg, end, sum_out, nullptr);
-}
+{ return im_depth_query_max_tid(ctx, tid, n, beg, end, sum_out, nullptr); }
 
 // Host-buffer entry point.  The batch is cut into chunks that travel through a two-slot pipeline: chunk c is
 // packed into PINNED staging memory and copied in on one copy stream while chunk c-1 runs on the compute stream
@@ -793,159 +822,65 @@ int im_realign_batch(im_ctx* ctx, const im_params* params, const im_read_batch* 
 }
 
 int im_depth_build(im_ctx* ctx, int64_t contig_len, int32_t n_seg, const int32_t* seg_start, const int32_t* seg_len)
-{
-    if (!ctx || contig_len < 0 || n_seg < 0) return IM_E_ARG;
-    return build_array(ctx, ctx->depth, contig_len, n_seg, seg_start, seg_len, 0, 0);
-}
+{ return build_array(ctx, &im_ctx::depth, "im_depth", contig_len, n_seg, seg_start, seg_len, nullptr); }
 
 int im_depth_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out)
-{
-    if (!ctx || n < 0) return IM_E_ARG;
-    if (ctx->depth.len < 0) { set_err(ctx, "im_depth_build has not been called"); return IM_E_ARG; }
-    if (n == 0) return IM_OK;
-    return query_array(ctx, n, beg, end, ctx->depth.data, ctx->depth.sums, ctx->depth.len, false, sum_out, nullptr);
-}
+{ return query_contig_array(ctx, &im_ctx::depth, "im_depth", n, beg, end, false, sum_out); }
 
 // ---- reference-spanning read counts (the genotype columns) ------------------------------------
 
-int im_span_enable(im_ctx* ctx, int32_t flank, int32_t min_mapq)
-{
-    if (!ctx) return IM_E_ARG;
-    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
-    if (flank < 1) { set_err(ctx, "im_span_enable: flank %d, must be >= 1", flank); return IM_E_ARG; }
-    if (ctx->gspan) {
-        if (flank != ctx->span_flank || min_mapq != ctx->span_min_mapq) { set_err(ctx, "im_span_enable: already enabled with flank %d, min_mapq %d", ctx->span_flank, ctx->span_min_mapq); return IM_E_ARG; }
-        return IM_OK;
-    }
-    int rc = enable_genome_array(ctx, &ctx->gspan, &ctx->gspan_sums);
-    if (rc) return rc;
-    ctx->span_flank = flank; ctx->span_min_mapq = min_mapq;
-    return IM_OK;
-}
+int im_span_enable(im_ctx* ctx, int32_t flank, int32_t min_mapq) { return enable_genome_array(ctx, &im_ctx::all_span, "im_span", &flank, min_mapq); }
 
 int im_dev_span_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
 {
     if (!ctx || !recs) return IM_E_ARG;
-    if (!ctx->gspan) { set_err(ctx, "im_span_enable has not been called"); return IM_E_ARG; }
+    const GenomeArray& g = ctx->all_span;
+    if (!g.data) { set_err(ctx, "im_span_enable has not been called"); return IM_E_ARG; }
     if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    im::RefDev ref;
-    ref.ascii = ctx->ref_ascii; ref.pk = reinterpret_cast<const uint8_t*>(ctx->ref_pk);
-    ref.asc_off = ctx->d_asc_off; ref.pk_off = ctx->d_pk_off; ref.len = ctx->d_len; ref.n_contigs = ctx->n_contigs;
-    HIP_TRY(ctx, im::launch_span_scatter(ref, ctx->span_flank, ctx->span_min_mapq, *recs, ctx->gspan, (hipStream_t)stream));
+    HIP_TRY(ctx, im::launch_span_scatter(ref_dev(ctx), g.flank, g.min_mapq, *recs, g.data, (hipStream_t)stream));
     return IM_OK;
 }
 
-int im_span_scan(im_ctx* ctx, int32_t tid, void* stream)
-{
-    if (!ctx || !ctx->gspan || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_depth_scan_tiled(ctx->gspan + ctx->h_asc_off[tid], (int64_t)ctx->h_len[tid] + 1, ctx->gspan_sums + ctx->h_sums_off[tid], (hipStream_t)stream));
-    return IM_OK;
-}
-
-int im_span_reset(im_ctx* ctx, int32_t tid, void* stream)
-{
-    if (!ctx || !ctx->gspan || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->gspan + ctx->h_asc_off[tid], 0, ((size_t)ctx->h_len[tid] + 1) * sizeof(int32_t), (hipStream_t)stream));
-    return IM_OK;
-}
+int im_span_scan(im_ctx* ctx, int32_t tid, void* stream) { return scan_genome_array(ctx, &im_ctx::all_span, tid, stream); }
+int im_span_reset(im_ctx* ctx, int32_t tid, void* stream) { return reset_genome_array(ctx, &im_ctx::all_span, tid, stream); }
 
 int im_span_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
-{
-    if (!ctx || n < 0 || !ctx->gspan || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    if (n == 0) return IM_OK;
-    if (!beg || !end || !min_out) return IM_E_ARG;
-    return query_array(ctx, n, beg, end, ctx->gspan + ctx->h_asc_off[tid], ctx->gspan_sums + ctx->h_sums_off[tid], ctx->h_len[tid], true, min_out, nullptr);
-}
+{ return query_genome_array(ctx, &im_ctx::all_span, tid, n, beg, end, true, min_out, nullptr); }
 
 int im_span_build(im_ctx* ctx, int64_t contig_len, int32_t n_run, const int32_t* run_start, const int32_t* run_len, int32_t flank)
-{
-    if (!ctx || contig_len < 0 || contig_len > 0x7fffff00LL || n_run < 0 || (n_run > 0 && (!run_start || !run_len))) return IM_E_ARG;
-    if (flank < 1) { set_err(ctx, "im_span_build: flank %d, must be >= 1", flank); return IM_E_ARG; }
-    return build_array(ctx, ctx->span, contig_len, n_run, run_start, run_len, flank, flank - 1);
-}
+{ return build_array(ctx, &im_ctx::span, "im_span", contig_len, n_run, run_start, run_len, &flank); }
 
 int im_span_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
-{
-    if (!ctx || n < 0) return IM_E_ARG;
-    if (ctx->span.len < 0) { set_err(ctx, "im_span_build has not been called"); return IM_E_ARG; }
-    if (n == 0) return IM_OK;
-    if (!beg || !end || !min_out) return IM_E_ARG;
-    return query_array(ctx, n, beg, end, ctx->span.data, ctx->span.sums, ctx->span.len, true, min_out, nullptr);
-}
+{ return query_contig_array(ctx, &im_ctx::span, "im_span", n, beg, end, true, min_out); }
 
 // ---- concordant-pair counts (the genotype columns of PAIRED_READ records) ----------------------
 
-int im_pairspan_enable(im_ctx* ctx, int32_t flank, int32_t min_mapq)
-{
-    if (!ctx) return IM_E_ARG;
-    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
-    if (flank < 1) { set_err(ctx, "im_pairspan_enable: flank %d, must be >= 1", flank); return IM_E_ARG; }
-    if (ctx->gpair) {
-        if (flank != ctx->pair_flank || min_mapq != ctx->pair_min_mapq) { set_err(ctx, "im_pairspan_enable: already enabled with flank %d, min_mapq %d", ctx->pair_flank, ctx->pair_min_mapq); return IM_E_ARG; }
-        return IM_OK;
-    }
-    int rc = enable_genome_array(ctx, &ctx->gpair, &ctx->gpair_sums);
-    if (rc) return rc;
-    ctx->pair_flank = flank; ctx->pair_min_mapq = min_mapq;
-    return IM_OK;
-}
+int im_pairspan_enable(im_ctx* ctx, int32_t flank, int32_t min_mapq) { return enable_genome_array(ctx, &im_ctx::all_pair, "im_pairspan", &flank, min_mapq); }
 
 int im_dev_pairspan_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
 {
     if (!ctx || !recs) return IM_E_ARG;
-    if (!ctx->gpair) { set_err(ctx, "im_pairspan_enable has not been called"); return IM_E_ARG; }
+    const GenomeArray& g = ctx->all_pair;
+    if (!g.data) { set_err(ctx, "im_pairspan_enable has not been called"); return IM_E_ARG; }
     if (!ctx->rg_blob) { set_err(ctx, "im_set_insert_ranges has not been called"); return IM_E_ARG; }
     if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    im::RefDev ref;
-    ref.ascii = ctx->ref_ascii; ref.pk = reinterpret_cast<const uint8_t*>(ctx->ref_pk);
-    ref.asc_off = ctx->d_asc_off; ref.pk_off = ctx->d_pk_off; ref.len = ctx->d_len; ref.n_contigs = ctx->n_contigs;
-    HIP_TRY(ctx, im::launch_pair_scatter(ref, ctx->rg, ctx->pair_flank, ctx->pair_min_mapq, *recs, ctx->gpair, (hipStream_t)stream));
+    HIP_TRY(ctx, im::launch_pair_scatter(ref_dev(ctx), ctx->rg, g.flank, g.min_mapq, *recs, g.data, (hipStream_t)stream));
     return IM_OK;
 }
 
-int im_pairspan_scan(im_ctx* ctx, int32_t tid, void* stream)
-{
-    if (!ctx || !ctx->gpair || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_depth_scan_tiled(ctx->gpair + ctx->h_asc_off[tid], (int64_t)ctx->h_len[tid] + 1, ctx->gpair_sums + ctx->h_sums_off[tid], (hipStream_t)stream));
-    return IM_OK;
-}
-
-int im_pairspan_reset(im_ctx* ctx, int32_t tid, void* stream)
-{
-    if (!ctx || !ctx->gpair || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->gpair + ctx->h_asc_off[tid], 0, ((size_t)ctx->h_len[tid] + 1) * sizeof(int32_t), (hipStream_t)stream));
-    return IM_OK;
-}
+int im_pairspan_scan(im_ctx* ctx, int32_t tid, void* stream) { return scan_genome_array(ctx, &im_ctx::all_pair, tid, stream); }
+int im_pairspan_reset(im_ctx* ctx, int32_t tid, void* stream) { return reset_genome_array(ctx, &im_ctx::all_pair, tid, stream); }
 
 int im_pairspan_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
-{
-    if (!ctx || n < 0 || !ctx->gpair || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    if (n == 0) return IM_OK;
-    if (!beg || !end || !min_out) return IM_E_ARG;
-    return query_array(ctx, n, beg, end, ctx->gpair + ctx->h_asc_off[tid], ctx->gpair_sums + ctx->h_sums_off[tid], ctx->h_len[tid], true, min_out, nullptr);
-}
+{ return query_genome_array(ctx, &im_ctx::all_pair, tid, n, beg, end, true, min_out, nullptr); }
 
 int im_pairspan_build(im_ctx* ctx, int64_t contig_len, int32_t n_frag, const int32_t* frag_start, const int32_t* frag_len, int32_t flank)
-{
-    if (!ctx || contig_len < 0 || contig_len > 0x7fffff00LL || n_frag < 0 || (n_frag > 0 && (!frag_start || !frag_len))) return IM_E_ARG;
-    if (flank < 1) { set_err(ctx, "im_pairspan_build: flank %d, must be >= 1", flank); return IM_E_ARG; }
-    return build_array(ctx, ctx->pair, contig_len, n_frag, frag_start, frag_len, flank, flank - 1);
-}
+{ return build_array(ctx, &im_ctx::pair, "im_pairspan", contig_len, n_frag, frag_start, frag_len, &flank); }
 
 int im_pairspan_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
-{
-    if (!ctx || n < 0) return IM_E_ARG;
-    if (ctx->pair.len < 0) { set_err(ctx, "im_pairspan_build has not been called"); return IM_E_ARG; }
-    if (n == 0) return IM_OK;
-    if (!beg || !end || !min_out) return IM_E_ARG;
-    return query_array(ctx, n, beg, end, ctx->pair.data, ctx->pair.sums, ctx->pair.len, true, min_out, nullptr);
-}
+{ return query_contig_array(ctx, &im_ctx::pair, "im_pairspan", n, beg, end, true, min_out); }
 
 int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64_t* t_off,
                      const uint8_t* queries, const int64_t* q_off, int32_t* out)
@@ -1052,10 +987,7 @@ int im_support_count(im_ctx* ctx, int32_t n_variants, const im_known_variant* va
         HIP_TRY(ctx, hipMemcpyAsync(d_bi, big_idx.data(), sizeof(int32_t) * (size_t)n_big, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(d_bo, big_toff.data(), sizeof(int64_t) * (size_t)(n_big + 1), hipMemcpyHostToDevice, st));
     }
-    im::RefDev ref;
-    ref.ascii = ctx->ref_ascii; ref.pk = reinterpret_cast<const uint8_t*>(ctx->ref_pk);
-    ref.asc_off = ctx->d_asc_off; ref.pk_off = ctx->d_pk_off; ref.len = ctx->d_len; ref.n_contigs = ctx->n_contigs;
-    HIP_TRY(ctx, im::launch_support_count(n_tasks, d_k, d_v, d_a, ref, d_q, d_c, max_short, n_big, d_bi, d_bo, d_bw, max_big_t, d_rows, big_grid,
+    HIP_TRY(ctx, im::launch_support_count(n_tasks, d_k, d_v, d_a, ref_dev(ctx), d_q, d_c, max_short, n_big, d_bi, d_bo, d_bw, max_big_t, d_rows, big_grid,
                                           &ctx->support_count_attr, st));
     HIP_TRY(ctx, hipMemcpyAsync(counts, d_c, sizeof(int32_t) * 3 * (size_t)n_variants, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));      // the one synchronisation: big_idx / big_toff are read by then too

@@ -70,12 +70,14 @@ __device__ __forceinline__ uint32_t span_cigar_word(const SpanRec& r, uint32_t k
     return k == 0u ? r.cig[0] : k == 1u ? r.cig[1] : k == 2u ? r.cig[2] : k == 3u ? r.cig[3] : ld_u32(r.p + r.o_cigar + 4u * k);
 }
 
-struct SpanArgs {
+// what both scatter kernels take
+struct ScatterArgs {
     im_dev_records recs;
     const int64_t* asc_off;     // [n_contigs] start of a contig's run in the array
     const int32_t* len;         // [n_contigs]
     int32_t n_contigs;
     int32_t flank, min_mapq;
+    RgTable rg;                 // read group -> range[1] (im_set_insert_ranges); the pair kernel only
     int32_t* diff;              // the genome-wide difference array
 };
 
@@ -131,7 +133,7 @@ __device__ __forceinline__ void win_out(const SpanWin& W, int32_t* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(kSpanBlock) void span_scatter_kernel(SpanArgs A)
+__global__ __launch_bounds__(kSpanBlock) void span_scatter_kernel(ScatterArgs A)
 {
     __shared__ int32_t s_win[kSpanWin];
     __shared__ int32_t s_wpos[kSpanBlock / 64], s_wtid[kSpanBlock / 64];
@@ -180,17 +182,7 @@ __global__ __launch_bounds__(kSpanBlock) void span_scatter_kernel(SpanArgs A)
     win_out(W, A.diff, A.asc_off, A.len, t);
 }
 
-struct PairArgs {
-    im_dev_records recs;
-    const int64_t* asc_off;     // [n_contigs] start of a contig's run in the array
-    const int32_t* len;         // [n_contigs]
-    int32_t n_contigs;
-    int32_t flank, min_mapq;
-    RgTable rg;                 // read group -> range[1] (im_set_insert_ranges)
-    int32_t* diff;              // the genome-wide difference array of the pair counts
-};
-
-__global__ __launch_bounds__(kSpanBlock) void pair_scatter_kernel(PairArgs A)
+__global__ __launch_bounds__(kSpanBlock) void pair_scatter_kernel(ScatterArgs A)
 {
     // A fragment's closing event lies up to range_max behind its opening one: with inserts of a few hundred bases most of them
     // still fall into the window, and the rest are the plain device atomics the window is there to thin out, not a corner case.
@@ -271,28 +263,28 @@ __global__ __launch_bounds__(256) void span_query_kernel(int32_t nq, const int32
     }
 }
 
+hipError_t launch_scatter(void (*kernel)(ScatterArgs), const RefDev& ref, const RgTable& rg, int32_t flank, int32_t min_mapq, const im_dev_records& recs,
+                          int32_t* diff, hipStream_t stream)
+{
+    if (recs.n <= 0) return hipSuccess;
+    ScatterArgs A;
+    A.recs = recs; A.asc_off = ref.asc_off; A.len = ref.len; A.n_contigs = ref.n_contigs;
+    A.flank = flank; A.min_mapq = min_mapq; A.rg = rg; A.diff = diff;
+    const int blocks = (recs.n + kSpanBlock - 1) / kSpanBlock;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kSpanBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_span_scatter(const RefDev& ref, int32_t flank, int32_t min_mapq, const im_dev_records& recs, int32_t* diff, hipStream_t stream)
 {
-    if (recs.n <= 0) return hipSuccess;
-    SpanArgs A;
-    A.recs = recs; A.asc_off = ref.asc_off; A.len = ref.len; A.n_contigs = ref.n_contigs;
-    A.flank = flank; A.min_mapq = min_mapq; A.diff = diff;
-    const int blocks = (recs.n + kSpanBlock - 1) / kSpanBlock;
-    hipLaunchKernelGGL(span_scatter_kernel, dim3(blocks), dim3(kSpanBlock), 0, stream, A);
-    return hipGetLastError();
+    return launch_scatter(span_scatter_kernel, ref, RgTable{nullptr, 0, 0}, flank, min_mapq, recs, diff, stream);
 }
 
 hipError_t launch_pair_scatter(const RefDev& ref, const RgTable& rg, int32_t flank, int32_t min_mapq, const im_dev_records& recs, int32_t* diff, hipStream_t stream)
 {
-    if (recs.n <= 0) return hipSuccess;
-    PairArgs A;
-    A.recs = recs; A.asc_off = ref.asc_off; A.len = ref.len; A.n_contigs = ref.n_contigs;
-    A.flank = flank; A.min_mapq = min_mapq; A.rg = rg; A.diff = diff;
-    const int blocks = (recs.n + kSpanBlock - 1) / kSpanBlock;
-    hipLaunchKernelGGL(pair_scatter_kernel, dim3(blocks), dim3(kSpanBlock), 0, stream, A);
-    return hipGetLastError();
+    return launch_scatter(pair_scatter_kernel, ref, rg, flank, min_mapq, recs, diff, stream);
 }
 
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,

@@ -303,6 +303,8 @@ typedef struct {
     char** qname; char* strand; uint8_t* qual;
 } cand_batch;
 
+/* intervals of one contig, for a device array of the record-at-a-time path */
+typedef struct { int32_t *start, *len; int64_t n, cap; } ivlist;
 typedef struct {
     im_ctx* gpu;
     bam_header* hdr;
@@ -324,13 +326,10 @@ typedef struct {
     cand_batch cb;
     evidence_t** pending; int64_t n_pending, cap_pending;
     int64_t arrival;
-    /* match segments of the contig's pileup-eligible records, for the device depth array */
-    int32_t *seg_start, *seg_len; int64_t n_seg, cap_seg;
+    /* record-at-a-time path: the match segments of the contig's pileup-eligible records (im_depth_build); -G: the M/=/X runs of its
+     * eligible records (im_span_build); -P: the fragments of its concordant left mates (im_pairspan_build) */
+    ivlist segs, runs, frags;
     int depth_tid;              /* contig whose depth array is resident on the device, -1 = none */
-    /* -G, record-at-a-time path: the M/=/X runs of the contig's eligible records, for the device span array (im_span_build) */
-    int32_t *run_start, *run_len; int64_t n_run, cap_run;
-    /* -P, record-at-a-time path: the fragments of the contig's concordant left mates, for the device pair-span array (im_pairspan_build) */
-    int32_t *frag_start, *frag_len; int64_t n_frag, cap_frag;
     int pipe_mode;              /* device pipeline: depth queries go to the genome-wide array */
     int marker_floor;           /* multi-GPU: smallest start of a stale pair-table entry of an earlier contig on another rank */
     /* live entries of the pair table (find_marker walks these) */
@@ -950,6 +949,12 @@ static void genotype_of(int64_t rs, int64_t ns, int* best_out, int* gq_out)
     if (gq > 99) gq = 99;
     *best_out = best; *gq_out = (int)gq;
 }
+static void print_gt_ad_gq(int64_t ref_count, int64_t alt_count)
+{
+    int best, gq;
+    genotype_of(ref_count, alt_count, &best, &gq);
+    printf("\tGT:AD:GQ\t%s:%lld,%lld:%d", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", (long long)ref_count, (long long)alt_count, gq);
+}
 static void print_genotype(const variant_t* v)
 {
     /* a PAIRED_READ record has no precise breakpoint to count spanning reads at; with -P its rs_cached is RP, the thinnest depth
@@ -958,9 +963,18 @@ static void print_genotype(const variant_t* v)
         printf("\tGT:AD:GQ\t./.:.,%u:.", v->support);
         return;
     }
-    int best, gq;
-    genotype_of((int64_t)v->rs_cached, (int64_t)v->support, &best, &gq);
-    printf("\tGT:AD:GQ\t%s:%u,%u:%d", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", v->rs_cached, v->support, gq);
+    print_gt_ad_gq((int64_t)v->rs_cached, (int64_t)v->support);
+}
+
+/* the span (pair: 0) or pair-span (pair: 1) minima over m > 0 intervals of one contig, as one query */
+static void query_minima(driver* d, int pair, int32_t tid, int m, const int32_t* beg, const int32_t* end, uint32_t* out)
+{
+    gpu_wait(d);
+    pthread_mutex_lock(&g_query_mu);
+    const int qrc = pair ? (d->pipe_mode ? im_pairspan_query_tid(d->gpu, tid, m, beg, end, out) : im_pairspan_query(d->gpu, m, beg, end, out))
+                         : (d->pipe_mode ? im_span_query_tid(d->gpu, tid, m, beg, end, out) : im_span_query(d->gpu, m, beg, end, out));
+    pthread_mutex_unlock(&g_query_mu);
+    if (qrc != IM_OK) fatalf("%s: %s", pair ? "im_pairspan_query" : "im_span_query", im_last_error(d->gpu));
 }
 
 /* print_vcf_output (src/variant.c:115-311) */
@@ -1280,12 +1294,7 @@ static void print_variants(driver* d, variant_list* vs)
             beg[m] = pos; end[m] = pos + (bp_end - endpos); who[m] = i; m++;
         }
         if (m > 0) {
-            gpu_wait(d);
-            pthread_mutex_lock(&g_query_mu);
-            /* all printed variants of a flush lie on one contig */
-            const int qrc = d->pipe_mode ? im_span_query_tid(d->gpu, out.v[who[0]]->tid, m, beg, end, rs) : im_span_query(d->gpu, m, beg, end, rs);
-            pthread_mutex_unlock(&g_query_mu);
-            if (qrc != IM_OK) fatalf("im_span_query: %s", im_last_error(d->gpu));
+            query_minima(d, 0, out.v[who[0]]->tid, m, beg, end, rs);       /* all printed variants of a flush lie on one contig */
             for (int q = 0; q < m; q++) { out.v[who[q]]->rs_cached = rs[q]; out.v[who[q]]->rs_valid = 1; }
         }
         /* ... -P: the PAIRED_READ ones from the pair-span array, over everything between their two breakpoints */
@@ -1298,11 +1307,7 @@ static void print_variants(driver* d, variant_list* vs)
                 vcf_coordinates(v, &pos, &endpos, &bp_end);
                 beg[m] = pos; end[m] = bp_end > endpos ? bp_end : endpos; who[m] = i; m++;
             }
-            gpu_wait(d);
-            pthread_mutex_lock(&g_query_mu);
-            const int qrc = d->pipe_mode ? im_pairspan_query_tid(d->gpu, out.v[who[0]]->tid, m, beg, end, rs) : im_pairspan_query(d->gpu, m, beg, end, rs);
-            pthread_mutex_unlock(&g_query_mu);
-            if (qrc != IM_OK) fatalf("im_pairspan_query: %s", im_last_error(d->gpu));
+            query_minima(d, 1, out.v[who[0]]->tid, m, beg, end, rs);
             for (int q = 0; q < m; q++) { out.v[who[q]]->rs_cached = rs[q]; out.v[who[q]]->rs_valid = 1; }
         }
         free(beg); free(end); free(rs); free(who);
@@ -1874,9 +1879,7 @@ static void print_known_genotype(const knownvariant_t* k)
         /* -P: RP = the thinnest depth of concordant fragments over [POS, max(END, BP_END)], AP = the pairs the discovery pass
          * clustered into the variant that re-finds this one */
         if (k->rs + k->ap == 0) { printf("\tGT:AD:GQ\t./.:0,0:."); return; }
-        int best, gq;
-        genotype_of((int64_t)k->rs, (int64_t)k->ap, &best, &gq);
-        printf("\tGT:AD:GQ\t%s:%u,%u:%d", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", k->rs, k->ap, gq);
+        print_gt_ad_gq((int64_t)k->rs, (int64_t)k->ap);
         return;
     }
     int64_t rs = k->rs_valid ? (int64_t)k->rs : 0;
@@ -1886,9 +1889,7 @@ static void print_known_genotype(const knownvariant_t* k)
     forceassert(rs >= k->n_dc);
     rs -= k->n_dc;
     if (rs + k->n_as == 0) { printf("\tGT:AD:GQ\t./.:0,0:."); return; }
-    int best, gq;
-    genotype_of(rs, (int64_t)k->n_as, &best, &gq);
-    printf("\tGT:AD:GQ\t%s:%d,%d:%d", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", (int)rs, (int)k->n_as, gq);
+    print_gt_ad_gq(rs, (int64_t)k->n_as);
 }
 
 /* -A: known variants [from, to) of the list go out; found[ki - from] says which of them the discovery pass re-found (NULL: none).
@@ -1911,11 +1912,7 @@ static void print_known_counted(driver* d, known_list* kl, int from, int to, con
         beg[m] = (int32_t)k->start; end[m] = (int32_t)(k->bpstop >= k->stop ? k->start + (k->bpstop - k->stop) : k->start); who[m] = ki; m++;
     }
     if (m > 0) {
-        gpu_wait(d);
-        pthread_mutex_lock(&g_query_mu);
-        const int qrc = d->pipe_mode ? im_span_query_tid(d->gpu, kl->v[who[0]]->tid, m, beg, end, rs) : im_span_query(d->gpu, m, beg, end, rs);
-        pthread_mutex_unlock(&g_query_mu);
-        if (qrc != IM_OK) fatalf("im_span_query: %s", im_last_error(d->gpu));
+        query_minima(d, 0, kl->v[who[0]]->tid, m, beg, end, rs);
         for (int q = 0; q < m; q++) { kl->v[who[q]]->rs = rs[q]; kl->v[who[q]]->rs_valid = 1; }
     }
     if (g_pair_counts) {
@@ -1927,11 +1924,7 @@ static void print_known_counted(driver* d, known_list* kl, int from, int to, con
             beg[m] = (int32_t)k->start; end[m] = (int32_t)(k->bpstop > k->stop ? k->bpstop : k->stop); who[m] = ki; m++;
         }
         if (m > 0) {
-            gpu_wait(d);
-            pthread_mutex_lock(&g_query_mu);
-            const int qrc = d->pipe_mode ? im_pairspan_query_tid(d->gpu, kl->v[who[0]]->tid, m, beg, end, rs) : im_pairspan_query(d->gpu, m, beg, end, rs);
-            pthread_mutex_unlock(&g_query_mu);
-            if (qrc != IM_OK) fatalf("im_pairspan_query: %s", im_last_error(d->gpu));
+            query_minima(d, 1, kl->v[who[0]]->tid, m, beg, end, rs);
             for (int q = 0; q < m; q++) { kl->v[who[q]]->rs = rs[q]; kl->v[who[q]]->rs_valid = 1; }
         }
     }

@@ -150,18 +150,18 @@ int main(int argc, char** argv)
     /* -P: behind the refusals of -G and -A, in front of what the three need of the library (the newest entry points first) */
     if (g_pair_counts) {
         if (!g_genotype && !g_known_counts) { fprintf(stderr, "indelminer: -P needs -G or -A\n"); return EXIT_FAILURE; }
-        if (!im_pairspan_enable || !im_dev_pairspan_scatter || !im_pairspan_scan || !im_pairspan_query_tid || !im_pairspan_build || !im_pairspan_query) {
+        if (!PAIR_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping paired-read records (-P) needs the device library\n"); return EXIT_FAILURE;
         }
     }
     if (g_genotype) {
-        if (!im_span_enable || !im_dev_span_scatter || !im_span_scan || !im_span_query_tid || !im_span_build || !im_span_query) {
+        if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
         if (strcmp(O.outputformat, "detailed") == 0) g_genotype = g_pair_counts = 0;    /* -o detailed has no columns to add to */
     }
     if (g_known_counts) {
-        if (!im_support_count || !im_span_enable || !im_dev_span_scatter || !im_span_scan || !im_span_query_tid || !im_span_build || !im_span_query) {
+        if (!im_support_count || !SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping known indels (-A) needs the device library\n"); return EXIT_FAILURE;
         }
     }

@@ -307,6 +307,26 @@ static void resolve_candidate(driver* d, const item_t* it, const im_read_result*
     (void)tid;
 }
 
+static void ivl_push(ivlist* l, int32_t start, int32_t len)
+{
+    if (l->n == l->cap) {
+        l->cap = l->cap ? l->cap * 2 : (1 << 16);
+        l->start = xrealloc(l->start, sizeof(int32_t) * (size_t)l->cap);
+        l->len = xrealloc(l->len, sizeof(int32_t) * (size_t)l->cap);
+    }
+    l->start[l->n] = start; l->len[l->n] = len; l->n++;
+}
+
+/* -G, -A (pair: 0) or -P (pair: 1): the contig's span or pair-span array from the intervals pass A collected */
+static void build_counted(driver* d, int pair, int32_t tid, const ivlist* l, int32_t flank)
+{
+    gpu_wait(d);
+    if (l->n > INT32_MAX) fatalf(pair ? "more than 2^31 concordant pairs on one contig" : "more than 2^31 alignment runs on one contig");
+    if ((pair ? im_pairspan_build : im_span_build)(d->gpu, d->seqlen[tid], (int32_t)l->n, l->start, l->len, flank) != IM_OK)
+        fatalf("%s: %s", pair ? "im_pairspan_build" : "im_span_build", im_last_error(d->gpu));
+    phase_time(pair ? "pair-span array (device)" : "span array (device)");
+}
+
 static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_reader* r)
 {
     d->n_items = 0; d->n_flushes = 0;
@@ -314,7 +334,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
     bam_region_iter it;
     bam_record b; memset(&b, 0, sizeof b);
     if (bam_region_begin(&it, r, d->idx, tid, beg, end) != 0) fatalf("cannot seek in %s", d->bam_name);
-    d->n_seg = 0; d->n_run = 0; d->n_frag = 0;
+    d->segs.n = 0; d->runs.n = 0; d->frags.n = 0;
     const int whole = (beg <= 0 && end >= d->hdr->target_len[tid]);
     volatile int died = 0;              /* a record the reference dies on ended the pass: the flushes in front of it are still to print */
     t_is_main_thread_of_passA = 1;
@@ -328,12 +348,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
             for (int kk = 0; kk < b.n_cigar; kk++) {
                 const int op = CIG_OP(bamr_cigar_at(cig, kk)), len = CIG_LEN(bamr_cigar_at(cig, kk));
                 if (op == OP_M || op == OP_EQ || op == OP_X) {
-                    if (d->n_seg == d->cap_seg) {
-                        d->cap_seg = d->cap_seg ? d->cap_seg * 2 : (1 << 16);
-                        d->seg_start = xrealloc(d->seg_start, sizeof(int32_t) * (size_t)d->cap_seg);
-                        d->seg_len = xrealloc(d->seg_len, sizeof(int32_t) * (size_t)d->cap_seg);
-                    }
-                    d->seg_start[d->n_seg] = x; d->seg_len[d->n_seg] = len; d->n_seg++;
+                    ivl_push(&d->segs, x, len);
                     x += len;
                 } else if (op == OP_D || op == OP_N) x += len;
             }
@@ -349,14 +364,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
                 if (in_run) {
                     /* clipped to what an int32 start and length hold (the device clips to the contig) */
                     int64_t a = rs < 0 ? 0 : rs, e = x > INT32_MAX ? INT32_MAX : x;
-                    if (e > a) {
-                        if (d->n_run == d->cap_run) {
-                            d->cap_run = d->cap_run ? d->cap_run * 2 : (1 << 16);
-                            d->run_start = xrealloc(d->run_start, sizeof(int32_t) * (size_t)d->cap_run);
-                            d->run_len = xrealloc(d->run_len, sizeof(int32_t) * (size_t)d->cap_run);
-                        }
-                        d->run_start[d->n_run] = (int32_t)a; d->run_len[d->n_run] = (int32_t)(e - a); d->n_run++;
-                    }
+                    if (e > a) ivl_push(&d->runs, (int32_t)a, (int32_t)(e - a));
                     in_run = 0;
                 }
                 if (op == OP_D || op == OP_N) x += len;
@@ -367,14 +375,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
             /* -P: the fragment [pos, pos + isize) of the pair, clipped to what an int32 start and length hold (the device clips
              * to the contig).  Behind dispatch_record: a read group that is not in the table has ended the run there. */
             const int64_t a = b.pos < 0 ? 0 : b.pos, e = (int64_t)b.pos + b.isize > INT32_MAX ? INT32_MAX : (int64_t)b.pos + b.isize;
-            if (e > a) {
-                if (d->n_frag == d->cap_frag) {
-                    d->cap_frag = d->cap_frag ? d->cap_frag * 2 : (1 << 16);
-                    d->frag_start = xrealloc(d->frag_start, sizeof(int32_t) * (size_t)d->cap_frag);
-                    d->frag_len = xrealloc(d->frag_len, sizeof(int32_t) * (size_t)d->cap_frag);
-                }
-                d->frag_start[d->n_frag] = (int32_t)a; d->frag_len[d->n_frag] = (int32_t)(e - a); d->n_frag++;
-            }
+            if (e > a) ivl_push(&d->frags, (int32_t)a, (int32_t)(e - a));
         }
     }
     g_passA_armed = 0;
@@ -383,25 +384,13 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
     d->depth_tid = -1;
     if (whole) {
         gpu_wait(d);
-        if (im_depth_build(d->gpu, d->seqlen[tid], (int32_t)d->n_seg, d->seg_start, d->seg_len) != IM_OK)
+        if (im_depth_build(d->gpu, d->seqlen[tid], (int32_t)d->segs.n, d->segs.start, d->segs.len) != IM_OK)
             fatalf("im_depth_build: %s", im_last_error(d->gpu));
         d->depth_tid = tid;
     }
     phase_time("depth array (device)");
-    if (SPAN_ON) {
-        gpu_wait(d);
-        if (d->n_run > INT32_MAX) fatalf("more than 2^31 alignment runs on one contig");
-        if (im_span_build(d->gpu, d->seqlen[tid], (int32_t)d->n_run, d->run_start, d->run_len, (int32_t)O.ethreshold) != IM_OK)
-            fatalf("im_span_build: %s", im_last_error(d->gpu));
-        phase_time("span array (device)");
-    }
-    if (PAIR_ON) {
-        gpu_wait(d);
-        if (d->n_frag > INT32_MAX) fatalf("more than 2^31 concordant pairs on one contig");
-        if (im_pairspan_build(d->gpu, d->seqlen[tid], (int32_t)d->n_frag, d->frag_start, d->frag_len, (int32_t)O.ethreshold) != IM_OK)
-            fatalf("im_pairspan_build: %s", im_last_error(d->gpu));
-        phase_time("pair-span array (device)");
-    }
+    if (SPAN_ON) build_counted(d, 0, tid, &d->runs, (int32_t)O.ethreshold);
+    if (PAIR_ON) build_counted(d, 1, tid, &d->frags, (int32_t)O.ethreshold);
 
     im_read_result* res = NULL;
     if (d->cb.n > 0) {

@@ -775,16 +775,12 @@ static void run_pipeline(driver* d, walkpool_t* o)
         }
         /* the contig (or the run of small contigs) is complete: its depth array, then its groups' replays */
         for (int k = 0; k < n_held; k++)
-            for (int cj = 0; cj < held[k]->n_ctg; cj++)
-                if (held[k]->ctg[cj].last && g_region_tid < 0) GPU2(d, im_depth_scan(d->gpu, held[k]->ctg[cj].tid, S.stream));
-        if (SPAN_ON)                             /* -G, -A: the span array too, region runs included */
-            for (int k = 0; k < n_held; k++)
-                for (int cj = 0; cj < held[k]->n_ctg; cj++)
-                    if (held[k]->ctg[cj].last) GPU2(d, im_span_scan(d->gpu, held[k]->ctg[cj].tid, S.stream));
-        if (PAIR_ON)                             /* -P: and the pair-span array */
-            for (int k = 0; k < n_held; k++)
-                for (int cj = 0; cj < held[k]->n_ctg; cj++)
-                    if (held[k]->ctg[cj].last) GPU2(d, im_pairspan_scan(d->gpu, held[k]->ctg[cj].tid, S.stream));
+            for (int cj = 0; cj < held[k]->n_ctg; cj++) {
+                if (!held[k]->ctg[cj].last) continue;
+                if (g_region_tid < 0) GPU2(d, im_depth_scan(d->gpu, held[k]->ctg[cj].tid, S.stream));
+                if (SPAN_ON) GPU2(d, im_span_scan(d->gpu, held[k]->ctg[cj].tid, S.stream));          /* -G, -A: the span array too, region runs included */
+                if (PAIR_ON) GPU2(d, im_pairspan_scan(d->gpu, held[k]->ctg[cj].tid, S.stream));      /* -P: and the pair-span array */
+            }
         GPU2(d, im_stream_sync(d->gpu, S.stream));
         if (nrep) {
             pthread_mutex_lock(&o->mu);

@@ -121,6 +121,7 @@ extern int im_span_query(im_ctx*, int32_t, const int32_t*, const int32_t*, uint3
 static int g_known_counts = 0;
 extern int im_support_count(im_ctx*, int32_t, const im_known_variant*, const uint8_t*, int64_t, int32_t, const im_count_task*, const uint8_t*, int64_t, int32_t*) __attribute__((weak));
 #define SPAN_ON (g_genotype || g_known_counts)     /* the walk scatters the span array */
+#define SPAN_API_PRESENT (im_span_enable && im_dev_span_scatter && im_span_scan && im_span_query_tid && im_span_build && im_span_query)
 /* -P, with -G or -A: PAIRED_READ records get their columns too, from the device's count of concordant pairs whose fragment spans
  * the deletion (one more genome-wide array).  Not an option of the reference; referenced weakly like the span entries. */
 static int g_pair_counts = 0;
@@ -131,6 +132,7 @@ extern int im_pairspan_query_tid(im_ctx*, int32_t, int32_t, const int32_t*, cons
 extern int im_pairspan_build(im_ctx*, int64_t, int32_t, const int32_t*, const int32_t*, int32_t) __attribute__((weak));
 extern int im_pairspan_query(im_ctx*, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
 #define PAIR_ON (g_pair_counts)                    /* the walk scatters the pair-span array */
+#define PAIR_API_PRESENT (im_pairspan_enable && im_dev_pairspan_scatter && im_pairspan_scan && im_pairspan_query_tid && im_pairspan_build && im_pairspan_query)
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that

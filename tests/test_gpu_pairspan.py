@@ -14,6 +14,7 @@ of the record's read group (its RG:Z tag, "generic" without one):
 
 The group names used here are never a prefix of one another, so the table look-up is a plain dictionary.
 """
+import functools
 import importlib.util
 import os
 import struct
@@ -22,10 +23,10 @@ import subprocess
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from tests.support import spanarrays
+from tests.support.spanarrays import GOLD, ROOT, _product, check_device, genotype_of, interval_minima, interval_queries
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
+pytestmark = pytest.mark.gpu
 
 EXCLUDED = 0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800
 
@@ -86,17 +87,6 @@ def pspan_brute(records, clen, tid_want, m, q, table, n_contigs):
             if a + m <= p and p + m <= b:
                 out[p] += 1
     return out
-
-
-def genotype_of(rs, ns):
-    """(GT, GQ) in thousandths of a phred, integers only"""
-    E, C, H = 20000, 44, 3010
-    L = [ns * E + rs * C, (ns + rs) * H, ns * C + rs * E]
-    lo = min(L)
-    L = [x - lo for x in L]
-    best = L.index(0)                       # the lower index wins a tie
-    second = sorted(L[:best] + L[best + 1:])[0]
-    return ("0/0", "0/1", "1/1")[best], min(99, (second + 500) // 1000)
 
 
 # ------------------------------------------------------------------------------------------ records
@@ -162,90 +152,13 @@ def parse_raw(raw, off):
     return [parse_record(b, int(off[i]), int(off[i + 1])) for i in range(len(off) - 1)]
 
 
-def read_bam_records(path):
-    """(contigs [(name, length)], records) of a BAM file"""
-    from tests.support import bamlite
-    raw = bytes(bamlite.bgzf_decompress(path))
-    assert raw[:4] == b"BAM\1"
-    p = 8 + struct.unpack_from("<i", raw, 4)[0]
-    n_ref = struct.unpack_from("<i", raw, p)[0]; p += 4
-    refs = []
-    for _ in range(n_ref):
-        l_name = struct.unpack_from("<i", raw, p)[0]; p += 4
-        name = raw[p:p + l_name - 1].decode(); p += l_name
-        refs.append((name, struct.unpack_from("<i", raw, p)[0])); p += 4
-    recs = []
-    while p < len(raw):
-        bs = struct.unpack_from("<i", raw, p)[0]; p += 4
-        recs.append(parse_record(raw, p, p + bs))
-        p += bs
-    return refs, recs
+read_bam_records = functools.partial(spanarrays.read_bam_records, parse_record=parse_record)
 
 
 # ------------------------------------------------------------------------------------------ device level
 
-class Device:
-    """one context with the genome-wide pair-span array enabled for (m, q) over contigs of the given lengths"""
 
-    def __init__(self, clens, m, q, table=None, seed=3):
-        from indelminer_amd import capi
-        self.capi = capi
-        rng = np.random.default_rng(seed)
-        self.clens = list(clens)
-        self.ctx = capi.Context(0)
-        self.ctx.set_reference([bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), n)) for n in clens])
-        if table is not None:
-            self.ctx.set_insert_ranges(list(table), [table[k] for k in table])
-        self.ctx.pairspan_enable(m, q)
-        self.keep = []
-
-    def scatter(self, raw, off):
-        capi = self.capi
-        d_raw = capi.DevBuf(self.ctx, len(raw) + 64).upload(raw)
-        d_off = capi.DevBuf(self.ctx, 4 * len(off)).upload(off)
-        self.keep += [d_raw, d_off]
-        self.ctx.pairspan_scatter(capi.DevRecords(len(off) - 1, d_raw.ptr, d_off.ptr, 0))
-
-    def scan(self):
-        for t in range(len(self.clens)):
-            self.ctx.pairspan_scan(t)
-        self.ctx._check(self.capi.lib().im_stream_sync(self.ctx.h, self.ctx.stream))
-
-    def every_position(self, tid):
-        p = np.arange(self.clens[tid] + 1, dtype=np.int32)
-        return self.ctx.pairspan_query_tid(tid, p, p).astype(np.int64)
-
-    def close(self):
-        for b in self.keep:
-            b.free()
-        self.ctx.close()
-
-
-def interval_queries(rng, clen, n=400):
-    """whole intervals: short, longer than a wave's 64 lanes, reaching out of the contig on both sides, the whole contig"""
-    beg = rng.integers(-50, clen + 1, n)
-    ln = np.concatenate([rng.integers(0, 8, n // 2), rng.integers(60, 700, n - n // 2)])
-    end = beg + ln
-    beg = np.concatenate([beg, [0, -5, clen, clen - 1]]); end = np.concatenate([end, [clen, clen + 40, clen, clen + 9]])
-    return beg.astype(np.int32), end.astype(np.int32)
-
-
-def interval_minima(span, beg, end, clen):
-    out = []
-    for a, b in zip(beg, end):
-        a, b = max(int(a), 0), min(int(b), clen)
-        out.append(int(span[a:b + 1].min()) if a <= b else 0)
-    return np.array(out, np.int64)
-
-
-def check_device(dev, want, rng):
-    for tid, clen in enumerate(dev.clens):
-        got = dev.every_position(tid)
-        bad = np.nonzero(got != want[tid])[0]
-        assert len(bad) == 0, (tid, bad[:10], got[bad[:10]], want[tid][bad[:10]])
-        beg, end = interval_queries(rng, clen)
-        assert np.array_equal(dev.ctx.pairspan_query_tid(tid, beg, end).astype(np.int64), interval_minima(want[tid], beg, end, clen)), tid
-
+Device = functools.partial(spanarrays.Device, "pairspan")
 
 CLENS = [150_000, 5_000]
 TABLE = {"generic": 700, "rgB": 400}
@@ -472,15 +385,75 @@ def test_pairspan_scatter_without_insert_ranges_is_an_error():
         dev.close()
 
 
+def _span_restatement():
+    spec = importlib.util.spec_from_file_location("span_restatement", os.path.join(ROOT, "tests", "test_gpu_span.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.span_of
+
+
+def test_span_and_pairspan_genome_arrays_are_independent():
+    """-G -P on the device pipeline holds both genome-wide arrays in one context: the same chunk scattered into each, each scanned,
+    reset and queried on its own, each enable refusing other parameters under its own name.  Contig 0 crosses one edge of the
+    scan's 8192-position tile."""
+    import ctypes as C
+    clens, m, q = [8292, 300], 10, 10
+    rng = np.random.default_rng(41)
+    pos0 = np.concatenate([rng.integers(0, 8292, 1400), rng.integers(7600, 8292, 400)])       # 400 of them around position 8192
+    recs = [left(0, int(p), int(s), rg=g, mapq=int(mq)) for p, s, g, mq in
+            zip(pos0, rng.choice([150, 300, 450, 700], len(pos0)), rng.choice([None, "rgB"], len(pos0)), rng.choice([9, 10, 60], len(pos0)))]
+    recs += [left(1, int(p), int(s)) for p, s in zip(rng.integers(0, 290, 200), rng.choice([19, 20, 60, 150, 400], 200))]
+    recs.sort(key=lambda r: (r[0], r[1]))
+    assert any(r[1] < 8192 < r[1] + r[6] for r in recs)
+    want_pair = pspan_of(recs, clens, m, q, TABLE)
+    want_span = _span_restatement()([(r[0], r[1], r[2], r[3], [(0, 100)]) for r in recs], clens, m, q)      # the packer writes 100M
+    assert all(not np.array_equal(s, p) for s, p in zip(want_span, want_pair)) and all(w.max() > 0 for w in want_span + want_pair)
+    dev = Device(clens, m, q, TABLE)
+    ctx, L = dev.ctx, dev.capi.lib()
+    span_at = lambda t: ctx.span_query_tid(t, np.arange(clens[t] + 1, dtype=np.int32), np.arange(clens[t] + 1, dtype=np.int32)).astype(np.int64)
+    try:
+        ctx.span_enable(m, q)
+        chunk = dev.scatter(*raw_records(recs))                     # into the pair array ...
+        ctx.span_scatter(chunk)                                     # ... and the same chunk into the span array
+        dev.scan()
+        for t in range(2):
+            ctx.span_scan(t)
+        for t in range(2):
+            assert np.array_equal(dev.every_position(t), want_pair[t]), t
+            assert np.array_equal(span_at(t), want_span[t]), t
+        ctx.span_reset(0); ctx.span_scan(0)
+        assert not span_at(0).any() and np.array_equal(span_at(1), want_span[1])
+        assert all(np.array_equal(dev.every_position(t), want_pair[t]) for t in range(2))
+        ctx.span_scatter(chunk)                                     # contig 1 now holds its records twice: contig 0 is what is read
+        ctx.span_scan(0)
+        ctx.pairspan_reset(0); ctx.pairspan_scan(0)
+        assert not dev.every_position(0).any() and np.array_equal(dev.every_position(1), want_pair[1])
+        assert np.array_equal(span_at(0), want_span[0])
+        # the refusals, each under its own name
+        assert L.im_span_enable(ctx.h, 11, 10) != 0
+        assert L.im_last_error(ctx.h) == b"im_span_enable: already enabled with flank 10, min_mapq 10"
+        assert L.im_pairspan_enable(ctx.h, 10, 11) != 0
+        assert L.im_last_error(ctx.h) == b"im_pairspan_enable: already enabled with flank 10, min_mapq 10"
+        assert L.im_span_enable(ctx.h, 10, 10) == 0 and L.im_pairspan_enable(ctx.h, 10, 10) == 0
+        # a null pointer with n = 1 is an argument error, not a fault
+        one, out = np.zeros(1, np.int32), np.zeros(1, np.uint32)
+        ctx.depth_enable()
+        for fn in (L.im_span_query_tid, L.im_pairspan_query_tid, L.im_depth_query_tid):
+            assert fn(ctx.h, 0, 1, None, one.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0
+    finally:
+        dev.close()
+    fresh = dev.capi.Context(0)
+    try:
+        fresh.set_reference([b"ACGT" * 25])
+        assert L.im_span_enable(fresh.h, 0, 10) != 0
+        assert L.im_last_error(fresh.h) == b"im_span_enable: flank 0, must be >= 1"
+    finally:
+        fresh.close()
+
+
 # ------------------------------------------------------------------------------------------ the product
 
 META = '##pairedReadAD="PAIRED_READ records: AD = concordant pairs spanning the deletion with -n bases on each side (lower bound), pairs supporting it"'
-
-
-def _product():
-    from indelminer_amd import build
-    build.build()
-    return build.build_host()
 
 
 def _run(binary, flags, cwd, env=None, vcf=None, sample="sample"):

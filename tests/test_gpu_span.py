@@ -9,6 +9,7 @@ include/indelminer_amd.h and DESIGN.md, not the code under test:
   * span[p], 0 <= p <= clen, counts the runs with s <= p - m and p + m <= e;
   * RS of a printed variant = min(span[p] for p in POS .. POS + (BP_END - END)); GT / GQ from (RS, NS) in integers.
 """
+import functools
 import importlib.util
 import os
 import struct
@@ -17,10 +18,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.support import spanarrays
+from tests.support.spanarrays import GOLD, ROOT, _golden, _product, check_device, genotype_of, interval_minima, interval_queries
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 TD = os.path.join(GOLD, "test_data")
 
 OPS = "MIDNSHP=X"
@@ -85,17 +87,6 @@ def span_brute(records, clen, tid_want, m, min_mapq, n_contigs):
     return out
 
 
-def genotype_of(rs, ns):
-    """(GT, GQ) in thousandths of a phred, integers only"""
-    E, C, H = 20000, 44, 3010
-    L = [ns * E + rs * C, (ns + rs) * H, ns * C + rs * E]
-    lo = min(L)
-    L = [x - lo for x in L]
-    best = L.index(0)                       # the lower index wins a tie
-    second = sorted(L[:best] + L[best + 1:])[0]
-    return ("0/0", "0/1", "1/1")[best], min(99, (second + 500) // 1000)
-
-
 # ------------------------------------------------------------------------------------------ records
 
 def cig(text):
@@ -124,105 +115,26 @@ def raw_records(records):
     return np.frombuffer(bytes(blob), np.uint8).copy(), np.array(off, np.uint32)
 
 
+def parse_record(b, o, _end=None):
+    """one record at b[o:] -> (tid, pos, mapq, flag, cigar), bases left alone"""
+    tid, pos, l_qname, mapq, _bin, n_cig, flag = struct.unpack_from("<iiBBHHH", b, o)
+    cw = struct.unpack_from("<%dI" % n_cig, b, o + 32 + l_qname)
+    return tid, pos, mapq, flag, [(c & 15, c >> 4) for c in cw]
+
+
 def parse_raw(raw, off):
     """the device layout back into [(tid, pos, mapq, flag, cigar)]"""
     b = raw.tobytes()
-    out = []
-    for i in range(len(off) - 1):
-        o = int(off[i])
-        tid, pos, l_qname, mapq, _bin, n_cig, flag = struct.unpack_from("<iiBBHHH", b, o)
-        cw = struct.unpack_from("<%dI" % n_cig, b, o + 32 + l_qname)
-        out.append((tid, pos, mapq, flag, [(c & 15, c >> 4) for c in cw]))
-    return out
+    return [parse_record(b, int(off[i])) for i in range(len(off) - 1)]
 
 
-def read_bam_records(path):
-    """(contigs [(name, length)], [(tid, pos, mapq, flag, cigar)]) of a BAM file, bases left alone"""
-    from tests.support import bamlite
-    raw = bytes(bamlite.bgzf_decompress(path))
-    assert raw[:4] == b"BAM\1"
-    p = 8 + struct.unpack_from("<i", raw, 4)[0]
-    n_ref = struct.unpack_from("<i", raw, p)[0]; p += 4
-    refs = []
-    for _ in range(n_ref):
-        l_name = struct.unpack_from("<i", raw, p)[0]; p += 4
-        name = raw[p:p + l_name - 1].decode(); p += l_name
-        refs.append((name, struct.unpack_from("<i", raw, p)[0])); p += 4
-    recs = []
-    while p < len(raw):
-        bs = struct.unpack_from("<i", raw, p)[0]; p += 4
-        tid, pos, l_qname, mapq, _bin, n_cig, flag = struct.unpack_from("<iiBBHHH", raw, p)
-        cw = struct.unpack_from("<%dI" % n_cig, raw, p + 32 + l_qname)
-        recs.append((tid, pos, mapq, flag, [(c & 15, c >> 4) for c in cw]))
-        p += bs
-    return refs, recs
+read_bam_records = functools.partial(spanarrays.read_bam_records, parse_record=parse_record)
 
 
 # ------------------------------------------------------------------------------------------ device level
 
-class Device:
-    """one context with the genome-wide span array enabled for (m, min_mapq) over contigs of the given lengths"""
 
-    def __init__(self, clens, m, min_mapq, seed=3):
-        from indelminer_amd import capi
-        self.capi = capi
-        rng = np.random.default_rng(seed)
-        self.contigs = [bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), n)) for n in clens]
-        self.clens = list(clens)
-        self.ctx = capi.Context(0)
-        self.ctx.set_reference(self.contigs)
-        self.ctx.span_enable(m, min_mapq)
-        self.keep = []
-
-    def scatter(self, raw, off):
-        capi = self.capi
-        d_raw = capi.DevBuf(self.ctx, len(raw) + 64).upload(raw)
-        d_off = capi.DevBuf(self.ctx, 4 * len(off)).upload(off)
-        self.keep += [d_raw, d_off]
-        recs = capi.DevRecords(len(off) - 1, d_raw.ptr, d_off.ptr, 0)
-        self.ctx.span_scatter(recs)
-        return recs
-
-    def scan(self):
-        for t in range(len(self.clens)):
-            self.ctx.span_scan(t)
-        self.ctx._check(self.capi.lib().im_stream_sync(self.ctx.h, self.ctx.stream))
-
-    def every_position(self, tid):
-        p = np.arange(self.clens[tid] + 1, dtype=np.int32)
-        return self.ctx.span_query_tid(tid, p, p).astype(np.int64)
-
-    def close(self):
-        for b in self.keep:
-            b.free()
-        self.ctx.close()
-
-
-def interval_queries(rng, clen, n=400):
-    """whole intervals: short, longer than a wave's 64 lanes, reaching out of the contig on both sides, the whole contig"""
-    beg = rng.integers(-50, clen + 1, n)
-    ln = np.concatenate([rng.integers(0, 8, n // 2), rng.integers(60, 700, n - n // 2)])
-    end = beg + ln
-    beg = np.concatenate([beg, [0, -5, clen, clen - 1]]); end = np.concatenate([end, [clen, clen + 40, clen, clen + 9]])
-    return beg.astype(np.int32), end.astype(np.int32)
-
-
-def interval_minima(span, beg, end, clen):
-    out = []
-    for a, b in zip(beg, end):
-        a, b = max(int(a), 0), min(int(b), clen)
-        out.append(int(span[a:b + 1].min()) if a <= b else 0)
-    return np.array(out, np.int64)
-
-
-def check_device(dev, want, rng):
-    for tid, clen in enumerate(dev.clens):
-        got = dev.every_position(tid)
-        bad = np.nonzero(got != want[tid])[0]
-        assert len(bad) == 0, (tid, bad[:10], got[bad[:10]], want[tid][bad[:10]])
-        beg, end = interval_queries(rng, clen)
-        assert np.array_equal(dev.ctx.span_query_tid(tid, beg, end).astype(np.int64), interval_minima(want[tid], beg, end, clen)), tid
-
+Device = functools.partial(spanarrays.Device, "span")
 
 CLENS = [150_000, 5_000]
 
@@ -476,20 +388,10 @@ def _thd():
     return mod
 
 
-def _product():
-    from indelminer_amd import build
-    build.build()
-    return build.build_host()
-
-
 def _run(binary, flags, cwd, ref, bam, env=None, vcf=None, sample="sample"):
     e = dict(os.environ)
     e.update(env or {})
     return subprocess.run([binary] + flags + [ref] + ([vcf] if vcf else []) + [sample + "=" + bam], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e)
-
-
-def _golden(name):
-    return open(os.path.join(GOLD, "vcf", name + ".vcf"), "rb").read()
 
 
 def strip_columns(out):
