@@ -337,6 +337,74 @@ def test_support_kernel_matches_reference_realign_with_indel(gpu_ctx):
         assert [int(x) for x in got[k][:3]] == c["expect"], (k, c["expect"], tuple(got[k]))
 
 
+def _sw_oracle(t, q):
+    import ctypes as C
+    from tests.support import oraclebind as ob
+    s, i, a = C.c_int32(), C.c_int32(), C.c_int32()
+    ob.lib().imo_sw_indel(t, len(t), q, len(q), C.byref(s), C.byref(i), C.byref(a))
+    return [s.value, i.value, a.value]
+
+
+def test_support_kernel_on_low_complexity_variants(gpu_ctx):
+    """variants inside or at the edge of homopolymers and short tandem repeats, whole repeat units among them
+    (tests/support/lowcomplexity.py: sw_cases): where equal-score paths are the norm the forward-carried path statistics must
+    follow the path the reference's traceback prefers.  Against the reference's own realign_with_indel answers
+    (tests/golden/ref_lowcomplexity.json) and against the oracle."""
+    import json
+    from tests.support import lowcomplexity as lc
+    from tests.test_oracle_units import variant_window
+    cases = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", lc.GOLDEN_NAME)))["sw"]
+    assert len(cases) == 300 and sum(c["expect"][1] > 0 for c in cases) >= 100
+    targets = [variant_window(c) for c in cases]
+    queries = [c["read"][c["qstart"]:c["qstop"]].encode() for c in cases]
+    got = gpu_ctx.support_batch(targets, queries)
+    for k, c in enumerate(cases):
+        assert [int(x) for x in got[k][:3]] == c["expect"], (k, c["expect"], tuple(got[k]))
+        assert _sw_oracle(targets[k], queries[k]) == c["expect"], k
+
+
+def test_support_sw_second_form_on_low_complexity(gpu_ctx):
+    """the second form (windows beyond IM_MAX_SW_TARGET, queries beyond IM_MAX_READ) on targets of alternating random and repeat
+    stretches; every query carries a deletion or an expansion of whole repeat units inside a repeat"""
+    from indelminer_amd import capi
+    from tests.support import lowcomplexity as lc
+    shapes = [(4096, 100), (5100, 150), (9000, 300), (3000, 1021), (2000, 2600), (1500, 255)] * 4
+    targets, queries = lc.support_pairs(88, shapes)
+    assert [(len(t), len(q)) for t, q in zip(targets, queries)] == shapes
+    got = gpu_ctx.support_batch(targets, queries)
+    n_big = n_indel = 0
+    for k, (t, q) in enumerate(zip(targets, queries)):
+        want = _sw_oracle(t, q)
+        assert [int(x) for x in got[k][:3]] == want and got[k][3] == capi.ST_EVIDENCE, (k, len(t), len(q), tuple(got[k]), want)
+        n_big += len(t) > 4095 or len(q) > capi.MAX_READ
+        n_indel += want[1] > 0
+    assert 2 * n_big >= len(shapes) and n_indel >= len(shapes) // 3
+
+
+def test_support_sw_hand_made_ties(gpu_ctx):
+    """nothing but ties: a query that fits a pure repeat at every period, with one unit deleted or inserted, each once more with
+    an N in the middle of the query"""
+    from indelminer_amd import capi
+    pairs = [(b"A" * 200, b"A" * 90),
+             (b"AC" * 100, b"AC" * 40 + b"AC" * 38),
+             (b"CAG" * 60, b"CAG" * 20 + b"CAG" + b"CAG" * 15)]
+    # the same between flanks of 25 bases that occur once and pin both ends (50 points each; a gap of six bases costs 10):
+    # two units deleted, two units inserted -- six indels each, their place in the repeat open -- and six units inserted
+    f1, f2 = b"GTTACGGATCCATTGACGTA" * 2, b"TCGGATACCTGAATCGTTCA" * 2
+    pairs += [(f1 + b"CAG" * 30 + f2, f1[-25:] + b"CAG" * n + f2[:25]) for n in (28, 32, 36)]
+    targets, queries = [], []
+    for t, q in pairs:
+        targets += [t, t]
+        queries += [q, q[:len(q) // 2] + b"N" + q[len(q) // 2 + 1:]]
+    got = gpu_ctx.support_batch(targets, queries)
+    indels = []
+    for k, (t, q) in enumerate(zip(targets, queries)):
+        want = _sw_oracle(t, q)
+        assert [int(x) for x in got[k][:3]] == want and got[k][3] == capi.ST_EVIDENCE, (k, tuple(got[k]), want)
+        indels.append(want[1])
+    assert indels[6:10] == [6, 6, 6, 6], indels
+
+
 @pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1000, 50001])
 def test_compact_results_packs_exactly_the_records_with_evidence(gpu_ctx, n):
     """im_dev_compact_results: status and place of every read, the records with status == IM_ST_EVIDENCE and n_ev > 0 packed whole

@@ -422,3 +422,54 @@ def test_what_used_to_be_unsupported_runs(gpu_ctx):
         st, res = ob.realign(ob.params(**kw), contig, len(contig), 100, 300, read.decode())
         assert gpucmp.hip_vs_oracle(out[0], st, res) is None, kw
     gpu_ctx.expect_read_length(capi.MAX_READ + 1)
+
+
+def _low_complexity_run(ctx, kw, seed, tag, **gen):
+    """one batch of tests/support/lowcomplexity.py: realign_cases against the oracle; returns (cases, records)"""
+    from indelminer_amd import capi
+    from tests.support import lowcomplexity as lc
+    contig, cases, share = lc.realign_cases(seed, **gen)
+    assert share >= 0.4, share
+    ctx.set_reference([contig.encode()])
+    out, bad = _run_cases(ctx, capi, capi.params(**kw), ob.params(**kw), contig.encode(), cases)
+    # the failing reads whole (index, difference, anchor, range_max, bases): each is a case to keep by name
+    assert not bad, "%s %r seed %d: %d of %d differ, first: %r" % (tag, kw, seed, len(bad), len(cases), bad[:5])
+    assert int((out["status"] == 1).sum()) >= 30
+    return cases, out
+
+
+@pytest.mark.parametrize("k,g", [(6, 0), (5, 0), (4, 0), (8, 0), (13, 0), (14, 0), (6, 1), (6, 3), (8, 2), (6, 12), (6, 40)])
+def test_hip_matches_oracle_on_low_complexity(gpu_ctx, k, g):
+    """Reads whose indel sits in a homopolymer or a short tandem repeat (tests/support/lowcomplexity.py): most k-mers of a piece
+    are not unique, so few vote, diagonals tie and select_band's nearest-the-anchor rule decides; a deletion inside a repeat has
+    a run of equally good cut points; equal-score paths are the norm for the g = 0 scans and the band kernel's traceback.
+    Direct table (k = 6 specialised, 5, 4), prefix table (8, 13), hash (14), band kernel (-g 1, 3, 2, 12) and a wide band (-g 40).
+    Where the reference's own answers to a run are committed (tests/golden/ref_lowcomplexity.json) the records are held
+    against them as well."""
+    from tests.support import lowcomplexity as lc, refcases
+    kw = dict(klength=k, numgaps=g, maxdelsize=1000, ethreshold=max(k, 10))
+    _low_complexity_run(gpu_ctx, kw, 1000 + 100 * k + g, "k%d_g%d" % (k, g), n=1500, clen=40000)
+    for seed in [s for kk, gg, s in lc.REALIGN_RUNS if (kk, gg) == (k, g)]:
+        want = golden.load(lc.GOLDEN_NAME)["realign"][refcases.key("lowc", k, g, seed)]
+        cases, out = _low_complexity_run(gpu_ctx, kw, seed, "k%d_g%d_golden" % (k, g))
+        assert len(want) == len(cases)
+        for rec, c, ro in zip(out, cases, want):
+            if ro == "abort":
+                assert int(rec["status"]) == -1, c
+                continue
+            ops = [int(x) for x in rec["ops"][:int(rec["n_ops"])]] if rec["status"] == 1 else []
+            evs = [(int(e["cls"]), int(e["b1"]), int(e["b2"]), int(e["seg"])) for e in rec["ev"][:int(rec["n_ev"])]] if rec["status"] == 1 else []
+            msg = golden.golden_vs_segments(ro, int(rec["status"]), int(rec["ref_start"]), ops, evs)
+            assert msg is None, (c, msg)
+
+
+@pytest.mark.parametrize("k", [6, 9])
+def test_hip_long_reads_match_oracle_on_low_complexity(gpu_ctx, k):
+    """the same family for the long-read kernel (indelminer_amd/csrc/im_realign_long.hip): reads of 256, 300 and 1020 bases in
+    one batch with reads of 100 bases, on a 20 kb contig; a piece of 1020 bases spans several repeat stretches"""
+    from indelminer_amd import capi
+    kw = dict(klength=k, numgaps=0, maxdelsize=3000, ethreshold=10)
+    cases, out = _low_complexity_run(gpu_ctx, kw, 2000 + k, "long_k%d" % k, n=400, clen=20000, lengths=(256, 300, 1020, 100), range_max=2500)
+    is_long = np.array([len(c["read"]) > capi.SHORT_READ for c in cases])
+    assert int((out["status"][is_long] == 1).sum()) >= 30 and int((out["status"][~is_long] == 1).sum()) >= 10
+    assert {len(c["read"]) for c in cases} == {256, 300, 1020, 100}

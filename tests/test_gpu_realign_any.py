@@ -199,3 +199,21 @@ def test_general_pass_on_the_device_entry(gpu_ctx):
         else:
             assert (cls[i] == 77).all()
     assert n_ev > 4
+
+
+@pytest.mark.parametrize("k,g,lengths,Rm,maxdel,n", [(6, 61, (100, 150, 250), 705, 1000, 400), (4, 64, (100, 150, 250), 705, 1000, 400),
+                                                     (6, 0, (1021, 1500, 2047, 2600), 5000, 3000, 200)])
+def test_general_pass_on_low_complexity(gpu_ctx, k, g, lengths, Rm, maxdel, n):
+    """Reads whose indel sits in a homopolymer or a short tandem repeat (tests/support/lowcomplexity.py) through the general
+    pass: bands wider than a wave, and reads beyond the long-read kernel's 1020 bases at -g 0.  Tied diagonals, runs of equally
+    good cut points and equal-score paths must come out as the reference places them.  Every window stays off the contig's first
+    3 kb: that geometry has its own test (test_long_reads_hanging_off_the_contig_start)."""
+    from indelminer_amd import capi
+    from tests.support import lowcomplexity as lc
+    first = 3000 + Rm + maxdel
+    contig, cases, share = lc.realign_cases(3000 + 10 * k + g, n=n, clen=first + 30000, lengths=lengths, first=first, range_max=Rm)
+    assert share >= 0.4, share
+    assert min(c["anchor"] - c["range_max"] - maxdel for c in cases) >= 3000
+    gpu_ctx.set_reference([contig.encode()])
+    out = _compare(gpu_ctx, capi, dict(klength=k, numgaps=g, maxdelsize=maxdel), contig.encode(), cases, "low complexity")
+    assert int((out["status"] == 1).sum()) >= 30

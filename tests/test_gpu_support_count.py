@@ -157,3 +157,41 @@ def test_support_count_mixes_lds_form_tasks_with_tasks_beyond_it():
     assert sum(len(w) > 4095 for w in wins) >= 24 and max(int(t["q_len"]) for t in tasks) > capi.MAX_READ
     assert (got[:, 0] > 0).all(), got
     ctx.close()
+
+
+def test_support_count_on_whole_repeat_unit_variants():
+    """known variants that delete or expand whole repeat units inside a homopolymer or a short tandem repeat
+    (tests/support/lowcomplexity.py: sw_cases), every read's own numbers one below, at or one above what the Smith-Waterman gives
+    for it, so that a count moves with any path statistic that comes out differently among the equal-score paths of a repeat"""
+    import json
+    import os
+    from indelminer_amd import capi
+    from tests.support import knowncounts as kc, lowcomplexity as lc
+    gold = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", lc.GOLDEN_NAME)))["sw"]
+    made = lc.sw_cases(lc.SW_SEED, lc.SW_N)
+    rng = np.random.default_rng(22)
+    contig, variants, alts, tasks, queries = b"", [], b"", [], b""
+    for c, g in zip(made, gold):
+        assert lc.sw_inputs(c) == {k: v for k, v in g.items() if k != "expect"}
+        if not (c["in_repeat"] and c["whole_units"]):
+            continue
+        base = len(contig)                                          # the cases' stretches one after another: one contig
+        contig += c["contig"].encode()
+        typ = kc.DEL if c["is_deletion"] else kc.INS
+        alt = c["alternate"].encode()
+        variants.append((0, base + c["vstart"], base + (c["vstop"] if typ == kc.DEL else c["vstart"] + 1), typ, len(alts), len(alt)))
+        alts += alt
+        q = c["read"][c["qstart"]:c["qstop"]].encode()
+        for _ in range(3):
+            own = tuple(int(x) + int(rng.integers(-1, 2)) for x in g["expect"])
+            tasks.append((len(variants) - 1, base + c["rstart"], base + c["rstop"], len(queries), len(q)) + own + (int(rng.integers(0, 8)) & ~capi.SC_DIRECT,))
+        queries += q
+    assert len(variants) >= 60
+    variants = np.array(variants, dtype=capi.KNOWN_VARIANT_DTYPE)
+    tasks = np.array(tasks, dtype=capi.COUNT_TASK_DTYPE)
+    ctx = capi.Context(0)
+    ctx.set_reference([contig])
+    got, wins = _check(ctx, capi, kc, [contig], variants, alts, tasks, queries)
+    assert {int(t) for t in variants["type"]} == {kc.INS, kc.DEL}
+    assert 0 < got[:, 0].sum() < len(tasks) and got[:, 2].sum() > 0
+    ctx.close()

@@ -72,3 +72,35 @@ def test_sw_indel_matches_realign_with_indel():
         assert [s.value, i.value, a.value] == c["expect"], (k, c["expect"], (s.value, i.value, a.value))
         kinds.add((c["is_deletion"], c["expect"][1] == 0))
     assert len(kinds) == 4 and len(cases) >= 300
+
+
+def test_sw_indel_matches_realign_with_indel_on_low_complexity():
+    """the same on variants inside or at the edge of homopolymers and short tandem repeats, sizes of whole repeat units among
+    them (tests/support/lowcomplexity.py: sw_cases; tests/golden/ref_lowcomplexity.json): the traceback's preference among
+    diagonal, up and left decides (score, indels, aligned) where equal-score paths are the norm.  Where the reference is
+    compiled in place it is called live and must still give the committed counts."""
+    from tests.support import lowcomplexity as lc
+    cases = json.load(open(os.path.join(GOLD, lc.GOLDEN_NAME)))["sw"]
+    made = lc.sw_cases(lc.SW_SEED, lc.SW_N)
+    assert [{k: v for k, v in c.items() if k != "expect"} for c in cases] == [lc.sw_inputs(c) for c in made]
+    assert len(cases) == 300
+    assert sum(c["in_repeat"] for c in made) >= 150 and sum(c["whole_units"] for c in made) >= 60
+    assert sum(c["expect"][1] > 0 for c in cases) >= 100
+    units = os.path.join(os.path.dirname(GOLD), os.pardir, "oracle", "_ref", "librefunits.so")
+    U = C.CDLL(units) if os.path.exists(units) else None
+    L = ob.lib()
+    kinds = set()
+    for k, c in enumerate(cases):
+        if U is not None:
+            s, i, a = C.c_int(), C.c_int(), C.c_int()
+            U.imref_realign_with_indel(c["contig"].encode(), C.c_int(c["rstart"]), C.c_int(c["rstop"]), c["read"].encode(),
+                                       C.c_int(c["qstart"]), C.c_int(c["qstop"]), C.c_int(c["is_deletion"]), C.c_uint(c["vstart"]),
+                                       C.c_uint(c["vstop"]), c["alternate"].encode(), C.byref(s), C.byref(i), C.byref(a))
+            assert [s.value, i.value, a.value] == c["expect"], k
+        t = variant_window(c)
+        q = c["read"][c["qstart"]:c["qstop"]].encode()
+        s, i, a = C.c_int32(), C.c_int32(), C.c_int32()
+        L.imo_sw_indel(t, len(t), q, len(q), C.byref(s), C.byref(i), C.byref(a))
+        assert [s.value, i.value, a.value] == c["expect"], (k, c["expect"], (s.value, i.value, a.value))
+        kinds.add((c["is_deletion"], c["expect"][1] == 0))
+    assert len(kinds) == 4
