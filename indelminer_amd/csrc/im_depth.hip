@@ -8,8 +8,9 @@
 // CIGAR op is M, = or X.  An array is clen + 1 int32 of one contig and goes through three steps:
 //   scatter             +1 / -1 events into the zeroed array (device atomics): depth_scatter here for host-given intervals
 //                       (the record-at-a-time path), im_triage.hip / im_span.hip from the records for the genome-wide arrays
-//   depth_scan_tiled    ONE launch: prefix sum inside tiles of 8192 positions; the workgroup that arrives last turns the tiles'
-//                       totals into exclusive tile offsets in sums[].  The array stays tile-local (HBM streaming, one pass)
+//   depth_scan_tiled    ONE launch: prefix sum inside tiles of 8192 positions, a tile per workgroup of 256 lanes with the whole tile
+//                       in flight; the workgroup that arrives last turns the tiles' totals into exclusive tile offsets in sums[].
+//                       The array stays tile-local (HBM streaming, one pass)
 //   depth_query_tiled   one wave per printed variant: sum of data[p] + sums[p / 8192] over [start-lw-1, stop+rw+1)
 // The host takes floor(sum / length) like the reference (src/shared.c:205).
 //
@@ -24,10 +25,14 @@
 namespace im {
 namespace {
 
-constexpr int kScanBlock = 1024;
-constexpr int kScanItems = 8;
-static_assert(kScanTile == kScanBlock * kScanItems, "im_device.hpp names the tile for the queries");
+constexpr int kScanBlock = 256;
+constexpr int kScanItems = 8;                               // a lane's share of one sub-tile: two 16-byte accesses
+constexpr int kScanSub = kScanBlock * kScanItems;           // positions of a sub-tile: a wave reads 2 KB of it in one piece
+constexpr int kScanSubs = kScanTile / kScanSub;             // sub-tiles of a tile, all with one workgroup
+constexpr int kScanWaves = kScanBlock / 64;
+static_assert(kScanTile == kScanSub * kScanSubs, "im_device.hpp names the tile for the queries");
 constexpr int kScanGroup = 32;      // tiles that count their arrival into one word (depth_scan_tiled_kernel)
+constexpr int kOffItems = 4;        // tile totals a lane of the last workgroup takes per round of the offset pass
 
 // host-given intervals [start, start + len) of one contig, clipped to [0, clen): +1 at a + lo, -1 at b - hi iff a + lo < b - hi
 // (launch_depth_build has the two uses)
@@ -44,78 +49,129 @@ __global__ __launch_bounds__(256) void depth_scatter_kernel(int32_t n_seg, const
     }
 }
 
+// One tile's inclusive scan, in place.  A lane holds kScanItems consecutive positions of each of the tile's kScanSubs sub-tiles;
+// every load of the tile is issued before the first is consumed (128 bytes in flight per lane, the whole tile per workgroup).
+// One barrier: the kScanSubs x kScanWaves wave totals meet in LDS, and every lane adds up the ones in front of it.
+// Whole: the tile lies inside [0, n) and travels as 16-byte accesses (the contig's run starts on a 256-byte boundary);
+// otherwise position by position, a clamped index instead of a branch around each load.  Lane 0 sends the tile's total to *total
+// in front of the tile's stores, so that its round trip runs beside them; returns what that atomic returned.
+template <bool Whole>
+__device__ __forceinline__ int32_t scan_tile(int32_t* __restrict__ data, int64_t n, int64_t tile0, int32_t* wsum, int tid, int32_t* total)
+{
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int32_t v[kScanSubs][kScanItems];
+    static_assert(kScanItems == 8, "a lane's eight items travel as two 16-byte accesses");
+    data += tile0;                                          // positions of the tile from here on: 32-bit offsets from a uniform base
+    const int32_t room = (int32_t)(n - tile0 < kScanTile ? n - tile0 : kScanTile);      // >= 1: the tile exists
+#pragma unroll
+    for (int s = 0; s < kScanSubs; s++) {
+        const int32_t base = s * kScanSub + tid * kScanItems;
+        if (Whole) {
+            const int4 a = *reinterpret_cast<const int4*>(data + base), c = *reinterpret_cast<const int4*>(data + base + 4);
+            v[s][0] = a.x; v[s][1] = a.y; v[s][2] = a.z; v[s][3] = a.w; v[s][4] = c.x; v[s][5] = c.y; v[s][6] = c.z; v[s][7] = c.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < kScanItems; e++) { const int32_t i = base + e, t = data[i < room ? i : room - 1]; v[s][e] = i < room ? t : 0; }
+        }
+    }
+    int32_t run[kScanSubs], x[kScanSubs];
+#pragma unroll
+    for (int s = 0; s < kScanSubs; s++) {
+        int32_t r = 0;
+#pragma unroll
+        for (int e = 0; e < kScanItems; e++) { r += v[s][e]; v[s][e] = r; }
+        run[s] = x[s] = r;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+#pragma unroll
+        for (int s = 0; s < kScanSubs; s++) { const int32_t t = __shfl_up(x[s], o); if (lane >= o) x[s] += t; }
+    }
+    if (lane == 63) {
+#pragma unroll
+        for (int s = 0; s < kScanSubs; s++) wsum[s * kScanWaves + wave] = x[s];
+    }
+    __syncthreads();
+    int32_t pre = 0, front[kScanSubs];
+#pragma unroll
+    for (int s = 0; s < kScanSubs; s++) {
+#pragma unroll
+        for (int w = 0; w < kScanWaves; w++) { if (w == wave) front[s] = pre; pre += wsum[s * kScanWaves + w]; }
+    }
+    int32_t seen = 0;
+    if (tid == 0) seen = atomicExch(total, pre);
+#pragma unroll
+    for (int s = 0; s < kScanSubs; s++) {
+        const int32_t base = s * kScanSub + tid * kScanItems;
+        const int32_t excl = front[s] + x[s] - run[s];
+        if (Whole) {
+            *reinterpret_cast<int4*>(data + base) = make_int4(v[s][0] + excl, v[s][1] + excl, v[s][2] + excl, v[s][3] + excl);
+            *reinterpret_cast<int4*>(data + base + 4) = make_int4(v[s][4] + excl, v[s][5] + excl, v[s][6] + excl, v[s][7] + excl);
+        } else {
+#pragma unroll
+            for (int e = 0; e < kScanItems; e++) if (base + e < room) data[base + e] = v[s][e] + excl;
+        }
+    }
+    return seen;
+}
+
 // ONE launch per contig: an inclusive scan inside each tile of 8192 elements, and the workgroup that finishes last turns the tile totals
 // into exclusive offsets in place.  The depths are left tile-local; depth_query_tiled adds a position's tile offset when it
-// reads it -- no third pass over the contig.  Totals travel through returning agent-scope atomics (written and read back
-// on the same path, no fence: im_triage.hip uses the same hand-over); sums[tiles] is the arrival counter, zero between launches.
+// reads it -- no third pass over the contig.  No workgroup waits for another: the one that arrives last does the extra work, every
+// other one leaves.  Totals travel through returning agent-scope atomics (written and read back on the same path, no fence:
+// im_triage.hip uses the same hand-over).  The arrival counters (sums[tiles] for the groups, then one per group) are zero between
+// launches: they count with a wrapping increment, so the arrival that completes a count also puts the word back to zero and
+// nothing is left to reset.  A tile's chain is its total, then its group's count; the tile that completes a group adds the groups' count.
 __global__ __launch_bounds__(kScanBlock) void depth_scan_tiled_kernel(int32_t* __restrict__ data, int64_t n, int32_t* __restrict__ sums, int32_t tiles)
 {
-    __shared__ int32_t wsum[kScanBlock / 64];
-    __shared__ int32_t s_last, carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)tid * kScanItems;
-    int32_t v[kScanItems];
-    int32_t run = 0;
-    static_assert(kScanItems == 8, "a thread's eight items travel as two 16-byte accesses");
-    const bool whole = base + kScanItems <= n;          // the contig's run starts on a 256-byte boundary: base is 32-byte aligned
-    if (whole) {
-        const int4 a = *reinterpret_cast<const int4*>(data + base), c = *reinterpret_cast<const int4*>(data + base + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < kScanItems; e++) { const int64_t i = base + e; v[e] = (i < n) ? data[i] : 0; }
-    }
-#pragma unroll
-    for (int e = 0; e < kScanItems; e++) { run += v[e]; v[e] = run; }
-    int32_t x = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { int32_t t = __shfl_up(x, o); if (lane >= o) x += t; }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int32_t woff = 0;
-    for (int w = 0; w < wave; w++) woff += wsum[w];
-    const int32_t excl = woff + x - run;
-    if (whole) {
-        *reinterpret_cast<int4*>(data + base) = make_int4(v[0] + excl, v[1] + excl, v[2] + excl, v[3] + excl);
-        *reinterpret_cast<int4*>(data + base + 4) = make_int4(v[4] + excl, v[5] + excl, v[6] + excl, v[7] + excl);
-    } else {
-#pragma unroll
-        for (int e = 0; e < kScanItems; e++) { const int64_t i = base + e; if (i < n) data[i] = v[e] + excl; }
-    }
-    if (tid == kScanBlock - 1) {
-        const int32_t seen = atomicExch(&sums[blockIdx.x], woff + x);
+    __shared__ int32_t wsum[kScanSubs * kScanWaves];
+    __shared__ int32_t osum[2][kScanWaves];
+    __shared__ int32_t s_last;
+    const int tid = threadIdx.x;
+    const int64_t tile0 = (int64_t)blockIdx.x * kScanTile;
+    const int32_t seen = tile0 + kScanTile <= n ? scan_tile<true>(data, n, tile0, wsum, tid, &sums[blockIdx.x])
+                                                : scan_tile<false>(data, n, tile0, wsum, tid, &sums[blockIdx.x]);
+    if (tid == 0) {
         asm volatile("" :: "v"(seen));                  // the total is in before this workgroup is counted
         // counted in two levels -- a group of kScanGroup tiles, then the groups: same-address atomics are served one after the
         // other (~9 ns each: 7 us of the 6.25 Mb contig's launch when every tile counted into one word, im_triage.hip has the measurement)
         const int32_t g = (int32_t)blockIdx.x / kScanGroup, groups = (tiles + kScanGroup - 1) / kScanGroup;
-        const int32_t g_n = min(kScanGroup, tiles - g * kScanGroup);
-        int32_t last = 0;
-        if (atomicAdd(&sums[tiles + 1 + g], 1) == g_n - 1) {
-            atomicExch(&sums[tiles + 1 + g], 0);        // ready for the next launch
-            last = atomicAdd(&sums[tiles], 1) == groups - 1 ? 1 : 0;
-        }
-        s_last = last;
-        carry_s = 0;
+        const uint32_t g_n = (uint32_t)min(kScanGroup, tiles - g * kScanGroup);
+        bool last = atomicInc(reinterpret_cast<uint32_t*>(&sums[tiles + 1 + g]), g_n - 1u) == g_n - 1u;
+        if (last && groups > 1) last = atomicInc(reinterpret_cast<uint32_t*>(&sums[tiles]), (uint32_t)groups - 1u) == (uint32_t)groups - 1u;
+        s_last = last ? 1 : 0;
     }
     __syncthreads();
     if (!s_last) return;
-    for (int32_t b0 = 0; b0 < tiles; b0 += kScanBlock) {
-        const int32_t j = b0 + tid;
-        const int32_t t = j < tiles ? atomicAdd(&sums[j], 0) : 0;
-        int32_t y = t;
+    // the offset pass: kScanBlock * kOffItems tiles a round, one barrier a round (the waves' sums alternate between two rows of
+    // osum; the running offset stays in registers).  The totals are read with agent-scope atomic loads, behind the barrier that
+    // follows the last count's return -- the instruction an atomicAdd(p, 0) becomes -- all of a round in flight at once and
+    // no branch around any of them (a clamped index instead).
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int32_t carry = 0;
+    for (int32_t b0 = 0, row = 0; b0 < tiles; b0 += kScanBlock * kOffItems, row ^= 1) {
+        const int32_t j0 = b0 + tid * kOffItems;
+        int32_t t[kOffItems];
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { int32_t u = __shfl_up(y, o); if (lane >= o) y += u; }
-        if (lane == 63) wsum[wave] = y;
+        for (int k = 0; k < kOffItems; k++) {
+            const int32_t j = j0 + k, u = __hip_atomic_load(&sums[j < tiles ? j : tiles - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            t[k] = j < tiles ? u : 0;
+        }
+        int32_t r = 0;
+#pragma unroll
+        for (int k = 0; k < kOffItems; k++) { const int32_t u = t[k]; t[k] = r; r += u; }
+        int32_t y = r;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int32_t u = __shfl_up(y, o); if (lane >= o) y += u; }
+        if (lane == 63) osum[row][wave] = y;
         __syncthreads();
-        int32_t wo = 0;
-        for (int w = 0; w < wave; w++) wo += wsum[w];
-        const int32_t carry = carry_s;
-        if (j < tiles) sums[j] = carry + wo + y - t;
-        __syncthreads();
-        if (tid == kScanBlock - 1) carry_s = carry + wo + y;
-        __syncthreads();
+        int32_t front = carry;
+#pragma unroll
+        for (int w = 0; w < kScanWaves; w++) { if (w == wave) front = carry; carry += osum[row][w]; }
+        const int32_t excl = front + y - r;
+#pragma unroll
+        for (int k = 0; k < kOffItems; k++) if (j0 + k < tiles) sums[j0 + k] = excl + t[k];
     }
-    if (tid == 0) sums[tiles] = 0;
 }
 
 __global__ __launch_bounds__(256) void depth_query_tiled_kernel(int32_t nq, const int32_t* __restrict__ beg, const int32_t* __restrict__ end,
