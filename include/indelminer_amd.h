@@ -184,6 +184,12 @@ int im_cluster_sr(im_ctx* ctx, int32_t n,
 int im_depth_build(im_ctx* ctx, int64_t contig_len, int32_t n_seg,
                    const int32_t* seg_start, const int32_t* seg_len);
 int im_depth_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out);
+/* Seam 3's order statistic (no reference counterpart: calculate_cov_params only ever sums, src/shared.c:178-212), over what
+ * im_depth_build left.  Per query [beg, end), clipped to [0, contig_len), the LOWER MEDIAN of the depths of its n positions: the
+ * smallest d such that at least (n + 1) / 2 of them have depth <= d.  A position with depth >= 4095 counts as 4095 -- the
+ * median saturates there.  A query that is empty after the clip (beg >= end included) answers 0xFFFFFFFF.  Exact for an
+ * interval of any length; one launch and one wait per call.  IM_E_ARG before im_depth_build, like im_depth_query. */
+int im_depth_median(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* med_out);
 
 /* ---- seam 4: annotate mode, "is this known indel supported by this read?" ------- */
 
@@ -473,6 +479,10 @@ int im_depth_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, 
  * once 8000 are buffered (src/samtools-0.1.19/bam_pileup.c:172,244): the host driver asks the file, with that rule, about the queries
  * whose maximum says the rule may have applied. */
 int im_depth_query_max_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out, uint32_t* max_out);
+/* im_depth_median over contig tid's run of the genome-wide array, behind im_depth_scan: the lower median of min(depth, 4095)
+ * over [beg, end) clipped to the contig, 0xFFFFFFFF for a query that is empty after the clip (the same definition, the same
+ * saturation).  Like the sum, it counts every record -- samtools' 8000-record pileup cap does not apply to it. */
+int im_depth_median_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* med_out);
 /* Multi-GPU, pieces of one contig walked by several ranks: every rank's difference array holds the +-1 of the records IT
  * delivered; their sum (one RCCL all-reduce over the whole array, before any im_depth_scan) is the single run's array.  The
  * reference has no counterpart (calculate_cov_params re-reads the file per variant, src/shared.c:178-212).  Synchronous. */

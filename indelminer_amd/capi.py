@@ -146,6 +146,7 @@ def lib():
         L.im_comm_last_error.restype = C.c_char_p
         L.im_depth_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.im_depth_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_depth_median.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_support_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_support_count.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -207,6 +208,7 @@ def lib():
         L.im_depth_scan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.im_depth_reset.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.im_depth_query_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_depth_median_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_span_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.im_dev_span_scatter.argtypes = [C.c_void_p, C.POINTER(DevRecords), C.c_void_p]
         L.im_span_scan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
@@ -444,6 +446,10 @@ class Context:
     def depth_query(self, beg, end):
         return self._query(lib().im_depth_query, beg, end)
 
+    def depth_median(self, beg, end):
+        """per query the lower median of min(depth, 4095) over [beg, end); 0xFFFFFFFF for an interval that is empty after the clip"""
+        return self._query(lib().im_depth_median, beg, end)
+
     def support_batch(self, targets, queries):
         """targets / queries: lists of bytes.  Returns int32 [n,4]: subs, indels, aligned, status."""
         n = len(targets)
@@ -482,6 +488,10 @@ class Context:
 
     def depth_query_tid(self, tid, beg, end):
         return self._query_tid(lib().im_depth_query_tid, tid, beg, end)
+
+    def depth_median_tid(self, tid, beg, end):
+        """depth_median over contig tid's run of the genome-wide array (after depth_scan)"""
+        return self._query_tid(lib().im_depth_median_tid, tid, beg, end)
 
     def span_enable(self, flank, min_mapq):
         """the genome-wide array of reference-spanning read counts (the genotype columns), 4 bytes per reference base"""

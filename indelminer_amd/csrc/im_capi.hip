@@ -59,6 +59,11 @@ struct im_ctx {
     int64_t ref_total = 0;
     // genome-wide depth / difference array, reference-spanning counts and concordant-pair counts
     GenomeArray all_depth, all_span, all_pair;
+    // the median queries' histograms of queries of several slabs (im::launch_depth_median): zeros between calls, sized by the call that
+    // needed the most; med_dirty: a call did not get to its end, the next one clears them
+    uint32_t* med_scratch = nullptr;
+    int32_t med_slots = 0;
+    bool med_dirty = false;
     bool support_count_attr = false;    // im_support_count: its kernel's LDS attribute has been set on this context's device
     std::mutex gb_mu;
     std::unordered_map<void*, int32_t> gb_layout;   // group-by scratch -> the slot count it was initialised (and is carved) for
@@ -186,12 +191,75 @@ int build_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* family, int
     return IM_OK;
 }
 
-// the queries' trip through the context's workspace and stream, n > 0: [beg][end] in, one launch on a scanned array, out back.
-// minimum: the span query (out = the minimum over [beg, end]); otherwise the depth query (out = the sum over [beg, end), and
-// max_out, where not null, the deepest position of [beg - 1, end])
-int query_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, const int32_t* data, const int32_t* sums, int64_t clen,
-                bool minimum, uint32_t* out, uint32_t* max_out)
+// what a query answers per interval: the sum over [beg, end) (the depth query; max_out, where not null, the deepest position of
+// [beg - 1, end]), the minimum over [beg, end] (the span queries), or the lower median over [beg, end) of the values capped at 4095
+enum Reduce { kSum, kMinimum, kMedian };
+
+// the median's trip, n > 0: [beg][end][first][slot] in, one launch (one per kMedMaxSlots queries of several slabs), out back, one wait.
+// The answers of queries that are empty after the clip are set here.  The call that needs more histograms than any before it
+// pays for them here (free, allocate, clear: at most 16 MB), under whatever lock the caller holds around its queries.
+int median_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, const int32_t* data, const int32_t* sums, int64_t clen,
+                 uint32_t* out)
 {
+    constexpr int32_t kMedMaxSlots = 1024;                  // 16 MB of histograms at the most
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<int32_t> first((size_t)n + 1), slot((size_t)n, -1), cut;      // cut: the queries at which a launch starts
+    int64_t items = 0;
+    int32_t used = 0, most = 0;
+    cut.push_back(0);
+    for (int32_t q = 0; q < n; q++) {
+        const int32_t s = im::depth_median_slabs(beg[q], end[q], clen);
+        first[q] = (int32_t)items;
+        items += s;
+        if (items > 0x7fffffff) { set_err(ctx, "median query: more than 2^31 slabs in one call"); return IM_E_ARG; }
+        if (s > 1) {
+            if (used == kMedMaxSlots) { cut.push_back(q); used = 0; }
+            slot[q] = used++;
+            if (used > most) most = used;
+        }
+    }
+    first[n] = (int32_t)items;
+    cut.push_back(n);
+    if (most > ctx->med_slots) {
+        if (ctx->med_scratch) { HIP_TRY(ctx, hipFree(ctx->med_scratch)); ctx->med_scratch = nullptr; ctx->med_slots = 0; }
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->med_scratch, im::depth_median_scratch_bytes(most)));
+        ctx->med_slots = most;
+        ctx->med_dirty = true;
+    }
+    if (ctx->med_dirty && ctx->med_scratch) HIP_TRY(ctx, hipMemsetAsync(ctx->med_scratch, 0, im::depth_median_scratch_bytes(ctx->med_slots), ctx->stream));
+    const size_t sb = up256(sizeof(int32_t) * ((size_t)n + 1));
+    int rc = ensure_ws(ctx, 5 * sb);
+    if (rc) return rc;
+    int32_t* d_beg = (int32_t*)ctx->ws;
+    int32_t* d_end = (int32_t*)((char*)ctx->ws + sb);
+    int32_t* d_first = (int32_t*)((char*)ctx->ws + 2 * sb);
+    int32_t* d_slot = (int32_t*)((char*)ctx->ws + 3 * sb);
+    uint32_t* d_out = (uint32_t*)((char*)ctx->ws + 4 * sb);
+    if (items > 0) {
+        ctx->med_dirty = true;
+        HIP_TRY(ctx, hipMemcpyAsync(d_beg, beg, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_end, end, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_first, first.data(), sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_slot, slot.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        for (size_t k = 0; k + 1 < cut.size(); k++) {
+            const int32_t q0 = cut[k], q1 = cut[k + 1];
+            HIP_TRY(ctx, im::launch_depth_median(q1 - q0, first[q1] - first[q0], d_beg + q0, d_end + q0, d_first + q0, d_slot + q0, data, sums, clen,
+                                                 ctx->med_scratch, ctx->med_slots, 8 * (ctx->n_cu > 0 ? ctx->n_cu : 256), d_out + q0, ctx->stream));
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(out, d_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->med_dirty = false;
+    for (int32_t q = 0; q < n; q++) if (first[q + 1] == first[q]) out[q] = 0xFFFFFFFFu;
+    return IM_OK;
+}
+
+// the queries' trip through the context's workspace and stream, n > 0: [beg][end] in, one launch on a scanned array, out back
+int query_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, const int32_t* data, const int32_t* sums, int64_t clen,
+                Reduce what, uint32_t* out, uint32_t* max_out)
+{
+    if (what == kMedian) return median_array(ctx, n, beg, end, data, sums, clen, out);     // max_out belongs to the sum alone: not looked at
+    const bool minimum = what == kMinimum;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t sb = up256(sizeof(int32_t) * (size_t)n);
     int rc = ensure_ws(ctx, 4 * sb);
@@ -210,8 +278,8 @@ int query_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, 
     return IM_OK;
 }
 
-// im_depth_query / im_span_query / im_pairspan_query
-int query_contig_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* family, int32_t n, const int32_t* beg, const int32_t* end, bool minimum,
+// im_depth_query / im_depth_median / im_span_query / im_pairspan_query
+int query_contig_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* family, int32_t n, const int32_t* beg, const int32_t* end, Reduce what,
                        uint32_t* out)
 {
     if (!ctx || n < 0) return IM_E_ARG;
@@ -219,7 +287,7 @@ int query_contig_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* fami
     if (a.len < 0) { set_err(ctx, "%s_build has not been called", family); return IM_E_ARG; }
     if (n == 0) return IM_OK;
     if (!beg || !end || !out) return IM_E_ARG;
-    return query_array(ctx, n, beg, end, a.data, a.sums, a.len, minimum, out, nullptr);
+    return query_array(ctx, n, beg, end, a.data, a.sums, a.len, what, out, nullptr);
 }
 
 // im_depth_enable / im_span_enable / im_pairspan_enable: a genome-wide array and its sums, zeroed.  Each contig has its own run of sums (scans of
@@ -267,15 +335,15 @@ int reset_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, voi
     return IM_OK;
 }
 
-// im_depth_query_max_tid / im_span_query_tid / im_pairspan_query_tid
-int query_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, bool minimum,
+// im_depth_query_max_tid / im_depth_median_tid / im_span_query_tid / im_pairspan_query_tid
+int query_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, Reduce what,
                        uint32_t* out, uint32_t* max_out)
 {
     if (!ctx || n < 0 || !(ctx->*which).data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
     if (n == 0) return IM_OK;
     if (!beg || !end || !out) return IM_E_ARG;
     const GenomeArray& g = ctx->*which;
-    return query_array(ctx, n, beg, end, g.data + ctx->h_asc_off[tid], g.sums + ctx->h_sums_off[tid], ctx->h_len[tid], minimum, out, max_out);
+    return query_array(ctx, n, beg, end, g.data + ctx->h_asc_off[tid], g.sums + ctx->h_sums_off[tid], ctx->h_len[tid], what, out, max_out);
 }
 
 im::RefDev ref_dev(const im_ctx* ctx)
@@ -328,6 +396,7 @@ void im_ctx_destroy(im_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     free_reference(ctx);
     if (ctx->ws) (void)hipFree(ctx->ws);
+    if (ctx->med_scratch) (void)hipFree(ctx->med_scratch);
     free_array(ctx->depth);
     free_array(ctx->span);
     free_array(ctx->pair);
@@ -702,10 +771,13 @@ int im_depth_allreduce(im_ctx* ctx, im_comm* comm)
 }
 
 int im_depth_query_max_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out, uint32_t* max_out)
-{ return query_genome_array(ctx, &im_ctx::all_depth, tid, n, beg, end, false, sum_out, max_out); }
+{ return query_genome_array(ctx, &im_ctx::all_depth, tid, n, beg, end, kSum, sum_out, max_out); }
 
 int im_depth_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out)
 { return im_depth_query_max_tid(ctx, tid, n, beg, end, sum_out, nullptr); }
+
+int im_depth_median_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* med_out)
+{ return query_genome_array(ctx, &im_ctx::all_depth, tid, n, beg, end, kMedian, med_out, nullptr); }
 
 // Host-buffer entry point.  The batch is cut into chunks that travel through a two-slot pipeline: chunk c is
 // packed into PINNED staging memory and copied in on one copy stream while chunk c-1 runs on the compute stream
@@ -825,7 +897,10 @@ int im_depth_build(im_ctx* ctx, int64_t contig_len, int32_t n_seg, const int32_t
 { return build_array(ctx, &im_ctx::depth, "im_depth", contig_len, n_seg, seg_start, seg_len, nullptr); }
 
 int im_depth_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out)
-{ return query_contig_array(ctx, &im_ctx::depth, "im_depth", n, beg, end, false, sum_out); }
+{ return query_contig_array(ctx, &im_ctx::depth, "im_depth", n, beg, end, kSum, sum_out); }
+
+int im_depth_median(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* med_out)
+{ return query_contig_array(ctx, &im_ctx::depth, "im_depth", n, beg, end, kMedian, med_out); }
 
 // ---- reference-spanning read counts (the genotype columns) ------------------------------------
 
@@ -846,13 +921,13 @@ int im_span_scan(im_ctx* ctx, int32_t tid, void* stream) { return scan_genome_ar
 int im_span_reset(im_ctx* ctx, int32_t tid, void* stream) { return reset_genome_array(ctx, &im_ctx::all_span, tid, stream); }
 
 int im_span_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
-{ return query_genome_array(ctx, &im_ctx::all_span, tid, n, beg, end, true, min_out, nullptr); }
+{ return query_genome_array(ctx, &im_ctx::all_span, tid, n, beg, end, kMinimum, min_out, nullptr); }
 
 int im_span_build(im_ctx* ctx, int64_t contig_len, int32_t n_run, const int32_t* run_start, const int32_t* run_len, int32_t flank)
 { return build_array(ctx, &im_ctx::span, "im_span", contig_len, n_run, run_start, run_len, &flank); }
 
 int im_span_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
-{ return query_contig_array(ctx, &im_ctx::span, "im_span", n, beg, end, true, min_out); }
+{ return query_contig_array(ctx, &im_ctx::span, "im_span", n, beg, end, kMinimum, min_out); }
 
 // ---- concordant-pair counts (the genotype columns of PAIRED_READ records) ----------------------
 
@@ -874,13 +949,13 @@ int im_pairspan_scan(im_ctx* ctx, int32_t tid, void* stream) { return scan_genom
 int im_pairspan_reset(im_ctx* ctx, int32_t tid, void* stream) { return reset_genome_array(ctx, &im_ctx::all_pair, tid, stream); }
 
 int im_pairspan_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
-{ return query_genome_array(ctx, &im_ctx::all_pair, tid, n, beg, end, true, min_out, nullptr); }
+{ return query_genome_array(ctx, &im_ctx::all_pair, tid, n, beg, end, kMinimum, min_out, nullptr); }
 
 int im_pairspan_build(im_ctx* ctx, int64_t contig_len, int32_t n_frag, const int32_t* frag_start, const int32_t* frag_len, int32_t flank)
 { return build_array(ctx, &im_ctx::pair, "im_pairspan", contig_len, n_frag, frag_start, frag_len, &flank); }
 
 int im_pairspan_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
-{ return query_contig_array(ctx, &im_ctx::pair, "im_pairspan", n, beg, end, true, min_out); }
+{ return query_contig_array(ctx, &im_ctx::pair, "im_pairspan", n, beg, end, kMinimum, min_out); }
 
 int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64_t* t_off,
                      const uint8_t* queries, const int64_t* q_off, int32_t* out)

@@ -199,6 +199,159 @@ __global__ __launch_bounds__(256) void depth_query_tiled_kernel(int32_t nq, cons
     }
 }
 
+// ---- the median of a scanned array over an interval (im_depth_median, im_depth_median_tid) ----------------------------------
+// Lower median of v[p] = min(data[p] + sums[p / kScanTile], kMedBins - 1) over the positions of [beg, end) clipped to [0, clen):
+// the smallest d with at least (n + 1) / 2 of the n positions at v <= d.  By histogram: kMedBins counters of 32 bits in LDS.
+// An interval is cut into slabs of kMedSlab positions from its first position rounded down to a multiple of 4 (so that every lane's
+// four positions are one 16-byte access and lie in one scan tile); a slab is one work item of a workgroup of 256 lanes, the
+// work items of a call are numbered query by query (first[q] .. first[q + 1]) and the workgroups take them grid-stride.
+//   one slab      the workgroup picks the median from its LDS histogram and is done
+//   several       every slab adds its non-zero bins to the query's histogram in device memory (g_hist, returning agent-scope
+//                 atomics, every access to that memory is one) and counts its arrival with a wrapping increment; the slab that
+//                 arrives last takes the bins out with exchanges against zero and picks.  Bins and counter are zero again
+//                 behind it: nothing to reset between calls.  Order: every lane consumes the returns of its adds, a barrier,
+//                 then lane 0 counts behind an agent-scope release fence; the last arriver passes an acquire fence before its
+//                 lanes read.  depth_scan_tiled_kernel relies on the consumed returns alone; here the fences make the pairing
+//                 formal, so it does not hang on where the compiler places a wait (about 2 us per slab of such a query).
+// LDS form: a lane folds the equal neighbours among its four consecutive positions into one ds_add of the run's length (depth
+// moves at read ends only: most quads are one run, a quarter of the atomics), and nothing is combined across lanes.  A wave-wide
+// combination would need a 64-lane match per instruction, which gfx950 has no instruction for; neither form has been measured.
+constexpr int kMedBins = 4096;
+constexpr int kMedSlab = 4 * kScanTile;                     // positions of a slab: 128 KB of the array
+constexpr int kMedBlock = 256;
+constexpr int kMedAhead = 4;                                // 16-byte loads a lane has in flight in front of the LDS atomics
+constexpr int kMedSegs = kMedBins / (kMedBlock * 4);        // a lane holds 4 consecutive bins of each of these segments of the histogram
+constexpr int kMedWaves = kMedBlock / 64;
+constexpr int kMedTiles = kMedSlab / kScanTile + 1;         // scan tiles a slab can touch (it starts anywhere in one)
+static_assert(kMedSegs * kMedBlock * 4 == kMedBins && kMedSlab % kScanTile == 0 && kMedSlab % (4 * kMedBlock * kMedAhead) == 0, "");
+
+__device__ __forceinline__ uint32_t med_bin(int32_t v) { return min((uint32_t)v, (uint32_t)(kMedBins - 1)); }
+
+// four consecutive positions into the histogram: one add per run of equal values
+__device__ __forceinline__ void med_add_quad(uint32_t* hist, const int4 v, int32_t off)
+{
+    const uint32_t d0 = med_bin(v.x + off), d1 = med_bin(v.y + off), d2 = med_bin(v.z + off), d3 = med_bin(v.w + off);
+    uint32_t run = 1;
+    if (d1 == d0) run++; else { atomicAdd(&hist[d0], run); run = 1; }
+    if (d2 == d1) run++; else { atomicAdd(&hist[d1], run); run = 1; }
+    if (d3 == d2) run++; else { atomicAdd(&hist[d2], run); run = 1; }
+    atomicAdd(&hist[d3], run);
+}
+
+__global__ __launch_bounds__(kMedBlock) void depth_median_kernel(int32_t nq, const int32_t* __restrict__ beg, const int32_t* __restrict__ end,
+                                                                 const int32_t* __restrict__ first, const int32_t* __restrict__ slot,
+                                                                 const int32_t* __restrict__ data, const int32_t* __restrict__ sums, int64_t clen,
+                                                                 uint32_t* __restrict__ g_hist, uint32_t* __restrict__ g_count, uint32_t* __restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t hist[kMedBins];
+    __shared__ int32_t s_tsum[kMedTiles];
+    __shared__ uint32_t wsum[kMedSegs * kMedWaves];
+    __shared__ int32_t s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll
+    for (int s = 0; s < kMedSegs; s++) reinterpret_cast<uint4*>(hist)[s * kMedBlock + tid] = make_uint4(0, 0, 0, 0);
+    const int32_t w_first = first[0], items = first[nq] - w_first;
+    for (int32_t w = blockIdx.x; w < items; w += gridDim.x) {
+        // the query of this work item: first[q] <= w_first + w < first[q + 1] (queries without positions have no items)
+        const int32_t wabs = w_first + w;
+        int32_t q = 0;
+        for (int32_t hi = nq; hi - q > 1;) { const int32_t mid = (q + hi) >> 1; if (first[mid] <= wabs) q = mid; else hi = mid; }
+        int64_t a = beg[q], b = end[q];
+        if (a < 0) a = 0;
+        if (b > clen) b = clen;                                     // a < b: the query has items
+        const int32_t nslab = first[q + 1] - first[q];
+        const int64_t s0 = (a & ~(int64_t)3) + (int64_t)(wabs - first[q]) * kMedSlab;       // a multiple of 4
+        const int64_t s1 = s0 + kMedSlab < b ? s0 + kMedSlab : b, lo = a > s0 ? a : s0;     // the slab's positions are [lo, s1)
+        const int32_t r0 = (int32_t)(s0 % kScanTile);
+        if (tid < kMedTiles) { const int64_t t = s0 / kScanTile + tid, tl = (b - 1) / kScanTile; s_tsum[tid] = sums[t < tl ? t : tl]; }
+        __syncthreads();                                            // the tile offsets are in, the histogram is zero
+        const int32_t* __restrict__ base = data + s0;               // 32-bit offsets from a uniform base from here on
+        // whole quads [body_lo, body_hi) of the slab, kMedAhead 16-byte loads of a lane issued before the first is consumed; a
+        // clamped index instead of a branch around a load
+        const int32_t body_lo = (int32_t)(((lo + 3) & ~(int64_t)3) - s0), body_hi = (int32_t)(s1 - s0) & ~3;
+        const int32_t nquad = body_hi > body_lo ? (body_hi - body_lo) >> 2 : 0;
+        for (int32_t i0 = 0; i0 < nquad; i0 += kMedBlock * kMedAhead) {
+            int4 v[kMedAhead];
+            int32_t off[kMedAhead];
+#pragma unroll
+            for (int k = 0; k < kMedAhead; k++) {
+                const int32_t i = i0 + k * kMedBlock + tid, o = body_lo + 4 * (i < nquad ? i : nquad - 1);
+                v[k] = *reinterpret_cast<const int4*>(base + o);
+                off[k] = s_tsum[(r0 + o) / kScanTile];
+            }
+#pragma unroll
+            for (int k = 0; k < kMedAhead; k++) if (i0 + k * kMedBlock + tid < nquad) med_add_quad(hist, v[k], off[k]);
+        }
+        // the positions in front of the first whole quad (lanes 0..3) and behind the last (lanes 4..7), one each
+        if (tid < 8) {
+            const int32_t o = tid < 4 ? body_lo - 4 + tid : (body_hi > body_lo ? body_hi : body_lo) + tid - 4;
+            const int64_t p = s0 + o, stop = tid < 4 && s0 + body_lo < s1 ? s0 + body_lo : s1;
+            if (p >= lo && p < stop) atomicAdd(&hist[med_bin(base[o] + s_tsum[(r0 + o) / kScanTile])], 1u);
+        }
+        __syncthreads();                                            // the slab's histogram is complete
+        uint32_t c[kMedSegs][4];
+#pragma unroll
+        for (int s = 0; s < kMedSegs; s++) {
+            const uint4 t = reinterpret_cast<const uint4*>(hist)[s * kMedBlock + tid];
+            reinterpret_cast<uint4*>(hist)[s * kMedBlock + tid] = make_uint4(0, 0, 0, 0);       // for the next work item
+            c[s][0] = t.x; c[s][1] = t.y; c[s][2] = t.z; c[s][3] = t.w;
+        }
+        if (nslab > 1) {
+            uint32_t* __restrict__ gh = g_hist + (size_t)slot[q] * kMedBins;
+            uint32_t seen = 0;
+#pragma unroll
+            for (int s = 0; s < kMedSegs; s++) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) if (c[s][e]) seen |= atomicAdd(&gh[(s * kMedBlock + tid) * 4 + e], c[s][e]);
+            }
+            asm volatile("" :: "v"(seen));                          // this lane's adds are in before the barrier in front of the count
+            __syncthreads();
+            if (tid == 0) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // the workgroup's adds happen before its count ...
+                const bool last = atomicInc(&g_count[slot[q]], (uint32_t)nslab - 1u) == (uint32_t)nslab - 1u;
+                if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // ... and every count before the last arriver's reads
+                s_last = last ? 1 : 0;
+            }
+            __syncthreads();
+            if (!s_last) continue;                                  // uniform: every lane reads the same word
+#pragma unroll
+            for (int s = 0; s < kMedSegs; s++) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) c[s][e] = atomicExch(&gh[(s * kMedBlock + tid) * 4 + e], 0u);
+            }
+        }
+        // the pick: bins in the order segment, lane, element; a wave scan per segment, the waves' totals meet in LDS behind one barrier
+        uint32_t run[kMedSegs], x[kMedSegs];
+#pragma unroll
+        for (int s = 0; s < kMedSegs; s++) run[s] = x[s] = c[s][0] + c[s][1] + c[s][2] + c[s][3];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+#pragma unroll
+            for (int s = 0; s < kMedSegs; s++) { const uint32_t t = (uint32_t)__shfl_up((int)x[s], o); if (lane >= o) x[s] += t; }
+        }
+        if (lane == 63) {
+#pragma unroll
+            for (int s = 0; s < kMedSegs; s++) wsum[s * kMedWaves + wave] = x[s];
+        }
+        __syncthreads();
+        const uint32_t want = (uint32_t)((b - a + 1) / 2);          // 1 <= want <= b - a = the sum of all bins: exactly one bin is the answer
+        uint32_t pre = 0;
+#pragma unroll
+        for (int s = 0; s < kMedSegs; s++) {
+            uint32_t front = 0;
+#pragma unroll
+            for (int k = 0; k < kMedWaves; k++) { if (k == wave) front = pre; pre += wsum[s * kMedWaves + k]; }
+            uint32_t acc = front + x[s] - run[s];
+            if (acc < want && want <= acc + run[s]) {
+                int e = 0;
+                for (; e < 3; e++) { acc += c[s][e]; if (acc >= want) break; }
+                out[q] = (uint32_t)((s * kMedBlock + tid) * 4 + e);
+            }
+        }
+        // wsum is read above and written behind the next work item's two barriers; s_tsum and s_last likewise
+    }
+}
+
 }  // namespace
 
 int64_t depth_sums_ints(int64_t clen) { const int64_t t = (clen + 1 + kScanTile - 1) / kScanTile; return t + 1 + (t + kScanGroup - 1) / kScanGroup; }
@@ -237,6 +390,32 @@ hipError_t launch_depth_query_tiled(int32_t nq, const int32_t* beg, const int32_
     int b = (nq + 3) / 4;
     if (b > 2048) b = 2048;
     hipLaunchKernelGGL(depth_query_tiled_kernel, dim3(b), dim3(256), 0, stream, nq, beg, end, depth, sums, clen, out, out_max);
+    return hipGetLastError();
+}
+
+// slabs (work items of depth_median_kernel) of the query [beg, end) of a contig of clen positions: 0 iff it is empty after the clip
+int32_t depth_median_slabs(int32_t beg, int32_t end, int64_t clen)
+{
+    int64_t a = beg, b = end;
+    if (a < 0) a = 0;
+    if (b > clen) b = clen;
+    if (a >= b) return 0;
+    return (int32_t)((b - (a & ~(int64_t)3) + kMedSlab - 1) / kMedSlab);
+}
+
+size_t depth_median_scratch_bytes(int32_t slots) { return (size_t)slots * (kMedBins + 1) * sizeof(uint32_t); }
+
+// nq queries of one contig whose work items are first[0] .. first[nq] (first[q + 1] - first[q] = depth_median_slabs of query q); slot[q]:
+// which histogram of scratch a query of several slabs adds into (distinct, < slots; unused for the others).  scratch holds
+// depth_median_scratch_bytes(slots) of zeros and is left that way.  out[q] is written for every query that has positions.
+hipError_t launch_depth_median(int32_t nq, int32_t items, const int32_t* beg, const int32_t* end, const int32_t* first, const int32_t* slot,
+                               const int32_t* data, const int32_t* sums, int64_t clen, uint32_t* scratch, int32_t slots, int32_t max_blocks,
+                               uint32_t* out, hipStream_t stream)
+{
+    if (nq <= 0 || items <= 0) return hipSuccess;
+    const int b = items < max_blocks ? items : max_blocks;
+    hipLaunchKernelGGL(depth_median_kernel, dim3(b), dim3(kMedBlock), 0, stream, nq, beg, end, first, slot, data, sums, clen,
+                       scratch, scratch + (size_t)slots * kMedBins, out);
     return hipGetLastError();
 }
 

@@ -86,6 +86,12 @@ hipError_t launch_depth_build(int64_t clen, int32_t n_seg, const int32_t* seg_st
 // sum over [beg, end); out_max (may be null): the deepest position of [beg - 1, end]
 hipError_t launch_depth_query_tiled(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* depth, const int32_t* sums,
                                     int64_t clen, uint32_t* out, uint32_t* out_max, hipStream_t stream);
+// lower median over [beg, end) of min(value, 4095), by histogram: one launch; im_depth.hip has the work items, the scratch and the rule
+int32_t depth_median_slabs(int32_t beg, int32_t end, int64_t clen);
+size_t depth_median_scratch_bytes(int32_t slots);
+hipError_t launch_depth_median(int32_t nq, int32_t items, const int32_t* beg, const int32_t* end, const int32_t* first, const int32_t* slot,
+                               const int32_t* data, const int32_t* sums, int64_t clen, uint32_t* scratch, int32_t slots, int32_t max_blocks,
+                               uint32_t* out, hipStream_t stream);
 
 // im_realign.hip
 hipError_t launch_pack_reference(const uint8_t* ascii, uint64_t* pk, int64_t n_bases_padded,

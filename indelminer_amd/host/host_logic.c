@@ -949,21 +949,32 @@ static void genotype_of(int64_t rs, int64_t ns, int* best_out, int* gq_out)
     if (gq > 99) gq = 99;
     *best_out = best; *gq_out = (int)gq;
 }
-static void print_gt_ad_gq(int64_t ref_count, int64_t alt_count)
+/* more_keys: what the record's FORMAT has behind GT:AD:GQ ("" or ":DM:DFC"; the caller prints the values) */
+static void print_gt_ad_gq(const char* more_keys, int64_t ref_count, int64_t alt_count)
 {
     int best, gq;
     genotype_of(ref_count, alt_count, &best, &gq);
-    printf("\tGT:AD:GQ\t%s:%lld,%lld:%d", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", (long long)ref_count, (long long)alt_count, gq);
+    printf("\tGT:AD:GQ%s\t%s:%lld,%lld:%d", more_keys, best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", (long long)ref_count, (long long)alt_count, gq);
+}
+/* -D: the values of DM and DFC.  DFC = the median inside over the mean of the flanks present, in thousandths, rounded, in integers */
+static void print_depth_evidence(const variant_t* v)
+{
+    const uint32_t in = v->dm_cached[0], l = v->dm_cached[1], r = v->dm_cached[2];
+    uint64_t num = 0, den = 0;
+    if (l != DEPTH_EV_NONE && r != DEPTH_EV_NONE) { num = 2000ull * in; den = (uint64_t)l + r; }
+    else if (l != DEPTH_EV_NONE || r != DEPTH_EV_NONE) { num = 1000ull * in; den = l != DEPTH_EV_NONE ? l : r; }
+    printf(":");
+    for (int k = 0; k < 3; k++) { if (v->dm_cached[k] == DEPTH_EV_NONE) printf("%s.", k ? "," : ""); else printf("%s%u", k ? "," : "", v->dm_cached[k]); }
+    if (den == 0 || in == DEPTH_EV_NONE) printf(":."); else printf(":%llu", (unsigned long long)((num + den / 2) / den));
 }
 static void print_genotype(const variant_t* v)
 {
+    const char* more_keys = v->dm_valid ? ":DM:DFC" : "";
     /* a PAIRED_READ record has no precise breakpoint to count spanning reads at; with -P its rs_cached is RP, the thinnest depth
      * of concordant fragments over [POS, max(END, BP_END)] */
-    if ((v->evdnctype == EV_PAIRED_READ && !g_pair_counts) || !v->rs_valid) {
-        printf("\tGT:AD:GQ\t./.:.,%u:.", v->support);
-        return;
-    }
-    print_gt_ad_gq((int64_t)v->rs_cached, (int64_t)v->support);
+    if ((v->evdnctype == EV_PAIRED_READ && !g_pair_counts) || !v->rs_valid) printf("\tGT:AD:GQ%s\t./.:.,%u:.", more_keys, v->support);
+    else print_gt_ad_gq(more_keys, (int64_t)v->rs_cached, (int64_t)v->support);
+    if (v->dm_valid) print_depth_evidence(v);
 }
 
 /* the span (pair: 0) or pair-span (pair: 1) minima over m > 0 intervals of one contig, as one query */
@@ -1311,6 +1322,41 @@ static void print_variants(driver* d, variant_list* vs)
             for (int q = 0; q < m; q++) { out.v[who[q]]->rs_cached = rs[q]; out.v[who[q]]->rs_valid = 1; }
         }
         free(beg); free(end); free(rs); free(who);
+    }
+    /* ... -D: the deletions of DEPTH_EV_MIN_LEN bases and more get the median depth of their deleted bases [POS, END) and of the
+     * DEPTH_EV_FLANK bases on either side: three queries each, all of a flush in one call (the device clips to the contig) ... */
+    for (int i = 0; i < out.n; i++) out.v[i]->dm_valid = 0;
+    if (g_depth_evidence && out.n > 0) {
+        int32_t* beg = xmalloc(sizeof(int32_t) * 3 * (size_t)out.n);
+        int32_t* end = xmalloc(sizeof(int32_t) * 3 * (size_t)out.n);
+        uint32_t* med = xmalloc(sizeof(uint32_t) * 3 * (size_t)out.n);
+        int* who = xmalloc(sizeof(int) * (size_t)out.n);
+        int m = 0;
+        for (int i = 0; i < out.n; i++) {
+            const variant_t* v = out.v[i];
+            if (v->type != CLS_DELETION) continue;
+            int pos, endpos, bp_end;
+            vcf_coordinates(v, &pos, &endpos, &bp_end);
+            if (endpos - pos < DEPTH_EV_MIN_LEN) continue;
+            forceassert(d->depth_tid == v->tid);            /* -c is refused with -D: the contig's depth array is there */
+            beg[3 * m] = pos; end[3 * m] = endpos;
+            beg[3 * m + 1] = pos - DEPTH_EV_FLANK; end[3 * m + 1] = pos;
+            beg[3 * m + 2] = endpos; end[3 * m + 2] = endpos + DEPTH_EV_FLANK;
+            who[m++] = i;
+        }
+        if (m > 0) {
+            gpu_wait(d);
+            pthread_mutex_lock(&g_query_mu);
+            const int qrc = d->pipe_mode ? im_depth_median_tid(d->gpu, d->depth_tid, 3 * m, beg, end, med) : im_depth_median(d->gpu, 3 * m, beg, end, med);
+            pthread_mutex_unlock(&g_query_mu);
+            if (qrc != IM_OK) fatalf("im_depth_median: %s", im_last_error(d->gpu));
+            for (int q = 0; q < m; q++) {
+                variant_t* v = out.v[who[q]];
+                for (int k = 0; k < 3; k++) v->dm_cached[k] = med[3 * q + k];
+                v->dm_valid = 1;
+            }
+        }
+        free(beg); free(end); free(med); free(who);
     }
     /* ... and out they go */
     for (int i = 0; i < out.n; i++) emit_variant(d, out.v[i]);
@@ -1879,7 +1925,7 @@ static void print_known_genotype(const knownvariant_t* k)
         /* -P: RP = the thinnest depth of concordant fragments over [POS, max(END, BP_END)], AP = the pairs the discovery pass
          * clustered into the variant that re-finds this one */
         if (k->rs + k->ap == 0) { printf("\tGT:AD:GQ\t./.:0,0:."); return; }
-        print_gt_ad_gq((int64_t)k->rs, (int64_t)k->ap);
+        print_gt_ad_gq("", (int64_t)k->rs, (int64_t)k->ap);
         return;
     }
     int64_t rs = k->rs_valid ? (int64_t)k->rs : 0;
@@ -1889,7 +1935,7 @@ static void print_known_genotype(const knownvariant_t* k)
     forceassert(rs >= k->n_dc);
     rs -= k->n_dc;
     if (rs + k->n_as == 0) { printf("\tGT:AD:GQ\t./.:0,0:."); return; }
-    print_gt_ad_gq(rs, (int64_t)k->n_as);
+    print_gt_ad_gq("", rs, (int64_t)k->n_as);
 }
 
 /* -A: known variants [from, to) of the list go out; found[ki - from] says which of them the discovery pass re-found (NULL: none).

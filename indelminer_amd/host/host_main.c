@@ -38,6 +38,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    (FORMAT GT:AD:GQ from the reads for and against each)\n");
     fprintf(file, "\t-P, with -G or -A: genotype PAIRED_READ records too, from the\n");
     fprintf(file, "\t    concordant pairs whose fragment spans the deletion\n");
+    fprintf(file, "\t-D, with -G: depth evidence for deletions of 50 bp and more\n");
+    fprintf(file, "\t    (FORMAT DM:DFC, median depth inside against the flanks)\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -80,7 +82,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAP")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPD")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -107,6 +109,7 @@ int main(int argc, char** argv)
         case 'G': g_genotype = 1; break;                            /* not an option of the reference */
         case 'A': g_known_counts = 1; break;                        /* not an option of the reference */
         case 'P': g_pair_counts = 1; break;                         /* not an option of the reference */
+        case 'D': g_depth_evidence = 1; break;                      /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -154,11 +157,21 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: genotyping paired-read records (-P) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -D: behind the refusals of -G, -A and -P; what it needs of the library in front of what -G needs (the newer entry points first) */
+    if (g_depth_evidence) {
+        if (g_vcfname != NULL) { fprintf(stderr, "indelminer: -D is not available with a VCF argument (annotate mode)\n"); return EXIT_FAILURE; }
+        if (!g_genotype) { fprintf(stderr, "indelminer: -D needs -G\n"); return EXIT_FAILURE; }
+        /* a region run builds no depth array, and the flanks would lie outside the walked stretch */
+        if (O.region != NULL) { fprintf(stderr, "indelminer: -D is not available with -c\n"); return EXIT_FAILURE; }
+        if (!MEDIAN_API_PRESENT) {
+            fprintf(stderr, "indelminer: depth evidence (-D) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) g_genotype = g_pair_counts = 0;    /* -o detailed has no columns to add to */
+        if (strcmp(O.outputformat, "detailed") == 0) g_genotype = g_pair_counts = g_depth_evidence = 0;    /* -o detailed has no columns to add to */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {

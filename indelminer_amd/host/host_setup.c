@@ -46,7 +46,15 @@ static void print_output_header(void)
         printf("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype, the most likely of 0/0, 0/1, 1/1 given AD\">\n");
         printf("##FORMAT=<ID=AD,Number=2,Type=Integer,Description=\"Read support of the reference and the alternative allele: the smallest number, over the positions POS .. POS+(BP_END-END) the breakpoint can lie at, of alignments that match the reference for the -n distance on both sides of it (an upper bound of the reads spanning the whole interval, exact when the interval is one position), and NS\">\n");
         printf("##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred-scaled distance to the second most likely genotype, at most 99\">\n");
+        if (g_depth_evidence) {
+            /* -D: no reference counterpart */
+            printf("##FORMAT=<ID=DM,Number=3,Type=Integer,Description=\"Median depth over the deleted bases POS+1..END, over the %d bases in front of them and over the %d bases behind them\">\n", DEPTH_EV_FLANK, DEPTH_EV_FLANK);
+            printf("##FORMAT=<ID=DFC,Number=1,Type=Integer,Description=\"Depth fold change in thousandths: the median inside the deletion over the mean of the flank medians\">\n");
+        }
         if (g_pair_counts) printf("##pairedReadAD=\"PAIRED_READ records: AD = concordant pairs spanning the deletion with -n bases on each side (lower bound), pairs supporting it\"\n");
+        if (g_depth_evidence)
+            printf("##depthEvidence=\"DELETION records with END-POS >= %d: DM = lower median (the smallest depth that at least half of the positions, rounded up, do not exceed) of the per-position depth over the deleted bases, the %d bases in front and the %d bases behind, each clipped to the contig, . for a flank without bases; DFC = 1000 * inside / mean of the flanks present, rounded, . without a flank or with flanks of depth 0. Depth = records samtools' pileup would count whose M/=/X covers the position, capped at 4095 per position; these are array counts without the pileup's limit of 8000 records, so DM can exceed what DP= implies at such loci\"\n",
+                   DEPTH_EV_MIN_LEN, DEPTH_EV_FLANK, DEPTH_EV_FLANK);
         printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", g_sample_name);
     } else if (strncmp(O.outputformat, "vcf", 3) == 0) printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
     fflush(OUT);

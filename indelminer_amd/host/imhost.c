@@ -133,6 +133,15 @@ extern int im_pairspan_build(im_ctx*, int64_t, int32_t, const int32_t*, const in
 extern int im_pairspan_query(im_ctx*, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
 #define PAIR_ON (g_pair_counts)                    /* the walk scatters the pair-span array */
 #define PAIR_API_PRESENT (im_pairspan_enable && im_dev_pairspan_scatter && im_pairspan_scan && im_pairspan_query_tid && im_pairspan_build && im_pairspan_query)
+/* -D, with -G: depth evidence for the deletions of DEPTH_EV_MIN_LEN bases and more (FORMAT DM:DFC) -- the device's median of the
+ * depth array inside the deletion and over DEPTH_EV_FLANK bases on either side.  Not an option of the reference; referenced weakly. */
+static int g_depth_evidence = 0;
+extern int im_depth_median_tid(im_ctx*, int32_t, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
+extern int im_depth_median(im_ctx*, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
+#define MEDIAN_API_PRESENT (im_depth_median_tid && im_depth_median)
+#define DEPTH_EV_MIN_LEN 50        /* END - POS of the shortest deletion that gets the fields */
+#define DEPTH_EV_FLANK 1000        /* bases of each flank */
+#define DEPTH_EV_NONE 0xFFFFFFFFu  /* what the device answers for an interval without positions */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that

@@ -74,6 +74,9 @@ typedef struct {
     /* -G: reference support of the variant (reads that span its breakpoint interval), asked for in the same way */
     uint32_t  rs_cached;
     int       rs_valid;
+    /* -D: median depth inside the deletion, over its left and over its right flank, asked for in the same way */
+    uint32_t  dm_cached[3];
+    int       dm_valid;
 } variant_t;
 
 typedef struct {

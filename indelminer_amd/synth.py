@@ -74,12 +74,13 @@ class Reads:
 
 def simulate(seed, ref_len=1_000_000, coverage=30, read_len=100, isize_mean=500, isize_sd=50,
              isize_min=300, isize_max=700, sub_rate=0.005, indel_spacing=2000, n_contigs=1, big_every=0,
-             read_seed=None, somatic_spacing=0, ref_lens=None):
+             read_seed=None, somatic_spacing=0, ref_lens=None, events=None):
     """Returns (refs, reads): refs = list of uint8 arrays (one per contig); reads = Reads.
     `seed` fixes the reference and its (germline) indels; `read_seed` (default: derived from seed)
     the sampled pairs; somatic_spacing > 0 adds extra indels about every that many bases, drawn from
     the read_seed stream -- a tumour/normal pair shares `seed` and differs in the other two
-    (BASELINE config 5)."""
+    (BASELINE config 5).  events = (pos, size, is_ins) arrays: these indels on every contig in place of the
+    planted ones (tests that need a deletion of a given size at a given place)."""
     rng = np.random.default_rng(seed)
     rrng = np.random.default_rng(seed + 7919 if read_seed is None else read_seed)
     L = read_len
@@ -93,7 +94,10 @@ def simulate(seed, ref_len=1_000_000, coverage=30, read_len=100, isize_mean=500,
             ref_len = int(ref_lens[tid])
         ref = random_genome(rng, ref_len)
         refs.append(ref)
-        epos, esize, eins = plant_indels(rng, ref_len, indel_spacing, big_every=big_every)
+        if events is not None:
+            epos, esize, eins = (np.asarray(events[0], np.int64), np.asarray(events[1], np.int64), np.asarray(events[2], bool))
+        else:
+            epos, esize, eins = plant_indels(rng, ref_len, indel_spacing, big_every=big_every)
         if somatic_spacing:
             spos, ssize, sins = plant_indels(rrng, ref_len, somatic_spacing, margin=1500 + indel_spacing // 2)
             far = np.array([np.min(np.abs(epos - p)) > 300 for p in spos], dtype=bool)
