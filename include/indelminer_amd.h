@@ -542,6 +542,38 @@ int im_pairspan_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* be
 int im_pairspan_build(im_ctx* ctx, int64_t contig_len, int32_t n_frag, const int32_t* frag_start, const int32_t* frag_len, int32_t flank);
 int im_pairspan_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out);
 
+/* Clipped reads, the breakpoint evidence of large deletions (-C).  Replaces nothing in the reference either: it realigns a clipped
+ * read only when the deletion is shorter than -s and looks at no clip beyond that.  Two POINT-COUNT arrays of the family's layout
+ * (per contig length + 1 entries), never scanned.  With c = min_clip >= 1 and q = min_mapq, a record is ELIGIBLE iff
+ *   its flag has none of 0x4 | 0x100 | 0x200 | 0x400 (the span scatter's mask);  0 <= tid < n_contigs;  mapq >= q;
+ *   its CIGAR has at least one reference-consuming operation (M, =, X, D, N).
+ * Let `first` be its first operation that is not H and `last` its last that is not H, and refend = pos + the lengths of its
+ * M / = / X / D / N operations.  Then
+ *   RIGHT CLIP: last is S with length >= c and 0 <= refend <= length:  clipR[refend] += 1  (the read stops aligning in front of refend);
+ *   LEFT CLIP:  first is S with length >= c and 0 <= pos <= length:    clipL[pos] += 1     (the read starts aligning at pos).
+ * A record can add to both arrays.  A record whose only operation that is not H is an S adds nothing (it consumes no reference).
+ * An S anywhere else in the CIGAR is ignored here: the triage of the same chunk ends the run on it.  For a deletion of the
+ * 0-based bases [a, b) the reads from the left pile up on clipR[a] and the reads from the right on clipL[b].
+ *
+ * QUERY: a side (0: clipR, 1: clipL) and an interval [beg, end] INCLUSIVE, clipped to [0, length].  The answer is the LARGEST
+ * count in the interval and the SMALLEST position that holds it (an interval of zeros answers count 0 at its first position); an
+ * interval that is empty after the clip answers count 0 and position -1.  side is given per query, so one call serves both sides
+ * of every record of a flush.  A null pointer with n >= 1, or a side other than 0 and 1, is IM_E_ARG.
+ *
+ * im_clip_enable allocates both arrays for all contigs (8 bytes per reference base of HBM, on this call only; min_clip >= 1) and
+ * fixes min_clip and min_mapq: a second call with other values is refused.  im_dev_clip_scatter adds a chunk of delivered records
+ * (the chunk im_dev_triage takes, with or without base qualities; one launch of its own, asynchronous); there is no scan, the
+ * arrays are counts as they stand once the scatters have completed.  im_clip_reset puts contig tid's run of both arrays back to
+ * zeros.  Host-buffer form: im_clip_build takes one contig's events (position, side) -- the caller applies the record rule;
+ * positions outside [0, contig_len] are dropped -- and leaves both arrays of that contig resident beside what the other builds
+ * made; im_clip_query answers like im_clip_query_tid.  Synchronous. */
+int im_clip_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq);
+int im_dev_clip_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream);
+int im_clip_reset(im_ctx* ctx, int32_t tid, void* stream);
+int im_clip_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const uint8_t* side, const int32_t* beg, const int32_t* end, uint32_t* count_out, int32_t* pos_out);
+int im_clip_build(im_ctx* ctx, int64_t contig_len, int32_t n, const int32_t* pos, const uint8_t* side);
+int im_clip_query(im_ctx* ctx, int32_t n, const uint8_t* side, const int32_t* beg, const int32_t* end, uint32_t* count_out, int32_t* pos_out);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

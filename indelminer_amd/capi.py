@@ -223,6 +223,12 @@ def lib():
         L.im_pairspan_query_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_pairspan_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         L.im_pairspan_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_clip_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.im_dev_clip_scatter.argtypes = [C.c_void_p, C.POINTER(DevRecords), C.c_void_p]
+        L.im_clip_reset.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.im_clip_query_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_clip_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+        L.im_clip_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_capture_begin.argtypes = [C.c_void_p, C.c_void_p]
@@ -540,6 +546,42 @@ class Context:
 
     def pairspan_query(self, beg, end):
         return self._query(lib().im_pairspan_query, beg, end)
+
+    def clip_enable(self, min_clip, min_mapq):
+        """the two genome-wide arrays of clipped-read counts (right clips at refend, left clips at pos), 8 bytes per reference base"""
+        self._check(lib().im_clip_enable(self.h, int(min_clip), int(min_mapq)))
+
+    def clip_scatter(self, recs, stream=None):
+        """DevRecords -> the clipped reads of the chunk counted into both arrays (asynchronous; there is no scan)"""
+        self._check(lib().im_dev_clip_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
+
+    def clip_reset(self, tid, stream=None):
+        self._reset(lib().im_clip_reset, tid, stream)
+
+    def _clip_query(self, fn, side, beg, end, *tid):
+        side = np.ascontiguousarray(side, dtype=np.uint8)
+        beg = np.ascontiguousarray(beg, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        assert len(side) == len(beg) == len(end)
+        count = np.zeros(max(len(beg), 1), dtype=np.uint32)
+        pos = np.zeros(max(len(beg), 1), dtype=np.int32)
+        self._check(fn(self.h, *tid, len(beg), _ptr(side), _ptr(beg), _ptr(end), _ptr(count), _ptr(pos)))
+        return count[:len(beg)], pos[:len(beg)]
+
+    def clip_query_tid(self, tid, side, beg, end):
+        """per query (side 0: right clips, 1: left clips) the largest count over [beg, end] inclusive on contig tid and the
+        smallest position that holds it; (0, -1) for an interval that is empty after the clip to the contig"""
+        return self._clip_query(lib().im_clip_query_tid, side, beg, end, tid)
+
+    def clip_build(self, contig_len, pos, side):
+        """one contig's clip events as the caller found them: positions and sides (0: right, 1: left)"""
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        side = np.ascontiguousarray(side, dtype=np.uint8)
+        assert len(pos) == len(side)
+        self._check(lib().im_clip_build(self.h, contig_len, len(pos), _ptr(pos), _ptr(side)))
+
+    def clip_query(self, side, beg, end):
+        return self._clip_query(lib().im_clip_query, side, beg, end)
 
     def cluster_sr(self, cls, b1, b2, marker=2**31 - 1, tie_desc=0):
         n = len(cls)

@@ -53,12 +53,16 @@ struct im_ctx {
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_k[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
     // resident depth, span and pair-span arrays of the current contig (im_depth_build, im_span_build, im_pairspan_build)
     ContigArray depth, span, pair;
+    // -C: the clipped-read counts of the current contig, right and left (im_clip_build); point counts, no sums
+    ContigArray clip_r, clip_l;
     // host copies of the reference layout
     std::vector<int64_t> h_asc_off;
     std::vector<int32_t> h_len;
     int64_t ref_total = 0;
     // genome-wide depth / difference array, reference-spanning counts and concordant-pair counts
     GenomeArray all_depth, all_span, all_pair;
+    // genome-wide clipped-read counts, right and left (im_clip_enable): flank holds min_clip; never scanned, their sums stay null
+    GenomeArray all_clip_r, all_clip_l;
     // the median queries' histograms of queries of several slabs (im::launch_depth_median): zeros between calls, sized by the call that
     // needed the most; med_dirty: a call did not get to its end, the next one clears them
     uint32_t* med_scratch = nullptr;
@@ -142,7 +146,7 @@ void free_reference(im_ctx* ctx)
     if (ctx->d_len) (void)hipFree(ctx->d_len);
     ctx->ref_ascii = nullptr; ctx->ref_pk = nullptr; ctx->d_asc_off = nullptr; ctx->d_pk_off = nullptr; ctx->d_len = nullptr;
     ctx->n_contigs = 0;
-    for (GenomeArray* g : {&ctx->all_depth, &ctx->all_span, &ctx->all_pair}) {
+    for (GenomeArray* g : {&ctx->all_depth, &ctx->all_span, &ctx->all_pair, &ctx->all_clip_r, &ctx->all_clip_l}) {
         if (g->data) (void)hipFree(g->data);
         if (g->sums) (void)hipFree(g->sums);
         g->data = nullptr; g->sums = nullptr;
@@ -160,6 +164,20 @@ void free_array(ContigArray& a)
 // The helpers below serve one member of either family each; `family` ("im_depth", "im_span", "im_pairspan") names it in the messages, and
 // flank is null for the depth arrays, which count whole intervals.
 
+// a build's first step: the array counts as not built until the build is through, and holds clen + 1 entries (with_sums: and its tile sums)
+int grow_array(im_ctx* ctx, ContigArray& a, int64_t clen, bool with_sums)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    a.len = -1;
+    if (clen + 1 > a.cap) {
+        free_array(a);
+        HIP_TRY(ctx, hipMalloc((void**)&a.data, (size_t)(clen + 1) * sizeof(int32_t)));
+        if (with_sums) HIP_TRY(ctx, hipMalloc((void**)&a.sums, (size_t)im::depth_sums_ints(clen) * sizeof(int32_t)));     // zeroed by every build
+        a.cap = clen + 1;
+    }
+    return IM_OK;
+}
+
 // im_depth_build / im_span_build / im_pairspan_build: check, grow, stage the intervals, memset + scatter + scan (one launcher, im_depth.hip), wait
 int build_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* family, int64_t clen, int32_t n, const int32_t* start, const int32_t* len,
                 const int32_t* flank)
@@ -168,16 +186,10 @@ int build_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* family, int
     if (flank && *flank < 1) { set_err(ctx, "%s_build: flank %d, must be >= 1", family, *flank); return IM_E_ARG; }
     const int32_t lo = flank ? *flank : 0, hi = flank ? *flank - 1 : 0;
     ContigArray& a = ctx->*which;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    a.len = -1;
-    if (clen + 1 > a.cap) {
-        free_array(a);
-        HIP_TRY(ctx, hipMalloc((void**)&a.data, (size_t)(clen + 1) * sizeof(int32_t)));
-        HIP_TRY(ctx, hipMalloc((void**)&a.sums, (size_t)im::depth_sums_ints(clen) * sizeof(int32_t)));     // zeroed by every build
-        a.cap = clen + 1;
-    }
+    int rc = grow_array(ctx, a, clen, true);
+    if (rc) return rc;
     const size_t sb = up256(sizeof(int32_t) * (size_t)(n ? n : 1));
-    int rc = ensure_ws(ctx, 2 * sb);
+    rc = ensure_ws(ctx, 2 * sb);
     if (rc) return rc;
     int32_t* d_start = (int32_t*)ctx->ws;
     int32_t* d_len = (int32_t*)((char*)ctx->ws + sb);
@@ -193,7 +205,16 @@ int build_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* family, int
 
 // what a query answers per interval: the sum over [beg, end) (the depth query; max_out, where not null, the deepest position of
 // [beg - 1, end]), the minimum over [beg, end] (the span queries), or the lower median over [beg, end) of the values capped at 4095
-enum Reduce { kSum, kMinimum, kMedian };
+// kArgMax: the largest value over [beg, end] and the smallest position that holds it, of one of two unscanned arrays (the clip queries)
+enum Reduce { kSum, kMinimum, kMedian, kArgMax };
+
+// what an arg-max query has beyond the family's (beg, end, out): per query which of the two arrays it reads (0: the helper's own,
+// the right clips; 1: `other`, the left clips), and where the positions go
+struct ArgMaxSide {
+    const uint8_t* side;
+    const int32_t* other;
+    int32_t* pos_out;
+};
 
 // the median's trip, n > 0: [beg][end][first][slot] in, one launch (one per kMedMaxSlots queries of several slabs), out back, one wait.
 // The answers of queries that are empty after the clip are set here.  The call that needs more histograms than any before it
@@ -254,11 +275,36 @@ int median_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end,
     return IM_OK;
 }
 
+// the arg-max's trip, n > 0: [side][beg][end] in, one launch on the two arrays as they stand, counts and positions back, one wait
+int argmax_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, const int32_t* data, int64_t clen, const ArgMaxSide& x, uint32_t* out)
+{
+    if (!x.side || !x.pos_out) return IM_E_ARG;
+    for (int32_t q = 0; q < n; q++) if (x.side[q] > 1) { set_err(ctx, "clip query %d: side %d, must be 0 (right) or 1 (left)", q, (int)x.side[q]); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = up256(sizeof(int32_t) * (size_t)n);
+    int rc = ensure_ws(ctx, 5 * sb);
+    if (rc) return rc;
+    int32_t* d_beg = (int32_t*)ctx->ws;
+    int32_t* d_end = (int32_t*)((char*)ctx->ws + sb);
+    uint32_t* d_out = (uint32_t*)((char*)ctx->ws + 2 * sb);
+    int32_t* d_pos = (int32_t*)((char*)ctx->ws + 3 * sb);
+    uint8_t* d_side = (uint8_t*)ctx->ws + 4 * sb;
+    HIP_TRY(ctx, hipMemcpyAsync(d_beg, beg, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_end, end, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_side, x.side, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, im::launch_clip_argmax(n, d_side, d_beg, d_end, data, x.other, clen, d_out, d_pos, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(x.pos_out, d_pos, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
 // the queries' trip through the context's workspace and stream, n > 0: [beg][end] in, one launch on a scanned array, out back
 int query_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, const int32_t* data, const int32_t* sums, int64_t clen,
-                Reduce what, uint32_t* out, uint32_t* max_out)
+                Reduce what, uint32_t* out, uint32_t* max_out, const ArgMaxSide* argmax = nullptr)
 {
     if (what == kMedian) return median_array(ctx, n, beg, end, data, sums, clen, out);     // max_out belongs to the sum alone: not looked at
+    if (what == kArgMax) return argmax ? argmax_array(ctx, n, beg, end, data, clen, *argmax, out) : IM_E_ARG;      // these arrays have no sums
     const bool minimum = what == kMinimum;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t sb = up256(sizeof(int32_t) * (size_t)n);
@@ -278,28 +324,30 @@ int query_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, 
     return IM_OK;
 }
 
-// im_depth_query / im_depth_median / im_span_query / im_pairspan_query
+// im_depth_query / im_depth_median / im_span_query / im_pairspan_query / im_clip_query
 int query_contig_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* family, int32_t n, const int32_t* beg, const int32_t* end, Reduce what,
-                       uint32_t* out)
+                       uint32_t* out, const ArgMaxSide* argmax = nullptr)
 {
     if (!ctx || n < 0) return IM_E_ARG;
     const ContigArray& a = ctx->*which;
     if (a.len < 0) { set_err(ctx, "%s_build has not been called", family); return IM_E_ARG; }
     if (n == 0) return IM_OK;
     if (!beg || !end || !out) return IM_E_ARG;
-    return query_array(ctx, n, beg, end, a.data, a.sums, a.len, what, out, nullptr);
+    return query_array(ctx, n, beg, end, a.data, a.sums, a.len, what, out, nullptr, argmax);
 }
 
-// im_depth_enable / im_span_enable / im_pairspan_enable: a genome-wide array and its sums, zeroed.  Each contig has its own run of sums (scans of
-// different contigs may be in flight on different streams), at the same place in every array
-int enable_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, const char* family, const int32_t* flank, int32_t min_mapq)
+// im_depth_enable / im_span_enable / im_pairspan_enable / im_clip_enable: a genome-wide array and its sums, zeroed.  Each contig has its own
+// run of sums (scans of different contigs may be in flight on different streams), at the same place in every array.  knob: what the family
+// calls its flank in the messages; scanned = false: an array of point counts, which has no sums
+int enable_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, const char* family, const int32_t* flank, int32_t min_mapq,
+                        const char* knob = "flank", bool scanned = true)
 {
     if (!ctx) return IM_E_ARG;
     if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
-    if (flank && *flank < 1) { set_err(ctx, "%s_enable: flank %d, must be >= 1", family, *flank); return IM_E_ARG; }
+    if (flank && *flank < 1) { set_err(ctx, "%s_enable: %s %d, must be >= 1", family, knob, *flank); return IM_E_ARG; }
     GenomeArray& g = ctx->*which;
     if (g.data) {
-        if (flank && (*flank != g.flank || min_mapq != g.min_mapq)) { set_err(ctx, "%s_enable: already enabled with flank %d, min_mapq %d", family, g.flank, g.min_mapq); return IM_E_ARG; }
+        if (flank && (*flank != g.flank || min_mapq != g.min_mapq)) { set_err(ctx, "%s_enable: already enabled with %s %d, min_mapq %d", family, knob, g.flank, g.min_mapq); return IM_E_ARG; }
         return IM_OK;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -308,9 +356,9 @@ int enable_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, const char* fam
     for (int32_t l : ctx->h_len) { sums_off.push_back(ints); ints += im::depth_sums_ints(l); }
     ctx->h_sums_off = sums_off;
     HIP_TRY(ctx, hipMalloc((void**)&g.data, (size_t)ctx->ref_total * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMalloc((void**)&g.sums, (size_t)(ints + 1) * sizeof(int32_t)));
+    if (scanned) HIP_TRY(ctx, hipMalloc((void**)&g.sums, (size_t)(ints + 1) * sizeof(int32_t)));
     HIP_TRY(ctx, hipMemsetAsync(g.data, 0, (size_t)ctx->ref_total * sizeof(int32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(g.sums, 0, (size_t)(ints + 1) * sizeof(int32_t), ctx->stream));      // the arrival counters start at zero
+    if (scanned) HIP_TRY(ctx, hipMemsetAsync(g.sums, 0, (size_t)(ints + 1) * sizeof(int32_t), ctx->stream));      // the arrival counters start at zero
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (flank) { g.flank = *flank; g.min_mapq = min_mapq; }
     return IM_OK;
@@ -326,7 +374,7 @@ int scan_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, void
     return IM_OK;
 }
 
-// im_depth_reset / im_span_reset / im_pairspan_reset
+// im_depth_reset / im_span_reset / im_pairspan_reset / im_clip_reset (both arrays)
 int reset_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, void* stream)
 {
     if (!ctx || !(ctx->*which).data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
@@ -335,15 +383,16 @@ int reset_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, voi
     return IM_OK;
 }
 
-// im_depth_query_max_tid / im_depth_median_tid / im_span_query_tid / im_pairspan_query_tid
+// im_depth_query_max_tid / im_depth_median_tid / im_span_query_tid / im_pairspan_query_tid / im_clip_query_tid
 int query_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, Reduce what,
-                       uint32_t* out, uint32_t* max_out)
+                       uint32_t* out, uint32_t* max_out, const ArgMaxSide* argmax = nullptr)
 {
     if (!ctx || n < 0 || !(ctx->*which).data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
     if (n == 0) return IM_OK;
     if (!beg || !end || !out) return IM_E_ARG;
     const GenomeArray& g = ctx->*which;
-    return query_array(ctx, n, beg, end, g.data + ctx->h_asc_off[tid], g.sums + ctx->h_sums_off[tid], ctx->h_len[tid], what, out, max_out);
+    const int32_t* sums = g.sums ? g.sums + ctx->h_sums_off[tid] : nullptr;
+    return query_array(ctx, n, beg, end, g.data + ctx->h_asc_off[tid], sums, ctx->h_len[tid], what, out, max_out, argmax);
 }
 
 im::RefDev ref_dev(const im_ctx* ctx)
@@ -400,6 +449,8 @@ void im_ctx_destroy(im_ctx* ctx)
     free_array(ctx->depth);
     free_array(ctx->span);
     free_array(ctx->pair);
+    free_array(ctx->clip_r);
+    free_array(ctx->clip_l);
     if (ctx->rg_blob) (void)hipFree(ctx->rg_blob);
     if (ctx->any_list) (void)hipFree(ctx->any_list);
     if (ctx->any_counters) (void)hipFree(ctx->any_counters);
@@ -956,6 +1007,69 @@ int im_pairspan_build(im_ctx* ctx, int64_t contig_len, int32_t n_frag, const int
 
 int im_pairspan_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
 { return query_contig_array(ctx, &im_ctx::pair, "im_pairspan", n, beg, end, kMinimum, min_out); }
+
+// ---- clipped-read counts (the breakpoint evidence of large deletions) --------------------------
+
+int im_clip_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq)
+{
+    const int rc = enable_genome_array(ctx, &im_ctx::all_clip_r, "im_clip", &min_clip, min_mapq, "min_clip", false);
+    return rc ? rc : enable_genome_array(ctx, &im_ctx::all_clip_l, "im_clip", &min_clip, min_mapq, "min_clip", false);
+}
+
+int im_dev_clip_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
+{
+    if (!ctx || !recs) return IM_E_ARG;
+    const GenomeArray& g = ctx->all_clip_r;
+    if (!g.data || !ctx->all_clip_l.data) { set_err(ctx, "im_clip_enable has not been called"); return IM_E_ARG; }
+    if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, im::launch_clip_scatter(ref_dev(ctx), g.flank, g.min_mapq, *recs, g.data, ctx->all_clip_l.data, (hipStream_t)stream));
+    return IM_OK;
+}
+
+int im_clip_reset(im_ctx* ctx, int32_t tid, void* stream)
+{
+    if (!ctx || !ctx->all_clip_l.data) return IM_E_ARG;
+    const int rc = reset_genome_array(ctx, &im_ctx::all_clip_r, tid, stream);
+    return rc ? rc : reset_genome_array(ctx, &im_ctx::all_clip_l, tid, stream);
+}
+
+int im_clip_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const uint8_t* side, const int32_t* beg, const int32_t* end, uint32_t* count_out, int32_t* pos_out)
+{
+    if (!ctx || !ctx->all_clip_l.data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    const ArgMaxSide x = {side, ctx->all_clip_l.data + ctx->h_asc_off[tid], pos_out};
+    return query_genome_array(ctx, &im_ctx::all_clip_r, tid, n, beg, end, kArgMax, count_out, nullptr, &x);
+}
+
+// the host names the events: both arrays grown through the family's helper, cleared, one count per event, wait
+int im_clip_build(im_ctx* ctx, int64_t contig_len, int32_t n, const int32_t* pos, const uint8_t* side)
+{
+    if (!ctx || contig_len < 0 || contig_len > 0x7fffff00LL || n < 0 || (n > 0 && (!pos || !side))) return IM_E_ARG;
+    for (int32_t i = 0; i < n; i++) if (side[i] > 1) { set_err(ctx, "im_clip_build: event %d: side %d, must be 0 (right) or 1 (left)", i, (int)side[i]); return IM_E_ARG; }
+    int rc = grow_array(ctx, ctx->clip_r, contig_len, false);
+    if (!rc) rc = grow_array(ctx, ctx->clip_l, contig_len, false);
+    if (rc) return rc;
+    const size_t sb = up256(sizeof(int32_t) * (size_t)(n ? n : 1));
+    rc = ensure_ws(ctx, 2 * sb);
+    if (rc) return rc;
+    int32_t* d_pos = (int32_t*)ctx->ws;
+    uint8_t* d_side = (uint8_t*)ctx->ws + sb;
+    if (n > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_pos, pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_side, side, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(ctx, im::launch_clip_build(contig_len, n, d_pos, d_side, ctx->clip_r.data, ctx->clip_l.data, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->clip_r.len = ctx->clip_l.len = contig_len;
+    return IM_OK;
+}
+
+int im_clip_query(im_ctx* ctx, int32_t n, const uint8_t* side, const int32_t* beg, const int32_t* end, uint32_t* count_out, int32_t* pos_out)
+{
+    if (!ctx) return IM_E_ARG;
+    const ArgMaxSide x = {side, ctx->clip_l.data, pos_out};
+    return query_contig_array(ctx, &im_ctx::clip_r, "im_clip", n, beg, end, kArgMax, count_out, &x);
+}
 
 int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64_t* t_off,
                      const uint8_t* queries, const int64_t* q_off, int32_t* out)

@@ -117,6 +117,14 @@ hipError_t launch_compact_results(const im_read_result* res, int32_t n_cap, cons
 hipError_t launch_span_scatter(const RefDev& ref, int32_t flank, int32_t min_mapq, const im_dev_records& recs, int32_t* diff, hipStream_t stream);
 // concordant left mates -> fragment events in a difference array of the same layout (rg: the table of im_set_insert_ranges)
 hipError_t launch_pair_scatter(const RefDev& ref, const RgTable& rg, int32_t flank, int32_t min_mapq, const im_dev_records& recs, int32_t* diff, hipStream_t stream);
+// clipped reads -> point counts in two arrays of that layout: right[refend] and left[pos] (see im_span.hip); never scanned
+hipError_t launch_clip_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const im_dev_records& recs, int32_t* right, int32_t* left,
+                               hipStream_t stream);
+// memset of both arrays' clen + 1 entries + one count per host-named event (side 0: right, 1: left; positions outside [0, clen] dropped)
+hipError_t launch_clip_build(int64_t clen, int32_t n, const int32_t* pos, const uint8_t* side, int32_t* right, int32_t* left, hipStream_t stream);
+// per query the largest count over [beg, end] inclusive of right (side 0) or left (side 1) and the smallest position holding it; (0, -1) when empty
+hipError_t launch_clip_argmax(int32_t nq, const uint8_t* side, const int32_t* beg, const int32_t* end, const int32_t* right, const int32_t* left,
+                              int64_t clen, uint32_t* count_out, int32_t* pos_out, hipStream_t stream);
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);

@@ -26,6 +26,16 @@
 // Its FRAGMENT is [a, b) = [pos, pos + isize) clipped to [0, clen).  pspan[p], 0 <= p <= clen, counts the fragments with
 // a + m <= p and p + m <= b: a fragment with b - a >= 2 m adds +1 at a + m and -1 at b - m + 1.  Scan and query as for span[].
 //   pair_scatter   one lane per delivered record: the core decides first, the survivors find RG:Z and look the group up (im_rg.hpp)
+//
+// Clipped reads (-C), two POINT-COUNT arrays of the same layout, never scanned.  A record is eligible as for span[] and when its
+// CIGAR has at least one M / = / X / D / N.  `first` / `last`: its first / last operation that is not H; refend = pos + the
+// lengths of its M / = / X / D / N operations.
+//   clipR[refend] += 1  iff last is S of >= min_clip bases and 0 <= refend <= clen  (a read that stops aligning in front of refend)
+//   clipL[pos] += 1     iff first is S of >= min_clip bases and 0 <= pos <= clen    (a read that starts aligning at pos)
+// A record can add to both; an S anywhere else is not looked at here (the triage of the same chunk ends the run on it).
+//   clip_scatter   one lane per delivered record: the core and two CIGAR words at either end decide, a right clip walks its CIGAR
+//   clip_argmax    one wave per query: the largest count over [beg, end] inclusive and the smallest position that holds it
+// The record-at-a-time path names the events itself: clip_build adds one per (position, side).
 
 #include "im_device.hpp"
 #include "im_rg.hpp"
@@ -242,6 +252,142 @@ __global__ __launch_bounds__(kSpanBlock) void pair_scatter_kernel(ScatterArgs A)
     win_out(W, A.diff, A.asc_off, A.len, t);
 }
 
+// what the clip scatter takes
+struct ClipArgs {
+    im_dev_records recs;
+    const int64_t* asc_off;
+    const int32_t* len;
+    int32_t n_contigs;
+    int32_t min_clip, min_mapq;
+    int32_t* right;             // clipR, genome-wide
+    int32_t* left;              // clipL
+};
+
+constexpr uint32_t kClipLeftOne = 1u << 16;     // one left clip in a packed window word; a right clip is 1
+
+// Both sides share the window: a word holds the right clips of its position in the low half and the left clips in the high half.
+// A workgroup has kSpanBlock = 256 records and a record adds at most one to either half, so no half carries over.
+__device__ __forceinline__ void clip_event(const SpanWin& W, int32_t* __restrict__ arr, int64_t base, int32_t tid, int64_t at, bool left)
+{
+    const int64_t rel = at - W.pos;
+    if (tid == W.tid && rel >= 0 && rel < kSpanWin) atomicAdd(reinterpret_cast<uint32_t*>(&W.lds[rel]), left ? kClipLeftOne : 1u);
+    else atomicAdd(&arr[base + at], 1);
+}
+
+__global__ __launch_bounds__(kSpanBlock) void clip_scatter_kernel(ClipArgs A)
+{
+    __shared__ int32_t s_win[kSpanWin];
+    __shared__ int32_t s_wpos[kSpanBlock / 64], s_wtid[kSpanBlock / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t i = (int64_t)blockIdx.x * kSpanBlock + t;
+    win_clear(s_win, t);
+    SpanRec r; r.ok = false; r.tid = -1; r.pos = 0; r.flag = 0; r.mapq = 0; r.n_cigar = 0; r.o_cigar = 0; r.p = A.recs.raw;
+    if (i < A.recs.n) r = span_record(A.recs.raw, A.recs.rec_off[i], A.recs.rec_off[i + 1]);
+    const uint32_t n = r.ok ? r.n_cigar : 0u;
+    // the two words at either end, where the record has them: H may stand outside S (cig[0], cig[1]: first; cig[2], cig[3]: last)
+    if (n >= 1u) { r.cig[0] = ld_u32(r.p + r.o_cigar); r.cig[3] = ld_u32(r.p + r.o_cigar + 4u * (n - 1u)); }
+    if (n >= 2u) { r.cig[1] = ld_u32(r.p + r.o_cigar + 4u); r.cig[2] = ld_u32(r.p + r.o_cigar + 4u * (n - 2u)); }
+    auto word = [&](uint32_t k) -> uint32_t {
+        return k == 0u ? r.cig[0] : k == n - 1u ? r.cig[3] : k == 1u ? r.cig[1] : k == n - 2u ? r.cig[2] : ld_u32(r.p + r.o_cigar + 4u * k);
+    };
+    const bool eligible = n >= 1u && r.tid >= 0 && r.tid < A.n_contigs && !(r.flag & (0x4u | 0x100u | 0x200u | 0x400u)) && (int32_t)r.mapq >= A.min_mapq;
+    bool clip_l = false, clip_r = false;
+    uint32_t kf = 0, kl = 0;
+    if (eligible) {
+        // first and last operation that is not H (more than one H at an end: the further words come from memory)
+        while (kf < n && (word(kf) & 15u) == 5u) kf++;
+        kl = n - 1u;
+        while (kl > kf && (word(kl) & 15u) == 5u) kl--;
+        if (kf < kl) {                                              // one operation alone cannot both clip and consume reference
+            const uint32_t wf = word(kf), wl = word(kl);
+            clip_l = (wf & 15u) == 4u && (int64_t)(wf >> 4) >= A.min_clip;
+            clip_r = (wl & 15u) == 4u && (int64_t)(wl >> 4) >= A.min_clip;
+        }
+    }
+    win_propose(s_wpos, s_wtid, clip_l || clip_r, r.pos, r.tid, lane, wave);
+    __syncthreads();
+    const SpanWin W = win_open(s_win, s_wpos, s_wtid);
+    if (W.tid < 0) return;                                          // no clipped record in the whole workgroup
+
+    if (clip_l || clip_r) {
+        // refend for a right clip: the whole CIGAR; a left clip alone stops at the first operation that consumes reference
+        int64_t x = r.pos;
+        bool consumes = false;
+        for (uint32_t k = kf; k <= kl; k++) {
+            const uint32_t cw = word(k), op = cw & 15u;
+            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) {
+                consumes = true;
+                if (!clip_r) break;
+                x += cw >> 4;
+            }
+        }
+        if (consumes) {
+            const int64_t base = A.asc_off[r.tid], clen = A.len[r.tid];
+            if (clip_r && x >= 0 && x <= clen) clip_event(W, A.right, base, r.tid, x, false);
+            if (clip_l && r.pos >= 0 && r.pos <= clen) clip_event(W, A.left, base, r.tid, r.pos, true);
+        }
+    }
+    __syncthreads();
+    // the gathered window out, unpacked: consecutive lanes hold consecutive positions, only non-zero halves touch memory
+    const int64_t at0 = A.asc_off[W.tid] + W.pos;
+    const int64_t room = (int64_t)A.len[W.tid] + 1 - W.pos;
+#pragma unroll 4
+    for (int k = 0; k < kSpanWin / kSpanBlock; k++) {
+        const int idx = t + k * kSpanBlock;
+        const uint32_t v = (uint32_t)W.lds[idx];
+        if (v != 0u && idx < room) {
+            if (v & 0xFFFFu) atomicAdd(&A.right[at0 + idx], (int32_t)(v & 0xFFFFu));
+            if (v >> 16) atomicAdd(&A.left[at0 + idx], (int32_t)(v >> 16));
+        }
+    }
+}
+
+// the record-at-a-time path: one lane per event the host named (side 0: clipR, 1: clipL), positions outside [0, clen] dropped
+__global__ __launch_bounds__(256) void clip_build_kernel(int32_t n, const int32_t* __restrict__ pos, const uint8_t* __restrict__ side, int64_t clen,
+                                                        int32_t* __restrict__ right, int32_t* __restrict__ left)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = pos[i];
+    if (p < 0 || p > clen) return;
+    atomicAdd(side[i] ? &left[p] : &right[p], 1);
+}
+
+// One wave per query: the largest count over [beg, end] INCLUSIVE, clipped to [0, clen], of clipR (side 0) or clipL (side 1), and
+// the smallest position that holds it; (0, -1) for an interval that is empty after the clip.  Each lane keeps count : ~position as
+// one 64-bit key, so the wave's maximum prefers the smaller position among equal counts.  The arrays are counts as they stand:
+// no tile sums.
+__global__ __launch_bounds__(256) void clip_argmax_kernel(int32_t nq, const uint8_t* __restrict__ side, const int32_t* __restrict__ beg,
+                                                         const int32_t* __restrict__ end, const int32_t* __restrict__ right,
+                                                         const int32_t* __restrict__ left, int64_t clen,
+                                                         uint32_t* __restrict__ count_out, int32_t* __restrict__ pos_out)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int q = wave; q < nq; q += nwaves) {
+        int64_t a = beg[q], b = end[q];
+        if (a < 0) a = 0;
+        if (b > clen) b = clen;
+        const int32_t* data = side[q] ? left : right;
+        uint64_t key = 0;                                           // below every key of a position: ~p > 0 for p < 2^31
+        for (int64_t p = a + lane; p <= b; p += 64) {
+            const uint64_t k = ((uint64_t)(uint32_t)data[p] << 32) | (0xFFFFFFFFu - (uint32_t)p);
+            key = k > key ? k : key;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t hi = (uint32_t)__shfl_xor((int)(key >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)key, o);
+            const uint64_t k = ((uint64_t)hi << 32) | lo;
+            key = k > key ? k : key;
+        }
+        if (lane == 0) {
+            count_out[q] = a <= b ? (uint32_t)(key >> 32) : 0u;
+            pos_out[q] = a <= b ? (int32_t)(0xFFFFFFFFu - (uint32_t)key) : -1;
+        }
+    }
+}
+
 // One wave per query: the minimum of span[p] over [beg, end] INCLUSIVE, clipped to [0, clen]; an interval that is empty after
 // the clip answers 0.  sums: the tile offsets of the tiled scan.
 __global__ __launch_bounds__(256) void span_query_kernel(int32_t nq, const int32_t* __restrict__ beg, const int32_t* __restrict__ end,
@@ -285,6 +431,37 @@ hipError_t launch_span_scatter(const RefDev& ref, int32_t flank, int32_t min_map
 hipError_t launch_pair_scatter(const RefDev& ref, const RgTable& rg, int32_t flank, int32_t min_mapq, const im_dev_records& recs, int32_t* diff, hipStream_t stream)
 {
     return launch_scatter(pair_scatter_kernel, ref, rg, flank, min_mapq, recs, diff, stream);
+}
+
+hipError_t launch_clip_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const im_dev_records& recs, int32_t* right, int32_t* left,
+                               hipStream_t stream)
+{
+    if (recs.n <= 0) return hipSuccess;
+    ClipArgs A;
+    A.recs = recs; A.asc_off = ref.asc_off; A.len = ref.len; A.n_contigs = ref.n_contigs;
+    A.min_clip = min_clip; A.min_mapq = min_mapq; A.right = right; A.left = left;
+    const int blocks = (recs.n + kSpanBlock - 1) / kSpanBlock;
+    hipLaunchKernelGGL(clip_scatter_kernel, dim3(blocks), dim3(kSpanBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_clip_build(int64_t clen, int32_t n, const int32_t* pos, const uint8_t* side, int32_t* right, int32_t* left, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(right, 0, (size_t)(clen + 1) * sizeof(int32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(left, 0, (size_t)(clen + 1) * sizeof(int32_t), stream);
+    if (e != hipSuccess || n <= 0) return e;
+    hipLaunchKernelGGL(clip_build_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, pos, side, clen, right, left);
+    return hipGetLastError();
+}
+
+hipError_t launch_clip_argmax(int32_t nq, const uint8_t* side, const int32_t* beg, const int32_t* end, const int32_t* right, const int32_t* left,
+                              int64_t clen, uint32_t* count_out, int32_t* pos_out, hipStream_t stream)
+{
+    if (nq <= 0) return hipSuccess;
+    int b = (nq + 3) / 4;
+    if (b > 2048) b = 2048;
+    hipLaunchKernelGGL(clip_argmax_kernel, dim3(b), dim3(256), 0, stream, nq, side, beg, end, right, left, clen, count_out, pos_out);
+    return hipGetLastError();
 }
 
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,

@@ -329,6 +329,8 @@ typedef struct {
     /* record-at-a-time path: the match segments of the contig's pileup-eligible records (im_depth_build); -G: the M/=/X runs of its
      * eligible records (im_span_build); -P: the fragments of its concordant left mates (im_pairspan_build) */
     ivlist segs, runs, frags;
+    /* -C, record-at-a-time path: the clip events of the contig's eligible records, position and side (im_clip_build) */
+    int32_t* clip_pos; uint8_t* clip_side; int64_t n_clip, cap_clip;
     int depth_tid;              /* contig whose depth array is resident on the device, -1 = none */
     int pipe_mode;              /* device pipeline: depth queries go to the genome-wide array */
     int marker_floor;           /* multi-GPU: smallest start of a stale pair-table entry of an earlier contig on another rank */
@@ -949,7 +951,7 @@ static void genotype_of(int64_t rs, int64_t ns, int* best_out, int* gq_out)
     if (gq > 99) gq = 99;
     *best_out = best; *gq_out = (int)gq;
 }
-/* more_keys: what the record's FORMAT has behind GT:AD:GQ ("" or ":DM:DFC"; the caller prints the values) */
+/* more_keys: what the record's FORMAT has behind GT:AD:GQ ("", ":DM:DFC", ":CB:CS" or both; the caller prints the values) */
 static void print_gt_ad_gq(const char* more_keys, int64_t ref_count, int64_t alt_count)
 {
     int best, gq;
@@ -967,14 +969,24 @@ static void print_depth_evidence(const variant_t* v)
     for (int k = 0; k < 3; k++) { if (v->dm_cached[k] == DEPTH_EV_NONE) printf("%s.", k ? "," : ""); else printf("%s%u", k ? "," : "", v->dm_cached[k]); }
     if (den == 0 || in == DEPTH_EV_NONE) printf(":."); else printf(":%llu", (unsigned long long)((num + den / 2) / den));
 }
+/* -C: the values of CB and CS.  CB in the coordinates of POS and END: a right clip at array position p is the coordinate p, a
+ * left clip at p is p + 1; a side without clipped reads prints . and 0 */
+static void print_clip_evidence(const variant_t* v)
+{
+    printf(":");
+    if (v->cs_cached[0] > 0) printf("%d,", (int)v->cb_cached[0]); else printf(".,");
+    if (v->cs_cached[1] > 0) printf("%d", (int)v->cb_cached[1] + 1); else printf(".");
+    printf(":%u,%u", v->cs_cached[0], v->cs_cached[1]);
+}
 static void print_genotype(const variant_t* v)
 {
-    const char* more_keys = v->dm_valid ? ":DM:DFC" : "";
+    const char* more_keys = v->dm_valid ? (v->cb_valid ? ":DM:DFC:CB:CS" : ":DM:DFC") : (v->cb_valid ? ":CB:CS" : "");
     /* a PAIRED_READ record has no precise breakpoint to count spanning reads at; with -P its rs_cached is RP, the thinnest depth
      * of concordant fragments over [POS, max(END, BP_END)] */
     if ((v->evdnctype == EV_PAIRED_READ && !g_pair_counts) || !v->rs_valid) printf("\tGT:AD:GQ%s\t./.:.,%u:.", more_keys, v->support);
     else print_gt_ad_gq(more_keys, (int64_t)v->rs_cached, (int64_t)v->support);
     if (v->dm_valid) print_depth_evidence(v);
+    if (v->cb_valid) print_clip_evidence(v);
 }
 
 /* the span (pair: 0) or pair-span (pair: 1) minima over m > 0 intervals of one contig, as one query */
@@ -1357,6 +1369,49 @@ static void print_variants(driver* d, variant_list* vs)
             }
         }
         free(beg); free(end); free(med); free(who);
+    }
+    /* ... -C: the same deletions get the clipped reads at their two breakpoints: per record one arg-max over the right clips
+     * around POS and one over the left clips around END - 1 (a PAIRED_READ record has no precise breakpoint: both over everything
+     * between its two), all of a flush in one call (the device clips to the contig) ... */
+    for (int i = 0; i < out.n; i++) out.v[i]->cb_valid = 0;
+    if (g_clip_evidence && out.n > 0) {
+        int32_t* beg = xmalloc(sizeof(int32_t) * 2 * (size_t)out.n);
+        int32_t* end = xmalloc(sizeof(int32_t) * 2 * (size_t)out.n);
+        uint8_t* side = xmalloc(2 * (size_t)out.n);
+        uint32_t* cnt = xmalloc(sizeof(uint32_t) * 2 * (size_t)out.n);
+        int32_t* at = xmalloc(sizeof(int32_t) * 2 * (size_t)out.n);
+        int* who = xmalloc(sizeof(int) * (size_t)out.n);
+        int m = 0;
+        for (int i = 0; i < out.n; i++) {
+            const variant_t* v = out.v[i];
+            if (v->type != CLS_DELETION) continue;
+            int pos, endpos, bp_end;
+            vcf_coordinates(v, &pos, &endpos, &bp_end);
+            if (endpos - pos < DEPTH_EV_MIN_LEN) continue;
+            const int w = CLIP_EV_SLACK, amb = bp_end > endpos ? bp_end - endpos : 0, hi = bp_end > endpos ? bp_end : endpos;
+            side[2 * m] = 0; side[2 * m + 1] = 1;
+            if (v->evdnctype == EV_PAIRED_READ) {
+                beg[2 * m] = beg[2 * m + 1] = pos - w; end[2 * m] = end[2 * m + 1] = hi + w;
+            } else {
+                beg[2 * m] = pos - w; end[2 * m] = pos + amb + w;
+                beg[2 * m + 1] = endpos - 1 - w; end[2 * m + 1] = endpos - 1 + amb + w;
+            }
+            who[m++] = i;
+        }
+        if (m > 0) {
+            gpu_wait(d);
+            pthread_mutex_lock(&g_query_mu);
+            const int qrc = d->pipe_mode ? im_clip_query_tid(d->gpu, out.v[who[0]]->tid, 2 * m, side, beg, end, cnt, at)      /* a flush lies on one contig */
+                                         : im_clip_query(d->gpu, 2 * m, side, beg, end, cnt, at);
+            pthread_mutex_unlock(&g_query_mu);
+            if (qrc != IM_OK) fatalf("im_clip_query: %s", im_last_error(d->gpu));
+            for (int q = 0; q < m; q++) {
+                variant_t* v = out.v[who[q]];
+                for (int k = 0; k < 2; k++) { v->cs_cached[k] = cnt[2 * q + k]; v->cb_cached[k] = at[2 * q + k]; }
+                v->cb_valid = 1;
+            }
+        }
+        free(beg); free(end); free(side); free(cnt); free(at); free(who);
     }
     /* ... and out they go */
     for (int i = 0; i < out.n; i++) emit_variant(d, out.v[i]);

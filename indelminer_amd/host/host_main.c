@@ -40,6 +40,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    concordant pairs whose fragment spans the deletion\n");
     fprintf(file, "\t-D, with -G: depth evidence for deletions of 50 bp and more\n");
     fprintf(file, "\t    (FORMAT DM:DFC, median depth inside against the flanks)\n");
+    fprintf(file, "\t-C, with -G: clipped-read breakpoints for the same deletions\n");
+    fprintf(file, "\t    (FORMAT CB:CS, where soft-clipped reads pile up and how many)\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -82,7 +84,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPD")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDC")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -110,6 +112,7 @@ int main(int argc, char** argv)
         case 'A': g_known_counts = 1; break;                        /* not an option of the reference */
         case 'P': g_pair_counts = 1; break;                         /* not an option of the reference */
         case 'D': g_depth_evidence = 1; break;                      /* not an option of the reference */
+        case 'C': g_clip_evidence = 1; break;                       /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -167,11 +170,21 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: depth evidence (-D) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -C: behind the refusals of -G, -A, -P and -D, in the same order as -D's */
+    if (g_clip_evidence) {
+        if (g_vcfname != NULL) { fprintf(stderr, "indelminer: -C is not available with a VCF argument (annotate mode)\n"); return EXIT_FAILURE; }
+        if (!g_genotype) { fprintf(stderr, "indelminer: -C needs -G\n"); return EXIT_FAILURE; }
+        /* the slack, and the windows of a PAIRED_READ record, reach outside a walked stretch */
+        if (O.region != NULL) { fprintf(stderr, "indelminer: -C is not available with -c\n"); return EXIT_FAILURE; }
+        if (!CLIP_API_PRESENT) {
+            fprintf(stderr, "indelminer: clip evidence (-C) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) g_genotype = g_pair_counts = g_depth_evidence = 0;    /* -o detailed has no columns to add to */
+        if (strcmp(O.outputformat, "detailed") == 0) g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = 0;    /* -o detailed has no columns to add to */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {

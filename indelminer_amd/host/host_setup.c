@@ -51,10 +51,18 @@ static void print_output_header(void)
             printf("##FORMAT=<ID=DM,Number=3,Type=Integer,Description=\"Median depth over the deleted bases POS+1..END, over the %d bases in front of them and over the %d bases behind them\">\n", DEPTH_EV_FLANK, DEPTH_EV_FLANK);
             printf("##FORMAT=<ID=DFC,Number=1,Type=Integer,Description=\"Depth fold change in thousandths: the median inside the deletion over the mean of the flank medians\">\n");
         }
+        if (g_clip_evidence) {
+            /* -C: no reference counterpart */
+            printf("##FORMAT=<ID=CB,Number=2,Type=Integer,Description=\"Breakpoints by clipped reads, in the coordinates of POS and END: where most soft-clipped reads stop aligning left of the deletion, and the base in front of where most start aligning right of it\">\n");
+            printf("##FORMAT=<ID=CS,Number=2,Type=Integer,Description=\"Clipped reads at the two positions of CB\">\n");
+        }
         if (g_pair_counts) printf("##pairedReadAD=\"PAIRED_READ records: AD = concordant pairs spanning the deletion with -n bases on each side (lower bound), pairs supporting it\"\n");
         if (g_depth_evidence)
             printf("##depthEvidence=\"DELETION records with END-POS >= %d: DM = lower median (the smallest depth that at least half of the positions, rounded up, do not exceed) of the per-position depth over the deleted bases, the %d bases in front and the %d bases behind, each clipped to the contig, . for a flank without bases; DFC = 1000 * inside / mean of the flanks present, rounded, . without a flank or with flanks of depth 0. Depth = records samtools' pileup would count whose M/=/X covers the position, capped at 4095 per position; these are array counts without the pileup's limit of 8000 records, so DM can exceed what DP= implies at such loci\"\n",
                    DEPTH_EV_MIN_LEN, DEPTH_EV_FLANK, DEPTH_EV_FLANK);
+        if (g_clip_evidence)
+            printf("##clipEvidence=\"DELETION records with END-POS >= %d: a clipped read is an alignment samtools' pileup would count, with mapping quality of at least -q, whose first (last) CIGAR operation apart from hard clips is a soft clip of at least %d bases and whose CIGAR consumes reference; it counts at its first aligned base (left clip) or behind its last one (right clip). CS = the largest number of right clips on one position within %d positions of POS .. POS+(BP_END-END), and of left clips on one position within %d positions of END .. BP_END (PAIRED_READ records: both between POS-%d and max(END,BP_END)+%d); CB = the two positions, the smaller one among equal counts, printed so that a deletion whose clipped reads agree with the call shows its own POS,END; . and 0 for a side without clipped reads\"\n",
+                   DEPTH_EV_MIN_LEN, CLIP_EV_MIN_CLIP, CLIP_EV_SLACK, CLIP_EV_SLACK, CLIP_EV_SLACK, CLIP_EV_SLACK);
         printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", g_sample_name);
     } else if (strncmp(O.outputformat, "vcf", 3) == 0) printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
     fflush(OUT);
@@ -335,6 +343,35 @@ static void build_counted(driver* d, int pair, int32_t tid, const ivlist* l, int
     phase_time(pair ? "pair-span array (device)" : "span array (device)");
 }
 
+/* -C: the record rule of the device's clip scatter (include/indelminer_amd.h), for the record-at-a-time path: a soft clip of
+ * CLIP_EV_MIN_CLIP bases as the first or last operation apart from H, on a record that consumes reference.  The device drops
+ * positions outside the contig; here only what an int32 does not hold. */
+static void clip_push(driver* d, int64_t pos, int side)
+{
+    if (pos < 0 || pos > INT32_MAX) return;
+    if (d->n_clip == d->cap_clip) {
+        d->cap_clip = d->cap_clip ? d->cap_clip * 2 : (1 << 14);
+        d->clip_pos = xrealloc(d->clip_pos, sizeof(int32_t) * (size_t)d->cap_clip);
+        d->clip_side = xrealloc(d->clip_side, (size_t)d->cap_clip);
+    }
+    d->clip_pos[d->n_clip] = (int32_t)pos; d->clip_side[d->n_clip] = (uint8_t)side; d->n_clip++;
+}
+static void clip_events(driver* d, const bam_record* b)
+{
+    if (b->tid < 0 || b->tid >= d->hdr->n_targets || (b->flag & (0x4 | 0x100 | 0x200 | 0x400)) || (int)b->mapq < O.qthreshold) return;
+    const uint8_t* cig = BAMR_CIGAR(b);
+    int first = -1, last = -1, consumes = 0;
+    int64_t refend = b->pos;
+    for (int kk = 0; kk < b->n_cigar; kk++) {
+        const int op = CIG_OP(bamr_cigar_at(cig, kk)), len = CIG_LEN(bamr_cigar_at(cig, kk));
+        if (op != OP_H) { if (first < 0) first = kk; last = kk; }
+        if (op == OP_M || op == OP_EQ || op == OP_X || op == OP_D || op == OP_N) { consumes = 1; refend += len; }
+    }
+    if (!consumes) return;
+    if (CIG_OP(bamr_cigar_at(cig, last)) == OP_S && CIG_LEN(bamr_cigar_at(cig, last)) >= CLIP_EV_MIN_CLIP) clip_push(d, refend, 0);
+    if (CIG_OP(bamr_cigar_at(cig, first)) == OP_S && CIG_LEN(bamr_cigar_at(cig, first)) >= CLIP_EV_MIN_CLIP) clip_push(d, b->pos, 1);
+}
+
 static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_reader* r)
 {
     d->n_items = 0; d->n_flushes = 0;
@@ -342,7 +379,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
     bam_region_iter it;
     bam_record b; memset(&b, 0, sizeof b);
     if (bam_region_begin(&it, r, d->idx, tid, beg, end) != 0) fatalf("cannot seek in %s", d->bam_name);
-    d->segs.n = 0; d->runs.n = 0; d->frags.n = 0;
+    d->segs.n = 0; d->runs.n = 0; d->frags.n = 0; d->n_clip = 0;
     const int whole = (beg <= 0 && end >= d->hdr->target_len[tid]);
     volatile int died = 0;              /* a record the reference dies on ended the pass: the flushes in front of it are still to print */
     t_is_main_thread_of_passA = 1;
@@ -378,6 +415,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
                 if (op == OP_D || op == OP_N) x += len;
             }
         }
+        if (CLIP_ON) clip_events(d, &b);
         dispatch_record(d, &b);
         if (PAIR_ON && concordant_left_mate(d, &b)) {
             /* -P: the fragment [pos, pos + isize) of the pair, clipped to what an int32 start and length hold (the device clips
@@ -399,6 +437,12 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
     phase_time("depth array (device)");
     if (SPAN_ON) build_counted(d, 0, tid, &d->runs, (int32_t)O.ethreshold);
     if (PAIR_ON) build_counted(d, 1, tid, &d->frags, (int32_t)O.ethreshold);
+    if (CLIP_ON) {
+        gpu_wait(d);
+        if (d->n_clip > INT32_MAX) fatalf("more than 2^31 clipped reads on one contig");
+        if (im_clip_build(d->gpu, d->seqlen[tid], (int32_t)d->n_clip, d->clip_pos, d->clip_side) != IM_OK) fatalf("im_clip_build: %s", im_last_error(d->gpu));
+        phase_time("clip arrays (device)");
+    }
 
     im_read_result* res = NULL;
     if (d->cb.n > 0) {

@@ -142,6 +142,21 @@ extern int im_depth_median(im_ctx*, int32_t, const int32_t*, const int32_t*, uin
 #define DEPTH_EV_MIN_LEN 50        /* END - POS of the shortest deletion that gets the fields */
 #define DEPTH_EV_FLANK 1000        /* bases of each flank */
 #define DEPTH_EV_NONE 0xFFFFFFFFu  /* what the device answers for an interval without positions */
+/* -C, with -G: clipped-read breakpoint evidence for the same deletions (FORMAT CB:CS) -- on either side of the deletion the position
+ * most reads of at least CLIP_EV_MIN_CLIP soft-clipped bases stop (or start) aligning at, within CLIP_EV_SLACK of where the record
+ * puts the breakpoint, and how many do: the device's arg-max over two arrays of clipped-read counts.  Not an option of the
+ * reference; referenced weakly. */
+static int g_clip_evidence = 0;
+extern int im_clip_enable(im_ctx*, int32_t, int32_t) __attribute__((weak));
+extern int im_dev_clip_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
+extern int im_clip_reset(im_ctx*, int32_t, void*) __attribute__((weak));
+extern int im_clip_query_tid(im_ctx*, int32_t, int32_t, const uint8_t*, const int32_t*, const int32_t*, uint32_t*, int32_t*) __attribute__((weak));
+extern int im_clip_build(im_ctx*, int64_t, int32_t, const int32_t*, const uint8_t*) __attribute__((weak));
+extern int im_clip_query(im_ctx*, int32_t, const uint8_t*, const int32_t*, const int32_t*, uint32_t*, int32_t*) __attribute__((weak));
+#define CLIP_ON (g_clip_evidence)                  /* the walk scatters the two clip arrays */
+#define CLIP_API_PRESENT (im_clip_enable && im_dev_clip_scatter && im_clip_reset && im_clip_query_tid && im_clip_build && im_clip_query)
+#define CLIP_EV_MIN_CLIP 20        /* soft-clipped bases of the shortest clip that counts */
+#define CLIP_EV_SLACK 10           /* positions the windows reach beyond where the record puts its breakpoints */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that

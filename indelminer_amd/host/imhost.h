@@ -77,6 +77,10 @@ typedef struct {
     /* -D: median depth inside the deletion, over its left and over its right flank, asked for in the same way */
     uint32_t  dm_cached[3];
     int       dm_valid;
+    /* -C: the clipped reads left and right of the deletion, (count, array position) each, asked for in the same way */
+    uint32_t  cs_cached[2];
+    int32_t   cb_cached[2];
+    int       cb_valid;
 } variant_t;
 
 typedef struct {
