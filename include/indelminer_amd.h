@@ -574,6 +574,56 @@ int im_clip_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const uint8_t* side, 
 int im_clip_build(im_ctx* ctx, int64_t contig_len, int32_t n, const int32_t* pos, const uint8_t* side);
 int im_clip_query(im_ctx* ctx, int32_t n, const uint8_t* side, const int32_t* beg, const int32_t* end, uint32_t* count_out, int32_t* pos_out);
 
+/* Clip tails, what the clipped reads were clipped OF (-V).  The counts above say where reads stop; an adapter, a chimera, an insertion
+ * or an inversion leaves the same pile.  At a deletion of the 0-based bases [a, b) the clipped tail of a read from the left is the
+ * reference from b on, and the clipped head of a read from the right is the reference in front of a.  A keyed table keeps the
+ * clipped bases nearest the junction; a query compares them with the resident reference behind the partner breakpoint.
+ *
+ * WHICH RECORDS STORE AN ENTRY.  The record rule is the one above, unchanged: the same eligibility, the same first / last operation
+ * apart from H, c = min_clip, q = min_mapq, refend and pos inside [0, length].  Read bases are counted from 0 in the record's packed
+ * bases, codes as BAM packs them (A C G T = 1 2 4 8).
+ *   RIGHT ENTRY at (tid, refend): a right clip of L >= c bases; n = min(L, 32); base i, i = 0 .. n - 1, is read base l_seq - L + i
+ *                                 (base 0 is the first clipped base, the one nearest the junction);
+ *   LEFT ENTRY at (tid, pos):     a left clip of L >= c bases;  n = min(L, 32); base i is read base L - 1 - i (the head, reversed:
+ *                                 base 0 is again the one nearest the junction).
+ * An entry is stored only if all its n codes are A, C, G or T and the bases lie inside the record's packed-base bytes: l_seq > 0,
+ * L <= l_seq, and the (l_seq + 1) / 2 bytes behind the CIGAR end inside the record.  Otherwise nothing is stored for that side; an N
+ * beyond the first n clipped bases does not matter.  The counts of clipR / clipL are not touched by any of this.  Both delivered
+ * record forms are taken (im_dev_records): the packed bases sit behind the CIGAR with base qualities behind them or without.
+ *
+ * A QUERY is (tid, pr, pl), a right-clip position and a left-clip position in array coordinates (for the deletion [a, b): pr = a,
+ * pl = b), with max_shift S, 0 <= S <= 32.  For a shift s = 0 .. S
+ *   a right entry at (tid, pr) MATCHES iff at most n >> 4 of its n bases differ from what is expected: base i is ref[pl + s + i];
+ *   a left entry at (tid, pl) MATCHES iff at most n >> 4 of its n bases differ from what is expected: base i is ref[pr - 1 - s - i].
+ * A reference position outside [0, length) and a reference byte other than A, C, G, T (the resident reference is upper-cased ASCII)
+ * are mismatches.  The shift is the micro-homology an aligner extends into before it clips: with deleted bases [a, b) and a homology
+ * of h bases the piles stand at a + h and b, or at a and b - h, and both sides match at s = h.  vR(s) and vL(s) are the matching
+ * entries of either side; the chosen s has the largest vR(s) + vL(s), the smallest shift among equals.  The answer is vR, vL and s of
+ * that shift, and the numbers of entries stored at (tid, pr, right) and (tid, pl, left), whatever their bases.  A query with pl <= pr
+ * answers 0, 0, -1; a best sum of 0 answers 0, 0, -1 as well.
+ *
+ * THE TABLE has 2^log2_slots slots of 16 bytes (6 <= log2_slots <= 30): a multimap with open addressing; the home slot of an entry
+ * is ((key >> 6) * 0x9E3779B97F4A7C15) >> (64 - log2_slots) with key = 1 << 63 | tid << 39 | position << 7 | side << 6 | n, probing is
+ * linear and wraps past the last slot.  Only half of the slots are ever taken: the number of entries stored is exactly
+ * min(entries asked for, 2^log2_slots / 2) and the rest are counted as dropped.  Once dropped > 0 an answer could miss entries, so
+ * im_cliptail_verify then returns IM_OK and fills EVERY output of the call with 0xFFFFFFFF (shift: -1): no answer, not a wrong one.
+ *
+ * im_cliptail_enable allocates the table (16 << log2_slots bytes of HBM, on this call only; the reference must be set, at most 2^24
+ * contigs) and fixes min_clip >= 1 and min_mapq: a second call with other values is refused.  im_dev_cliptail_scatter adds the
+ * entries of a chunk of delivered records (one launch of its own, asynchronous).  im_cliptail_add adds n entries of contig tid the
+ * caller names -- it applies the record rule itself -- as position, side (0: right, 1: left), number of bases 1 .. 32 and
+ * planes[2 i], planes[2 i + 1]: bit k of the first word is the low bit and of the second the high bit of base k's code A C G T =
+ * 0 1 2 3 (bits from n on are ignored); positions outside [0, length] are dropped without counting; synchronous.  im_cliptail_verify
+ * answers nq queries of contig tid; synchronous, on the context's stream.  im_cliptail_reset puts all slots and both counters back to
+ * zero.  im_cliptail_stats gives the entries stored and dropped since the last reset; synchronous. */
+int im_cliptail_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq, int32_t log2_slots);
+int im_dev_cliptail_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream);
+int im_cliptail_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, const uint8_t* side, const uint8_t* nbases, const uint32_t* planes);
+int im_cliptail_verify(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* pr, const int32_t* pl, int32_t max_shift, uint32_t* v_right,
+                       uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left);
+int im_cliptail_reset(im_ctx* ctx, void* stream);
+int im_cliptail_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

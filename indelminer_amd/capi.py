@@ -229,6 +229,12 @@ def lib():
         L.im_clip_query_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_clip_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.im_clip_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_cliptail_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.im_dev_cliptail_scatter.argtypes = [C.c_void_p, C.POINTER(DevRecords), C.c_void_p]
+        L.im_cliptail_add.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_cliptail_verify.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_cliptail_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.im_cliptail_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_capture_begin.argtypes = [C.c_void_p, C.c_void_p]
@@ -582,6 +588,43 @@ class Context:
 
     def clip_query(self, side, beg, end):
         return self._clip_query(lib().im_clip_query, side, beg, end)
+
+    def cliptail_enable(self, min_clip, min_mapq, log2_slots):
+        """the keyed table of clipped bases (-V): 2^log2_slots slots of 16 bytes, half of them usable"""
+        self._check(lib().im_cliptail_enable(self.h, int(min_clip), int(min_mapq), int(log2_slots)))
+
+    def cliptail_scatter(self, recs, stream=None):
+        """DevRecords -> one entry per clipping end of the chunk's clipped reads (asynchronous)"""
+        self._check(lib().im_dev_cliptail_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
+
+    def cliptail_add(self, tid, pos, side, nbases, planes):
+        """entries of contig tid as the caller found them: position, side (0: right, 1: left), bases 1 .. 32, planes[i] = (low bits, high bits)"""
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        side = np.ascontiguousarray(side, dtype=np.uint8)
+        nbases = np.ascontiguousarray(nbases, dtype=np.uint8)
+        planes = np.ascontiguousarray(planes, dtype=np.uint32).reshape(-1)
+        assert len(pos) == len(side) == len(nbases) and len(planes) == 2 * len(pos)
+        self._check(lib().im_cliptail_add(self.h, int(tid), len(pos), _ptr(pos), _ptr(side), _ptr(nbases), _ptr(planes)))
+
+    def cliptail_verify(self, tid, pr, pl, max_shift=32):
+        """per query (pr, pl) on contig tid: (v_right, v_left, shift, stored_right, stored_left); after an overflow every value is
+        0xFFFFFFFF and every shift -1"""
+        pr = np.ascontiguousarray(pr, dtype=np.int32)
+        pl = np.ascontiguousarray(pl, dtype=np.int32)
+        assert len(pr) == len(pl)
+        n = len(pr)
+        out = [np.zeros(max(n, 1), dtype=np.int32 if k == 2 else np.uint32) for k in range(5)]
+        self._check(lib().im_cliptail_verify(self.h, int(tid), n, _ptr(pr), _ptr(pl), int(max_shift), *[_ptr(o) for o in out]))
+        return tuple(o[:n] for o in out)
+
+    def cliptail_reset(self, stream=None):
+        self._check(lib().im_cliptail_reset(self.h, self.stream if stream is None else stream))
+
+    def cliptail_stats(self):
+        """(entries stored, entries dropped) since the last reset"""
+        stored, dropped = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().im_cliptail_stats(self.h, C.byref(stored), C.byref(dropped)))
+        return int(stored.value), int(dropped.value)
 
     def cluster_sr(self, cls, b1, b2, marker=2**31 - 1, tie_desc=0):
         n = len(cls)

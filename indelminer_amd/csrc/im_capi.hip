@@ -63,6 +63,9 @@ struct im_ctx {
     GenomeArray all_depth, all_span, all_pair;
     // genome-wide clipped-read counts, right and left (im_clip_enable): flank holds min_clip; never scanned, their sums stay null
     GenomeArray all_clip_r, all_clip_l;
+    // -V: the keyed table of clipped bases (im_cliptail_enable); slots null: not enabled.  min_clip and min_mapq are its scatter's
+    im::TailTable tail = {nullptr, nullptr, 0};
+    int32_t tail_min_clip = 0, tail_min_mapq = 0;
     // the median queries' histograms of queries of several slabs (im::launch_depth_median): zeros between calls, sized by the call that
     // needed the most; med_dirty: a call did not get to its end, the next one clears them
     uint32_t* med_scratch = nullptr;
@@ -152,6 +155,10 @@ void free_reference(im_ctx* ctx)
         g->data = nullptr; g->sums = nullptr;
     }
     ctx->h_asc_off.clear(); ctx->h_len.clear(); ctx->ref_total = 0;
+    // the clip-tail table is keyed by the contigs of the reference that goes
+    if (ctx->tail.slots) (void)hipFree(ctx->tail.slots);
+    if (ctx->tail.counters) (void)hipFree(ctx->tail.counters);
+    ctx->tail = {nullptr, nullptr, 0};
 }
 
 void free_array(ContigArray& a)
@@ -1069,6 +1076,125 @@ int im_clip_query(im_ctx* ctx, int32_t n, const uint8_t* side, const int32_t* be
     if (!ctx) return IM_E_ARG;
     const ArgMaxSide x = {side, ctx->clip_l.data, pos_out};
     return query_contig_array(ctx, &im_ctx::clip_r, "im_clip", n, beg, end, kArgMax, count_out, &x);
+}
+
+// ---- clip tails: the clipped bases of clipped reads against the reference behind the partner breakpoint ----------
+
+int im_cliptail_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq, int32_t log2_slots)
+{
+    if (!ctx) return IM_E_ARG;
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    if (min_clip < 1) { set_err(ctx, "im_cliptail_enable: min_clip %d, must be >= 1", min_clip); return IM_E_ARG; }
+    if (log2_slots < 6 || log2_slots > 30) { set_err(ctx, "im_cliptail_enable: log2_slots %d, must be 6 .. 30", log2_slots); return IM_E_ARG; }
+    if (ctx->n_contigs > (1 << 24)) { set_err(ctx, "im_cliptail_enable: more than 2^24 contigs"); return IM_E_ARG; }
+    if (ctx->tail.slots) {
+        if (min_clip != ctx->tail_min_clip || min_mapq != ctx->tail_min_mapq || log2_slots != ctx->tail.log2_slots) {
+            set_err(ctx, "im_cliptail_enable: already enabled with min_clip %d, min_mapq %d, log2_slots %d", ctx->tail_min_clip, ctx->tail_min_mapq, ctx->tail.log2_slots);
+            return IM_E_ARG;
+        }
+        return IM_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)16 << log2_slots;
+    unsigned long long* slots = nullptr;
+    unsigned long long* counters = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&slots, bytes));
+    if (hipMalloc((void**)&counters, 2 * sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(slots); set_err(ctx, "im_cliptail_enable: out of device memory"); return IM_E_HIP; }
+    ctx->tail = {slots, counters, log2_slots};
+    ctx->tail_min_clip = min_clip; ctx->tail_min_mapq = min_mapq;
+    HIP_TRY(ctx, hipMemsetAsync(slots, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+int im_dev_cliptail_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
+{
+    if (!ctx || !recs) return IM_E_ARG;
+    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
+    if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, im::launch_cliptail_scatter(ref_dev(ctx), ctx->tail_min_clip, ctx->tail_min_mapq, *recs, ctx->tail, (hipStream_t)stream));
+    return IM_OK;
+}
+
+// the host names the entries: checked here, staged through the workspace, one lane inserts each, wait
+int im_cliptail_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, const uint8_t* side, const uint8_t* nbases, const uint32_t* planes)
+{
+    if (!ctx || n < 0 || (n > 0 && (!pos || !side || !nbases || !planes))) return IM_E_ARG;
+    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
+    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    for (int32_t i = 0; i < n; i++) {
+        if (side[i] > 1) { set_err(ctx, "im_cliptail_add: entry %d: side %d, must be 0 (right) or 1 (left)", i, (int)side[i]); return IM_E_ARG; }
+        if (nbases[i] < 1 || nbases[i] > 32) { set_err(ctx, "im_cliptail_add: entry %d: %d bases, must be 1 .. 32", i, (int)nbases[i]); return IM_E_ARG; }
+    }
+    if (n == 0) return IM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = up256(sizeof(int32_t) * (size_t)n);
+    int rc = ensure_ws(ctx, 5 * sb);
+    if (rc) return rc;
+    int32_t* d_pos = (int32_t*)ctx->ws;
+    uint32_t* d_planes = (uint32_t*)((char*)ctx->ws + sb);          // two words per entry
+    uint8_t* d_side = (uint8_t*)ctx->ws + 3 * sb;
+    uint8_t* d_nb = (uint8_t*)ctx->ws + 4 * sb;
+    HIP_TRY(ctx, hipMemcpyAsync(d_pos, pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_planes, planes, 2 * sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_side, side, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_nb, nbases, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, im::launch_cliptail_add(n, tid, ctx->h_len[tid], d_pos, d_side, d_nb, d_planes, ctx->tail, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+// [pr][pl] in, one launch, the five answers and the two counters back, one wait; after an overflow every answer is "none"
+int im_cliptail_verify(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* pr, const int32_t* pl, int32_t max_shift, uint32_t* v_right,
+                       uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left)
+{
+    if (!ctx || nq < 0) return IM_E_ARG;
+    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
+    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    if (max_shift < 0 || max_shift > 32) { set_err(ctx, "im_cliptail_verify: max_shift %d, must be 0 .. 32", max_shift); return IM_E_ARG; }
+    if (nq == 0) return IM_OK;
+    if (!pr || !pl || !v_right || !v_left || !shift || !stored_right || !stored_left) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = up256(sizeof(int32_t) * (size_t)nq);
+    int rc = ensure_ws(ctx, 7 * sb);
+    if (rc) return rc;
+    int32_t* d_in[2]; uint32_t* d_out[5];
+    for (int k = 0; k < 2; k++) d_in[k] = (int32_t*)((char*)ctx->ws + k * sb);
+    for (int k = 0; k < 5; k++) d_out[k] = (uint32_t*)((char*)ctx->ws + (2 + k) * sb);
+    uint32_t* h_out[5] = {v_right, v_left, (uint32_t*)shift, stored_right, stored_left};
+    unsigned long long counters[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(d_in[0], pr, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_in[1], pl, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, im::launch_cliptail_verify(nq, tid, d_in[0], d_in[1], max_shift, ctx->ref_ascii + ctx->h_asc_off[tid], ctx->h_len[tid], ctx->tail,
+                                            d_out[0], d_out[1], (int32_t*)d_out[2], d_out[3], d_out[4], ctx->stream));
+    for (int k = 0; k < 5; k++) HIP_TRY(ctx, hipMemcpyAsync(h_out[k], d_out[k], sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (counters[1] > 0) for (int k = 0; k < 5; k++) memset(h_out[k], 0xFF, sizeof(uint32_t) * (size_t)nq);     // no answer, not a wrong one
+    return IM_OK;
+}
+
+int im_cliptail_reset(im_ctx* ctx, void* stream)
+{
+    if (!ctx || !ctx->tail.slots) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->tail.slots, 0, (size_t)16 << ctx->tail.log2_slots, (hipStream_t)stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->tail.counters, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream));
+    return IM_OK;
+}
+
+int im_cliptail_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped)
+{
+    if (!ctx || !ctx->tail.slots || !stored || !dropped) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long counters[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned long long half = 1ull << (ctx->tail.log2_slots - 1);
+    *stored = counters[0] < half ? counters[0] : half; *dropped = counters[1];
+    return IM_OK;
 }
 
 int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64_t* t_off,

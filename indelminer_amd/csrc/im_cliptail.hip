@@ -1,0 +1,348 @@
+// im_cliptail.hip -- the clipped bases of clipped reads (-V): kept in a keyed table, compared against the reference behind the
+// partner breakpoint (gfx950).  The definition is in include/indelminer_amd.h (seam 5, "Clip tails"); DESIGN.md 4.5f has the cost.
+//
+// A record that clips under -C's rule (im_spanrec.hpp: clip_decide, clip_refend -- the very code of clip_scatter_kernel) stores per
+// clipping end ONE ENTRY: the n = min(clip length, 32) read bases nearest the junction, base 0 the nearest, at the key
+// (tid, position, side), position = refend for a right clip (side 0) and pos for a left clip (side 1).  Nothing is stored when one
+// of the n bases is not A / C / G / T or when the packed bases do not lie inside the record.
+//
+// THE TABLE: 2^k slots of 16 bytes, open addressing, a multimap.
+//   word 0   the key: bit 63 set (an empty slot is 0) | tid << 39 | position << 7 | side << 6 | n           (tid < 2^24, n = 1 .. 32)
+//   word 1   the payload: the n bases as 2-bit codes (A 0, C 1, G 2, T 3) in two planes, low bits in bits 0 .. 31, high bits in
+//            bits 32 .. 63; bit i of a plane belongs to the base at distance i from the junction
+// The home slot of a key is ((key >> 6) * 0x9E3779B97F4A7C15) >> (64 - k): n does not enter, so every entry of one (tid, position,
+// side) lies on one probe run.  Probing is linear and wraps.  An insert first draws a ticket (returning atomic add); tickets at or
+// above 2^k / 2 store nothing and are counted in `dropped`, so at least half of the slots stay empty, every probe run ends at an
+// empty slot, and the number stored is exactly min(inserts, 2^k / 2).  A slot is claimed by a 64-bit compare-and-swap from 0, its
+// payload is a plain store behind it: readers are later launches.  Every probe loop is bounded by the slot count as well.
+//
+//   cliptail_scatter   one lane per delivered record; the ~1 % of lanes that clip read their packed bases and insert, on tickets
+//                      their workgroup draws with one atomic add
+//   cliptail_add       one lane per entry the host names (the record-at-a-time path)
+//   cliptail_verify    one wave per query (tid, pr, pl): see the kernel
+
+#include "im_device.hpp"
+#include "im_spanrec.hpp"
+
+namespace im {
+namespace {
+
+constexpr int kTailBlock = 1024;      // records of a scatter workgroup: one ticket draw each (see cliptail_scatter_kernel)
+constexpr int kTailWaveBlock = 256;   // threads of the add and verify kernels
+// An entry holds at most kTailBases bases and a query tries the shifts 0 .. S <= kTailMaxShift, so a comparison reaches at most
+// kTailMaxShift + kTailBases = 64 bases behind the partner breakpoint: EXACTLY ONE WAVEFRONT of reference bases per side, one base
+// per lane, turned into wave-uniform 64-bit planes by three ballots.  Neither constant can grow without a second window.
+constexpr int kTailBases = 32;
+constexpr int kTailMaxShift = 32;
+static_assert(kTailBases + kTailMaxShift == 64, "the reference window of a query is one wavefront");
+
+constexpr uint64_t kTailUsed = 1ull << 63;
+constexpr uint64_t kTailHashMul = 0x9E3779B97F4A7C15ull;
+
+__device__ __forceinline__ uint64_t tail_key(int32_t tid, int64_t pos, uint32_t side, uint32_t n)
+{
+    return kTailUsed | ((uint64_t)(uint32_t)tid << 39) | ((uint64_t)(uint32_t)pos << 7) | ((uint64_t)side << 6) | n;
+}
+
+__device__ __forceinline__ uint64_t tail_home(uint64_t key, int32_t log2_slots) { return ((key >> 6) * kTailHashMul) >> (64 - log2_slots); }
+
+// A ticket decides whether an entry is stored: tickets at or above half of the slots are counted in counters[1] and dropped.
+__device__ __forceinline__ bool tail_admit(const TailTable& T, unsigned long long ticket)
+{
+    if (ticket < (1ull << T.log2_slots) / 2ull) return true;
+    atomicAdd(&T.counters[1], 1ull);
+    return false;
+}
+
+// An admitted entry into the first empty slot of its key's probe run (there is one: half of the slots stay empty).
+__device__ __forceinline__ void tail_place(const TailTable& T, uint64_t key, uint64_t payload)
+{
+    const uint64_t slots = 1ull << T.log2_slots, mask = slots - 1ull;
+    uint64_t s = tail_home(key, T.log2_slots);
+    for (uint64_t step = 0; step < slots; step++, s = (s + 1ull) & mask) {
+        unsigned long long* k = &T.slots[2ull * s];
+        // the home slot gets the compare-and-swap at once (in a table at most half full it is mostly empty: one trip to memory,
+        // not two); further along a run a slot that reads non-zero stays taken and is passed by a load
+        if (step != 0ull && __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) continue;
+        if (atomicCAS(k, 0ull, (unsigned long long)key) == 0ull) { T.slots[2ull * s + 1ull] = payload; return; }
+    }
+}
+
+// One entry in, the ticket drawn by the lane itself (counters[0]: inserts): the record-at-a-time form.
+__device__ __forceinline__ void tail_insert(const TailTable& T, uint64_t key, uint64_t payload)
+{
+    if (tail_admit(T, atomicAdd(&T.counters[0], 1ull))) tail_place(T, key, payload);
+}
+
+// per nibble of x (a 4-bit base code each): bit 0 of the nibble set iff the code is one of 1, 2, 4, 8
+__device__ __forceinline__ uint32_t nib_one_hot(uint32_t x)
+{
+    const uint32_t s01 = x | (x >> 1), a01 = x & (x >> 1);
+    return (s01 ^ (s01 >> 2)) & ~a01 & ~(a01 >> 2) & 0x11111111u;
+}
+
+// bit 0 of each of the 8 nibbles -> bits 0 .. 7
+__device__ __forceinline__ uint32_t nib_gather(uint32_t a)
+{
+    a = (a | (a >> 3)) & 0x03030303u;
+    a = (a | (a >> 6)) & 0x000F000Fu;
+    return (a | (a >> 12)) & 0xFFu;
+}
+
+// The n <= 32 read bases lo .. lo + n - 1 of the packed bases at seq as planes in ASCENDING read order (bit k: base lo + k).
+// BAM packs two bases per byte, the earlier one in the HIGH nibble, and lo may be odd: the nibbles of every word are swapped so
+// that nibble m of the stream sits at bit 4 m, then the stream moves down by one nibble where lo is odd.  Reads 20 bytes from
+// seq + lo / 2, which stay inside the chunk buffer (>= 64 spare bytes behind the last record).  Returns whether all n are A/C/G/T.
+__device__ __forceinline__ bool tail_planes(const uint8_t* seq, uint32_t lo, uint32_t n, uint32_t* p_lo, uint32_t* p_hi)
+{
+    const uint8_t* at = seq + (lo >> 1);
+    uint32_t w[5];
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        const uint32_t x = ld_u32(at + 4 * j);
+        w[j] = ((x & 0x0F0F0F0Fu) << 4) | ((x >> 4) & 0x0F0F0F0Fu);
+    }
+    const bool odd = lo & 1u;
+    uint32_t lo_plane = 0, hi_plane = 0, ok = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t v = odd ? (w[j] >> 4) | (w[j + 1] << 28) : w[j];
+        // codes 1 2 4 8 = A C G T -> 0 1 2 3: the low bit is set for 2 and 8, the high bit for 4 and 8
+        lo_plane |= nib_gather(((v >> 1) | (v >> 3)) & 0x11111111u) << (8 * j);
+        hi_plane |= nib_gather(((v >> 2) | (v >> 3)) & 0x11111111u) << (8 * j);
+        ok |= nib_gather(nib_one_hot(v)) << (8 * j);
+    }
+    const uint32_t m = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u;
+    *p_lo = lo_plane & m; *p_hi = hi_plane & m;
+    return (ok & m) == m;
+}
+
+struct TailScatterArgs {
+    im_dev_records recs;
+    const int32_t* len;
+    int32_t n_contigs;
+    int32_t min_clip, min_mapq;
+    TailTable tab;
+};
+
+// what a lane of the scatter has to insert: at most one entry per clipping end
+struct TailPair { uint64_t key[2], payload[2]; uint32_t n; };
+
+__device__ __forceinline__ TailPair tail_entries(const TailScatterArgs& A, int64_t i)
+{
+    TailPair P; P.n = 0; P.key[0] = P.key[1] = P.payload[0] = P.payload[1] = 0;
+    if (i >= A.recs.n) return P;
+    const uint32_t off = A.recs.rec_off[i], end = A.recs.rec_off[i + 1];
+    SpanRec r = span_record(A.recs.raw, off, end);
+    const ClipEnds e = clip_decide(r, A.n_contigs, A.min_clip, A.min_mapq);
+    if (!e.left && !e.right) return P;                              // ~99 % of the lanes of a 30x chunk end here
+    int64_t refend;
+    if (!clip_refend(r, e, &refend)) return P;
+    const int64_t clen = A.len[r.tid];
+    // the packed bases sit behind the CIGAR, with qualities behind them or without: (l_seq + 1) / 2 bytes inside the record
+    const int64_t l_seq = (int32_t)ld_u32(r.p + 16);
+    const uint32_t o_seq = r.o_cigar + 4u * r.n_cigar;
+    if (l_seq <= 0 || (uint64_t)o_seq + (uint64_t)((l_seq + 1) >> 1) > (uint64_t)(end - off)) return P;
+    const uint8_t* seq = r.p + o_seq;
+    if (e.right && refend >= 0 && refend <= clen && (int64_t)e.len_r <= l_seq) {
+        // base i = read base l_seq - L + i: ascending read order is junction order
+        const uint32_t n = e.len_r < (uint32_t)kTailBases ? e.len_r : (uint32_t)kTailBases;
+        uint32_t pl, ph;
+        if (tail_planes(seq, (uint32_t)(l_seq - e.len_r), n, &pl, &ph)) {
+            P.key[0] = tail_key(r.tid, refend, 0u, n); P.payload[0] = ((uint64_t)ph << 32) | pl; P.n = 1;
+        }
+    }
+    if (e.left && r.pos >= 0 && r.pos <= clen && (int64_t)e.len_l <= l_seq) {
+        // base i = read base L - 1 - i: the bases L - n .. L - 1, reversed
+        const uint32_t n = e.len_l < (uint32_t)kTailBases ? e.len_l : (uint32_t)kTailBases;
+        uint32_t pl, ph;
+        if (tail_planes(seq, e.len_l - n, n, &pl, &ph)) {
+            pl = __brev(pl) >> (32u - n); ph = __brev(ph) >> (32u - n);
+            const uint64_t key = tail_key(r.tid, r.pos, 1u, n), payload = ((uint64_t)ph << 32) | pl;
+            if (P.n == 0u) { P.key[0] = key; P.payload[0] = payload; } else { P.key[1] = key; P.payload[1] = payload; }
+            P.n++;
+        }
+    }
+    return P;
+}
+
+// The tickets of a workgroup are drawn by ONE atomic add: returning atomics of a whole chunk on one address take turns, and one
+// per clipped read made them most of the launch.  So the lanes count their entries through two ballots per wave and 64 bytes of
+// LDS, thread 0 adds the workgroup's total to counters[0] and every lane's ticket is that base + its rank.  The number stored stays
+// exactly min(inserts, slots / 2).
+__global__ __launch_bounds__(kTailBlock) void cliptail_scatter_kernel(TailScatterArgs A)
+{
+    __shared__ uint32_t s_wave[kTailBlock / 64];
+    __shared__ unsigned long long s_base;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const TailPair P = tail_entries(A, (int64_t)blockIdx.x * kTailBlock + t);
+    const uint64_t one = __ballot(P.n >= 1u), two = __ballot(P.n == 2u);
+    const uint64_t below = (1ull << lane) - 1ull;
+    const uint32_t rank = (uint32_t)__builtin_popcountll(one & below) + (uint32_t)__builtin_popcountll(two & below);
+    if (lane == 0) s_wave[wave] = (uint32_t)__builtin_popcountll(one) + (uint32_t)__builtin_popcountll(two);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kTailBlock / 64; w++) { before += w < wave ? s_wave[w] : 0u; total += s_wave[w]; }
+    if (total == 0u) return;                                        // uniform over the workgroup
+    if (t == 0) s_base = atomicAdd(&A.tab.counters[0], (unsigned long long)total);
+    __syncthreads();
+    const unsigned long long ticket = s_base + before + rank;
+    if (P.n >= 1u && tail_admit(A.tab, ticket)) tail_place(A.tab, P.key[0], P.payload[0]);
+    if (P.n == 2u && tail_admit(A.tab, ticket + 1ull)) tail_place(A.tab, P.key[1], P.payload[1]);
+}
+
+// the record-at-a-time path: one lane per entry the host named; positions outside [0, clen] are dropped (no ticket)
+__global__ __launch_bounds__(kTailWaveBlock) void cliptail_add_kernel(int32_t n, int32_t tid, int64_t clen, const int32_t* __restrict__ pos,
+                                                                 const uint8_t* __restrict__ side, const uint8_t* __restrict__ nbases,
+                                                                 const uint32_t* __restrict__ planes, TailTable tab)
+{
+    const int64_t i = (int64_t)blockIdx.x * kTailWaveBlock + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = pos[i];
+    if (p < 0 || p > clen) return;
+    const uint32_t nb = nbases[i], m = nb >= 32u ? 0xFFFFFFFFu : (1u << nb) - 1u;
+    tail_insert(tab, tail_key(tid, p, side[i], nb), ((uint64_t)(planes[2 * i + 1] & m) << 32) | (planes[2 * i] & m));
+}
+
+// the resident reference is upper-cased ASCII: A C G T -> 0 1 2 3, anything else is no base
+__device__ __forceinline__ uint32_t ref_code(uint8_t c, bool* valid)
+{
+    *valid = c == 'A' || c == 'C' || c == 'G' || c == 'T';
+    return c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 0u;
+}
+
+struct TailWindow { uint64_t lo, hi, ok; };
+
+// lane i names the reference position of the base at distance i from the junction; positions outside [0, clen) are no base
+__device__ __forceinline__ TailWindow tail_window(const uint8_t* __restrict__ ref, int64_t clen, int64_t p)
+{
+    bool valid = false;
+    uint32_t code = 0;
+    if (p >= 0 && p < clen) code = ref_code(ref[p], &valid);
+    TailWindow W;
+    W.lo = __ballot(valid && (code & 1u)); W.hi = __ballot(valid && (code & 2u)); W.ok = __ballot(valid);
+    return W;
+}
+
+// One side of a query: the wave walks the probe run of (tid, pos, side) 64 slots at a time until a batch shows an empty slot.  A lane
+// whose slot (in front of the first empty one) holds an entry of the key tests the shifts 0 .. S against the window: a shift of the
+// planes, two XORs, the window's validity, a mask of n bits and a popcount.  Lane s gathers v(s) from the ballots.  Returns the
+// entries stored at the key (wave-uniform); *v: this lane's v(lane).
+__device__ __forceinline__ uint32_t tail_side(const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, const TailWindow& W,
+                                              bool compare, int32_t S, int lane, uint32_t* v)
+{
+    uint32_t stored = 0, mine = 0;
+    *v = 0;
+    if (pos < 0 || pos > clen) return 0;
+    const uint64_t slots = 1ull << T.log2_slots, mask = slots - 1ull;
+    const uint64_t want = tail_key(tid, pos, side, 0u) >> 6;
+    const uint64_t home = tail_home(want << 6, T.log2_slots);
+    for (uint64_t base = 0; base < slots; base += 64ull) {
+        const uint64_t s = (home + base + (uint64_t)lane) & mask;
+        const uint64_t key = T.slots[2ull * s];
+        const uint64_t empty = __ballot(key == 0ull);
+        const int stop = empty ? (int)__builtin_ctzll(empty) : 64;
+        const bool has = lane < stop && (key >> 6) == want;
+        const uint64_t holders = __ballot(has);
+        if (holders) {
+            stored += (uint32_t)__builtin_popcountll(holders);
+            if (compare) {
+                const uint64_t payload = has ? T.slots[2ull * s + 1ull] : 0ull;
+                const uint32_t e_lo = (uint32_t)payload, e_hi = (uint32_t)(payload >> 32);
+                const uint32_t n = (uint32_t)key & 63u, m = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u, allowed = n >> 4;
+                for (int32_t sh = 0; sh <= S; sh++) {               // wave-uniform
+                    const uint32_t diff = (((uint32_t)(W.lo >> sh) ^ e_lo) | ((uint32_t)(W.hi >> sh) ^ e_hi) | ~(uint32_t)(W.ok >> sh)) & m;
+                    const uint64_t match = __ballot(has && (uint32_t)__builtin_popcount(diff) <= allowed);
+                    if (lane == sh) mine += (uint32_t)__builtin_popcountll(match);
+                }
+            }
+        }
+        if (empty) break;
+    }
+    *v = mine;
+    return stored;
+}
+
+struct TailVerifyArgs {
+    int32_t nq, tid, max_shift;
+    const int32_t* pr;
+    const int32_t* pl;
+    const uint8_t* ref;         // the contig's ASCII bases
+    int64_t clen;
+    TailTable tab;
+    uint32_t* v_right;
+    uint32_t* v_left;
+    int32_t* shift;
+    uint32_t* stored_right;
+    uint32_t* stored_left;
+};
+
+// One wave per query (pr: where right clips pile up, pl: where left clips do).  A right entry at pr continues at pl + s, a left entry
+// at pl continues backwards from pr - 1 - s: one 64-base window per side, fetched once.  The chosen shift has the largest
+// vR(s) + vL(s), the smallest s among equals (the wave's maximum over sum : ~s).
+__global__ __launch_bounds__(kTailWaveBlock) void cliptail_verify_kernel(TailVerifyArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int q = wave; q < A.nq; q += nwaves) {
+        const int64_t pr = A.pr[q], pl = A.pl[q];
+        const bool compare = pl > pr;
+        const TailWindow Wr = tail_window(A.ref, A.clen, pl + lane);            // what right entries are expected to hold
+        const TailWindow Wl = tail_window(A.ref, A.clen, pr - 1 - lane);        // what left entries are expected to hold
+        uint32_t vr, vl;
+        const uint32_t sr = tail_side(A.tab, A.tid, pr, 0u, A.clen, Wr, compare, A.max_shift, lane, &vr);
+        const uint32_t sl = tail_side(A.tab, A.tid, pl, 1u, A.clen, Wl, compare, A.max_shift, lane, &vl);
+        uint64_t key = ((uint64_t)(lane <= A.max_shift ? vr + vl : 0u) << 32) | (0xFFFFFFFFu - (uint32_t)lane);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t hi = (uint32_t)__shfl_xor((int)(key >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)key, o);
+            const uint64_t k = ((uint64_t)hi << 32) | lo;
+            key = k > key ? k : key;
+        }
+        const bool found = (key >> 32) != 0ull;
+        const int best = found ? (int)(0xFFFFFFFFu - (uint32_t)key) : 0;
+        const uint32_t br = (uint32_t)__shfl((int)vr, best), bl = (uint32_t)__shfl((int)vl, best);
+        if (lane == 0) {
+            A.v_right[q] = found ? br : 0u; A.v_left[q] = found ? bl : 0u; A.shift[q] = found ? best : -1;
+            A.stored_right[q] = sr; A.stored_left[q] = sl;
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_cliptail_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const im_dev_records& recs, const TailTable& tab,
+                                   hipStream_t stream)
+{
+    if (recs.n <= 0) return hipSuccess;
+    TailScatterArgs A;
+    A.recs = recs; A.len = ref.len; A.n_contigs = ref.n_contigs; A.min_clip = min_clip; A.min_mapq = min_mapq; A.tab = tab;
+    hipLaunchKernelGGL(cliptail_scatter_kernel, dim3((recs.n + kTailBlock - 1) / kTailBlock), dim3(kTailBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_cliptail_add(int32_t n, int32_t tid, int64_t clen, const int32_t* pos, const uint8_t* side, const uint8_t* nbases,
+                               const uint32_t* planes, const TailTable& tab, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cliptail_add_kernel, dim3((n + kTailWaveBlock - 1) / kTailWaveBlock), dim3(kTailWaveBlock), 0, stream, n, tid, clen, pos, side, nbases, planes, tab);
+    return hipGetLastError();
+}
+
+hipError_t launch_cliptail_verify(int32_t nq, int32_t tid, const int32_t* pr, const int32_t* pl, int32_t max_shift, const uint8_t* ref,
+                                  int64_t clen, const TailTable& tab, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
+                                  uint32_t* stored_right, uint32_t* stored_left, hipStream_t stream)
+{
+    if (nq <= 0) return hipSuccess;
+    TailVerifyArgs A;
+    A.nq = nq; A.tid = tid; A.max_shift = max_shift; A.pr = pr; A.pl = pl; A.ref = ref; A.clen = clen; A.tab = tab;
+    A.v_right = v_right; A.v_left = v_left; A.shift = shift; A.stored_right = stored_right; A.stored_left = stored_left;
+    int b = (nq + 3) / 4;
+    if (b > 2048) b = 2048;
+    hipLaunchKernelGGL(cliptail_verify_kernel, dim3(b), dim3(kTailWaveBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace im

@@ -125,6 +125,24 @@ hipError_t launch_clip_build(int64_t clen, int32_t n, const int32_t* pos, const 
 // per query the largest count over [beg, end] inclusive of right (side 0) or left (side 1) and the smallest position holding it; (0, -1) when empty
 hipError_t launch_clip_argmax(int32_t nq, const uint8_t* side, const int32_t* beg, const int32_t* end, const int32_t* right, const int32_t* left,
                               int64_t clen, uint32_t* count_out, int32_t* pos_out, hipStream_t stream);
+// im_cliptail.hip: the clipped bases of clipped reads in a keyed table (-V).  slots: 2^log2_slots pairs (key, payload) of 64-bit
+// words, zeros = empty; counters[0]: inserts asked for, counters[1]: those dropped because half of the slots were taken
+struct TailTable {
+    unsigned long long* slots;
+    unsigned long long* counters;
+    int32_t log2_slots;
+};
+// the records that clip under the clip scatter's rule -> one entry per clipping end whose nearest min(clip, 32) bases are all A/C/G/T
+hipError_t launch_cliptail_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const im_dev_records& recs, const TailTable& tab,
+                                   hipStream_t stream);
+// one entry per host-named (position, side, bases, planes[2]: low-bit plane, high-bit plane); positions outside [0, clen] dropped
+hipError_t launch_cliptail_add(int32_t n, int32_t tid, int64_t clen, const int32_t* pos, const uint8_t* side, const uint8_t* nbases,
+                               const uint32_t* planes, const TailTable& tab, hipStream_t stream);
+// per query (pr, pl) on contig tid (ref: its ASCII bases): the entries at either key that continue behind the other breakpoint at the
+// best shift 0 .. max_shift <= 32, that shift (-1: none matched or pl <= pr), and the entries stored at the two keys
+hipError_t launch_cliptail_verify(int32_t nq, int32_t tid, const int32_t* pr, const int32_t* pl, int32_t max_shift, const uint8_t* ref,
+                                  int64_t clen, const TailTable& tab, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
+                                  uint32_t* stored_right, uint32_t* stored_left, hipStream_t stream);
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);

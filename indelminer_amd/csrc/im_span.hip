@@ -39,42 +39,13 @@
 
 #include "im_device.hpp"
 #include "im_rg.hpp"
+#include "im_spanrec.hpp"
 
 namespace im {
 namespace {
 
 constexpr int kSpanBlock = 256;
 constexpr int kSpanWin = 4096;      // positions of the difference array a workgroup gathers in LDS before it touches memory
-constexpr int kSpanHead = 4;        // CIGAR words a lane keeps in registers; the rest come from memory
-
-// What the scatter needs of a record (the 32-byte core; layout as in include/indelminer_amd.h, im_dev_records)
-struct SpanRec {
-    const uint8_t* p;
-    int32_t tid, pos;
-    uint32_t mapq, n_cigar, flag, o_cigar;
-    uint32_t cig[kSpanHead];
-    bool ok;
-};
-
-__device__ __forceinline__ SpanRec span_record(const uint8_t* raw, uint32_t off, uint32_t end)
-{
-    SpanRec r;
-    r.p = raw + off; r.ok = false; r.tid = -1; r.pos = 0; r.mapq = r.n_cigar = r.flag = r.o_cigar = 0;
-#pragma unroll
-    for (int k = 0; k < kSpanHead; k++) r.cig[k] = 0;
-    if (end < off || end - off < 32u) return r;
-    const uint32_t len = end - off;
-    const uint32_t* c = reinterpret_cast<const uint32_t*>(r.p);     // 4-byte aligned by contract
-    r.tid = (int32_t)c[0]; r.pos = (int32_t)c[1];
-    const uint32_t w2 = c[2], w3 = c[3];
-    r.mapq = (w2 >> 8) & 255u;
-    r.n_cigar = w3 & 0xFFFFu; r.flag = w3 >> 16;
-    r.o_cigar = 32u + (w2 & 255u);
-    if ((uint64_t)r.o_cigar + 4ull * r.n_cigar > len) return r;     // the CIGAR lies inside the record
-    r.ok = true;
-    return r;
-}
-
 __device__ __forceinline__ uint32_t span_cigar_word(const SpanRec& r, uint32_t k)
 {
     return k == 0u ? r.cig[0] : k == 1u ? r.cig[1] : k == 2u ? r.cig[2] : k == 3u ? r.cig[3] : ld_u32(r.p + r.o_cigar + 4u * k);
@@ -283,44 +254,16 @@ __global__ __launch_bounds__(kSpanBlock) void clip_scatter_kernel(ClipArgs A)
     win_clear(s_win, t);
     SpanRec r; r.ok = false; r.tid = -1; r.pos = 0; r.flag = 0; r.mapq = 0; r.n_cigar = 0; r.o_cigar = 0; r.p = A.recs.raw;
     if (i < A.recs.n) r = span_record(A.recs.raw, A.recs.rec_off[i], A.recs.rec_off[i + 1]);
-    const uint32_t n = r.ok ? r.n_cigar : 0u;
-    // the two words at either end, where the record has them: H may stand outside S (cig[0], cig[1]: first; cig[2], cig[3]: last)
-    if (n >= 1u) { r.cig[0] = ld_u32(r.p + r.o_cigar); r.cig[3] = ld_u32(r.p + r.o_cigar + 4u * (n - 1u)); }
-    if (n >= 2u) { r.cig[1] = ld_u32(r.p + r.o_cigar + 4u); r.cig[2] = ld_u32(r.p + r.o_cigar + 4u * (n - 2u)); }
-    auto word = [&](uint32_t k) -> uint32_t {
-        return k == 0u ? r.cig[0] : k == n - 1u ? r.cig[3] : k == 1u ? r.cig[1] : k == n - 2u ? r.cig[2] : ld_u32(r.p + r.o_cigar + 4u * k);
-    };
-    const bool eligible = n >= 1u && r.tid >= 0 && r.tid < A.n_contigs && !(r.flag & (0x4u | 0x100u | 0x200u | 0x400u)) && (int32_t)r.mapq >= A.min_mapq;
-    bool clip_l = false, clip_r = false;
-    uint32_t kf = 0, kl = 0;
-    if (eligible) {
-        // first and last operation that is not H (more than one H at an end: the further words come from memory)
-        while (kf < n && (word(kf) & 15u) == 5u) kf++;
-        kl = n - 1u;
-        while (kl > kf && (word(kl) & 15u) == 5u) kl--;
-        if (kf < kl) {                                              // one operation alone cannot both clip and consume reference
-            const uint32_t wf = word(kf), wl = word(kl);
-            clip_l = (wf & 15u) == 4u && (int64_t)(wf >> 4) >= A.min_clip;
-            clip_r = (wl & 15u) == 4u && (int64_t)(wl >> 4) >= A.min_clip;
-        }
-    }
+    const ClipEnds e = clip_decide(r, A.n_contigs, A.min_clip, A.min_mapq);
+    const bool clip_l = e.left, clip_r = e.right;
     win_propose(s_wpos, s_wtid, clip_l || clip_r, r.pos, r.tid, lane, wave);
     __syncthreads();
     const SpanWin W = win_open(s_win, s_wpos, s_wtid);
     if (W.tid < 0) return;                                          // no clipped record in the whole workgroup
 
     if (clip_l || clip_r) {
-        // refend for a right clip: the whole CIGAR; a left clip alone stops at the first operation that consumes reference
-        int64_t x = r.pos;
-        bool consumes = false;
-        for (uint32_t k = kf; k <= kl; k++) {
-            const uint32_t cw = word(k), op = cw & 15u;
-            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) {
-                consumes = true;
-                if (!clip_r) break;
-                x += cw >> 4;
-            }
-        }
+        int64_t x;
+        const bool consumes = clip_refend(r, e, &x);
         if (consumes) {
             const int64_t base = A.asc_off[r.tid], clen = A.len[r.tid];
             if (clip_r && x >= 0 && x <= clen) clip_event(W, A.right, base, r.tid, x, false);

@@ -331,6 +331,8 @@ typedef struct {
     ivlist segs, runs, frags;
     /* -C, record-at-a-time path: the clip events of the contig's eligible records, position and side (im_clip_build) */
     int32_t* clip_pos; uint8_t* clip_side; int64_t n_clip, cap_clip;
+    /* -V, the same path: their clip-tail entries, position, side, bases and the two planes each (im_cliptail_add) */
+    int32_t* tail_pos; uint8_t* tail_side; uint8_t* tail_n; uint32_t* tail_planes; int64_t n_tail, cap_tail;
     int depth_tid;              /* contig whose depth array is resident on the device, -1 = none */
     int pipe_mode;              /* device pipeline: depth queries go to the genome-wide array */
     int marker_floor;           /* multi-GPU: smallest start of a stale pair-table entry of an earlier contig on another rank */
@@ -978,15 +980,26 @@ static void print_clip_evidence(const variant_t* v)
     if (v->cs_cached[1] > 0) printf("%d", (int)v->cb_cached[1] + 1); else printf(".");
     printf(":%u,%u", v->cs_cached[0], v->cs_cached[1]);
 }
+/* -V: the values of CV and CH behind them.  A record without both sides, or without an answer after the table's overflow, prints
+ * .,. and . ; one whose clipped reads verify at no shift prints 0,0 and . */
+static void print_clip_verification(const variant_t* v)
+{
+    if (v->cv_state != 1) { printf(":.,.:."); return; }
+    printf(":%u,%u", v->cv_cached[0], v->cv_cached[1]);
+    if (v->ch_cached < 0) printf(":."); else printf(":%d", (int)v->ch_cached);
+}
 static void print_genotype(const variant_t* v)
 {
-    const char* more_keys = v->dm_valid ? (v->cb_valid ? ":DM:DFC:CB:CS" : ":DM:DFC") : (v->cb_valid ? ":CB:CS" : "");
+    const int cv = v->cb_valid && g_clip_verify;                    /* CV:CH stand on exactly the records that carry CB:CS */
+    const char* more_keys = v->dm_valid ? (v->cb_valid ? (cv ? ":DM:DFC:CB:CS:CV:CH" : ":DM:DFC:CB:CS") : ":DM:DFC")
+                                        : (v->cb_valid ? (cv ? ":CB:CS:CV:CH" : ":CB:CS") : "");
     /* a PAIRED_READ record has no precise breakpoint to count spanning reads at; with -P its rs_cached is RP, the thinnest depth
      * of concordant fragments over [POS, max(END, BP_END)] */
     if ((v->evdnctype == EV_PAIRED_READ && !g_pair_counts) || !v->rs_valid) printf("\tGT:AD:GQ%s\t./.:.,%u:.", more_keys, v->support);
     else print_gt_ad_gq(more_keys, (int64_t)v->rs_cached, (int64_t)v->support);
     if (v->dm_valid) print_depth_evidence(v);
     if (v->cb_valid) print_clip_evidence(v);
+    if (cv) print_clip_verification(v);
 }
 
 /* the span (pair: 0) or pair-span (pair: 1) minima over m > 0 intervals of one contig, as one query */
@@ -1412,6 +1425,37 @@ static void print_variants(driver* d, variant_list* vs)
             }
         }
         free(beg); free(end); free(side); free(cnt); free(at); free(who);
+    }
+    /* ... -V: and the records whose two piles were found, the left one in front of the right one, ask whether the clipped bases of
+     * either pile continue behind the other: one verify call per flush, behind the clip call ... */
+    for (int i = 0; i < out.n; i++) out.v[i]->cv_state = 0;
+    if (g_clip_verify && out.n > 0) {
+        int32_t* pr = xmalloc(sizeof(int32_t) * (size_t)out.n);
+        int32_t* pl = xmalloc(sizeof(int32_t) * (size_t)out.n);
+        uint32_t* ans = xmalloc(sizeof(uint32_t) * 5 * (size_t)out.n);
+        int* who = xmalloc(sizeof(int) * (size_t)out.n);
+        int m = 0;
+        for (int i = 0; i < out.n; i++) {
+            const variant_t* v = out.v[i];
+            if (!v->cb_valid || v->cs_cached[0] == 0 || v->cs_cached[1] == 0 || v->cb_cached[1] <= v->cb_cached[0]) continue;
+            pr[m] = v->cb_cached[0]; pl[m] = v->cb_cached[1];
+            who[m++] = i;
+        }
+        if (m > 0) {
+            uint32_t* vr = ans; uint32_t* vl = ans + m; int32_t* sh = (int32_t*)(ans + 2 * m);
+            gpu_wait(d);
+            pthread_mutex_lock(&g_query_mu);
+            const int qrc = im_cliptail_verify(d->gpu, out.v[who[0]]->tid, m, pr, pl, CLIPTAIL_MAX_SHIFT, vr, vl, sh, ans + 3 * m, ans + 4 * m);     /* a flush lies on one contig */
+            pthread_mutex_unlock(&g_query_mu);
+            if (qrc != IM_OK) fatalf("im_cliptail_verify: %s", im_last_error(d->gpu));
+            for (int q = 0; q < m; q++) {
+                variant_t* v = out.v[who[q]];
+                if (ans[3 * m + q] == CLIPTAIL_NONE) { v->cv_state = 2; continue; }
+                v->cv_cached[0] = vr[q]; v->cv_cached[1] = vl[q]; v->ch_cached = sh[q];
+                v->cv_state = 1;
+            }
+        }
+        free(pr); free(pl); free(ans); free(who);
     }
     /* ... and out they go */
     for (int i = 0; i < out.n; i++) emit_variant(d, out.v[i]);

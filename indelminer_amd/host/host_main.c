@@ -42,6 +42,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    (FORMAT DM:DFC, median depth inside against the flanks)\n");
     fprintf(file, "\t-C, with -G: clipped-read breakpoints for the same deletions\n");
     fprintf(file, "\t    (FORMAT CB:CS, where soft-clipped reads pile up and how many)\n");
+    fprintf(file, "\t-V, with -G -C: verify those breakpoints by the clipped bases\n");
+    fprintf(file, "\t    (FORMAT CV:CH, reads that continue across the deletion, and the shift)\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -84,7 +86,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDC")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCV")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -113,6 +115,7 @@ int main(int argc, char** argv)
         case 'P': g_pair_counts = 1; break;                         /* not an option of the reference */
         case 'D': g_depth_evidence = 1; break;                      /* not an option of the reference */
         case 'C': g_clip_evidence = 1; break;                       /* not an option of the reference */
+        case 'V': g_clip_verify = 1; break;                         /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -180,11 +183,18 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: clip evidence (-C) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -V: behind -C's refusals; every other refusal reaches it through -G and -C */
+    if (g_clip_verify) {
+        if (!g_clip_evidence) { fprintf(stderr, "indelminer: -V needs -C\n"); return EXIT_FAILURE; }
+        if (!CLIPTAIL_API_PRESENT) {
+            fprintf(stderr, "indelminer: clip verification (-V) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = 0;    /* -o detailed has no columns to add to */
+        if (strcmp(O.outputformat, "detailed") == 0) g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = 0;    /* -o detailed has no columns to add to */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {
@@ -327,6 +337,13 @@ int main(int argc, char** argv)
     }
 
     gpu_wait(&d);
+    if (CLIPTAIL_ON) {
+        /* -V: a table that overflowed has answered nothing since; said once, here */
+        uint64_t stored = 0, dropped = 0;
+        if (im_cliptail_stats(d.gpu, &stored, &dropped) == IM_OK && dropped > 0)
+            fprintf(stderr, "indelminer: -V: the clip-tail table overflowed (%llu entries stored, %llu dropped): CV and CH are . from there on\n",
+                    (unsigned long long)stored, (unsigned long long)dropped);
+    }
     if (t_out) fflush(t_out);
     if (g_vcfname != NULL) cpu_report();            /* annotate mode has no replay workers: its report comes here */
     if (!getenv("INDELMINER_TIDY_EXIT")) {

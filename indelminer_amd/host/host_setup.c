@@ -55,6 +55,11 @@ static void print_output_header(void)
             /* -C: no reference counterpart */
             printf("##FORMAT=<ID=CB,Number=2,Type=Integer,Description=\"Breakpoints by clipped reads, in the coordinates of POS and END: where most soft-clipped reads stop aligning left of the deletion, and the base in front of where most start aligning right of it\">\n");
             printf("##FORMAT=<ID=CS,Number=2,Type=Integer,Description=\"Clipped reads at the two positions of CB\">\n");
+            if (g_clip_verify) {
+                /* -V: no reference counterpart */
+                printf("##FORMAT=<ID=CV,Number=2,Type=Integer,Description=\"Of the clipped reads of CS, those whose clipped bases continue in the reference behind the other position of CB: left of the deletion, right of it\">\n");
+                printf("##FORMAT=<ID=CH,Number=1,Type=Integer,Description=\"Bases of micro-homology (shift) at which the reads of CV continue\">\n");
+            }
         }
         if (g_pair_counts) printf("##pairedReadAD=\"PAIRED_READ records: AD = concordant pairs spanning the deletion with -n bases on each side (lower bound), pairs supporting it\"\n");
         if (g_depth_evidence)
@@ -63,6 +68,9 @@ static void print_output_header(void)
         if (g_clip_evidence)
             printf("##clipEvidence=\"DELETION records with END-POS >= %d: a clipped read is an alignment samtools' pileup would count, with mapping quality of at least -q, whose first (last) CIGAR operation apart from hard clips is a soft clip of at least %d bases and whose CIGAR consumes reference; it counts at its first aligned base (left clip) or behind its last one (right clip). CS = the largest number of right clips on one position within %d positions of POS .. POS+(BP_END-END), and of left clips on one position within %d positions of END .. BP_END (PAIRED_READ records: both between POS-%d and max(END,BP_END)+%d); CB = the two positions, the smaller one among equal counts, printed so that a deletion whose clipped reads agree with the call shows its own POS,END; . and 0 for a side without clipped reads\"\n",
                    DEPTH_EV_MIN_LEN, CLIP_EV_MIN_CLIP, CLIP_EV_SLACK, CLIP_EV_SLACK, CLIP_EV_SLACK, CLIP_EV_SLACK);
+        if (g_clip_verify)
+            printf("##clipVerification=\"Records that carry CB:CS with both positions found and the second behind the first: of every clipped read counted there the %d clipped bases nearest the junction are kept (all of a shorter clip; a read with a base other than A, C, G, T among them is left out) and compared with the reference behind the other position, skipping s = 0 .. %d bases of micro-homology; a read is verified when at most n >> 4 of its n bases differ (1 of 16 .. 31, 2 of 32). CV = the verified reads left and right of the deletion at the s that verifies most, the smallest s among equals, CH = that s; 0,0 and . when none verifies; .,. and . for a record without both positions, and for every record once the table of clipped bases has overflowed (said on stderr at the end of the run)\"\n",
+                   CLIPTAIL_BASES, CLIPTAIL_MAX_SHIFT);
         printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", g_sample_name);
     } else if (strncmp(O.outputformat, "vcf", 3) == 0) printf("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
     fflush(OUT);
@@ -356,6 +364,41 @@ static void clip_push(driver* d, int64_t pos, int side)
     }
     d->clip_pos[d->n_clip] = (int32_t)pos; d->clip_side[d->n_clip] = (uint8_t)side; d->n_clip++;
 }
+/* -V: the entry of one clipping end (include/indelminer_amd.h, "Clip tails"): the n = min(L, 32) clipped bases nearest the junction,
+ * read base `first` and on in steps of `step`, as two planes of 2-bit codes; nothing when one of them is not A, C, G or T or when the
+ * clip is longer than the read */
+static void tail_push(driver* d, const bam_record* b, int64_t pos, int side, int L, int64_t first, int step)
+{
+    if (pos < 0 || pos > INT32_MAX || pos > d->hdr->target_len[b->tid] || b->l_seq <= 0 || L > b->l_seq) return;
+    const int n = L < CLIPTAIL_BASES ? L : CLIPTAIL_BASES;
+    const uint8_t* seq = BAMR_SEQ(b);
+    uint32_t lo = 0, hi = 0;
+    for (int i = 0; i < n; i++) {
+        const int code = BAMR_SEQI(seq, first + (int64_t)step * i);
+        const int two = code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : -1;
+        if (two < 0) return;
+        lo |= (uint32_t)(two & 1) << i; hi |= (uint32_t)(two >> 1) << i;
+    }
+    if (d->n_tail == d->cap_tail) {
+        d->cap_tail = d->cap_tail ? d->cap_tail * 2 : (1 << 14);
+        d->tail_pos = xrealloc(d->tail_pos, sizeof(int32_t) * (size_t)d->cap_tail);
+        d->tail_side = xrealloc(d->tail_side, (size_t)d->cap_tail);
+        d->tail_n = xrealloc(d->tail_n, (size_t)d->cap_tail);
+        d->tail_planes = xrealloc(d->tail_planes, 2 * sizeof(uint32_t) * (size_t)d->cap_tail);
+    }
+    d->tail_pos[d->n_tail] = (int32_t)pos; d->tail_side[d->n_tail] = (uint8_t)side; d->tail_n[d->n_tail] = (uint8_t)n;
+    d->tail_planes[2 * d->n_tail] = lo; d->tail_planes[2 * d->n_tail + 1] = hi;
+    d->n_tail++;
+}
+/* the size of -V's table: the smallest 2^k >= max(65 536, BAM bytes / 64), at most 2^30 (DESIGN.md 4.5f has the reasoning) */
+static void cliptail_enable(driver* d)
+{
+    struct stat sb;
+    const int64_t bytes = stat(d->bam_name, &sb) == 0 ? (int64_t)sb.st_size : 0;
+    int k = 16;
+    while (k < 30 && ((int64_t)1 << k) < bytes / 64) k++;
+    if (im_cliptail_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, k) != IM_OK) fatalf("im_cliptail_enable: %s", im_last_error(d->gpu));
+}
 static void clip_events(driver* d, const bam_record* b)
 {
     if (b->tid < 0 || b->tid >= d->hdr->n_targets || (b->flag & (0x4 | 0x100 | 0x200 | 0x400)) || (int)b->mapq < O.qthreshold) return;
@@ -368,8 +411,16 @@ static void clip_events(driver* d, const bam_record* b)
         if (op == OP_M || op == OP_EQ || op == OP_X || op == OP_D || op == OP_N) { consumes = 1; refend += len; }
     }
     if (!consumes) return;
-    if (CIG_OP(bamr_cigar_at(cig, last)) == OP_S && CIG_LEN(bamr_cigar_at(cig, last)) >= CLIP_EV_MIN_CLIP) clip_push(d, refend, 0);
-    if (CIG_OP(bamr_cigar_at(cig, first)) == OP_S && CIG_LEN(bamr_cigar_at(cig, first)) >= CLIP_EV_MIN_CLIP) clip_push(d, b->pos, 1);
+    if (CIG_OP(bamr_cigar_at(cig, last)) == OP_S && CIG_LEN(bamr_cigar_at(cig, last)) >= CLIP_EV_MIN_CLIP) {
+        clip_push(d, refend, 0);
+        const int L = CIG_LEN(bamr_cigar_at(cig, last));
+        if (CLIPTAIL_ON) tail_push(d, b, refend, 0, L, (int64_t)b->l_seq - L, 1);
+    }
+    if (CIG_OP(bamr_cigar_at(cig, first)) == OP_S && CIG_LEN(bamr_cigar_at(cig, first)) >= CLIP_EV_MIN_CLIP) {
+        clip_push(d, b->pos, 1);
+        const int L = CIG_LEN(bamr_cigar_at(cig, first));
+        if (CLIPTAIL_ON) tail_push(d, b, b->pos, 1, L, L - 1, -1);
+    }
 }
 
 static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_reader* r)
@@ -379,7 +430,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
     bam_region_iter it;
     bam_record b; memset(&b, 0, sizeof b);
     if (bam_region_begin(&it, r, d->idx, tid, beg, end) != 0) fatalf("cannot seek in %s", d->bam_name);
-    d->segs.n = 0; d->runs.n = 0; d->frags.n = 0; d->n_clip = 0;
+    d->segs.n = 0; d->runs.n = 0; d->frags.n = 0; d->n_clip = 0; d->n_tail = 0;
     const int whole = (beg <= 0 && end >= d->hdr->target_len[tid]);
     volatile int died = 0;              /* a record the reference dies on ended the pass: the flushes in front of it are still to print */
     t_is_main_thread_of_passA = 1;
@@ -442,6 +493,13 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
         if (d->n_clip > INT32_MAX) fatalf("more than 2^31 clipped reads on one contig");
         if (im_clip_build(d->gpu, d->seqlen[tid], (int32_t)d->n_clip, d->clip_pos, d->clip_side) != IM_OK) fatalf("im_clip_build: %s", im_last_error(d->gpu));
         phase_time("clip arrays (device)");
+    }
+    if (CLIPTAIL_ON) {
+        /* -V: the contig's entries go up in one call; the table is keyed by contig, what earlier contigs left does not matter */
+        cliptail_enable(d);
+        if (d->n_tail > INT32_MAX) fatalf("more than 2^31 clipped reads on one contig");
+        if (im_cliptail_add(d->gpu, tid, (int32_t)d->n_tail, d->tail_pos, d->tail_side, d->tail_n, d->tail_planes) != IM_OK) fatalf("im_cliptail_add: %s", im_last_error(d->gpu));
+        phase_time("clip tails (device)");
     }
 
     im_read_result* res = NULL;

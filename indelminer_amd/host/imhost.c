@@ -157,6 +157,21 @@ extern int im_clip_query(im_ctx*, int32_t, const uint8_t*, const int32_t*, const
 #define CLIP_API_PRESENT (im_clip_enable && im_dev_clip_scatter && im_clip_reset && im_clip_query_tid && im_clip_build && im_clip_query)
 #define CLIP_EV_MIN_CLIP 20        /* soft-clipped bases of the shortest clip that counts */
 #define CLIP_EV_SLACK 10           /* positions the windows reach beyond where the record puts its breakpoints */
+/* -V, with -G -C: the clipped bases of the reads CB / CS counted, against the reference behind the partner breakpoint (FORMAT CV:CH) --
+ * how many of them continue across the deletion, and the micro-homology (shift) at which they do: the device's keyed table of clip
+ * tails and its verify call.  Not an option of the reference; referenced weakly. */
+static int g_clip_verify = 0;
+extern int im_cliptail_enable(im_ctx*, int32_t, int32_t, int32_t) __attribute__((weak));
+extern int im_dev_cliptail_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
+extern int im_cliptail_add(im_ctx*, int32_t, int32_t, const int32_t*, const uint8_t*, const uint8_t*, const uint32_t*) __attribute__((weak));
+extern int im_cliptail_verify(im_ctx*, int32_t, int32_t, const int32_t*, const int32_t*, int32_t, uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*) __attribute__((weak));
+extern int im_cliptail_reset(im_ctx*, void*) __attribute__((weak));
+extern int im_cliptail_stats(im_ctx*, uint64_t*, uint64_t*) __attribute__((weak));
+#define CLIPTAIL_ON (g_clip_verify)                /* the walk also keeps the clipped bases */
+#define CLIPTAIL_API_PRESENT (im_cliptail_enable && im_dev_cliptail_scatter && im_cliptail_add && im_cliptail_verify && im_cliptail_reset && im_cliptail_stats)
+#define CLIPTAIL_BASES 32          /* bases an entry keeps at most */
+#define CLIPTAIL_MAX_SHIFT 32      /* the largest micro-homology a query tries */
+#define CLIPTAIL_NONE 0xFFFFFFFFu  /* what the device answers after its table has overflowed */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that

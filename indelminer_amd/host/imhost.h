@@ -81,6 +81,11 @@ typedef struct {
     uint32_t  cs_cached[2];
     int32_t   cb_cached[2];
     int       cb_valid;
+    /* -V: of those reads, the ones whose clipped bases continue behind the other breakpoint (left of the deletion, right of it), and the
+     * shift at which they do; cv_state 0: not asked (a side without clipped reads), 1: answered, 2: no answer (the table overflowed) */
+    uint32_t  cv_cached[2];
+    int32_t   ch_cached;
+    int       cv_state;
 } variant_t;
 
 typedef struct {
