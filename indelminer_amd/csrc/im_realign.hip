@@ -21,9 +21,12 @@
 // is integer scan / histogram work; measured, it is bound by VALU issue
 // (profiles/README.md), so the design rule is fewest vector instructions per read.
 //
-// Lane layout for everything positional: lane l owns read positions
-// 4l..4l+3 (reads of up to kShortRead = 255 bases; longer ones are im_realign_long.hip's); prefix sums / minima
-// run as lane-local 4-step chains plus one 64-lane scan.
+// Lane layout for everything positional: lane l owns PPL consecutive read positions, PPL l .. PPL l + PPL - 1.
+// PPL = 2 for reads of up to kTwoPerLane = 128 bases, PPL = 4 up to kShortRead = 255 (longer ones are
+// im_realign_long.hip's), chosen per read and wave-uniformly: a vector instruction costs the same with 25 lanes
+// busy as with 50, so a read of 100 bases runs the per-lane loops of its positional phases (read staging, k-mer
+// table, diagonal scans, merge) half as long.  Prefix sums / minima run as lane-local PPL-step chains plus one
+// 64-lane scan.  The vote between those phases has no lane layout of its own and exists once per band search.
 
 #include "im_device.hpp"
 #include "im_wave.hpp"
@@ -73,6 +76,7 @@ constexpr int kDiagChunk = IM_DIAG_CHUNK;   // diagonals per histogram pass (1 b
 constexpr int kTblBytes  = 4096;            // 4^6 direct table, or 512-slot hash (keys+vals)
 constexpr int kHashSlots = 512;
 constexpr int kDirectMaxK = 6;
+constexpr int kTwoPerLane = 128;            // reads up to here lie two positions to a lane, longer ones four
 
 constexpr int kDiagWords = kDiagChunk / 4 + 16;     // packed byte counters (+ slack for band sums)
 static_assert(kDiagWords % 4 == 0, "the histogram is cleared with 16-byte stores");
@@ -86,6 +90,18 @@ struct WaveLds {
 #endif
 };
 
+// base2bits of two ASCII bytes (the upper half of v is zero): code2x4's look-up, the two codes as one nibble
+__device__ __forceinline__ uint32_t code2x2(uint32_t v)
+{
+    uint32_t x = (v >> 1) & 0x0303u;
+    x ^= (x >> 1) & 0x0101u;
+    const uint32_t want = __builtin_amdgcn_perm(0u, 0x74676361u, x);           // 'a' 'c' 'g' 't' by code
+    const uint32_t d = (v | 0x2020u) ^ (want & 0xFFFFu);                        // zero byte: a valid letter
+    const uint32_t nz = (((d & 0x7F7Fu) + 0x7F7Fu) | d) & 0x8080u;             // 0x80 in every non-zero byte
+    x &= ~((nz >> 7) * 3u);
+    return (x | (x >> 6)) & 0xFu;
+}
+
 // ---- K1: band search ---------------------------------------------------------
 
 struct Band {
@@ -98,15 +114,19 @@ struct Band {
 // the read k-mer table: 1 + offset of the k-mer in the piece, for k-mers that occur exactly once
 // (bin_diagonals only lets read-unique k-mers vote, 97-98).  In the direct (k <= 6) table every
 // other entry is 0, so "votes" is simply "non-zero"; the hash table (k > 6) marks repeats 0xFF.
-template <int KT, bool DIRECT>
-__device__ __forceinline__ void table_build(WaveLds& s, uint32_t p0, uint32_t nq, uint32_t k, int lane, uint32_t read_pk8, uint32_t* codes)
+// read_pk: the 2-bit codes of this lane's PPL bases, first base in the low bits (a byte at PPL = 4, a nibble at PPL = 2).
+// The hash form (KT = 0) reads the staged bytes instead and keeps four k-mer starts per lane whatever the read's layout.
+template <int KT, bool DIRECT, int PPL>
+__device__ __forceinline__ void table_build(WaveLds& s, uint32_t p0, uint32_t nq, uint32_t k, int lane, uint32_t read_pk, uint32_t* codes)
 {
+    static_assert(PPL == 2 || PPL == 4, "two or four read positions per lane");
+    static_assert(KT != 0 || PPL == 4, "the hash table is built four starts per lane");
     if constexpr (KT == 6 || KT == -1) {
         // direct table (k = 6, the reference default, with its mask a constant; KT = -1: any k <= 6): cleared with four
         // 16-byte stores per lane -- cheaper in vector instructions than un-doing the entries after the vote, and vector
         // issue is what binds the kernel.  The read's 2-bit codes travel as one packed byte per lane
-        // (bases 4l..4l+3); the two following lanes' bytes come over DPP, and the lane's four
-        // 6-mers are bit fields of that 24-bit window.
+        // (bases 4l..4l+3; a nibble, bases 2l, 2l+1, at PPL = 2); the two (three) following lanes' codes come over DPP,
+        // and the lane's PPL 6-mers are bit fields of that 24-bit (16-bit) window.
         {
             uint4* t4 = reinterpret_cast<uint4*>(s.tbl);
 #pragma unroll
@@ -114,25 +134,30 @@ __device__ __forceinline__ void table_build(WaveLds& s, uint32_t p0, uint32_t nq
             wave_lds_sync();
         }
         uint8_t* t8 = reinterpret_cast<uint8_t*>(s.tbl);
-        const uint32_t n1 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)read_pk8);
+        const uint32_t n1 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)read_pk);
         const uint32_t n2 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)n1);
-        const uint32_t w24 = read_pk8 | (n1 << 8) | (n2 << 16);
-        uint32_t code[4]; bool have[4];
+        uint32_t win;                                                   // bases 4l .. 4l+11 (PPL = 2: 2l .. 2l+7)
+        if constexpr (PPL == 4) win = read_pk | (n1 << 8) | (n2 << 16);
+        else {
+            const uint32_t n3 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)n2);
+            win = read_pk | (n1 << 4) | (n2 << 8) | (n3 << 12);
+        }
+        uint32_t code[PPL]; bool have[PPL];
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint32_t x = 4u * lane + j;
+        for (int j = 0; j < PPL; j++) {
+            const uint32_t x = (uint32_t)PPL * lane + j;
             have[j] = x >= p0 && x < p0 + nq;
-            code[j] = (w24 >> (2 * j)) & (KT == 6 ? 0xFFFu : ((1u << (2 * k)) - 1u));
+            code[j] = (win >> (2 * j)) & (KT == 6 ? 0xFFFu : ((1u << (2 * k)) - 1u));
         }
 #pragma unroll
-        for (int j = 0; j < 4; j++) if (have[j]) t8[code[j]] = (uint8_t)(4u * lane + j - p0 + 1u);
+        for (int j = 0; j < PPL; j++) if (have[j]) t8[code[j]] = (uint8_t)((uint32_t)PPL * lane + j - p0 + 1u);
         wave_lds_sync();
-        bool lost[4];
+        bool lost[PPL];
 #pragma unroll
-        for (int j = 0; j < 4; j++) lost[j] = have[j] && (t8[code[j]] != (uint8_t)(4u * lane + j - p0 + 1u));
+        for (int j = 0; j < PPL; j++) lost[j] = have[j] && (t8[code[j]] != (uint8_t)((uint32_t)PPL * lane + j - p0 + 1u));
         wave_lds_sync();
 #pragma unroll
-        for (int j = 0; j < 4; j++) if (lost[j]) t8[code[j]] = 0u;      // repeated: nobody votes with it
+        for (int j = 0; j < PPL; j++) if (lost[j]) t8[code[j]] = 0u;    // repeated: nobody votes with it
         wave_lds_sync();
         return;
     }
@@ -147,35 +172,44 @@ __device__ __forceinline__ void table_build(WaveLds& s, uint32_t p0, uint32_t nq
             for (int i = 0; i < kTblBytes / 16 / 64; i++) t4[lane + 64 * i] = make_uint4(0u, 0u, 0u, 0u);
         }
         // bases 4l .. 4l+18 of the read as 2-bit codes: this lane's byte and the four lanes' behind it
-        const uint32_t n1 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)read_pk8);
+        // (PPL = 2: bases 2l .. 2l+15, this lane's nibble and the seven lanes' behind it -- the second start's 13-mer ends at 2l+13)
+        const uint32_t n1 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)read_pk);
         const uint32_t n2 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)n1);
         const uint32_t n3 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)n2);
         const uint32_t n4 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)n3);
-        const uint32_t lo = read_pk8 | (n1 << 8) | (n2 << 16) | (n3 << 24);
+        uint32_t lo, hi = 0u;
+        if constexpr (PPL == 4) { lo = read_pk | (n1 << 8) | (n2 << 16) | (n3 << 24); hi = n4; }
+        else {
+            const uint32_t n5 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)n4);
+            const uint32_t n6 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)n5);
+            const uint32_t n7 = (uint32_t)dpp_mov<kDppWaveShl1>(0, (int)n6);
+            lo = read_pk | (n1 << 4) | (n2 << 8) | (n3 << 12) | (n4 << 16) | (n5 << 20) | (n6 << 24) | (n7 << 28);
+        }
         const uint32_t kmask = (1u << (2 * k)) - 1u;
-        uint32_t code[4], slot[4]; bool pend[4];
+        uint32_t code[PPL], slot[PPL]; bool pend[PPL];
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint32_t x = 4u * lane + j;
+        for (int j = 0; j < PPL; j++) {
+            const uint32_t x = (uint32_t)PPL * lane + j;
             pend[j] = x >= p0 && x < p0 + nq;
-            code[j] = __builtin_amdgcn_alignbit(n4, lo, 2u * j) & kmask;          // k <= 13: 26 bits
+            if constexpr (PPL == 4) code[j] = __builtin_amdgcn_alignbit(hi, lo, 2u * j) & kmask;          // k <= 13: 26 bits
+            else                    code[j] = (lo >> (2 * j)) & kmask;                                      // 26 of 32 - 2j bits
             slot[j] = code[j] & 0xFFFu;
             if (pend[j]) codes[x - p0] = code[j];
         }
         wave_lds_sync();
         for (;;) {
-            uint32_t e[4];
+            uint32_t e[PPL];
 #pragma unroll
-            for (int j = 0; j < 4; j++) { e[j] = pend[j] ? lds_byte(s.tbl, slot[j]) : 1u; }
+            for (int j = 0; j < PPL; j++) { e[j] = pend[j] ? lds_byte(s.tbl, slot[j]) : 1u; }
             wave_lds_sync();
 #pragma unroll
-            for (int j = 0; j < 4; j++) if (pend[j] && e[j] == 0u) t8[slot[j]] = (uint8_t)(4u * lane + j - p0 + 1u);
+            for (int j = 0; j < PPL; j++) if (pend[j] && e[j] == 0u) t8[slot[j]] = (uint8_t)((uint32_t)PPL * lane + j - p0 + 1u);
             wave_lds_sync();
             bool any = false;
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
+            for (int j = 0; j < PPL; j++) {
                 if (!pend[j]) continue;
-                const uint32_t me = 4u * lane + j - p0 + 1u;
+                const uint32_t me = (uint32_t)PPL * lane + j - p0 + 1u;
                 const uint32_t now = lds_byte(s.tbl, slot[j]);
                 if (now == me) { pend[j] = false; continue; }                       // in
                 const uint32_t other = codes[now - 1u];
@@ -354,7 +388,7 @@ __device__ __forceinline__ uint32_t vote_unit_direct(WaveLds& s, const uint32_t 
 template <int KT, bool DIRECT>
 __device__ __forceinline__ Band band_search(WaveLds& s, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ contig,
                             uint32_t w0, uint32_t w1, uint32_t anchor,
-                            uint32_t p0, uint32_t p1, uint32_t k, uint32_t g, int lane, uint32_t read_pk8, uint32_t* codes IM_STAMP_ARG)
+                            uint32_t p0, uint32_t p1, uint32_t k, uint32_t g, int lane, uint32_t read_pk, bool two, uint32_t* codes IM_STAMP_ARG)
 {
     Band b;
     const uint32_t W = w1 - w0, Lp = p1 - p0;
@@ -400,7 +434,10 @@ __device__ __forceinline__ Band band_search(WaveLds& s, const uint8_t* __restric
             for (int j = 0; j < 8; j++) wd[j] = load_u32_unaligned(src + 16 * j);
         }
         if (c0 == 0) {
-            table_build<KT, DIRECT>(s, p0, nq, k, lane, read_pk8, codes);
+            // the read's lane layout (`two`: two positions per lane, wave-uniform) ends with the table: one vote loop serves both
+            if constexpr (KT == 0) table_build<KT, DIRECT, 4>(s, p0, nq, k, lane, read_pk, codes);
+            else if (two)          table_build<KT, DIRECT, 2>(s, p0, nq, k, lane, read_pk, codes);
+            else                   table_build<KT, DIRECT, 4>(s, p0, nq, k, lane, read_pk, codes);
             IM_STAMP_B(0);
         }
         // clear the histogram: 16 bytes per lane and store, whole array (two stores for 1984 bytes)
@@ -524,69 +561,98 @@ struct Aln {
     int st;                 // 0 ok, IM_ST_ABORT
     int q1, q2, r1, r2;     // 0-based half-open read / contig coordinates; q1 == q2: no alignment
     int f, l;               // leading / trailing '=' run (src/alignment.c:585-599)
-    uint32_t eqbits;        // per lane: bit j = read position 4*lane+j is an aligned '=' (read coordinates)
+    uint32_t eqbits;        // per lane: bit j = read position PPL*lane+j is an aligned '=' (read coordinates)
 };
+
+// the per-field maximum of two unsigned 16-bit fields over the wave: v_pk_max_u16 has no DPP form, so a step is a move and a maximum
+__device__ __forceinline__ uint32_t wave_pk_max_u16(uint32_t v)
+{
+    v = pk_max_u16(v, (uint32_t)dpp_mov<kDppRowShr1>(0, (int)v));
+    v = pk_max_u16(v, (uint32_t)dpp_mov<kDppRowShr2>(0, (int)v));
+    v = pk_max_u16(v, (uint32_t)dpp_mov<kDppRowShr4>(0, (int)v));
+    v = pk_max_u16(v, (uint32_t)dpp_mov<kDppRowShr8>(0, (int)v));
+    v = pk_max_u16(v, (uint32_t)dpp_mov<kDppBcast15, 0xa>(0, (int)v));
+    v = pk_max_u16(v, (uint32_t)dpp_mov<kDppBcast31, 0xc>(0, (int)v));
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
 
 // local_align + ALIGN + fetch_cigar for low == up == d (src/localalign.c:100-176
 // with band == 1; closed form validated in SURVEY.md A.5a):
 //   forward : c_t = max(0, c_{t-1} + w_t); end = first t where c_t is the strict maximum
 //   reverse : start = largest s <= end with sum_{s..end} w == best
 // Match flags of the aligned positions come back in Aln::eqbits, in read coordinates.
-template <bool WANT_RUNS>            // the leading / trailing '=' runs are only used of the first piece
+// PPL piece positions per lane (lane l owns t = PPL l .. PPL l + PPL - 1); WANT_RUNS: the leading / trailing '=' runs are
+// only used of the first piece.
+template <int PPL, bool WANT_RUNS>
 __device__ __forceinline__ Aln diag_scan(WaveLds& s, const uint8_t* __restrict__ contig,
                          uint32_t w0, uint32_t w1, uint32_t p0, uint32_t p1, int d, int lane)
 {
+    static_assert(PPL == 2 || PPL == 4, "two or four read positions per lane");
+    constexpr int kLog = PPL == 4 ? 2 : 1;
     Aln a;
     a.st = 0; a.q1 = a.q2 = a.r1 = a.r2 = 0; a.f = a.l = 0; a.eqbits = 0u;
     const int M = (int)(p1 - p0), N = (int)(w1 - w0);
     if (M <= 0 || N <= 0 || d < -M || d > N) { a.st = IM_ST_ABORT; return a; }   // src/localalign.c:31-32,70-77
     const int t_lo = max(0, -d), t_hi = min(M, N - d);
 
-    const int t0 = 4 * lane;
+    const int t0 = PPL * lane;
     uint32_t rdw = 0, rfw = 0;
-    if (t0 < t_hi && t0 + 3 >= t_lo) {
+    if (t0 < t_hi && t0 + PPL - 1 >= t_lo) {
         const uint8_t* rb = reinterpret_cast<const uint8_t*>(s.rd) + p0 + t0;
-        rdw = (uint32_t)rb[0] | ((uint32_t)rb[1] << 8) | ((uint32_t)rb[2] << 16) | ((uint32_t)rb[3] << 24);
-        rfw = load_u32_unaligned(contig + ((int64_t)w0 + d + t0));
+        if constexpr (PPL == 4) {
+            rdw = (uint32_t)rb[0] | ((uint32_t)rb[1] << 8) | ((uint32_t)rb[2] << 16) | ((uint32_t)rb[3] << 24);
+            rfw = load_u32_unaligned(contig + ((int64_t)w0 + d + t0));
+        } else {
+            rdw = (uint32_t)rb[0] | ((uint32_t)rb[1] << 8);
+            uint16_t h;
+            __builtin_memcpy(&h, contig + ((int64_t)w0 + d + t0), 2);
+            rfw = h;
+        }
     }
-    int w[4]; bool eq[4];
+    int w[PPL]; bool eq[PPL];
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
+    for (int j = 0; j < PPL; j++) {
         const int t = t0 + j;
         const bool valid = t >= t_lo && t < t_hi;
         eq[j] = valid && (((rdw >> (8 * j)) & 255u) == ((rfw >> (8 * j)) & 255u));
         w[j] = valid ? (eq[j] ? kScoreMatch : kScoreMismatch) : 0;
     }
     // inclusive prefix sums S_t
-    int S[4];
-    S[0] = w[0]; S[1] = S[0] + w[1]; S[2] = S[1] + w[2]; S[3] = S[2] + w[3];
-    const int incl = wave_scan_add(S[3], lane);
-    const int excl = incl - S[3];
+    int S[PPL];
+    S[0] = w[0];
 #pragma unroll
-    for (int j = 0; j < 4; j++) S[j] += excl;
+    for (int j = 1; j < PPL; j++) S[j] = S[j - 1] + w[j];
+    const int incl = wave_scan_add(S[PPL - 1], lane);
+    const int excl = incl - S[PPL - 1];
+#pragma unroll
+    for (int j = 0; j < PPL; j++) S[j] += excl;
     // running minimum of S including the empty prefix (0)
-    int m[4];
-    m[0] = S[0]; m[1] = min(m[0], S[1]); m[2] = min(m[1], S[2]); m[3] = min(m[2], S[3]);
-    const int pm = min(0, wave_scan_min_excl(m[3], lane));
-    int c[4];
+    int m[PPL];
+    m[0] = S[0];
 #pragma unroll
-    for (int j = 0; j < 4; j++) c[j] = S[j] - min(pm, m[j]);
+    for (int j = 1; j < PPL; j++) m[j] = min(m[j - 1], S[j]);
+    const int pm = min(0, wave_scan_min_excl(m[PPL - 1], lane));
+    int c[PPL];
+#pragma unroll
+    for (int j = 0; j < PPL; j++) c[j] = S[j] - min(pm, m[j]);
     // the best score and the FIRST cell that holds it in one reduction: scores are 0..255 (c_t >= 0, at most one per base
     // of a read of up to 255), cells 0..255 -- (score << 8) | (255 - t), largest wins
     int bk = (c[0] << 8) | (255 - t0);
 #pragma unroll
-    for (int j = 1; j < 4; j++) bk = max(bk, (c[j] << 8) | (255 - t0 - j));
+    for (int j = 1; j < PPL; j++) bk = max(bk, (c[j] << 8) | (255 - t0 - j));
     bk = wave_max(bk);
     const int best = bk >> 8;
     if (best <= 0) return a;                                       // score <= 0 (src/alignment.c:365-372)
     const int end = 255 - (bk & 255);
-    const int el = end >> 2, ej = end & 3;
-    int s_sel = (ej == 0) ? S[0] : (ej == 1) ? S[1] : (ej == 2) ? S[2] : S[3];
+    const int el = end >> kLog, ej = end & (PPL - 1);
+    int s_sel = S[PPL - 1];
+#pragma unroll
+    for (int j = PPL - 2; j >= 0; j--) s_sel = (ej == j) ? S[j] : s_sel;
     const int Send = __builtin_amdgcn_readlane(s_sel, el);
     const int target = Send - best;
     int st_loc = -1;
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
+    for (int j = 0; j < PPL; j++) {
         const int t = t0 + j;
         const int sprev = (j == 0) ? excl : S[j - 1];
         if (t >= t_lo && t <= end && sprev == target) st_loc = t;
@@ -594,36 +660,40 @@ __device__ __forceinline__ Aln diag_scan(WaveLds& s, const uint8_t* __restrict__
     const int start = wave_max(st_loc);
     if (start < 0 || end == start) return a;                       // single cell: score 0 (src/localalign.c:191-193)
 
-    // '='/X flags of the aligned span, and the leading/trailing '=' runs
+    // '='/X flags of the aligned span, and the leading/trailing '=' runs: the first and the last X of the span in ONE
+    // reduction -- positions are below 256, so (256 - t) and (t + 1) are two 16-bit fields whose maxima are taken side by
+    // side, and a field that stays 0 says the span has no X
     uint32_t flags = 0;
-    int fm = INT_MAX, lm = -1;
+    uint32_t xk = 0u;
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
+    for (int j = 0; j < PPL; j++) {
         const int t = t0 + j;
         if (t >= start && t <= end) {
             if (eq[j]) flags |= 1u << j;
-            else { fm = min(fm, t); lm = max(lm, t); }
+            else if (WANT_RUNS) xk = pk_max_u16(xk, ((uint32_t)(256 - t) << 16) | (uint32_t)(t + 1));
         }
     }
     if (WANT_RUNS) {
-        fm = wave_min(fm); lm = wave_max(lm);
-        a.f = (fm == INT_MAX ? end + 1 : fm) - start;
-        a.l = end - (lm < 0 ? start - 1 : lm);
+        const uint32_t X = wave_pk_max_u16(xk);
+        const int fm = (X >> 16) ? 256 - (int)(X >> 16) : end + 1;
+        const int lm = (X & 0xFFFFu) ? (int)(X & 0xFFFFu) - 1 : start - 1;
+        a.f = fm - start;
+        a.l = end - lm;
     }
-    // flags live in piece coordinates t (lane owns t0..t0+3); read position x = p0 + t belongs to
-    // lane x >> 2, so lane L collects bits 4L - p0 .. 4L - p0 + 3 of the 256-bit flag string from
+    // flags live in piece coordinates t (lane owns t0..t0+PPL-1); read position x = p0 + t belongs to
+    // lane x / PPL, so lane L collects bits PPL L - p0 .. PPL L - p0 + PPL - 1 of the flag string from
     // the two lanes that hold them (ds_bpermute: no LDS storage, no barrier)
     {
         const uint32_t f4 = flags;
         if (p0 == 0u) a.eqbits = f4;
         else {
-            const int base = 4 * lane - (int)p0;
-            const int ql = base >> 2, r = base & 3;                 // floor division
+            const int base = PPL * lane - (int)p0;
+            const int ql = base >> kLog, r = base & (PPL - 1);      // floor division
             const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute((ql & 63) << 2, (int)f4);
             const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(((ql + 1) & 63) << 2, (int)f4);
             const uint32_t lo_ok = (ql >= 0 && ql < 64) ? lo : 0u;
             const uint32_t hi_ok = (ql + 1 >= 0 && ql + 1 < 64) ? hi : 0u;
-            a.eqbits = ((lo_ok | (hi_ok << 4)) >> r) & 0xFu;
+            a.eqbits = ((lo_ok | (hi_ok << PPL)) >> r) & ((1u << PPL) - 1u);
         }
     }
     a.q1 = (int)p0 + start;                                         // src/alignment.c:385-388
@@ -672,16 +742,29 @@ __device__ __forceinline__ void realign_one(WaveLds& s, const RealignArgs& A, in
     const uint8_t* pk = A.ref.pk + sload(A.ref.pk_off + tid);
     const int clen = sload(A.ref.len + tid);
 
-    // stage the read; lane l also keeps the 2-bit codes of its four bases (read_pk8, for the k-mer table)
-    uint32_t rdw = 0;
-    if (4 * lane < L) rdw = *reinterpret_cast<const uint32_t*>(A.batch.bases + off + 4 * lane);
-    {
-        const int rem = L - 4 * lane;                              // zero the bytes past the read
-        if (rem < 4) rdw &= (rem <= 0) ? 0u : ((1u << (8 * rem)) - 1u);
+    // stage the read; lane l also keeps the 2-bit codes of its bases (read_pk, for the k-mer table).  A read of up to
+    // kTwoPerLane bases lies two positions to a lane from here on, a longer one four: L is in an SGPR, the branch is scalar.
+    // Either way s.rd holds the read's bytes and zeros behind them.
+    const bool two = L <= kTwoPerLane;
+    uint32_t read_pk;                            // first base in the low bits: a nibble (two), a byte
+    if (two) {
+        uint32_t rdh = 0;
+        if (2 * lane < L) rdh = *reinterpret_cast<const uint16_t*>(A.batch.bases + off + 2 * lane);
+        if (L - 2 * lane == 1) rdh &= 0xFFu;                       // zero the byte past the read
+        read_pk = code2x2(rdh);
+        reinterpret_cast<uint16_t*>(s.rd)[lane] = (uint16_t)rdh;
+        if (lane < (256 + 16 - kTwoPerLane) / 4) s.rd[kTwoPerLane / 4 + lane] = 0u;
+    } else {
+        uint32_t rdw = 0;
+        if (4 * lane < L) rdw = *reinterpret_cast<const uint32_t*>(A.batch.bases + off + 4 * lane);
+        {
+            const int rem = L - 4 * lane;                          // zero the bytes past the read
+            if (rem < 4) rdw &= (rem <= 0) ? 0u : ((1u << (8 * rem)) - 1u);
+        }
+        read_pk = code2x4(rdw);
+        s.rd[lane] = rdw;
+        if (lane < 4) s.rd[64 + lane] = 0u;
     }
-    const uint32_t read_pk8 = code2x4(rdw);      // 2-bit codes of this lane's four bases, first base in the low bits
-    s.rd[lane] = rdw;
-    if (lane < 4) s.rd[64 + lane] = 0u;
     wave_lds_sync();
 
     const Windows win = realign_windows(anchor, R, A.P.maxdelsize, clen);
@@ -690,9 +773,10 @@ __device__ __forceinline__ void realign_one(WaveLds& s, const RealignArgs& A, in
 
     // piece 1: the whole read in [left1,right1) (557-566)
     IM_STAMP(0);
-    const Band b1 = band_search<KT, DIRECT>(s, pk, contig, (uint32_t)left1, (uint32_t)right1, (uint32_t)anchor, 0u, (uint32_t)L, k, g, lane, read_pk8, codes IM_STAMP_PASS(1));
+    const Band b1 = band_search<KT, DIRECT>(s, pk, contig, (uint32_t)left1, (uint32_t)right1, (uint32_t)anchor, 0u, (uint32_t)L, k, g, lane, read_pk, two, codes IM_STAMP_PASS(1));
     if (b1.st) { finish(out, b1.st, 1, lane); return; }
-    const Aln a1 = diag_scan<true>(s, contig, (uint32_t)left1, (uint32_t)right1, 0u, (uint32_t)L, b1.low, lane);
+    const Aln a1 = two ? diag_scan<2, true>(s, contig, (uint32_t)left1, (uint32_t)right1, 0u, (uint32_t)L, b1.low, lane)
+                       : diag_scan<4, true>(s, contig, (uint32_t)left1, (uint32_t)right1, 0u, (uint32_t)L, b1.low, lane);
     store_band(out, 0, b1, a1, lane);
     IM_STAMP(6);
     if (a1.st) { finish(out, a1.st, 1, lane); return; }
@@ -705,9 +789,10 @@ __device__ __forceinline__ void realign_one(WaveLds& s, const RealignArgs& A, in
     const uint32_t w0 = pl.w0, w1 = pl.w1, p0 = pl.p0, p1 = pl.p1;
 
     IM_STAMP(7);
-    const Band b2 = band_search<KT, DIRECT>(s, pk, contig, w0, w1, pl.anc, p0, p1, k, g, lane, read_pk8, codes IM_STAMP_PASS(8));
+    const Band b2 = band_search<KT, DIRECT>(s, pk, contig, w0, w1, pl.anc, p0, p1, k, g, lane, read_pk, two, codes IM_STAMP_PASS(8));
     if (b2.st) { finish(out, b2.st, 2, lane); return; }
-    const Aln a2 = diag_scan<false>(s, contig, w0, w1, p0, p1, b2.low, lane);
+    const Aln a2 = two ? diag_scan<2, false>(s, contig, w0, w1, p0, p1, b2.low, lane)
+                       : diag_scan<4, false>(s, contig, w0, w1, p0, p1, b2.low, lane);
     store_band(out, 1, b2, a2, lane);
     IM_STAMP(13);
     if (a2.st) { finish(out, a2.st, 2, lane); return; }
@@ -719,8 +804,10 @@ __device__ __forceinline__ void realign_one(WaveLds& s, const RealignArgs& A, in
     // find_best_del_candidate asserts its first piece starts at read offset 0 (314-315): not tested here, it holds by
     // accept_piece2 (the A piece has q == 0); the band and the one-lane-per-read kernels test it.
     // The boundary positions go where the vote histogram was (idle by now).
-    const int st = merge_pieces<4>(pc.a_is_second ? a2.eqbits : a1.eqbits, pc.a_is_second ? a1.eqbits : a2.eqbits,
-                                   pc.qa2, pc.rA, pc.qb1, pc.rB, pc.split, L, reinterpret_cast<int32_t*>(s.diag), out, A, c, lane);
+    const uint32_t eqA = pc.a_is_second ? a2.eqbits : a1.eqbits, eqB = pc.a_is_second ? a1.eqbits : a2.eqbits;
+    int32_t* bpos = reinterpret_cast<int32_t*>(s.diag);
+    const int st = two ? merge_pieces<2>(eqA, eqB, pc.qa2, pc.rA, pc.qb1, pc.rB, pc.split, L, bpos, out, A, c, lane)
+                       : merge_pieces<4>(eqA, eqB, pc.qa2, pc.rA, pc.qb1, pc.rB, pc.split, L, bpos, out, A, c, lane);
     if (st != IM_ST_EVIDENCE) { finish(out, st, 2, lane); return; }
     IM_STAMP(14);
 }
@@ -1531,7 +1618,7 @@ __global__ __launch_bounds__(64, 5) void realign_band_kernel(RealignArgs A)
         if (!win.ok) { finish(out, IM_ST_ABORT, 0, lane); continue; }
         const int left1 = win.left1, right1 = win.right1;
         // piece 1: the whole read in [left1, right1)
-        const Band b1 = band_search<0, DIRECT>(s, pk, contig, (uint32_t)left1, (uint32_t)right1, (uint32_t)anchor, 0u, (uint32_t)L, k, g, lane, 0u, nullptr IM_STAMP_PASS(16));
+        const Band b1 = band_search<0, DIRECT>(s, pk, contig, (uint32_t)left1, (uint32_t)right1, (uint32_t)anchor, 0u, (uint32_t)L, k, g, lane, 0u, false, nullptr IM_STAMP_PASS(16));
         if (b1.st) { finish(out, b1.st, 1, lane); continue; }
         const int up1 = ((uint32_t)L < k) ? b1.low : b1.low + (int)g;      // read shorter than k: low == up (408-412)
         const BandAln a1 = band_alignment(G, contig, rd, 0, L, left1, right1 - left1, b1.low, up1, 0, lane);
@@ -1566,7 +1653,7 @@ __global__ __launch_bounds__(64, 5) void realign_band_kernel(RealignArgs A)
         if (pl.st != kStGoOn) { finish(out, pl.st, 1, lane); continue; }
         const uint32_t w0 = pl.w0, w1 = pl.w1, p0 = pl.p0, p1 = pl.p1; const bool want_tail = pl.want_tail;
         // piece 2
-        const Band b2 = band_search<0, DIRECT>(s, pk, contig, w0, w1, pl.anc, p0, p1, k, g, lane, 0u, nullptr IM_STAMP_PASS(21));
+        const Band b2 = band_search<0, DIRECT>(s, pk, contig, w0, w1, pl.anc, p0, p1, k, g, lane, 0u, false, nullptr IM_STAMP_PASS(21));
         if (b2.st) { finish(out, b2.st, 2, lane); continue; }
         const int up2 = ((p1 - p0) < k) ? b2.low : b2.low + (int)g;
         const BandAln a2 = band_alignment(G, contig, rd, (int)p0, (int)(p1 - p0), (int)w0, (int)(w1 - w0), b2.low, up2, 1, lane);

@@ -116,13 +116,13 @@ __device__ __forceinline__ Pieces choose_pieces(int q1, int q2, int q3, int q4, 
 // evidence slots.  eqA / eqB: bit j set where this lane's position j is an aligned '=' of A / B (bits outside the
 // pieces are ignored: A counts on [0,qa2), B on [qb1,L)).  bpos: IM_MAX_OPS + 1 ints of LDS nobody else uses meanwhile.
 // Returns IM_ST_EVIDENCE with the record complete, or the status the caller finishes the read with.
-// PPL == 4 means L <= 255 (kShortRead): both prefix counts then travel in one scan and the split search is one packed
-// maximum -- realign_kernel is bound by instruction issue and keeps both.
+// PPL <= 4 means L <= 255 (kShortRead; PPL == 2: L <= 128): both prefix counts then travel in one scan and the split
+// search is one packed maximum -- realign_kernel is bound by instruction issue and keeps both.
 template <int PPL>
 __device__ __forceinline__ int merge_pieces(uint32_t eqA, uint32_t eqB, int qa2, int rA, int qb1, int rB, bool split, int L,
                                             int32_t* bpos, im_read_result* out, const RealignArgs& A, int c, int lane)
 {
-    static_assert(PPL == 4 || PPL == 16, "four positions per lane (reads up to kShortRead) or sixteen");
+    static_assert(PPL == 2 || PPL == 4 || PPL == 16, "two positions per lane (reads up to 128 bases), four (up to kShortRead) or sixteen");
     // per-position match flags of A on [0,qa2) and B on [qb1,L)
     const int x0 = PPL * lane;
     uint32_t fa = 0, fb = 0;
@@ -134,7 +134,7 @@ __device__ __forceinline__ int merge_pieces(uint32_t eqA, uint32_t eqB, int qa2,
     }
     const int ta = __popc(fa), tb = __popc(fb);
     int ia, ib, totA, totB;
-    if constexpr (PPL == 4) {
+    if constexpr (PPL <= 4) {
         const int iab = wave_scan_add(ta | (tb << 16), lane);          // both counts in one scan: each stays below 2^15
         const int tot = __builtin_amdgcn_readlane(iab, 63);
         ia = iab & 0xFFFF; ib = iab >> 16;
@@ -149,7 +149,7 @@ __device__ __forceinline__ int merge_pieces(uint32_t eqA, uint32_t eqB, int qa2,
     if (split) {
         // count_matches(i) = '=' of A in read[0,i) + '=' of B in read[i,L); X counts are L - that, so "max matches,
         // then min mismatches, first wins" is the first maximum.
-        if constexpr (PPL == 4) {
+        if constexpr (PPL <= 4) {
             // one reduction for both: (matches << 8) | (255 - x), largest wins -- matches and x stay below 256
             int bk = -1;
 #pragma unroll
@@ -235,7 +235,9 @@ __device__ __forceinline__ int merge_pieces(uint32_t eqA, uint32_t eqB, int qa2,
             slot++;
         }
     }
-    seg_indel = __builtin_amdgcn_readlane(seg_indel, (uint32_t)index / PPL);    // the lane that owns read position `index` set it (0 if index == L)
+    // the lane that owns read position `index` set it (0 if index == L: no lane owns L -- at PPL == 2 and L == 128 that is
+    // lane 64, which is lane 0 again, and lane 0 owns no boundary at `index` then)
+    seg_indel = __builtin_amdgcn_readlane(seg_indel, ((uint32_t)index / PPL) & 63u);
     if (lane == 0) {
         if (hasD) out->ops[seg_indel] = ((uint32_t)(rindex - refindx) << 4) | IM_OP_D;
         im_evidence* e = &out->ev[0];
