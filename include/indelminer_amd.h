@@ -574,6 +574,27 @@ int im_clip_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const uint8_t* side, 
 int im_clip_build(im_ctx* ctx, int64_t contig_len, int32_t n, const int32_t* pos, const uint8_t* side);
 int im_clip_query(im_ctx* ctx, int32_t n, const uint8_t* side, const int32_t* beg, const int32_t* end, uint32_t* count_out, int32_t* pos_out);
 
+/* Facing piles, the breakpoints of large insertions (-I).  An insertion too long for a read to span leaves what a deletion leaves,
+ * the other way round: the reads from the left align through pr - 1 and clip there (clipR[pr]), the reads from the right align from
+ * pl and clip in front of it (clipL[pl]), and pl <= pr -- the stretch [pl, pr) is the target-site duplication, or the micro-homology
+ * an aligner extended into.  A deletion has pl > pr and is never a facing pile.  Unlike every query above this one names no interval:
+ * it SEARCHES a whole contig.  With m = min_reads >= 1 and T = max_overlap, 0 <= T <= 64, on a contig with R = clipR and L = clipL
+ * (length + 1 entries each), position p in [0, length] is a FACING PILE iff
+ *   R[p] >= m;
+ *   p is a peak of R: R[p] > R[x] for every x in [p - T, p) and R[p] >= R[x] for every x in (p, p + T], both clipped to [0, length]
+ *   (of equal peaks within reach of each other the leftmost is the pile: the family's "smallest position" rule);
+ *   the largest L[x] over x in [p - T, p], clipped to [0, length], the largest x among equals (the smallest overlap), is >= m.
+ * The answer per pile is pr = p, pl = that x, cr = R[p], cl = L[x].  The windows stop at the contig's own entries: the run of the next
+ * contig in the genome-wide arrays never enters.  Piles come back sorted by pr ascending.  *n_found is ALWAYS the number of piles;
+ * when it exceeds cap the call still returns IM_OK, the four arrays are unspecified and the caller asks again with a larger cap.
+ * im_clip_facing_tid searches contig tid of the genome-wide arrays (im_clip_enable; the scatters must have completed),
+ * im_clip_facing the arrays of the last im_clip_build.  A min_reads below 1, a max_overlap outside 0 .. 64, a negative cap, a null
+ * n_found, or a null array with cap >= 1 is IM_E_ARG; the rest as for im_clip_query_tid.  Synchronous, on the context's stream. */
+int im_clip_facing_tid(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t max_overlap, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr,
+                       uint32_t* cl, int32_t* n_found);
+int im_clip_facing(im_ctx* ctx, int32_t min_reads, int32_t max_overlap, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl,
+                   int32_t* n_found);
+
 /* Clip tails, what the clipped reads were clipped OF (-V).  The counts above say where reads stop; an adapter, a chimera, an insertion
  * or an inversion leaves the same pile.  At a deletion of the 0-based bases [a, b) the clipped tail of a read from the left is the
  * reference from b on, and the clipped head of a read from the right is the reference in front of a.  A keyed table keeps the
@@ -623,6 +644,21 @@ int im_cliptail_verify(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* pr, 
                        uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left);
 int im_cliptail_reset(im_ctx* ctx, void* stream);
 int im_cliptail_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
+
+/* The consensus of a pile (-I): what the entries at one key say when compared with EACH OTHER, not with the reference -- at a facing
+ * pile the right entries at pr hold the first bases of the inserted sequence and the left entries at pl its last ones.  A query is
+ * (tid, pos, side), with min_cover c >= 1.  E = the entries stored at the key; entry e has n_e bases b_e[i], i = 0 nearest the junction.
+ *   cover(i) = #{e : n_e > i} (it does not increase with i);  len = #{i < 32 : cover(i) >= c};
+ *   for i < len, cons[i] = the base most entries hold at i, the smallest code (A < C < G < T) among equals;
+ *   entry e AGREES iff it differs from cons in at most min(n_e, len) >> 4 of its first min(n_e, len) bases (the tolerance of verify).
+ * The answer per query is entries = |E|, len, the consensus as the table's own two planes (planes[2 q]: low bits, planes[2 q + 1]: high
+ * bits, codes A C G T = 0 1 2 3, bits from len on zero) and agree, which is 0 when len is 0.  Every output is independent of the order in
+ * which the entries arrived.  A position outside [0, length] answers all zeros.  Once dropped > 0 every output of the call is
+ * 0xFFFFFFFF, as for im_cliptail_verify.  A min_cover below 1 or a side other than 0 and 1 is IM_E_ARG.  The table is built for piles
+ * of tens of reads: a pile of thousands of entries is one long probe run that every query of its neighbourhood walks twice here.
+ * Synchronous, on the context's stream. */
+int im_cliptail_consensus(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* pos, const uint8_t* side, int32_t min_cover, uint32_t* entries,
+                          uint32_t* len, uint32_t* planes, uint32_t* agree);
 
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 

@@ -235,6 +235,9 @@ def lib():
         L.im_cliptail_verify.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_cliptail_reset.argtypes = [C.c_void_p, C.c_void_p]
         L.im_cliptail_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.im_clip_facing_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        L.im_clip_facing.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        L.im_cliptail_consensus.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_capture_begin.argtypes = [C.c_void_p, C.c_void_p]
@@ -625,6 +628,37 @@ class Context:
         stored, dropped = C.c_uint64(0), C.c_uint64(0)
         self._check(lib().im_cliptail_stats(self.h, C.byref(stored), C.byref(dropped)))
         return int(stored.value), int(dropped.value)
+
+    def _clip_facing(self, fn, min_reads, max_overlap, cap, *tid):
+        """(pr, pl, cr, cl) of the facing piles, sorted by pr; asks again with a larger cap when there are more than cap"""
+        while True:
+            out = [np.zeros(max(cap, 1), dtype=np.int32 if k < 2 else np.uint32) for k in range(4)]
+            found = C.c_int32(0)
+            self._check(fn(self.h, *tid, int(min_reads), int(max_overlap), int(cap), *[_ptr(o) for o in out], C.byref(found)))
+            if found.value <= cap:
+                return tuple(o[:found.value] for o in out)
+            cap = found.value
+
+    def clip_facing_tid(self, tid, min_reads, max_overlap, cap=65536):
+        """the facing piles of contig tid in the genome-wide clip arrays (-I): right clips piling up at pr with left clips piling up
+        at pl in [pr - max_overlap, pr], at least min_reads on either side"""
+        return self._clip_facing(lib().im_clip_facing_tid, min_reads, max_overlap, cap, int(tid))
+
+    def clip_facing(self, min_reads, max_overlap, cap=65536):
+        """the same on the arrays of the last clip_build"""
+        return self._clip_facing(lib().im_clip_facing, min_reads, max_overlap, cap)
+
+    def cliptail_consensus(self, tid, pos, side, min_cover):
+        """per query (pos, side) on contig tid: (entries, len, low-bit plane, high-bit plane, agree) of the pile's per-base consensus;
+        after an overflow every value is 0xFFFFFFFF"""
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        side = np.ascontiguousarray(side, dtype=np.uint8)
+        assert len(pos) == len(side)
+        n = len(pos)
+        entries, ln, agree = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        planes = np.zeros(2 * max(n, 1), dtype=np.uint32)
+        self._check(lib().im_cliptail_consensus(self.h, int(tid), n, _ptr(pos), _ptr(side), int(min_cover), _ptr(entries), _ptr(ln), _ptr(planes), _ptr(agree)))
+        return entries[:n], ln[:n], planes[0:2 * n:2], planes[1:2 * n:2], agree[:n]
 
     def cluster_sr(self, cls, b1, b2, marker=2**31 - 1, tie_desc=0):
         n = len(cls)

@@ -1078,6 +1078,62 @@ int im_clip_query(im_ctx* ctx, int32_t n, const uint8_t* side, const int32_t* be
     return query_contig_array(ctx, &im_ctx::clip_r, "im_clip", n, beg, end, kArgMax, count_out, &x);
 }
 
+// the facing piles of one contig's two arrays: the counter and four arrays of cap in the workspace, one launch, the counter back,
+// then what was found (piles are few), sorted by pr here
+static int facing_arrays(im_ctx* ctx, const char* who, const int32_t* right, const int32_t* left, int64_t clen, int32_t min_reads, int32_t max_overlap,
+                         int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, int32_t* n_found)
+{
+    if (min_reads < 1) { set_err(ctx, "%s: min_reads %d, must be >= 1", who, min_reads); return IM_E_ARG; }
+    if (max_overlap < 0 || max_overlap > 64) { set_err(ctx, "%s: max_overlap %d, must be 0 .. 64", who, max_overlap); return IM_E_ARG; }
+    if (cap < 0) { set_err(ctx, "%s: cap %d, must be >= 0", who, cap); return IM_E_ARG; }
+    if (!n_found || (cap > 0 && (!pr || !pl || !cr || !cl))) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = up256(sizeof(int32_t) * (size_t)(cap ? cap : 1));
+    int rc = ensure_ws(ctx, 256 + 4 * sb);
+    if (rc) return rc;
+    uint32_t* d_count = (uint32_t*)ctx->ws;
+    void* d_out[4];
+    for (int k = 0; k < 4; k++) d_out[k] = (char*)ctx->ws + 256 + k * sb;
+    uint32_t found = 0;
+    HIP_TRY(ctx, im::launch_clip_facing(right, left, clen, min_reads, max_overlap, cap, (int32_t*)d_out[0], (int32_t*)d_out[1], (uint32_t*)d_out[2],
+                                        (uint32_t*)d_out[3], d_count, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&found, d_count, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *n_found = (int32_t)found;
+    if (found == 0 || found > (uint32_t)cap) return IM_OK;          // more than cap: the caller asks again
+    std::vector<int32_t> h[4];
+    for (int k = 0; k < 4; k++) {
+        h[k].resize(found);
+        HIP_TRY(ctx, hipMemcpyAsync(h[k].data(), d_out[k], sizeof(int32_t) * (size_t)found, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> order(found);
+    for (uint32_t i = 0; i < found; i++) order[i] = (int32_t)i;
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return h[0][a] < h[0][b]; });      // a position is a pile once
+    for (uint32_t i = 0; i < found; i++) {
+        const int32_t k = order[i];
+        pr[i] = h[0][k]; pl[i] = h[1][k]; cr[i] = (uint32_t)h[2][k]; cl[i] = (uint32_t)h[3][k];
+    }
+    return IM_OK;
+}
+
+int im_clip_facing_tid(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t max_overlap, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr,
+                       uint32_t* cl, int32_t* n_found)
+{
+    if (!ctx || !ctx->all_clip_r.data || !ctx->all_clip_l.data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    const int64_t at = ctx->h_asc_off[tid];
+    return facing_arrays(ctx, "im_clip_facing_tid", ctx->all_clip_r.data + at, ctx->all_clip_l.data + at, ctx->h_len[tid], min_reads, max_overlap, cap,
+                         pr, pl, cr, cl, n_found);
+}
+
+int im_clip_facing(im_ctx* ctx, int32_t min_reads, int32_t max_overlap, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl,
+                   int32_t* n_found)
+{
+    if (!ctx) return IM_E_ARG;
+    if (ctx->clip_r.len < 0 || ctx->clip_l.len < 0) { set_err(ctx, "im_clip_build has not been called"); return IM_E_ARG; }
+    return facing_arrays(ctx, "im_clip_facing", ctx->clip_r.data, ctx->clip_l.data, ctx->clip_r.len, min_reads, max_overlap, cap, pr, pl, cr, cl, n_found);
+}
+
 // ---- clip tails: the clipped bases of clipped reads against the reference behind the partner breakpoint ----------
 
 int im_cliptail_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq, int32_t log2_slots)
@@ -1173,6 +1229,44 @@ int im_cliptail_verify(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* pr, 
     HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (counters[1] > 0) for (int k = 0; k < 5; k++) memset(h_out[k], 0xFF, sizeof(uint32_t) * (size_t)nq);     // no answer, not a wrong one
+    return IM_OK;
+}
+
+// [pos][side] in, one launch, the five words per query and the two counters back, one wait; after an overflow every answer is "none"
+int im_cliptail_consensus(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* pos, const uint8_t* side, int32_t min_cover, uint32_t* entries,
+                          uint32_t* len, uint32_t* planes, uint32_t* agree)
+{
+    if (!ctx || nq < 0) return IM_E_ARG;
+    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
+    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    if (min_cover < 1) { set_err(ctx, "im_cliptail_consensus: min_cover %d, must be >= 1", min_cover); return IM_E_ARG; }
+    if (nq == 0) return IM_OK;
+    if (!pos || !side || !entries || !len || !planes || !agree) return IM_E_ARG;
+    for (int32_t q = 0; q < nq; q++) if (side[q] > 1) { set_err(ctx, "im_cliptail_consensus: query %d: side %d, must be 0 (right) or 1 (left)", q, (int)side[q]); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = up256(sizeof(int32_t) * (size_t)nq);
+    int rc = ensure_ws(ctx, 7 * sb);
+    if (rc) return rc;
+    int32_t* d_pos = (int32_t*)ctx->ws;
+    uint8_t* d_side = (uint8_t*)ctx->ws + sb;
+    uint32_t* d_entries = (uint32_t*)((char*)ctx->ws + 2 * sb);
+    uint32_t* d_len = (uint32_t*)((char*)ctx->ws + 3 * sb);
+    uint32_t* d_agree = (uint32_t*)((char*)ctx->ws + 4 * sb);
+    uint32_t* d_planes = (uint32_t*)((char*)ctx->ws + 5 * sb);      // two words per query
+    unsigned long long counters[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(d_pos, pos, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_side, side, (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, im::launch_cliptail_consensus(nq, tid, d_pos, d_side, min_cover, ctx->h_len[tid], ctx->tail, d_entries, d_len, d_planes, d_agree, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(entries, d_entries, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(len, d_len, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(agree, d_agree, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(planes, d_planes, 2 * sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (counters[1] > 0) {                                          // no answer, not a wrong one
+        memset(entries, 0xFF, sizeof(uint32_t) * (size_t)nq); memset(len, 0xFF, sizeof(uint32_t) * (size_t)nq);
+        memset(agree, 0xFF, sizeof(uint32_t) * (size_t)nq); memset(planes, 0xFF, 2 * sizeof(uint32_t) * (size_t)nq);
+    }
     return IM_OK;
 }
 

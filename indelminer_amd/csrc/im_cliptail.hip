@@ -20,6 +20,7 @@
 //                      their workgroup draws with one atomic add
 //   cliptail_add       one lane per entry the host names (the record-at-a-time path)
 //   cliptail_verify    one wave per query (tid, pr, pl): see the kernel
+//   cliptail_consensus one wave per query (tid, position, side): the per-base consensus of a pile's entries (-I), on the same walk
 
 #include "im_device.hpp"
 #include "im_spanrec.hpp"
@@ -225,15 +226,14 @@ __device__ __forceinline__ TailWindow tail_window(const uint8_t* __restrict__ re
     return W;
 }
 
-// One side of a query: the wave walks the probe run of (tid, pos, side) 64 slots at a time until a batch shows an empty slot.  A lane
-// whose slot (in front of the first empty one) holds an entry of the key tests the shifts 0 .. S against the window: a shift of the
-// planes, two XORs, the window's validity, a mask of n bits and a popcount.  Lane s gathers v(s) from the ballots.  Returns the
-// entries stored at the key (wave-uniform); *v: this lane's v(lane).
-__device__ __forceinline__ uint32_t tail_side(const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, const TailWindow& W,
-                                              bool compare, int32_t S, int lane, uint32_t* v)
+// The walk every query shares: the wave goes along the probe run of (tid, pos, side) 64 slots at a time until a batch shows an empty
+// slot.  each(has, key, slot) is called, by the whole wave, for every batch in which some lane's slot (in front of the first empty
+// one) holds an entry of the key: has says whether this lane's does.  Returns the entries stored at the key (wave-uniform); a
+// position outside [0, clen] has none.
+template <class Each>
+__device__ __forceinline__ uint32_t tail_walk(const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, int lane, Each each)
 {
-    uint32_t stored = 0, mine = 0;
-    *v = 0;
+    uint32_t stored = 0;
     if (pos < 0 || pos > clen) return 0;
     const uint64_t slots = 1ull << T.log2_slots, mask = slots - 1ull;
     const uint64_t want = tail_key(tid, pos, side, 0u) >> 6;
@@ -247,19 +247,31 @@ __device__ __forceinline__ uint32_t tail_side(const TailTable& T, int32_t tid, i
         const uint64_t holders = __ballot(has);
         if (holders) {
             stored += (uint32_t)__builtin_popcountll(holders);
-            if (compare) {
-                const uint64_t payload = has ? T.slots[2ull * s + 1ull] : 0ull;
-                const uint32_t e_lo = (uint32_t)payload, e_hi = (uint32_t)(payload >> 32);
-                const uint32_t n = (uint32_t)key & 63u, m = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u, allowed = n >> 4;
-                for (int32_t sh = 0; sh <= S; sh++) {               // wave-uniform
-                    const uint32_t diff = (((uint32_t)(W.lo >> sh) ^ e_lo) | ((uint32_t)(W.hi >> sh) ^ e_hi) | ~(uint32_t)(W.ok >> sh)) & m;
-                    const uint64_t match = __ballot(has && (uint32_t)__builtin_popcount(diff) <= allowed);
-                    if (lane == sh) mine += (uint32_t)__builtin_popcountll(match);
-                }
-            }
+            each(has, key, s);
         }
         if (empty) break;
     }
+    return stored;
+}
+
+// One side of a verify query.  A lane whose slot holds an entry of the key tests the shifts 0 .. S against the window: a shift of the
+// planes, two XORs, the window's validity, a mask of n bits and a popcount.  Lane s gathers v(s) from the ballots.  Returns the
+// entries stored at the key (wave-uniform); *v: this lane's v(lane).
+__device__ __forceinline__ uint32_t tail_side(const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, const TailWindow& W,
+                                              bool compare, int32_t S, int lane, uint32_t* v)
+{
+    uint32_t mine = 0;
+    const uint32_t stored = tail_walk(T, tid, pos, side, clen, lane, [&](bool has, uint64_t key, uint64_t s) {
+        if (!compare) return;
+        const uint64_t payload = has ? T.slots[2ull * s + 1ull] : 0ull;
+        const uint32_t e_lo = (uint32_t)payload, e_hi = (uint32_t)(payload >> 32);
+        const uint32_t n = (uint32_t)key & 63u, m = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u, allowed = n >> 4;
+        for (int32_t sh = 0; sh <= S; sh++) {                       // wave-uniform
+            const uint32_t diff = (((uint32_t)(W.lo >> sh) ^ e_lo) | ((uint32_t)(W.hi >> sh) ^ e_hi) | ~(uint32_t)(W.ok >> sh)) & m;
+            const uint64_t match = __ballot(has && (uint32_t)__builtin_popcount(diff) <= allowed);
+            if (lane == sh) mine += (uint32_t)__builtin_popcountll(match);
+        }
+    });
     *v = mine;
     return stored;
 }
@@ -311,7 +323,80 @@ __global__ __launch_bounds__(kTailWaveBlock) void cliptail_verify_kernel(TailVer
     }
 }
 
+struct TailConsensusArgs {
+    int32_t nq, tid, min_cover;
+    const int32_t* pos;
+    const uint8_t* side;
+    int64_t clen;
+    TailTable tab;
+    uint32_t* entries;
+    uint32_t* len;
+    uint32_t* planes;           // two per query: low bits, high bits
+    uint32_t* agree;
+};
+
+// One wave per query (tid, pos, side): the per-base consensus of the entries stored at the key (-I).  First walk: for base
+// i = 0 .. 31 (wave-uniform) three ballots over the lanes that hold an entry with n > i -- those, their low bits, their high bits --
+// give the four codes' counts at i as popcounts, and lane i keeps them.  Lanes 0 .. 31 then pick their base (the most entries, the
+// smallest code among equals) where cover(i) >= min_cover; cover does not increase with i, so those lanes are 0 .. len - 1 and two
+// ballots give the planes.  Second walk: the entries that differ from the consensus in at most min(n, len) >> 4 of their first
+// min(n, len) bases.  Counts are sums over the entries: nothing depends on the order they arrived in.
+__global__ __launch_bounds__(kTailWaveBlock) void cliptail_consensus_kernel(TailConsensusArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int q = wave; q < A.nq; q += nwaves) {
+        const int64_t pos = A.pos[q];
+        const uint32_t side = A.side[q];
+        uint32_t cnt[4] = {0u, 0u, 0u, 0u};
+        const uint32_t stored = tail_walk(A.tab, A.tid, pos, side, A.clen, lane, [&](bool has, uint64_t key, uint64_t s) {
+            const uint64_t payload = has ? A.tab.slots[2ull * s + 1ull] : 0ull;
+            const uint32_t e_lo = (uint32_t)payload, e_hi = (uint32_t)(payload >> 32);
+            const uint32_t n = has ? (uint32_t)key & 63u : 0u;
+#pragma unroll 4
+            for (int i = 0; i < kTailBases; i++) {                  // wave-uniform
+                const uint64_t cov = __ballot(n > (uint32_t)i);
+                const uint64_t lo = __ballot(n > (uint32_t)i && ((e_lo >> i) & 1u)), hi = __ballot(n > (uint32_t)i && ((e_hi >> i) & 1u));
+                if (lane == i) {
+                    cnt[0] += (uint32_t)__builtin_popcountll(cov & ~lo & ~hi); cnt[1] += (uint32_t)__builtin_popcountll(lo & ~hi);
+                    cnt[2] += (uint32_t)__builtin_popcountll(hi & ~lo); cnt[3] += (uint32_t)__builtin_popcountll(lo & hi);
+                }
+            }
+        });
+        const bool covered = lane < kTailBases && cnt[0] + cnt[1] + cnt[2] + cnt[3] >= (uint32_t)A.min_cover;
+        uint32_t code = 0, most = cnt[0];
+#pragma unroll
+        for (uint32_t c = 1; c < 4u; c++) if (cnt[c] > most) { most = cnt[c]; code = c; }      // strictly: the smallest code among equals stays
+        const uint32_t len = (uint32_t)__builtin_popcountll(__ballot(covered));
+        const uint32_t c_lo = (uint32_t)__ballot(covered && (code & 1u)), c_hi = (uint32_t)__ballot(covered && (code & 2u));
+        uint32_t agree = 0;
+        if (len > 0u) {
+            (void)tail_walk(A.tab, A.tid, pos, side, A.clen, lane, [&](bool has, uint64_t key, uint64_t s) {
+                const uint64_t payload = has ? A.tab.slots[2ull * s + 1ull] : 0ull;
+                const uint32_t n = (uint32_t)key & 63u, k = n < len ? n : len, m = k >= 32u ? 0xFFFFFFFFu : (1u << k) - 1u;
+                const uint32_t diff = (((uint32_t)payload ^ c_lo) | ((uint32_t)(payload >> 32) ^ c_hi)) & m;
+                agree += (uint32_t)__builtin_popcountll(__ballot(has && (uint32_t)__builtin_popcount(diff) <= (k >> 4)));
+            });
+        }
+        if (lane == 0) { A.entries[q] = stored; A.len[q] = len; A.planes[2 * q] = c_lo; A.planes[2 * q + 1] = c_hi; A.agree[q] = agree; }
+    }
+}
+
 }  // namespace
+
+hipError_t launch_cliptail_consensus(int32_t nq, int32_t tid, const int32_t* pos, const uint8_t* side, int32_t min_cover, int64_t clen,
+                                     const TailTable& tab, uint32_t* entries, uint32_t* len, uint32_t* planes, uint32_t* agree, hipStream_t stream)
+{
+    if (nq <= 0) return hipSuccess;
+    TailConsensusArgs A;
+    A.nq = nq; A.tid = tid; A.min_cover = min_cover; A.pos = pos; A.side = side; A.clen = clen; A.tab = tab;
+    A.entries = entries; A.len = len; A.planes = planes; A.agree = agree;
+    int b = (nq + 3) / 4;
+    if (b > 2048) b = 2048;
+    hipLaunchKernelGGL(cliptail_consensus_kernel, dim3(b), dim3(kTailWaveBlock), 0, stream, A);
+    return hipGetLastError();
+}
 
 hipError_t launch_cliptail_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const im_dev_records& recs, const TailTable& tab,
                                    hipStream_t stream)

@@ -125,6 +125,11 @@ hipError_t launch_clip_build(int64_t clen, int32_t n, const int32_t* pos, const 
 // per query the largest count over [beg, end] inclusive of right (side 0) or left (side 1) and the smallest position holding it; (0, -1) when empty
 hipError_t launch_clip_argmax(int32_t nq, const uint8_t* side, const int32_t* beg, const int32_t* end, const int32_t* right, const int32_t* left,
                               int64_t clen, uint32_t* count_out, int32_t* pos_out, hipStream_t stream);
+// the facing piles of one contig's two arrays (clen + 1 entries each, 16-byte aligned): positions pr with right[pr] >= min_reads that
+// are a peak of right within max_overlap and have left[pl] >= min_reads for some pl in [pr - max_overlap, pr]; *n_found (cleared here)
+// counts them all, the first cap that take a slot are written, in no particular order
+hipError_t launch_clip_facing(const int32_t* right, const int32_t* left, int64_t clen, int32_t min_reads, int32_t max_overlap, int32_t cap,
+                              int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* n_found, hipStream_t stream);
 // im_cliptail.hip: the clipped bases of clipped reads in a keyed table (-V).  slots: 2^log2_slots pairs (key, payload) of 64-bit
 // words, zeros = empty; counters[0]: inserts asked for, counters[1]: those dropped because half of the slots were taken
 struct TailTable {
@@ -143,6 +148,10 @@ hipError_t launch_cliptail_add(int32_t n, int32_t tid, int64_t clen, const int32
 hipError_t launch_cliptail_verify(int32_t nq, int32_t tid, const int32_t* pr, const int32_t* pl, int32_t max_shift, const uint8_t* ref,
                                   int64_t clen, const TailTable& tab, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
                                   uint32_t* stored_right, uint32_t* stored_left, hipStream_t stream);
+// per query (pos, side) on contig tid: the entries stored at the key, the bases covered by at least min_cover of them, their per-base
+// consensus as two planes (planes[2 q], planes[2 q + 1]) and the entries that agree with it; a position outside [0, clen] answers zeros
+hipError_t launch_cliptail_consensus(int32_t nq, int32_t tid, const int32_t* pos, const uint8_t* side, int32_t min_cover, int64_t clen,
+                                     const TailTable& tab, uint32_t* entries, uint32_t* len, uint32_t* planes, uint32_t* agree, hipStream_t stream);
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);

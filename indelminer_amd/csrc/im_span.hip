@@ -35,6 +35,7 @@
 // A record can add to both; an S anywhere else is not looked at here (the triage of the same chunk ends the run on it).
 //   clip_scatter   one lane per delivered record: the core and two CIGAR words at either end decide, a right clip walks its CIGAR
 //   clip_argmax    one wave per query: the largest count over [beg, end] inclusive and the smallest position that holds it
+//   clip_facing    one lane per four positions of one contig: the facing piles of the two arrays (-I), the one chip-wide search
 // The record-at-a-time path names the events itself: clip_build adds one per (position, side).
 
 #include "im_device.hpp"
@@ -331,6 +332,89 @@ __global__ __launch_bounds__(256) void clip_argmax_kernel(int32_t nq, const uint
     }
 }
 
+// Facing piles (-I): the positions of one contig at which right clips pile up with left clips piling up at or just in front of
+// them -- the definition is in include/indelminer_amd.h (seam 5, "Facing piles").  R, L: the contig's clen + 1 counts.
+constexpr int kFacingBlock = 256;
+constexpr int kFacingPer = 4;                                   // positions of a lane's one 16-byte load
+constexpr int kFacingSweeps = 4;                                // loads a lane has in flight: a workgroup owns 4 x 1024 positions
+constexpr int kFacingSweep = kFacingBlock * kFacingPer;         // positions a workgroup covers with one load per lane
+constexpr int kFacingTile = kFacingSweep * kFacingSweeps;
+
+struct FacingArgs {
+    const int32_t* right;
+    const int32_t* left;
+    int64_t clen;
+    int32_t min_reads, max_overlap, cap;
+    int32_t* pr;
+    int32_t* pl;
+    uint32_t* cr;
+    uint32_t* cl;
+    uint32_t* n_found;
+};
+
+// whether p (R[p] = v >= min_reads) is a peak of R and has a partner in L: the windows stop at the contig's own entries
+__device__ __forceinline__ bool facing_at(const FacingArgs& A, int64_t p, int32_t v, int32_t* pl, int32_t* cl)
+{
+    const int64_t T = A.max_overlap;
+    const int64_t lo = p - T < 0 ? 0 : p - T, hi = p + T > A.clen ? A.clen : p + T;
+    bool peak = true;
+    for (int64_t x = lo; x < p; x++) peak = peak && A.right[x] < v;             // the leftmost of equal peaks wins
+    for (int64_t x = p + 1; x <= hi; x++) peak = peak && A.right[x] <= v;
+    if (!peak) return false;
+    int32_t best = -1;
+    int64_t at = p;
+    for (int64_t x = p; x >= lo; x--) {                                          // downwards: the largest x among equal counts stays
+        const int32_t c = A.left[x];
+        if (c > best) { best = c; at = x; }
+    }
+    *pl = (int32_t)at; *cl = best;
+    return best >= A.min_reads;
+}
+
+// One streaming pass over R.  A lane takes four consecutive positions per 16-byte load, kFacingSweeps loads up front; nearly every
+// lane is done when all of them are below min_reads.  The rare lane that is not reads its windows from memory (L2: the workgroup has
+// just streamed R there), L is read only there.  Piles take their slots with one returning atomic per wave: the rank comes from a
+// ballot, the first lane of the ballot adds.  n_found counts every pile; only slots below cap are written.
+__global__ __launch_bounds__(kFacingBlock) void clip_facing_kernel(FacingArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t n = A.clen + 1;
+    const int64_t tile = (int64_t)blockIdx.x * kFacingTile;
+    int4 v[kFacingSweeps];
+#pragma unroll
+    for (int s = 0; s < kFacingSweeps; s++) {
+        const int64_t p0 = tile + (int64_t)s * kFacingSweep + (int64_t)threadIdx.x * kFacingPer;
+        if (p0 + kFacingPer <= n) v[s] = *reinterpret_cast<const int4*>(A.right + p0);
+        else {
+            // the contig's last entries: one by one, nothing is read behind entry clen
+            v[s].x = p0 < n ? A.right[p0] : 0; v[s].y = p0 + 1 < n ? A.right[p0 + 1] : 0;
+            v[s].z = p0 + 2 < n ? A.right[p0 + 2] : 0; v[s].w = 0;
+        }
+    }
+    const int32_t m = A.min_reads;
+#pragma unroll
+    for (int s = 0; s < kFacingSweeps; s++) {
+        const bool any = v[s].x >= m || v[s].y >= m || v[s].z >= m || v[s].w >= m;
+        if (!__ballot(any)) continue;                                            // wave-uniform: almost every sweep of every wave
+        const int64_t p0 = tile + (int64_t)s * kFacingSweep + (int64_t)threadIdx.x * kFacingPer;
+#pragma unroll
+        for (int j = 0; j < kFacingPer; j++) {
+            const int32_t c = j == 0 ? v[s].x : j == 1 ? v[s].y : j == 2 ? v[s].z : v[s].w;
+            const int64_t p = p0 + j;
+            int32_t pl = 0, cl = 0;
+            const bool pile = c >= m && p < n && facing_at(A, p, c, &pl, &cl);
+            const uint64_t piles = __ballot(pile);
+            if (!piles) continue;
+            const int first = (int)__builtin_ctzll(piles);
+            uint32_t base = 0;
+            if (lane == first) base = atomicAdd(A.n_found, (uint32_t)__builtin_popcountll(piles));
+            base = (uint32_t)__shfl((int)base, first);
+            const uint32_t slot = base + (uint32_t)__builtin_popcountll(piles & ((1ull << lane) - 1ull));
+            if (pile && slot < (uint32_t)A.cap) { A.pr[slot] = (int32_t)p; A.pl[slot] = pl; A.cr[slot] = (uint32_t)c; A.cl[slot] = (uint32_t)cl; }
+        }
+    }
+}
+
 // One wave per query: the minimum of span[p] over [beg, end] INCLUSIVE, clipped to [0, clen]; an interval that is empty after
 // the clip answers 0.  sums: the tile offsets of the tiled scan.
 __global__ __launch_bounds__(256) void span_query_kernel(int32_t nq, const int32_t* __restrict__ beg, const int32_t* __restrict__ end,
@@ -404,6 +488,19 @@ hipError_t launch_clip_argmax(int32_t nq, const uint8_t* side, const int32_t* be
     int b = (nq + 3) / 4;
     if (b > 2048) b = 2048;
     hipLaunchKernelGGL(clip_argmax_kernel, dim3(b), dim3(256), 0, stream, nq, side, beg, end, right, left, clen, count_out, pos_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_clip_facing(const int32_t* right, const int32_t* left, int64_t clen, int32_t min_reads, int32_t max_overlap, int32_t cap,
+                              int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* n_found, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(n_found, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    FacingArgs A;
+    A.right = right; A.left = left; A.clen = clen; A.min_reads = min_reads; A.max_overlap = max_overlap; A.cap = cap;
+    A.pr = pr; A.pl = pl; A.cr = cr; A.cl = cl; A.n_found = n_found;
+    const int64_t blocks = (clen + 1 + kFacingTile - 1) / kFacingTile;          // clen <= 0x7fffff00: at most 2^19 workgroups
+    hipLaunchKernelGGL(clip_facing_kernel, dim3((unsigned)blocks), dim3(kFacingBlock), 0, stream, A);
     return hipGetLastError();
 }
 

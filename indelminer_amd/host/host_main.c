@@ -44,6 +44,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    (FORMAT CB:CS, where soft-clipped reads pile up and how many)\n");
     fprintf(file, "\t-V, with -G -C: verify those breakpoints by the clipped bases\n");
     fprintf(file, "\t    (FORMAT CV:CH, reads that continue across the deletion, and the shift)\n");
+    fprintf(file, "\t-I, with -G -C -V: write large insertions to this file, a VCF of its own\n");
+    fprintf(file, "\t    (clipped reads from either side facing each other, and what they agree on)\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -86,7 +88,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCV")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -116,6 +118,7 @@ int main(int argc, char** argv)
         case 'D': g_depth_evidence = 1; break;                      /* not an option of the reference */
         case 'C': g_clip_evidence = 1; break;                       /* not an option of the reference */
         case 'V': g_clip_verify = 1; break;                         /* not an option of the reference */
+        case 'I': g_ins_file = optarg; break;                       /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -190,11 +193,18 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: clip verification (-V) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -I: behind -V's refusals; every other refusal reaches it through -G, -C and -V */
+    if (g_ins_file) {
+        if (!g_clip_verify) { fprintf(stderr, "indelminer: -I needs -V\n"); return EXIT_FAILURE; }
+        if (!FACING_API_PRESENT) {
+            fprintf(stderr, "indelminer: large-insertion evidence (-I) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = 0;    /* -o detailed has no columns to add to */
+        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = 0; g_ins_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {
@@ -334,9 +344,18 @@ int main(int argc, char** argv)
         }
         if (chromid == -1) run_contig(&d, i, 0, d.hdr->target_len[i], r);
         else run_contig(&d, i, chromstart, chromstop, r);
+        if (FACING_ON) ins_contig(&d, i);            /* -I, record-at-a-time: behind the contig's flushes, on the arrays of its im_clip_build */
     }
 
     gpu_wait(&d);
+    if (FACING_ON) {
+        /* -I, pipelined: once, now that the last flush has printed and every scatter has completed; the genome-wide arrays were never
+         * reset and the table is keyed by contig */
+        for (int32_t i = 0; i < d.hdr->n_targets && use_pipeline; i++) ins_contig(&d, i);
+        if (!g_ins_out) ins_open();                 /* no contig at all: the header alone */
+        if (fclose(g_ins_out) != 0) fatalf("cannot write %s", g_ins_file);
+        g_ins_out = NULL;
+    }
     if (CLIPTAIL_ON) {
         /* -V: a table that overflowed has answered nothing since; said once, here */
         uint64_t stored = 0, dropped = 0;

@@ -423,6 +423,93 @@ static void clip_events(driver* d, const bam_record* b)
     }
 }
 
+/* -I: FILE, opened when the first contig is about to be searched (a run handed to the record-at-a-time child never gets here in the
+ * parent: the child writes the file) */
+static FILE* g_ins_out = NULL;
+static void ins_open(void)
+{
+    g_ins_out = fopen(g_ins_file, "w");
+    if (!g_ins_out) fatalf("cannot write %s", g_ins_file);
+    FILE* f = g_ins_out;
+    fprintf(f, "##fileformat=VCFv4.1\n");
+    fprintf(f, "##ALT=<ID=INS,Description=\"Insertion too long for a read to span: clipped reads from either side face each other\">\n");
+    fprintf(f, "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n");
+    fprintf(f, "##INFO=<ID=END,Number=1,Type=Integer,Description=\"Where the reads from the left stop aligning (POS: where the reads from the right start)\">\n");
+    fprintf(f, "##INFO=<ID=HOMLEN,Number=1,Type=Integer,Description=\"END - POS: bases aligned from both sides (target-site duplication or micro-homology)\">\n");
+    fprintf(f, "##INFO=<ID=CR,Number=2,Type=Integer,Description=\"Clipped reads that stop aligning at END, clipped reads that start aligning at POS\">\n");
+    fprintf(f, "##INFO=<ID=CN,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases were kept, either side\">\n");
+    fprintf(f, "##INFO=<ID=CA,Number=2,Type=Integer,Description=\"Of those, the reads that agree with the consensus of their side\">\n");
+    fprintf(f, "##INFO=<ID=LSEQ,Number=1,Type=String,Description=\"First bases of the inserted sequence: consensus of the clipped bases behind END\">\n");
+    fprintf(f, "##INFO=<ID=RSEQ,Number=1,Type=String,Description=\"Last bases of the inserted sequence: consensus of the clipped bases in front of POS\">\n");
+    fprintf(f, "##largeInsertion=\"a record per position END at which at least %d reads of mapping quality >= -q stop aligning with a soft clip of at least %d bases, "
+               "more than at any of the %d positions in front and no fewer than at any of the %d behind, when at least %d such reads start aligning at one of "
+               "the positions END - %d .. END (POS: the one with the most, the nearest to END among equals); LSEQ and RSEQ: per base the majority of up to 32 "
+               "clipped bases per read (A before C before G before T among equals), as far as at least %d reads reach; CA: reads with at most 1 difference "
+               "in 16 from it; CN, CA, LSEQ and RSEQ are . once the clip-tail table has overflowed (stderr says so); contig ends are skipped\"\n",
+            INS_EV_MIN_READS, CLIP_EV_MIN_CLIP, INS_EV_MAX_OVERLAP, INS_EV_MAX_OVERLAP, INS_EV_MIN_READS, INS_EV_MAX_OVERLAP, INS_EV_MIN_COVER);
+    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
+}
+
+/* the consensus of one pile as text: base 0 first, or (the left pile, turned back to reference orientation) base len - 1 first */
+static void ins_seq(char* out, uint32_t len, uint32_t lo, uint32_t hi, int reversed)
+{
+    if (len == 0 || len > CLIPTAIL_BASES) { strcpy(out, "."); return; }
+    for (uint32_t i = 0; i < len; i++) {
+        const uint32_t k = reversed ? len - 1 - i : i;
+        out[i] = "ACGT"[((lo >> k) & 1u) | (((hi >> k) & 1u) << 1)];
+    }
+    out[len] = 0;
+}
+
+/* -I: one contig's facing piles and the consensus of either pile, into FILE.  The clip arrays and the table hold every record of the
+ * contig: the pipelined path comes here when the last flush has printed, the record-at-a-time path behind the contig's flushes. */
+static void ins_contig(driver* d, int32_t tid)
+{
+    if (!g_ins_out) ins_open();
+    gpu_wait(d);
+    const int64_t clen = d->seqlen[tid];
+    int32_t cap = 65536, found = 0;
+    int32_t* pr = NULL; int32_t* pl = NULL; uint32_t* cr = NULL; uint32_t* cl = NULL;
+    pthread_mutex_lock(&g_query_mu);
+    for (;;) {
+        pr = xrealloc(pr, sizeof(int32_t) * (size_t)cap); pl = xrealloc(pl, sizeof(int32_t) * (size_t)cap);
+        cr = xrealloc(cr, sizeof(uint32_t) * (size_t)cap); cl = xrealloc(cl, sizeof(uint32_t) * (size_t)cap);
+        const int rc = d->pipe_mode ? im_clip_facing_tid(d->gpu, tid, INS_EV_MIN_READS, INS_EV_MAX_OVERLAP, cap, pr, pl, cr, cl, &found)
+                                    : im_clip_facing(d->gpu, INS_EV_MIN_READS, INS_EV_MAX_OVERLAP, cap, pr, pl, cr, cl, &found);
+        if (rc != IM_OK) fatalf("im_clip_facing: %s", im_last_error(d->gpu));
+        if (found <= cap) break;
+        cap = found;                /* more piles than asked for: once more, with room for all */
+    }
+    /* contig ends have nothing to anchor on */
+    int32_t n = 0;
+    for (int32_t k = 0; k < found; k++)
+        if (pl[k] != 0 && pr[k] != clen) { pr[n] = pr[k]; pl[n] = pl[k]; cr[n] = cr[k]; cl[n] = cl[k]; n++; }
+    if (n > 0) {
+        /* two queries per pile: right at pr, left at pl */
+        int32_t* qpos = xmalloc(sizeof(int32_t) * 2 * (size_t)n);
+        uint8_t* qside = xmalloc(2 * (size_t)n);
+        uint32_t* ans = xmalloc(sizeof(uint32_t) * 10 * (size_t)n);
+        uint32_t* ent = ans; uint32_t* len = ans + 2 * n; uint32_t* agree = ans + 4 * n; uint32_t* planes = ans + 6 * n;
+        for (int32_t k = 0; k < n; k++) { qpos[2 * k] = pr[k]; qside[2 * k] = 0; qpos[2 * k + 1] = pl[k]; qside[2 * k + 1] = 1; }
+        if (im_cliptail_consensus(d->gpu, tid, 2 * n, qpos, qside, INS_EV_MIN_COVER, ent, len, planes, agree) != IM_OK)
+            fatalf("im_cliptail_consensus: %s", im_last_error(d->gpu));
+        const char* seq = d->sequences[tid];
+        for (int32_t k = 0; k < n; k++) {
+            fprintf(g_ins_out, "%s\t%d\t.\t%c\t<INS>\t.\t.\tSVTYPE=INS;END=%d;HOMLEN=%d;CR=%u,%u;", d->hdr->target_name[tid], pl[k],
+                    toupper((unsigned char)seq[pl[k] - 1]), pr[k], pr[k] - pl[k], cr[k], cl[k]);
+            if (ent[2 * k] == CLIPTAIL_NONE) { fprintf(g_ins_out, "CN=.;CA=.;LSEQ=.;RSEQ=.\n"); continue; }
+            char ls[CLIPTAIL_BASES + 1], rs[CLIPTAIL_BASES + 1];
+            ins_seq(ls, len[2 * k], planes[4 * k], planes[4 * k + 1], 0);
+            ins_seq(rs, len[2 * k + 1], planes[4 * k + 2], planes[4 * k + 3], 1);
+            fprintf(g_ins_out, "CN=%u,%u;CA=%u,%u;LSEQ=%s;RSEQ=%s\n", ent[2 * k], ent[2 * k + 1], agree[2 * k], agree[2 * k + 1], ls, rs);
+        }
+        free(qpos); free(qside); free(ans);
+    }
+    pthread_mutex_unlock(&g_query_mu);
+    free(pr); free(pl); free(cr); free(cl);
+    phase_time("large-insertion evidence (device)");
+}
+
 static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_reader* r)
 {
     d->n_items = 0; d->n_flushes = 0;

@@ -172,6 +172,20 @@ extern int im_cliptail_stats(im_ctx*, uint64_t*, uint64_t*) __attribute__((weak)
 #define CLIPTAIL_BASES 32          /* bases an entry keeps at most */
 #define CLIPTAIL_MAX_SHIFT 32      /* the largest micro-homology a query tries */
 #define CLIPTAIL_NONE 0xFFFFFFFFu  /* what the device answers after its table has overflowed */
+/* -I FILE, with -G -C -V: large insertions, the one event the calls above cannot show -- where at least INS_EV_MIN_READS right clips
+ * pile up with as many left clips piling up at most INS_EV_MAX_OVERLAP bases in front of them (the device's search of the two clip
+ * arrays), and what the clipped bases of either pile agree on (the device's consensus over the clip-tail table).  A small VCF of its
+ * own, written to FILE; stdout and stderr stay as they are.  Not an option of the reference; referenced weakly. */
+static const char* g_ins_file = NULL;
+extern int im_clip_facing_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
+extern int im_clip_facing(im_ctx*, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
+extern int im_cliptail_consensus(im_ctx*, int32_t, int32_t, const int32_t*, const uint8_t*, int32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*) __attribute__((weak));
+#define FACING_ON (g_ins_file != NULL)             /* the run ends (a contig ends) with the search of the clip arrays */
+#define FACING_API_PRESENT (im_clip_facing_tid && im_clip_facing && im_cliptail_consensus)
+#define INS_EV_MIN_READS 3         /* clipped reads of the smaller pile */
+#define INS_EV_MAX_OVERLAP 30      /* bases the left-clip pile may stand in front of the right-clip pile: below DEPTH_EV_MIN_LEN, so the two
+                                    * piles of a deletion that gets CB:CS can never face each other */
+#define INS_EV_MIN_COVER 2         /* entries that must hold a base for the consensus to have one */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that
