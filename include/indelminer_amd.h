@@ -660,6 +660,44 @@ int im_cliptail_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
 int im_cliptail_consensus(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* pos, const uint8_t* side, int32_t min_cover, uint32_t* entries,
                           uint32_t* len, uint32_t* planes, uint32_t* agree);
 
+/* Crossed piles, the breakpoints of tandem duplications (-U).  One arrangement of two piles is left that nothing above reads: a
+ * right-clip pile at pr and a left-clip pile at pl with pl FAR IN FRONT of pr.  That is what a tandem duplication of the bases [pl, pr)
+ * leaves: a read that runs off the end of the first copy continues at the start of the second, so its clipped tail is ref[pl ...], and a
+ * read that enters the second copy from the first has a clipped head of ref[... pr - 1] -- the match rule of im_cliptail_verify to the
+ * letter, which answers 0, 0, -1 for every pl <= pr, while the facing search looks no further than its max_overlap in front of a pile.
+ * With m = min_reads >= 1, T = reach (0 .. 64), dmin = min_len >= 1, dmax = max_len >= dmin, S = max_shift (0 .. 32) and
+ * mv = min_verified >= 1, on a contig of length clen:
+ *   position p is a PEAK of an array A (clen + 1 entries) iff A[p] >= m, A[p] > A[x] for every x in [p - T, p) and A[p] >= A[x] for every
+ *   x in (p, p + T], both windows clipped to [0, clen] -- the peak half of the facing rule, applied to clipR and to clipL alike; two
+ *   peaks of one array are at least T + 1 apart;
+ *   a CANDIDATE is a peak pr of clipR and a peak pl of clipL of the same contig with dmin <= pr - pl <= dmax;
+ *   vR(s) = the right entries at (tid, pr) of which at most n >> 4 bases differ from ref[pl + s + i], vL(s) = the left entries at
+ *   (tid, pl) of which at most n >> 4 differ from ref[pr - 1 - s - i]; positions outside [0, clen) and bytes other than A, C, G, T are
+ *   mismatches (the rule of im_cliptail_verify, without its pl > pr condition);
+ *   the chosen s has the largest vR(s) + vL(s) over 0 .. S, the smallest s among equals;
+ *   a candidate QUALIFIES iff vR >= mv and vL >= mv at the chosen s.
+ * The answer per qualifying pair is pr, pl, cr = clipR[pr], cl = clipL[pl], vR, vL, s and the entries stored at the two keys.  Pairs
+ * come back sorted by (pr, pl); a peak may qualify with several partners (a repeat), and all of them are reported.  *n_found is
+ * ALWAYS the number of qualifying pairs; when it exceeds cap the call still returns IM_OK, the arrays are unspecified and the caller
+ * asks again with a larger cap.  Once the table has dropped entries *n_found = -1, nothing is written and the call returns IM_OK: no
+ * answer, not a wrong one.
+ * im_clip_peaks_tid / im_clip_peaks answer the peaks of ONE array, side 0 (clipR) or 1 (clipL), sorted by position, with the cap
+ * contract above; apart from side their argument checks are those of im_clip_facing_tid / im_clip_facing.  im_clip_crossed_tid searches
+ * contig tid of the genome-wide arrays, im_clip_crossed the arrays of the last im_clip_build, which must be contig tid's (the table is
+ * keyed by contig and the reference is the contig's: the build form has to be told which).  Parameters outside the ranges above, a
+ * negative cap, a null n_found or a null array with cap >= 1 are IM_E_ARG; so are clip arrays or a table that are not enabled and a
+ * reference that is not set.  The candidates of a peak are walked one by one: max_len bounds them to max_len / (T + 1) + 1 per peak.
+ * Synchronous, on the context's stream. */
+int im_clip_peaks_tid(im_ctx* ctx, int32_t tid, int32_t side, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count,
+                      int32_t* n_found);
+int im_clip_peaks(im_ctx* ctx, int32_t side, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count, int32_t* n_found);
+int im_clip_crossed_tid(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift,
+                        int32_t min_verified, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right, uint32_t* v_left,
+                        int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found);
+int im_clip_crossed(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift,
+                    int32_t min_verified, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right, uint32_t* v_left,
+                    int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

@@ -238,6 +238,10 @@ def lib():
         L.im_clip_facing_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.im_clip_facing.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.im_cliptail_consensus.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_clip_peaks_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        L.im_clip_peaks.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        L.im_clip_crossed_tid.argtypes = [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p] * 9 + [C.POINTER(C.c_int32)]
+        L.im_clip_crossed.argtypes = [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p] * 9 + [C.POINTER(C.c_int32)]
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_capture_begin.argtypes = [C.c_void_p, C.c_void_p]
@@ -659,6 +663,39 @@ class Context:
         planes = np.zeros(2 * max(n, 1), dtype=np.uint32)
         self._check(lib().im_cliptail_consensus(self.h, int(tid), n, _ptr(pos), _ptr(side), int(min_cover), _ptr(entries), _ptr(ln), _ptr(planes), _ptr(agree)))
         return entries[:n], ln[:n], planes[0:2 * n:2], planes[1:2 * n:2], agree[:n]
+
+    def _clip_search(self, fn, kinds, cap, *args):
+        """the arrays of a search that counts what it finds, asked again with a larger cap when there is more than cap; None for the
+        no-answer value (n_found -1)"""
+        while True:
+            out = [np.zeros(max(cap, 1), dtype=k) for k in kinds]
+            found = C.c_int32(0)
+            self._check(fn(self.h, *[int(a) for a in args], int(cap), *[_ptr(o) for o in out], C.byref(found)))
+            if found.value < 0:
+                return None
+            if found.value <= cap:
+                return tuple(o[:found.value] for o in out)
+            cap = found.value
+
+    def clip_peaks_tid(self, tid, side, min_reads, reach, cap=65536):
+        """(pos, count) of the peaks of contig tid's clipR (side 0) or clipL (side 1) in the genome-wide arrays, sorted by position"""
+        return self._clip_search(lib().im_clip_peaks_tid, (np.int32, np.uint32), cap, tid, side, min_reads, reach)
+
+    def clip_peaks(self, side, min_reads, reach, cap=65536):
+        """the same on the arrays of the last clip_build"""
+        return self._clip_search(lib().im_clip_peaks, (np.int32, np.uint32), cap, side, min_reads, reach)
+
+    _CROSSED = (np.int32, np.int32, np.uint32, np.uint32, np.uint32, np.uint32, np.int32, np.uint32, np.uint32)
+
+    def clip_crossed_tid(self, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap=65536):
+        """(pr, pl, cr, cl, vR, vL, shift, stored right, stored left) of the crossed piles of contig tid (-U), sorted by (pr, pl): a peak
+        of clipR with a peak of clipL min_len .. max_len in front of it whose clipped bases verify on either side; None once the
+        clip-tail table has overflowed"""
+        return self._clip_search(lib().im_clip_crossed_tid, self._CROSSED, cap, tid, min_reads, reach, min_len, max_len, max_shift, min_verified)
+
+    def clip_crossed(self, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap=65536):
+        """the same on the arrays of the last clip_build, which must be contig tid's"""
+        return self._clip_search(lib().im_clip_crossed, self._CROSSED, cap, tid, min_reads, reach, min_len, max_len, max_shift, min_verified)
 
     def cluster_sr(self, cls, b1, b2, marker=2**31 - 1, tie_desc=0):
         n = len(cls)

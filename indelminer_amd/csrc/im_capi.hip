@@ -1270,6 +1270,176 @@ int im_cliptail_consensus(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* p
     return IM_OK;
 }
 
+// ---- crossed piles: the peaks of either clip array, and the pairs of them a tandem duplication leaves (-U) ----------
+
+static int peaks_args(im_ctx* ctx, const char* who, int32_t min_reads, int32_t reach, int32_t cap)
+{
+    if (min_reads < 1) { set_err(ctx, "%s: min_reads %d, must be >= 1", who, min_reads); return IM_E_ARG; }
+    if (reach < 0 || reach > 64) { set_err(ctx, "%s: reach %d, must be 0 .. 64", who, reach); return IM_E_ARG; }
+    if (cap < 0) { set_err(ctx, "%s: cap %d, must be >= 0", who, cap); return IM_E_ARG; }
+    return IM_OK;
+}
+
+// (position, count) pairs from two device arrays of n, sorted by position (a position is a peak once)
+static int sorted_peaks(im_ctx* ctx, const void* d_pos, const void* d_cnt, uint32_t n, std::vector<int32_t>& pos, std::vector<uint32_t>& cnt)
+{
+    std::vector<int32_t> p(n);
+    std::vector<uint32_t> c(n);
+    pos.resize(n); cnt.resize(n);
+    if (n == 0) return IM_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(p.data(), d_pos, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(c.data(), d_cnt, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return p[a] < p[b]; });
+    for (uint32_t i = 0; i < n; i++) { pos[i] = p[order[i]]; cnt[i] = c[order[i]]; }
+    return IM_OK;
+}
+
+// the peaks of one contig's one array: the counter and two arrays of cap in the workspace, one launch, the counter back, then what
+// was found, sorted by position here
+static int peaks_array(im_ctx* ctx, const char* who, const int32_t* arr, int64_t clen, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos,
+                       uint32_t* count, int32_t* n_found)
+{
+    int rc = peaks_args(ctx, who, min_reads, reach, cap);
+    if (rc) return rc;
+    if (!n_found || (cap > 0 && (!pos || !count))) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = up256(sizeof(int32_t) * (size_t)(cap ? cap : 1));
+    rc = ensure_ws(ctx, 256 + 2 * sb);
+    if (rc) return rc;
+    uint32_t* d_count = (uint32_t*)ctx->ws;
+    int32_t* d_pos = (int32_t*)((char*)ctx->ws + 256);
+    uint32_t* d_cnt = (uint32_t*)((char*)ctx->ws + 256 + sb);
+    uint32_t found = 0;
+    HIP_TRY(ctx, im::launch_clip_peaks(arr, clen, min_reads, reach, cap, d_pos, d_cnt, d_count, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&found, d_count, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *n_found = (int32_t)found;
+    if (found == 0 || found > (uint32_t)cap) return IM_OK;          // more than cap: the caller asks again
+    std::vector<int32_t> p;
+    std::vector<uint32_t> c;
+    rc = sorted_peaks(ctx, d_pos, d_cnt, found, p, c);
+    if (rc) return rc;
+    memcpy(pos, p.data(), sizeof(int32_t) * (size_t)found); memcpy(count, c.data(), sizeof(uint32_t) * (size_t)found);
+    return IM_OK;
+}
+
+int im_clip_peaks_tid(im_ctx* ctx, int32_t tid, int32_t side, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count, int32_t* n_found)
+{
+    if (!ctx || !ctx->all_clip_r.data || !ctx->all_clip_l.data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    if (side < 0 || side > 1) { set_err(ctx, "im_clip_peaks_tid: side %d, must be 0 (right) or 1 (left)", side); return IM_E_ARG; }
+    return peaks_array(ctx, "im_clip_peaks_tid", (side ? ctx->all_clip_l.data : ctx->all_clip_r.data) + ctx->h_asc_off[tid], ctx->h_len[tid], min_reads, reach,
+                       cap, pos, count, n_found);
+}
+
+int im_clip_peaks(im_ctx* ctx, int32_t side, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count, int32_t* n_found)
+{
+    if (!ctx) return IM_E_ARG;
+    if (ctx->clip_r.len < 0 || ctx->clip_l.len < 0) { set_err(ctx, "im_clip_build has not been called"); return IM_E_ARG; }
+    if (side < 0 || side > 1) { set_err(ctx, "im_clip_peaks: side %d, must be 0 (right) or 1 (left)", side); return IM_E_ARG; }
+    return peaks_array(ctx, "im_clip_peaks", side ? ctx->clip_l.data : ctx->clip_r.data, ctx->clip_r.len, min_reads, reach, cap, pos, count, n_found);
+}
+
+// The crossed piles of one contig.  In order: the table's counters (an overflowed table answers nothing), both peak passes into the
+// workspace, their two counters back (once more with room for all when a list did not fit), the lists down, SORTED HERE (piles are
+// few) and up again, the cross launch, its counter back, then min(found, cap) pairs down and sorted by (pr, pl).
+static int crossed_arrays(im_ctx* ctx, const char* who, const int32_t* right, const int32_t* left, int32_t tid, int32_t min_reads, int32_t reach,
+                          int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr,
+                          uint32_t* cl, uint32_t* v_right, uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found)
+{
+    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    int rc = peaks_args(ctx, who, min_reads, reach, cap);
+    if (rc) return rc;
+    if (min_len < 1) { set_err(ctx, "%s: min_len %d, must be >= 1", who, min_len); return IM_E_ARG; }
+    if (max_len < min_len) { set_err(ctx, "%s: max_len %d, must be >= min_len %d", who, max_len, min_len); return IM_E_ARG; }
+    if (max_shift < 0 || max_shift > 32) { set_err(ctx, "%s: max_shift %d, must be 0 .. 32", who, max_shift); return IM_E_ARG; }
+    if (min_verified < 1) { set_err(ctx, "%s: min_verified %d, must be >= 1", who, min_verified); return IM_E_ARG; }
+    if (!n_found || (cap > 0 && (!pr || !pl || !cr || !cl || !v_right || !v_left || !shift || !stored_right || !stored_left))) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t clen = ctx->h_len[tid];
+    unsigned long long counters[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (counters[1] > 0) { *n_found = -1; return IM_OK; }           // no answer, not a wrong one
+    const size_t ob = up256(sizeof(int32_t) * (size_t)(cap ? cap : 1));
+    uint32_t pcap = 65536, found[3] = {0, 0, 0};
+    char* base = nullptr;
+    size_t pb = 0;
+    for (;;) {
+        pb = up256(sizeof(int32_t) * (size_t)pcap);
+        rc = ensure_ws(ctx, 256 + 4 * pb + 9 * ob);
+        if (rc) return rc;
+        base = (char*)ctx->ws;
+        uint32_t* d_count = (uint32_t*)base;
+        HIP_TRY(ctx, im::launch_clip_peaks(right, clen, min_reads, reach, (int32_t)pcap, (int32_t*)(base + 256), (uint32_t*)(base + 256 + pb), d_count, ctx->stream));
+        HIP_TRY(ctx, im::launch_clip_peaks(left, clen, min_reads, reach, (int32_t)pcap, (int32_t*)(base + 256 + 2 * pb), (uint32_t*)(base + 256 + 3 * pb), d_count + 1, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(found, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (found[0] <= pcap && found[1] <= pcap) break;
+        pcap = found[0] > found[1] ? found[0] : found[1];           // a list did not fit: once more, with room for all
+    }
+    *n_found = 0;
+    if (found[0] == 0 || found[1] == 0) return IM_OK;
+    void* d_list[4];
+    for (int k = 0; k < 4; k++) d_list[k] = base + 256 + k * pb;
+    std::vector<int32_t> hp[2];
+    std::vector<uint32_t> hc[2];
+    for (int k = 0; k < 2; k++) {
+        rc = sorted_peaks(ctx, d_list[2 * k], d_list[2 * k + 1], found[k], hp[k], hc[k]);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(d_list[2 * k], hp[k].data(), sizeof(int32_t) * (size_t)found[k], hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_list[2 * k + 1], hc[k].data(), sizeof(uint32_t) * (size_t)found[k], hipMemcpyHostToDevice, ctx->stream));
+    }
+    void* d_out[9];
+    for (int k = 0; k < 9; k++) d_out[k] = base + 256 + 4 * pb + k * ob;
+    uint32_t* d_pairs = (uint32_t*)base + 2;
+    HIP_TRY(ctx, im::launch_cliptail_cross((int32_t)found[0], (const int32_t*)d_list[0], (const uint32_t*)d_list[1], (int32_t)found[1], (const int32_t*)d_list[2],
+                                           (const uint32_t*)d_list[3], tid, min_len, max_len, max_shift, min_verified, cap, ctx->ref_ascii + ctx->h_asc_off[tid],
+                                           clen, ctx->tail, (int32_t*)d_out[0], (int32_t*)d_out[1], (uint32_t*)d_out[2], (uint32_t*)d_out[3], (uint32_t*)d_out[4],
+                                           (uint32_t*)d_out[5], (int32_t*)d_out[6], (uint32_t*)d_out[7], (uint32_t*)d_out[8], d_pairs, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&found[2], d_pairs, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                // the uploads' host vectors are done with here as well
+    *n_found = (int32_t)found[2];
+    const uint32_t n = found[2] < (uint32_t)cap ? found[2] : (uint32_t)cap;
+    if (n == 0) return IM_OK;
+    std::vector<int32_t> h[9];
+    for (int k = 0; k < 9; k++) {
+        h[k].resize(n);
+        HIP_TRY(ctx, hipMemcpyAsync(h[k].data(), d_out[k], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return h[0][a] != h[0][b] ? h[0][a] < h[0][b] : h[1][a] < h[1][b]; });
+    int32_t* out[9] = {pr, pl, (int32_t*)cr, (int32_t*)cl, (int32_t*)v_right, (int32_t*)v_left, shift, (int32_t*)stored_right, (int32_t*)stored_left};
+    for (uint32_t i = 0; i < n; i++) for (int k = 0; k < 9; k++) out[k][i] = h[k][order[i]];
+    return IM_OK;
+}
+
+int im_clip_crossed_tid(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified,
+                        int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
+                        uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found)
+{
+    if (!ctx || !ctx->all_clip_r.data || !ctx->all_clip_l.data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    const int64_t at = ctx->h_asc_off[tid];
+    return crossed_arrays(ctx, "im_clip_crossed_tid", ctx->all_clip_r.data + at, ctx->all_clip_l.data + at, tid, min_reads, reach, min_len, max_len, max_shift,
+                          min_verified, cap, pr, pl, cr, cl, v_right, v_left, shift, stored_right, stored_left, n_found);
+}
+
+int im_clip_crossed(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified,
+                    int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
+                    uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found)
+{
+    if (!ctx || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    if (ctx->clip_r.len < 0 || ctx->clip_l.len < 0) { set_err(ctx, "im_clip_build has not been called"); return IM_E_ARG; }
+    if (ctx->clip_r.len != ctx->h_len[tid]) { set_err(ctx, "im_clip_crossed: the arrays of the last im_clip_build are not contig %d's", tid); return IM_E_ARG; }
+    return crossed_arrays(ctx, "im_clip_crossed", ctx->clip_r.data, ctx->clip_l.data, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap,
+                          pr, pl, cr, cl, v_right, v_left, shift, stored_right, stored_left, n_found);
+}
+
 int im_cliptail_reset(im_ctx* ctx, void* stream)
 {
     if (!ctx || !ctx->tail.slots) return IM_E_ARG;

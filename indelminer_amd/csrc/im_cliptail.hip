@@ -21,6 +21,7 @@
 //   cliptail_add       one lane per entry the host names (the record-at-a-time path)
 //   cliptail_verify    one wave per query (tid, pr, pl): see the kernel
 //   cliptail_consensus one wave per query (tid, position, side): the per-base consensus of a pile's entries (-I), on the same walk
+//   cliptail_cross     one wave per peak of clipR: the peaks of clipL the right distance in front of it, verified as above (-U)
 
 #include "im_device.hpp"
 #include "im_spanrec.hpp"
@@ -254,26 +255,51 @@ __device__ __forceinline__ uint32_t tail_walk(const TailTable& T, int32_t tid, i
     return stored;
 }
 
-// One side of a verify query.  A lane whose slot holds an entry of the key tests the shifts 0 .. S against the window: a shift of the
-// planes, two XORs, the window's validity, a mask of n bits and a popcount.  Lane s gathers v(s) from the ballots.  Returns the
-// entries stored at the key (wave-uniform); *v: this lane's v(lane).
+// The shift-compare of one batch.  A lane whose slot holds an entry of the key (has; key: n in its low bits, payload: the two planes)
+// tests the shifts 0 .. S against the window: a shift of the planes, two XORs, the window's validity, a mask of n bits and a
+// popcount.  Returns what lane s adds to v(s) from the ballots.
+__device__ __forceinline__ uint32_t tail_shifts(bool has, uint64_t key, uint64_t payload, const TailWindow& W, int32_t S, int lane)
+{
+    uint32_t mine = 0;
+    const uint32_t e_lo = (uint32_t)payload, e_hi = (uint32_t)(payload >> 32);
+    const uint32_t n = (uint32_t)key & 63u, m = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u, allowed = n >> 4;
+    for (int32_t sh = 0; sh <= S; sh++) {                           // wave-uniform
+        const uint32_t diff = (((uint32_t)(W.lo >> sh) ^ e_lo) | ((uint32_t)(W.hi >> sh) ^ e_hi) | ~(uint32_t)(W.ok >> sh)) & m;
+        const uint64_t match = __ballot(has && (uint32_t)__builtin_popcount(diff) <= allowed);
+        if (lane == sh) mine += (uint32_t)__builtin_popcountll(match);
+    }
+    return mine;
+}
+
+// One side of a verify query: the walk, and the shift-compare of every batch that holds entries of the key.  Lane s gathers v(s).
+// Returns the entries stored at the key (wave-uniform); *v: this lane's v(lane).
 __device__ __forceinline__ uint32_t tail_side(const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, const TailWindow& W,
                                               bool compare, int32_t S, int lane, uint32_t* v)
 {
     uint32_t mine = 0;
     const uint32_t stored = tail_walk(T, tid, pos, side, clen, lane, [&](bool has, uint64_t key, uint64_t s) {
         if (!compare) return;
-        const uint64_t payload = has ? T.slots[2ull * s + 1ull] : 0ull;
-        const uint32_t e_lo = (uint32_t)payload, e_hi = (uint32_t)(payload >> 32);
-        const uint32_t n = (uint32_t)key & 63u, m = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u, allowed = n >> 4;
-        for (int32_t sh = 0; sh <= S; sh++) {                       // wave-uniform
-            const uint32_t diff = (((uint32_t)(W.lo >> sh) ^ e_lo) | ((uint32_t)(W.hi >> sh) ^ e_hi) | ~(uint32_t)(W.ok >> sh)) & m;
-            const uint64_t match = __ballot(has && (uint32_t)__builtin_popcount(diff) <= allowed);
-            if (lane == sh) mine += (uint32_t)__builtin_popcountll(match);
-        }
+        mine += tail_shifts(has, key, has ? T.slots[2ull * s + 1ull] : 0ull, W, S, lane);
     });
     *v = mine;
     return stored;
+}
+
+// The chosen shift of a query: the largest vR(s) + vL(s) over s = 0 .. S, the smallest s among equals (the wave's maximum over
+// sum : ~s).  vr, vl: this lane's v(lane).  Returns whether any entry matched at any shift; *best, *br, *bl: wave-uniform.
+__device__ __forceinline__ bool tail_best_shift(uint32_t vr, uint32_t vl, int32_t S, int lane, int* best, uint32_t* br, uint32_t* bl)
+{
+    uint64_t key = ((uint64_t)(lane <= S ? vr + vl : 0u) << 32) | (0xFFFFFFFFu - (uint32_t)lane);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(key >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)key, o);
+        const uint64_t k = ((uint64_t)hi << 32) | lo;
+        key = k > key ? k : key;
+    }
+    const bool found = (key >> 32) != 0ull;
+    *best = found ? (int)(0xFFFFFFFFu - (uint32_t)key) : 0;
+    *br = (uint32_t)__shfl((int)vr, *best); *bl = (uint32_t)__shfl((int)vl, *best);
+    return found;
 }
 
 struct TailVerifyArgs {
@@ -291,8 +317,7 @@ struct TailVerifyArgs {
 };
 
 // One wave per query (pr: where right clips pile up, pl: where left clips do).  A right entry at pr continues at pl + s, a left entry
-// at pl continues backwards from pr - 1 - s: one 64-base window per side, fetched once.  The chosen shift has the largest
-// vR(s) + vL(s), the smallest s among equals (the wave's maximum over sum : ~s).
+// at pl continues backwards from pr - 1 - s: one 64-base window per side, fetched once.  The chosen shift: tail_best_shift.
 __global__ __launch_bounds__(kTailWaveBlock) void cliptail_verify_kernel(TailVerifyArgs A)
 {
     const int lane = threadIdx.x & 63;
@@ -306,19 +331,85 @@ __global__ __launch_bounds__(kTailWaveBlock) void cliptail_verify_kernel(TailVer
         uint32_t vr, vl;
         const uint32_t sr = tail_side(A.tab, A.tid, pr, 0u, A.clen, Wr, compare, A.max_shift, lane, &vr);
         const uint32_t sl = tail_side(A.tab, A.tid, pl, 1u, A.clen, Wl, compare, A.max_shift, lane, &vl);
-        uint64_t key = ((uint64_t)(lane <= A.max_shift ? vr + vl : 0u) << 32) | (0xFFFFFFFFu - (uint32_t)lane);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint32_t hi = (uint32_t)__shfl_xor((int)(key >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)key, o);
-            const uint64_t k = ((uint64_t)hi << 32) | lo;
-            key = k > key ? k : key;
-        }
-        const bool found = (key >> 32) != 0ull;
-        const int best = found ? (int)(0xFFFFFFFFu - (uint32_t)key) : 0;
-        const uint32_t br = (uint32_t)__shfl((int)vr, best), bl = (uint32_t)__shfl((int)vl, best);
+        int best;
+        uint32_t br, bl;
+        const bool found = tail_best_shift(vr, vl, A.max_shift, lane, &best, &br, &bl);
         if (lane == 0) {
             A.v_right[q] = found ? br : 0u; A.v_left[q] = found ? bl : 0u; A.shift[q] = found ? best : -1;
             A.stored_right[q] = sr; A.stored_left[q] = sl;
+        }
+    }
+}
+
+struct TailCrossArgs {
+    int32_t n_right, n_left, tid;
+    const int32_t* rpos;        // the peaks of clipR, ascending, and their counts
+    const uint32_t* rcnt;
+    const int32_t* lpos;        // the peaks of clipL, ascending, and their counts
+    const uint32_t* lcnt;
+    int32_t min_len, max_len, max_shift, min_verified, cap;
+    const uint8_t* ref;
+    int64_t clen;
+    TailTable tab;
+    int32_t* pr; int32_t* pl; uint32_t* cr; uint32_t* cl;
+    uint32_t* v_right; uint32_t* v_left; int32_t* shift; uint32_t* stored_right; uint32_t* stored_left;
+    uint32_t* n_found;
+};
+
+// the first index of the ascending list at which pos[i] >= x (n when there is none): every lane runs the same search
+__device__ __forceinline__ int32_t first_at_or_behind(const int32_t* __restrict__ pos, int32_t n, int64_t x)
+{
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)pos[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// Crossed piles (-U; include/indelminer_amd.h, seam 5, "Crossed piles"): one wave per peak pr of clipR.  Its candidates are the run of
+// the left list inside [pr - max_len, pr - min_len], found by two binary searches; a peak without one ends there.  What depends on
+// pr alone is fetched once: the window ref[pr - 1 - lane] the left entries of every partner are compared with, and the right pile's
+// entries -- when one batch of the walk holds them all (the usual pile of tens of reads) they stay in the lanes, and a candidate
+// costs no walk on this side; a pile spread over several batches is walked per candidate, as verify does.  Per candidate: the
+// window ref[pl + lane], the left pile's walk, the chosen shift.  The rare pair that qualifies takes its slot with one returning
+// atomic by lane 0; n_found counts every pair, only slots below cap are written.  Nothing here is divergent: every branch is on
+// values the whole wave shares.
+__global__ __launch_bounds__(kTailWaveBlock) void cliptail_cross_kernel(TailCrossArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int q = wave; q < A.n_right; q += nwaves) {
+        const int64_t pr = A.rpos[q];
+        const int32_t k0 = first_at_or_behind(A.lpos, A.n_left, pr - (int64_t)A.max_len);
+        const int32_t k1 = first_at_or_behind(A.lpos, A.n_left, pr - (int64_t)A.min_len + 1);
+        if (k0 >= k1) continue;
+        const TailWindow Wl = tail_window(A.ref, A.clen, pr - 1 - lane);        // what the left entries of every partner are expected to hold
+        int batches = 0;
+        bool h_has = false;
+        uint64_t h_key = 0, h_payload = 0;
+        const uint32_t sr = tail_walk(A.tab, A.tid, pr, 0u, A.clen, lane, [&](bool has, uint64_t key, uint64_t s) {
+            if (batches++ == 0) { h_has = has; h_key = key; h_payload = has ? A.tab.slots[2ull * s + 1ull] : 0ull; }
+        });
+        for (int32_t k = k0; k < k1; k++) {
+            const int64_t pl = A.lpos[k];
+            const TailWindow Wr = tail_window(A.ref, A.clen, pl + lane);        // what the right entries are expected to hold
+            uint32_t vr, vl;
+            if (batches <= 1) vr = tail_shifts(h_has, h_key, h_payload, Wr, A.max_shift, lane);
+            else (void)tail_side(A.tab, A.tid, pr, 0u, A.clen, Wr, true, A.max_shift, lane, &vr);
+            const uint32_t sl = tail_side(A.tab, A.tid, pl, 1u, A.clen, Wl, true, A.max_shift, lane, &vl);
+            int best;
+            uint32_t br, bl;
+            const bool found = tail_best_shift(vr, vl, A.max_shift, lane, &best, &br, &bl);
+            if (!found || br < (uint32_t)A.min_verified || bl < (uint32_t)A.min_verified) continue;
+            if (lane == 0) {
+                const uint32_t slot = atomicAdd(A.n_found, 1u);
+                if (slot < (uint32_t)A.cap) {
+                    A.pr[slot] = (int32_t)pr; A.pl[slot] = (int32_t)pl; A.cr[slot] = A.rcnt[q]; A.cl[slot] = A.lcnt[k];
+                    A.v_right[slot] = br; A.v_left[slot] = bl; A.shift[slot] = best; A.stored_right[slot] = sr; A.stored_left[slot] = sl;
+                }
+            }
         }
     }
 }
@@ -395,6 +486,24 @@ hipError_t launch_cliptail_consensus(int32_t nq, int32_t tid, const int32_t* pos
     int b = (nq + 3) / 4;
     if (b > 2048) b = 2048;
     hipLaunchKernelGGL(cliptail_consensus_kernel, dim3(b), dim3(kTailWaveBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_cliptail_cross(int32_t n_right, const int32_t* rpos, const uint32_t* rcnt, int32_t n_left, const int32_t* lpos, const uint32_t* lcnt,
+                                 int32_t tid, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, const uint8_t* ref,
+                                 int64_t clen, const TailTable& tab, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right,
+                                 uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, uint32_t* n_found, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(n_found, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess || n_right <= 0 || n_left <= 0) return e;
+    TailCrossArgs A;
+    A.n_right = n_right; A.n_left = n_left; A.tid = tid; A.rpos = rpos; A.rcnt = rcnt; A.lpos = lpos; A.lcnt = lcnt;
+    A.min_len = min_len; A.max_len = max_len; A.max_shift = max_shift; A.min_verified = min_verified; A.cap = cap;
+    A.ref = ref; A.clen = clen; A.tab = tab; A.pr = pr; A.pl = pl; A.cr = cr; A.cl = cl; A.v_right = v_right; A.v_left = v_left;
+    A.shift = shift; A.stored_right = stored_right; A.stored_left = stored_left; A.n_found = n_found;
+    int b = (n_right + 3) / 4;
+    if (b > 2048) b = 2048;
+    hipLaunchKernelGGL(cliptail_cross_kernel, dim3(b), dim3(kTailWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 

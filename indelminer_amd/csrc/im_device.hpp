@@ -130,6 +130,11 @@ hipError_t launch_clip_argmax(int32_t nq, const uint8_t* side, const int32_t* be
 // counts them all, the first cap that take a slot are written, in no particular order
 hipError_t launch_clip_facing(const int32_t* right, const int32_t* left, int64_t clen, int32_t min_reads, int32_t max_overlap, int32_t cap,
                               int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* n_found, hipStream_t stream);
+// the peaks of ONE array (clen + 1 entries, 16-byte aligned): positions p with arr[p] >= min_reads, arr[p] > every count of
+// [p - reach, p) and >= every count of (p, p + reach]; *n_found (cleared here) counts them all, the first cap that take a slot are
+// written, in no particular order
+hipError_t launch_clip_peaks(const int32_t* arr, int64_t clen, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count,
+                             uint32_t* n_found, hipStream_t stream);
 // im_cliptail.hip: the clipped bases of clipped reads in a keyed table (-V).  slots: 2^log2_slots pairs (key, payload) of 64-bit
 // words, zeros = empty; counters[0]: inserts asked for, counters[1]: those dropped because half of the slots were taken
 struct TailTable {
@@ -152,6 +157,13 @@ hipError_t launch_cliptail_verify(int32_t nq, int32_t tid, const int32_t* pr, co
 // consensus as two planes (planes[2 q], planes[2 q + 1]) and the entries that agree with it; a position outside [0, clen] answers zeros
 hipError_t launch_cliptail_consensus(int32_t nq, int32_t tid, const int32_t* pos, const uint8_t* side, int32_t min_cover, int64_t clen,
                                      const TailTable& tab, uint32_t* entries, uint32_t* len, uint32_t* planes, uint32_t* agree, hipStream_t stream);
+// crossed piles: the pairs (pr of the right peaks, pl of the left peaks; both lists ascending) with min_len <= pr - pl <= max_len whose
+// entries verify (at least min_verified on either side at the chosen shift); *n_found (cleared here) counts them all, the first cap
+// that take a slot are written, in no particular order
+hipError_t launch_cliptail_cross(int32_t n_right, const int32_t* rpos, const uint32_t* rcnt, int32_t n_left, const int32_t* lpos, const uint32_t* lcnt,
+                                 int32_t tid, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, const uint8_t* ref,
+                                 int64_t clen, const TailTable& tab, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right,
+                                 uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, uint32_t* n_found, hipStream_t stream);
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);

@@ -36,6 +36,7 @@
 //   clip_scatter   one lane per delivered record: the core and two CIGAR words at either end decide, a right clip walks its CIGAR
 //   clip_argmax    one wave per query: the largest count over [beg, end] inclusive and the smallest position that holds it
 //   clip_facing    one lane per four positions of one contig: the facing piles of the two arrays (-I), the one chip-wide search
+//   clip_peaks     the same stream over one array: its peaks (-U), once per side
 // The record-at-a-time path names the events itself: clip_build adds one per (position, side).
 
 #include "im_device.hpp"
@@ -352,15 +353,23 @@ struct FacingArgs {
     uint32_t* n_found;
 };
 
+// whether p (arr[p] = v) is a PEAK of arr within T: more than every count of [p - T, p), no fewer than every count of (p, p + T],
+// the windows stopping at the contig's own entries.  The leftmost of equal peaks wins.  Facing piles test R with it, the peaks
+// pass (-U) either array.
+__device__ __forceinline__ bool peak_at(const int32_t* __restrict__ arr, int64_t clen, int64_t T, int64_t p, int32_t v)
+{
+    const int64_t lo = p - T < 0 ? 0 : p - T, hi = p + T > clen ? clen : p + T;
+    bool peak = true;
+    for (int64_t x = lo; x < p; x++) peak = peak && arr[x] < v;
+    for (int64_t x = p + 1; x <= hi; x++) peak = peak && arr[x] <= v;
+    return peak;
+}
+
 // whether p (R[p] = v >= min_reads) is a peak of R and has a partner in L: the windows stop at the contig's own entries
 __device__ __forceinline__ bool facing_at(const FacingArgs& A, int64_t p, int32_t v, int32_t* pl, int32_t* cl)
 {
-    const int64_t T = A.max_overlap;
-    const int64_t lo = p - T < 0 ? 0 : p - T, hi = p + T > A.clen ? A.clen : p + T;
-    bool peak = true;
-    for (int64_t x = lo; x < p; x++) peak = peak && A.right[x] < v;             // the leftmost of equal peaks wins
-    for (int64_t x = p + 1; x <= hi; x++) peak = peak && A.right[x] <= v;
-    if (!peak) return false;
+    if (!peak_at(A.right, A.clen, A.max_overlap, p, v)) return false;
+    const int64_t lo = p - A.max_overlap < 0 ? 0 : p - A.max_overlap;
     int32_t best = -1;
     int64_t at = p;
     for (int64_t x = p; x >= lo; x--) {                                          // downwards: the largest x among equal counts stays
@@ -371,27 +380,28 @@ __device__ __forceinline__ bool facing_at(const FacingArgs& A, int64_t p, int32_
     return best >= A.min_reads;
 }
 
-// One streaming pass over R.  A lane takes four consecutive positions per 16-byte load, kFacingSweeps loads up front; nearly every
-// lane is done when all of them are below min_reads.  The rare lane that is not reads its windows from memory (L2: the workgroup has
-// just streamed R there), L is read only there.  Piles take their slots with one returning atomic per wave: the rank comes from a
-// ballot, the first lane of the ballot adds.  n_found counts every pile; only slots below cap are written.
-__global__ __launch_bounds__(kFacingBlock) void clip_facing_kernel(FacingArgs A)
+// One streaming pass over one count array (clen + 1 entries), the skeleton of the facing search and of the peaks pass.  A lane
+// takes four consecutive positions per 16-byte load, kFacingSweeps loads up front; nearly every lane is done when all of them are
+// below m.  The rare lane that is not asks hit(p, c), which reads its windows from memory (L2: the workgroup has just streamed the
+// array there).  Hits take their slots with one returning atomic per wave: the rank comes from a ballot, the first lane of the
+// ballot adds.  n_found counts every hit; put(slot, p, c) is called only for slots below cap.
+template <class Hit, class Put>
+__device__ __forceinline__ void clip_stream(const int32_t* __restrict__ arr, int64_t clen, int32_t m, int32_t cap, uint32_t* n_found, Hit hit, Put put)
 {
     const int lane = threadIdx.x & 63;
-    const int64_t n = A.clen + 1;
+    const int64_t n = clen + 1;
     const int64_t tile = (int64_t)blockIdx.x * kFacingTile;
     int4 v[kFacingSweeps];
 #pragma unroll
     for (int s = 0; s < kFacingSweeps; s++) {
         const int64_t p0 = tile + (int64_t)s * kFacingSweep + (int64_t)threadIdx.x * kFacingPer;
-        if (p0 + kFacingPer <= n) v[s] = *reinterpret_cast<const int4*>(A.right + p0);
+        if (p0 + kFacingPer <= n) v[s] = *reinterpret_cast<const int4*>(arr + p0);
         else {
             // the contig's last entries: one by one, nothing is read behind entry clen
-            v[s].x = p0 < n ? A.right[p0] : 0; v[s].y = p0 + 1 < n ? A.right[p0 + 1] : 0;
-            v[s].z = p0 + 2 < n ? A.right[p0 + 2] : 0; v[s].w = 0;
+            v[s].x = p0 < n ? arr[p0] : 0; v[s].y = p0 + 1 < n ? arr[p0 + 1] : 0;
+            v[s].z = p0 + 2 < n ? arr[p0 + 2] : 0; v[s].w = 0;
         }
     }
-    const int32_t m = A.min_reads;
 #pragma unroll
     for (int s = 0; s < kFacingSweeps; s++) {
         const bool any = v[s].x >= m || v[s].y >= m || v[s].z >= m || v[s].w >= m;
@@ -401,18 +411,44 @@ __global__ __launch_bounds__(kFacingBlock) void clip_facing_kernel(FacingArgs A)
         for (int j = 0; j < kFacingPer; j++) {
             const int32_t c = j == 0 ? v[s].x : j == 1 ? v[s].y : j == 2 ? v[s].z : v[s].w;
             const int64_t p = p0 + j;
-            int32_t pl = 0, cl = 0;
-            const bool pile = c >= m && p < n && facing_at(A, p, c, &pl, &cl);
+            const bool pile = c >= m && p < n && hit(p, c);
             const uint64_t piles = __ballot(pile);
             if (!piles) continue;
             const int first = (int)__builtin_ctzll(piles);
             uint32_t base = 0;
-            if (lane == first) base = atomicAdd(A.n_found, (uint32_t)__builtin_popcountll(piles));
+            if (lane == first) base = atomicAdd(n_found, (uint32_t)__builtin_popcountll(piles));
             base = (uint32_t)__shfl((int)base, first);
             const uint32_t slot = base + (uint32_t)__builtin_popcountll(piles & ((1ull << lane) - 1ull));
-            if (pile && slot < (uint32_t)A.cap) { A.pr[slot] = (int32_t)p; A.pl[slot] = pl; A.cr[slot] = (uint32_t)c; A.cl[slot] = (uint32_t)cl; }
+            if (pile && slot < (uint32_t)cap) put(slot, p, c);
         }
     }
+}
+
+// The facing search: the stream runs over R, L is read only by the lane that holds a peak.
+__global__ __launch_bounds__(kFacingBlock) void clip_facing_kernel(FacingArgs A)
+{
+    int32_t pl = 0, cl = 0;
+    clip_stream(A.right, A.clen, A.min_reads, A.cap, A.n_found,
+                [&](int64_t p, int32_t c) { return facing_at(A, p, c, &pl, &cl); },
+                [&](uint32_t slot, int64_t p, int32_t c) { A.pr[slot] = (int32_t)p; A.pl[slot] = pl; A.cr[slot] = (uint32_t)c; A.cl[slot] = (uint32_t)cl; });
+}
+
+struct PeaksArgs {
+    const int32_t* arr;
+    int64_t clen;
+    int32_t min_reads, reach, cap;
+    int32_t* pos;
+    uint32_t* count;
+    uint32_t* n_found;
+};
+
+// The peaks of ONE array (-U; include/indelminer_amd.h, seam 5, "Crossed piles"): the same stream, the peak test alone.  It runs once
+// per side.
+__global__ __launch_bounds__(kFacingBlock) void clip_peaks_kernel(PeaksArgs A)
+{
+    clip_stream(A.arr, A.clen, A.min_reads, A.cap, A.n_found,
+                [&](int64_t p, int32_t c) { return peak_at(A.arr, A.clen, A.reach, p, c); },
+                [&](uint32_t slot, int64_t p, int32_t c) { A.pos[slot] = (int32_t)p; A.count[slot] = (uint32_t)c; });
 }
 
 // One wave per query: the minimum of span[p] over [beg, end] INCLUSIVE, clipped to [0, clen]; an interval that is empty after
@@ -501,6 +537,18 @@ hipError_t launch_clip_facing(const int32_t* right, const int32_t* left, int64_t
     A.pr = pr; A.pl = pl; A.cr = cr; A.cl = cl; A.n_found = n_found;
     const int64_t blocks = (clen + 1 + kFacingTile - 1) / kFacingTile;          // clen <= 0x7fffff00: at most 2^19 workgroups
     hipLaunchKernelGGL(clip_facing_kernel, dim3((unsigned)blocks), dim3(kFacingBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_clip_peaks(const int32_t* arr, int64_t clen, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count,
+                             uint32_t* n_found, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(n_found, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    PeaksArgs A;
+    A.arr = arr; A.clen = clen; A.min_reads = min_reads; A.reach = reach; A.cap = cap; A.pos = pos; A.count = count; A.n_found = n_found;
+    const int64_t blocks = (clen + 1 + kFacingTile - 1) / kFacingTile;
+    hipLaunchKernelGGL(clip_peaks_kernel, dim3((unsigned)blocks), dim3(kFacingBlock), 0, stream, A);
     return hipGetLastError();
 }
 

@@ -960,17 +960,19 @@ static void print_gt_ad_gq(const char* more_keys, int64_t ref_count, int64_t alt
     genotype_of(ref_count, alt_count, &best, &gq);
     printf("\tGT:AD:GQ%s\t%s:%lld,%lld:%d", more_keys, best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", (long long)ref_count, (long long)alt_count, gq);
 }
-/* -D: the values of DM and DFC.  DFC = the median inside over the mean of the flanks present, in thousandths, rounded, in integers */
-static void print_depth_evidence(const variant_t* v)
+/* -D: the values of DM and DFC behind `lead` and `between`.  DFC = the median inside over the mean of the flanks present, in
+ * thousandths, rounded, in integers.  dm: inside, left flank, right flank.  The genotype columns and -U's records share it. */
+static void fprint_depth_values(FILE* f, const uint32_t dm[3], const char* lead, const char* between)
 {
-    const uint32_t in = v->dm_cached[0], l = v->dm_cached[1], r = v->dm_cached[2];
+    const uint32_t in = dm[0], l = dm[1], r = dm[2];
     uint64_t num = 0, den = 0;
     if (l != DEPTH_EV_NONE && r != DEPTH_EV_NONE) { num = 2000ull * in; den = (uint64_t)l + r; }
     else if (l != DEPTH_EV_NONE || r != DEPTH_EV_NONE) { num = 1000ull * in; den = l != DEPTH_EV_NONE ? l : r; }
-    printf(":");
-    for (int k = 0; k < 3; k++) { if (v->dm_cached[k] == DEPTH_EV_NONE) printf("%s.", k ? "," : ""); else printf("%s%u", k ? "," : "", v->dm_cached[k]); }
-    if (den == 0 || in == DEPTH_EV_NONE) printf(":."); else printf(":%llu", (unsigned long long)((num + den / 2) / den));
+    fprintf(f, "%s", lead);
+    for (int k = 0; k < 3; k++) { if (dm[k] == DEPTH_EV_NONE) fprintf(f, "%s.", k ? "," : ""); else fprintf(f, "%s%u", k ? "," : "", dm[k]); }
+    if (den == 0 || in == DEPTH_EV_NONE) fprintf(f, "%s.", between); else fprintf(f, "%s%llu", between, (unsigned long long)((num + den / 2) / den));
 }
+static void print_depth_evidence(const variant_t* v) { fprint_depth_values(OUT, v->dm_cached, ":", ":"); }
 /* -C: the values of CB and CS.  CB in the coordinates of POS and END: a right clip at array position p is the coordinate p, a
  * left clip at p is p + 1; a side without clipped reads prints . and 0 */
 static void print_clip_evidence(const variant_t* v)

@@ -510,6 +510,90 @@ static void ins_contig(driver* d, int32_t tid)
     phase_time("large-insertion evidence (device)");
 }
 
+/* -U: FILE, opened when the first contig is about to be searched (as -I's: the record-at-a-time child writes it, not its parent) */
+static FILE* g_dup_out = NULL;
+static void dup_open(void)
+{
+    g_dup_out = fopen(g_dup_file, "w");
+    if (!g_dup_out) fatalf("cannot write %s", g_dup_file);
+    FILE* f = g_dup_out;
+    fprintf(f, "##fileformat=VCFv4.1\n");
+    fprintf(f, "##ALT=<ID=DUP:TANDEM,Description=\"Tandem duplication: reads clipped at its end continue at its start\">\n");
+    fprintf(f, "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n");
+    fprintf(f, "##INFO=<ID=END,Number=1,Type=Integer,Description=\"Last duplicated base: where the reads from the left stop aligning (POS + 1: the first, where the reads from the right start)\">\n");
+    fprintf(f, "##INFO=<ID=SVLEN,Number=1,Type=Integer,Description=\"END - POS: bases duplicated\">\n");
+    fprintf(f, "##INFO=<ID=HOMLEN,Number=1,Type=Integer,Description=\"Bases by which the clipped reads continue behind the other breakpoint (micro-homology the aligner extended into)\">\n");
+    fprintf(f, "##INFO=<ID=CR,Number=2,Type=Integer,Description=\"Clipped reads that stop aligning at END, clipped reads that start aligning at POS\">\n");
+    fprintf(f, "##INFO=<ID=CN,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases were kept, either side\">\n");
+    fprintf(f, "##INFO=<ID=CV,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases are the reference at the other breakpoint\">\n");
+    if (g_depth_evidence) {
+        fprintf(f, "##INFO=<ID=DM,Number=3,Type=Integer,Description=\"Median depth over the duplicated bases POS+1..END, over the %d bases in front of them and over the %d bases behind them\">\n", DEPTH_EV_FLANK, DEPTH_EV_FLANK);
+        fprintf(f, "##INFO=<ID=DFC,Number=1,Type=Integer,Description=\"Depth fold change in thousandths: the first DM value over the mean of the other two\">\n");
+    }
+    fprintf(f, "##tandemDuplication=\"a record per pair of positions END and POS, %d <= END - POS <= %d, where END is a position at which at least %d reads of mapping "
+               "quality >= -q stop aligning with a soft clip of at least %d bases, more than at any of the %d positions in front and no fewer than at any of the %d "
+               "behind, and POS is such a position of the reads that start aligning with such a clip, when for one shift s in 0 .. %d at least %d of the reads at END "
+               "continue with the reference from POS + s on and at least %d of the reads at POS continue backwards with the reference from END - 1 - s on, in up to 32 "
+               "clipped bases per read with at most 1 difference in 16 (HOMLEN: the s with the most such reads, the smallest among equals; CV: those reads); "
+               "the file has no records once the clip-tail table has overflowed (stderr says so); POS 0 is skipped\"\n",
+            DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, DUP_EV_MIN_READS, CLIP_EV_MIN_CLIP, DUP_EV_REACH, DUP_EV_REACH, CLIPTAIL_MAX_SHIFT, DUP_EV_MIN_VERIFIED, DUP_EV_MIN_VERIFIED);
+    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
+}
+
+/* -U: one contig's crossed piles into FILE, where ins_contig is called and for the same reason: the clip arrays and the table hold
+ * every record of the contig.  With -D the contig's scanned depth array is resident as well -- the genome-wide array is scanned
+ * contig by contig as the walk leaves each (im_depth_scan) and never reset, the record-at-a-time path has built this contig's. */
+static void dup_contig(driver* d, int32_t tid)
+{
+    if (!g_dup_out) dup_open();
+    gpu_wait(d);
+    int32_t cap = 4096, found = 0;
+    int32_t* pos = NULL; uint32_t* cnt = NULL;
+    pthread_mutex_lock(&g_query_mu);
+    for (;;) {
+        /* pr pl shift | cr cl vR vL stored right, stored left */
+        pos = xrealloc(pos, sizeof(int32_t) * 3 * (size_t)cap); cnt = xrealloc(cnt, sizeof(uint32_t) * 6 * (size_t)cap);
+        int32_t* pr = pos; int32_t* pl = pos + cap; int32_t* sh = pos + 2 * cap;
+        const int rc = d->pipe_mode
+            ? im_clip_crossed_tid(d->gpu, tid, DUP_EV_MIN_READS, DUP_EV_REACH, DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT, DUP_EV_MIN_VERIFIED, cap,
+                                  pr, pl, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, sh, cnt + 4 * cap, cnt + 5 * cap, &found)
+            : im_clip_crossed(d->gpu, tid, DUP_EV_MIN_READS, DUP_EV_REACH, DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT, DUP_EV_MIN_VERIFIED, cap,
+                              pr, pl, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, sh, cnt + 4 * cap, cnt + 5 * cap, &found);
+        if (rc != IM_OK) fatalf("im_clip_crossed: %s", im_last_error(d->gpu));
+        if (found <= cap) break;
+        cap = found;                /* more pairs than asked for: once more, with room for all */
+    }
+    /* found < 0: the table has overflowed, the header alone */
+    uint32_t* med = NULL;
+    if (found > 0 && g_depth_evidence) {
+        /* three queries per pair: the duplicated bases [pl, pr) and DEPTH_EV_FLANK bases on either side (the device clips to the contig) */
+        int32_t* beg = xmalloc(sizeof(int32_t) * 6 * (size_t)found); int32_t* end = beg + 3 * (size_t)found;
+        med = xmalloc(sizeof(uint32_t) * 3 * (size_t)found);
+        for (int32_t k = 0; k < found; k++) {
+            const int32_t pr = pos[k], pl = pos[cap + k];
+            beg[3 * k] = pl; end[3 * k] = pr;
+            beg[3 * k + 1] = pl - DEPTH_EV_FLANK; end[3 * k + 1] = pl;
+            beg[3 * k + 2] = pr; end[3 * k + 2] = (int32_t)((int64_t)pr + DEPTH_EV_FLANK > INT32_MAX ? INT32_MAX : pr + DEPTH_EV_FLANK);
+        }
+        const int qrc = d->pipe_mode ? im_depth_median_tid(d->gpu, tid, 3 * found, beg, end, med) : im_depth_median(d->gpu, 3 * found, beg, end, med);
+        if (qrc != IM_OK) fatalf("im_depth_median: %s", im_last_error(d->gpu));
+        free(beg);
+    }
+    pthread_mutex_unlock(&g_query_mu);
+    const char* seq = d->sequences[tid];
+    for (int32_t k = 0; k < found; k++) {
+        const int32_t pr = pos[k], pl = pos[cap + k];
+        if (pl == 0) continue;      /* nothing in front to anchor on */
+        fprintf(g_dup_out, "%s\t%d\t.\t%c\t<DUP:TANDEM>\t.\t.\tSVTYPE=DUP;END=%d;SVLEN=%d;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u", d->hdr->target_name[tid], pl,
+                toupper((unsigned char)seq[pl - 1]), pr, pr - pl, pos[2 * cap + k], cnt[k], cnt[cap + k], cnt[4 * cap + k], cnt[5 * cap + k],
+                cnt[2 * cap + k], cnt[3 * cap + k]);
+        if (med) fprint_depth_values(g_dup_out, med + 3 * k, ";DM=", ";DFC=");
+        fprintf(g_dup_out, "\n");
+    }
+    free(med); free(pos); free(cnt);
+    phase_time("tandem-duplication evidence (device)");
+}
+
 static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_reader* r)
 {
     d->n_items = 0; d->n_flushes = 0;

@@ -186,6 +186,26 @@ extern int im_cliptail_consensus(im_ctx*, int32_t, int32_t, const int32_t*, cons
 #define INS_EV_MAX_OVERLAP 30      /* bases the left-clip pile may stand in front of the right-clip pile: below DEPTH_EV_MIN_LEN, so the two
                                     * piles of a deletion that gets CB:CS can never face each other */
 #define INS_EV_MIN_COVER 2         /* entries that must hold a base for the consensus to have one */
+/* -U FILE, with -G -C -V: tandem duplications -- a peak of the right clips with a peak of the left clips DUP_EV_MIN_LEN .. DUP_EV_MAX_LEN
+ * bases IN FRONT of it (crossed piles: the device's peaks of either clip array), kept when at least DUP_EV_MIN_VERIFIED clipped reads of
+ * either pile continue at the other breakpoint (the device's verify, over the clip-tail table, enumerating its own candidates).  A small
+ * VCF of its own, written to FILE; with -D every record carries the median depth inside and beside it.  stdout, stderr and -I's FILE
+ * stay as they are.  Not an option of the reference; referenced weakly. */
+static const char* g_dup_file = NULL;
+extern int im_clip_peaks_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, uint32_t*, int32_t*) __attribute__((weak));
+extern int im_clip_peaks(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t*, uint32_t*, int32_t*) __attribute__((weak));
+extern int im_clip_crossed_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*,
+                               uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
+extern int im_clip_crossed(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*,
+                           uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
+#define CROSSED_ON (g_dup_file != NULL)            /* the run ends (a contig ends) with the search for crossed piles */
+#define CROSSED_API_PRESENT (im_clip_peaks_tid && im_clip_peaks && im_clip_crossed_tid && im_clip_crossed)
+#define DUP_EV_MIN_READS 3         /* clipped reads of the smaller pile */
+#define DUP_EV_REACH 30            /* the reach of a peak: the peaks -I sees */
+#define DUP_EV_MIN_LEN 50          /* the shortest duplication: DEPTH_EV_MIN_LEN, and above INS_EV_MAX_OVERLAP, so no pair of piles is ever both a
+                                    * facing pile and a crossed pile */
+#define DUP_EV_MAX_LEN 100000      /* the longest */
+#define DUP_EV_MIN_VERIFIED 2      /* clipped reads of either pile that continue at the other breakpoint */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that
