@@ -352,7 +352,16 @@ typedef struct im_triage_params {
  * counters[3] = records with an IM_REC_ERR_* class.  batch holds the device arrays (capacity cap_cand
  * reads / cap_bases bytes); batch.n is ignored.  The evidence slots of a candidate receive its
  * CIGAR-derived evidence (check_variants); im_dev_realign later REPLACES them when the realignment
- * finds evidence (src/indelminer.c:494-512) -- launch it with keep_slots = 1 (im_dev_realign_keep). */
+ * finds evidence (src/indelminer.c:494-512) -- launch it with keep_slots = 1 (im_dev_realign_keep).
+ *
+ * Overflow.  A candidate with index ci and base offset bo (the padded lengths of the candidates in front of it) is
+ * ACCEPTED iff  ci < cap_cand  and  bo + padded4(l_seq) + 16 <= cap_bases  (16 bytes of slack behind the last read for the
+ * realign kernels' whole-piece loads).  bo only grows, so the accepted candidates are a prefix of the batch.  Every candidate
+ * that is refused adds 1 to counters[4] (zero after a call with restart = 1; else zero it with the other counters); nothing
+ * of it is written: no bases, no scalars, no slots, no cand_rec -- except that one refused for its bytes below cap_cand gets
+ * read_len 0 and base_off 0.  counters[0] and counters[1] still count the refused candidates, so min(counters[0], cap_cand)
+ * bounds the entries that hold anything.  A caller that sees counters[4] != 0 must drop the batch (or repeat it with larger
+ * buffers): the accepted prefix is right, the rest is missing. */
 typedef struct im_dev_cands {
     im_dev_batch batch;
     int32_t*     cand_rec;      /* cap_cand: record index (rec_base + i) of every candidate      */

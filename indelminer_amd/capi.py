@@ -801,6 +801,17 @@ class Pipeline:
         c(L.im_dev_memset(self.ctx.h, self.d_cut.ptr, 0xFF, 8 * self.n_flushes, st))
         c(L.im_dev_triage(self.ctx.h, C.byref(self.tp), C.byref(self.recs), C.byref(self.cands), self.d_ts.ptr, self.ts_bytes, st))
 
+    def triage_append(self, n, rec_base, restart=False, defer=False, stream=None, clear=False):
+        """the triage of the n records now in the record buffer the way the product issues it chunk after chunk: no memset in front,
+        the candidates go behind those the running counters hold (restart: the call opens a new batch whatever the counters hold),
+        cand_rec counts from rec_base.  clear: the call also clears the flush marks of its new candidates (asynchronous)"""
+        st = self.ctx.stream if stream is None else stream
+        tp = TriageParams(self.tp.qthreshold, self.tp.ethreshold_vcfcheck, self.tp.maxpedelsize, self.tp.want_depth,
+                          1 if defer else 0, 1 if restart else 0)
+        recs = DevRecords(int(n), self.d_raw.ptr, self.d_off.ptr, int(rec_base))
+        self.ctx._check(lib().im_dev_triage(self.ctx.h, C.byref(tp), C.byref(recs), C.byref(self.cands_clear if clear else self.cands),
+                                            self.d_ts.ptr, self.ts_bytes, st))
+
     def fetch_counts(self):
         """the one host synchronisation of a batch: candidates found (sizes the realign grid)"""
         self.sync()                         # the context's stream does not synchronise with the copy below by itself

@@ -531,8 +531,18 @@ __global__ __launch_bounds__(kTriBlock) void triage_emit_kernel(TriageArgs A)
     const uint2 base = s_base;
     const uint32_t ci = base.x + oc + below;
     const uint32_t bo = base.y + ob + ib - bytes;
-    if (!(ci < (uint32_t)A.out.cap_cand && (uint64_t)bo + bytes + 16u <= (uint64_t)A.out.cap_bases)) { atomicAdd(&A.out.counters[4], 1); return; }
     const im_dev_batch& B = A.out.batch;
+    if (!(ci < (uint32_t)A.out.cap_cand && (uint64_t)bo + bytes + 16u <= (uint64_t)A.out.cap_bases)) {
+        atomicAdd(&A.out.counters[4], 1);
+        // The decode kernel walks every candidate below min(counters[0], cap_cand): one whose bases do not fit gets the
+        // length 0 there, so that nothing is read or written for it (its words would hold what an earlier batch left)
+        if (ci < (uint32_t)A.out.cap_cand) {
+            const_cast<int64_t*>(B.base_off)[ci] = 0;
+            const_cast<int32_t*>(B.read_len)[ci] = 0;
+            A.seq_at[ci - (uint32_t)A.chunk_base[0]] = 0u;
+        }
+        return;
+    }
     const_cast<int64_t*>(B.base_off)[ci] = (int64_t)bo;
     const_cast<int32_t*>(B.read_len)[ci] = r.l_seq;
     const_cast<int32_t*>(B.tid)[ci] = r.mtid;

@@ -98,9 +98,9 @@ class Triage(C.Structure):
                 ("n_ev", C.c_int32), ("ev_cls", C.c_int32 * MAX_EV), ("ev_b1", C.c_int32 * MAX_EV), ("ev_b2", C.c_int32 * MAX_EV), ("want", C.c_int32)]
 
 
-def triage_records(raw, rec_off, rg_names, rg_range_max, qthreshold=10, eth_vcf=10, maxpedelsize=1000000):
+def triage_records(raw, rec_off, rg_names, rg_range_max, qthreshold=10, eth_vcf=10, maxpedelsize=1000000, defer=False):
     """imo_triage_record over every record of a device-layout buffer.  Returns a list of
-    (Triage, bases bytes or None)."""
+    (Triage, bases bytes or None).  defer: no read-group look-up (n_rg = -1, im_triage_params.defer_ranges)."""
     import numpy as np
     L = lib()
     L.imo_triage_record.restype = None
@@ -116,7 +116,7 @@ def triage_records(raw, rec_off, rg_names, rg_range_max, qthreshold=10, eth_vcf=
         t = Triage()
         ln = int(rec_off[i + 1]) - int(rec_off[i])
         buf = C.create_string_buffer(4096)
-        L.imo_triage_record(base + int(rec_off[i]), ln, len(rg_names), names, rm.ctypes.data, qthreshold, eth_vcf, maxpedelsize,
+        L.imo_triage_record(base + int(rec_off[i]), ln, -1 if defer else len(rg_names), names, rm.ctypes.data, qthreshold, eth_vcf, maxpedelsize,
                             C.byref(t), buf)
         out.append((t, buf.raw[:t.l_seq] if t.cls in (2, 3) else None))
     return out
