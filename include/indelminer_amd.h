@@ -707,6 +707,43 @@ int im_clip_crossed(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, 
                     int32_t min_verified, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right, uint32_t* v_left,
                     int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found);
 
+/* Inverted piles, the breakpoints of inversions (-N).  Every rule above pairs a right-clip pile with a left-clip pile and compares the
+ * clipped bases with the reference as it stands.  An inversion of the bases [a, b) -- the sample reads ref[0, a) + revcomp(ref[a, b)) +
+ * ref[b, ...) -- leaves neither.  At its LEFT junction the reads that keep most of their bases in front of a stop aligning at a with a
+ * right clip, and clipped base i is comp(ref[b - 1 - i]); the reads that keep most of their bases inside the inverted segment align on
+ * the other strand, stop at b with a right clip, and clipped base i is comp(ref[a - 1 - i]): two RIGHT-clip piles, each holding the
+ * complement of the reference running backwards from the other.  The RIGHT junction leaves two LEFT-clip piles at a and b that hold, in
+ * junction order, comp(ref[b + i]) and comp(ref[a + i]).  Micro-homology the aligner extended into, h1 bases at one pile and h2 at the
+ * other, moves the piles to a + h1 and b + h2 (right clips; a - h1 and b - h2 for left clips), and both piles then verify at the ONE
+ * shift s = h1 + h2.  In the table's 2-bit planes (A 0, C 1, G 2, T 3) the complement is both planes inverted.
+ * With m = min_reads >= 1, T = reach (0 .. 64), dmin = min_len >= 1, dmax = max_len >= dmin, S = max_shift (0 .. 32) and
+ * mv = min_verified >= 1, on a contig of length clen:
+ *   PEAK is the definition of "Crossed piles", unchanged;
+ *   a CANDIDATE of side sigma (0 = clipR, 1 = clipL) is two peaks x < y of the SAME array with dmin <= y - x <= dmax;
+ *   an entry of n bases matches iff at most n >> 4 of its bases differ from what is expected; a position outside [0, clen) is a
+ *   mismatch, and so is a reference byte other than A, C, G, T.  Base i at shift s is expected to be
+ *     sigma = 0, the entry at x:  comp(ref[y - 1 - s - i])        sigma = 0, the entry at y:  comp(ref[x - 1 - s - i])
+ *     sigma = 1, the entry at x:  comp(ref[y + s + i])            sigma = 1, the entry at y:  comp(ref[x + s + i])
+ *   v1(s) = the matching entries at (tid, x, sigma), v2(s) = the matching entries at (tid, y, sigma);
+ *   the chosen s has the largest v1(s) + v2(s) over 0 .. S, the smallest s among equals;
+ *   a candidate QUALIFIES iff v1 >= mv and v2 >= mv at the chosen s.
+ * The answer per qualifying pair is side, x, y, c1 = A[x], c2 = A[y], v1, v2, s and the entries stored at the two keys.  Pairs come
+ * back sorted by (x, y, side); a pair x < y is reported once, a peak may be the y of one pair and the x of another, and a peak may
+ * qualify with several partners.  *n_found is ALWAYS the number of qualifying pairs, under the cap contract of im_clip_crossed_tid:
+ * when it exceeds cap the call still returns IM_OK, the arrays are unspecified and the caller asks again with a larger cap.  Once the
+ * table has dropped entries *n_found = -1, nothing is written and the call returns IM_OK: no answer, not a wrong one.
+ * im_clip_inverted_tid searches contig tid of the genome-wide arrays, im_clip_inverted the arrays of the last im_clip_build, which must
+ * be contig tid's.  Argument errors are those of the crossed entries: parameters outside the ranges above, a negative cap, a null
+ * n_found or a null array with cap >= 1 are IM_E_ARG; so are clip arrays or a table that are not enabled and a reference that is not
+ * set.  The two junctions of one inversion are two pairs, one of either side; nothing joins them here.  Synchronous, on the
+ * context's stream. */
+int im_clip_inverted_tid(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift,
+                         int32_t min_verified, int32_t cap, uint8_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1,
+                         uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2, int32_t* n_found);
+int im_clip_inverted(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift,
+                     int32_t min_verified, int32_t cap, uint8_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1,
+                     uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2, int32_t* n_found);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

@@ -242,6 +242,8 @@ def lib():
         L.im_clip_peaks.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.im_clip_crossed_tid.argtypes = [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p] * 9 + [C.POINTER(C.c_int32)]
         L.im_clip_crossed.argtypes = [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p] * 9 + [C.POINTER(C.c_int32)]
+        L.im_clip_inverted_tid.argtypes = [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p] * 10 + [C.POINTER(C.c_int32)]
+        L.im_clip_inverted.argtypes = [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p] * 10 + [C.POINTER(C.c_int32)]
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_capture_begin.argtypes = [C.c_void_p, C.c_void_p]
@@ -696,6 +698,18 @@ class Context:
     def clip_crossed(self, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap=65536):
         """the same on the arrays of the last clip_build, which must be contig tid's"""
         return self._clip_search(lib().im_clip_crossed, self._CROSSED, cap, tid, min_reads, reach, min_len, max_len, max_shift, min_verified)
+
+    _INVERTED = (np.uint8, np.int32, np.int32, np.uint32, np.uint32, np.uint32, np.uint32, np.int32, np.uint32, np.uint32)
+
+    def clip_inverted_tid(self, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap=65536):
+        """(side, x, y, c1, c2, v1, v2, shift, stored at x, stored at y) of the inverted piles of contig tid (-N), sorted by (x, y, side):
+        two peaks of ONE clip array (side 0 clipR, 1 clipL) min_len .. max_len apart whose clipped bases are the complement of the
+        reference running backwards from the other peak; None once the clip-tail table has overflowed"""
+        return self._clip_search(lib().im_clip_inverted_tid, self._INVERTED, cap, tid, min_reads, reach, min_len, max_len, max_shift, min_verified)
+
+    def clip_inverted(self, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap=65536):
+        """the same on the arrays of the last clip_build, which must be contig tid's"""
+        return self._clip_search(lib().im_clip_inverted, self._INVERTED, cap, tid, min_reads, reach, min_len, max_len, max_shift, min_verified)
 
     def cluster_sr(self, cls, b1, b2, marker=2**31 - 1, tie_desc=0):
         n = len(cls)

@@ -1342,12 +1342,9 @@ int im_clip_peaks(im_ctx* ctx, int32_t side, int32_t min_reads, int32_t reach, i
     return peaks_array(ctx, "im_clip_peaks", side ? ctx->clip_l.data : ctx->clip_r.data, ctx->clip_r.len, min_reads, reach, cap, pos, count, n_found);
 }
 
-// The crossed piles of one contig.  In order: the table's counters (an overflowed table answers nothing), both peak passes into the
-// workspace, their two counters back (once more with room for all when a list did not fit), the lists down, SORTED HERE (piles are
-// few) and up again, the cross launch, its counter back, then min(found, cap) pairs down and sorted by (pr, pl).
-static int crossed_arrays(im_ctx* ctx, const char* who, const int32_t* right, const int32_t* left, int32_t tid, int32_t min_reads, int32_t reach,
-                          int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr,
-                          uint32_t* cl, uint32_t* v_right, uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found)
+// what the searches for pairs of piles (crossed, inverted) check alike, behind the table and the reference
+static int pile_pair_args(im_ctx* ctx, const char* who, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift,
+                          int32_t min_verified, int32_t cap)
 {
     if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
     if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
@@ -1357,6 +1354,55 @@ static int crossed_arrays(im_ctx* ctx, const char* who, const int32_t* right, co
     if (max_len < min_len) { set_err(ctx, "%s: max_len %d, must be >= min_len %d", who, max_len, min_len); return IM_E_ARG; }
     if (max_shift < 0 || max_shift > 32) { set_err(ctx, "%s: max_shift %d, must be 0 .. 32", who, max_shift); return IM_E_ARG; }
     if (min_verified < 1) { set_err(ctx, "%s: min_verified %d, must be >= 1", who, min_verified); return IM_E_ARG; }
+    return IM_OK;
+}
+
+// The peaks of both arrays of one contig in the workspace: the counter block (256 bytes: the two peak counters, then the caller's
+// pair counter), four lists of pb bytes (right positions, right counts, left positions, left counts), then out_bytes for the caller.
+// Both peak passes, their two counters back, once more with room for all when a list did not fit.  found: the peaks per side.
+struct PeakLists { char* base; size_t pb; uint32_t found[2]; };
+
+static int peak_lists(im_ctx* ctx, const int32_t* right, const int32_t* left, int64_t clen, int32_t min_reads, int32_t reach, size_t out_bytes, PeakLists* P)
+{
+    uint32_t pcap = 65536;
+    for (;;) {
+        P->pb = up256(sizeof(int32_t) * (size_t)pcap);
+        int rc = ensure_ws(ctx, 256 + 4 * P->pb + out_bytes);
+        if (rc) return rc;
+        P->base = (char*)ctx->ws;
+        uint32_t* d_count = (uint32_t*)P->base;
+        HIP_TRY(ctx, im::launch_clip_peaks(right, clen, min_reads, reach, (int32_t)pcap, (int32_t*)(P->base + 256), (uint32_t*)(P->base + 256 + P->pb), d_count, ctx->stream));
+        HIP_TRY(ctx, im::launch_clip_peaks(left, clen, min_reads, reach, (int32_t)pcap, (int32_t*)(P->base + 256 + 2 * P->pb), (uint32_t*)(P->base + 256 + 3 * P->pb), d_count + 1, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(P->found, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (P->found[0] <= pcap && P->found[1] <= pcap) return IM_OK;
+        pcap = P->found[0] > P->found[1] ? P->found[0] : P->found[1];       // a list did not fit: once more, with room for all
+    }
+}
+
+// the two lists down, SORTED HERE (piles are few) and up again; hp, hc: the host copies, which the uploads read until the next wait
+static int sort_peak_lists(im_ctx* ctx, const PeakLists& P, void* d_list[4], std::vector<int32_t> hp[2], std::vector<uint32_t> hc[2])
+{
+    for (int k = 0; k < 4; k++) d_list[k] = P.base + 256 + k * P.pb;
+    for (int k = 0; k < 2; k++) {
+        int rc = sorted_peaks(ctx, d_list[2 * k], d_list[2 * k + 1], P.found[k], hp[k], hc[k]);
+        if (rc) return rc;
+        if (P.found[k] == 0) continue;
+        HIP_TRY(ctx, hipMemcpyAsync(d_list[2 * k], hp[k].data(), sizeof(int32_t) * (size_t)P.found[k], hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_list[2 * k + 1], hc[k].data(), sizeof(uint32_t) * (size_t)P.found[k], hipMemcpyHostToDevice, ctx->stream));
+    }
+    return IM_OK;
+}
+
+// The crossed piles of one contig.  In order: the table's counters (an overflowed table answers nothing), both peak passes into the
+// workspace, their two counters back (peak_lists), the lists down, sorted and up again (sort_peak_lists), the cross launch, its
+// counter back, then min(found, cap) pairs down and sorted by (pr, pl).
+static int crossed_arrays(im_ctx* ctx, const char* who, const int32_t* right, const int32_t* left, int32_t tid, int32_t min_reads, int32_t reach,
+                          int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr,
+                          uint32_t* cl, uint32_t* v_right, uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found)
+{
+    int rc = pile_pair_args(ctx, who, min_reads, reach, min_len, max_len, max_shift, min_verified, cap);
+    if (rc) return rc;
     if (!n_found || (cap > 0 && (!pr || !pl || !cr || !cl || !v_right || !v_left || !shift || !stored_right || !stored_left))) return IM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t clen = ctx->h_len[tid];
@@ -1365,34 +1411,19 @@ static int crossed_arrays(im_ctx* ctx, const char* who, const int32_t* right, co
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (counters[1] > 0) { *n_found = -1; return IM_OK; }           // no answer, not a wrong one
     const size_t ob = up256(sizeof(int32_t) * (size_t)(cap ? cap : 1));
-    uint32_t pcap = 65536, found[3] = {0, 0, 0};
-    char* base = nullptr;
-    size_t pb = 0;
-    for (;;) {
-        pb = up256(sizeof(int32_t) * (size_t)pcap);
-        rc = ensure_ws(ctx, 256 + 4 * pb + 9 * ob);
-        if (rc) return rc;
-        base = (char*)ctx->ws;
-        uint32_t* d_count = (uint32_t*)base;
-        HIP_TRY(ctx, im::launch_clip_peaks(right, clen, min_reads, reach, (int32_t)pcap, (int32_t*)(base + 256), (uint32_t*)(base + 256 + pb), d_count, ctx->stream));
-        HIP_TRY(ctx, im::launch_clip_peaks(left, clen, min_reads, reach, (int32_t)pcap, (int32_t*)(base + 256 + 2 * pb), (uint32_t*)(base + 256 + 3 * pb), d_count + 1, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(found, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (found[0] <= pcap && found[1] <= pcap) break;
-        pcap = found[0] > found[1] ? found[0] : found[1];           // a list did not fit: once more, with room for all
-    }
+    PeakLists P;
+    rc = peak_lists(ctx, right, left, clen, min_reads, reach, 9 * ob, &P);
+    if (rc) return rc;
+    char* base = P.base;
+    const size_t pb = P.pb;
+    uint32_t found[3] = {P.found[0], P.found[1], 0};
     *n_found = 0;
     if (found[0] == 0 || found[1] == 0) return IM_OK;
     void* d_list[4];
-    for (int k = 0; k < 4; k++) d_list[k] = base + 256 + k * pb;
     std::vector<int32_t> hp[2];
     std::vector<uint32_t> hc[2];
-    for (int k = 0; k < 2; k++) {
-        rc = sorted_peaks(ctx, d_list[2 * k], d_list[2 * k + 1], found[k], hp[k], hc[k]);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(d_list[2 * k], hp[k].data(), sizeof(int32_t) * (size_t)found[k], hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_list[2 * k + 1], hc[k].data(), sizeof(uint32_t) * (size_t)found[k], hipMemcpyHostToDevice, ctx->stream));
-    }
+    rc = sort_peak_lists(ctx, P, d_list, hp, hc);
+    if (rc) return rc;
     void* d_out[9];
     for (int k = 0; k < 9; k++) d_out[k] = base + 256 + 4 * pb + k * ob;
     uint32_t* d_pairs = (uint32_t*)base + 2;
@@ -1438,6 +1469,93 @@ int im_clip_crossed(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, 
     if (ctx->clip_r.len != ctx->h_len[tid]) { set_err(ctx, "im_clip_crossed: the arrays of the last im_clip_build are not contig %d's", tid); return IM_E_ARG; }
     return crossed_arrays(ctx, "im_clip_crossed", ctx->clip_r.data, ctx->clip_l.data, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap,
                           pr, pl, cr, cl, v_right, v_left, shift, stored_right, stored_left, n_found);
+}
+
+// ---- inverted piles: the pairs of peaks of ONE clip array an inversion's junction leaves (-N) ----------
+
+// The inverted piles of one contig, crossed_arrays step for step: the table's counters (an overflowed table answers nothing), both
+// peak passes into the workspace, their two counters back (peak_lists), the lists down, sorted and up again (sort_peak_lists), the
+// ONE launch over both lists, its counter back, then min(found, cap) pairs down and sorted by (x, y, side).
+static int inverted_arrays(im_ctx* ctx, const char* who, const int32_t* right, const int32_t* left, int32_t tid, int32_t min_reads, int32_t reach,
+                           int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, uint8_t* side, int32_t* p1, int32_t* p2,
+                           uint32_t* c1, uint32_t* c2, uint32_t* v1, uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2, int32_t* n_found)
+{
+    int rc = pile_pair_args(ctx, who, min_reads, reach, min_len, max_len, max_shift, min_verified, cap);
+    if (rc) return rc;
+    if (!n_found || (cap > 0 && (!side || !p1 || !p2 || !c1 || !c2 || !v1 || !v2 || !shift || !stored1 || !stored2))) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t clen = ctx->h_len[tid];
+    unsigned long long counters[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (counters[1] > 0) { *n_found = -1; return IM_OK; }           // no answer, not a wrong one
+    const size_t ob = up256(sizeof(int32_t) * (size_t)(cap ? cap : 1));
+    PeakLists P;
+    rc = peak_lists(ctx, right, left, clen, min_reads, reach, 10 * ob, &P);
+    if (rc) return rc;
+    char* base = P.base;
+    const size_t pb = P.pb;
+    uint32_t found[3] = {P.found[0], P.found[1], 0};
+    *n_found = 0;
+    if (found[0] < 2 && found[1] < 2) return IM_OK;                 // a pair takes two peaks of one list
+    void* d_list[4];
+    std::vector<int32_t> hp[2];
+    std::vector<uint32_t> hc[2];
+    rc = sort_peak_lists(ctx, P, d_list, hp, hc);
+    if (rc) return rc;
+    void* d_out[10];
+    for (int k = 0; k < 10; k++) d_out[k] = base + 256 + 4 * pb + k * ob;
+    uint32_t* d_pairs = (uint32_t*)base + 2;
+    HIP_TRY(ctx, im::launch_cliptail_inverted((int32_t)found[0], (const int32_t*)d_list[0], (const uint32_t*)d_list[1], (int32_t)found[1], (const int32_t*)d_list[2],
+                                              (const uint32_t*)d_list[3], tid, min_len, max_len, max_shift, min_verified, cap, ctx->ref_ascii + ctx->h_asc_off[tid],
+                                              clen, ctx->tail, (uint32_t*)d_out[0], (int32_t*)d_out[1], (int32_t*)d_out[2], (uint32_t*)d_out[3], (uint32_t*)d_out[4],
+                                              (uint32_t*)d_out[5], (uint32_t*)d_out[6], (int32_t*)d_out[7], (uint32_t*)d_out[8], (uint32_t*)d_out[9], d_pairs,
+                                              ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&found[2], d_pairs, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                // the uploads' host vectors are done with here as well
+    *n_found = (int32_t)found[2];
+    const uint32_t n = found[2] < (uint32_t)cap ? found[2] : (uint32_t)cap;
+    if (n == 0) return IM_OK;
+    std::vector<int32_t> h[10];
+    for (int k = 0; k < 10; k++) {
+        h[k].resize(n);
+        HIP_TRY(ctx, hipMemcpyAsync(h[k].data(), d_out[k], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        if (h[1][a] != h[1][b]) return h[1][a] < h[1][b];
+        if (h[2][a] != h[2][b]) return h[2][a] < h[2][b];
+        return h[0][a] < h[0][b];
+    });
+    int32_t* out[9] = {p1, p2, (int32_t*)c1, (int32_t*)c2, (int32_t*)v1, (int32_t*)v2, shift, (int32_t*)stored1, (int32_t*)stored2};
+    for (uint32_t i = 0; i < n; i++) {
+        side[i] = (uint8_t)h[0][order[i]];
+        for (int k = 0; k < 9; k++) out[k][i] = h[k + 1][order[i]];
+    }
+    return IM_OK;
+}
+
+int im_clip_inverted_tid(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified,
+                         int32_t cap, uint8_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1, uint32_t* v2, int32_t* shift,
+                         uint32_t* stored1, uint32_t* stored2, int32_t* n_found)
+{
+    if (!ctx || !ctx->all_clip_r.data || !ctx->all_clip_l.data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    const int64_t at = ctx->h_asc_off[tid];
+    return inverted_arrays(ctx, "im_clip_inverted_tid", ctx->all_clip_r.data + at, ctx->all_clip_l.data + at, tid, min_reads, reach, min_len, max_len, max_shift,
+                           min_verified, cap, side, p1, p2, c1, c2, v1, v2, shift, stored1, stored2, n_found);
+}
+
+int im_clip_inverted(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified,
+                     int32_t cap, uint8_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1, uint32_t* v2, int32_t* shift,
+                     uint32_t* stored1, uint32_t* stored2, int32_t* n_found)
+{
+    if (!ctx || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    if (ctx->clip_r.len < 0 || ctx->clip_l.len < 0) { set_err(ctx, "im_clip_build has not been called"); return IM_E_ARG; }
+    if (ctx->clip_r.len != ctx->h_len[tid]) { set_err(ctx, "im_clip_inverted: the arrays of the last im_clip_build are not contig %d's", tid); return IM_E_ARG; }
+    return inverted_arrays(ctx, "im_clip_inverted", ctx->clip_r.data, ctx->clip_l.data, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap,
+                           side, p1, p2, c1, c2, v1, v2, shift, stored1, stored2, n_found);
 }
 
 int im_cliptail_reset(im_ctx* ctx, void* stream)

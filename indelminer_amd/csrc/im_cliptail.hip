@@ -22,6 +22,8 @@
 //   cliptail_verify    one wave per query (tid, pr, pl): see the kernel
 //   cliptail_consensus one wave per query (tid, position, side): the per-base consensus of a pile's entries (-I), on the same walk
 //   cliptail_cross     one wave per peak of clipR: the peaks of clipL the right distance in front of it, verified as above (-U)
+//   cliptail_inverted  one wave per peak of either array: the peaks of the SAME array the right distance behind it, verified against
+//                      the reference's reverse complement (-N)
 
 #include "im_device.hpp"
 #include "im_spanrec.hpp"
@@ -302,6 +304,36 @@ __device__ __forceinline__ bool tail_best_shift(uint32_t vr, uint32_t vl, int32_
     return found;
 }
 
+// The window of the other strand: the complement of A 0, C 1, G 2, T 3 is both planes inverted; what is no base stays no base.
+__device__ __forceinline__ TailWindow tail_complement(TailWindow W)
+{
+    W.lo = ~W.lo; W.hi = ~W.hi;
+    return W;
+}
+
+// A pile fetched once for many comparisons: when one batch of the walk shows all holders (the usual pile of tens of reads) its
+// entries stay in the lanes, and a comparison costs no walk; a pile spread over several batches is walked per comparison.
+struct TailHeld { int batches; bool has; uint64_t key, payload; uint32_t stored; };
+
+__device__ __forceinline__ TailHeld tail_hold(const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, int lane)
+{
+    TailHeld H; H.batches = 0; H.has = false; H.key = 0; H.payload = 0;
+    H.stored = tail_walk(T, tid, pos, side, clen, lane, [&](bool has, uint64_t key, uint64_t s) {
+        if (H.batches++ == 0) { H.has = has; H.key = key; H.payload = has ? T.slots[2ull * s + 1ull] : 0ull; }
+    });
+    return H;
+}
+
+// this lane's v(lane) of the held pile against the window W
+__device__ __forceinline__ uint32_t tail_held_shifts(const TailHeld& H, const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen,
+                                                     const TailWindow& W, int32_t S, int lane)
+{
+    if (H.batches <= 1) return tail_shifts(H.has, H.key, H.payload, W, S, lane);
+    uint32_t v;
+    (void)tail_side(T, tid, pos, side, clen, W, true, S, lane, &v);
+    return v;
+}
+
 struct TailVerifyArgs {
     int32_t nq, tid, max_shift;
     const int32_t* pr;
@@ -370,8 +402,7 @@ __device__ __forceinline__ int32_t first_at_or_behind(const int32_t* __restrict_
 // Crossed piles (-U; include/indelminer_amd.h, seam 5, "Crossed piles"): one wave per peak pr of clipR.  Its candidates are the run of
 // the left list inside [pr - max_len, pr - min_len], found by two binary searches; a peak without one ends there.  What depends on
 // pr alone is fetched once: the window ref[pr - 1 - lane] the left entries of every partner are compared with, and the right pile's
-// entries -- when one batch of the walk holds them all (the usual pile of tens of reads) they stay in the lanes, and a candidate
-// costs no walk on this side; a pile spread over several batches is walked per candidate, as verify does.  Per candidate: the
+// entries (tail_hold: in the lanes when one batch of the walk holds them all, walked per candidate otherwise).  Per candidate: the
 // window ref[pl + lane], the left pile's walk, the chosen shift.  The rare pair that qualifies takes its slot with one returning
 // atomic by lane 0; n_found counts every pair, only slots below cap are written.  Nothing here is divergent: every branch is on
 // values the whole wave shares.
@@ -386,18 +417,13 @@ __global__ __launch_bounds__(kTailWaveBlock) void cliptail_cross_kernel(TailCros
         const int32_t k1 = first_at_or_behind(A.lpos, A.n_left, pr - (int64_t)A.min_len + 1);
         if (k0 >= k1) continue;
         const TailWindow Wl = tail_window(A.ref, A.clen, pr - 1 - lane);        // what the left entries of every partner are expected to hold
-        int batches = 0;
-        bool h_has = false;
-        uint64_t h_key = 0, h_payload = 0;
-        const uint32_t sr = tail_walk(A.tab, A.tid, pr, 0u, A.clen, lane, [&](bool has, uint64_t key, uint64_t s) {
-            if (batches++ == 0) { h_has = has; h_key = key; h_payload = has ? A.tab.slots[2ull * s + 1ull] : 0ull; }
-        });
+        const TailHeld H = tail_hold(A.tab, A.tid, pr, 0u, A.clen, lane);
+        const uint32_t sr = H.stored;
         for (int32_t k = k0; k < k1; k++) {
             const int64_t pl = A.lpos[k];
             const TailWindow Wr = tail_window(A.ref, A.clen, pl + lane);        // what the right entries are expected to hold
-            uint32_t vr, vl;
-            if (batches <= 1) vr = tail_shifts(h_has, h_key, h_payload, Wr, A.max_shift, lane);
-            else (void)tail_side(A.tab, A.tid, pr, 0u, A.clen, Wr, true, A.max_shift, lane, &vr);
+            uint32_t vl;
+            const uint32_t vr = tail_held_shifts(H, A.tab, A.tid, pr, 0u, A.clen, Wr, A.max_shift, lane);
             const uint32_t sl = tail_side(A.tab, A.tid, pl, 1u, A.clen, Wl, true, A.max_shift, lane, &vl);
             int best;
             uint32_t br, bl;
@@ -408,6 +434,71 @@ __global__ __launch_bounds__(kTailWaveBlock) void cliptail_cross_kernel(TailCros
                 if (slot < (uint32_t)A.cap) {
                     A.pr[slot] = (int32_t)pr; A.pl[slot] = (int32_t)pl; A.cr[slot] = A.rcnt[q]; A.cl[slot] = A.lcnt[k];
                     A.v_right[slot] = br; A.v_left[slot] = bl; A.shift[slot] = best; A.stored_right[slot] = sr; A.stored_left[slot] = sl;
+                }
+            }
+        }
+    }
+}
+
+struct TailInvertedArgs {
+    int32_t n_right, n_left, tid;
+    const int32_t* rpos;        // the peaks of clipR, ascending, and their counts
+    const uint32_t* rcnt;
+    const int32_t* lpos;        // the peaks of clipL, ascending, and their counts
+    const uint32_t* lcnt;
+    int32_t min_len, max_len, max_shift, min_verified, cap;
+    const uint8_t* ref;
+    int64_t clen;
+    TailTable tab;
+    uint32_t* side; int32_t* p1; int32_t* p2; uint32_t* c1; uint32_t* c2;
+    uint32_t* v1; uint32_t* v2; int32_t* shift; uint32_t* stored1; uint32_t* stored2;
+    uint32_t* n_found;
+};
+
+// Inverted piles (-N; include/indelminer_amd.h, seam 5, "Inverted piles"): one wave per peak x of EITHER list, the waves below n_right
+// the right peaks, the others the left ones.  Its candidates are the run of the SAME list inside [x + min_len, x + max_len], found by
+// two binary searches; a peak without one ends there.  Entries are compared with the other strand, and backwards from the OTHER
+// peak: what depends on x alone is fetched once -- the complemented window at x (ref[x - 1 - lane] for right peaks, ref[x + lane]
+// for left ones) the entries of every partner are compared with, and the pile at x (tail_hold).  Per candidate: the complemented
+// window at y and v1(.) of the held pile; ONLY when some shift has v1 >= min_verified -- a candidate that has none cannot qualify --
+// the walk of the pile at y for v2(.), the chosen shift, the qualification.  A chance pair of peaks so costs one 64-byte load and one
+// shift loop.  The rare pair that qualifies takes its slot with one returning atomic by lane 0; n_found counts every pair, only slots
+// below cap are written.  Every branch is on values the whole wave shares.
+__global__ __launch_bounds__(kTailWaveBlock) void cliptail_inverted_kernel(TailInvertedArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    const int n_all = A.n_right + A.n_left;
+    for (int q = wave; q < n_all; q += nwaves) {
+        const bool left = q >= A.n_right;
+        const uint32_t side = left ? 1u : 0u;
+        const int32_t* __restrict__ pos = left ? A.lpos : A.rpos;
+        const uint32_t* __restrict__ cnt = left ? A.lcnt : A.rcnt;
+        const int32_t n = left ? A.n_left : A.n_right, at = left ? q - A.n_right : q;
+        const int64_t x = pos[at];
+        const int32_t k0 = first_at_or_behind(pos, n, x + (int64_t)A.min_len);
+        const int32_t k1 = first_at_or_behind(pos, n, x + (int64_t)A.max_len + 1);
+        if (k0 >= k1) continue;
+        // what the entries of every partner are expected to hold: the other strand, backwards from x
+        const TailWindow Wx = tail_complement(tail_window(A.ref, A.clen, left ? x + lane : x - 1 - lane));
+        const TailHeld H = tail_hold(A.tab, A.tid, x, side, A.clen, lane);
+        for (int32_t k = k0; k < k1; k++) {
+            const int64_t y = pos[k];
+            const TailWindow Wy = tail_complement(tail_window(A.ref, A.clen, left ? y + lane : y - 1 - lane));
+            const uint32_t v1 = tail_held_shifts(H, A.tab, A.tid, x, side, A.clen, Wy, A.max_shift, lane);
+            if (!__ballot(lane <= A.max_shift && v1 >= (uint32_t)A.min_verified)) continue;     // the first cut: no trip to the table
+            uint32_t v2;
+            const uint32_t s2 = tail_side(A.tab, A.tid, y, side, A.clen, Wx, true, A.max_shift, lane, &v2);
+            int best;
+            uint32_t b1, b2;
+            const bool found = tail_best_shift(v1, v2, A.max_shift, lane, &best, &b1, &b2);
+            if (!found || b1 < (uint32_t)A.min_verified || b2 < (uint32_t)A.min_verified) continue;
+            if (lane == 0) {
+                const uint32_t slot = atomicAdd(A.n_found, 1u);
+                if (slot < (uint32_t)A.cap) {
+                    A.side[slot] = side; A.p1[slot] = (int32_t)x; A.p2[slot] = (int32_t)y; A.c1[slot] = cnt[at]; A.c2[slot] = cnt[k];
+                    A.v1[slot] = b1; A.v2[slot] = b2; A.shift[slot] = best; A.stored1[slot] = H.stored; A.stored2[slot] = s2;
                 }
             }
         }
@@ -504,6 +595,26 @@ hipError_t launch_cliptail_cross(int32_t n_right, const int32_t* rpos, const uin
     int b = (n_right + 3) / 4;
     if (b > 2048) b = 2048;
     hipLaunchKernelGGL(cliptail_cross_kernel, dim3(b), dim3(kTailWaveBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_cliptail_inverted(int32_t n_right, const int32_t* rpos, const uint32_t* rcnt, int32_t n_left, const int32_t* lpos, const uint32_t* lcnt,
+                                    int32_t tid, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, const uint8_t* ref,
+                                    int64_t clen, const TailTable& tab, uint32_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1,
+                                    uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2, uint32_t* n_found, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(n_found, 0, sizeof(uint32_t), stream);
+    if (n_right < 0) n_right = 0;
+    if (n_left < 0) n_left = 0;
+    if (e != hipSuccess || n_right + n_left == 0) return e;
+    TailInvertedArgs A;
+    A.n_right = n_right; A.n_left = n_left; A.tid = tid; A.rpos = rpos; A.rcnt = rcnt; A.lpos = lpos; A.lcnt = lcnt;
+    A.min_len = min_len; A.max_len = max_len; A.max_shift = max_shift; A.min_verified = min_verified; A.cap = cap;
+    A.ref = ref; A.clen = clen; A.tab = tab; A.side = side; A.p1 = p1; A.p2 = p2; A.c1 = c1; A.c2 = c2; A.v1 = v1; A.v2 = v2;
+    A.shift = shift; A.stored1 = stored1; A.stored2 = stored2; A.n_found = n_found;
+    int64_t b = ((int64_t)n_right + n_left + 3) / 4;
+    if (b > 2048) b = 2048;
+    hipLaunchKernelGGL(cliptail_inverted_kernel, dim3((unsigned)b), dim3(kTailWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 

@@ -164,6 +164,14 @@ hipError_t launch_cliptail_cross(int32_t n_right, const int32_t* rpos, const uin
                                  int32_t tid, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, const uint8_t* ref,
                                  int64_t clen, const TailTable& tab, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right,
                                  uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, uint32_t* n_found, hipStream_t stream);
+// inverted piles: the pairs x < y of ONE list (side 0: the right peaks, 1: the left peaks; both lists ascending) with
+// min_len <= y - x <= max_len whose entries verify against the reference's reverse complement (at least min_verified at either peak
+// at the chosen shift); one launch for both lists, none when both are empty; *n_found (cleared here) counts them all, the first cap
+// that take a slot are written, in no particular order
+hipError_t launch_cliptail_inverted(int32_t n_right, const int32_t* rpos, const uint32_t* rcnt, int32_t n_left, const int32_t* lpos, const uint32_t* lcnt,
+                                    int32_t tid, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, const uint8_t* ref,
+                                    int64_t clen, const TailTable& tab, uint32_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1,
+                                    uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2, uint32_t* n_found, hipStream_t stream);
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);

@@ -48,6 +48,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    (clipped reads from either side facing each other, and what they agree on)\n");
     fprintf(file, "\t-U, with -G -C -V: write tandem duplications to this file, a VCF of its own\n");
     fprintf(file, "\t    (clipped reads at its end that continue at its start; with -D their depth)\n");
+    fprintf(file, "\t-N, with -G -C -V: write inversion breakpoints to this file, a VCF of its own\n");
+    fprintf(file, "\t    (two piles of reads clipped on the same side that continue on the other strand at each other)\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -90,7 +92,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -122,6 +124,7 @@ int main(int argc, char** argv)
         case 'V': g_clip_verify = 1; break;                         /* not an option of the reference */
         case 'I': g_ins_file = optarg; break;                       /* not an option of the reference */
         case 'U': g_dup_file = optarg; break;                       /* not an option of the reference */
+        case 'N': g_inv_file = optarg; break;                       /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -210,11 +213,18 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: tandem-duplication evidence (-U) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -N: behind -I's and -U's refusals, and independent of both */
+    if (g_inv_file) {
+        if (!g_clip_verify) { fprintf(stderr, "indelminer: -N needs -V\n"); return EXIT_FAILURE; }
+        if (!INVERTED_API_PRESENT) {
+            fprintf(stderr, "indelminer: inversion evidence (-N) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = 0; g_ins_file = g_dup_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
+        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = 0; g_ins_file = g_dup_file = g_inv_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {
@@ -356,6 +366,7 @@ int main(int argc, char** argv)
         else run_contig(&d, i, chromstart, chromstop, r);
         if (FACING_ON) ins_contig(&d, i);            /* -I, record-at-a-time: behind the contig's flushes, on the arrays of its im_clip_build */
         if (CROSSED_ON) dup_contig(&d, i);           /* -U: the same place, the same arrays */
+        if (INVERTED_ON) inv_contig(&d, i);          /* -N: the same place, the same arrays */
     }
 
     gpu_wait(&d);
@@ -373,6 +384,13 @@ int main(int argc, char** argv)
         if (!g_dup_out) dup_open();                 /* no contig at all: the header alone */
         if (fclose(g_dup_out) != 0) fatalf("cannot write %s", g_dup_file);
         g_dup_out = NULL;
+    }
+    if (INVERTED_ON) {
+        /* -N: as -I and -U, once on the pipelined path */
+        for (int32_t i = 0; i < d.hdr->n_targets && use_pipeline; i++) inv_contig(&d, i);
+        if (!g_inv_out) inv_open();                 /* no contig at all: the header alone */
+        if (fclose(g_inv_out) != 0) fatalf("cannot write %s", g_inv_file);
+        g_inv_out = NULL;
     }
     if (CLIPTAIL_ON) {
         /* -V: a table that overflowed has answered nothing since; said once, here */

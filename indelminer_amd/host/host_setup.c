@@ -594,6 +594,70 @@ static void dup_contig(driver* d, int32_t tid)
     phase_time("tandem-duplication evidence (device)");
 }
 
+/* -N: FILE, opened when the first contig is about to be searched (as -I's and -U's: the record-at-a-time child writes it, not its parent) */
+static FILE* g_inv_out = NULL;
+static void inv_open(void)
+{
+    g_inv_out = fopen(g_inv_file, "w");
+    if (!g_inv_out) fatalf("cannot write %s", g_inv_file);
+    FILE* f = g_inv_out;
+    fprintf(f, "##fileformat=VCFv4.1\n");
+    fprintf(f, "##ALT=<ID=INV,Description=\"Inversion breakpoint: reads clipped on one side at POS and at END continue on the other strand at each other\">\n");
+    fprintf(f, "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n");
+    fprintf(f, "##INFO=<ID=END,Number=1,Type=Integer,Description=\"The second pile of clipped reads (POS: the first)\">\n");
+    fprintf(f, "##INFO=<ID=SVLEN,Number=1,Type=Integer,Description=\"END - POS: bases inverted\">\n");
+    fprintf(f, "##INFO=<ID=CT,Number=1,Type=String,Description=\"Junction: 3to3, both piles of reads that stop aligning with a clip (the left junction), or 5to5, both of reads that start aligning with one (the right junction)\">\n");
+    fprintf(f, "##INFO=<ID=HOMLEN,Number=1,Type=Integer,Description=\"Bases by which the clipped reads continue behind the other breakpoint (micro-homology the aligner extended into, both piles together)\">\n");
+    fprintf(f, "##INFO=<ID=CR,Number=2,Type=Integer,Description=\"Clipped reads at POS, clipped reads at END\">\n");
+    fprintf(f, "##INFO=<ID=CN,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases were kept, either pile\">\n");
+    fprintf(f, "##INFO=<ID=CV,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases are the reverse complement of the reference at the other pile\">\n");
+    fprintf(f, "##inversion=\"a record per pair of positions POS < END, %d <= END - POS <= %d, at both of which at least %d reads of mapping quality >= -q stop aligning "
+               "(CT=3to3) or at both of which such reads start aligning (CT=5to5) with a soft clip of at least %d bases, more than at any of the %d positions in front "
+               "and no fewer than at any of the %d behind, when for one shift s in 0 .. %d at least %d of the reads at POS and at least %d of the reads at END "
+               "continue with the complement of the reference running away from the other position, backwards from its base - 1 - s (3to3) or forwards from its "
+               "base + s (5to5), in up to 32 clipped bases per read with at most 1 difference in 16 (HOMLEN: the s with the most such reads, the smallest among "
+               "equals; CV: those reads); the two junctions of an inversion are two records; the file has no records once the clip-tail table has overflowed "
+               "(stderr says so); POS 0 is skipped\"\n",
+            INV_EV_MIN_LEN, INV_EV_MAX_LEN, INV_EV_MIN_READS, CLIP_EV_MIN_CLIP, INV_EV_REACH, INV_EV_REACH, CLIPTAIL_MAX_SHIFT, INV_EV_MIN_VERIFIED, INV_EV_MIN_VERIFIED);
+    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
+}
+
+/* -N: one contig's inverted piles into FILE, where dup_contig is called and for the same reason.  No depth fields with -D: an inversion
+ * changes no depth. */
+static void inv_contig(driver* d, int32_t tid)
+{
+    if (!g_inv_out) inv_open();
+    gpu_wait(d);
+    int32_t cap = 4096, found = 0;
+    int32_t* pos = NULL; uint32_t* cnt = NULL; uint8_t* side = NULL;
+    pthread_mutex_lock(&g_query_mu);
+    for (;;) {
+        /* x y shift | c1 c2 v1 v2 stored at x, stored at y | side */
+        pos = xrealloc(pos, sizeof(int32_t) * 3 * (size_t)cap); cnt = xrealloc(cnt, sizeof(uint32_t) * 6 * (size_t)cap); side = xrealloc(side, (size_t)cap);
+        int32_t* x = pos; int32_t* y = pos + cap; int32_t* sh = pos + 2 * cap;
+        const int rc = d->pipe_mode
+            ? im_clip_inverted_tid(d->gpu, tid, INV_EV_MIN_READS, INV_EV_REACH, INV_EV_MIN_LEN, INV_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT, INV_EV_MIN_VERIFIED, cap,
+                                   side, x, y, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, sh, cnt + 4 * cap, cnt + 5 * cap, &found)
+            : im_clip_inverted(d->gpu, tid, INV_EV_MIN_READS, INV_EV_REACH, INV_EV_MIN_LEN, INV_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT, INV_EV_MIN_VERIFIED, cap,
+                               side, x, y, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, sh, cnt + 4 * cap, cnt + 5 * cap, &found);
+        if (rc != IM_OK) fatalf("im_clip_inverted: %s", im_last_error(d->gpu));
+        if (found <= cap) break;
+        cap = found;                /* more pairs than asked for: once more, with room for all */
+    }
+    pthread_mutex_unlock(&g_query_mu);
+    /* found < 0: the table has overflowed, the header alone */
+    const char* seq = d->sequences[tid];
+    for (int32_t k = 0; k < found; k++) {
+        const int32_t x = pos[k], y = pos[cap + k];
+        if (x == 0) continue;       /* nothing in front to anchor on */
+        fprintf(g_inv_out, "%s\t%d\t.\t%c\t<INV>\t.\t.\tSVTYPE=INV;END=%d;SVLEN=%d;CT=%s;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u\n", d->hdr->target_name[tid], x,
+                toupper((unsigned char)seq[x - 1]), y, y - x, side[k] ? "5to5" : "3to3", pos[2 * cap + k], cnt[k], cnt[cap + k], cnt[4 * cap + k],
+                cnt[5 * cap + k], cnt[2 * cap + k], cnt[3 * cap + k]);
+    }
+    free(pos); free(cnt); free(side);
+    phase_time("inversion evidence (device)");
+}
+
 static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_reader* r)
 {
     d->n_items = 0; d->n_flushes = 0;

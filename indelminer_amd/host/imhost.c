@@ -206,6 +206,24 @@ extern int im_clip_crossed(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t,
                                     * facing pile and a crossed pile */
 #define DUP_EV_MAX_LEN 100000      /* the longest */
 #define DUP_EV_MIN_VERIFIED 2      /* clipped reads of either pile that continue at the other breakpoint */
+/* -N FILE, with -G -C -V: inversion breakpoints -- two peaks of the SAME clip array INV_EV_MIN_LEN .. INV_EV_MAX_LEN bases apart (inverted
+ * piles: the device's peaks of either clip array, paired within each list), kept when at least INV_EV_MIN_VERIFIED clipped reads of
+ * either pile are the complement of the reference running backwards from the other (the device enumerates and verifies its own
+ * candidates).  A small VCF of its own, written to FILE: one record per junction.  stdout, stderr, -I's FILE and -U's FILE stay as they
+ * are.  Not an option of the reference; referenced weakly. */
+static const char* g_inv_file = NULL;
+extern int im_clip_inverted_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint8_t*, int32_t*, int32_t*, uint32_t*,
+                                uint32_t*, uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
+extern int im_clip_inverted(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint8_t*, int32_t*, int32_t*, uint32_t*,
+                            uint32_t*, uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
+#define INVERTED_ON (g_inv_file != NULL)           /* the run ends (a contig ends) with the search for inverted piles */
+#define INVERTED_API_PRESENT (im_clip_inverted_tid && im_clip_inverted)
+#define INV_EV_MIN_READS 3         /* clipped reads of the smaller pile */
+#define INV_EV_REACH 30            /* the reach of a peak: the peaks -I and -U see */
+#define INV_EV_MIN_LEN 50          /* the shortest inversion */
+#define INV_EV_MAX_LEN 1000000     /* the longest: inversions are often larger than duplications, and the device drops a chance pair of
+                                    * peaks after one comparison, before it reads the second pile */
+#define INV_EV_MIN_VERIFIED 2      /* clipped reads of either pile that continue, complemented, backwards from the other */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that
