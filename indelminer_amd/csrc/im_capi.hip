@@ -1078,10 +1078,53 @@ int im_clip_query(im_ctx* ctx, int32_t n, const uint8_t* side, const int32_t* be
     return query_contig_array(ctx, &im_ctx::clip_r, "im_clip", n, beg, end, kArgMax, count_out, &x);
 }
 
+// the two clip arrays a search reads, and their length
+struct ClipArrays { const int32_t* right; const int32_t* left; int64_t clen; };
+
+// the resident arrays of contig tid
+static int resident_clip(im_ctx* ctx, int32_t tid, ClipArrays* A)
+{
+    if (!ctx || !ctx->all_clip_r.data || !ctx->all_clip_l.data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    const int64_t at = ctx->h_asc_off[tid];
+    *A = {ctx->all_clip_r.data + at, ctx->all_clip_l.data + at, ctx->h_len[tid]};
+    return IM_OK;
+}
+
+// the arrays of the last im_clip_build; tid: the contig they must be the arrays of (a search that reads the reference), or null
+static int built_clip(im_ctx* ctx, const char* who, const int32_t* tid, ClipArrays* A)
+{
+    if (!ctx || (tid && (*tid < 0 || *tid >= ctx->n_contigs))) return IM_E_ARG;
+    if (ctx->clip_r.len < 0 || ctx->clip_l.len < 0) { set_err(ctx, "im_clip_build has not been called"); return IM_E_ARG; }
+    if (tid && ctx->clip_r.len != ctx->h_len[*tid]) { set_err(ctx, "%s: the arrays of the last im_clip_build are not contig %d's", who, *tid); return IM_E_ARG; }
+    *A = {ctx->clip_r.data, ctx->clip_l.data, ctx->clip_r.len};
+    return IM_OK;
+}
+
+// k device columns of n 32-bit words down, the rows sorted by up to three key columns (the first decides, then the next), into the
+// host columns.  Key columns hold positions, counts or a side, never a negative value, so a row's keys and its index pack into two
+// 64-bit words that sort as plain integers: a comparator that walks a list of columns cost a third more on a list of peaks.
+static int sorted_columns(im_ctx* ctx, int k, void* const* d_col, uint32_t n, std::initializer_list<int> keys, void* const* out)
+{
+    if (n == 0) return IM_OK;
+    std::vector<int32_t> h((size_t)k * n);
+    for (int c = 0; c < k; c++) HIP_TRY(ctx, hipMemcpyAsync(h.data() + (size_t)c * n, d_col[c], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<std::pair<uint64_t, uint64_t>> row(n);
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t v[3] = {0, 0, 0};
+        int j = 0;
+        for (int c : keys) v[j++] = (uint32_t)h[(size_t)c * n + i];
+        row[i] = {((uint64_t)v[0] << 32) | v[1], ((uint64_t)v[2] << 32) | i};
+    }
+    std::sort(row.begin(), row.end());
+    for (int c = 0; c < k; c++) for (uint32_t i = 0; i < n; i++) ((int32_t*)out[c])[i] = h[(size_t)c * n + (uint32_t)row[i].second];
+    return IM_OK;
+}
+
 // the facing piles of one contig's two arrays: the counter and four arrays of cap in the workspace, one launch, the counter back,
-// then what was found (piles are few), sorted by pr here
-static int facing_arrays(im_ctx* ctx, const char* who, const int32_t* right, const int32_t* left, int64_t clen, int32_t min_reads, int32_t max_overlap,
-                         int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, int32_t* n_found)
+// then what was found (piles are few), sorted by pr here (a position is a pile once)
+static int facing_arrays(im_ctx* ctx, const char* who, const ClipArrays& A, int32_t min_reads, int32_t max_overlap, int32_t cap, int32_t* pr, int32_t* pl,
+                         uint32_t* cr, uint32_t* cl, int32_t* n_found)
 {
     if (min_reads < 1) { set_err(ctx, "%s: min_reads %d, must be >= 1", who, min_reads); return IM_E_ARG; }
     if (max_overlap < 0 || max_overlap > 64) { set_err(ctx, "%s: max_overlap %d, must be 0 .. 64", who, max_overlap); return IM_E_ARG; }
@@ -1095,43 +1138,30 @@ static int facing_arrays(im_ctx* ctx, const char* who, const int32_t* right, con
     void* d_out[4];
     for (int k = 0; k < 4; k++) d_out[k] = (char*)ctx->ws + 256 + k * sb;
     uint32_t found = 0;
-    HIP_TRY(ctx, im::launch_clip_facing(right, left, clen, min_reads, max_overlap, cap, (int32_t*)d_out[0], (int32_t*)d_out[1], (uint32_t*)d_out[2],
+    HIP_TRY(ctx, im::launch_clip_facing(A.right, A.left, A.clen, min_reads, max_overlap, cap, (int32_t*)d_out[0], (int32_t*)d_out[1], (uint32_t*)d_out[2],
                                         (uint32_t*)d_out[3], d_count, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&found, d_count, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *n_found = (int32_t)found;
-    if (found == 0 || found > (uint32_t)cap) return IM_OK;          // more than cap: the caller asks again
-    std::vector<int32_t> h[4];
-    for (int k = 0; k < 4; k++) {
-        h[k].resize(found);
-        HIP_TRY(ctx, hipMemcpyAsync(h[k].data(), d_out[k], sizeof(int32_t) * (size_t)found, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<int32_t> order(found);
-    for (uint32_t i = 0; i < found; i++) order[i] = (int32_t)i;
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return h[0][a] < h[0][b]; });      // a position is a pile once
-    for (uint32_t i = 0; i < found; i++) {
-        const int32_t k = order[i];
-        pr[i] = h[0][k]; pl[i] = h[1][k]; cr[i] = (uint32_t)h[2][k]; cl[i] = (uint32_t)h[3][k];
-    }
-    return IM_OK;
+    if (found > (uint32_t)cap) return IM_OK;                        // more than cap: the caller asks again
+    void* const out[4] = {pr, pl, cr, cl};
+    return sorted_columns(ctx, 4, d_out, found, {0}, out);
 }
 
 int im_clip_facing_tid(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t max_overlap, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr,
                        uint32_t* cl, int32_t* n_found)
 {
-    if (!ctx || !ctx->all_clip_r.data || !ctx->all_clip_l.data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    const int64_t at = ctx->h_asc_off[tid];
-    return facing_arrays(ctx, "im_clip_facing_tid", ctx->all_clip_r.data + at, ctx->all_clip_l.data + at, ctx->h_len[tid], min_reads, max_overlap, cap,
-                         pr, pl, cr, cl, n_found);
+    ClipArrays A;
+    const int rc = resident_clip(ctx, tid, &A);
+    return rc ? rc : facing_arrays(ctx, "im_clip_facing_tid", A, min_reads, max_overlap, cap, pr, pl, cr, cl, n_found);
 }
 
 int im_clip_facing(im_ctx* ctx, int32_t min_reads, int32_t max_overlap, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl,
                    int32_t* n_found)
 {
-    if (!ctx) return IM_E_ARG;
-    if (ctx->clip_r.len < 0 || ctx->clip_l.len < 0) { set_err(ctx, "im_clip_build has not been called"); return IM_E_ARG; }
-    return facing_arrays(ctx, "im_clip_facing", ctx->clip_r.data, ctx->clip_l.data, ctx->clip_r.len, min_reads, max_overlap, cap, pr, pl, cr, cl, n_found);
+    ClipArrays A;
+    const int rc = built_clip(ctx, "im_clip_facing", nullptr, &A);
+    return rc ? rc : facing_arrays(ctx, "im_clip_facing", A, min_reads, max_overlap, cap, pr, pl, cr, cl, n_found);
 }
 
 // ---- clip tails: the clipped bases of clipped reads against the reference behind the partner breakpoint ----------
@@ -1270,7 +1300,7 @@ int im_cliptail_consensus(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* p
     return IM_OK;
 }
 
-// ---- crossed piles: the peaks of either clip array, and the pairs of them a tandem duplication leaves (-U) ----------
+// ---- the peaks of either clip array, which the searches for pairs of piles start from ----------
 
 static int peaks_args(im_ctx* ctx, const char* who, int32_t min_reads, int32_t reach, int32_t cap)
 {
@@ -1281,27 +1311,20 @@ static int peaks_args(im_ctx* ctx, const char* who, int32_t min_reads, int32_t r
 }
 
 // (position, count) pairs from two device arrays of n, sorted by position (a position is a peak once)
-static int sorted_peaks(im_ctx* ctx, const void* d_pos, const void* d_cnt, uint32_t n, std::vector<int32_t>& pos, std::vector<uint32_t>& cnt)
+static int sorted_peaks(im_ctx* ctx, void* d_pos, void* d_cnt, uint32_t n, std::vector<int32_t>& pos, std::vector<uint32_t>& cnt)
 {
-    std::vector<int32_t> p(n);
-    std::vector<uint32_t> c(n);
     pos.resize(n); cnt.resize(n);
-    if (n == 0) return IM_OK;
-    HIP_TRY(ctx, hipMemcpyAsync(p.data(), d_pos, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(c.data(), d_cnt, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint32_t> order(n);
-    for (uint32_t i = 0; i < n; i++) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return p[a] < p[b]; });
-    for (uint32_t i = 0; i < n; i++) { pos[i] = p[order[i]]; cnt[i] = c[order[i]]; }
-    return IM_OK;
+    void* const d_col[2] = {d_pos, d_cnt};
+    void* const out[2] = {pos.data(), cnt.data()};
+    return sorted_columns(ctx, 2, d_col, n, {0}, out);
 }
 
 // the peaks of one contig's one array: the counter and two arrays of cap in the workspace, one launch, the counter back, then what
 // was found, sorted by position here
-static int peaks_array(im_ctx* ctx, const char* who, const int32_t* arr, int64_t clen, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos,
+static int peaks_array(im_ctx* ctx, const char* who, const ClipArrays& A, int32_t side, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos,
                        uint32_t* count, int32_t* n_found)
 {
+    if (side < 0 || side > 1) { set_err(ctx, "%s: side %d, must be 0 (right) or 1 (left)", who, side); return IM_E_ARG; }
     int rc = peaks_args(ctx, who, min_reads, reach, cap);
     if (rc) return rc;
     if (!n_found || (cap > 0 && (!pos || !count))) return IM_E_ARG;
@@ -1310,51 +1333,29 @@ static int peaks_array(im_ctx* ctx, const char* who, const int32_t* arr, int64_t
     rc = ensure_ws(ctx, 256 + 2 * sb);
     if (rc) return rc;
     uint32_t* d_count = (uint32_t*)ctx->ws;
-    int32_t* d_pos = (int32_t*)((char*)ctx->ws + 256);
-    uint32_t* d_cnt = (uint32_t*)((char*)ctx->ws + 256 + sb);
+    void* const d_col[2] = {(char*)ctx->ws + 256, (char*)ctx->ws + 256 + sb};
     uint32_t found = 0;
-    HIP_TRY(ctx, im::launch_clip_peaks(arr, clen, min_reads, reach, cap, d_pos, d_cnt, d_count, ctx->stream));
+    HIP_TRY(ctx, im::launch_clip_peaks(side ? A.left : A.right, A.clen, min_reads, reach, cap, (int32_t*)d_col[0], (uint32_t*)d_col[1], d_count, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&found, d_count, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *n_found = (int32_t)found;
-    if (found == 0 || found > (uint32_t)cap) return IM_OK;          // more than cap: the caller asks again
-    std::vector<int32_t> p;
-    std::vector<uint32_t> c;
-    rc = sorted_peaks(ctx, d_pos, d_cnt, found, p, c);
-    if (rc) return rc;
-    memcpy(pos, p.data(), sizeof(int32_t) * (size_t)found); memcpy(count, c.data(), sizeof(uint32_t) * (size_t)found);
-    return IM_OK;
+    if (found > (uint32_t)cap) return IM_OK;                        // more than cap: the caller asks again
+    void* const out[2] = {pos, count};
+    return sorted_columns(ctx, 2, d_col, found, {0}, out);
 }
 
 int im_clip_peaks_tid(im_ctx* ctx, int32_t tid, int32_t side, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count, int32_t* n_found)
 {
-    if (!ctx || !ctx->all_clip_r.data || !ctx->all_clip_l.data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    if (side < 0 || side > 1) { set_err(ctx, "im_clip_peaks_tid: side %d, must be 0 (right) or 1 (left)", side); return IM_E_ARG; }
-    return peaks_array(ctx, "im_clip_peaks_tid", (side ? ctx->all_clip_l.data : ctx->all_clip_r.data) + ctx->h_asc_off[tid], ctx->h_len[tid], min_reads, reach,
-                       cap, pos, count, n_found);
+    ClipArrays A;
+    const int rc = resident_clip(ctx, tid, &A);
+    return rc ? rc : peaks_array(ctx, "im_clip_peaks_tid", A, side, min_reads, reach, cap, pos, count, n_found);
 }
 
 int im_clip_peaks(im_ctx* ctx, int32_t side, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count, int32_t* n_found)
 {
-    if (!ctx) return IM_E_ARG;
-    if (ctx->clip_r.len < 0 || ctx->clip_l.len < 0) { set_err(ctx, "im_clip_build has not been called"); return IM_E_ARG; }
-    if (side < 0 || side > 1) { set_err(ctx, "im_clip_peaks: side %d, must be 0 (right) or 1 (left)", side); return IM_E_ARG; }
-    return peaks_array(ctx, "im_clip_peaks", side ? ctx->clip_l.data : ctx->clip_r.data, ctx->clip_r.len, min_reads, reach, cap, pos, count, n_found);
-}
-
-// what the searches for pairs of piles (crossed, inverted) check alike, behind the table and the reference
-static int pile_pair_args(im_ctx* ctx, const char* who, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift,
-                          int32_t min_verified, int32_t cap)
-{
-    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
-    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
-    int rc = peaks_args(ctx, who, min_reads, reach, cap);
-    if (rc) return rc;
-    if (min_len < 1) { set_err(ctx, "%s: min_len %d, must be >= 1", who, min_len); return IM_E_ARG; }
-    if (max_len < min_len) { set_err(ctx, "%s: max_len %d, must be >= min_len %d", who, max_len, min_len); return IM_E_ARG; }
-    if (max_shift < 0 || max_shift > 32) { set_err(ctx, "%s: max_shift %d, must be 0 .. 32", who, max_shift); return IM_E_ARG; }
-    if (min_verified < 1) { set_err(ctx, "%s: min_verified %d, must be >= 1", who, min_verified); return IM_E_ARG; }
-    return IM_OK;
+    ClipArrays A;
+    const int rc = built_clip(ctx, "im_clip_peaks", nullptr, &A);
+    return rc ? rc : peaks_array(ctx, "im_clip_peaks", A, side, min_reads, reach, cap, pos, count, n_found);
 }
 
 // The peaks of both arrays of one contig in the workspace: the counter block (256 bytes: the two peak counters, then the caller's
@@ -1362,7 +1363,7 @@ static int pile_pair_args(im_ctx* ctx, const char* who, int32_t min_reads, int32
 // Both peak passes, their two counters back, once more with room for all when a list did not fit.  found: the peaks per side.
 struct PeakLists { char* base; size_t pb; uint32_t found[2]; };
 
-static int peak_lists(im_ctx* ctx, const int32_t* right, const int32_t* left, int64_t clen, int32_t min_reads, int32_t reach, size_t out_bytes, PeakLists* P)
+static int peak_lists(im_ctx* ctx, const ClipArrays& A, int32_t min_reads, int32_t reach, size_t out_bytes, PeakLists* P)
 {
     uint32_t pcap = 65536;
     for (;;) {
@@ -1371,8 +1372,8 @@ static int peak_lists(im_ctx* ctx, const int32_t* right, const int32_t* left, in
         if (rc) return rc;
         P->base = (char*)ctx->ws;
         uint32_t* d_count = (uint32_t*)P->base;
-        HIP_TRY(ctx, im::launch_clip_peaks(right, clen, min_reads, reach, (int32_t)pcap, (int32_t*)(P->base + 256), (uint32_t*)(P->base + 256 + P->pb), d_count, ctx->stream));
-        HIP_TRY(ctx, im::launch_clip_peaks(left, clen, min_reads, reach, (int32_t)pcap, (int32_t*)(P->base + 256 + 2 * P->pb), (uint32_t*)(P->base + 256 + 3 * P->pb), d_count + 1, ctx->stream));
+        HIP_TRY(ctx, im::launch_clip_peaks(A.right, A.clen, min_reads, reach, (int32_t)pcap, (int32_t*)(P->base + 256), (uint32_t*)(P->base + 256 + P->pb), d_count, ctx->stream));
+        HIP_TRY(ctx, im::launch_clip_peaks(A.left, A.clen, min_reads, reach, (int32_t)pcap, (int32_t*)(P->base + 256 + 2 * P->pb), (uint32_t*)(P->base + 256 + 3 * P->pb), d_count + 1, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(P->found, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (P->found[0] <= pcap && P->found[1] <= pcap) return IM_OK;
@@ -1394,168 +1395,106 @@ static int sort_peak_lists(im_ctx* ctx, const PeakLists& P, void* d_list[4], std
     return IM_OK;
 }
 
-// The crossed piles of one contig.  In order: the table's counters (an overflowed table answers nothing), both peak passes into the
-// workspace, their two counters back (peak_lists), the lists down, sorted and up again (sort_peak_lists), the cross launch, its
-// counter back, then min(found, cap) pairs down and sorted by (pr, pl).
-static int crossed_arrays(im_ctx* ctx, const char* who, const int32_t* right, const int32_t* left, int32_t tid, int32_t min_reads, int32_t reach,
-                          int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr,
-                          uint32_t* cl, uint32_t* v_right, uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found)
+// ---- pairs of piles: crossed, which a tandem duplication leaves (-U), and inverted, which an inversion's junction leaves (-N) ----------
+
+// The pairs of piles of one contig, crossed (a right peak with the left peaks in front of it) or inverted (two peaks of one list).
+// Behind the arguments, the table and the reference, in order: the table's counters (an overflowed table answers nothing), both peak
+// passes into the workspace, their two counters back (peak_lists), the lists down, sorted and up again (sort_peak_lists), the ONE
+// launch, its counter back, then min(found, cap) rows of ten columns down and sorted by (p1, p2, side) -- side is 0 in every crossed
+// row.  side: the caller's side column (inverted) or null (crossed); out: p1, p2, c1, c2, v1, v2, shift, stored1, stored2.  The crossed
+// search carries the side column too -- ten columns of workspace where it had nine, and a column of zeros brought down and dropped --
+// so that one launch, one layout and one key list serve both kinds.
+static int pile_pairs_arrays(im_ctx* ctx, const char* who, bool inverted, const ClipArrays& C, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len,
+                             int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, uint8_t* side, void* const out[9], int32_t* n_found)
 {
-    int rc = pile_pair_args(ctx, who, min_reads, reach, min_len, max_len, max_shift, min_verified, cap);
+    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    int rc = peaks_args(ctx, who, min_reads, reach, cap);
     if (rc) return rc;
-    if (!n_found || (cap > 0 && (!pr || !pl || !cr || !cl || !v_right || !v_left || !shift || !stored_right || !stored_left))) return IM_E_ARG;
+    if (min_len < 1) { set_err(ctx, "%s: min_len %d, must be >= 1", who, min_len); return IM_E_ARG; }
+    if (max_len < min_len) { set_err(ctx, "%s: max_len %d, must be >= min_len %d", who, max_len, min_len); return IM_E_ARG; }
+    if (max_shift < 0 || max_shift > 32) { set_err(ctx, "%s: max_shift %d, must be 0 .. 32", who, max_shift); return IM_E_ARG; }
+    if (min_verified < 1) { set_err(ctx, "%s: min_verified %d, must be >= 1", who, min_verified); return IM_E_ARG; }
+    bool all = n_found && (!inverted || cap == 0 || side);
+    for (int k = 0; k < 9; k++) all = all && (cap == 0 || out[k]);
+    if (!all) return IM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t clen = ctx->h_len[tid];
     unsigned long long counters[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (counters[1] > 0) { *n_found = -1; return IM_OK; }           // no answer, not a wrong one
     const size_t ob = up256(sizeof(int32_t) * (size_t)(cap ? cap : 1));
     PeakLists P;
-    rc = peak_lists(ctx, right, left, clen, min_reads, reach, 9 * ob, &P);
+    rc = peak_lists(ctx, C, min_reads, reach, 10 * ob, &P);
     if (rc) return rc;
-    char* base = P.base;
-    const size_t pb = P.pb;
-    uint32_t found[3] = {P.found[0], P.found[1], 0};
     *n_found = 0;
-    if (found[0] == 0 || found[1] == 0) return IM_OK;
-    void* d_list[4];
-    std::vector<int32_t> hp[2];
-    std::vector<uint32_t> hc[2];
-    rc = sort_peak_lists(ctx, P, d_list, hp, hc);
-    if (rc) return rc;
-    void* d_out[9];
-    for (int k = 0; k < 9; k++) d_out[k] = base + 256 + 4 * pb + k * ob;
-    uint32_t* d_pairs = (uint32_t*)base + 2;
-    HIP_TRY(ctx, im::launch_cliptail_cross((int32_t)found[0], (const int32_t*)d_list[0], (const uint32_t*)d_list[1], (int32_t)found[1], (const int32_t*)d_list[2],
-                                           (const uint32_t*)d_list[3], tid, min_len, max_len, max_shift, min_verified, cap, ctx->ref_ascii + ctx->h_asc_off[tid],
-                                           clen, ctx->tail, (int32_t*)d_out[0], (int32_t*)d_out[1], (uint32_t*)d_out[2], (uint32_t*)d_out[3], (uint32_t*)d_out[4],
-                                           (uint32_t*)d_out[5], (int32_t*)d_out[6], (uint32_t*)d_out[7], (uint32_t*)d_out[8], d_pairs, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&found[2], d_pairs, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                // the uploads' host vectors are done with here as well
-    *n_found = (int32_t)found[2];
-    const uint32_t n = found[2] < (uint32_t)cap ? found[2] : (uint32_t)cap;
-    if (n == 0) return IM_OK;
-    std::vector<int32_t> h[9];
-    for (int k = 0; k < 9; k++) {
-        h[k].resize(n);
-        HIP_TRY(ctx, hipMemcpyAsync(h[k].data(), d_out[k], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint32_t> order(n);
-    for (uint32_t i = 0; i < n; i++) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return h[0][a] != h[0][b] ? h[0][a] < h[0][b] : h[1][a] < h[1][b]; });
-    int32_t* out[9] = {pr, pl, (int32_t*)cr, (int32_t*)cl, (int32_t*)v_right, (int32_t*)v_left, shift, (int32_t*)stored_right, (int32_t*)stored_left};
-    for (uint32_t i = 0; i < n; i++) for (int k = 0; k < 9; k++) out[k][i] = h[k][order[i]];
-    return IM_OK;
-}
-
-int im_clip_crossed_tid(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified,
-                        int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
-                        uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found)
-{
-    if (!ctx || !ctx->all_clip_r.data || !ctx->all_clip_l.data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    const int64_t at = ctx->h_asc_off[tid];
-    return crossed_arrays(ctx, "im_clip_crossed_tid", ctx->all_clip_r.data + at, ctx->all_clip_l.data + at, tid, min_reads, reach, min_len, max_len, max_shift,
-                          min_verified, cap, pr, pl, cr, cl, v_right, v_left, shift, stored_right, stored_left, n_found);
-}
-
-int im_clip_crossed(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified,
-                    int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
-                    uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found)
-{
-    if (!ctx || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    if (ctx->clip_r.len < 0 || ctx->clip_l.len < 0) { set_err(ctx, "im_clip_build has not been called"); return IM_E_ARG; }
-    if (ctx->clip_r.len != ctx->h_len[tid]) { set_err(ctx, "im_clip_crossed: the arrays of the last im_clip_build are not contig %d's", tid); return IM_E_ARG; }
-    return crossed_arrays(ctx, "im_clip_crossed", ctx->clip_r.data, ctx->clip_l.data, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap,
-                          pr, pl, cr, cl, v_right, v_left, shift, stored_right, stored_left, n_found);
-}
-
-// ---- inverted piles: the pairs of peaks of ONE clip array an inversion's junction leaves (-N) ----------
-
-// The inverted piles of one contig, crossed_arrays step for step: the table's counters (an overflowed table answers nothing), both
-// peak passes into the workspace, their two counters back (peak_lists), the lists down, sorted and up again (sort_peak_lists), the
-// ONE launch over both lists, its counter back, then min(found, cap) pairs down and sorted by (x, y, side).
-static int inverted_arrays(im_ctx* ctx, const char* who, const int32_t* right, const int32_t* left, int32_t tid, int32_t min_reads, int32_t reach,
-                           int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, uint8_t* side, int32_t* p1, int32_t* p2,
-                           uint32_t* c1, uint32_t* c2, uint32_t* v1, uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2, int32_t* n_found)
-{
-    int rc = pile_pair_args(ctx, who, min_reads, reach, min_len, max_len, max_shift, min_verified, cap);
-    if (rc) return rc;
-    if (!n_found || (cap > 0 && (!side || !p1 || !p2 || !c1 || !c2 || !v1 || !v2 || !shift || !stored1 || !stored2))) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t clen = ctx->h_len[tid];
-    unsigned long long counters[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (counters[1] > 0) { *n_found = -1; return IM_OK; }           // no answer, not a wrong one
-    const size_t ob = up256(sizeof(int32_t) * (size_t)(cap ? cap : 1));
-    PeakLists P;
-    rc = peak_lists(ctx, right, left, clen, min_reads, reach, 10 * ob, &P);
-    if (rc) return rc;
-    char* base = P.base;
-    const size_t pb = P.pb;
-    uint32_t found[3] = {P.found[0], P.found[1], 0};
-    *n_found = 0;
-    if (found[0] < 2 && found[1] < 2) return IM_OK;                 // a pair takes two peaks of one list
+    // crossed: a pair takes a peak of either list; inverted: two peaks of one list
+    if (inverted ? P.found[0] < 2 && P.found[1] < 2 : P.found[0] == 0 || P.found[1] == 0) return IM_OK;
     void* d_list[4];
     std::vector<int32_t> hp[2];
     std::vector<uint32_t> hc[2];
     rc = sort_peak_lists(ctx, P, d_list, hp, hc);
     if (rc) return rc;
     void* d_out[10];
-    for (int k = 0; k < 10; k++) d_out[k] = base + 256 + 4 * pb + k * ob;
-    uint32_t* d_pairs = (uint32_t*)base + 2;
-    HIP_TRY(ctx, im::launch_cliptail_inverted((int32_t)found[0], (const int32_t*)d_list[0], (const uint32_t*)d_list[1], (int32_t)found[1], (const int32_t*)d_list[2],
-                                              (const uint32_t*)d_list[3], tid, min_len, max_len, max_shift, min_verified, cap, ctx->ref_ascii + ctx->h_asc_off[tid],
-                                              clen, ctx->tail, (uint32_t*)d_out[0], (int32_t*)d_out[1], (int32_t*)d_out[2], (uint32_t*)d_out[3], (uint32_t*)d_out[4],
-                                              (uint32_t*)d_out[5], (uint32_t*)d_out[6], (int32_t*)d_out[7], (uint32_t*)d_out[8], (uint32_t*)d_out[9], d_pairs,
-                                              ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&found[2], d_pairs, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    for (int k = 0; k < 10; k++) d_out[k] = P.base + 256 + 4 * P.pb + k * ob;
+    im::TailPairsArgs A;
+    A.n_right = (int32_t)P.found[0]; A.n_left = (int32_t)P.found[1]; A.tid = tid;
+    A.rpos = (const int32_t*)d_list[0]; A.rcnt = (const uint32_t*)d_list[1]; A.lpos = (const int32_t*)d_list[2]; A.lcnt = (const uint32_t*)d_list[3];
+    A.min_len = min_len; A.max_len = max_len; A.max_shift = max_shift; A.min_verified = min_verified; A.cap = cap;
+    A.ref = ctx->ref_ascii + ctx->h_asc_off[tid]; A.clen = ctx->h_len[tid]; A.tab = ctx->tail;
+    for (int k = 0; k < 10; k++) A.col[k] = (uint32_t*)d_out[k];
+    A.n_found = (uint32_t*)P.base + 2;
+    uint32_t found = 0;
+    HIP_TRY(ctx, im::launch_cliptail_pairs(inverted, A, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&found, A.n_found, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                // the uploads' host vectors are done with here as well
-    *n_found = (int32_t)found[2];
-    const uint32_t n = found[2] < (uint32_t)cap ? found[2] : (uint32_t)cap;
-    if (n == 0) return IM_OK;
-    std::vector<int32_t> h[10];
-    for (int k = 0; k < 10; k++) {
-        h[k].resize(n);
-        HIP_TRY(ctx, hipMemcpyAsync(h[k].data(), d_out[k], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint32_t> order(n);
-    for (uint32_t i = 0; i < n; i++) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        if (h[1][a] != h[1][b]) return h[1][a] < h[1][b];
-        if (h[2][a] != h[2][b]) return h[2][a] < h[2][b];
-        return h[0][a] < h[0][b];
-    });
-    int32_t* out[9] = {p1, p2, (int32_t*)c1, (int32_t*)c2, (int32_t*)v1, (int32_t*)v2, shift, (int32_t*)stored1, (int32_t*)stored2};
-    for (uint32_t i = 0; i < n; i++) {
-        side[i] = (uint8_t)h[0][order[i]];
-        for (int k = 0; k < 9; k++) out[k][i] = h[k + 1][order[i]];
-    }
-    return IM_OK;
+    *n_found = (int32_t)found;
+    const uint32_t n = found < (uint32_t)cap ? found : (uint32_t)cap;
+    std::vector<int32_t> hside(n);                                  // a word per row here, a byte per row (or nothing) at the caller
+    void* const h_out[10] = {hside.data(), out[0], out[1], out[2], out[3], out[4], out[5], out[6], out[7], out[8]};
+    rc = sorted_columns(ctx, 10, d_out, n, {1, 2, 0}, h_out);
+    for (uint32_t i = 0; i < n && side && !rc; i++) side[i] = (uint8_t)hside[i];
+    return rc;
+}
+
+int im_clip_crossed_tid(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified,
+                        int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
+                        uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found)
+{
+    ClipArrays A;
+    void* const out[9] = {pr, pl, cr, cl, v_right, v_left, shift, stored_right, stored_left};
+    const int rc = resident_clip(ctx, tid, &A);
+    return rc ? rc : pile_pairs_arrays(ctx, "im_clip_crossed_tid", false, A, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap, nullptr, out, n_found);
+}
+
+int im_clip_crossed(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified,
+                    int32_t cap, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
+                    uint32_t* stored_right, uint32_t* stored_left, int32_t* n_found)
+{
+    ClipArrays A;
+    void* const out[9] = {pr, pl, cr, cl, v_right, v_left, shift, stored_right, stored_left};
+    const int rc = built_clip(ctx, "im_clip_crossed", &tid, &A);
+    return rc ? rc : pile_pairs_arrays(ctx, "im_clip_crossed", false, A, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap, nullptr, out, n_found);
 }
 
 int im_clip_inverted_tid(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified,
                          int32_t cap, uint8_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1, uint32_t* v2, int32_t* shift,
                          uint32_t* stored1, uint32_t* stored2, int32_t* n_found)
 {
-    if (!ctx || !ctx->all_clip_r.data || !ctx->all_clip_l.data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    const int64_t at = ctx->h_asc_off[tid];
-    return inverted_arrays(ctx, "im_clip_inverted_tid", ctx->all_clip_r.data + at, ctx->all_clip_l.data + at, tid, min_reads, reach, min_len, max_len, max_shift,
-                           min_verified, cap, side, p1, p2, c1, c2, v1, v2, shift, stored1, stored2, n_found);
+    ClipArrays A;
+    void* const out[9] = {p1, p2, c1, c2, v1, v2, shift, stored1, stored2};
+    const int rc = resident_clip(ctx, tid, &A);
+    return rc ? rc : pile_pairs_arrays(ctx, "im_clip_inverted_tid", true, A, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap, side, out, n_found);
 }
 
 int im_clip_inverted(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified,
                      int32_t cap, uint8_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1, uint32_t* v2, int32_t* shift,
                      uint32_t* stored1, uint32_t* stored2, int32_t* n_found)
 {
-    if (!ctx || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    if (ctx->clip_r.len < 0 || ctx->clip_l.len < 0) { set_err(ctx, "im_clip_build has not been called"); return IM_E_ARG; }
-    if (ctx->clip_r.len != ctx->h_len[tid]) { set_err(ctx, "im_clip_inverted: the arrays of the last im_clip_build are not contig %d's", tid); return IM_E_ARG; }
-    return inverted_arrays(ctx, "im_clip_inverted", ctx->clip_r.data, ctx->clip_l.data, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap,
-                           side, p1, p2, c1, c2, v1, v2, shift, stored1, stored2, n_found);
+    ClipArrays A;
+    void* const out[9] = {p1, p2, c1, c2, v1, v2, shift, stored1, stored2};
+    const int rc = built_clip(ctx, "im_clip_inverted", &tid, &A);
+    return rc ? rc : pile_pairs_arrays(ctx, "im_clip_inverted", true, A, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap, side, out, n_found);
 }
 
 int im_cliptail_reset(im_ctx* ctx, void* stream)

@@ -21,9 +21,9 @@
 //   cliptail_add       one lane per entry the host names (the record-at-a-time path)
 //   cliptail_verify    one wave per query (tid, pr, pl): see the kernel
 //   cliptail_consensus one wave per query (tid, position, side): the per-base consensus of a pile's entries (-I), on the same walk
-//   cliptail_cross     one wave per peak of clipR: the peaks of clipL the right distance in front of it, verified as above (-U)
-//   cliptail_inverted  one wave per peak of either array: the peaks of the SAME array the right distance behind it, verified against
-//                      the reference's reverse complement (-N)
+//   cliptail_pairs     one wave per peak: the peaks the right distance away, verified as above.  <false>: a peak of clipR with the
+//                      peaks of clipL in front of it (-U); <true>: a peak of either array with the peaks of the SAME array behind it,
+//                      against the reference's reverse complement (-N)
 
 #include "im_device.hpp"
 #include "im_spanrec.hpp"
@@ -304,10 +304,14 @@ __device__ __forceinline__ bool tail_best_shift(uint32_t vr, uint32_t vl, int32_
     return found;
 }
 
-// The window of the other strand: the complement of A 0, C 1, G 2, T 3 is both planes inverted; what is no base stays no base.
-__device__ __forceinline__ TailWindow tail_complement(TailWindow W)
+// The window the entries of a pile on `side` are expected to hold, given the other pile at position o: right entries (side 0) read on
+// from o, left entries (side 1) read backwards from o - 1; across an inversion's junction the directions swap and the bases are the
+// other strand's.  The complement of A 0, C 1, G 2, T 3 is both planes inverted; what is no base stays no base.
+__device__ __forceinline__ TailWindow tail_expected_window(const uint8_t* __restrict__ ref, int64_t clen, int64_t o, uint32_t side, bool inverted, int lane)
 {
-    W.lo = ~W.lo; W.hi = ~W.hi;
+    const bool forward = (side == 0u) != inverted;
+    TailWindow W = tail_window(ref, clen, forward ? o + lane : o - 1 - lane);
+    if (inverted) { W.lo = ~W.lo; W.hi = ~W.hi; }
     return W;
 }
 
@@ -358,8 +362,8 @@ __global__ __launch_bounds__(kTailWaveBlock) void cliptail_verify_kernel(TailVer
     for (int q = wave; q < A.nq; q += nwaves) {
         const int64_t pr = A.pr[q], pl = A.pl[q];
         const bool compare = pl > pr;
-        const TailWindow Wr = tail_window(A.ref, A.clen, pl + lane);            // what right entries are expected to hold
-        const TailWindow Wl = tail_window(A.ref, A.clen, pr - 1 - lane);        // what left entries are expected to hold
+        const TailWindow Wr = tail_expected_window(A.ref, A.clen, pl, 0u, false, lane);
+        const TailWindow Wl = tail_expected_window(A.ref, A.clen, pr, 1u, false, lane);
         uint32_t vr, vl;
         const uint32_t sr = tail_side(A.tab, A.tid, pr, 0u, A.clen, Wr, compare, A.max_shift, lane, &vr);
         const uint32_t sl = tail_side(A.tab, A.tid, pl, 1u, A.clen, Wl, compare, A.max_shift, lane, &vl);
@@ -373,21 +377,6 @@ __global__ __launch_bounds__(kTailWaveBlock) void cliptail_verify_kernel(TailVer
     }
 }
 
-struct TailCrossArgs {
-    int32_t n_right, n_left, tid;
-    const int32_t* rpos;        // the peaks of clipR, ascending, and their counts
-    const uint32_t* rcnt;
-    const int32_t* lpos;        // the peaks of clipL, ascending, and their counts
-    const uint32_t* lcnt;
-    int32_t min_len, max_len, max_shift, min_verified, cap;
-    const uint8_t* ref;
-    int64_t clen;
-    TailTable tab;
-    int32_t* pr; int32_t* pl; uint32_t* cr; uint32_t* cl;
-    uint32_t* v_right; uint32_t* v_left; int32_t* shift; uint32_t* stored_right; uint32_t* stored_left;
-    uint32_t* n_found;
-};
-
 // the first index of the ascending list at which pos[i] >= x (n when there is none): every lane runs the same search
 __device__ __forceinline__ int32_t first_at_or_behind(const int32_t* __restrict__ pos, int32_t n, int64_t x)
 {
@@ -399,97 +388,50 @@ __device__ __forceinline__ int32_t first_at_or_behind(const int32_t* __restrict_
     return lo;
 }
 
-// Crossed piles (-U; include/indelminer_amd.h, seam 5, "Crossed piles"): one wave per peak pr of clipR.  Its candidates are the run of
-// the left list inside [pr - max_len, pr - min_len], found by two binary searches; a peak without one ends there.  What depends on
-// pr alone is fetched once: the window ref[pr - 1 - lane] the left entries of every partner are compared with, and the right pile's
-// entries (tail_hold: in the lanes when one batch of the walk holds them all, walked per candidate otherwise).  Per candidate: the
-// window ref[pl + lane], the left pile's walk, the chosen shift.  The rare pair that qualifies takes its slot with one returning
-// atomic by lane 0; n_found counts every pair, only slots below cap are written.  Nothing here is divergent: every branch is on
-// values the whole wave shares.
-__global__ __launch_bounds__(kTailWaveBlock) void cliptail_cross_kernel(TailCrossArgs A)
+// Pairs of piles (include/indelminer_amd.h, seam 5, "Crossed piles" and "Inverted piles"): ONE BODY, two geometries.
+//                 the wave's peak p, pile side s       its partners o, pile side t                              windows
+//   crossed  (-U) a peak of the right list, s = 0      the LEFT list inside [p - max_len, p - min_len], t = 1   this strand
+//   inverted (-N) a peak of either list, s = its side  the SAME list inside [p + min_len, p + max_len], t = s   the other strand
+// (the inverted waves below n_right take the right peaks, the others the left ones).  The partners are a run of a sorted list, found by
+// two binary searches; a peak without one ends there.  What depends on p alone is fetched once: the window the entries of every
+// partner are expected to hold (tail_expected_window of p for side t), and the pile at p (tail_hold: in the lanes when one batch of
+// the walk holds it all, walked per partner otherwise).  Per partner: the window the held entries are expected to hold and v1(.) of
+// the held pile; ONLY when some shift has v1 >= min_verified the walk of the pile at o for v2(.), the chosen shift, the
+// qualification.  That first cut changes no answer -- a pair qualifies only with v1 >= min_verified at the chosen shift, so a held
+// pile that reaches it at no shift has no pair here -- and a chance pair of peaks so costs one 64-byte load and one shift loop.  The
+// rare pair that qualifies takes its slot with one returning atomic by lane 0; n_found counts every pair, only slots below cap are
+// written, column k at col[k][slot]: side (0 for crossed), p1 = p, p2 = o, their counts, v1, v2, shift, stored at p,
+// stored at o.  Every branch is on values the whole wave shares; kInverted is a compile-time parameter so that neither instantiation
+// carries the other's selects.
+template <bool kInverted>
+__global__ __launch_bounds__(kTailWaveBlock) void cliptail_pairs_kernel(TailPairsArgs A)
 {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    for (int q = wave; q < A.n_right; q += nwaves) {
-        const int64_t pr = A.rpos[q];
-        const int32_t k0 = first_at_or_behind(A.lpos, A.n_left, pr - (int64_t)A.max_len);
-        const int32_t k1 = first_at_or_behind(A.lpos, A.n_left, pr - (int64_t)A.min_len + 1);
-        if (k0 >= k1) continue;
-        const TailWindow Wl = tail_window(A.ref, A.clen, pr - 1 - lane);        // what the left entries of every partner are expected to hold
-        const TailHeld H = tail_hold(A.tab, A.tid, pr, 0u, A.clen, lane);
-        const uint32_t sr = H.stored;
-        for (int32_t k = k0; k < k1; k++) {
-            const int64_t pl = A.lpos[k];
-            const TailWindow Wr = tail_window(A.ref, A.clen, pl + lane);        // what the right entries are expected to hold
-            uint32_t vl;
-            const uint32_t vr = tail_held_shifts(H, A.tab, A.tid, pr, 0u, A.clen, Wr, A.max_shift, lane);
-            const uint32_t sl = tail_side(A.tab, A.tid, pl, 1u, A.clen, Wl, true, A.max_shift, lane, &vl);
-            int best;
-            uint32_t br, bl;
-            const bool found = tail_best_shift(vr, vl, A.max_shift, lane, &best, &br, &bl);
-            if (!found || br < (uint32_t)A.min_verified || bl < (uint32_t)A.min_verified) continue;
-            if (lane == 0) {
-                const uint32_t slot = atomicAdd(A.n_found, 1u);
-                if (slot < (uint32_t)A.cap) {
-                    A.pr[slot] = (int32_t)pr; A.pl[slot] = (int32_t)pl; A.cr[slot] = A.rcnt[q]; A.cl[slot] = A.lcnt[k];
-                    A.v_right[slot] = br; A.v_left[slot] = bl; A.shift[slot] = best; A.stored_right[slot] = sr; A.stored_left[slot] = sl;
-                }
-            }
-        }
-    }
-}
-
-struct TailInvertedArgs {
-    int32_t n_right, n_left, tid;
-    const int32_t* rpos;        // the peaks of clipR, ascending, and their counts
-    const uint32_t* rcnt;
-    const int32_t* lpos;        // the peaks of clipL, ascending, and their counts
-    const uint32_t* lcnt;
-    int32_t min_len, max_len, max_shift, min_verified, cap;
-    const uint8_t* ref;
-    int64_t clen;
-    TailTable tab;
-    uint32_t* side; int32_t* p1; int32_t* p2; uint32_t* c1; uint32_t* c2;
-    uint32_t* v1; uint32_t* v2; int32_t* shift; uint32_t* stored1; uint32_t* stored2;
-    uint32_t* n_found;
-};
-
-// Inverted piles (-N; include/indelminer_amd.h, seam 5, "Inverted piles"): one wave per peak x of EITHER list, the waves below n_right
-// the right peaks, the others the left ones.  Its candidates are the run of the SAME list inside [x + min_len, x + max_len], found by
-// two binary searches; a peak without one ends there.  Entries are compared with the other strand, and backwards from the OTHER
-// peak: what depends on x alone is fetched once -- the complemented window at x (ref[x - 1 - lane] for right peaks, ref[x + lane]
-// for left ones) the entries of every partner are compared with, and the pile at x (tail_hold).  Per candidate: the complemented
-// window at y and v1(.) of the held pile; ONLY when some shift has v1 >= min_verified -- a candidate that has none cannot qualify --
-// the walk of the pile at y for v2(.), the chosen shift, the qualification.  A chance pair of peaks so costs one 64-byte load and one
-// shift loop.  The rare pair that qualifies takes its slot with one returning atomic by lane 0; n_found counts every pair, only slots
-// below cap are written.  Every branch is on values the whole wave shares.
-__global__ __launch_bounds__(kTailWaveBlock) void cliptail_inverted_kernel(TailInvertedArgs A)
-{
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    const int n_all = A.n_right + A.n_left;
+    const int n_all = kInverted ? A.n_right + A.n_left : A.n_right;
     for (int q = wave; q < n_all; q += nwaves) {
-        const bool left = q >= A.n_right;
-        const uint32_t side = left ? 1u : 0u;
+        const bool left = kInverted && q >= A.n_right;
+        const bool pleft = kInverted ? left : true;                 // the partners' list
+        const uint32_t side = left ? 1u : 0u, pside = pleft ? 1u : 0u;
         const int32_t* __restrict__ pos = left ? A.lpos : A.rpos;
         const uint32_t* __restrict__ cnt = left ? A.lcnt : A.rcnt;
-        const int32_t n = left ? A.n_left : A.n_right, at = left ? q - A.n_right : q;
-        const int64_t x = pos[at];
-        const int32_t k0 = first_at_or_behind(pos, n, x + (int64_t)A.min_len);
-        const int32_t k1 = first_at_or_behind(pos, n, x + (int64_t)A.max_len + 1);
+        const int32_t* __restrict__ ppos = pleft ? A.lpos : A.rpos;
+        const uint32_t* __restrict__ pcnt = pleft ? A.lcnt : A.rcnt;
+        const int32_t pn = pleft ? A.n_left : A.n_right, at = left ? q - A.n_right : q;
+        const int64_t p = pos[at];
+        const int32_t k0 = first_at_or_behind(ppos, pn, kInverted ? p + (int64_t)A.min_len : p - (int64_t)A.max_len);
+        const int32_t k1 = first_at_or_behind(ppos, pn, (kInverted ? p + (int64_t)A.max_len : p - (int64_t)A.min_len) + 1);
         if (k0 >= k1) continue;
-        // what the entries of every partner are expected to hold: the other strand, backwards from x
-        const TailWindow Wx = tail_complement(tail_window(A.ref, A.clen, left ? x + lane : x - 1 - lane));
-        const TailHeld H = tail_hold(A.tab, A.tid, x, side, A.clen, lane);
+        const TailWindow Wp = tail_expected_window(A.ref, A.clen, p, pside, kInverted, lane);
+        const TailHeld H = tail_hold(A.tab, A.tid, p, side, A.clen, lane);
         for (int32_t k = k0; k < k1; k++) {
-            const int64_t y = pos[k];
-            const TailWindow Wy = tail_complement(tail_window(A.ref, A.clen, left ? y + lane : y - 1 - lane));
-            const uint32_t v1 = tail_held_shifts(H, A.tab, A.tid, x, side, A.clen, Wy, A.max_shift, lane);
+            const int64_t o = ppos[k];
+            const TailWindow Wo = tail_expected_window(A.ref, A.clen, o, side, kInverted, lane);
+            const uint32_t v1 = tail_held_shifts(H, A.tab, A.tid, p, side, A.clen, Wo, A.max_shift, lane);
             if (!__ballot(lane <= A.max_shift && v1 >= (uint32_t)A.min_verified)) continue;     // the first cut: no trip to the table
             uint32_t v2;
-            const uint32_t s2 = tail_side(A.tab, A.tid, y, side, A.clen, Wx, true, A.max_shift, lane, &v2);
+            const uint32_t s2 = tail_side(A.tab, A.tid, o, pside, A.clen, Wp, true, A.max_shift, lane, &v2);
             int best;
             uint32_t b1, b2;
             const bool found = tail_best_shift(v1, v2, A.max_shift, lane, &best, &b1, &b2);
@@ -497,8 +439,8 @@ __global__ __launch_bounds__(kTailWaveBlock) void cliptail_inverted_kernel(TailI
             if (lane == 0) {
                 const uint32_t slot = atomicAdd(A.n_found, 1u);
                 if (slot < (uint32_t)A.cap) {
-                    A.side[slot] = side; A.p1[slot] = (int32_t)x; A.p2[slot] = (int32_t)y; A.c1[slot] = cnt[at]; A.c2[slot] = cnt[k];
-                    A.v1[slot] = b1; A.v2[slot] = b2; A.shift[slot] = best; A.stored1[slot] = H.stored; A.stored2[slot] = s2;
+                    A.col[0][slot] = side; A.col[1][slot] = (uint32_t)p; A.col[2][slot] = (uint32_t)o; A.col[3][slot] = cnt[at]; A.col[4][slot] = pcnt[k];
+                    A.col[5][slot] = b1; A.col[6][slot] = b2; A.col[7][slot] = (uint32_t)best; A.col[8][slot] = H.stored; A.col[9][slot] = s2;
                 }
             }
         }
@@ -580,41 +522,18 @@ hipError_t launch_cliptail_consensus(int32_t nq, int32_t tid, const int32_t* pos
     return hipGetLastError();
 }
 
-hipError_t launch_cliptail_cross(int32_t n_right, const int32_t* rpos, const uint32_t* rcnt, int32_t n_left, const int32_t* lpos, const uint32_t* lcnt,
-                                 int32_t tid, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, const uint8_t* ref,
-                                 int64_t clen, const TailTable& tab, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right,
-                                 uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, uint32_t* n_found, hipStream_t stream)
+hipError_t launch_cliptail_pairs(bool inverted, TailPairsArgs A, hipStream_t stream)
 {
-    hipError_t e = hipMemsetAsync(n_found, 0, sizeof(uint32_t), stream);
-    if (e != hipSuccess || n_right <= 0 || n_left <= 0) return e;
-    TailCrossArgs A;
-    A.n_right = n_right; A.n_left = n_left; A.tid = tid; A.rpos = rpos; A.rcnt = rcnt; A.lpos = lpos; A.lcnt = lcnt;
-    A.min_len = min_len; A.max_len = max_len; A.max_shift = max_shift; A.min_verified = min_verified; A.cap = cap;
-    A.ref = ref; A.clen = clen; A.tab = tab; A.pr = pr; A.pl = pl; A.cr = cr; A.cl = cl; A.v_right = v_right; A.v_left = v_left;
-    A.shift = shift; A.stored_right = stored_right; A.stored_left = stored_left; A.n_found = n_found;
-    int b = (n_right + 3) / 4;
+    hipError_t e = hipMemsetAsync(A.n_found, 0, sizeof(uint32_t), stream);
+    if (A.n_right < 0) A.n_right = 0;
+    if (A.n_left < 0) A.n_left = 0;
+    // crossed: a wave per right peak, and nothing to pair it with while the left list is empty; inverted: a wave per peak of either list
+    const int64_t waves = inverted ? (int64_t)A.n_right + A.n_left : A.n_left > 0 ? A.n_right : 0;
+    if (e != hipSuccess || waves == 0) return e;
+    int64_t b = (waves + 3) / 4;
     if (b > 2048) b = 2048;
-    hipLaunchKernelGGL(cliptail_cross_kernel, dim3(b), dim3(kTailWaveBlock), 0, stream, A);
-    return hipGetLastError();
-}
-
-hipError_t launch_cliptail_inverted(int32_t n_right, const int32_t* rpos, const uint32_t* rcnt, int32_t n_left, const int32_t* lpos, const uint32_t* lcnt,
-                                    int32_t tid, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, const uint8_t* ref,
-                                    int64_t clen, const TailTable& tab, uint32_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1,
-                                    uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2, uint32_t* n_found, hipStream_t stream)
-{
-    hipError_t e = hipMemsetAsync(n_found, 0, sizeof(uint32_t), stream);
-    if (n_right < 0) n_right = 0;
-    if (n_left < 0) n_left = 0;
-    if (e != hipSuccess || n_right + n_left == 0) return e;
-    TailInvertedArgs A;
-    A.n_right = n_right; A.n_left = n_left; A.tid = tid; A.rpos = rpos; A.rcnt = rcnt; A.lpos = lpos; A.lcnt = lcnt;
-    A.min_len = min_len; A.max_len = max_len; A.max_shift = max_shift; A.min_verified = min_verified; A.cap = cap;
-    A.ref = ref; A.clen = clen; A.tab = tab; A.side = side; A.p1 = p1; A.p2 = p2; A.c1 = c1; A.c2 = c2; A.v1 = v1; A.v2 = v2;
-    A.shift = shift; A.stored1 = stored1; A.stored2 = stored2; A.n_found = n_found;
-    int64_t b = ((int64_t)n_right + n_left + 3) / 4;
-    if (b > 2048) b = 2048;
-    hipLaunchKernelGGL(cliptail_inverted_kernel, dim3((unsigned)b), dim3(kTailWaveBlock), 0, stream, A);
+    if (inverted) hipLaunchKernelGGL(cliptail_pairs_kernel<true>, dim3((unsigned)b), dim3(kTailWaveBlock), 0, stream, A);
+    else hipLaunchKernelGGL(cliptail_pairs_kernel<false>, dim3((unsigned)b), dim3(kTailWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 

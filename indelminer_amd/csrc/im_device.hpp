@@ -157,21 +157,26 @@ hipError_t launch_cliptail_verify(int32_t nq, int32_t tid, const int32_t* pr, co
 // consensus as two planes (planes[2 q], planes[2 q + 1]) and the entries that agree with it; a position outside [0, clen] answers zeros
 hipError_t launch_cliptail_consensus(int32_t nq, int32_t tid, const int32_t* pos, const uint8_t* side, int32_t min_cover, int64_t clen,
                                      const TailTable& tab, uint32_t* entries, uint32_t* len, uint32_t* planes, uint32_t* agree, hipStream_t stream);
-// crossed piles: the pairs (pr of the right peaks, pl of the left peaks; both lists ascending) with min_len <= pr - pl <= max_len whose
-// entries verify (at least min_verified on either side at the chosen shift); *n_found (cleared here) counts them all, the first cap
-// that take a slot are written, in no particular order
-hipError_t launch_cliptail_cross(int32_t n_right, const int32_t* rpos, const uint32_t* rcnt, int32_t n_left, const int32_t* lpos, const uint32_t* lcnt,
-                                 int32_t tid, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, const uint8_t* ref,
-                                 int64_t clen, const TailTable& tab, int32_t* pr, int32_t* pl, uint32_t* cr, uint32_t* cl, uint32_t* v_right,
-                                 uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left, uint32_t* n_found, hipStream_t stream);
-// inverted piles: the pairs x < y of ONE list (side 0: the right peaks, 1: the left peaks; both lists ascending) with
-// min_len <= y - x <= max_len whose entries verify against the reference's reverse complement (at least min_verified at either peak
-// at the chosen shift); one launch for both lists, none when both are empty; *n_found (cleared here) counts them all, the first cap
-// that take a slot are written, in no particular order
-hipError_t launch_cliptail_inverted(int32_t n_right, const int32_t* rpos, const uint32_t* rcnt, int32_t n_left, const int32_t* lpos, const uint32_t* lcnt,
-                                    int32_t tid, int32_t min_len, int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, const uint8_t* ref,
-                                    int64_t clen, const TailTable& tab, uint32_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1,
-                                    uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2, uint32_t* n_found, hipStream_t stream);
+// Pairs of piles whose entries verify: at least min_verified at either pile at the chosen shift 0 .. max_shift <= 32.  Both peak lists
+// are ascending.  Crossed (-U): p1 of the right peaks, p2 of the left peaks, min_len <= p1 - p2 <= max_len, against the reference
+// behind the other pile; nothing is launched while either list is empty.  Inverted (-N): p1 < p2 of ONE list (side 0: the right peaks,
+// 1: the left peaks), min_len <= p2 - p1 <= max_len, against the reference's reverse complement; one launch for both lists, none when
+// both are empty.  *n_found (cleared by the launch) counts every pair; the first cap that take a slot are written, in no particular
+// order, into ten columns: side (0 for crossed), p1, p2, their counts, v1, v2, shift, stored at p1, stored at p2.
+struct TailPairsArgs {
+    int32_t n_right, n_left, tid;
+    const int32_t* rpos;        // the peaks of clipR, ascending, and their counts
+    const uint32_t* rcnt;
+    const int32_t* lpos;        // the peaks of clipL, ascending, and their counts
+    const uint32_t* lcnt;
+    int32_t min_len, max_len, max_shift, min_verified, cap;
+    const uint8_t* ref;         // the contig's ASCII bases
+    int64_t clen;
+    TailTable tab;
+    uint32_t* col[10];
+    uint32_t* n_found;
+};
+hipError_t launch_cliptail_pairs(bool inverted, TailPairsArgs A, hipStream_t stream);
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);

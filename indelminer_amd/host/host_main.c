@@ -63,6 +63,13 @@ static void print_help(FILE* file)
 
 static void free_range(void* p) { free(p); }
 
+/* the evidence FILEs, in the order they are written on the pipelined path, and per contig on the record-at-a-time path */
+static evfile g_evidence[3] = {
+    {&g_ins_file, NULL, ins_describe, ins_contig, "large-insertion evidence (device)"},
+    {&g_dup_file, NULL, dup_describe, dup_contig, "tandem-duplication evidence (device)"},
+    {&g_inv_file, NULL, inv_describe, inv_contig, "inversion evidence (device)"},
+};
+
 int main(int argc, char** argv)
 {
     t_is_main = 1;
@@ -364,33 +371,17 @@ int main(int argc, char** argv)
         }
         if (chromid == -1) run_contig(&d, i, 0, d.hdr->target_len[i], r);
         else run_contig(&d, i, chromstart, chromstop, r);
-        if (FACING_ON) ins_contig(&d, i);            /* -I, record-at-a-time: behind the contig's flushes, on the arrays of its im_clip_build */
-        if (CROSSED_ON) dup_contig(&d, i);           /* -U: the same place, the same arrays */
-        if (INVERTED_ON) inv_contig(&d, i);          /* -N: the same place, the same arrays */
+        /* -I, -U, -N, record-at-a-time: behind the contig's flushes, on the arrays of its im_clip_build */
+        for (int e = 0; e < 3; e++) if (*g_evidence[e].path) ev_contig(&g_evidence[e], &d, i);
     }
 
     gpu_wait(&d);
-    if (FACING_ON) {
-        /* -I, pipelined: once, now that the last flush has printed and every scatter has completed; the genome-wide arrays were never
-         * reset and the table is keyed by contig */
-        for (int32_t i = 0; i < d.hdr->n_targets && use_pipeline; i++) ins_contig(&d, i);
-        if (!g_ins_out) ins_open();                 /* no contig at all: the header alone */
-        if (fclose(g_ins_out) != 0) fatalf("cannot write %s", g_ins_file);
-        g_ins_out = NULL;
-    }
-    if (CROSSED_ON) {
-        /* -U: as -I, once on the pipelined path */
-        for (int32_t i = 0; i < d.hdr->n_targets && use_pipeline; i++) dup_contig(&d, i);
-        if (!g_dup_out) dup_open();                 /* no contig at all: the header alone */
-        if (fclose(g_dup_out) != 0) fatalf("cannot write %s", g_dup_file);
-        g_dup_out = NULL;
-    }
-    if (INVERTED_ON) {
-        /* -N: as -I and -U, once on the pipelined path */
-        for (int32_t i = 0; i < d.hdr->n_targets && use_pipeline; i++) inv_contig(&d, i);
-        if (!g_inv_out) inv_open();                 /* no contig at all: the header alone */
-        if (fclose(g_inv_out) != 0) fatalf("cannot write %s", g_inv_file);
-        g_inv_out = NULL;
+    for (int e = 0; e < 3; e++) {
+        /* -I, then -U, then -N, pipelined: once, now that the last flush has printed and every scatter has completed; the genome-wide
+         * arrays were never reset and the table is keyed by contig */
+        if (!*g_evidence[e].path) continue;
+        for (int32_t i = 0; i < d.hdr->n_targets && use_pipeline; i++) ev_contig(&g_evidence[e], &d, i);
+        ev_finish(&g_evidence[e]);
     }
     if (CLIPTAIL_ON) {
         /* -V: a table that overflowed has answered nothing since; said once, here */

@@ -423,15 +423,43 @@ static void clip_events(driver* d, const bam_record* b)
     }
 }
 
-/* -I: FILE, opened when the first contig is about to be searched (a run handed to the record-at-a-time child never gets here in the
- * parent: the child writes the file) */
-static FILE* g_ins_out = NULL;
-static void ins_open(void)
+/* An evidence FILE (-I, -U, -N): opened when its first contig is about to be searched (a run handed to the record-at-a-time child
+ * never gets here in the parent: the child writes the file), finished when the last has been -- or with the header alone. */
+typedef struct evfile {
+    const char* const* path; FILE* out;                 /* the option's argument (NULL: not given), the file once it is open */
+    void (*describe)(FILE* f);                          /* the ##ALT, ##INFO and description lines */
+    void (*contig)(driver* d, int32_t tid, FILE* f);    /* one contig's records */
+    const char* phase;
+} evfile;
+
+static FILE* ev_open(evfile* e)
 {
-    g_ins_out = fopen(g_ins_file, "w");
-    if (!g_ins_out) fatalf("cannot write %s", g_ins_file);
-    FILE* f = g_ins_out;
-    fprintf(f, "##fileformat=VCFv4.1\n");
+    if (e->out) return e->out;
+    e->out = fopen(*e->path, "w");
+    if (!e->out) fatalf("cannot write %s", *e->path);
+    fprintf(e->out, "##fileformat=VCFv4.1\n");
+    e->describe(e->out);
+    fprintf(e->out, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
+    return e->out;
+}
+
+/* one contig, whose every record the clip arrays and the table hold: behind the last flush (pipelined) or the contig's (record-at-a-time) */
+static void ev_contig(evfile* e, driver* d, int32_t tid)
+{
+    FILE* f = ev_open(e);
+    gpu_wait(d);
+    e->contig(d, tid, f);
+    phase_time(e->phase);
+}
+
+static void ev_finish(evfile* e)
+{
+    if (fclose(ev_open(e)) != 0) fatalf("cannot write %s", *e->path);     /* no contig at all: the header alone */
+    e->out = NULL;
+}
+
+static void ins_describe(FILE* f)
+{
     fprintf(f, "##ALT=<ID=INS,Description=\"Insertion too long for a read to span: clipped reads from either side face each other\">\n");
     fprintf(f, "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n");
     fprintf(f, "##INFO=<ID=END,Number=1,Type=Integer,Description=\"Where the reads from the left stop aligning (POS: where the reads from the right start)\">\n");
@@ -447,7 +475,6 @@ static void ins_open(void)
                "clipped bases per read (A before C before G before T among equals), as far as at least %d reads reach; CA: reads with at most 1 difference "
                "in 16 from it; CN, CA, LSEQ and RSEQ are . once the clip-tail table has overflowed (stderr says so); contig ends are skipped\"\n",
             INS_EV_MIN_READS, CLIP_EV_MIN_CLIP, INS_EV_MAX_OVERLAP, INS_EV_MAX_OVERLAP, INS_EV_MIN_READS, INS_EV_MAX_OVERLAP, INS_EV_MIN_COVER);
-    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
 }
 
 /* the consensus of one pile as text: base 0 first, or (the left pile, turned back to reference orientation) base len - 1 first */
@@ -461,12 +488,9 @@ static void ins_seq(char* out, uint32_t len, uint32_t lo, uint32_t hi, int rever
     out[len] = 0;
 }
 
-/* -I: one contig's facing piles and the consensus of either pile, into FILE.  The clip arrays and the table hold every record of the
- * contig: the pipelined path comes here when the last flush has printed, the record-at-a-time path behind the contig's flushes. */
-static void ins_contig(driver* d, int32_t tid)
+/* -I: one contig's facing piles and the consensus of either pile, into FILE */
+static void ins_contig(driver* d, int32_t tid, FILE* f)
 {
-    if (!g_ins_out) ins_open();
-    gpu_wait(d);
     const int64_t clen = d->seqlen[tid];
     int32_t cap = 65536, found = 0;
     int32_t* pr = NULL; int32_t* pl = NULL; uint32_t* cr = NULL; uint32_t* cl = NULL;
@@ -495,29 +519,22 @@ static void ins_contig(driver* d, int32_t tid)
             fatalf("im_cliptail_consensus: %s", im_last_error(d->gpu));
         const char* seq = d->sequences[tid];
         for (int32_t k = 0; k < n; k++) {
-            fprintf(g_ins_out, "%s\t%d\t.\t%c\t<INS>\t.\t.\tSVTYPE=INS;END=%d;HOMLEN=%d;CR=%u,%u;", d->hdr->target_name[tid], pl[k],
+            fprintf(f, "%s\t%d\t.\t%c\t<INS>\t.\t.\tSVTYPE=INS;END=%d;HOMLEN=%d;CR=%u,%u;", d->hdr->target_name[tid], pl[k],
                     toupper((unsigned char)seq[pl[k] - 1]), pr[k], pr[k] - pl[k], cr[k], cl[k]);
-            if (ent[2 * k] == CLIPTAIL_NONE) { fprintf(g_ins_out, "CN=.;CA=.;LSEQ=.;RSEQ=.\n"); continue; }
+            if (ent[2 * k] == CLIPTAIL_NONE) { fprintf(f, "CN=.;CA=.;LSEQ=.;RSEQ=.\n"); continue; }
             char ls[CLIPTAIL_BASES + 1], rs[CLIPTAIL_BASES + 1];
             ins_seq(ls, len[2 * k], planes[4 * k], planes[4 * k + 1], 0);
             ins_seq(rs, len[2 * k + 1], planes[4 * k + 2], planes[4 * k + 3], 1);
-            fprintf(g_ins_out, "CN=%u,%u;CA=%u,%u;LSEQ=%s;RSEQ=%s\n", ent[2 * k], ent[2 * k + 1], agree[2 * k], agree[2 * k + 1], ls, rs);
+            fprintf(f, "CN=%u,%u;CA=%u,%u;LSEQ=%s;RSEQ=%s\n", ent[2 * k], ent[2 * k + 1], agree[2 * k], agree[2 * k + 1], ls, rs);
         }
         free(qpos); free(qside); free(ans);
     }
     pthread_mutex_unlock(&g_query_mu);
     free(pr); free(pl); free(cr); free(cl);
-    phase_time("large-insertion evidence (device)");
 }
 
-/* -U: FILE, opened when the first contig is about to be searched (as -I's: the record-at-a-time child writes it, not its parent) */
-static FILE* g_dup_out = NULL;
-static void dup_open(void)
+static void dup_describe(FILE* f)
 {
-    g_dup_out = fopen(g_dup_file, "w");
-    if (!g_dup_out) fatalf("cannot write %s", g_dup_file);
-    FILE* f = g_dup_out;
-    fprintf(f, "##fileformat=VCFv4.1\n");
     fprintf(f, "##ALT=<ID=DUP:TANDEM,Description=\"Tandem duplication: reads clipped at its end continue at its start\">\n");
     fprintf(f, "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n");
     fprintf(f, "##INFO=<ID=END,Number=1,Type=Integer,Description=\"Last duplicated base: where the reads from the left stop aligning (POS + 1: the first, where the reads from the right start)\">\n");
@@ -537,33 +554,41 @@ static void dup_open(void)
                "clipped bases per read with at most 1 difference in 16 (HOMLEN: the s with the most such reads, the smallest among equals; CV: those reads); "
                "the file has no records once the clip-tail table has overflowed (stderr says so); POS 0 is skipped\"\n",
             DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, DUP_EV_MIN_READS, CLIP_EV_MIN_CLIP, DUP_EV_REACH, DUP_EV_REACH, CLIPTAIL_MAX_SHIFT, DUP_EV_MIN_VERIFIED, DUP_EV_MIN_VERIFIED);
-    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
 }
 
-/* -U: one contig's crossed piles into FILE, where ins_contig is called and for the same reason: the clip arrays and the table hold
- * every record of the contig.  With -D the contig's scanned depth array is resident as well -- the genome-wide array is scanned
- * contig by contig as the walk leaves each (im_depth_scan) and never reset, the record-at-a-time path has built this contig's. */
-static void dup_contig(driver* d, int32_t tid)
+/* The pairs of piles of one contig, crossed (-U) or inverted (-N).  Columns of cap: pos = p1 p2 shift | cnt = c1 c2 v1 v2 stored at p1,
+ * stored at p2 | side (inverted alone).  found < 0: the table has overflowed, the header alone. */
+typedef struct pile_pairs { int32_t cap, found; int32_t* pos; uint32_t* cnt; uint8_t* side; } pile_pairs;
+
+static pile_pairs pile_pairs_query(driver* d, int32_t tid, int inverted)
 {
-    if (!g_dup_out) dup_open();
-    gpu_wait(d);
-    int32_t cap = 4096, found = 0;
-    int32_t* pos = NULL; uint32_t* cnt = NULL;
+    pile_pairs P = {4096, 0, NULL, NULL, NULL};
     pthread_mutex_lock(&g_query_mu);
-    for (;;) {
-        /* pr pl shift | cr cl vR vL stored right, stored left */
-        pos = xrealloc(pos, sizeof(int32_t) * 3 * (size_t)cap); cnt = xrealloc(cnt, sizeof(uint32_t) * 6 * (size_t)cap);
-        int32_t* pr = pos; int32_t* pl = pos + cap; int32_t* sh = pos + 2 * cap;
-        const int rc = d->pipe_mode
-            ? im_clip_crossed_tid(d->gpu, tid, DUP_EV_MIN_READS, DUP_EV_REACH, DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT, DUP_EV_MIN_VERIFIED, cap,
-                                  pr, pl, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, sh, cnt + 4 * cap, cnt + 5 * cap, &found)
-            : im_clip_crossed(d->gpu, tid, DUP_EV_MIN_READS, DUP_EV_REACH, DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT, DUP_EV_MIN_VERIFIED, cap,
-                              pr, pl, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, sh, cnt + 4 * cap, cnt + 5 * cap, &found);
-        if (rc != IM_OK) fatalf("im_clip_crossed: %s", im_last_error(d->gpu));
-        if (found <= cap) break;
-        cap = found;                /* more pairs than asked for: once more, with room for all */
+    for (;; P.cap = P.found) {      /* more pairs than asked for: once more, with room for all */
+        const int32_t cap = P.cap;
+        int32_t* pos = P.pos = xrealloc(P.pos, sizeof(int32_t) * 3 * (size_t)cap);
+        uint32_t* cnt = P.cnt = xrealloc(P.cnt, sizeof(uint32_t) * 6 * (size_t)cap);
+        if (inverted) P.side = xrealloc(P.side, (size_t)cap);
+        const int rc = inverted
+            ? (d->pipe_mode ? im_clip_inverted_tid : im_clip_inverted)(d->gpu, tid, INV_EV_MIN_READS, INV_EV_REACH, INV_EV_MIN_LEN, INV_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT,
+                  INV_EV_MIN_VERIFIED, cap, P.side, pos, pos + cap, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, pos + 2 * cap, cnt + 4 * cap, cnt + 5 * cap, &P.found)
+            : (d->pipe_mode ? im_clip_crossed_tid : im_clip_crossed)(d->gpu, tid, DUP_EV_MIN_READS, DUP_EV_REACH, DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT,
+                  DUP_EV_MIN_VERIFIED, cap, pos, pos + cap, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, pos + 2 * cap, cnt + 4 * cap, cnt + 5 * cap, &P.found);
+        if (rc != IM_OK) fatalf("%s: %s", inverted ? "im_clip_inverted" : "im_clip_crossed", im_last_error(d->gpu));
+        if (P.found <= cap) break;
     }
-    /* found < 0: the table has overflowed, the header alone */
+    pthread_mutex_unlock(&g_query_mu);
+    return P;
+}
+
+/* -U: one contig's crossed piles into FILE.  With -D the contig's scanned depth array is resident as well -- the genome-wide array is
+ * scanned contig by contig as the walk leaves each (im_depth_scan) and never reset, the record-at-a-time path has built this contig's.
+ * g_query_mu is taken again for the depth queries: the pairs are on the host by then, so nothing needs it held in between. */
+static void dup_contig(driver* d, int32_t tid, FILE* f)
+{
+    pile_pairs P = pile_pairs_query(d, tid, 0);
+    const int32_t cap = P.cap, found = P.found;
+    const int32_t* pos = P.pos; const uint32_t* cnt = P.cnt;
     uint32_t* med = NULL;
     if (found > 0 && g_depth_evidence) {
         /* three queries per pair: the duplicated bases [pl, pr) and DEPTH_EV_FLANK bases on either side (the device clips to the contig) */
@@ -575,33 +600,27 @@ static void dup_contig(driver* d, int32_t tid)
             beg[3 * k + 1] = pl - DEPTH_EV_FLANK; end[3 * k + 1] = pl;
             beg[3 * k + 2] = pr; end[3 * k + 2] = (int32_t)((int64_t)pr + DEPTH_EV_FLANK > INT32_MAX ? INT32_MAX : pr + DEPTH_EV_FLANK);
         }
+        pthread_mutex_lock(&g_query_mu);
         const int qrc = d->pipe_mode ? im_depth_median_tid(d->gpu, tid, 3 * found, beg, end, med) : im_depth_median(d->gpu, 3 * found, beg, end, med);
+        pthread_mutex_unlock(&g_query_mu);
         if (qrc != IM_OK) fatalf("im_depth_median: %s", im_last_error(d->gpu));
         free(beg);
     }
-    pthread_mutex_unlock(&g_query_mu);
     const char* seq = d->sequences[tid];
     for (int32_t k = 0; k < found; k++) {
         const int32_t pr = pos[k], pl = pos[cap + k];
         if (pl == 0) continue;      /* nothing in front to anchor on */
-        fprintf(g_dup_out, "%s\t%d\t.\t%c\t<DUP:TANDEM>\t.\t.\tSVTYPE=DUP;END=%d;SVLEN=%d;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u", d->hdr->target_name[tid], pl,
+        fprintf(f, "%s\t%d\t.\t%c\t<DUP:TANDEM>\t.\t.\tSVTYPE=DUP;END=%d;SVLEN=%d;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u", d->hdr->target_name[tid], pl,
                 toupper((unsigned char)seq[pl - 1]), pr, pr - pl, pos[2 * cap + k], cnt[k], cnt[cap + k], cnt[4 * cap + k], cnt[5 * cap + k],
                 cnt[2 * cap + k], cnt[3 * cap + k]);
-        if (med) fprint_depth_values(g_dup_out, med + 3 * k, ";DM=", ";DFC=");
-        fprintf(g_dup_out, "\n");
+        if (med) fprint_depth_values(f, med + 3 * k, ";DM=", ";DFC=");
+        fprintf(f, "\n");
     }
-    free(med); free(pos); free(cnt);
-    phase_time("tandem-duplication evidence (device)");
+    free(med); free(P.pos); free(P.cnt);
 }
 
-/* -N: FILE, opened when the first contig is about to be searched (as -I's and -U's: the record-at-a-time child writes it, not its parent) */
-static FILE* g_inv_out = NULL;
-static void inv_open(void)
+static void inv_describe(FILE* f)
 {
-    g_inv_out = fopen(g_inv_file, "w");
-    if (!g_inv_out) fatalf("cannot write %s", g_inv_file);
-    FILE* f = g_inv_out;
-    fprintf(f, "##fileformat=VCFv4.1\n");
     fprintf(f, "##ALT=<ID=INV,Description=\"Inversion breakpoint: reads clipped on one side at POS and at END continue on the other strand at each other\">\n");
     fprintf(f, "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n");
     fprintf(f, "##INFO=<ID=END,Number=1,Type=Integer,Description=\"The second pile of clipped reads (POS: the first)\">\n");
@@ -619,43 +638,23 @@ static void inv_open(void)
                "equals; CV: those reads); the two junctions of an inversion are two records; the file has no records once the clip-tail table has overflowed "
                "(stderr says so); POS 0 is skipped\"\n",
             INV_EV_MIN_LEN, INV_EV_MAX_LEN, INV_EV_MIN_READS, CLIP_EV_MIN_CLIP, INV_EV_REACH, INV_EV_REACH, CLIPTAIL_MAX_SHIFT, INV_EV_MIN_VERIFIED, INV_EV_MIN_VERIFIED);
-    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
 }
 
-/* -N: one contig's inverted piles into FILE, where dup_contig is called and for the same reason.  No depth fields with -D: an inversion
- * changes no depth. */
-static void inv_contig(driver* d, int32_t tid)
+/* -N: one contig's inverted piles into FILE.  No depth fields with -D: an inversion changes no depth. */
+static void inv_contig(driver* d, int32_t tid, FILE* f)
 {
-    if (!g_inv_out) inv_open();
-    gpu_wait(d);
-    int32_t cap = 4096, found = 0;
-    int32_t* pos = NULL; uint32_t* cnt = NULL; uint8_t* side = NULL;
-    pthread_mutex_lock(&g_query_mu);
-    for (;;) {
-        /* x y shift | c1 c2 v1 v2 stored at x, stored at y | side */
-        pos = xrealloc(pos, sizeof(int32_t) * 3 * (size_t)cap); cnt = xrealloc(cnt, sizeof(uint32_t) * 6 * (size_t)cap); side = xrealloc(side, (size_t)cap);
-        int32_t* x = pos; int32_t* y = pos + cap; int32_t* sh = pos + 2 * cap;
-        const int rc = d->pipe_mode
-            ? im_clip_inverted_tid(d->gpu, tid, INV_EV_MIN_READS, INV_EV_REACH, INV_EV_MIN_LEN, INV_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT, INV_EV_MIN_VERIFIED, cap,
-                                   side, x, y, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, sh, cnt + 4 * cap, cnt + 5 * cap, &found)
-            : im_clip_inverted(d->gpu, tid, INV_EV_MIN_READS, INV_EV_REACH, INV_EV_MIN_LEN, INV_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT, INV_EV_MIN_VERIFIED, cap,
-                               side, x, y, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, sh, cnt + 4 * cap, cnt + 5 * cap, &found);
-        if (rc != IM_OK) fatalf("im_clip_inverted: %s", im_last_error(d->gpu));
-        if (found <= cap) break;
-        cap = found;                /* more pairs than asked for: once more, with room for all */
-    }
-    pthread_mutex_unlock(&g_query_mu);
-    /* found < 0: the table has overflowed, the header alone */
+    pile_pairs P = pile_pairs_query(d, tid, 1);
+    const int32_t cap = P.cap;
+    const int32_t* pos = P.pos; const uint32_t* cnt = P.cnt;
     const char* seq = d->sequences[tid];
-    for (int32_t k = 0; k < found; k++) {
+    for (int32_t k = 0; k < P.found; k++) {
         const int32_t x = pos[k], y = pos[cap + k];
         if (x == 0) continue;       /* nothing in front to anchor on */
-        fprintf(g_inv_out, "%s\t%d\t.\t%c\t<INV>\t.\t.\tSVTYPE=INV;END=%d;SVLEN=%d;CT=%s;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u\n", d->hdr->target_name[tid], x,
-                toupper((unsigned char)seq[x - 1]), y, y - x, side[k] ? "5to5" : "3to3", pos[2 * cap + k], cnt[k], cnt[cap + k], cnt[4 * cap + k],
+        fprintf(f, "%s\t%d\t.\t%c\t<INV>\t.\t.\tSVTYPE=INV;END=%d;SVLEN=%d;CT=%s;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u\n", d->hdr->target_name[tid], x,
+                toupper((unsigned char)seq[x - 1]), y, y - x, P.side[k] ? "5to5" : "3to3", pos[2 * cap + k], cnt[k], cnt[cap + k], cnt[4 * cap + k],
                 cnt[5 * cap + k], cnt[2 * cap + k], cnt[3 * cap + k]);
     }
-    free(pos); free(cnt); free(side);
-    phase_time("inversion evidence (device)");
+    free(P.pos); free(P.cnt); free(P.side);
 }
 
 static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_reader* r)

@@ -180,7 +180,6 @@ static const char* g_ins_file = NULL;
 extern int im_clip_facing_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
 extern int im_clip_facing(im_ctx*, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
 extern int im_cliptail_consensus(im_ctx*, int32_t, int32_t, const int32_t*, const uint8_t*, int32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*) __attribute__((weak));
-#define FACING_ON (g_ins_file != NULL)             /* the run ends (a contig ends) with the search of the clip arrays */
 #define FACING_API_PRESENT (im_clip_facing_tid && im_clip_facing && im_cliptail_consensus)
 #define INS_EV_MIN_READS 3         /* clipped reads of the smaller pile */
 #define INS_EV_MAX_OVERLAP 30      /* bases the left-clip pile may stand in front of the right-clip pile: below DEPTH_EV_MIN_LEN, so the two
@@ -198,7 +197,6 @@ extern int im_clip_crossed_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int3
                                uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
 extern int im_clip_crossed(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*,
                            uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
-#define CROSSED_ON (g_dup_file != NULL)            /* the run ends (a contig ends) with the search for crossed piles */
 #define CROSSED_API_PRESENT (im_clip_peaks_tid && im_clip_peaks && im_clip_crossed_tid && im_clip_crossed)
 #define DUP_EV_MIN_READS 3         /* clipped reads of the smaller pile */
 #define DUP_EV_REACH 30            /* the reach of a peak: the peaks -I sees */
@@ -216,7 +214,6 @@ extern int im_clip_inverted_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int
                                 uint32_t*, uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
 extern int im_clip_inverted(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint8_t*, int32_t*, int32_t*, uint32_t*,
                             uint32_t*, uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
-#define INVERTED_ON (g_inv_file != NULL)           /* the run ends (a contig ends) with the search for inverted piles */
 #define INVERTED_API_PRESENT (im_clip_inverted_tid && im_clip_inverted)
 #define INV_EV_MIN_READS 3         /* clipped reads of the smaller pile */
 #define INV_EV_REACH 30            /* the reach of a peak: the peaks -I and -U see */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""clip_peaks_kernel (-U, im_span.hip) over both arrays of one contig next to clip_facing_kernel on the same contig, cliptail_cross_kernel's
+"""clip_peaks_kernel (-U, im_span.hip) over both arrays of one contig next to clip_facing_kernel on the same contig, cliptail_pairs_kernel<false>'s
 time per candidate next to cliptail_verify_kernel's time per query, and the product with -G -C -V -U next to -G -C -V.
 
 Peaks: one contig of --positions (64 M) positions whose two clip arrays get the clip events of the configs[1] chunk (synth seed 1, 1 Mb at

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""cliptail_inverted_kernel's time per candidate (-N, im_cliptail.hip) next to cliptail_cross_kernel's in the same process, and the product
+"""cliptail_pairs_kernel<true>'s time per candidate (-N, im_cliptail.hip) next to cliptail_pairs_kernel<false>'s in the same process, and the product
 with -G -C -V -N next to -G -C -V.
 
 Launch: the arrays and the table of the configs[1] chunk (synth seed 1, 1 Mb at 30x, clips of >= 20 bases; im_dev_clip_scatter,

@@ -1,5 +1,5 @@
 """Tandem duplications from crossed clip piles (-U): the peaks pass of im_span.hip's clip_peaks_kernel, the candidate enumeration and
-verification of im_cliptail.hip's cliptail_cross_kernel, and what the host driver makes of them (-U FILE).
+verification of im_cliptail.hip's cliptail_pairs_kernel<false>, and what the host driver makes of them (-U FILE).
 
 The yardstick is the plain restatement in tests/support/crossedpiles.py, written from the definition in include/indelminer_amd.h (seam 5,
 "Crossed piles"), not from the code under test; tests/test_crossed_host.py pins it to cases worked by hand.  Every answer is compared
@@ -227,6 +227,18 @@ class Scenario:
         dup(70, 0, tid=0, n=32); self.known[(0, 70)] = [(0, 3, 3, 3, 3, 0)]
         # a pair on contig 1 with the positions of a pair on contig 0: the table is keyed by contig
         dup(3_200, 3_000, tid=1); self.known[(1, 3_200)] = [(3_000, 3, 3, 3, 3, 0)]
+        # the cut in front of the partner's walk: a right pile that reaches min_verified at no shift ends the pair before the left pile is
+        # read (cut: {name: pr}, every left pile 150 in front).  One right entry continues at pl, three are somebody else's bases, the
+        # left pile is good ...
+        self.cut = {}
+        foreign = lambda n, at: [codes(self.refs[0], at + 40 * i, 30) for i in range(n)]
+        p = self.cut["none"] = next(at); dup(p, p - 150, nr=1, nl=4); self.add_right(p, foreign(3, 777)); self.known[(0, p)] = []
+        # ... the right pile reaches it at shift 5 only and the left pile at shift 0 only: the cut passes, no shift serves both ...
+        p = self.cut["no common shift"] = next(at); dup(p, p - 150, nr=3, nl=4, sr=5, sl=0); self.known[(0, p)] = []
+        # ... a right pile of 65 entries, more than one batch of the walk, of which one verifies: the cut on the walked path ...
+        p = self.cut["walked, one short"] = next(at); dup(p, p - 150, nr=1, nl=3); self.add_right(p, foreign(64, 5_555)); self.known[(0, p)] = []
+        # ... and such a pile of which two verify, beside 63 of somebody else's: the cut passes on the walked path, and the pair stands
+        p = self.cut["walked, enough"] = next(at); dup(p, p - 150, nr=2, nl=3); self.add_right(p, foreign(63, 9_999)); self.known[(0, p)] = [(p - 150, 65, 3, 2, 3, 0)]
 
     def dup(self, pr, pl, tid=0, nr=3, nl=3, sr=0, sl=0, n=30, mixed=False):
         ref = self.refs[tid]
@@ -238,6 +250,10 @@ class Scenario:
         self.L[tid][pl] += len(entries)
         self.table[(tid, LEFT, pl)] += entries
 
+    def add_right(self, pr, entries, tid=0):
+        self.R[tid][pr] += len(entries)
+        self.table[(tid, RIGHT, pr)] += entries
+
 
 @pytest.fixture(scope="module")
 def scenario():
@@ -248,6 +264,17 @@ def scenario():
         for (t, pr), rows in sc.known.items():
             if t == tid:
                 assert [w[1:7] for w in want if w[0] == pr] == rows, (t, pr, [w for w in want if w[0] == pr], rows)
+    # the cut's sites are candidates under PAR -- both piles are peaks -- and v(.) of the held right pile is what each site says it is
+    m, T, _, _, S, mv = PAR
+    code, peaks_r, peaks_l = ct.ref_codes(sc.refs[0]), dict(cp.peaks_many(sc.R[0], m, T)), dict(cp.peaks_many(sc.L[0], m, T))
+    reach = {"none": [], "no common shift": [5], "walked, one short": [], "walked, enough": [0]}
+    for name, pr in sc.cut.items():
+        assert pr in peaks_r and pr - 150 in peaks_l, name
+        v1 = cp.shift_counts(sc.table[(0, RIGHT, pr)], code, pr - 150, 1, S)
+        assert [s for s in range(S + 1) if v1[s] >= mv] == reach[name], (name, list(v1))
+        assert (len(sc.table[(0, RIGHT, pr)]) > 64) == name.startswith("walked"), name          # more than one batch of 64 slots
+    v2 = cp.shift_counts(sc.table[(0, LEFT, sc.cut["no common shift"] - 150)], code, sc.cut["no common shift"] - 1, -1, S)
+    assert [s for s in range(S + 1) if v2[s] >= mv] == [0]
     return sc
 
 
@@ -270,7 +297,7 @@ def test_crossed_pairs_made_by_hand(scenario):
         dev.add({k: v for k, v in table.items() if k != (0, RIGHT, sc.foreign_at)})
         table[(0, foreign[0], foreign[1])] = table.get((0, foreign[0], foreign[1]), []) + theirs
         assert dev.ctx.cliptail_stats() == (sum(len(v) for v in table.values()), 0)
-        total = check_crossed(dev, sc.R, sc.L, table, PAR, at_least=19)
+        total = check_crossed(dev, sc.R, sc.L, table, PAR, at_least=20)         # 19, and the one pair of the cut's sites
         for tid in range(3):
             got = crossed_of(dev, tid, PAR)
             for (t, pr), rows in sc.known.items():
@@ -302,6 +329,51 @@ def test_crossed_pairs_made_by_hand(scenario):
             assert lib.im_clip_crossed(dev.ctx.h, other, *PAR, 4, *[ptr(o) for o in out], C.byref(found)) != 0 and b"are not contig" in lib.im_last_error(dev.ctx.h)
     finally:
         dev.close()
+
+
+def test_crossed_more_peaks_than_waves():
+    """a contig of 20 000 positions, R 1 on every even position and L 1 on every odd one, m = 1, T = 0, distances 1 .. 5: 10 000 right
+    peaks on a grid that is capped at 8 192 waves, two or three partners each; some dozens of planted duplications among them, a third
+    with a second partner at shift 2, and many behind the 8 192nd right peak, which only the second round of the grid's loop reaches"""
+    from indelminer_amd import capi
+    clen = 20_000
+    rng = np.random.default_rng(18)
+    ref = bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), clen))
+    R, L = np.zeros(clen + 1, np.int64), np.zeros(clen + 1, np.int64)
+    R[0:clen:2] = 1; L[1:clen:2] = 1
+    table = {}
+    sites = list(range(400, 17_000, 400)) + list(range(17_050, 19_950, 100))
+    for k, x in enumerate(sites):
+        # [x - 3, x) duplicated, and every third time the left pile at x - 5 verifies as well, at shift 2
+        table[(0, RIGHT, x)] = [codes(ref, x - 3, 30)]; table[(0, LEFT, x - 3)] = [codes(ref, x - 1, 30, -1)]
+        if k % 3 == 0:
+            table[(0, LEFT, x - 5)] = [codes(ref, x - 1 - 2, 30, -1)]
+    par = (1, 0, 1, 5, 32, 1)
+    # The restatement tries every right peak with every left peak.  With T = 0 a peak is a position with a count, whatever stands beside
+    # it, so the contig is asked slice by slice: the right peaks of [a, a + 500) and the left peaks they can reach, [a - 5, a + 500).
+    want, n_cand = [], 0
+    for a in range(0, clen + 1, 500):
+        Rs, Ls = np.zeros_like(R), np.zeros_like(L)
+        Rs[a:a + 500] = R[a:a + 500]; Ls[max(a - 5, 0):a + 500] = L[max(a - 5, 0):a + 500]
+        rows, n = cp.crossed(Rs, Ls, table, ref, 0, *par)
+        want += rows; n_cand += n
+    assert n_cand > 2 * 8_192 and want == sorted(want) and len(want) >= len(sites) + len(sites) // 3 >= 36
+    assert sum(1 for w in want if w[6] == 2) >= len(sites) // 3 and sum(1 for w in want if w[0] >= 17_000) >= 30     # 17 000: the 8 500th right peak
+    ctx = capi.Context(0)
+    try:
+        ctx.set_reference([ref])
+        ctx.clip_enable(20, 10)
+        ctx.cliptail_enable(20, 10, 12)
+        ent = [(p, side, b) for (_, side, p), lst in table.items() for b in lst]
+        ctx.cliptail_add(0, [e[0] for e in ent], [e[1] for e in ent], [len(e[2]) for e in ent], np.array([ct.planes_of(e[2]) for e in ent], np.uint32).reshape(-1, 2))
+        pos = np.concatenate([np.nonzero(R)[0], np.nonzero(L)[0]])
+        ctx.clip_build(clen, pos, np.concatenate([np.zeros(clen // 2, np.uint8), np.ones(clen // 2, np.uint8)]))
+        assert len(ctx.clip_peaks(RIGHT, 1, 0)[0]) == len(ctx.clip_peaks(LEFT, 1, 0)[0]) == 10_000
+        rows = lambda got: [tuple(int(x) for x in row) for row in zip(*got)]
+        assert rows(ctx.clip_crossed(0, *par)) == want
+        assert rows(ctx.clip_crossed(0, *par, cap=5)) == want       # cap below the total: the binding asks again
+    finally:
+        ctx.close()
 
 
 def test_crossed_table_at_its_smallest_overflow_and_reset():

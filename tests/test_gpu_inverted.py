@@ -1,5 +1,5 @@
 """Inversion breakpoints from same-side clip piles (-N): the candidate enumeration and verification of im_cliptail.hip's
-cliptail_inverted_kernel behind im_clip_inverted_tid / im_clip_inverted, and what the host driver makes of them (-N FILE).
+cliptail_pairs_kernel<true> behind im_clip_inverted_tid / im_clip_inverted, and what the host driver makes of them (-N FILE).
 
 The yardstick is the plain restatement in tests/support/invertedpiles.py, written from the definition in include/indelminer_amd.h (seam 5,
 "Inverted piles"), not from the code under test; tests/test_inverted_host.py pins it to cases worked by hand.  Every answer is compared
@@ -267,6 +267,40 @@ def test_inverted_one_list_empty_and_empty_arrays(scenario):
         dev.counts(zeros, zeros)
         assert [inverted_of(dev, tid, PAR) for tid in range(3)] == [[], [], []]
         assert [inverted_of(dev, tid, (1, 0, 1, 2_000_000_000, 32, 1)) for tid in range(3)] == [[], [], []]
+    finally:
+        dev.close()
+
+
+def test_the_searches_share_the_workspace(scenario):
+    """the crossed, inverted and facing searches lay their lists and columns over one workspace: asked in turns on one context, each
+    answers as the restatement does, whatever ran before it -- also when every search asks again, with cap = 1, between the others.
+    The scenario's own piles make no crossed pair, so four duplications are planted into a copy of it, clear of its sites."""
+    from tests.support import crossedpiles as cp
+    from tests.support import facingpiles as fp
+    from tests.test_gpu_crossed import codes
+    sc, ref = scenario, scenario.refs[0]
+    R, L = [a.copy() for a in sc.R], [a.copy() for a in sc.L]
+    table = {k: list(v) for k, v in sc.table.items()}
+    planted = ((3_700, 3), (10_700, 4), (50_700, 70), (120_700, 3))
+    for p, n in planted:                                            # [p - 150, p) duplicated: n right entries at p, 3 left ones at p - 150
+        R[0][p] += n; L[0][p - 150] += 3
+        table.setdefault((0, RIGHT, p), []).extend([codes(ref, p - 150, 30)] * n)
+        table.setdefault((0, LEFT, p - 150), []).extend([codes(ref, p - 1, 30, -1)] * 3)
+    want = {"crossed": cp.crossed(R[0], L[0], table, ref, 0, *PAR)[0], "inverted": ip.inverted(R[0], L[0], table, ref, 0, *PAR)[0],
+            "facing": fp.facing_many(R[0], L[0], 3, 30)}
+    assert [w[:7] for w in want["crossed"]] == [(p, p - 150, n, 3, n, 3, 0) for p, n in planted]
+    assert want["inverted"] == ip.inverted(sc.R[0], sc.L[0], sc.table, ref, 0, *PAR)[0] and len(want["inverted"]) > 50 and len(want["facing"]) >= 3
+    dev = Device(log2_slots=13, refs=sc.refs)
+    ask = {"crossed": lambda cap: rows(dev.ctx.clip_crossed_tid(0, *PAR, cap)), "inverted": lambda cap: inverted_of(dev, 0, PAR, cap),
+           "facing": lambda cap: dev.facing(0, 3, 30, cap)}
+    try:
+        dev.counts(R, L)
+        dev.add(table)
+        turns = ("crossed", "inverted", "crossed", "facing")
+        for cap in (65536, 1):
+            for order in (turns, turns[::-1]):
+                for kind in order:
+                    assert ask[kind](cap) == want[kind], (cap, order, kind)
     finally:
         dev.close()
 
