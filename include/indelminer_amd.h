@@ -744,6 +744,53 @@ int im_clip_inverted(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach,
                      int32_t min_verified, int32_t cap, uint8_t* side, int32_t* p1, int32_t* p2, uint32_t* c1, uint32_t* c2, uint32_t* v1,
                      uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2, int32_t* n_found);
 
+/* Pair links, the read pairs that span a junction (-M).  The piles above are one kind of evidence, the clipped reads AT the two
+ * breakpoints.  A second, independent one is the orientation of the pairs whose reads lie on either side of a junction: a tandem
+ * duplication of [pl, pr) leaves EVERTED pairs (the leftmost read on the reverse strand near pl, its mate on the forward strand just in
+ * front of pr), the left junction of an inversion leaves pairs with BOTH READS FORWARD, its right junction pairs with BOTH READS REVERSE.
+ * A keyed table of its own, beside the clip-tail table, keeps one link per such pair; a query counts the links between two windows.
+ *
+ * WHICH RECORDS STORE A LINK.  With q = min_mapq a delivered record is a LINK iff all of
+ *   flag & 0x1 is set and none of 0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800 is;
+ *   0 <= tid < n_contigs and mtid == tid;
+ *   pos < mpos, or pos == mpos and flag & 0x40 (each pair once, at its leftmost record: the rule of the pair-span scatter);
+ *   mapq >= q (the record's own mapping quality; its mate's is not known);
+ *   0 <= pos <= length and 0 <= mpos <= length of the contig;
+ *   with r = (flag >> 4) & 1 and m = (flag >> 5) & 1 the pair (r, m) gives the KIND:
+ *     (1, 0)  kind 0, EVERTED   the duplication signature
+ *     (0, 0)  kind 1, FORWARD   the inversion's left junction
+ *     (1, 1)  kind 2, REVERSE   the inversion's right junction
+ *     (0, 1)  none              the normal orientation is NOT a link, whatever its insert size
+ * hold.  Only the 32-byte core of the record is read, so both delivered record forms are taken (im_dev_records); no read group is
+ * looked up.  A link stores (tid, kind, pos, mpos).
+ *
+ * A QUERY is (kind, a0, a1, b0, b1) on contig tid; the call also takes one min_sep >= 0.  Both intervals are inclusive and are clipped
+ * to [0, length].  The answer is the number of stored links of that kind with a0 <= pos <= a1, b0 <= mpos <= b1 and
+ * mpos - pos >= min_sep; an interval that is empty after the clip answers 0.  a1 - a0 above 65 535 before the clip is IM_E_ARG, and so
+ * are a kind outside 0 .. 2 and a negative min_sep.  The answer does not depend on the order in which the links arrived.
+ *
+ * THE TABLE has 2^log2_slots slots of 16 bytes (6 <= log2_slots <= 30), the design of the clip-tail table: a multimap with open
+ * addressing; the home slot of a link is (key * 0x9E3779B97F4A7C15) >> (64 - log2_slots) with
+ * key = 1 << 63 | tid << 26 | (pos >> 8) << 2 | kind, so all links of one (tid, 256-base bucket, kind) lie on one probe run; the payload
+ * is pos | mpos << 32; probing is linear and wraps past the last slot.  Only half of the slots are ever taken: the number of links
+ * stored is exactly min(links asked for, 2^log2_slots / 2) and the rest are counted as dropped.  Once dropped > 0 an answer could miss
+ * links, so im_pairlink_count then returns IM_OK and fills every count of the call with 0xFFFFFFFF: no answer, not a wrong one.  A
+ * query walks one probe run per bucket of [a0, a1], at most 257; a bucket with thousands of links is one long probe run.
+ *
+ * im_pairlink_enable allocates the table (16 << log2_slots bytes of HBM, on this call only; the reference must be set, at most 2^24
+ * contigs) and fixes min_mapq: a second call with other values is refused.  im_dev_pairlink_scatter adds the links of a chunk of
+ * delivered records (one launch of its own, asynchronous).  im_pairlink_add adds n links of contig tid the caller names -- it applies
+ * the record rule itself -- as pos, mpos and kind 0 .. 2; a link with a position outside [0, length] is dropped without counting;
+ * synchronous.  im_pairlink_count answers nq queries of contig tid; synchronous, on the context's stream.  im_pairlink_reset puts all
+ * slots and both counters back to zero.  im_pairlink_stats gives the links stored and dropped since the last reset; synchronous. */
+int im_pairlink_enable(im_ctx* ctx, int32_t min_mapq, int32_t log2_slots);
+int im_dev_pairlink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream);
+int im_pairlink_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, const int32_t* mpos, const uint8_t* kind);
+int im_pairlink_count(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kind, const int32_t* a0, const int32_t* a1, const int32_t* b0,
+                      const int32_t* b1, int32_t min_sep, uint32_t* count_out);
+int im_pairlink_reset(im_ctx* ctx, void* stream);
+int im_pairlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

@@ -244,6 +244,12 @@ def lib():
         L.im_clip_crossed.argtypes = [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p] * 9 + [C.POINTER(C.c_int32)]
         L.im_clip_inverted_tid.argtypes = [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p] * 10 + [C.POINTER(C.c_int32)]
         L.im_clip_inverted.argtypes = [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p] * 10 + [C.POINTER(C.c_int32)]
+        L.im_pairlink_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.im_dev_pairlink_scatter.argtypes = [C.c_void_p, C.POINTER(DevRecords), C.c_void_p]
+        L.im_pairlink_add.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_pairlink_count.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.im_pairlink_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.im_pairlink_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_capture_begin.argtypes = [C.c_void_p, C.c_void_p]
@@ -686,6 +692,42 @@ class Context:
     def clip_peaks(self, side, min_reads, reach, cap=65536):
         """the same on the arrays of the last clip_build"""
         return self._clip_search(lib().im_clip_peaks, (np.int32, np.uint32), cap, side, min_reads, reach)
+
+    def pairlink_enable(self, min_mapq, log2_slots):
+        """the keyed table of pair links (-M): 2^log2_slots slots of 16 bytes, half of them usable"""
+        self._check(lib().im_pairlink_enable(self.h, int(min_mapq), int(log2_slots)))
+
+    def pairlink_scatter(self, recs, stream=None):
+        """DevRecords -> one link per leftmost record of a pair in an abnormal orientation (asynchronous)"""
+        self._check(lib().im_dev_pairlink_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
+
+    def pairlink_add(self, tid, pos, mpos, kind):
+        """links of contig tid as the caller found them: pos, mpos, kind (0: everted, 1: both forward, 2: both reverse)"""
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        mpos = np.ascontiguousarray(mpos, dtype=np.int32)
+        kind = np.ascontiguousarray(kind, dtype=np.uint8)
+        assert len(pos) == len(mpos) == len(kind)
+        self._check(lib().im_pairlink_add(self.h, int(tid), len(pos), _ptr(pos), _ptr(mpos), _ptr(kind)))
+
+    def pairlink_count(self, tid, kind, a0, a1, b0, b1, min_sep=0):
+        """per query (kind, [a0, a1], [b0, b1]) on contig tid: the links of that kind with pos in the first interval, mpos in the second
+        and mpos - pos >= min_sep; after an overflow every count is 0xFFFFFFFF"""
+        kind = np.ascontiguousarray(kind, dtype=np.uint8)
+        a0, a1, b0, b1 = (np.ascontiguousarray(x, dtype=np.int32) for x in (a0, a1, b0, b1))
+        n = len(kind)
+        assert len(a0) == len(a1) == len(b0) == len(b1) == n
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(lib().im_pairlink_count(self.h, int(tid), n, _ptr(kind), _ptr(a0), _ptr(a1), _ptr(b0), _ptr(b1), int(min_sep), _ptr(out)))
+        return out[:n]
+
+    def pairlink_reset(self, stream=None):
+        self._check(lib().im_pairlink_reset(self.h, self.stream if stream is None else stream))
+
+    def pairlink_stats(self):
+        """(links stored, links dropped) since the last reset"""
+        stored, dropped = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().im_pairlink_stats(self.h, C.byref(stored), C.byref(dropped)))
+        return int(stored.value), int(dropped.value)
 
     _CROSSED = (np.int32, np.int32, np.uint32, np.uint32, np.uint32, np.uint32, np.int32, np.uint32, np.uint32)
 

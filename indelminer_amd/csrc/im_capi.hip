@@ -66,6 +66,9 @@ struct im_ctx {
     // -V: the keyed table of clipped bases (im_cliptail_enable); slots null: not enabled.  min_clip and min_mapq are its scatter's
     im::TailTable tail = {nullptr, nullptr, 0};
     int32_t tail_min_clip = 0, tail_min_mapq = 0;
+    // -M: the keyed table of pair links (im_pairlink_enable), an allocation of its own; slots null: not enabled
+    im::LinkTable link = {nullptr, nullptr, 0};
+    int32_t link_min_mapq = 0;
     // the median queries' histograms of queries of several slabs (im::launch_depth_median): zeros between calls, sized by the call that
     // needed the most; med_dirty: a call did not get to its end, the next one clears them
     uint32_t* med_scratch = nullptr;
@@ -159,6 +162,10 @@ void free_reference(im_ctx* ctx)
     if (ctx->tail.slots) (void)hipFree(ctx->tail.slots);
     if (ctx->tail.counters) (void)hipFree(ctx->tail.counters);
     ctx->tail = {nullptr, nullptr, 0};
+    // and so is the pair-link table
+    if (ctx->link.slots) (void)hipFree(ctx->link.slots);
+    if (ctx->link.counters) (void)hipFree(ctx->link.counters);
+    ctx->link = {nullptr, nullptr, 0};
 }
 
 void free_array(ContigArray& a)
@@ -1514,6 +1521,125 @@ int im_cliptail_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped)
     HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const unsigned long long half = 1ull << (ctx->tail.log2_slots - 1);
+    *stored = counters[0] < half ? counters[0] : half; *dropped = counters[1];
+    return IM_OK;
+}
+
+// ---- pair links: the read pairs of an abnormal orientation, counted between two windows (-M) ----------
+
+int im_pairlink_enable(im_ctx* ctx, int32_t min_mapq, int32_t log2_slots)
+{
+    if (!ctx) return IM_E_ARG;
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    if (log2_slots < 6 || log2_slots > 30) { set_err(ctx, "im_pairlink_enable: log2_slots %d, must be 6 .. 30", log2_slots); return IM_E_ARG; }
+    if (ctx->n_contigs > (1 << 24)) { set_err(ctx, "im_pairlink_enable: more than 2^24 contigs"); return IM_E_ARG; }
+    if (ctx->link.slots) {
+        if (min_mapq != ctx->link_min_mapq || log2_slots != ctx->link.log2_slots) {
+            set_err(ctx, "im_pairlink_enable: already enabled with min_mapq %d, log2_slots %d", ctx->link_min_mapq, ctx->link.log2_slots);
+            return IM_E_ARG;
+        }
+        return IM_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)16 << log2_slots;
+    unsigned long long* slots = nullptr;
+    unsigned long long* counters = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&slots, bytes));
+    if (hipMalloc((void**)&counters, 2 * sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(slots); set_err(ctx, "im_pairlink_enable: out of device memory"); return IM_E_HIP; }
+    ctx->link = {slots, counters, log2_slots};
+    ctx->link_min_mapq = min_mapq;
+    HIP_TRY(ctx, hipMemsetAsync(slots, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+int im_dev_pairlink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
+{
+    if (!ctx || !recs) return IM_E_ARG;
+    if (!ctx->link.slots) { set_err(ctx, "im_pairlink_enable has not been called"); return IM_E_ARG; }
+    if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, im::launch_pairlink_scatter(ref_dev(ctx), ctx->link_min_mapq, *recs, ctx->link, (hipStream_t)stream));
+    return IM_OK;
+}
+
+// the host names the links: checked here, staged through the workspace, one lane inserts each, wait
+int im_pairlink_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, const int32_t* mpos, const uint8_t* kind)
+{
+    if (!ctx || n < 0 || (n > 0 && (!pos || !mpos || !kind))) return IM_E_ARG;
+    if (!ctx->link.slots) { set_err(ctx, "im_pairlink_enable has not been called"); return IM_E_ARG; }
+    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    for (int32_t i = 0; i < n; i++)
+        if (kind[i] > 2) { set_err(ctx, "im_pairlink_add: link %d: kind %d, must be 0 (everted), 1 (forward) or 2 (reverse)", i, (int)kind[i]); return IM_E_ARG; }
+    if (n == 0) return IM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = up256(sizeof(int32_t) * (size_t)n);
+    int rc = ensure_ws(ctx, 3 * sb);
+    if (rc) return rc;
+    int32_t* d_pos = (int32_t*)ctx->ws;
+    int32_t* d_mpos = (int32_t*)((char*)ctx->ws + sb);
+    uint8_t* d_kind = (uint8_t*)ctx->ws + 2 * sb;
+    HIP_TRY(ctx, hipMemcpyAsync(d_pos, pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_mpos, mpos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_kind, kind, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, im::launch_pairlink_add(n, tid, ctx->h_len[tid], d_pos, d_mpos, d_kind, ctx->link, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+// [kind][a0][a1][b0][b1] in, one launch, the counts and the two counters back, one wait; after an overflow every answer is "none"
+int im_pairlink_count(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kind, const int32_t* a0, const int32_t* a1, const int32_t* b0,
+                      const int32_t* b1, int32_t min_sep, uint32_t* count_out)
+{
+    if (!ctx || nq < 0) return IM_E_ARG;
+    if (!ctx->link.slots) { set_err(ctx, "im_pairlink_enable has not been called"); return IM_E_ARG; }
+    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    if (min_sep < 0) { set_err(ctx, "im_pairlink_count: min_sep %d, must be >= 0", min_sep); return IM_E_ARG; }
+    if (nq == 0) return IM_OK;
+    if (!kind || !a0 || !a1 || !b0 || !b1 || !count_out) return IM_E_ARG;
+    for (int32_t q = 0; q < nq; q++) {
+        if (kind[q] > 2) { set_err(ctx, "im_pairlink_count: query %d: kind %d, must be 0 (everted), 1 (forward) or 2 (reverse)", q, (int)kind[q]); return IM_E_ARG; }
+        // the wave walks one probe run per 256-base bucket of [a0, a1]: 257 at the most
+        if ((int64_t)a1[q] - (int64_t)a0[q] > 65535) { set_err(ctx, "im_pairlink_count: query %d: a1 - a0 = %lld, must be <= 65535", q, (long long)a1[q] - (long long)a0[q]); return IM_E_ARG; }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = up256(sizeof(int32_t) * (size_t)nq);
+    int rc = ensure_ws(ctx, 6 * sb);
+    if (rc) return rc;
+    const int32_t* h_in[4] = {a0, a1, b0, b1};
+    int32_t* d_in[4];
+    for (int k = 0; k < 4; k++) d_in[k] = (int32_t*)((char*)ctx->ws + k * sb);
+    uint8_t* d_kind = (uint8_t*)ctx->ws + 4 * sb;
+    uint32_t* d_out = (uint32_t*)((char*)ctx->ws + 5 * sb);
+    unsigned long long counters[2] = {0, 0};
+    for (int k = 0; k < 4; k++) HIP_TRY(ctx, hipMemcpyAsync(d_in[k], h_in[k], sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_kind, kind, (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, im::launch_pairlink_count(nq, tid, d_kind, d_in[0], d_in[1], d_in[2], d_in[3], min_sep, ctx->h_len[tid], ctx->link, d_out, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(count_out, d_out, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->link.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (counters[1] > 0) memset(count_out, 0xFF, sizeof(uint32_t) * (size_t)nq);       // no answer, not a wrong one
+    return IM_OK;
+}
+
+int im_pairlink_reset(im_ctx* ctx, void* stream)
+{
+    if (!ctx || !ctx->link.slots) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->link.slots, 0, (size_t)16 << ctx->link.log2_slots, (hipStream_t)stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->link.counters, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream));
+    return IM_OK;
+}
+
+int im_pairlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped)
+{
+    if (!ctx || !ctx->link.slots || !stored || !dropped) return IM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long counters[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->link.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned long long half = 1ull << (ctx->link.log2_slots - 1);
     *stored = counters[0] < half ? counters[0] : half; *dropped = counters[1];
     return IM_OK;
 }

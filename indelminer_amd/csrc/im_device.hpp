@@ -177,6 +177,22 @@ struct TailPairsArgs {
     uint32_t* n_found;
 };
 hipError_t launch_cliptail_pairs(bool inverted, TailPairsArgs A, hipStream_t stream);
+// im_pairlink.hip: the read pairs of an abnormal orientation in a keyed table of its own (-M), the clip-tail table's design: slots:
+// 2^log2_slots pairs (key, payload) of 64-bit words, zeros = empty; counters[0]: inserts asked for, counters[1]: those dropped
+struct LinkTable {
+    unsigned long long* slots;
+    unsigned long long* counters;
+    int32_t log2_slots;
+};
+// the records that are a link under the record rule (include/indelminer_amd.h, "Pair links") -> one entry each
+hipError_t launch_pairlink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const LinkTable& tab, hipStream_t stream);
+// one entry per host-named (pos, mpos, kind 0 .. 2) of contig tid; a position outside [0, clen] drops the link
+hipError_t launch_pairlink_add(int32_t n, int32_t tid, int64_t clen, const int32_t* pos, const int32_t* mpos, const uint8_t* kind,
+                               const LinkTable& tab, hipStream_t stream);
+// per query (kind, [a0, a1], [b0, b1]) on contig tid, both intervals inclusive and clipped to [0, clen]: the links of that kind with pos
+// in the first, mpos in the second and mpos - pos >= min_sep; the caller holds a1 - a0 to 65 535
+hipError_t launch_pairlink_count(int32_t nq, int32_t tid, const uint8_t* kind, const int32_t* a0, const int32_t* a1, const int32_t* b0,
+                                 const int32_t* b1, int32_t min_sep, int64_t clen, const LinkTable& tab, uint32_t* count, hipStream_t stream);
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);

@@ -333,6 +333,8 @@ typedef struct {
     int32_t* clip_pos; uint8_t* clip_side; int64_t n_clip, cap_clip;
     /* -V, the same path: their clip-tail entries, position, side, bases and the two planes each (im_cliptail_add) */
     int32_t* tail_pos; uint8_t* tail_side; uint8_t* tail_n; uint32_t* tail_planes; int64_t n_tail, cap_tail;
+    /* -M, the same path: the contig's pair links, pos, mpos and kind each (im_pairlink_add) */
+    int32_t* link_pos; int32_t* link_mpos; uint8_t* link_kind; int64_t n_link, cap_link;
     int depth_tid;              /* contig whose depth array is resident on the device, -1 = none */
     int pipe_mode;              /* device pipeline: depth queries go to the genome-wide array */
     int marker_floor;           /* multi-GPU: smallest start of a stale pair-table entry of an earlier contig on another rank */

@@ -50,6 +50,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    (clipped reads at its end that continue at its start; with -D their depth)\n");
     fprintf(file, "\t-N, with -G -C -V: write inversion breakpoints to this file, a VCF of its own\n");
     fprintf(file, "\t    (two piles of reads clipped on the same side that continue on the other strand at each other)\n");
+    fprintf(file, "\t-M, with -U or -N: add PE= to their records, the read pairs whose orientation\n");
+    fprintf(file, "\t    is the junction's (everted; both forward; both reverse) between two windows at the breakpoints\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -99,7 +101,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:M")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -132,6 +134,7 @@ int main(int argc, char** argv)
         case 'I': g_ins_file = optarg; break;                       /* not an option of the reference */
         case 'U': g_dup_file = optarg; break;                       /* not an option of the reference */
         case 'N': g_inv_file = optarg; break;                       /* not an option of the reference */
+        case 'M': g_pair_links = 1; break;                          /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -227,11 +230,18 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: inversion evidence (-N) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -M: behind -N's refusals; every other refusal reaches it through -U or -N, that is through -G, -C and -V */
+    if (g_pair_links) {
+        if (!g_dup_file && !g_inv_file) { fprintf(stderr, "indelminer: -M needs -U or -N\n"); return EXIT_FAILURE; }
+        if (!PAIRLINK_API_PRESENT) {
+            fprintf(stderr, "indelminer: pair links (-M) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = 0; g_ins_file = g_dup_file = g_inv_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
+        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = 0; g_ins_file = g_dup_file = g_inv_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {
@@ -388,6 +398,13 @@ int main(int argc, char** argv)
         uint64_t stored = 0, dropped = 0;
         if (im_cliptail_stats(d.gpu, &stored, &dropped) == IM_OK && dropped > 0)
             fprintf(stderr, "indelminer: -V: the clip-tail table overflowed (%llu entries stored, %llu dropped): CV and CH are . from there on\n",
+                    (unsigned long long)stored, (unsigned long long)dropped);
+    }
+    if (PAIRLINK_ON) {
+        /* -M: the same for its table */
+        uint64_t stored = 0, dropped = 0;
+        if (im_pairlink_stats(d.gpu, &stored, &dropped) == IM_OK && dropped > 0)
+            fprintf(stderr, "indelminer: -M: the pair-link table overflowed (%llu links stored, %llu dropped): PE is . in the files of -U and -N\n",
                     (unsigned long long)stored, (unsigned long long)dropped);
     }
     if (t_out) fflush(t_out);

@@ -196,6 +196,8 @@ static void pipe_global_init(driver* d)
     if (CLIP_ON && im_clip_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold) != IM_OK) fatalf("im_clip_enable: %s", im_last_error(d->gpu));
     /* -V: and the table of their clipped bases */
     if (CLIPTAIL_ON) cliptail_enable(d);
+    /* -M: and the table of pair links */
+    if (PAIRLINK_ON) pairlink_enable(d);
 }
 
 /* one walker's buffers (with_chunks: the pinned chunk ring a walk delivers records through; the main thread's stage pipeline
@@ -416,6 +418,7 @@ static void pipe_submit(ppipe* P, pgroup* G)
     if (PAIR_ON) GPU(im_dev_pairspan_scatter(g, &recs, P->stream));  /* -P: one more, only then */
     if (CLIP_ON) GPU(im_dev_clip_scatter(g, &recs, P->stream));      /* -C: one more, only then; these arrays need no scan */
     if (CLIPTAIL_ON) GPU(im_dev_cliptail_scatter(g, &recs, P->stream));      /* -V: and one behind it, only then */
+    if (PAIRLINK_ON) GPU(im_dev_pairlink_scatter(g, &recs, P->stream));      /* -M: and one behind that, only then */
     GPU(im_dev_download_async(g, c->h_cnt, P->counters, 32, P->stream));
     GPU(im_event_record(c->done, P->stream));
     c->busy = 1; P->n_busy++;

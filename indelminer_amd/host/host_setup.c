@@ -399,6 +399,36 @@ static void cliptail_enable(driver* d)
     while (k < 30 && ((int64_t)1 << k) < bytes / 64) k++;
     if (im_cliptail_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, k) != IM_OK) fatalf("im_cliptail_enable: %s", im_last_error(d->gpu));
 }
+/* the size of -M's table: -V's rule with one sixteenth of its slots (LINK_EV_SLOTS_SHIFT says what that assumes) */
+static void pairlink_enable(driver* d)
+{
+    struct stat sb;
+    const int64_t bytes = stat(d->bam_name, &sb) == 0 ? (int64_t)sb.st_size : 0;
+    int k = 16;
+    while (k < 30 && ((int64_t)1 << k) < bytes / 64) k++;
+    if (im_pairlink_enable(d->gpu, O.qthreshold, k - LINK_EV_SLOTS_SHIFT) != IM_OK) fatalf("im_pairlink_enable: %s", im_last_error(d->gpu));
+}
+/* -M: the record rule of the device's pair-link scatter (include/indelminer_amd.h, "Pair links"), for the record-at-a-time path: the
+ * leftmost record of a pair on one contig, both reads mapped, in any orientation but forward in front of reverse */
+static void link_events(driver* d, const bam_record* b)
+{
+    if (!(b->flag & 0x1) || (b->flag & (0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800))) return;
+    if (b->tid < 0 || b->tid >= d->hdr->n_targets || b->mtid != b->tid || (int)b->mapq < O.qthreshold) return;
+    if (!(b->pos < b->mpos || (b->pos == b->mpos && (b->flag & 0x40)))) return;
+    const int64_t clen = d->hdr->target_len[b->tid];
+    if (b->pos < 0 || b->pos > clen || b->mpos < 0 || b->mpos > clen) return;
+    const int rev = (b->flag >> 4) & 1, mrev = (b->flag >> 5) & 1;
+    if (!rev && mrev) return;
+    if (d->n_link == d->cap_link) {
+        d->cap_link = d->cap_link ? d->cap_link * 2 : (1 << 12);
+        d->link_pos = xrealloc(d->link_pos, sizeof(int32_t) * (size_t)d->cap_link);
+        d->link_mpos = xrealloc(d->link_mpos, sizeof(int32_t) * (size_t)d->cap_link);
+        d->link_kind = xrealloc(d->link_kind, (size_t)d->cap_link);
+    }
+    d->link_pos[d->n_link] = b->pos; d->link_mpos[d->n_link] = b->mpos;
+    d->link_kind[d->n_link] = (uint8_t)(rev ? (mrev ? LINK_REVERSE : LINK_EVERTED) : LINK_FORWARD);
+    d->n_link++;
+}
 static void clip_events(driver* d, const bam_record* b)
 {
     if (b->tid < 0 || b->tid >= d->hdr->n_targets || (b->flag & (0x4 | 0x100 | 0x200 | 0x400)) || (int)b->mapq < O.qthreshold) return;
@@ -533,6 +563,34 @@ static void ins_contig(driver* d, int32_t tid, FILE* f)
     free(pr); free(pl); free(cr); free(cl);
 }
 
+/* -M: the ##pairLinks line, the rule and its constants (the ##INFO line of PE is the FILE's own: dup_describe, inv_describe) */
+static void pe_describe(FILE* f)
+{
+    fprintf(f, "##pairLinks=\"PE counts read pairs on one contig, each once at its leftmost read: paired, both reads mapped, neither secondary, supplementary, duplicate "
+               "nor failing quality control, the leftmost read of mapping quality >= -q, both starts inside the contig, in the orientation of the record's junction "
+               "(the normal one, forward in front of reverse, never counts, whatever its insert size); start of the leftmost read and start of its mate each within a "
+               "window that reaches %d bases from the record's breakpoint towards where the junction's pairs lie and %d bases the other way, the two starts at "
+               "least %d bases apart; PE is . once the pair-link table has overflowed (stderr says so); a duplication shorter than a read leaves no everted pair: "
+               "PE=0 is expected there; pairs whose mate lies on another contig are not counted\"\n", LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT, LINK_EV_MIN_SEP);
+}
+
+/* -M: PE of one contig's records, one query each; kind, and the two windows [a0, a1] (pos) and [b0, b1] (mpos) as the caller filled them.
+ * The device clips the windows to the contig; what an int32 does not hold is clipped here. */
+static int32_t link_clamp(int64_t x) { return (int32_t)(x < INT32_MIN ? INT32_MIN : x > INT32_MAX ? INT32_MAX : x); }
+static uint32_t* pair_links_query(driver* d, int32_t tid, int32_t n, const uint8_t* kind, const int32_t* win)
+{
+    uint32_t* pe = xmalloc(sizeof(uint32_t) * (size_t)(n > 0 ? n : 1));
+    pthread_mutex_lock(&g_query_mu);
+    const int rc = im_pairlink_count(d->gpu, tid, n, kind, win, win + n, win + 2 * (size_t)n, win + 3 * (size_t)n, LINK_EV_MIN_SEP, pe);
+    pthread_mutex_unlock(&g_query_mu);
+    if (rc != IM_OK) fatalf("im_pairlink_count: %s", im_last_error(d->gpu));
+    return pe;
+}
+static void fprint_pe(FILE* f, uint32_t pe)
+{
+    if (pe == PAIRLINK_NONE) fprintf(f, ";PE=."); else fprintf(f, ";PE=%u", pe);
+}
+
 static void dup_describe(FILE* f)
 {
     fprintf(f, "##ALT=<ID=DUP:TANDEM,Description=\"Tandem duplication: reads clipped at its end continue at its start\">\n");
@@ -547,6 +605,9 @@ static void dup_describe(FILE* f)
         fprintf(f, "##INFO=<ID=DM,Number=3,Type=Integer,Description=\"Median depth over the duplicated bases POS+1..END, over the %d bases in front of them and over the %d bases behind them\">\n", DEPTH_EV_FLANK, DEPTH_EV_FLANK);
         fprintf(f, "##INFO=<ID=DFC,Number=1,Type=Integer,Description=\"Depth fold change in thousandths: the first DM value over the mean of the other two\">\n");
     }
+    if (PAIRLINK_ON)
+        fprintf(f, "##INFO=<ID=PE,Number=1,Type=Integer,Description=\"everted read pairs (the leftmost read reverse, its mate forward) that start within POS - %d .. POS + %d "
+                   "and whose mate starts within END - %d .. END + %d, at least %d bases apart\">\n", CLIPTAIL_MAX_SHIFT, LINK_EV_WINDOW, LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT, LINK_EV_MIN_SEP);
     fprintf(f, "##tandemDuplication=\"a record per pair of positions END and POS, %d <= END - POS <= %d, where END is a position at which at least %d reads of mapping "
                "quality >= -q stop aligning with a soft clip of at least %d bases, more than at any of the %d positions in front and no fewer than at any of the %d "
                "behind, and POS is such a position of the reads that start aligning with such a clip, when for one shift s in 0 .. %d at least %d of the reads at END "
@@ -554,6 +615,7 @@ static void dup_describe(FILE* f)
                "clipped bases per read with at most 1 difference in 16 (HOMLEN: the s with the most such reads, the smallest among equals; CV: those reads); "
                "the file has no records once the clip-tail table has overflowed (stderr says so); POS 0 is skipped\"\n",
             DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, DUP_EV_MIN_READS, CLIP_EV_MIN_CLIP, DUP_EV_REACH, DUP_EV_REACH, CLIPTAIL_MAX_SHIFT, DUP_EV_MIN_VERIFIED, DUP_EV_MIN_VERIFIED);
+    if (PAIRLINK_ON) pe_describe(f);
 }
 
 /* The pairs of piles of one contig, crossed (-U) or inverted (-N).  Columns of cap: pos = p1 p2 shift | cnt = c1 c2 v1 v2 stored at p1,
@@ -606,6 +668,19 @@ static void dup_contig(driver* d, int32_t tid, FILE* f)
         if (qrc != IM_OK) fatalf("im_depth_median: %s", im_last_error(d->gpu));
         free(beg);
     }
+    uint32_t* pe = NULL;
+    if (found > 0 && PAIRLINK_ON) {
+        /* one query per pair: everted pairs, the leftmost read at the start of the duplicated bases, its mate in front of their end */
+        uint8_t* kind = xmalloc((size_t)found); int32_t* win = xmalloc(sizeof(int32_t) * 4 * (size_t)found);
+        for (int32_t k = 0; k < found; k++) {
+            const int64_t pr = pos[k], pl = pos[cap + k];
+            kind[k] = LINK_EVERTED;
+            win[k] = link_clamp(pl - CLIPTAIL_MAX_SHIFT); win[found + k] = link_clamp(pl + LINK_EV_WINDOW);
+            win[2 * found + k] = link_clamp(pr - LINK_EV_WINDOW); win[3 * found + k] = link_clamp(pr + CLIPTAIL_MAX_SHIFT);
+        }
+        pe = pair_links_query(d, tid, found, kind, win);
+        free(kind); free(win);
+    }
     const char* seq = d->sequences[tid];
     for (int32_t k = 0; k < found; k++) {
         const int32_t pr = pos[k], pl = pos[cap + k];
@@ -614,9 +689,10 @@ static void dup_contig(driver* d, int32_t tid, FILE* f)
                 toupper((unsigned char)seq[pl - 1]), pr, pr - pl, pos[2 * cap + k], cnt[k], cnt[cap + k], cnt[4 * cap + k], cnt[5 * cap + k],
                 cnt[2 * cap + k], cnt[3 * cap + k]);
         if (med) fprint_depth_values(f, med + 3 * k, ";DM=", ";DFC=");
+        if (pe) fprint_pe(f, pe[k]);
         fprintf(f, "\n");
     }
-    free(med); free(P.pos); free(P.cnt);
+    free(med); free(pe); free(P.pos); free(P.cnt);
 }
 
 static void inv_describe(FILE* f)
@@ -630,6 +706,9 @@ static void inv_describe(FILE* f)
     fprintf(f, "##INFO=<ID=CR,Number=2,Type=Integer,Description=\"Clipped reads at POS, clipped reads at END\">\n");
     fprintf(f, "##INFO=<ID=CN,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases were kept, either pile\">\n");
     fprintf(f, "##INFO=<ID=CV,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases are the reverse complement of the reference at the other pile\">\n");
+    if (PAIRLINK_ON)
+        fprintf(f, "##INFO=<ID=PE,Number=1,Type=Integer,Description=\"read pairs with both reads forward (CT=3to3: both start within %d bases in front of and %d behind POS "
+                   "and END) or both reverse (CT=5to5: within %d in front of and %d behind), at least %d bases apart\">\n", LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT, CLIPTAIL_MAX_SHIFT, LINK_EV_WINDOW, LINK_EV_MIN_SEP);
     fprintf(f, "##inversion=\"a record per pair of positions POS < END, %d <= END - POS <= %d, at both of which at least %d reads of mapping quality >= -q stop aligning "
                "(CT=3to3) or at both of which such reads start aligning (CT=5to5) with a soft clip of at least %d bases, more than at any of the %d positions in front "
                "and no fewer than at any of the %d behind, when for one shift s in 0 .. %d at least %d of the reads at POS and at least %d of the reads at END "
@@ -638,6 +717,7 @@ static void inv_describe(FILE* f)
                "equals; CV: those reads); the two junctions of an inversion are two records; the file has no records once the clip-tail table has overflowed "
                "(stderr says so); POS 0 is skipped\"\n",
             INV_EV_MIN_LEN, INV_EV_MAX_LEN, INV_EV_MIN_READS, CLIP_EV_MIN_CLIP, INV_EV_REACH, INV_EV_REACH, CLIPTAIL_MAX_SHIFT, INV_EV_MIN_VERIFIED, INV_EV_MIN_VERIFIED);
+    if (PAIRLINK_ON) pe_describe(f);
 }
 
 /* -N: one contig's inverted piles into FILE.  No depth fields with -D: an inversion changes no depth. */
@@ -646,15 +726,32 @@ static void inv_contig(driver* d, int32_t tid, FILE* f)
     pile_pairs P = pile_pairs_query(d, tid, 1);
     const int32_t cap = P.cap;
     const int32_t* pos = P.pos; const uint32_t* cnt = P.cnt;
+    uint32_t* pe = NULL;
+    if (P.found > 0 && PAIRLINK_ON) {
+        /* one query per junction: both reads forward in front of the two piles of a left junction, both reverse behind those of a right one */
+        const int32_t n = P.found;
+        uint8_t* kind = xmalloc((size_t)n); int32_t* win = xmalloc(sizeof(int32_t) * 4 * (size_t)n);
+        for (int32_t k = 0; k < n; k++) {
+            const int64_t x = pos[k], y = pos[cap + k];
+            const int64_t lo = P.side[k] ? CLIPTAIL_MAX_SHIFT : LINK_EV_WINDOW, hi = P.side[k] ? LINK_EV_WINDOW : CLIPTAIL_MAX_SHIFT;
+            kind[k] = P.side[k] ? LINK_REVERSE : LINK_FORWARD;
+            win[k] = link_clamp(x - lo); win[n + k] = link_clamp(x + hi);
+            win[2 * n + k] = link_clamp(y - lo); win[3 * n + k] = link_clamp(y + hi);
+        }
+        pe = pair_links_query(d, tid, n, kind, win);
+        free(kind); free(win);
+    }
     const char* seq = d->sequences[tid];
     for (int32_t k = 0; k < P.found; k++) {
         const int32_t x = pos[k], y = pos[cap + k];
         if (x == 0) continue;       /* nothing in front to anchor on */
-        fprintf(f, "%s\t%d\t.\t%c\t<INV>\t.\t.\tSVTYPE=INV;END=%d;SVLEN=%d;CT=%s;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u\n", d->hdr->target_name[tid], x,
+        fprintf(f, "%s\t%d\t.\t%c\t<INV>\t.\t.\tSVTYPE=INV;END=%d;SVLEN=%d;CT=%s;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u", d->hdr->target_name[tid], x,
                 toupper((unsigned char)seq[x - 1]), y, y - x, P.side[k] ? "5to5" : "3to3", pos[2 * cap + k], cnt[k], cnt[cap + k], cnt[4 * cap + k],
                 cnt[5 * cap + k], cnt[2 * cap + k], cnt[3 * cap + k]);
+        if (pe) fprint_pe(f, pe[k]);
+        fprintf(f, "\n");
     }
-    free(P.pos); free(P.cnt); free(P.side);
+    free(pe); free(P.pos); free(P.cnt); free(P.side);
 }
 
 static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_reader* r)
@@ -664,7 +761,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
     bam_region_iter it;
     bam_record b; memset(&b, 0, sizeof b);
     if (bam_region_begin(&it, r, d->idx, tid, beg, end) != 0) fatalf("cannot seek in %s", d->bam_name);
-    d->segs.n = 0; d->runs.n = 0; d->frags.n = 0; d->n_clip = 0; d->n_tail = 0;
+    d->segs.n = 0; d->runs.n = 0; d->frags.n = 0; d->n_clip = 0; d->n_tail = 0; d->n_link = 0;
     const int whole = (beg <= 0 && end >= d->hdr->target_len[tid]);
     volatile int died = 0;              /* a record the reference dies on ended the pass: the flushes in front of it are still to print */
     t_is_main_thread_of_passA = 1;
@@ -701,6 +798,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
             }
         }
         if (CLIP_ON) clip_events(d, &b);
+        if (PAIRLINK_ON) link_events(d, &b);
         dispatch_record(d, &b);
         if (PAIR_ON && concordant_left_mate(d, &b)) {
             /* -P: the fragment [pos, pos + isize) of the pair, clipped to what an int32 start and length hold (the device clips
@@ -734,6 +832,13 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
         if (d->n_tail > INT32_MAX) fatalf("more than 2^31 clipped reads on one contig");
         if (im_cliptail_add(d->gpu, tid, (int32_t)d->n_tail, d->tail_pos, d->tail_side, d->tail_n, d->tail_planes) != IM_OK) fatalf("im_cliptail_add: %s", im_last_error(d->gpu));
         phase_time("clip tails (device)");
+    }
+    if (PAIRLINK_ON) {
+        /* -M: the contig's links go up in one call; this table is keyed by contig too */
+        pairlink_enable(d);
+        if (d->n_link > INT32_MAX) fatalf("more than 2^31 pair links on one contig");
+        if (im_pairlink_add(d->gpu, tid, (int32_t)d->n_link, d->link_pos, d->link_mpos, d->link_kind) != IM_OK) fatalf("im_pairlink_add: %s", im_last_error(d->gpu));
+        phase_time("pair links (device)");
     }
 
     im_read_result* res = NULL;

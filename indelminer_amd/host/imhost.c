@@ -221,6 +221,27 @@ extern int im_clip_inverted(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t
 #define INV_EV_MAX_LEN 1000000     /* the longest: inversions are often larger than duplications, and the device drops a chance pair of
                                     * peaks after one comparison, before it reads the second pile */
 #define INV_EV_MIN_VERIFIED 2      /* clipped reads of either pile that continue, complemented, backwards from the other */
+/* -M, with -U or -N: the records of their FILEs gain PE=, the read pairs whose orientation is the junction's -- everted pairs around a
+ * duplication, pairs with both reads forward (3to3) or both reverse (5to5) at an inversion's junctions -- counted between two windows
+ * of LINK_EV_WINDOW bases at the breakpoints (the device's keyed table of pair links and its count query).  Evidence of another kind
+ * than the clipped reads that made the record: nothing is filtered by it.  stdout, stderr and -I's FILE stay as they are.  Not an
+ * option of the reference; referenced weakly. */
+static int g_pair_links = 0;
+extern int im_pairlink_enable(im_ctx*, int32_t, int32_t) __attribute__((weak));
+extern int im_dev_pairlink_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
+extern int im_pairlink_add(im_ctx*, int32_t, int32_t, const int32_t*, const int32_t*, const uint8_t*) __attribute__((weak));
+extern int im_pairlink_count(im_ctx*, int32_t, int32_t, const uint8_t*, const int32_t*, const int32_t*, const int32_t*, const int32_t*, int32_t, uint32_t*) __attribute__((weak));
+extern int im_pairlink_reset(im_ctx*, void*) __attribute__((weak));
+extern int im_pairlink_stats(im_ctx*, uint64_t*, uint64_t*) __attribute__((weak));
+#define PAIRLINK_ON (g_pair_links)                 /* the walk also keeps the pair links */
+#define PAIRLINK_API_PRESENT (im_pairlink_enable && im_dev_pairlink_scatter && im_pairlink_add && im_pairlink_count && im_pairlink_reset && im_pairlink_stats)
+#define LINK_EV_WINDOW 1000        /* bases a window reaches from a breakpoint towards where the junction's pairs lie: above the largest insert of
+                                    * the usual libraries, so the read of a spanning pair that lies away from the breakpoint is inside */
+#define LINK_EV_MIN_SEP 50         /* mpos - pos of the nearest pair that counts: DUP_EV_MIN_LEN and INV_EV_MIN_LEN */
+#define LINK_EV_SLOTS_SHIFT 4      /* the table has one sixteenth of the clip-tail table's slots: links are ASSUMED rarer than clipped reads
+                                    * (a chimeric or mis-oriented pair against a clipped read), which nobody has measured on real data */
+#define PAIRLINK_NONE 0xFFFFFFFFu  /* what the device answers after its table has overflowed */
+enum { LINK_EVERTED = 0, LINK_FORWARD = 1, LINK_REVERSE = 2 };
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that

@@ -1,0 +1,214 @@
+"""-M (discordant-pair support for -U's and -N's records) where there is no GPU: the host driver linked against tests/shim/im_shim.c,
+which implements the C ABI without the clip, clip-tail, facing, crossed, inverted and pair-link entry points.  The driver must still
+link, behave as before without -M, and say what -M needs.  The restatement the GPU tests measure against (tests/support/pairlinks.py) is
+pinned here on cases worked by hand and on the planted data sets of tests/test_gpu_pairlink.py."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+TD = os.path.join(GOLD, "test_data")
+
+PAIRLINK_ENTRY_POINTS = ["im_pairlink_enable", "im_dev_pairlink_scatter", "im_pairlink_add", "im_pairlink_count", "im_pairlink_reset", "im_pairlink_stats"]
+BASE = ["-i", "indelminer.config"]
+IN = ["reference.fa", "sample=alignments.bam"]
+KNOWN = ["reference.fa", "known.vcf", "sample=alignments.bam"]
+
+
+def _shim():
+    from tests.support.shimbuild import build_shim
+    return build_shim()
+
+
+def _run(args, cwd, env=None):
+    return subprocess.run(args, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+
+
+def _refused(r, line):
+    assert r.returncode != 0 and r.stdout == b"", r
+    assert r.stderr.count(b"\n") == 1 and line in r.stderr, r.stderr
+
+
+def test_the_option_is_refused_where_it_does_not_apply_and_output_is_unchanged_without_it(tmp_path):
+    shim = _shim()
+    f, g, u = str(tmp_path / "inv.vcf"), str(tmp_path / "ins.vcf"), str(tmp_path / "dup.vcf")
+    # its own refusal: alone, with everything but -U and -N, with -I alone
+    _refused(_run([shim] + BASE + ["-M"] + IN, TD), b"indelminer: -M needs -U or -N")
+    _refused(_run([shim] + BASE + ["-M", "-q", "10"] + IN, TD), b"indelminer: -M needs -U or -N")
+    # -I's, -U's and -N's refusals come first
+    _refused(_run([shim] + BASE + ["-M", "-I", g] + IN, TD), b"indelminer: -I needs -V")
+    _refused(_run([shim] + BASE + ["-M", "-U", u] + IN, TD), b"indelminer: -U needs -V")
+    _refused(_run([shim] + BASE + ["-M", "-N", f] + IN, TD), b"indelminer: -N needs -V")
+    _refused(_run([shim] + BASE + ["-M", "-N", f, "-U", u] + IN, TD), b"indelminer: -U needs -V")
+    _refused(_run([shim] + BASE + ["-G", "-C", "-M", "-N", f] + IN, TD), b"indelminer: clip evidence (-C) needs the device library")
+    # every other refusal reaches it through -G, -C and -V, and theirs come first
+    for with_ in (["-U", u], ["-N", f], ["-U", u, "-N", f]):
+        _refused(_run([shim] + BASE + ["-G", "-V", "-M"] + with_ + IN, TD), b"indelminer: -V needs -C")
+        _refused(_run([shim] + BASE + ["-C", "-V", "-M"] + with_ + IN, TD), b"indelminer: -C needs -G")
+        _refused(_run([shim] + BASE + ["-C", "-V", "-M"] + with_ + KNOWN, TD), b"indelminer: -C is not available with a VCF argument (annotate mode)")
+        _refused(_run([shim] + BASE + ["-G", "-C", "-V", "-M", "-c", "reference:1-5000"] + with_ + IN, TD), b"indelminer: -C is not available with -c")
+        _refused(_run([shim] + BASE + ["-G", "-C", "-V", "-M"] + with_ + IN, TD), b"indelminer: clip evidence (-C) needs the device library")
+        _refused(_run([shim] + BASE + ["-G", "-D", "-C", "-V", "-M"] + with_ + IN, TD), b"indelminer: depth evidence (-D) needs the device library")
+        env = dict(os.environ, WORLD_SIZE="2", RANK="0")
+        _refused(_run([shim] + BASE + ["-G", "-C", "-V", "-M"] + with_ + IN, TD, env=env), b"-G is not available with more than one rank")
+        _refused(_run([shim] + BASE + ["-G", "-C", "-V", "-M"] + with_ + KNOWN, TD), b"-G is not available with a VCF argument")
+    # with -G -C -V and neither FILE, -V's library refusal comes first on this library; -M's own needs the stubs (the next test)
+    _refused(_run([shim] + BASE + ["-G", "-C", "-V", "-M"] + IN, TD), b"indelminer: clip evidence (-C) needs the device library")
+    assert not os.path.exists(f) and not os.path.exists(g) and not os.path.exists(u)        # a refused run writes no FILE
+    r = _run([shim] + BASE + IN, TD)
+    assert r.returncode == 0 and r.stdout == open(os.path.join(GOLD, "vcf", "default_config.vcf"), "rb").read()
+
+
+def test_a_library_with_every_earlier_entry_family_and_without_the_pair_link_entries(tmp_path):
+    """the shim beside stubs of -C's six, -V's six, -I's three, -U's four and -N's two entries: -M's own refusal, behind theirs"""
+    from indelminer_amd import build
+    srcs = [os.path.join(build.HOST_DIR, s) for s in build.HOST_SOURCES]
+    srcs += [os.path.join(ROOT, "tests", "shim", s) for s in ("im_shim.c", "clip_entries_stub.c", "cliptail_entries_stub.c", "facing_entries_stub.c",
+                                                              "crossed_entries_stub.c", "inverted_entries_stub.c")]
+    srcs += [os.path.join(ROOT, "oracle", "im_oracle.c"), os.path.join(ROOT, "oracle", "im_oracle_triage.c")]
+    binary = str(tmp_path / "indelminer_shim_inverted")
+    subprocess.check_call(["gcc", "-O0", "-std=c11", "-pthread", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(ROOT, "indelminer_amd", "host"), "-o", binary] + srcs + ["-lz", "-lm"])
+    f, g, u = str(tmp_path / "inv.vcf"), str(tmp_path / "ins.vcf"), str(tmp_path / "dup.vcf")
+    for flags in (["-G", "-C", "-V", "-U", u, "-M"], ["-M", "-N", f, "-V", "-C", "-G"], ["-G", "-C", "-V", "-I", g, "-U", u, "-N", f, "-M"]):
+        _refused(_run([binary] + BASE + flags + IN, TD), b"indelminer: pair links (-M) needs the device library")
+    _refused(_run([binary] + BASE + ["-G", "-D", "-C", "-V", "-M", "-N", f] + IN, TD), b"indelminer: depth evidence (-D) needs the device library")
+    # in its order: -M's own condition first, the refusals of the options in front of it before that
+    _refused(_run([binary] + BASE + ["-G", "-C", "-V", "-M"] + IN, TD), b"indelminer: -M needs -U or -N")
+    _refused(_run([binary] + BASE + ["-G", "-C", "-V", "-I", g, "-M"] + IN, TD), b"indelminer: -M needs -U or -N")
+    _refused(_run([binary] + BASE + ["-G", "-C", "-M", "-N", f] + IN, TD), b"indelminer: -N needs -V")
+    _refused(_run([binary] + BASE + ["-G", "-C", "-M", "-U", u] + IN, TD), b"indelminer: -U needs -V")
+    assert not os.path.exists(f) and not os.path.exists(g) and not os.path.exists(u)
+    r = _run([binary] + BASE + IN, TD)
+    assert r.returncode == 0 and r.stdout == open(os.path.join(GOLD, "vcf", "default_config.vcf"), "rb").read()
+
+
+def test_help_names_the_option():
+    h = _run([_shim(), "-h"], TD)
+    assert h.returncode == 0 and re.search(rb"^\t-M, with -U or -N", h.stdout, re.M) and re.search(rb"^\t-N, with -G -C -V", h.stdout, re.M)
+
+
+def test_pair_link_entry_points_are_declared_bound_and_exported():
+    text = open(os.path.join(ROOT, "include", "indelminer_amd.h")).read()
+    from indelminer_amd import build, capi
+    import ctypes as C
+    L = C.CDLL(build.build())
+    src = open(capi.__file__).read()
+    for s in PAIRLINK_ENTRY_POINTS:
+        assert re.search(r"\bint %s\(" % s, text), s
+        assert hasattr(L, s), s
+        assert "L.%s.argtypes" % s in src, s
+    for s in ("pairlink_enable", "pairlink_scatter", "pairlink_add", "pairlink_count", "pairlink_reset", "pairlink_stats"):
+        assert callable(getattr(capi.Context, s)), s
+    capi.lib()
+    assert [len(getattr(capi.lib(), s).argtypes) for s in PAIRLINK_ENTRY_POINTS] == [3, 3, 6, 10, 2, 3]
+    # the definition is stated in seam 5, behind the inverted piles and in front of the multi-GPU part
+    assert (text.index("Inverted piles, the breakpoints of inversions (-N)") < text.index("Pair links, the read pairs that span a junction (-M)")
+            < text.index("multi-GPU: one collective"))
+    for words in ("none of 0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800", "mtid == tid", "pos == mpos and flag & 0x40", "kind 0, EVERTED", "kind 1, FORWARD",
+                  "kind 2, REVERSE", "NOT a link, whatever its insert size", "a0 <= pos <= a1, b0 <= mpos <= b1", "mpos - pos >= min_sep",
+                  "a1 - a0 above 65 535", "(pos >> 8) << 2 | kind", "pos | mpos << 32", "0xFFFFFFFF", "min(links asked for, 2^log2_slots / 2)"):
+        assert words in text, words
+    # additive: the ABI version and the mirrored structs keep their layout; the shim stays without the entries
+    assert "#define IM_ABI_VERSION 3" in text
+    assert C.sizeof(capi.TriageParams) == 24 and C.sizeof(capi.DevRecords) == 32
+    shim = open(os.path.join(ROOT, "tests", "shim", "im_shim.c")).read()
+    assert "im_pairlink" not in shim and "im_dev_pairlink" not in shim
+    assert "im_pairlink.hip" in build.SOURCES
+
+
+def test_pair_link_restatement_on_cases_worked_by_hand():
+    """the yardstick of the GPU tests (tests/support/pairlinks.py), pinned here where no GPU is needed"""
+    from tests.support import pairlinks as pk
+    from tests.support.pairlinks import EVERTED, FORWARD, REVERSE, Rec
+    clens, q = [1_000, 500], 10
+    link = lambda **kw: pk.link_of(Rec(**dict(dict(tid=0, pos=100, mapq=60, flag=0x1 | 0x10 | 0x40, mtid=0, mpos=400), **kw)), clens, q)
+    assert link() == (0, EVERTED, 100, 400)
+    # each excluded flag bit, and the paired bit
+    for bit in (0x4, 0x8, 0x100, 0x200, 0x400, 0x800):
+        assert link(flag=0x1 | 0x10 | 0x40 | bit) is None, hex(bit)
+    assert link(flag=0x10 | 0x40) is None
+    assert link(flag=0x1 | 0x2 | 0x10 | 0x40 | 0x80) == (0, EVERTED, 100, 400)         # proper-pair and last-in-pair do not matter
+    # the four orientations
+    assert link(flag=0x1 | 0x10) == (0, EVERTED, 100, 400) and link(flag=0x1) == (0, FORWARD, 100, 400)
+    assert link(flag=0x1 | 0x10 | 0x20) == (0, REVERSE, 100, 400) and link(flag=0x1 | 0x20) is None
+    assert link(flag=0x1 | 0x20, mpos=900) is None                                     # the normal orientation, whatever its insert size
+    # leftmost record only; the tie goes to the first in pair
+    assert link(pos=400, mpos=100) is None
+    assert link(pos=300, mpos=300, flag=0x1 | 0x40) == (0, FORWARD, 300, 300) and link(pos=300, mpos=300, flag=0x1 | 0x80) is None
+    # mapq at q - 1 and at q; another contig; no contig
+    assert link(mapq=9) is None and link(mapq=10) == (0, EVERTED, 100, 400)
+    assert link(mtid=1) is None and link(mtid=-1) is None and link(tid=1, mtid=1) == (1, EVERTED, 100, 400)
+    assert link(tid=2, mtid=2) is None and link(tid=-1, mtid=-1) is None
+    # positions at 0, length and length + 1
+    assert link(pos=0) == (0, EVERTED, 0, 400) and link(pos=-1) is None
+    assert link(mpos=1_000) == (0, EVERTED, 100, 1_000) and link(mpos=1_001) is None
+    assert link(pos=1_000, mpos=1_000) == (0, EVERTED, 1_000, 1_000) and link(pos=1_001, mpos=1_001) is None
+    assert link(tid=1, mtid=1, mpos=500) == (1, EVERTED, 100, 500) and link(tid=1, mtid=1, mpos=501) is None
+    # the query: window edges, min_sep at its edge, kind, contig, clipping, empty intervals
+    links = [(0, EVERTED, 100, 400), (0, EVERTED, 100, 150), (0, FORWARD, 100, 400), (1, EVERTED, 100, 400), (0, EVERTED, 0, 1_000)]
+    n = lambda *a, sep=0, tid=0, kind=EVERTED: pk.count(links, clens, tid, kind, *a, sep)
+    assert n(100, 100, 400, 400) == 1 and n(101, 200, 400, 400) == 0 and n(0, 99, 400, 400) == 0
+    assert n(100, 100, 401, 500) == 0 and n(100, 100, 300, 399) == 0 and n(100, 100, 150, 400) == 2
+    assert n(100, 100, 0, 1_000, sep=50) == 2 and n(100, 100, 0, 1_000, sep=51) == 1 and n(100, 100, 0, 1_000, sep=300) == 1 and n(100, 100, 0, 1_000, sep=301) == 0
+    assert n(100, 100, 400, 400, kind=FORWARD) == 1 and n(100, 100, 400, 400, kind=REVERSE) == 0 and n(100, 100, 400, 400, tid=1) == 1
+    assert n(-50, 0, 900, 5_000) == 1 and n(-50, -1, 0, 1_000) == 0 and n(0, 1_000, 1_001, 2_000) == 0 and n(200, 100, 0, 1_000) == 0
+    assert n(0, 1_000, 0, 1_000) == 3
+    # the windows of the three kinds of record
+    assert pk.window_of("DUP", None, 5_000, 5_300) == (EVERTED, 4_968, 6_000, 4_300, 5_332)
+    assert pk.window_of("INV", "3to3", 5_000, 5_300) == (FORWARD, 4_000, 5_032, 4_300, 5_332)
+    assert pk.window_of("INV", "5to5", 5_000, 5_300) == (REVERSE, 4_968, 6_000, 5_268, 6_300)
+    # the planted pairs of a junction: both edges, the middle, one base outside; the upper edge gives way to min_sep on a short site
+    assert pk.planted_pairs(4_000, 5_032, 6_000, 7_032) == [(4_000, 6_007), (5_032, 6_007), (4_516, 6_007), (3_999, 6_007)]
+    assert pk.planted_pairs(4_968, 6_000, 4_300, 5_332) == [(4_968, 5_025), (5_282, 5_332), (5_125, 5_182), (4_967, 5_024)]
+    # the rendering: the two header lines in their places, PE at the end of every record
+    plain = (b"##fileformat=VCFv4.1\n##ALT=<ID=INV,Description=\"x\">\n##INFO=<ID=SVTYPE,Number=1>\n##INFO=<ID=CV,Number=2>\n##inversion=\"y\"\n"
+             b"#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n"
+             b"c\t500\t.\tA\t<INV>\t.\t.\tSVTYPE=INV;END=900;SVLEN=400;CT=3to3;HOMLEN=0;CR=3,3;CN=3,3;CV=3,3\n"
+             b"c\t500\t.\tA\t<INV>\t.\t.\tSVTYPE=INV;END=900;SVLEN=400;CT=5to5;HOMLEN=0;CR=3,3;CN=3,3;CV=3,3\n")
+    links = [(0, FORWARD, 450, 850), (0, FORWARD, 533, 850), (0, REVERSE, 468, 868), (0, REVERSE, 467, 868), (0, EVERTED, 500, 900)]
+    text, found = pk.with_pe(plain, "INV", ["c"], [2_000], links)
+    assert found == [("c", 500, 900, "3to3", 1), ("c", 500, 900, "5to5", 1)]
+    lines = text.decode().split("\n")
+    assert lines[3].startswith("##INFO=<ID=CV") and lines[4].startswith("##INFO=<ID=PE,") and lines[5].startswith("##inversion=") and lines[6].startswith("##pairLinks=\"")
+    assert lines[7].startswith("#CHROM") and lines[8].endswith(";CV=3,3;PE=1") and lines[9].endswith(";CV=3,3;PE=1") and len(lines) == 11
+    assert pk.with_pe(plain, "INV", ["c"], [2_000], links, overflowed=True)[0].count(b";PE=.\n") == 2
+
+
+@pytest.mark.parametrize("svtype", ["DUP", "INV"])
+def test_pair_link_restatement_on_the_planted_data_sets(svtype, tmp_path):
+    """what tests/test_gpu_pairlink.py relies on.  The counts found, recorded here: on either planted set the only links in the file are
+    the planted ones (16 on the duplications, 32 on the inversions: the simulator's own pairs are all forward in front of reverse);
+    every record of a site of at least 300 bases -- 300, 1 000, 3 000 and 4 990 -- has PE=3, the three pairs planted inside its window,
+    and the fourth, one base in front of the window, is counted by a window one base wider; every record of a site below 300 bases --
+    50, 60, 75, 100, 150 -- has PE=0.  The driver's CPU stand-in runs on them to exit status 0."""
+    from tests.support import crossedpiles as cp
+    from tests.support import invertedpiles as ip
+    from tests.support import pairlinks as pk
+    refs, rd, planted = pk.planted_dup_reads() if svtype == "DUP" else pk.planted_inv_reads()
+    d = pk.write_planted(str(tmp_path), refs, rd)
+    plain, text, found = pk.render_of_bam(svtype, d + "/aln.bam", d + "/ref.fa", 10)
+    names, clens, links = pk.links_of_bam(d + "/aln.bam", 10)
+    sites = cp.SITES if svtype == "DUP" else ip.SITES
+    junctions = [None] if svtype == "DUP" else ["3to3", "5to5"]
+    assert len(planted) == pk.PAIRS_PER_JUNCTION * len(junctions) * 4 and sorted(links) == sorted((0, k, p, m) for k, p, m in planted)
+    assert [(p, e - p) for _, p, e, ct, _ in found if ct == junctions[0]] == sites and len(found) == len(sites) * len(junctions)
+    for name, pos, end, ct, pe in found:
+        kind, a0, a1, b0, b1 = pk.window_of(svtype, ct, pos, end)
+        inside = [(p, m) for k, p, m in planted if k == kind and a0 <= p <= a1 and b0 <= m <= b1]
+        if end - pos >= pk.MIN_SITE:
+            assert pe == len(inside) == 3, (pos, end, ct, pe)
+            assert {p for p, _ in inside} >= {a0, min(a1, b1 - pk.MIN_SEP)}                    # one exactly on either edge
+            assert pk.count(links, clens, 0, kind, a0 - 1, a1, b0, b1, pk.MIN_SEP) == 4         # and the fourth one base outside
+        else:
+            assert pe == 0 and inside == [], (pos, end, ct, pe)
+    # the file: what it is without -M, plus two header lines and one field per record
+    assert plain == (cp if svtype == "DUP" else ip).render_of_bam(d + "/aln.bam", d + "/ref.fa", 10)[0]
+    assert text.count(b"\n") == plain.count(b"\n") + 2 and text.count(b";PE=") == len(found) and text.count(b";PE=3\n") == 4 * len(junctions)
+    assert text.count(b"##INFO=<ID=PE,") == 1 and text.count(b"##pairLinks=\"") == 1
+    assert b"".join(ln.split(b";PE=")[0] + b"\n" for ln in text.split(b"\n")[:-1] if not ln.startswith((b"##INFO=<ID=PE,", b"##pairLinks="))) == plain
+    r = _run([_shim(), "-i", "cfg.txt", "-s", "100", "ref.fa", "sample=aln.bam"], d)
+    assert r.returncode == 0 and len(r.stdout) > 1000
