@@ -81,7 +81,7 @@ struct im_ctx {
     std::vector<int64_t> h_sums_off;    // each contig's own run of tile sums: scans of different contigs may be in flight on different streams
     // read-group -> range[1] table (im_set_insert_ranges), flattened hashtable chains
     void* rg_blob = nullptr;
-    im::RgTable rg = {nullptr, 0, 0};
+    im::RgTable rg = {nullptr, 0, 0, 0, 0};
     // the general realign pass (im_realign_any.hip): list of the reads it takes, counters, arena; one call at a time
     std::mutex any_mu;
     int32_t* any_list = nullptr; int32_t any_list_cap = 0;
@@ -393,7 +393,7 @@ int reset_genome_array(im_ctx* ctx, GenomeArray im_ctx::*which, int32_t tid, voi
 {
     if (!ctx || !(ctx->*which).data || tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync((ctx->*which).data + ctx->h_asc_off[tid], 0, ((size_t)ctx->h_len[tid] + 1) * sizeof(int32_t), (hipStream_t)stream));
+    HIP_TRY(ctx, im::launch_fill_zero((ctx->*which).data + ctx->h_asc_off[tid], (int64_t)ctx->h_len[tid] + 1, (hipStream_t)stream));
     return IM_OK;
 }
 
@@ -667,6 +667,16 @@ int im_set_insert_ranges(im_ctx* ctx, int32_t n, const char* const* names_in, co
     HIP_TRY(ctx, hipMalloc(&ctx->rg_blob, total + 256));
     HIP_TRY(ctx, hipMemcpy(ctx->rg_blob, host.data(), total, hipMemcpyHostToDevice));
     ctx->rg.blob = (const uint8_t*)ctx->rg_blob; ctx->rg.n = n; ctx->rg.bytes = (int32_t)total;
+    // "generic" as rg_lookup (im_rg.hpp) finds it: its bin's chain head to tail, strncmp over the seven bytes, the LAST hit wins
+    {
+        const char* gname = "generic";
+        uint32_t h = 5381u;
+        for (int k = 6; k >= 0; k--) h += (h << 5) + (uint32_t)(int)gname[k];
+        const int gb = (int)(h & 15u);
+        ctx->rg.generic_ok = 0; ctx->rg.generic_range = 0;
+        for (int32_t k = bin_start[gb]; k < bin_start[gb + 1]; k++)
+            if (name_len[k] >= 7 && memcmp(names.data() + name_off[k], gname, 7) == 0) { ctx->rg.generic_ok = 1; ctx->rg.generic_range = rmax[k]; }
+    }
     return IM_OK;
 }
 

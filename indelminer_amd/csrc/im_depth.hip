@@ -352,7 +352,32 @@ __global__ __launch_bounds__(kMedBlock) void depth_median_kernel(int32_t nq, con
     }
 }
 
+// zeroes n ints from p (16-byte aligned): 16-byte stores, the up to three ints behind them by the first lanes of workgroup 0 -- one launch
+constexpr int kFillBlock = 256;
+__global__ __launch_bounds__(kFillBlock) void fill_zero_kernel(int32_t* p, int64_t n)
+{
+    const int64_t quads = n / 4;
+    int4* q = reinterpret_cast<int4*>(p);
+    const int64_t stride = (int64_t)gridDim.x * kFillBlock;
+    for (int64_t k = (int64_t)blockIdx.x * kFillBlock + threadIdx.x; k < quads; k += stride) q[k] = make_int4(0, 0, 0, 0);
+    if (blockIdx.x == 0 && 4 * quads + threadIdx.x < n) p[4 * quads + threadIdx.x] = 0;
+}
+
 }  // namespace
+
+// A contig's run of a counted array back to zero (im_*_reset): one launch of our own.  A hipMemsetAsync of a run whose
+// length is not a multiple of the runtime's fill width came out as two dispatches per call (profiles/README.md).
+// p is 16-byte aligned: a contig's run starts at a multiple of 256 ints of a hipMalloc'ed array (im_set_reference).
+hipError_t launch_fill_zero(int32_t* p, int64_t n, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    if (reinterpret_cast<uintptr_t>(p) & 15u) return hipErrorInvalidValue;
+    int64_t b = (n / 4 + 4 * kFillBlock - 1) / (4 * kFillBlock);       // four 16-byte stores per lane
+    if (b < 1) b = 1;
+    if (b > 2048) b = 2048;
+    hipLaunchKernelGGL(fill_zero_kernel, dim3((int)b), dim3(kFillBlock), 0, stream, p, n);
+    return hipGetLastError();
+}
 
 int64_t depth_sums_ints(int64_t clen) { const int64_t t = (clen + 1 + kScanTile - 1) / kScanTile; return t + 1 + (t + kScanGroup - 1) / kScanGroup; }
 

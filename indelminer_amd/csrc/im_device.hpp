@@ -48,6 +48,9 @@ struct RgTable {
     const uint8_t* blob;
     int32_t n;
     int32_t bytes;
+    // must_find_hashtable(insertlengths, "generic") (records without an RG tag, src/indelminer.c:370), looked up once on the
+    // host when the table is set: the table does not change until the next im_set_insert_ranges
+    int32_t generic_ok, generic_range;
 };
 
 size_t triage_scratch_bytes(int32_t n_records);
@@ -80,6 +83,7 @@ hipError_t launch_flush_groupby(int32_t n_slots_layout, int32_t n_fl_layout, con
 constexpr int kScanTile = 8192;
 int64_t depth_sums_ints(int64_t clen);
 hipError_t launch_depth_scan_tiled(int32_t* depth, int64_t n, int32_t* sums, hipStream_t stream);
+hipError_t launch_fill_zero(int32_t* p, int64_t n, hipStream_t stream);       // n ints from p (16-byte aligned) to zero, one launch
 // memset + interval scatter (+1 at a + lo, -1 at b - hi of every clipped [a, b) with a + lo < b - hi) + scan; zeroes sums itself
 hipError_t launch_depth_build(int64_t clen, int32_t n_seg, const int32_t* seg_start, const int32_t* seg_len, int32_t lo, int32_t hi,
                               int32_t* data, int32_t* sums, hipStream_t stream);
