@@ -64,10 +64,10 @@ struct im_ctx {
     // genome-wide clipped-read counts, right and left (im_clip_enable): flank holds min_clip; never scanned, their sums stay null
     GenomeArray all_clip_r, all_clip_l;
     // -V: the keyed table of clipped bases (im_cliptail_enable); slots null: not enabled.  min_clip and min_mapq are its scatter's
-    im::TailTable tail = {nullptr, nullptr, 0};
+    im::KeyedTable tail = {nullptr, nullptr, 0};
     int32_t tail_min_clip = 0, tail_min_mapq = 0;
     // -M: the keyed table of pair links (im_pairlink_enable), an allocation of its own; slots null: not enabled
-    im::LinkTable link = {nullptr, nullptr, 0};
+    im::KeyedTable link = {nullptr, nullptr, 0};
     int32_t link_min_mapq = 0;
     // the median queries' histograms of queries of several slabs (im::launch_depth_median): zeros between calls, sized by the call that
     // needed the most; med_dirty: a call did not get to its end, the next one clears them
@@ -158,14 +158,87 @@ void free_reference(im_ctx* ctx)
         g->data = nullptr; g->sums = nullptr;
     }
     ctx->h_asc_off.clear(); ctx->h_len.clear(); ctx->ref_total = 0;
-    // the clip-tail table is keyed by the contigs of the reference that goes
-    if (ctx->tail.slots) (void)hipFree(ctx->tail.slots);
-    if (ctx->tail.counters) (void)hipFree(ctx->tail.counters);
-    ctx->tail = {nullptr, nullptr, 0};
-    // and so is the pair-link table
-    if (ctx->link.slots) (void)hipFree(ctx->link.slots);
-    if (ctx->link.counters) (void)hipFree(ctx->link.counters);
-    ctx->link = {nullptr, nullptr, 0};
+    // the clip-tail table and the pair-link table are keyed by the contigs of the reference that goes
+    for (im::KeyedTable* t : {&ctx->tail, &ctx->link}) {
+        if (t->slots) (void)hipFree(t->slots);
+        if (t->counters) (void)hipFree(t->counters);
+        *t = {nullptr, nullptr, 0};
+    }
+}
+
+// ---- the keyed table (im_keyed.hpp) behind the clip tails (im_ctx::tail) and the pair links (im_ctx::link) ----------
+
+// The checks both tables share; then, unless the member is enabled already -- which the caller has looked at, and compares its own
+// parameters for -- its slots and counters allocated, cleared and waited for.  who: the entry point, for the messages.
+int keyed_enable(im_ctx* ctx, im::KeyedTable im_ctx::*which, const char* who, int32_t log2_slots)
+{
+    if (log2_slots < 6 || log2_slots > 30) { set_err(ctx, "%s: log2_slots %d, must be 6 .. 30", who, log2_slots); return IM_E_ARG; }
+    if (ctx->n_contigs > (1 << 24)) { set_err(ctx, "%s: more than 2^24 contigs", who); return IM_E_ARG; }
+    if ((ctx->*which).slots) return IM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)16 << log2_slots;
+    unsigned long long* slots = nullptr;
+    unsigned long long* counters = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&slots, bytes));
+    if (hipMalloc((void**)&counters, 2 * sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(slots); set_err(ctx, "%s: out of device memory", who); return IM_E_HIP; }
+    ctx->*which = {slots, counters, log2_slots};
+    HIP_TRY(ctx, hipMemsetAsync(slots, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+int keyed_reset(im_ctx* ctx, const im::KeyedTable& T, void* stream)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemsetAsync(T.slots, 0, (size_t)16 << T.log2_slots, (hipStream_t)stream));
+    HIP_TRY(ctx, hipMemsetAsync(T.counters, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream));
+    return IM_OK;
+}
+
+// the two counters, copied on the context's stream behind what the caller has queued there, and the ONE wait of its call
+int keyed_counters(im_ctx* ctx, const im::KeyedTable& T, unsigned long long counters[2])
+{
+    HIP_TRY(ctx, hipMemcpyAsync(counters, T.counters, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+// the same, for a query: whether the table has dropped an entry, so that the caller blanks its answers -- none, not a wrong one
+int keyed_overflowed(im_ctx* ctx, const im::KeyedTable& T, bool* over)
+{
+    unsigned long long counters[2] = {0, 0};
+    const int rc = keyed_counters(ctx, T, counters);
+    *over = counters[1] > 0;
+    return rc;
+}
+
+int keyed_stats(im_ctx* ctx, const im::KeyedTable& T, uint64_t* stored, uint64_t* dropped)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long counters[2] = {0, 0};
+    const int rc = keyed_counters(ctx, T, counters);
+    if (rc) return rc;
+    const unsigned long long half = 1ull << (T.log2_slots - 1);
+    *stored = counters[0] < half ? counters[0] : half; *dropped = counters[1];
+    return IM_OK;
+}
+
+// The workspace as columns of n elements for the entry points of either table: column k at k * up256(4 n) bytes (a column of 8-byte
+// elements takes two), host -> device and back on the context's stream.
+struct WsColumns {
+    im_ctx* ctx;
+    size_t n, sb;
+    template <class T> T* at(int k) const { return (T*)((char*)ctx->ws + k * sb); }
+    int down(int k, const void* host, size_t elem) const { HIP_TRY(ctx, hipMemcpyAsync(at<char>(k), host, elem * n, hipMemcpyHostToDevice, ctx->stream)); return IM_OK; }
+    int up(int k, void* host, size_t elem) const { HIP_TRY(ctx, hipMemcpyAsync(host, at<char>(k), elem * n, hipMemcpyDeviceToHost, ctx->stream)); return IM_OK; }
+};
+
+int ws_columns(im_ctx* ctx, int32_t n, int k, WsColumns* C)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    *C = {ctx, (size_t)n, up256(sizeof(int32_t) * (size_t)n)};
+    return ensure_ws(ctx, k * C->sb);
 }
 
 void free_array(ContigArray& a)
@@ -1188,26 +1261,14 @@ int im_cliptail_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq, int32_t 
     if (!ctx) return IM_E_ARG;
     if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
     if (min_clip < 1) { set_err(ctx, "im_cliptail_enable: min_clip %d, must be >= 1", min_clip); return IM_E_ARG; }
-    if (log2_slots < 6 || log2_slots > 30) { set_err(ctx, "im_cliptail_enable: log2_slots %d, must be 6 .. 30", log2_slots); return IM_E_ARG; }
-    if (ctx->n_contigs > (1 << 24)) { set_err(ctx, "im_cliptail_enable: more than 2^24 contigs"); return IM_E_ARG; }
-    if (ctx->tail.slots) {
-        if (min_clip != ctx->tail_min_clip || min_mapq != ctx->tail_min_mapq || log2_slots != ctx->tail.log2_slots) {
-            set_err(ctx, "im_cliptail_enable: already enabled with min_clip %d, min_mapq %d, log2_slots %d", ctx->tail_min_clip, ctx->tail_min_mapq, ctx->tail.log2_slots);
-            return IM_E_ARG;
-        }
-        return IM_OK;
+    const bool enabled = ctx->tail.slots;
+    const int rc = keyed_enable(ctx, &im_ctx::tail, "im_cliptail_enable", log2_slots);
+    if (rc) return rc;
+    if (enabled && (min_clip != ctx->tail_min_clip || min_mapq != ctx->tail_min_mapq || log2_slots != ctx->tail.log2_slots)) {
+        set_err(ctx, "im_cliptail_enable: already enabled with min_clip %d, min_mapq %d, log2_slots %d", ctx->tail_min_clip, ctx->tail_min_mapq, ctx->tail.log2_slots);
+        return IM_E_ARG;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)16 << log2_slots;
-    unsigned long long* slots = nullptr;
-    unsigned long long* counters = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&slots, bytes));
-    if (hipMalloc((void**)&counters, 2 * sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(slots); set_err(ctx, "im_cliptail_enable: out of device memory"); return IM_E_HIP; }
-    ctx->tail = {slots, counters, log2_slots};
     ctx->tail_min_clip = min_clip; ctx->tail_min_mapq = min_mapq;
-    HIP_TRY(ctx, hipMemsetAsync(slots, 0, bytes, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return IM_OK;
 }
 
@@ -1232,19 +1293,10 @@ int im_cliptail_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, con
         if (nbases[i] < 1 || nbases[i] > 32) { set_err(ctx, "im_cliptail_add: entry %d: %d bases, must be 1 .. 32", i, (int)nbases[i]); return IM_E_ARG; }
     }
     if (n == 0) return IM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = up256(sizeof(int32_t) * (size_t)n);
-    int rc = ensure_ws(ctx, 5 * sb);
-    if (rc) return rc;
-    int32_t* d_pos = (int32_t*)ctx->ws;
-    uint32_t* d_planes = (uint32_t*)((char*)ctx->ws + sb);          // two words per entry
-    uint8_t* d_side = (uint8_t*)ctx->ws + 3 * sb;
-    uint8_t* d_nb = (uint8_t*)ctx->ws + 4 * sb;
-    HIP_TRY(ctx, hipMemcpyAsync(d_pos, pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_planes, planes, 2 * sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_side, side, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_nb, nbases, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, im::launch_cliptail_add(n, tid, ctx->h_len[tid], d_pos, d_side, d_nb, d_planes, ctx->tail, ctx->stream));
+    WsColumns C;                                                    // pos, planes (two words per entry: two columns), side, bases
+    int rc = ws_columns(ctx, n, 5, &C);
+    if (rc || (rc = C.down(0, pos, 4)) || (rc = C.down(1, planes, 8)) || (rc = C.down(3, side, 1)) || (rc = C.down(4, nbases, 1))) return rc;
+    HIP_TRY(ctx, im::launch_cliptail_add(n, tid, ctx->h_len[tid], C.at<int32_t>(0), C.at<uint8_t>(3), C.at<uint8_t>(4), C.at<uint32_t>(1), ctx->tail, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return IM_OK;
 }
@@ -1259,23 +1311,16 @@ int im_cliptail_verify(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* pr, 
     if (max_shift < 0 || max_shift > 32) { set_err(ctx, "im_cliptail_verify: max_shift %d, must be 0 .. 32", max_shift); return IM_E_ARG; }
     if (nq == 0) return IM_OK;
     if (!pr || !pl || !v_right || !v_left || !shift || !stored_right || !stored_left) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = up256(sizeof(int32_t) * (size_t)nq);
-    int rc = ensure_ws(ctx, 7 * sb);
-    if (rc) return rc;
-    int32_t* d_in[2]; uint32_t* d_out[5];
-    for (int k = 0; k < 2; k++) d_in[k] = (int32_t*)((char*)ctx->ws + k * sb);
-    for (int k = 0; k < 5; k++) d_out[k] = (uint32_t*)((char*)ctx->ws + (2 + k) * sb);
-    uint32_t* h_out[5] = {v_right, v_left, (uint32_t*)shift, stored_right, stored_left};
-    unsigned long long counters[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(d_in[0], pr, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_in[1], pl, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, im::launch_cliptail_verify(nq, tid, d_in[0], d_in[1], max_shift, ctx->ref_ascii + ctx->h_asc_off[tid], ctx->h_len[tid], ctx->tail,
-                                            d_out[0], d_out[1], (int32_t*)d_out[2], d_out[3], d_out[4], ctx->stream));
-    for (int k = 0; k < 5; k++) HIP_TRY(ctx, hipMemcpyAsync(h_out[k], d_out[k], sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (counters[1] > 0) for (int k = 0; k < 5; k++) memset(h_out[k], 0xFF, sizeof(uint32_t) * (size_t)nq);     // no answer, not a wrong one
+    WsColumns C;                                                    // pr, pl, then the five answers
+    int rc = ws_columns(ctx, nq, 7, &C);
+    if (rc || (rc = C.down(0, pr, 4)) || (rc = C.down(1, pl, 4))) return rc;
+    HIP_TRY(ctx, im::launch_cliptail_verify(nq, tid, C.at<int32_t>(0), C.at<int32_t>(1), max_shift, ctx->ref_ascii + ctx->h_asc_off[tid], ctx->h_len[tid], ctx->tail,
+                                            C.at<uint32_t>(2), C.at<uint32_t>(3), C.at<int32_t>(4), C.at<uint32_t>(5), C.at<uint32_t>(6), ctx->stream));
+    void* const h_out[5] = {v_right, v_left, shift, stored_right, stored_left};
+    for (int k = 0; k < 5 && !rc; k++) rc = C.up(2 + k, h_out[k], 4);
+    bool over = false;
+    if (rc || (rc = keyed_overflowed(ctx, ctx->tail, &over))) return rc;
+    if (over) for (int k = 0; k < 5; k++) memset(h_out[k], 0xFF, sizeof(uint32_t) * (size_t)nq);
     return IM_OK;
 }
 
@@ -1290,27 +1335,15 @@ int im_cliptail_consensus(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* p
     if (nq == 0) return IM_OK;
     if (!pos || !side || !entries || !len || !planes || !agree) return IM_E_ARG;
     for (int32_t q = 0; q < nq; q++) if (side[q] > 1) { set_err(ctx, "im_cliptail_consensus: query %d: side %d, must be 0 (right) or 1 (left)", q, (int)side[q]); return IM_E_ARG; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = up256(sizeof(int32_t) * (size_t)nq);
-    int rc = ensure_ws(ctx, 7 * sb);
-    if (rc) return rc;
-    int32_t* d_pos = (int32_t*)ctx->ws;
-    uint8_t* d_side = (uint8_t*)ctx->ws + sb;
-    uint32_t* d_entries = (uint32_t*)((char*)ctx->ws + 2 * sb);
-    uint32_t* d_len = (uint32_t*)((char*)ctx->ws + 3 * sb);
-    uint32_t* d_agree = (uint32_t*)((char*)ctx->ws + 4 * sb);
-    uint32_t* d_planes = (uint32_t*)((char*)ctx->ws + 5 * sb);      // two words per query
-    unsigned long long counters[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(d_pos, pos, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_side, side, (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, im::launch_cliptail_consensus(nq, tid, d_pos, d_side, min_cover, ctx->h_len[tid], ctx->tail, d_entries, d_len, d_planes, d_agree, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(entries, d_entries, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(len, d_len, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(agree, d_agree, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(planes, d_planes, 2 * sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (counters[1] > 0) {                                          // no answer, not a wrong one
+    WsColumns C;                                                    // pos, side, entries, len, agree, planes (two words per query)
+    int rc = ws_columns(ctx, nq, 7, &C);
+    if (rc || (rc = C.down(0, pos, 4)) || (rc = C.down(1, side, 1))) return rc;
+    HIP_TRY(ctx, im::launch_cliptail_consensus(nq, tid, C.at<int32_t>(0), C.at<uint8_t>(1), min_cover, ctx->h_len[tid], ctx->tail, C.at<uint32_t>(2),
+                                               C.at<uint32_t>(3), C.at<uint32_t>(5), C.at<uint32_t>(4), ctx->stream));
+    bool over = false;
+    if ((rc = C.up(2, entries, 4)) || (rc = C.up(3, len, 4)) || (rc = C.up(4, agree, 4)) || (rc = C.up(5, planes, 8)) ||
+        (rc = keyed_overflowed(ctx, ctx->tail, &over))) return rc;
+    if (over) {
         memset(entries, 0xFF, sizeof(uint32_t) * (size_t)nq); memset(len, 0xFF, sizeof(uint32_t) * (size_t)nq);
         memset(agree, 0xFF, sizeof(uint32_t) * (size_t)nq); memset(planes, 0xFF, 2 * sizeof(uint32_t) * (size_t)nq);
     }
@@ -1436,10 +1469,10 @@ static int pile_pairs_arrays(im_ctx* ctx, const char* who, bool inverted, const 
     for (int k = 0; k < 9; k++) all = all && (cap == 0 || out[k]);
     if (!all) return IM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    unsigned long long counters[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (counters[1] > 0) { *n_found = -1; return IM_OK; }           // no answer, not a wrong one
+    bool over = false;
+    rc = keyed_overflowed(ctx, ctx->tail, &over);
+    if (rc) return rc;
+    if (over) { *n_found = -1; return IM_OK; }
     const size_t ob = up256(sizeof(int32_t) * (size_t)(cap ? cap : 1));
     PeakLists P;
     rc = peak_lists(ctx, C, min_reads, reach, 10 * ob, &P);
@@ -1517,22 +1550,13 @@ int im_clip_inverted(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach,
 int im_cliptail_reset(im_ctx* ctx, void* stream)
 {
     if (!ctx || !ctx->tail.slots) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->tail.slots, 0, (size_t)16 << ctx->tail.log2_slots, (hipStream_t)stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->tail.counters, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream));
-    return IM_OK;
+    return keyed_reset(ctx, ctx->tail, stream);
 }
 
 int im_cliptail_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped)
 {
     if (!ctx || !ctx->tail.slots || !stored || !dropped) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    unsigned long long counters[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->tail.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned long long half = 1ull << (ctx->tail.log2_slots - 1);
-    *stored = counters[0] < half ? counters[0] : half; *dropped = counters[1];
-    return IM_OK;
+    return keyed_stats(ctx, ctx->tail, stored, dropped);
 }
 
 // ---- pair links: the read pairs of an abnormal orientation, counted between two windows (-M) ----------
@@ -1541,26 +1565,14 @@ int im_pairlink_enable(im_ctx* ctx, int32_t min_mapq, int32_t log2_slots)
 {
     if (!ctx) return IM_E_ARG;
     if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
-    if (log2_slots < 6 || log2_slots > 30) { set_err(ctx, "im_pairlink_enable: log2_slots %d, must be 6 .. 30", log2_slots); return IM_E_ARG; }
-    if (ctx->n_contigs > (1 << 24)) { set_err(ctx, "im_pairlink_enable: more than 2^24 contigs"); return IM_E_ARG; }
-    if (ctx->link.slots) {
-        if (min_mapq != ctx->link_min_mapq || log2_slots != ctx->link.log2_slots) {
-            set_err(ctx, "im_pairlink_enable: already enabled with min_mapq %d, log2_slots %d", ctx->link_min_mapq, ctx->link.log2_slots);
-            return IM_E_ARG;
-        }
-        return IM_OK;
+    const bool enabled = ctx->link.slots;
+    const int rc = keyed_enable(ctx, &im_ctx::link, "im_pairlink_enable", log2_slots);
+    if (rc) return rc;
+    if (enabled && (min_mapq != ctx->link_min_mapq || log2_slots != ctx->link.log2_slots)) {
+        set_err(ctx, "im_pairlink_enable: already enabled with min_mapq %d, log2_slots %d", ctx->link_min_mapq, ctx->link.log2_slots);
+        return IM_E_ARG;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)16 << log2_slots;
-    unsigned long long* slots = nullptr;
-    unsigned long long* counters = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&slots, bytes));
-    if (hipMalloc((void**)&counters, 2 * sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(slots); set_err(ctx, "im_pairlink_enable: out of device memory"); return IM_E_HIP; }
-    ctx->link = {slots, counters, log2_slots};
     ctx->link_min_mapq = min_mapq;
-    HIP_TRY(ctx, hipMemsetAsync(slots, 0, bytes, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return IM_OK;
 }
 
@@ -1583,17 +1595,10 @@ int im_pairlink_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, con
     for (int32_t i = 0; i < n; i++)
         if (kind[i] > 2) { set_err(ctx, "im_pairlink_add: link %d: kind %d, must be 0 (everted), 1 (forward) or 2 (reverse)", i, (int)kind[i]); return IM_E_ARG; }
     if (n == 0) return IM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = up256(sizeof(int32_t) * (size_t)n);
-    int rc = ensure_ws(ctx, 3 * sb);
-    if (rc) return rc;
-    int32_t* d_pos = (int32_t*)ctx->ws;
-    int32_t* d_mpos = (int32_t*)((char*)ctx->ws + sb);
-    uint8_t* d_kind = (uint8_t*)ctx->ws + 2 * sb;
-    HIP_TRY(ctx, hipMemcpyAsync(d_pos, pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_mpos, mpos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_kind, kind, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, im::launch_pairlink_add(n, tid, ctx->h_len[tid], d_pos, d_mpos, d_kind, ctx->link, ctx->stream));
+    WsColumns C;                                                    // pos, mpos, kind
+    int rc = ws_columns(ctx, n, 3, &C);
+    if (rc || (rc = C.down(0, pos, 4)) || (rc = C.down(1, mpos, 4)) || (rc = C.down(2, kind, 1))) return rc;
+    HIP_TRY(ctx, im::launch_pairlink_add(n, tid, ctx->h_len[tid], C.at<int32_t>(0), C.at<int32_t>(1), C.at<uint8_t>(2), ctx->link, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return IM_OK;
 }
@@ -1613,45 +1618,29 @@ int im_pairlink_count(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kind,
         // the wave walks one probe run per 256-base bucket of [a0, a1]: 257 at the most
         if ((int64_t)a1[q] - (int64_t)a0[q] > 65535) { set_err(ctx, "im_pairlink_count: query %d: a1 - a0 = %lld, must be <= 65535", q, (long long)a1[q] - (long long)a0[q]); return IM_E_ARG; }
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = up256(sizeof(int32_t) * (size_t)nq);
-    int rc = ensure_ws(ctx, 6 * sb);
-    if (rc) return rc;
+    WsColumns C;                                                    // a0, a1, b0, b1, kind, the counts
+    int rc = ws_columns(ctx, nq, 6, &C);
     const int32_t* h_in[4] = {a0, a1, b0, b1};
-    int32_t* d_in[4];
-    for (int k = 0; k < 4; k++) d_in[k] = (int32_t*)((char*)ctx->ws + k * sb);
-    uint8_t* d_kind = (uint8_t*)ctx->ws + 4 * sb;
-    uint32_t* d_out = (uint32_t*)((char*)ctx->ws + 5 * sb);
-    unsigned long long counters[2] = {0, 0};
-    for (int k = 0; k < 4; k++) HIP_TRY(ctx, hipMemcpyAsync(d_in[k], h_in[k], sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_kind, kind, (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, im::launch_pairlink_count(nq, tid, d_kind, d_in[0], d_in[1], d_in[2], d_in[3], min_sep, ctx->h_len[tid], ctx->link, d_out, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(count_out, d_out, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->link.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (counters[1] > 0) memset(count_out, 0xFF, sizeof(uint32_t) * (size_t)nq);       // no answer, not a wrong one
+    for (int k = 0; k < 4 && !rc; k++) rc = C.down(k, h_in[k], 4);
+    if (rc || (rc = C.down(4, kind, 1))) return rc;
+    HIP_TRY(ctx, im::launch_pairlink_count(nq, tid, C.at<uint8_t>(4), C.at<int32_t>(0), C.at<int32_t>(1), C.at<int32_t>(2), C.at<int32_t>(3), min_sep, ctx->h_len[tid],
+                                           ctx->link, C.at<uint32_t>(5), ctx->stream));
+    bool over = false;
+    if ((rc = C.up(5, count_out, 4)) || (rc = keyed_overflowed(ctx, ctx->link, &over))) return rc;
+    if (over) memset(count_out, 0xFF, sizeof(uint32_t) * (size_t)nq);
     return IM_OK;
 }
 
 int im_pairlink_reset(im_ctx* ctx, void* stream)
 {
     if (!ctx || !ctx->link.slots) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->link.slots, 0, (size_t)16 << ctx->link.log2_slots, (hipStream_t)stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->link.counters, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream));
-    return IM_OK;
+    return keyed_reset(ctx, ctx->link, stream);
 }
 
 int im_pairlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped)
 {
     if (!ctx || !ctx->link.slots || !stored || !dropped) return IM_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    unsigned long long counters[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(counters, ctx->link.counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned long long half = 1ull << (ctx->link.log2_slots - 1);
-    *stored = counters[0] < half ? counters[0] : half; *dropped = counters[1];
-    return IM_OK;
+    return keyed_stats(ctx, ctx->link, stored, dropped);
 }
 
 int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64_t* t_off,

@@ -6,15 +6,11 @@
 // (tid, position, side), position = refend for a right clip (side 0) and pos for a left clip (side 1).  Nothing is stored when one
 // of the n bases is not A / C / G / T or when the packed bases do not lie inside the record.
 //
-// THE TABLE: 2^k slots of 16 bytes, open addressing, a multimap.
+// THE TABLE is the keyed table of im_keyed.hpp (slots, tickets, claim, walk), with
 //   word 0   the key: bit 63 set (an empty slot is 0) | tid << 39 | position << 7 | side << 6 | n           (tid < 2^24, n = 1 .. 32)
 //   word 1   the payload: the n bases as 2-bit codes (A 0, C 1, G 2, T 3) in two planes, low bits in bits 0 .. 31, high bits in
 //            bits 32 .. 63; bit i of a plane belongs to the base at distance i from the junction
-// The home slot of a key is ((key >> 6) * 0x9E3779B97F4A7C15) >> (64 - k): n does not enter, so every entry of one (tid, position,
-// side) lies on one probe run.  Probing is linear and wraps.  An insert first draws a ticket (returning atomic add); tickets at or
-// above 2^k / 2 store nothing and are counted in `dropped`, so at least half of the slots stay empty, every probe run ends at an
-// empty slot, and the number stored is exactly min(inserts, 2^k / 2).  A slot is claimed by a 64-bit compare-and-swap from 0, its
-// payload is a plain store behind it: readers are later launches.  Every probe loop is bounded by the slot count as well.
+// key >> 6 is what enters the hash: n does not, so every entry of one (tid, position, side) lies on one probe run.
 //
 //   cliptail_scatter   one lane per delivered record; the ~1 % of lanes that clip read their packed bases and insert, on tickets
 //                      their workgroup draws with one atomic add
@@ -25,7 +21,7 @@
 //                      peaks of clipL in front of it (-U); <true>: a peak of either array with the peaks of the SAME array behind it,
 //                      against the reference's reverse complement (-N)
 
-#include "im_device.hpp"
+#include "im_keyed.hpp"
 #include "im_spanrec.hpp"
 
 namespace im {
@@ -40,43 +36,13 @@ constexpr int kTailBases = 32;
 constexpr int kTailMaxShift = 32;
 static_assert(kTailBases + kTailMaxShift == 64, "the reference window of a query is one wavefront");
 
-constexpr uint64_t kTailUsed = 1ull << 63;
-constexpr uint64_t kTailHashMul = 0x9E3779B97F4A7C15ull;
-
 __device__ __forceinline__ uint64_t tail_key(int32_t tid, int64_t pos, uint32_t side, uint32_t n)
 {
-    return kTailUsed | ((uint64_t)(uint32_t)tid << 39) | ((uint64_t)(uint32_t)pos << 7) | ((uint64_t)side << 6) | n;
+    return kKeyedUsed | ((uint64_t)(uint32_t)tid << 39) | ((uint64_t)(uint32_t)pos << 7) | ((uint64_t)side << 6) | n;
 }
 
-__device__ __forceinline__ uint64_t tail_home(uint64_t key, int32_t log2_slots) { return ((key >> 6) * kTailHashMul) >> (64 - log2_slots); }
-
-// A ticket decides whether an entry is stored: tickets at or above half of the slots are counted in counters[1] and dropped.
-__device__ __forceinline__ bool tail_admit(const TailTable& T, unsigned long long ticket)
-{
-    if (ticket < (1ull << T.log2_slots) / 2ull) return true;
-    atomicAdd(&T.counters[1], 1ull);
-    return false;
-}
-
-// An admitted entry into the first empty slot of its key's probe run (there is one: half of the slots stay empty).
-__device__ __forceinline__ void tail_place(const TailTable& T, uint64_t key, uint64_t payload)
-{
-    const uint64_t slots = 1ull << T.log2_slots, mask = slots - 1ull;
-    uint64_t s = tail_home(key, T.log2_slots);
-    for (uint64_t step = 0; step < slots; step++, s = (s + 1ull) & mask) {
-        unsigned long long* k = &T.slots[2ull * s];
-        // the home slot gets the compare-and-swap at once (in a table at most half full it is mostly empty: one trip to memory,
-        // not two); further along a run a slot that reads non-zero stays taken and is passed by a load
-        if (step != 0ull && __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) continue;
-        if (atomicCAS(k, 0ull, (unsigned long long)key) == 0ull) { T.slots[2ull * s + 1ull] = payload; return; }
-    }
-}
-
-// One entry in, the ticket drawn by the lane itself (counters[0]: inserts): the record-at-a-time form.
-__device__ __forceinline__ void tail_insert(const TailTable& T, uint64_t key, uint64_t payload)
-{
-    if (tail_admit(T, atomicAdd(&T.counters[0], 1ull))) tail_place(T, key, payload);
-}
+// the home slot of an entry, and of the query for its (tid, position, side): n stays out of the hash
+__device__ __forceinline__ uint64_t tail_home(uint64_t key, int32_t log2_slots) { return keyed_home(key >> 6, log2_slots); }
 
 // per nibble of x (a 4-bit base code each): bit 0 of the nibble set iff the code is one of 1, 2, 4, 8
 __device__ __forceinline__ uint32_t nib_one_hot(uint32_t x)
@@ -126,7 +92,7 @@ struct TailScatterArgs {
     const int32_t* len;
     int32_t n_contigs;
     int32_t min_clip, min_mapq;
-    TailTable tab;
+    KeyedTable tab;
 };
 
 // what a lane of the scatter has to insert: at most one entry per clipping end
@@ -170,43 +136,29 @@ __device__ __forceinline__ TailPair tail_entries(const TailScatterArgs& A, int64
     return P;
 }
 
-// The tickets of a workgroup are drawn by ONE atomic add: returning atomics of a whole chunk on one address take turns, and one
-// per clipped read made them most of the launch.  So the lanes count their entries through two ballots per wave and 64 bytes of
-// LDS, thread 0 adds the workgroup's total to counters[0] and every lane's ticket is that base + its rank.  The number stored stays
-// exactly min(inserts, slots / 2).
+// one ticket draw per workgroup (keyed_block_tickets has the reason), a lane holding up to two entries
 __global__ __launch_bounds__(kTailBlock) void cliptail_scatter_kernel(TailScatterArgs A)
 {
-    __shared__ uint32_t s_wave[kTailBlock / 64];
-    __shared__ unsigned long long s_base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const TailPair P = tail_entries(A, (int64_t)blockIdx.x * kTailBlock + t);
-    const uint64_t one = __ballot(P.n >= 1u), two = __ballot(P.n == 2u);
-    const uint64_t below = (1ull << lane) - 1ull;
-    const uint32_t rank = (uint32_t)__builtin_popcountll(one & below) + (uint32_t)__builtin_popcountll(two & below);
-    if (lane == 0) s_wave[wave] = (uint32_t)__builtin_popcountll(one) + (uint32_t)__builtin_popcountll(two);
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kTailBlock / 64; w++) { before += w < wave ? s_wave[w] : 0u; total += s_wave[w]; }
-    if (total == 0u) return;                                        // uniform over the workgroup
-    if (t == 0) s_base = atomicAdd(&A.tab.counters[0], (unsigned long long)total);
-    __syncthreads();
-    const unsigned long long ticket = s_base + before + rank;
-    if (P.n >= 1u && tail_admit(A.tab, ticket)) tail_place(A.tab, P.key[0], P.payload[0]);
-    if (P.n == 2u && tail_admit(A.tab, ticket + 1ull)) tail_place(A.tab, P.key[1], P.payload[1]);
+    const TailPair P = tail_entries(A, (int64_t)blockIdx.x * kTailBlock + threadIdx.x);
+    unsigned long long ticket;
+    if (!keyed_block_tickets<kTailBlock, 2>(A.tab, P.n, &ticket)) return;
+    const int32_t k = A.tab.log2_slots;
+    if (P.n >= 1u && keyed_admit(A.tab, ticket)) keyed_place(A.tab, tail_home(P.key[0], k), P.key[0], P.payload[0]);
+    if (P.n == 2u && keyed_admit(A.tab, ticket + 1ull)) keyed_place(A.tab, tail_home(P.key[1], k), P.key[1], P.payload[1]);
 }
 
 // the record-at-a-time path: one lane per entry the host named; positions outside [0, clen] are dropped (no ticket)
 __global__ __launch_bounds__(kTailWaveBlock) void cliptail_add_kernel(int32_t n, int32_t tid, int64_t clen, const int32_t* __restrict__ pos,
                                                                  const uint8_t* __restrict__ side, const uint8_t* __restrict__ nbases,
-                                                                 const uint32_t* __restrict__ planes, TailTable tab)
+                                                                 const uint32_t* __restrict__ planes, KeyedTable tab)
 {
     const int64_t i = (int64_t)blockIdx.x * kTailWaveBlock + threadIdx.x;
     if (i >= n) return;
     const int64_t p = pos[i];
     if (p < 0 || p > clen) return;
     const uint32_t nb = nbases[i], m = nb >= 32u ? 0xFFFFFFFFu : (1u << nb) - 1u;
-    tail_insert(tab, tail_key(tid, p, side[i], nb), ((uint64_t)(planes[2 * i + 1] & m) << 32) | (planes[2 * i] & m));
+    const uint64_t key = tail_key(tid, p, side[i], nb);
+    keyed_insert(tab, tail_home(key, tab.log2_slots), key, ((uint64_t)(planes[2 * i + 1] & m) << 32) | (planes[2 * i] & m));
 }
 
 // the resident reference is upper-cased ASCII: A C G T -> 0 1 2 3, anything else is no base
@@ -229,32 +181,14 @@ __device__ __forceinline__ TailWindow tail_window(const uint8_t* __restrict__ re
     return W;
 }
 
-// The walk every query shares: the wave goes along the probe run of (tid, pos, side) 64 slots at a time until a batch shows an empty
-// slot.  each(has, key, slot) is called, by the whole wave, for every batch in which some lane's slot (in front of the first empty
-// one) holds an entry of the key: has says whether this lane's does.  Returns the entries stored at the key (wave-uniform); a
-// position outside [0, clen] has none.
+// The walk of the probe run of (tid, pos, side), whatever the entries' n: keyed_walk has each(has, key, slot).  Returns the entries
+// stored at the key (wave-uniform); a position outside [0, clen] has none.
 template <class Each>
-__device__ __forceinline__ uint32_t tail_walk(const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, int lane, Each each)
+__device__ __forceinline__ uint32_t tail_walk(const KeyedTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, int lane, Each each)
 {
-    uint32_t stored = 0;
     if (pos < 0 || pos > clen) return 0;
-    const uint64_t slots = 1ull << T.log2_slots, mask = slots - 1ull;
     const uint64_t want = tail_key(tid, pos, side, 0u) >> 6;
-    const uint64_t home = tail_home(want << 6, T.log2_slots);
-    for (uint64_t base = 0; base < slots; base += 64ull) {
-        const uint64_t s = (home + base + (uint64_t)lane) & mask;
-        const uint64_t key = T.slots[2ull * s];
-        const uint64_t empty = __ballot(key == 0ull);
-        const int stop = empty ? (int)__builtin_ctzll(empty) : 64;
-        const bool has = lane < stop && (key >> 6) == want;
-        const uint64_t holders = __ballot(has);
-        if (holders) {
-            stored += (uint32_t)__builtin_popcountll(holders);
-            each(has, key, s);
-        }
-        if (empty) break;
-    }
-    return stored;
+    return keyed_walk(T, tail_home(want << 6, T.log2_slots), [want](uint64_t key) { return (key >> 6) == want; }, lane, each);
 }
 
 // The shift-compare of one batch.  A lane whose slot holds an entry of the key (has; key: n in its low bits, payload: the two planes)
@@ -275,7 +209,7 @@ __device__ __forceinline__ uint32_t tail_shifts(bool has, uint64_t key, uint64_t
 
 // One side of a verify query: the walk, and the shift-compare of every batch that holds entries of the key.  Lane s gathers v(s).
 // Returns the entries stored at the key (wave-uniform); *v: this lane's v(lane).
-__device__ __forceinline__ uint32_t tail_side(const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, const TailWindow& W,
+__device__ __forceinline__ uint32_t tail_side(const KeyedTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, const TailWindow& W,
                                               bool compare, int32_t S, int lane, uint32_t* v)
 {
     uint32_t mine = 0;
@@ -319,7 +253,7 @@ __device__ __forceinline__ TailWindow tail_expected_window(const uint8_t* __rest
 // entries stay in the lanes, and a comparison costs no walk; a pile spread over several batches is walked per comparison.
 struct TailHeld { int batches; bool has; uint64_t key, payload; uint32_t stored; };
 
-__device__ __forceinline__ TailHeld tail_hold(const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, int lane)
+__device__ __forceinline__ TailHeld tail_hold(const KeyedTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen, int lane)
 {
     TailHeld H; H.batches = 0; H.has = false; H.key = 0; H.payload = 0;
     H.stored = tail_walk(T, tid, pos, side, clen, lane, [&](bool has, uint64_t key, uint64_t s) {
@@ -329,7 +263,7 @@ __device__ __forceinline__ TailHeld tail_hold(const TailTable& T, int32_t tid, i
 }
 
 // this lane's v(lane) of the held pile against the window W
-__device__ __forceinline__ uint32_t tail_held_shifts(const TailHeld& H, const TailTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen,
+__device__ __forceinline__ uint32_t tail_held_shifts(const TailHeld& H, const KeyedTable& T, int32_t tid, int64_t pos, uint32_t side, int64_t clen,
                                                      const TailWindow& W, int32_t S, int lane)
 {
     if (H.batches <= 1) return tail_shifts(H.has, H.key, H.payload, W, S, lane);
@@ -344,7 +278,7 @@ struct TailVerifyArgs {
     const int32_t* pl;
     const uint8_t* ref;         // the contig's ASCII bases
     int64_t clen;
-    TailTable tab;
+    KeyedTable tab;
     uint32_t* v_right;
     uint32_t* v_left;
     int32_t* shift;
@@ -452,7 +386,7 @@ struct TailConsensusArgs {
     const int32_t* pos;
     const uint8_t* side;
     int64_t clen;
-    TailTable tab;
+    KeyedTable tab;
     uint32_t* entries;
     uint32_t* len;
     uint32_t* planes;           // two per query: low bits, high bits
@@ -510,15 +444,13 @@ __global__ __launch_bounds__(kTailWaveBlock) void cliptail_consensus_kernel(Tail
 }  // namespace
 
 hipError_t launch_cliptail_consensus(int32_t nq, int32_t tid, const int32_t* pos, const uint8_t* side, int32_t min_cover, int64_t clen,
-                                     const TailTable& tab, uint32_t* entries, uint32_t* len, uint32_t* planes, uint32_t* agree, hipStream_t stream)
+                                     const KeyedTable& tab, uint32_t* entries, uint32_t* len, uint32_t* planes, uint32_t* agree, hipStream_t stream)
 {
     if (nq <= 0) return hipSuccess;
     TailConsensusArgs A;
     A.nq = nq; A.tid = tid; A.min_cover = min_cover; A.pos = pos; A.side = side; A.clen = clen; A.tab = tab;
     A.entries = entries; A.len = len; A.planes = planes; A.agree = agree;
-    int b = (nq + 3) / 4;
-    if (b > 2048) b = 2048;
-    hipLaunchKernelGGL(cliptail_consensus_kernel, dim3(b), dim3(kTailWaveBlock), 0, stream, A);
+    hipLaunchKernelGGL(cliptail_consensus_kernel, dim3(wave_grid(nq)), dim3(kTailWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 
@@ -530,14 +462,12 @@ hipError_t launch_cliptail_pairs(bool inverted, TailPairsArgs A, hipStream_t str
     // crossed: a wave per right peak, and nothing to pair it with while the left list is empty; inverted: a wave per peak of either list
     const int64_t waves = inverted ? (int64_t)A.n_right + A.n_left : A.n_left > 0 ? A.n_right : 0;
     if (e != hipSuccess || waves == 0) return e;
-    int64_t b = (waves + 3) / 4;
-    if (b > 2048) b = 2048;
-    if (inverted) hipLaunchKernelGGL(cliptail_pairs_kernel<true>, dim3((unsigned)b), dim3(kTailWaveBlock), 0, stream, A);
-    else hipLaunchKernelGGL(cliptail_pairs_kernel<false>, dim3((unsigned)b), dim3(kTailWaveBlock), 0, stream, A);
+    if (inverted) hipLaunchKernelGGL(cliptail_pairs_kernel<true>, dim3(wave_grid(waves)), dim3(kTailWaveBlock), 0, stream, A);
+    else hipLaunchKernelGGL(cliptail_pairs_kernel<false>, dim3(wave_grid(waves)), dim3(kTailWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 
-hipError_t launch_cliptail_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const im_dev_records& recs, const TailTable& tab,
+hipError_t launch_cliptail_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab,
                                    hipStream_t stream)
 {
     if (recs.n <= 0) return hipSuccess;
@@ -548,7 +478,7 @@ hipError_t launch_cliptail_scatter(const RefDev& ref, int32_t min_clip, int32_t 
 }
 
 hipError_t launch_cliptail_add(int32_t n, int32_t tid, int64_t clen, const int32_t* pos, const uint8_t* side, const uint8_t* nbases,
-                               const uint32_t* planes, const TailTable& tab, hipStream_t stream)
+                               const uint32_t* planes, const KeyedTable& tab, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(cliptail_add_kernel, dim3((n + kTailWaveBlock - 1) / kTailWaveBlock), dim3(kTailWaveBlock), 0, stream, n, tid, clen, pos, side, nbases, planes, tab);
@@ -556,16 +486,14 @@ hipError_t launch_cliptail_add(int32_t n, int32_t tid, int64_t clen, const int32
 }
 
 hipError_t launch_cliptail_verify(int32_t nq, int32_t tid, const int32_t* pr, const int32_t* pl, int32_t max_shift, const uint8_t* ref,
-                                  int64_t clen, const TailTable& tab, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
+                                  int64_t clen, const KeyedTable& tab, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
                                   uint32_t* stored_right, uint32_t* stored_left, hipStream_t stream)
 {
     if (nq <= 0) return hipSuccess;
     TailVerifyArgs A;
     A.nq = nq; A.tid = tid; A.max_shift = max_shift; A.pr = pr; A.pl = pl; A.ref = ref; A.clen = clen; A.tab = tab;
     A.v_right = v_right; A.v_left = v_left; A.shift = shift; A.stored_right = stored_right; A.stored_left = stored_left;
-    int b = (nq + 3) / 4;
-    if (b > 2048) b = 2048;
-    hipLaunchKernelGGL(cliptail_verify_kernel, dim3(b), dim3(kTailWaveBlock), 0, stream, A);
+    hipLaunchKernelGGL(cliptail_verify_kernel, dim3(wave_grid(nq)), dim3(kTailWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 

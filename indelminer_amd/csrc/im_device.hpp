@@ -139,28 +139,30 @@ hipError_t launch_clip_facing(const int32_t* right, const int32_t* left, int64_t
 // written, in no particular order
 hipError_t launch_clip_peaks(const int32_t* arr, int64_t clen, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count,
                              uint32_t* n_found, hipStream_t stream);
-// im_cliptail.hip: the clipped bases of clipped reads in a keyed table (-V).  slots: 2^log2_slots pairs (key, payload) of 64-bit
-// words, zeros = empty; counters[0]: inserts asked for, counters[1]: those dropped because half of the slots were taken
-struct TailTable {
+// The keyed table behind the clip tails (-V) and the pair links (-M), an allocation each; im_keyed.hpp has its definition.  slots:
+// 2^log2_slots pairs (key, payload) of 64-bit words, zeros = empty; counters[0]: inserts asked for, counters[1]: those dropped because
+// half of the slots were taken
+struct KeyedTable {
     unsigned long long* slots;
     unsigned long long* counters;
     int32_t log2_slots;
 };
+// im_cliptail.hip: the clipped bases of clipped reads in a keyed table (-V)
 // the records that clip under the clip scatter's rule -> one entry per clipping end whose nearest min(clip, 32) bases are all A/C/G/T
-hipError_t launch_cliptail_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const im_dev_records& recs, const TailTable& tab,
+hipError_t launch_cliptail_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab,
                                    hipStream_t stream);
 // one entry per host-named (position, side, bases, planes[2]: low-bit plane, high-bit plane); positions outside [0, clen] dropped
 hipError_t launch_cliptail_add(int32_t n, int32_t tid, int64_t clen, const int32_t* pos, const uint8_t* side, const uint8_t* nbases,
-                               const uint32_t* planes, const TailTable& tab, hipStream_t stream);
+                               const uint32_t* planes, const KeyedTable& tab, hipStream_t stream);
 // per query (pr, pl) on contig tid (ref: its ASCII bases): the entries at either key that continue behind the other breakpoint at the
 // best shift 0 .. max_shift <= 32, that shift (-1: none matched or pl <= pr), and the entries stored at the two keys
 hipError_t launch_cliptail_verify(int32_t nq, int32_t tid, const int32_t* pr, const int32_t* pl, int32_t max_shift, const uint8_t* ref,
-                                  int64_t clen, const TailTable& tab, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
+                                  int64_t clen, const KeyedTable& tab, uint32_t* v_right, uint32_t* v_left, int32_t* shift,
                                   uint32_t* stored_right, uint32_t* stored_left, hipStream_t stream);
 // per query (pos, side) on contig tid: the entries stored at the key, the bases covered by at least min_cover of them, their per-base
 // consensus as two planes (planes[2 q], planes[2 q + 1]) and the entries that agree with it; a position outside [0, clen] answers zeros
 hipError_t launch_cliptail_consensus(int32_t nq, int32_t tid, const int32_t* pos, const uint8_t* side, int32_t min_cover, int64_t clen,
-                                     const TailTable& tab, uint32_t* entries, uint32_t* len, uint32_t* planes, uint32_t* agree, hipStream_t stream);
+                                     const KeyedTable& tab, uint32_t* entries, uint32_t* len, uint32_t* planes, uint32_t* agree, hipStream_t stream);
 // Pairs of piles whose entries verify: at least min_verified at either pile at the chosen shift 0 .. max_shift <= 32.  Both peak lists
 // are ascending.  Crossed (-U): p1 of the right peaks, p2 of the left peaks, min_len <= p1 - p2 <= max_len, against the reference
 // behind the other pile; nothing is launched while either list is empty.  Inverted (-N): p1 < p2 of ONE list (side 0: the right peaks,
@@ -176,27 +178,21 @@ struct TailPairsArgs {
     int32_t min_len, max_len, max_shift, min_verified, cap;
     const uint8_t* ref;         // the contig's ASCII bases
     int64_t clen;
-    TailTable tab;
+    KeyedTable tab;
     uint32_t* col[10];
     uint32_t* n_found;
 };
 hipError_t launch_cliptail_pairs(bool inverted, TailPairsArgs A, hipStream_t stream);
-// im_pairlink.hip: the read pairs of an abnormal orientation in a keyed table of its own (-M), the clip-tail table's design: slots:
-// 2^log2_slots pairs (key, payload) of 64-bit words, zeros = empty; counters[0]: inserts asked for, counters[1]: those dropped
-struct LinkTable {
-    unsigned long long* slots;
-    unsigned long long* counters;
-    int32_t log2_slots;
-};
+// im_pairlink.hip: the read pairs of an abnormal orientation in a keyed table of its own (-M)
 // the records that are a link under the record rule (include/indelminer_amd.h, "Pair links") -> one entry each
-hipError_t launch_pairlink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const LinkTable& tab, hipStream_t stream);
+hipError_t launch_pairlink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream);
 // one entry per host-named (pos, mpos, kind 0 .. 2) of contig tid; a position outside [0, clen] drops the link
 hipError_t launch_pairlink_add(int32_t n, int32_t tid, int64_t clen, const int32_t* pos, const int32_t* mpos, const uint8_t* kind,
-                               const LinkTable& tab, hipStream_t stream);
+                               const KeyedTable& tab, hipStream_t stream);
 // per query (kind, [a0, a1], [b0, b1]) on contig tid, both intervals inclusive and clipped to [0, clen]: the links of that kind with pos
 // in the first, mpos in the second and mpos - pos >= min_sep; the caller holds a1 - a0 to 65 535
 hipError_t launch_pairlink_count(int32_t nq, int32_t tid, const uint8_t* kind, const int32_t* a0, const int32_t* a1, const int32_t* b0,
-                                 const int32_t* b1, int32_t min_sep, int64_t clen, const LinkTable& tab, uint32_t* count, hipStream_t stream);
+                                 const int32_t* b1, int32_t min_sep, int64_t clen, const KeyedTable& tab, uint32_t* count, hipStream_t stream);
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);

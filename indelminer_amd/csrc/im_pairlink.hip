@@ -5,23 +5,17 @@
 // (forward in front of reverse), stores ONE LINK (tid, kind, pos, mpos): kind 0 EVERTED (this read reverse, its mate forward: a tandem
 // duplication's pairs), 1 FORWARD (both forward: an inversion's left junction), 2 REVERSE (both reverse: its right junction).
 //
-// THE TABLE is the clip-tail table's design (im_cliptail.hip) with another key: 2^k slots of 16 bytes, open addressing, a multimap.
+// THE TABLE is the keyed table of im_keyed.hpp (slots, tickets, claim, walk), an allocation of its own, with
 //   word 0   the key: bit 63 set (an empty slot is 0) | tid << 26 | (pos >> 8) << 2 | kind            (tid < 2^24, pos < 2^31)
 //   word 1   the payload: pos | mpos << 32
-// The home slot of a key is (key * 0x9E3779B97F4A7C15) >> (64 - k): every link of one (tid, 256-base bucket, kind) lies on one probe
-// run.  Probing is linear and wraps.  An insert first draws a ticket; tickets at or above 2^k / 2 store nothing and are counted in
-// `dropped`, so half of the slots stay empty, every probe run ends at an empty slot and the number stored is exactly
-// min(inserts, 2^k / 2).  A slot is claimed by a 64-bit compare-and-swap from 0, its payload is a plain store behind it: readers are
-// later launches.  Every probe loop is bounded by the slot count as well.  The hash, admit, place and walk below are this file's own
-// copies of im_cliptail.hip's: the key has no per-entry field to leave out of the hash and the walk tests a payload instead of
-// handing a batch on, and that file's kernels keep their code to the byte.
+// The whole key enters the hash: every link of one (tid, 256-base bucket, kind) lies on one probe run.
 //
 //   pairlink_scatter   one lane per delivered record; the lanes that hold a link insert it, on tickets their workgroup draws with one
 //                      atomic add
 //   pairlink_add       one lane per link the host names (the record-at-a-time path)
 //   pairlink_count     one wave per query (kind, a0, a1, b0, b1): the links with pos in [a0, a1], mpos in [b0, b1], mpos - pos >= min_sep
 
-#include "im_device.hpp"
+#include "im_keyed.hpp"
 #include "im_rg.hpp"
 
 namespace im {
@@ -31,44 +25,18 @@ constexpr int kLinkBlock = 1024;      // records of a scatter workgroup: one tic
 constexpr int kLinkWaveBlock = 256;   // threads of the add and count kernels
 constexpr int kLinkBucketShift = 8;   // a bucket is 256 bases: a query window of 1 000 bases walks 4 or 5 probe runs
 
-constexpr uint64_t kLinkUsed = 1ull << 63;
-constexpr uint64_t kLinkHashMul = 0x9E3779B97F4A7C15ull;
-
 __device__ __forceinline__ uint64_t link_key(int32_t tid, int64_t bucket, uint32_t kind)
 {
-    return kLinkUsed | ((uint64_t)(uint32_t)tid << 26) | ((uint64_t)bucket << 2) | kind;
+    return kKeyedUsed | ((uint64_t)(uint32_t)tid << 26) | ((uint64_t)bucket << 2) | kind;
 }
-
-__device__ __forceinline__ uint64_t link_home(uint64_t key, int32_t log2_slots) { return (key * kLinkHashMul) >> (64 - log2_slots); }
 
 __device__ __forceinline__ uint64_t link_payload(int64_t pos, int64_t mpos) { return (uint64_t)(uint32_t)pos | ((uint64_t)(uint32_t)mpos << 32); }
-
-// A ticket decides whether a link is stored: tickets at or above half of the slots are counted in counters[1] and dropped.
-__device__ __forceinline__ bool link_admit(const LinkTable& T, unsigned long long ticket)
-{
-    if (ticket < (1ull << T.log2_slots) / 2ull) return true;
-    atomicAdd(&T.counters[1], 1ull);
-    return false;
-}
-
-// An admitted link into the first empty slot of its key's probe run (there is one: half of the slots stay empty).
-__device__ __forceinline__ void link_place(const LinkTable& T, uint64_t key, uint64_t payload)
-{
-    const uint64_t slots = 1ull << T.log2_slots, mask = slots - 1ull;
-    uint64_t s = link_home(key, T.log2_slots);
-    for (uint64_t step = 0; step < slots; step++, s = (s + 1ull) & mask) {
-        unsigned long long* k = &T.slots[2ull * s];
-        // the home slot gets the compare-and-swap at once; further along a run a slot that reads non-zero stays taken
-        if (step != 0ull && __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) continue;
-        if (atomicCAS(k, 0ull, (unsigned long long)key) == 0ull) { T.slots[2ull * s + 1ull] = payload; return; }
-    }
-}
 
 struct LinkScatterArgs {
     im_dev_records recs;
     const int32_t* len;
     int32_t n_contigs, min_mapq;
-    LinkTable tab;
+    KeyedTable tab;
 };
 
 // The record rule, on the 32-byte core alone.  Returns whether record i stores a link; *key, *payload: what it stores.
@@ -91,38 +59,26 @@ __device__ __forceinline__ bool link_of_record(const LinkScatterArgs& A, int64_t
     return true;
 }
 
-// The tickets of a workgroup are drawn by ONE atomic add (cliptail_scatter_kernel has the reason): the lanes count their links through
-// one ballot per wave and 64 bytes of LDS, thread 0 adds the workgroup's total to counters[0] and every lane's ticket is that base +
-// its rank.  A workgroup without a link -- most of them -- ends before the atomic.
+// one ticket draw per workgroup (keyed_block_tickets has the reason); a workgroup without a link -- most of them -- ends there
 __global__ __launch_bounds__(kLinkBlock) void pairlink_scatter_kernel(LinkScatterArgs A)
 {
-    __shared__ uint32_t s_wave[kLinkBlock / 64];
-    __shared__ unsigned long long s_base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     uint64_t key = 0, payload = 0;
-    const bool has = link_of_record(A, (int64_t)blockIdx.x * kLinkBlock + t, &key, &payload);
-    const uint64_t mine = __ballot(has);
-    const uint32_t rank = (uint32_t)__builtin_popcountll(mine & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[wave] = (uint32_t)__builtin_popcountll(mine);
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kLinkBlock / 64; w++) { before += w < wave ? s_wave[w] : 0u; total += s_wave[w]; }
-    if (total == 0u) return;                                        // uniform over the workgroup
-    if (t == 0) s_base = atomicAdd(&A.tab.counters[0], (unsigned long long)total);
-    __syncthreads();
-    if (has && link_admit(A.tab, s_base + before + rank)) link_place(A.tab, key, payload);
+    const bool has = link_of_record(A, (int64_t)blockIdx.x * kLinkBlock + threadIdx.x, &key, &payload);
+    unsigned long long ticket;
+    if (!keyed_block_tickets<kLinkBlock, 1>(A.tab, has ? 1u : 0u, &ticket)) return;
+    if (has && keyed_admit(A.tab, ticket)) keyed_place(A.tab, keyed_home(key, A.tab.log2_slots), key, payload);
 }
 
 // the record-at-a-time path: one lane per link the host named; positions outside [0, clen] are dropped (no ticket)
 __global__ __launch_bounds__(kLinkWaveBlock) void pairlink_add_kernel(int32_t n, int32_t tid, int64_t clen, const int32_t* __restrict__ pos,
-                                                                      const int32_t* __restrict__ mpos, const uint8_t* __restrict__ kind, LinkTable tab)
+                                                                      const int32_t* __restrict__ mpos, const uint8_t* __restrict__ kind, KeyedTable tab)
 {
     const int64_t i = (int64_t)blockIdx.x * kLinkWaveBlock + threadIdx.x;
     if (i >= n) return;
     const int64_t p = pos[i], m = mpos[i];
     if (p < 0 || p > clen || m < 0 || m > clen) return;
-    if (link_admit(tab, atomicAdd(&tab.counters[0], 1ull))) link_place(tab, link_key(tid, p >> kLinkBucketShift, kind[i]), link_payload(p, m));
+    const uint64_t key = link_key(tid, p >> kLinkBucketShift, kind[i]);
+    keyed_insert(tab, keyed_home(key, tab.log2_slots), key, link_payload(p, m));
 }
 
 struct LinkCountArgs {
@@ -133,20 +89,19 @@ struct LinkCountArgs {
     const int32_t* b0;
     const int32_t* b1;
     int64_t clen;
-    LinkTable tab;
+    KeyedTable tab;
     uint32_t* count;
 };
 
 // One wave per query.  Both intervals are clipped to [0, clen]; for every bucket of the pos interval (at most 257: the caller holds
-// a1 - a0 to 65 535) the wave goes along the bucket's probe run 64 slots at a time until a batch shows an empty slot.  A lane's slot
-// counts when it lies in front of the first empty one, its key is the bucket's and its payload passes the three tests; the wave sums by
-// ballot and popcount.  Every branch is on values the whole wave shares; both loops are bounded, by the bucket count and the slot count.
+// a1 - a0 to 65 535) the wave walks the bucket's probe run (keyed_walk).  A lane's slot counts when its key is the bucket's and its
+// payload passes the three tests; the wave sums by ballot and popcount.  Every branch is on values the whole wave shares; both loops
+// are bounded, by the bucket count and the slot count.
 __global__ __launch_bounds__(kLinkWaveBlock) void pairlink_count_kernel(LinkCountArgs A)
 {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    const uint64_t slots = 1ull << A.tab.log2_slots, mask = slots - 1ull;
     for (int q = wave; q < A.nq; q += nwaves) {
         int64_t a0 = A.a0[q], a1 = A.a1[q], b0 = A.b0[q], b1 = A.b1[q];
         const uint32_t kind = A.kind[q];
@@ -156,13 +111,8 @@ __global__ __launch_bounds__(kLinkWaveBlock) void pairlink_count_kernel(LinkCoun
         if (a0 <= a1 && b0 <= b1) {
             for (int64_t bucket = a0 >> kLinkBucketShift; bucket <= (a1 >> kLinkBucketShift); bucket++) {
                 const uint64_t want = link_key(A.tid, bucket, kind);
-                const uint64_t home = link_home(want, A.tab.log2_slots);
-                for (uint64_t base = 0; base < slots; base += 64ull) {
-                    const uint64_t s = (home + base + (uint64_t)lane) & mask;
-                    const uint64_t key = A.tab.slots[2ull * s];
-                    const uint64_t empty = __ballot(key == 0ull);
-                    const int stop = empty ? (int)__builtin_ctzll(empty) : 64;
-                    const bool has = lane < stop && key == want;
+                (void)keyed_walk(A.tab, keyed_home(want, A.tab.log2_slots), [want](uint64_t key) { return key == want; }, lane,
+                                 [&](bool has, uint64_t, uint64_t s) {
                     bool counts = false;
                     if (has) {
                         const uint64_t payload = A.tab.slots[2ull * s + 1ull];
@@ -170,8 +120,7 @@ __global__ __launch_bounds__(kLinkWaveBlock) void pairlink_count_kernel(LinkCoun
                         counts = pos >= a0 && pos <= a1 && mpos >= b0 && mpos <= b1 && mpos - pos >= (int64_t)A.min_sep;
                     }
                     n += (uint32_t)__builtin_popcountll(__ballot(counts));
-                    if (empty) break;
-                }
+                });
             }
         }
         if (lane == 0) A.count[q] = n;
@@ -180,7 +129,7 @@ __global__ __launch_bounds__(kLinkWaveBlock) void pairlink_count_kernel(LinkCoun
 
 }  // namespace
 
-hipError_t launch_pairlink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const LinkTable& tab, hipStream_t stream)
+hipError_t launch_pairlink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)
 {
     if (recs.n <= 0) return hipSuccess;
     LinkScatterArgs A;
@@ -190,7 +139,7 @@ hipError_t launch_pairlink_scatter(const RefDev& ref, int32_t min_mapq, const im
 }
 
 hipError_t launch_pairlink_add(int32_t n, int32_t tid, int64_t clen, const int32_t* pos, const int32_t* mpos, const uint8_t* kind,
-                               const LinkTable& tab, hipStream_t stream)
+                               const KeyedTable& tab, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(pairlink_add_kernel, dim3((n + kLinkWaveBlock - 1) / kLinkWaveBlock), dim3(kLinkWaveBlock), 0, stream, n, tid, clen, pos, mpos, kind, tab);
@@ -198,14 +147,12 @@ hipError_t launch_pairlink_add(int32_t n, int32_t tid, int64_t clen, const int32
 }
 
 hipError_t launch_pairlink_count(int32_t nq, int32_t tid, const uint8_t* kind, const int32_t* a0, const int32_t* a1, const int32_t* b0,
-                                 const int32_t* b1, int32_t min_sep, int64_t clen, const LinkTable& tab, uint32_t* count, hipStream_t stream)
+                                 const int32_t* b1, int32_t min_sep, int64_t clen, const KeyedTable& tab, uint32_t* count, hipStream_t stream)
 {
     if (nq <= 0) return hipSuccess;
     LinkCountArgs A;
     A.nq = nq; A.tid = tid; A.min_sep = min_sep; A.kind = kind; A.a0 = a0; A.a1 = a1; A.b0 = b0; A.b1 = b1; A.clen = clen; A.tab = tab; A.count = count;
-    int b = (nq + 3) / 4;
-    if (b > 2048) b = 2048;
-    hipLaunchKernelGGL(pairlink_count_kernel, dim3(b), dim3(kLinkWaveBlock), 0, stream, A);
+    hipLaunchKernelGGL(pairlink_count_kernel, dim3(wave_grid(nq)), dim3(kLinkWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 

@@ -65,6 +65,13 @@ static void print_help(FILE* file)
 
 static void free_range(void* p) { free(p); }
 
+/* a keyed table that overflowed has answered nothing since; said once, at the end.  fmt takes the stored and the dropped count (%llu each) */
+static void say_overflow(im_ctx* gpu, int (*stats)(im_ctx*, uint64_t*, uint64_t*), const char* fmt)
+{
+    uint64_t stored = 0, dropped = 0;
+    if (stats(gpu, &stored, &dropped) == IM_OK && dropped > 0) fprintf(stderr, fmt, (unsigned long long)stored, (unsigned long long)dropped);
+}
+
 /* the evidence FILEs, in the order they are written on the pipelined path, and per contig on the record-at-a-time path */
 static evfile g_evidence[3] = {
     {&g_ins_file, NULL, ins_describe, ins_contig, "large-insertion evidence (device)"},
@@ -393,20 +400,8 @@ int main(int argc, char** argv)
         for (int32_t i = 0; i < d.hdr->n_targets && use_pipeline; i++) ev_contig(&g_evidence[e], &d, i);
         ev_finish(&g_evidence[e]);
     }
-    if (CLIPTAIL_ON) {
-        /* -V: a table that overflowed has answered nothing since; said once, here */
-        uint64_t stored = 0, dropped = 0;
-        if (im_cliptail_stats(d.gpu, &stored, &dropped) == IM_OK && dropped > 0)
-            fprintf(stderr, "indelminer: -V: the clip-tail table overflowed (%llu entries stored, %llu dropped): CV and CH are . from there on\n",
-                    (unsigned long long)stored, (unsigned long long)dropped);
-    }
-    if (PAIRLINK_ON) {
-        /* -M: the same for its table */
-        uint64_t stored = 0, dropped = 0;
-        if (im_pairlink_stats(d.gpu, &stored, &dropped) == IM_OK && dropped > 0)
-            fprintf(stderr, "indelminer: -M: the pair-link table overflowed (%llu links stored, %llu dropped): PE is . in the files of -U and -N\n",
-                    (unsigned long long)stored, (unsigned long long)dropped);
-    }
+    if (CLIPTAIL_ON) say_overflow(d.gpu, im_cliptail_stats, "indelminer: -V: the clip-tail table overflowed (%llu entries stored, %llu dropped): CV and CH are . from there on\n");
+    if (PAIRLINK_ON) say_overflow(d.gpu, im_pairlink_stats, "indelminer: -M: the pair-link table overflowed (%llu links stored, %llu dropped): PE is . in the files of -U and -N\n");
     if (t_out) fflush(t_out);
     if (g_vcfname != NULL) cpu_report();            /* annotate mode has no replay workers: its report comes here */
     if (!getenv("INDELMINER_TIDY_EXIT")) {

@@ -391,22 +391,22 @@ static void tail_push(driver* d, const bam_record* b, int64_t pos, int side, int
     d->n_tail++;
 }
 /* the size of -V's table: the smallest 2^k >= max(65 536, BAM bytes / 64), at most 2^30 (DESIGN.md 4.5f has the reasoning) */
-static void cliptail_enable(driver* d)
+static int evidence_table_log2(const driver* d)
 {
     struct stat sb;
     const int64_t bytes = stat(d->bam_name, &sb) == 0 ? (int64_t)sb.st_size : 0;
     int k = 16;
     while (k < 30 && ((int64_t)1 << k) < bytes / 64) k++;
-    if (im_cliptail_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, k) != IM_OK) fatalf("im_cliptail_enable: %s", im_last_error(d->gpu));
+    return k;
+}
+static void cliptail_enable(driver* d)
+{
+    if (im_cliptail_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, evidence_table_log2(d)) != IM_OK) fatalf("im_cliptail_enable: %s", im_last_error(d->gpu));
 }
 /* the size of -M's table: -V's rule with one sixteenth of its slots (LINK_EV_SLOTS_SHIFT says what that assumes) */
 static void pairlink_enable(driver* d)
 {
-    struct stat sb;
-    const int64_t bytes = stat(d->bam_name, &sb) == 0 ? (int64_t)sb.st_size : 0;
-    int k = 16;
-    while (k < 30 && ((int64_t)1 << k) < bytes / 64) k++;
-    if (im_pairlink_enable(d->gpu, O.qthreshold, k - LINK_EV_SLOTS_SHIFT) != IM_OK) fatalf("im_pairlink_enable: %s", im_last_error(d->gpu));
+    if (im_pairlink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT) != IM_OK) fatalf("im_pairlink_enable: %s", im_last_error(d->gpu));
 }
 /* -M: the record rule of the device's pair-link scatter (include/indelminer_amd.h, "Pair links"), for the record-at-a-time path: the
  * leftmost record of a pair on one contig, both reads mapped, in any orientation but forward in front of reverse */
