@@ -14,7 +14,7 @@
 //
 //   cliptail_scatter   one lane per delivered record; the ~1 % of lanes that clip read their packed bases and insert, on tickets
 //                      their workgroup draws with one atomic add
-//   cliptail_add       one lane per entry the host names (the record-at-a-time path)
+//   cliptail_add       one lane per entry, for callers that name the events themselves
 //   cliptail_verify    one wave per query (tid, pr, pl): see the kernel
 //   cliptail_consensus one wave per query (tid, position, side): the per-base consensus of a pile's entries (-I), on the same walk
 //   cliptail_pairs     one wave per peak: the peaks the right distance away, verified as above.  <false>: a peak of clipR with the
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(kTailBlock) void cliptail_scatter_kernel(TailScatte
     if (P.n == 2u && keyed_admit(A.tab, ticket + 1ull)) keyed_place(A.tab, tail_home(P.key[1], k), P.key[1], P.payload[1]);
 }
 
-// the record-at-a-time path: one lane per entry the host named; positions outside [0, clen] are dropped (no ticket)
+// for callers that name the events themselves: one lane per entry; positions outside [0, clen] are dropped (no ticket)
 __global__ __launch_bounds__(kTailWaveBlock) void cliptail_add_kernel(int32_t n, int32_t tid, int64_t clen, const int32_t* __restrict__ pos,
                                                                  const uint8_t* __restrict__ side, const uint8_t* __restrict__ nbases,
                                                                  const uint32_t* __restrict__ planes, KeyedTable tab)

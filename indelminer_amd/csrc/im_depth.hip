@@ -7,7 +7,8 @@
 // the default mask (unmapped / secondary / QC-fail / duplicate are skipped) and its covering
 // CIGAR op is M, = or X.  An array is clen + 1 int32 of one contig and goes through three steps:
 //   scatter             +1 / -1 events into the zeroed array (device atomics): depth_scatter here for host-given intervals
-//                       (the record-at-a-time path), im_triage.hip / im_span.hip from the records for the genome-wide arrays
+//                       (the build forms, for callers that name the events themselves; the host driver's record-at-a-time path
+//                       uses the depth one), im_triage.hip / im_span.hip from the records for the genome-wide arrays
 //   depth_scan_tiled    ONE launch: prefix sum inside tiles of 8192 positions, a tile per workgroup of 256 lanes with the whole tile
 //                       in flight; the workgroup that arrives last turns the tiles' totals into exclusive tile offsets in sums[].
 //                       The array stays tile-local (HBM streaming, one pass)

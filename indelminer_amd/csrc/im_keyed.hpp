@@ -52,7 +52,7 @@ __device__ __forceinline__ void keyed_place(const KeyedTable& T, uint64_t home, 
     }
 }
 
-// One entry in, the ticket drawn by the lane itself (counters[0]: inserts): the record-at-a-time form.
+// One entry in, the ticket drawn by the lane itself (counters[0]: inserts): the form for callers that name the events themselves.
 __device__ __forceinline__ void keyed_insert(const KeyedTable& T, uint64_t home, uint64_t key, uint64_t payload)
 {
     if (keyed_admit(T, atomicAdd(&T.counters[0], 1ull))) keyed_place(T, home, key, payload);

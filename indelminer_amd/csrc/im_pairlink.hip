@@ -12,7 +12,7 @@
 //
 //   pairlink_scatter   one lane per delivered record; the lanes that hold a link insert it, on tickets their workgroup draws with one
 //                      atomic add
-//   pairlink_add       one lane per link the host names (the record-at-a-time path)
+//   pairlink_add       one lane per link, for callers that name the events themselves
 //   pairlink_count     one wave per query (kind, a0, a1, b0, b1): the links with pos in [a0, a1], mpos in [b0, b1], mpos - pos >= min_sep
 
 #include "im_keyed.hpp"
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kLinkBlock) void pairlink_scatter_kernel(LinkScatte
     if (has && keyed_admit(A.tab, ticket)) keyed_place(A.tab, keyed_home(key, A.tab.log2_slots), key, payload);
 }
 
-// the record-at-a-time path: one lane per link the host named; positions outside [0, clen] are dropped (no ticket)
+// for callers that name the events themselves: one lane per link; positions outside [0, clen] are dropped (no ticket)
 __global__ __launch_bounds__(kLinkWaveBlock) void pairlink_add_kernel(int32_t n, int32_t tid, int64_t clen, const int32_t* __restrict__ pos,
                                                                       const int32_t* __restrict__ mpos, const uint8_t* __restrict__ kind, KeyedTable tab)
 {

@@ -12,8 +12,8 @@
 //   span_scatter   one lane per delivered record: runs -> events, gathered in an LDS window, written out with vector atomics
 //   (scan)         launch_depth_scan_tiled, as it is
 //   span_query     one wave per query: minimum of span[p] over [beg, end] inclusive
-// The record-at-a-time path hands over (start, length) runs instead of records: launch_depth_build(lo = m, hi = m - 1) makes the
-// same events from them.
+// The build form, for callers that name the events themselves, takes (start, length) runs instead of records:
+// launch_depth_build(lo = m, hi = m - 1) makes the same events from them.
 //
 // Concordant pairs (-P), a second array of the same shape for the records without a precise breakpoint (PAIRED_READ).  With
 // m = flank >= 1, q = min_mapq and range_max = range[1] of the record's read group (its RG:Z tag, "generic" without one: the
@@ -37,7 +37,7 @@
 //   clip_argmax    one wave per query: the largest count over [beg, end] inclusive and the smallest position that holds it
 //   clip_facing    one lane per four positions of one contig: the facing piles of the two arrays (-I), the one chip-wide search
 //   clip_peaks     the same stream over one array: its peaks (-U), once per side
-// The record-at-a-time path names the events itself: clip_build adds one per (position, side).
+// clip_build, for callers that name the events themselves, adds one per (position, side).
 
 #include "im_device.hpp"
 #include "im_rg.hpp"
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(kSpanBlock) void clip_scatter_kernel(ClipArgs A)
     }
 }
 
-// the record-at-a-time path: one lane per event the host named (side 0: clipR, 1: clipL), positions outside [0, clen] dropped
+// for callers that name the events themselves: one lane per event (side 0: clipR, 1: clipL), positions outside [0, clen] dropped
 __global__ __launch_bounds__(256) void clip_build_kernel(int32_t n, const int32_t* __restrict__ pos, const uint8_t* __restrict__ side, int64_t clen,
                                                         int32_t* __restrict__ right, int32_t* __restrict__ left)
 {

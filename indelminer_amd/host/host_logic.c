@@ -303,7 +303,7 @@ typedef struct {
     char** qname; char* strand; uint8_t* qual;
 } cand_batch;
 
-/* intervals of one contig, for a device array of the record-at-a-time path */
+/* intervals of one contig, for the depth array of the record-at-a-time path */
 typedef struct { int32_t *start, *len; int64_t n, cap; } ivlist;
 typedef struct {
     im_ctx* gpu;
@@ -326,15 +326,11 @@ typedef struct {
     cand_batch cb;
     evidence_t** pending; int64_t n_pending, cap_pending;
     int64_t arrival;
-    /* record-at-a-time path: the match segments of the contig's pileup-eligible records (im_depth_build); -G: the M/=/X runs of its
-     * eligible records (im_span_build); -P: the fragments of its concordant left mates (im_pairspan_build) */
-    ivlist segs, runs, frags;
-    /* -C, record-at-a-time path: the clip events of the contig's eligible records, position and side (im_clip_build) */
-    int32_t* clip_pos; uint8_t* clip_side; int64_t n_clip, cap_clip;
-    /* -V, the same path: their clip-tail entries, position, side, bases and the two planes each (im_cliptail_add) */
-    int32_t* tail_pos; uint8_t* tail_side; uint8_t* tail_n; uint32_t* tail_planes; int64_t n_tail, cap_tail;
-    /* -M, the same path: the contig's pair links, pos, mpos and kind each (im_pairlink_add) */
-    int32_t* link_pos; int32_t* link_mpos; uint8_t* link_kind; int64_t n_link, cap_link;
+    /* record-at-a-time path: the match segments of the contig's pileup-eligible records (im_depth_build) */
+    ivlist segs;
+    /* the same path: the chunk pass A reads its records into and the evidence options' scatters take them from (host_chunk_*,
+     * host_setup.c): records and their offsets, the device twins, what it holds and its cap of records */
+    uint8_t* ck_raw; uint32_t* ck_off; void *ck_draw, *ck_doff; int32_t ck_n, ck_cap; uint32_t ck_bytes;
     int depth_tid;              /* contig whose depth array is resident on the device, -1 = none */
     int pipe_mode;              /* device pipeline: depth queries go to the genome-wide array */
     int marker_floor;           /* multi-GPU: smallest start of a stale pair-table entry of an earlier contig on another rank */
@@ -531,25 +527,6 @@ static const int32_t* record_range(driver* d, const bam_record* b)
         d->rg_tmp_val = rb->val;
     } else d->rg_tmp_val = d->rg_last_val;
     return d->rg_tmp_val;
-}
-
-/* -P: the record rule of the device's pair scatter (include/indelminer_amd.h), for the record-at-a-time path: the left mate of
- * a pair the evidence rule of discordant_pair does NOT take (isize <= range[1]), each pair once.  A record whose read group is not
- * in the table does not count. */
-static int concordant_left_mate(driver* d, const bam_record* b)
-{
-    const int flag = b->flag;
-    if (!(flag & 0x1) || (flag & (0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800))) return 0;
-    if (b->tid < 0 || b->tid >= d->hdr->n_targets || b->mtid != b->tid) return 0;
-    if (((flag >> 4) & 1) == ((flag >> 5) & 1)) return 0;
-    if (b->isize <= 0) return 0;
-    if (!(b->pos < b->mpos || (b->pos == b->mpos && (flag & 0x40)))) return 0;
-    if ((int)b->mapq < O.qthreshold) return 0;
-    const uint8_t* rg = bam_aux_find(b, "RG");
-    if (rg && !(rg[0] == 'Z' || rg[0] == 'H')) return 0;
-    const char* rgname = rg ? bam_aux_str(rg) : "generic";
-    qbin* rb = qhash_lookup(d->insertlengths, rgname, (int)strlen(rgname));
-    return rb && b->isize <= ((const int32_t*)rb->val)[1];
 }
 
 /* fetch_func (src/indelminer.c:339-673) for one record, pass A part */
@@ -1011,8 +988,7 @@ static void query_minima(driver* d, int pair, int32_t tid, int m, const int32_t*
 {
     gpu_wait(d);
     pthread_mutex_lock(&g_query_mu);
-    const int qrc = pair ? (d->pipe_mode ? im_pairspan_query_tid(d->gpu, tid, m, beg, end, out) : im_pairspan_query(d->gpu, m, beg, end, out))
-                         : (d->pipe_mode ? im_span_query_tid(d->gpu, tid, m, beg, end, out) : im_span_query(d->gpu, m, beg, end, out));
+    const int qrc = (pair ? im_pairspan_query_tid : im_span_query_tid)(d->gpu, tid, m, beg, end, out);
     pthread_mutex_unlock(&g_query_mu);
     if (qrc != IM_OK) fatalf("%s: %s", pair ? "im_pairspan_query" : "im_span_query", im_last_error(d->gpu));
 }
@@ -1418,8 +1394,7 @@ static void print_variants(driver* d, variant_list* vs)
         if (m > 0) {
             gpu_wait(d);
             pthread_mutex_lock(&g_query_mu);
-            const int qrc = d->pipe_mode ? im_clip_query_tid(d->gpu, out.v[who[0]]->tid, 2 * m, side, beg, end, cnt, at)      /* a flush lies on one contig */
-                                         : im_clip_query(d->gpu, 2 * m, side, beg, end, cnt, at);
+            const int qrc = im_clip_query_tid(d->gpu, out.v[who[0]]->tid, 2 * m, side, beg, end, cnt, at);      /* a flush lies on one contig */
             pthread_mutex_unlock(&g_query_mu);
             if (qrc != IM_OK) fatalf("im_clip_query: %s", im_last_error(d->gpu));
             for (int q = 0; q < m; q++) {

@@ -72,7 +72,8 @@ static void say_overflow(im_ctx* gpu, int (*stats)(im_ctx*, uint64_t*, uint64_t*
     if (stats(gpu, &stored, &dropped) == IM_OK && dropped > 0) fprintf(stderr, fmt, (unsigned long long)stored, (unsigned long long)dropped);
 }
 
-/* the evidence FILEs, in the order they are written on the pipelined path, and per contig on the record-at-a-time path */
+/* the evidence FILEs, in the order they are written on the pipelined path, and per contig on the record-at-a-time path (the same
+ * genome-wide arrays and tables on both) */
 static evfile g_evidence[3] = {
     {&g_ins_file, NULL, ins_describe, ins_contig, "large-insertion evidence (device)"},
     {&g_dup_file, NULL, dup_describe, dup_contig, "tandem-duplication evidence (device)"},
@@ -378,7 +379,7 @@ int main(int argc, char** argv)
     if (g_mg) mg_finish(&mg, &d);
     /* the reference prints its header before it reads the first record (src/indelminer.c:745-754 in front of 756-): a run it
      * aborts on some record has the header on stdout.  Here the header waits for the GPU context (gpu_wait). */
-    if (!use_pipeline) gpu_wait(&d);
+    if (!use_pipeline) { gpu_wait(&d); evidence_enable(&d); }
     for (int32_t i = 0; i < d.hdr->n_targets && !use_pipeline; i++) {
         if (chromid != -1 && i != chromid) continue;
         if (g_vcfname != NULL) {
@@ -388,7 +389,7 @@ int main(int argc, char** argv)
         }
         if (chromid == -1) run_contig(&d, i, 0, d.hdr->target_len[i], r);
         else run_contig(&d, i, chromstart, chromstop, r);
-        /* -I, -U, -N, record-at-a-time: behind the contig's flushes, on the arrays of its im_clip_build */
+        /* -I, -U, -N, record-at-a-time: behind the contig's flushes, on what its chunks scattered */
         for (int e = 0; e < 3; e++) if (*g_evidence[e].path) ev_contig(&g_evidence[e], &d, i);
     }
 

@@ -26,11 +26,8 @@
  * (and serialised in the driver): an input of a few hundred megabytes gets two chunks of 16 MB per walker instead of four of
  * 32 MB, set once before the walkers start (walkpool_start). */
 #define PIPE_NCHUNK        4
-static uint32_t g_chunk_bytes = 32u << 20;
 static int g_nchunk = PIPE_NCHUNK;
 static int g_small_input;           /* walkpool_start: an input of less than 64 MB -- no streams of the pipelines' own */
-#define PIPE_CHUNK_BYTES   g_chunk_bytes
-#define PIPE_CHUNK_RECS    (g_chunk_bytes / 64u)
 
 typedef struct {
     uint8_t*  h_raw; uint32_t* h_off; int32_t* h_cnt;        /* pinned */
@@ -142,8 +139,7 @@ typedef struct {
     uint8_t* h_ring;                    /* the chunks' pinned memory when it is one allocation */
 } ppipe;
 
-#define GPU(call) do { if ((call) != IM_OK) fatalf("%s: %s", #call, im_last_error(P->d->gpu)); } while (0)
-#define GPU2(drv, call) do { if ((call) != IM_OK) fatalf("%s: %s", #call, im_last_error((drv)->gpu)); } while (0)
+#define GPU(call) GPU2(P->d, call)
 struct walkpool_s;
 static struct walkpool_s* g_handoff_pool = NULL;       /* set while run_pipeline can hand a run the reference aborts to a child */
 static int g_free_slabs = 1;                            /* parked groups' device slabs are freed once staged */
@@ -182,22 +178,8 @@ static void pipe_free_cands(ppipe* P)
 static void pipe_global_init(driver* d)
 {
     g_lean_evidence = g_vcfname == NULL && strncmp(O.outputformat, "vcf", 3) == 0;     /* host_logic.c: what nothing reads is not built */
-    /* the insert-length table in the order its entries were added, range[1] of each */
-    int32_t* rmax = xmalloc(sizeof(int32_t) * (size_t)(g_rg_n ? g_rg_n : 1));
-    for (int i = 0; i < g_rg_n; i++) rmax[i] = g_rg_range[i][1];
-    if (im_set_insert_ranges(d->gpu, g_rg_n, g_rg_name, rmax) != IM_OK) fatalf("im_set_insert_ranges: %s", im_last_error(d->gpu));
-    free(rmax);
     if (im_depth_enable(d->gpu) != IM_OK) fatalf("im_depth_enable: %s", im_last_error(d->gpu));
-    /* -G: the second genome-wide array, only then */
-    if (SPAN_ON && im_span_enable(d->gpu, (int32_t)O.ethreshold, O.qthreshold) != IM_OK) fatalf("im_span_enable: %s", im_last_error(d->gpu));
-    /* -P: and a third */
-    if (PAIR_ON && im_pairspan_enable(d->gpu, (int32_t)O.ethreshold, O.qthreshold) != IM_OK) fatalf("im_pairspan_enable: %s", im_last_error(d->gpu));
-    /* -C: and the two arrays of clipped-read counts */
-    if (CLIP_ON && im_clip_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold) != IM_OK) fatalf("im_clip_enable: %s", im_last_error(d->gpu));
-    /* -V: and the table of their clipped bases */
-    if (CLIPTAIL_ON) cliptail_enable(d);
-    /* -M: and the table of pair links */
-    if (PAIRLINK_ON) pairlink_enable(d);
+    evidence_enable(d);
 }
 
 /* one walker's buffers (with_chunks: the pinned chunk ring a walk delivers records through; the main thread's stage pipeline
@@ -414,11 +396,7 @@ static void pipe_submit(ppipe* P, pgroup* G)
     out.cand_rec = P->cand_rec; out.counters = P->counters; out.rec_class = c->d_class;
     out.cap_cand = P->cap_cand; out.cap_bases = P->cap_bases; out.consumed = NULL;     /* cleared once per group in pipe_run_group */
     GPU(im_dev_triage(g, &P->tp, &recs, &out, c->d_scratch, c->scratch_bytes, P->stream));
-    if (SPAN_ON) GPU(im_dev_span_scatter(g, &recs, P->stream));      /* -G, -A: a launch of its own behind the triage, in front of the chunk's event */
-    if (PAIR_ON) GPU(im_dev_pairspan_scatter(g, &recs, P->stream));  /* -P: one more, only then */
-    if (CLIP_ON) GPU(im_dev_clip_scatter(g, &recs, P->stream));      /* -C: one more, only then; these arrays need no scan */
-    if (CLIPTAIL_ON) GPU(im_dev_cliptail_scatter(g, &recs, P->stream));      /* -V: and one behind it, only then */
-    if (PAIRLINK_ON) GPU(im_dev_pairlink_scatter(g, &recs, P->stream));      /* -M: and one behind that, only then */
+    evidence_scatter(P->d, &recs, P->stream);       /* launches of their own behind the triage, in front of the chunk's event */
     GPU(im_dev_download_async(g, c->h_cnt, P->counters, 32, P->stream));
     GPU(im_event_record(c->done, P->stream));
     c->busy = 1; P->n_busy++;

@@ -341,55 +341,6 @@ static void ivl_push(ivlist* l, int32_t start, int32_t len)
     l->start[l->n] = start; l->len[l->n] = len; l->n++;
 }
 
-/* -G, -A (pair: 0) or -P (pair: 1): the contig's span or pair-span array from the intervals pass A collected */
-static void build_counted(driver* d, int pair, int32_t tid, const ivlist* l, int32_t flank)
-{
-    gpu_wait(d);
-    if (l->n > INT32_MAX) fatalf(pair ? "more than 2^31 concordant pairs on one contig" : "more than 2^31 alignment runs on one contig");
-    if ((pair ? im_pairspan_build : im_span_build)(d->gpu, d->seqlen[tid], (int32_t)l->n, l->start, l->len, flank) != IM_OK)
-        fatalf("%s: %s", pair ? "im_pairspan_build" : "im_span_build", im_last_error(d->gpu));
-    phase_time(pair ? "pair-span array (device)" : "span array (device)");
-}
-
-/* -C: the record rule of the device's clip scatter (include/indelminer_amd.h), for the record-at-a-time path: a soft clip of
- * CLIP_EV_MIN_CLIP bases as the first or last operation apart from H, on a record that consumes reference.  The device drops
- * positions outside the contig; here only what an int32 does not hold. */
-static void clip_push(driver* d, int64_t pos, int side)
-{
-    if (pos < 0 || pos > INT32_MAX) return;
-    if (d->n_clip == d->cap_clip) {
-        d->cap_clip = d->cap_clip ? d->cap_clip * 2 : (1 << 14);
-        d->clip_pos = xrealloc(d->clip_pos, sizeof(int32_t) * (size_t)d->cap_clip);
-        d->clip_side = xrealloc(d->clip_side, (size_t)d->cap_clip);
-    }
-    d->clip_pos[d->n_clip] = (int32_t)pos; d->clip_side[d->n_clip] = (uint8_t)side; d->n_clip++;
-}
-/* -V: the entry of one clipping end (include/indelminer_amd.h, "Clip tails"): the n = min(L, 32) clipped bases nearest the junction,
- * read base `first` and on in steps of `step`, as two planes of 2-bit codes; nothing when one of them is not A, C, G or T or when the
- * clip is longer than the read */
-static void tail_push(driver* d, const bam_record* b, int64_t pos, int side, int L, int64_t first, int step)
-{
-    if (pos < 0 || pos > INT32_MAX || pos > d->hdr->target_len[b->tid] || b->l_seq <= 0 || L > b->l_seq) return;
-    const int n = L < CLIPTAIL_BASES ? L : CLIPTAIL_BASES;
-    const uint8_t* seq = BAMR_SEQ(b);
-    uint32_t lo = 0, hi = 0;
-    for (int i = 0; i < n; i++) {
-        const int code = BAMR_SEQI(seq, first + (int64_t)step * i);
-        const int two = code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : -1;
-        if (two < 0) return;
-        lo |= (uint32_t)(two & 1) << i; hi |= (uint32_t)(two >> 1) << i;
-    }
-    if (d->n_tail == d->cap_tail) {
-        d->cap_tail = d->cap_tail ? d->cap_tail * 2 : (1 << 14);
-        d->tail_pos = xrealloc(d->tail_pos, sizeof(int32_t) * (size_t)d->cap_tail);
-        d->tail_side = xrealloc(d->tail_side, (size_t)d->cap_tail);
-        d->tail_n = xrealloc(d->tail_n, (size_t)d->cap_tail);
-        d->tail_planes = xrealloc(d->tail_planes, 2 * sizeof(uint32_t) * (size_t)d->cap_tail);
-    }
-    d->tail_pos[d->n_tail] = (int32_t)pos; d->tail_side[d->n_tail] = (uint8_t)side; d->tail_n[d->n_tail] = (uint8_t)n;
-    d->tail_planes[2 * d->n_tail] = lo; d->tail_planes[2 * d->n_tail + 1] = hi;
-    d->n_tail++;
-}
 /* the size of -V's table: the smallest 2^k >= max(65 536, BAM bytes / 64), at most 2^30 (DESIGN.md 4.5f has the reasoning) */
 static int evidence_table_log2(const driver* d)
 {
@@ -399,57 +350,94 @@ static int evidence_table_log2(const driver* d)
     while (k < 30 && ((int64_t)1 << k) < bytes / 64) k++;
     return k;
 }
-static void cliptail_enable(driver* d)
+
+#define GPU2(drv, call) do { if ((call) != IM_OK) fatalf("%s: %s", #call, im_last_error((drv)->gpu)); } while (0)
+#define EVIDENCE_ON (SPAN_ON || PAIR_ON || CLIP_ON || PAIRLINK_ON)     /* -V needs -C */
+
+/* Once per run, on either path, when the reference is on the device and the insert lengths are known: what the evidence options
+ * keep on the device.  Genome-wide arrays and tables keyed by contig: nothing is reset between contigs. */
+static void evidence_enable(driver* d)
 {
-    if (im_cliptail_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, evidence_table_log2(d)) != IM_OK) fatalf("im_cliptail_enable: %s", im_last_error(d->gpu));
+    /* the insert-length table in the order its entries were added, range[1] of each */
+    int32_t* rmax = xmalloc(sizeof(int32_t) * (size_t)(g_rg_n ? g_rg_n : 1));
+    for (int i = 0; i < g_rg_n; i++) rmax[i] = g_rg_range[i][1];
+    GPU2(d, im_set_insert_ranges(d->gpu, g_rg_n, g_rg_name, rmax));
+    free(rmax);
+    /* -G: the second genome-wide array, only then */
+    if (SPAN_ON) GPU2(d, im_span_enable(d->gpu, (int32_t)O.ethreshold, O.qthreshold));
+    /* -P: and a third */
+    if (PAIR_ON) GPU2(d, im_pairspan_enable(d->gpu, (int32_t)O.ethreshold, O.qthreshold));
+    /* -C: and the two arrays of clipped-read counts */
+    if (CLIP_ON) GPU2(d, im_clip_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold));
+    /* -V: and the table of their clipped bases */
+    if (CLIPTAIL_ON) GPU2(d, im_cliptail_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, evidence_table_log2(d)));
+    /* -M: and the table of pair links, -V's rule with one sixteenth of its slots (LINK_EV_SLOTS_SHIFT says what that assumes) */
+    if (PAIRLINK_ON) GPU2(d, im_pairlink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
 }
-/* the size of -M's table: -V's rule with one sixteenth of its slots (LINK_EV_SLOTS_SHIFT says what that assumes) */
-static void pairlink_enable(driver* d)
+
+/* a chunk of records on the device, as they are in the file: each option's record rule is its scatter kernel's, on either path */
+static void evidence_scatter(driver* d, const im_dev_records* recs, void* stream)
 {
-    if (im_pairlink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT) != IM_OK) fatalf("im_pairlink_enable: %s", im_last_error(d->gpu));
+    if (SPAN_ON) GPU2(d, im_dev_span_scatter(d->gpu, recs, stream));            /* -G, -A */
+    if (PAIR_ON) GPU2(d, im_dev_pairspan_scatter(d->gpu, recs, stream));        /* -P: one more, only then */
+    if (CLIP_ON) GPU2(d, im_dev_clip_scatter(d->gpu, recs, stream));            /* -C: one more, only then; these arrays need no scan */
+    if (CLIPTAIL_ON) GPU2(d, im_dev_cliptail_scatter(d->gpu, recs, stream));    /* -V: and one behind it, only then */
+    if (PAIRLINK_ON) GPU2(d, im_dev_pairlink_scatter(d->gpu, recs, stream));    /* -M: and one behind that, only then */
 }
-/* -M: the record rule of the device's pair-link scatter (include/indelminer_amd.h, "Pair links"), for the record-at-a-time path: the
- * leftmost record of a pair on one contig, both reads mapped, in any orientation but forward in front of reverse */
-static void link_events(driver* d, const bam_record* b)
+
+/* The chunks of both paths: the pipelined walk's ring has up to PIPE_NCHUNK of them per walker (host_pipeline.c), the record-at-a-time
+ * path cycles one. */
+static uint32_t g_chunk_bytes = 32u << 20;
+#define PIPE_CHUNK_BYTES   g_chunk_bytes
+#define PIPE_CHUNK_RECS    (g_chunk_bytes / 64u)
+
+/* The record-at-a-time path's chunk.  Pass A reads its records into one host buffer, 4-byte aligned and zero padded like the walk's;
+ * with an evidence option on, the buffer goes to a device twin and through the scatters whenever it is full, holds its cap of records,
+ * or the pass ends.  Nothing overlaps: every submit ends synchronised, so the queries that follow on the context's stream see it.
+ * INDELMINER_HOST_CHUNK_RECS lowers the cap (tests: a cap that cuts inside the scatters' workgroups). */
+static void host_chunk_submit(driver* d)
 {
-    if (!(b->flag & 0x1) || (b->flag & (0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800))) return;
-    if (b->tid < 0 || b->tid >= d->hdr->n_targets || b->mtid != b->tid || (int)b->mapq < O.qthreshold) return;
-    if (!(b->pos < b->mpos || (b->pos == b->mpos && (b->flag & 0x40)))) return;
-    const int64_t clen = d->hdr->target_len[b->tid];
-    if (b->pos < 0 || b->pos > clen || b->mpos < 0 || b->mpos > clen) return;
-    const int rev = (b->flag >> 4) & 1, mrev = (b->flag >> 5) & 1;
-    if (!rev && mrev) return;
-    if (d->n_link == d->cap_link) {
-        d->cap_link = d->cap_link ? d->cap_link * 2 : (1 << 12);
-        d->link_pos = xrealloc(d->link_pos, sizeof(int32_t) * (size_t)d->cap_link);
-        d->link_mpos = xrealloc(d->link_mpos, sizeof(int32_t) * (size_t)d->cap_link);
-        d->link_kind = xrealloc(d->link_kind, (size_t)d->cap_link);
+    if (d->ck_n > 0 && EVIDENCE_ON) {
+        void* stream = im_ctx_stream(d->gpu);
+        d->ck_off[d->ck_n] = d->ck_bytes;
+        GPU2(d, im_dev_upload_async(d->gpu, d->ck_draw, d->ck_raw, d->ck_bytes, stream));
+        GPU2(d, im_dev_upload_async(d->gpu, d->ck_doff, d->ck_off, 4 * ((size_t)d->ck_n + 1), stream));
+        im_dev_records recs = { d->ck_n, d->ck_draw, d->ck_doff, 0 };
+        evidence_scatter(d, &recs, stream);
+        GPU2(d, im_stream_sync(d->gpu, stream));
     }
-    d->link_pos[d->n_link] = b->pos; d->link_mpos[d->n_link] = b->mpos;
-    d->link_kind[d->n_link] = (uint8_t)(rev ? (mrev ? LINK_REVERSE : LINK_EVERTED) : LINK_FORWARD);
-    d->n_link++;
+    d->ck_n = 0; d->ck_bytes = 0;
 }
-static void clip_events(driver* d, const bam_record* b)
+
+static void host_chunk_init(driver* d)
 {
-    if (b->tid < 0 || b->tid >= d->hdr->n_targets || (b->flag & (0x4 | 0x100 | 0x200 | 0x400)) || (int)b->mapq < O.qthreshold) return;
-    const uint8_t* cig = BAMR_CIGAR(b);
-    int first = -1, last = -1, consumes = 0;
-    int64_t refend = b->pos;
-    for (int kk = 0; kk < b->n_cigar; kk++) {
-        const int op = CIG_OP(bamr_cigar_at(cig, kk)), len = CIG_LEN(bamr_cigar_at(cig, kk));
-        if (op != OP_H) { if (first < 0) first = kk; last = kk; }
-        if (op == OP_M || op == OP_EQ || op == OP_X || op == OP_D || op == OP_N) { consumes = 1; refend += len; }
-    }
-    if (!consumes) return;
-    if (CIG_OP(bamr_cigar_at(cig, last)) == OP_S && CIG_LEN(bamr_cigar_at(cig, last)) >= CLIP_EV_MIN_CLIP) {
-        clip_push(d, refend, 0);
-        const int L = CIG_LEN(bamr_cigar_at(cig, last));
-        if (CLIPTAIL_ON) tail_push(d, b, refend, 0, L, (int64_t)b->l_seq - L, 1);
-    }
-    if (CIG_OP(bamr_cigar_at(cig, first)) == OP_S && CIG_LEN(bamr_cigar_at(cig, first)) >= CLIP_EV_MIN_CLIP) {
-        clip_push(d, b->pos, 1);
-        const int L = CIG_LEN(bamr_cigar_at(cig, first));
-        if (CLIPTAIL_ON) tail_push(d, b, b->pos, 1, L, L - 1, -1);
+    if (d->ck_raw) return;
+    const char* e = getenv("INDELMINER_HOST_CHUNK_RECS");
+    d->ck_cap = (int32_t)PIPE_CHUNK_RECS;
+    if (e && atoi(e) >= 1 && atoi(e) < d->ck_cap) d->ck_cap = atoi(e);
+    d->ck_raw = xmalloc(PIPE_CHUNK_BYTES);
+    d->ck_off = xmalloc(4 * ((size_t)d->ck_cap + 1));
+    if (!EVIDENCE_ON) return;
+    GPU2(d, im_dev_alloc(d->gpu, (size_t)PIPE_CHUNK_BYTES + 64, &d->ck_draw));     /* the kernels read up to 64 bytes past the last record */
+    GPU2(d, im_dev_alloc(d->gpu, 4 * ((size_t)d->ck_cap + 1), &d->ck_doff));
+}
+
+/* the next record of the pass into the chunk (submitting what it holds when that is what makes room): 1 and the view, or 0 at the end */
+static int host_chunk_next(driver* d, bam_region_iter* it, bam_record* b)
+{
+    for (;;) {
+        int32_t len = 0;
+        const int rc = d->ck_n < d->ck_cap ? bam_region_next_raw(it, d->ck_raw + d->ck_bytes, (int64_t)PIPE_CHUNK_BYTES - d->ck_bytes, &len, b) : -2;
+        if (rc == -2) {
+            if (d->ck_n == 0) fatalf("a BAM record larger than %u bytes", PIPE_CHUNK_BYTES);
+            host_chunk_submit(d);
+            continue;
+        }
+        if (rc != 1) return 0;
+        d->ck_off[d->ck_n++] = d->ck_bytes;
+        for (uint32_t z = (uint32_t)len; z & 3u; z++) d->ck_raw[d->ck_bytes + z] = 0;
+        d->ck_bytes += ((uint32_t)len + 3u) & ~3u;
+        return 1;
     }
 }
 
@@ -473,7 +461,7 @@ static FILE* ev_open(evfile* e)
     return e->out;
 }
 
-/* one contig, whose every record the clip arrays and the table hold: behind the last flush (pipelined) or the contig's (record-at-a-time) */
+/* one contig, whose every record the clip arrays and the tables hold: behind the last flush (pipelined) or the contig's (record-at-a-time) */
 static void ev_contig(evfile* e, driver* d, int32_t tid)
 {
     FILE* f = ev_open(e);
@@ -528,8 +516,7 @@ static void ins_contig(driver* d, int32_t tid, FILE* f)
     for (;;) {
         pr = xrealloc(pr, sizeof(int32_t) * (size_t)cap); pl = xrealloc(pl, sizeof(int32_t) * (size_t)cap);
         cr = xrealloc(cr, sizeof(uint32_t) * (size_t)cap); cl = xrealloc(cl, sizeof(uint32_t) * (size_t)cap);
-        const int rc = d->pipe_mode ? im_clip_facing_tid(d->gpu, tid, INS_EV_MIN_READS, INS_EV_MAX_OVERLAP, cap, pr, pl, cr, cl, &found)
-                                    : im_clip_facing(d->gpu, INS_EV_MIN_READS, INS_EV_MAX_OVERLAP, cap, pr, pl, cr, cl, &found);
+        const int rc = im_clip_facing_tid(d->gpu, tid, INS_EV_MIN_READS, INS_EV_MAX_OVERLAP, cap, pr, pl, cr, cl, &found);
         if (rc != IM_OK) fatalf("im_clip_facing: %s", im_last_error(d->gpu));
         if (found <= cap) break;
         cap = found;                /* more piles than asked for: once more, with room for all */
@@ -632,9 +619,9 @@ static pile_pairs pile_pairs_query(driver* d, int32_t tid, int inverted)
         uint32_t* cnt = P.cnt = xrealloc(P.cnt, sizeof(uint32_t) * 6 * (size_t)cap);
         if (inverted) P.side = xrealloc(P.side, (size_t)cap);
         const int rc = inverted
-            ? (d->pipe_mode ? im_clip_inverted_tid : im_clip_inverted)(d->gpu, tid, INV_EV_MIN_READS, INV_EV_REACH, INV_EV_MIN_LEN, INV_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT,
+            ? im_clip_inverted_tid(d->gpu, tid, INV_EV_MIN_READS, INV_EV_REACH, INV_EV_MIN_LEN, INV_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT,
                   INV_EV_MIN_VERIFIED, cap, P.side, pos, pos + cap, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, pos + 2 * cap, cnt + 4 * cap, cnt + 5 * cap, &P.found)
-            : (d->pipe_mode ? im_clip_crossed_tid : im_clip_crossed)(d->gpu, tid, DUP_EV_MIN_READS, DUP_EV_REACH, DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT,
+            : im_clip_crossed_tid(d->gpu, tid, DUP_EV_MIN_READS, DUP_EV_REACH, DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, CLIPTAIL_MAX_SHIFT,
                   DUP_EV_MIN_VERIFIED, cap, pos, pos + cap, cnt, cnt + cap, cnt + 2 * cap, cnt + 3 * cap, pos + 2 * cap, cnt + 4 * cap, cnt + 5 * cap, &P.found);
         if (rc != IM_OK) fatalf("%s: %s", inverted ? "im_clip_inverted" : "im_clip_crossed", im_last_error(d->gpu));
         if (P.found <= cap) break;
@@ -644,7 +631,8 @@ static pile_pairs pile_pairs_query(driver* d, int32_t tid, int inverted)
 }
 
 /* -U: one contig's crossed piles into FILE.  With -D the contig's scanned depth array is resident as well -- the genome-wide array is
- * scanned contig by contig as the walk leaves each (im_depth_scan) and never reset, the record-at-a-time path has built this contig's.
+ * scanned contig by contig as the walk leaves each (im_depth_scan) and never reset; the record-at-a-time path has built this contig's
+ * depth array alone (im_depth_build) and scattered the rest like the walk.
  * g_query_mu is taken again for the depth queries: the pairs are on the host by then, so nothing needs it held in between. */
 static void dup_contig(driver* d, int32_t tid, FILE* f)
 {
@@ -761,13 +749,14 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
     bam_region_iter it;
     bam_record b; memset(&b, 0, sizeof b);
     if (bam_region_begin(&it, r, d->idx, tid, beg, end) != 0) fatalf("cannot seek in %s", d->bam_name);
-    d->segs.n = 0; d->runs.n = 0; d->frags.n = 0; d->n_clip = 0; d->n_tail = 0; d->n_link = 0;
+    d->segs.n = 0;
+    host_chunk_init(d);
     const int whole = (beg <= 0 && end >= d->hdr->target_len[tid]);
     volatile int died = 0;              /* a record the reference dies on ended the pass: the flushes in front of it are still to print */
     t_is_main_thread_of_passA = 1;
     if (setjmp(g_passA_jmp)) died = 1;
     else g_passA_armed = 1;
-    while (!died && bam_region_next(&it, &b) == 1) {
+    while (!died && host_chunk_next(d, &it, &b)) {
         if (whole && b.tid >= 0 && !(b.flag & (0x4 | 0x100 | 0x200 | 0x400))) {
             /* what samtools' pileup would count for DP= (bam_pileup.c:171-172,238-265) */
             const uint8_t* cig = BAMR_CIGAR(&b);
@@ -780,35 +769,11 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
                 } else if (op == OP_D || op == OP_N) x += len;
             }
         }
-        if (SPAN_ON && b.tid >= 0 && !(b.flag & (0x4 | 0x100 | 0x200 | 0x400)) && (int)b.mapq >= O.qthreshold) {
-            /* -G: the maximal M/=/X runs of the record (D and N advance and end a run, every other operation ends it) */
-            const uint8_t* cig = BAMR_CIGAR(&b);
-            int64_t x = b.pos, rs = 0;
-            int in_run = 0;
-            for (int kk = 0; kk <= b.n_cigar; kk++) {
-                const int op = kk < b.n_cigar ? CIG_OP(bamr_cigar_at(cig, kk)) : OP_S, len = kk < b.n_cigar ? CIG_LEN(bamr_cigar_at(cig, kk)) : 0;
-                if (op == OP_M || op == OP_EQ || op == OP_X) { if (!in_run) { rs = x; in_run = 1; } x += len; continue; }
-                if (in_run) {
-                    /* clipped to what an int32 start and length hold (the device clips to the contig) */
-                    int64_t a = rs < 0 ? 0 : rs, e = x > INT32_MAX ? INT32_MAX : x;
-                    if (e > a) ivl_push(&d->runs, (int32_t)a, (int32_t)(e - a));
-                    in_run = 0;
-                }
-                if (op == OP_D || op == OP_N) x += len;
-            }
-        }
-        if (CLIP_ON) clip_events(d, &b);
-        if (PAIRLINK_ON) link_events(d, &b);
         dispatch_record(d, &b);
-        if (PAIR_ON && concordant_left_mate(d, &b)) {
-            /* -P: the fragment [pos, pos + isize) of the pair, clipped to what an int32 start and length hold (the device clips
-             * to the contig).  Behind dispatch_record: a read group that is not in the table has ended the run there. */
-            const int64_t a = b.pos < 0 ? 0 : b.pos, e = (int64_t)b.pos + b.isize > INT32_MAX ? INT32_MAX : (int64_t)b.pos + b.isize;
-            if (e > a) ivl_push(&d->frags, (int32_t)a, (int32_t)(e - a));
-        }
     }
     g_passA_armed = 0;
-    free(b.data);
+    /* the last records go out now, the record the reference died on among them (the chunk is the driver's: it outlives the jump) */
+    host_chunk_submit(d);
     phase_time("pass A (BAM decode + dispatch)");
     d->depth_tid = -1;
     if (whole) {
@@ -818,28 +783,11 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
         d->depth_tid = tid;
     }
     phase_time("depth array (device)");
-    if (SPAN_ON) build_counted(d, 0, tid, &d->runs, (int32_t)O.ethreshold);
-    if (PAIR_ON) build_counted(d, 1, tid, &d->frags, (int32_t)O.ethreshold);
-    if (CLIP_ON) {
-        gpu_wait(d);
-        if (d->n_clip > INT32_MAX) fatalf("more than 2^31 clipped reads on one contig");
-        if (im_clip_build(d->gpu, d->seqlen[tid], (int32_t)d->n_clip, d->clip_pos, d->clip_side) != IM_OK) fatalf("im_clip_build: %s", im_last_error(d->gpu));
-        phase_time("clip arrays (device)");
-    }
-    if (CLIPTAIL_ON) {
-        /* -V: the contig's entries go up in one call; the table is keyed by contig, what earlier contigs left does not matter */
-        cliptail_enable(d);
-        if (d->n_tail > INT32_MAX) fatalf("more than 2^31 clipped reads on one contig");
-        if (im_cliptail_add(d->gpu, tid, (int32_t)d->n_tail, d->tail_pos, d->tail_side, d->tail_n, d->tail_planes) != IM_OK) fatalf("im_cliptail_add: %s", im_last_error(d->gpu));
-        phase_time("clip tails (device)");
-    }
-    if (PAIRLINK_ON) {
-        /* -M: the contig's links go up in one call; this table is keyed by contig too */
-        pairlink_enable(d);
-        if (d->n_link > INT32_MAX) fatalf("more than 2^31 pair links on one contig");
-        if (im_pairlink_add(d->gpu, tid, (int32_t)d->n_link, d->link_pos, d->link_mpos, d->link_kind) != IM_OK) fatalf("im_pairlink_add: %s", im_last_error(d->gpu));
-        phase_time("pair links (device)");
-    }
+    /* -G, -A, -P: the contig's stretch of the scattered difference arrays becomes counts; the clip arrays and the tables need nothing */
+    if (SPAN_ON) GPU2(d, im_span_scan(d->gpu, tid, im_ctx_stream(d->gpu)));
+    if (PAIR_ON) GPU2(d, im_pairspan_scan(d->gpu, tid, im_ctx_stream(d->gpu)));
+    if (SPAN_ON || PAIR_ON) GPU2(d, im_stream_sync(d->gpu, im_ctx_stream(d->gpu)));
+    phase_time("evidence arrays (device)");
 
     im_read_result* res = NULL;
     if (d->cb.n > 0) {

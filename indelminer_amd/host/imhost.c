@@ -114,14 +114,12 @@ extern int im_span_enable(im_ctx*, int32_t, int32_t) __attribute__((weak));
 extern int im_dev_span_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
 extern int im_span_scan(im_ctx*, int32_t, void*) __attribute__((weak));
 extern int im_span_query_tid(im_ctx*, int32_t, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
-extern int im_span_build(im_ctx*, int64_t, int32_t, const int32_t*, const int32_t*, int32_t) __attribute__((weak));
-extern int im_span_query(im_ctx*, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
 /* -A: annotate mode with read counts for and against every known indel (GT:AD:GQ per record), from the device's counting form
  * of the annotate-mode Smith-Waterman and the same span array.  Not an option of the reference either; referenced weakly too. */
 static int g_known_counts = 0;
 extern int im_support_count(im_ctx*, int32_t, const im_known_variant*, const uint8_t*, int64_t, int32_t, const im_count_task*, const uint8_t*, int64_t, int32_t*) __attribute__((weak));
 #define SPAN_ON (g_genotype || g_known_counts)     /* the walk scatters the span array */
-#define SPAN_API_PRESENT (im_span_enable && im_dev_span_scatter && im_span_scan && im_span_query_tid && im_span_build && im_span_query)
+#define SPAN_API_PRESENT (im_span_enable && im_dev_span_scatter && im_span_scan && im_span_query_tid)
 /* -P, with -G or -A: PAIRED_READ records get their columns too, from the device's count of concordant pairs whose fragment spans
  * the deletion (one more genome-wide array).  Not an option of the reference; referenced weakly like the span entries. */
 static int g_pair_counts = 0;
@@ -129,10 +127,8 @@ extern int im_pairspan_enable(im_ctx*, int32_t, int32_t) __attribute__((weak));
 extern int im_dev_pairspan_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
 extern int im_pairspan_scan(im_ctx*, int32_t, void*) __attribute__((weak));
 extern int im_pairspan_query_tid(im_ctx*, int32_t, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
-extern int im_pairspan_build(im_ctx*, int64_t, int32_t, const int32_t*, const int32_t*, int32_t) __attribute__((weak));
-extern int im_pairspan_query(im_ctx*, int32_t, const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
 #define PAIR_ON (g_pair_counts)                    /* the walk scatters the pair-span array */
-#define PAIR_API_PRESENT (im_pairspan_enable && im_dev_pairspan_scatter && im_pairspan_scan && im_pairspan_query_tid && im_pairspan_build && im_pairspan_query)
+#define PAIR_API_PRESENT (im_pairspan_enable && im_dev_pairspan_scatter && im_pairspan_scan && im_pairspan_query_tid)
 /* -D, with -G: depth evidence for the deletions of DEPTH_EV_MIN_LEN bases and more (FORMAT DM:DFC) -- the device's median of the
  * depth array inside the deletion and over DEPTH_EV_FLANK bases on either side.  Not an option of the reference; referenced weakly. */
 static int g_depth_evidence = 0;
@@ -151,10 +147,8 @@ extern int im_clip_enable(im_ctx*, int32_t, int32_t) __attribute__((weak));
 extern int im_dev_clip_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
 extern int im_clip_reset(im_ctx*, int32_t, void*) __attribute__((weak));
 extern int im_clip_query_tid(im_ctx*, int32_t, int32_t, const uint8_t*, const int32_t*, const int32_t*, uint32_t*, int32_t*) __attribute__((weak));
-extern int im_clip_build(im_ctx*, int64_t, int32_t, const int32_t*, const uint8_t*) __attribute__((weak));
-extern int im_clip_query(im_ctx*, int32_t, const uint8_t*, const int32_t*, const int32_t*, uint32_t*, int32_t*) __attribute__((weak));
 #define CLIP_ON (g_clip_evidence)                  /* the walk scatters the two clip arrays */
-#define CLIP_API_PRESENT (im_clip_enable && im_dev_clip_scatter && im_clip_reset && im_clip_query_tid && im_clip_build && im_clip_query)
+#define CLIP_API_PRESENT (im_clip_enable && im_dev_clip_scatter && im_clip_reset && im_clip_query_tid)
 #define CLIP_EV_MIN_CLIP 20        /* soft-clipped bases of the shortest clip that counts */
 #define CLIP_EV_SLACK 10           /* positions the windows reach beyond where the record puts its breakpoints */
 /* -V, with -G -C: the clipped bases of the reads CB / CS counted, against the reference behind the partner breakpoint (FORMAT CV:CH) --
@@ -163,12 +157,11 @@ extern int im_clip_query(im_ctx*, int32_t, const uint8_t*, const int32_t*, const
 static int g_clip_verify = 0;
 extern int im_cliptail_enable(im_ctx*, int32_t, int32_t, int32_t) __attribute__((weak));
 extern int im_dev_cliptail_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
-extern int im_cliptail_add(im_ctx*, int32_t, int32_t, const int32_t*, const uint8_t*, const uint8_t*, const uint32_t*) __attribute__((weak));
 extern int im_cliptail_verify(im_ctx*, int32_t, int32_t, const int32_t*, const int32_t*, int32_t, uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*) __attribute__((weak));
 extern int im_cliptail_reset(im_ctx*, void*) __attribute__((weak));
 extern int im_cliptail_stats(im_ctx*, uint64_t*, uint64_t*) __attribute__((weak));
 #define CLIPTAIL_ON (g_clip_verify)                /* the walk also keeps the clipped bases */
-#define CLIPTAIL_API_PRESENT (im_cliptail_enable && im_dev_cliptail_scatter && im_cliptail_add && im_cliptail_verify && im_cliptail_reset && im_cliptail_stats)
+#define CLIPTAIL_API_PRESENT (im_cliptail_enable && im_dev_cliptail_scatter && im_cliptail_verify && im_cliptail_reset && im_cliptail_stats)
 #define CLIPTAIL_BASES 32          /* bases an entry keeps at most */
 #define CLIPTAIL_MAX_SHIFT 32      /* the largest micro-homology a query tries */
 #define CLIPTAIL_NONE 0xFFFFFFFFu  /* what the device answers after its table has overflowed */
@@ -178,9 +171,8 @@ extern int im_cliptail_stats(im_ctx*, uint64_t*, uint64_t*) __attribute__((weak)
  * own, written to FILE; stdout and stderr stay as they are.  Not an option of the reference; referenced weakly. */
 static const char* g_ins_file = NULL;
 extern int im_clip_facing_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
-extern int im_clip_facing(im_ctx*, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
 extern int im_cliptail_consensus(im_ctx*, int32_t, int32_t, const int32_t*, const uint8_t*, int32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*) __attribute__((weak));
-#define FACING_API_PRESENT (im_clip_facing_tid && im_clip_facing && im_cliptail_consensus)
+#define FACING_API_PRESENT (im_clip_facing_tid && im_cliptail_consensus)
 #define INS_EV_MIN_READS 3         /* clipped reads of the smaller pile */
 #define INS_EV_MAX_OVERLAP 30      /* bases the left-clip pile may stand in front of the right-clip pile: below DEPTH_EV_MIN_LEN, so the two
                                     * piles of a deletion that gets CB:CS can never face each other */
@@ -191,13 +183,9 @@ extern int im_cliptail_consensus(im_ctx*, int32_t, int32_t, const int32_t*, cons
  * VCF of its own, written to FILE; with -D every record carries the median depth inside and beside it.  stdout, stderr and -I's FILE
  * stay as they are.  Not an option of the reference; referenced weakly. */
 static const char* g_dup_file = NULL;
-extern int im_clip_peaks_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, uint32_t*, int32_t*) __attribute__((weak));
-extern int im_clip_peaks(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t*, uint32_t*, int32_t*) __attribute__((weak));
 extern int im_clip_crossed_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*,
                                uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
-extern int im_clip_crossed(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint32_t*, uint32_t*,
-                           uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
-#define CROSSED_API_PRESENT (im_clip_peaks_tid && im_clip_peaks && im_clip_crossed_tid && im_clip_crossed)
+#define CROSSED_API_PRESENT (im_clip_crossed_tid)
 #define DUP_EV_MIN_READS 3         /* clipped reads of the smaller pile */
 #define DUP_EV_REACH 30            /* the reach of a peak: the peaks -I sees */
 #define DUP_EV_MIN_LEN 50          /* the shortest duplication: DEPTH_EV_MIN_LEN, and above INS_EV_MAX_OVERLAP, so no pair of piles is ever both a
@@ -212,9 +200,7 @@ extern int im_clip_crossed(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t,
 static const char* g_inv_file = NULL;
 extern int im_clip_inverted_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint8_t*, int32_t*, int32_t*, uint32_t*,
                                 uint32_t*, uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
-extern int im_clip_inverted(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint8_t*, int32_t*, int32_t*, uint32_t*,
-                            uint32_t*, uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
-#define INVERTED_API_PRESENT (im_clip_inverted_tid && im_clip_inverted)
+#define INVERTED_API_PRESENT (im_clip_inverted_tid)
 #define INV_EV_MIN_READS 3         /* clipped reads of the smaller pile */
 #define INV_EV_REACH 30            /* the reach of a peak: the peaks -I and -U see */
 #define INV_EV_MIN_LEN 50          /* the shortest inversion */
@@ -229,12 +215,11 @@ extern int im_clip_inverted(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t
 static int g_pair_links = 0;
 extern int im_pairlink_enable(im_ctx*, int32_t, int32_t) __attribute__((weak));
 extern int im_dev_pairlink_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
-extern int im_pairlink_add(im_ctx*, int32_t, int32_t, const int32_t*, const int32_t*, const uint8_t*) __attribute__((weak));
 extern int im_pairlink_count(im_ctx*, int32_t, int32_t, const uint8_t*, const int32_t*, const int32_t*, const int32_t*, const int32_t*, int32_t, uint32_t*) __attribute__((weak));
 extern int im_pairlink_reset(im_ctx*, void*) __attribute__((weak));
 extern int im_pairlink_stats(im_ctx*, uint64_t*, uint64_t*) __attribute__((weak));
 #define PAIRLINK_ON (g_pair_links)                 /* the walk also keeps the pair links */
-#define PAIRLINK_API_PRESENT (im_pairlink_enable && im_dev_pairlink_scatter && im_pairlink_add && im_pairlink_count && im_pairlink_reset && im_pairlink_stats)
+#define PAIRLINK_API_PRESENT (im_pairlink_enable && im_dev_pairlink_scatter && im_pairlink_count && im_pairlink_reset && im_pairlink_stats)
 #define LINK_EV_WINDOW 1000        /* bases a window reaches from a breakpoint towards where the junction's pairs lie: above the largest insert of
                                     * the usual libraries, so the read of a spanning pair that lies away from the breakpoint is inside */
 #define LINK_EV_MIN_SEP 50         /* mpos - pos of the nearest pair that counts: DUP_EV_MIN_LEN and INV_EV_MIN_LEN */

@@ -458,3 +458,34 @@ def test_product_after_an_overflow_of_the_link_table(tmp_path):
     assert r1.returncode == 0 and open(f0, "rb").read() == plain and open(f1, "rb").read() == want
     line = b"indelminer: -M: the pair-link table overflowed (2048 links stored, 52 dropped): PE is . in the files of -U and -N\n"
     assert r1.stdout == r0.stdout and r1.stderr == r0.stderr + line
+
+
+def test_product_record_at_a_time_chunk_edges(tmp_path):
+    """The record-at-a-time path hands its records to the scatters in chunks (run_contig).  The planted duplications, 18 000 records,
+    with every evidence option on, at caps of records per chunk that cut inside every launch shape: one record per launch, the
+    one-wave scatters' workgroup (64), the 256-record scatter workgroup with its LDS window, one past it, and the default (one chunk).
+    stdout, stderr and the three FILEs are the same bytes in all five runs, the default pipelined run's, and the restatement's."""
+    from tests.test_gpu_depth_evidence import depth_of_bam
+    refs, rd, _ = pk.planted_dup_reads()
+    assert rd.n <= 20_000
+    d = pk.write_planted(str(tmp_path), refs, rd)
+    bam, fa = d + "/aln.bam", d + "/ref.fa"
+    dup_pe_d = pk.render_of_bam("DUP", bam, fa, 10, depth_of_bam(bam)[1])[1]
+    inv_pe = pk.render_of_bam("INV", bam, fa, 10)[1]
+    prod = _product()
+
+    def leg(k, env):
+        files = [str(tmp_path / ("%s%d" % (f, k))) for f in "iun"]
+        flags = BASE + ["-G", "-P", "-D", "-C", "-V", "-I", files[0], "-U", files[1], "-N", files[2], "-M"]
+        r = subprocess.run([prod] + flags + ["ref.fa", "sample=aln.bam"], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           env=dict(os.environ, **env), timeout=120)
+        _ok(r)
+        return [r.stdout, r.stderr] + [open(f, "rb").read() for f in files]
+
+    want = leg(0, {})
+    assert want[3] == dup_pe_d and want[4] == inv_pe and want[3].count(b";PE=3\n") == 4 and len(want[0]) > 1000
+    for k, cap in enumerate(("1", "64", "256", "257", None), 1):
+        env = {"INDELMINER_PIPELINE": "host"}
+        if cap is not None:
+            env["INDELMINER_HOST_CHUNK_RECS"] = cap
+        assert leg(k, env) == want, cap

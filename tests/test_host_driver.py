@@ -1132,3 +1132,18 @@ def test_product_odd_inputs_match_the_reference(tmp_path):
     """the product with its real kernels: records made odd in every way the reference has an opinion on, random flags, read
     groups, with and without a configuration file -- exit status and stdout as the compiled reference gave them"""
     assert _odd_inputs(_product(), tmp_path, [{}, {"INDELMINER_WALKERS": "1", "INDELMINER_REPLAYERS": "1"}]) > 80
+
+
+@pytest.mark.parametrize("cap", ["1", "3", None])
+def test_host_record_at_a_time_chunk_edges(cap):
+    """the record-at-a-time path cycles one chunk of records (run_contig); whatever the cap of records per chunk, the bytes are the same"""
+    env = {"INDELMINER_PIPELINE": "host"}
+    if cap is not None:
+        env["INDELMINER_HOST_CHUNK_RECS"] = cap
+    assert _run(_build_shim(), FLAG_MATRIX["default_config"], TD, env=env) == _golden("default_config")
+
+
+def test_host_record_at_a_time_chunk_of_a_pass_the_reference_dies_in(tmp_path):
+    """seed 20003: a record the reference dies on in the middle of a contig -- the pass ends by the jump out of dispatch_record and
+    the chunk that holds the record is submitted behind it; status and stdout as the compiled reference gave them"""
+    assert _odd_inputs(_build_shim(), tmp_path, [{"INDELMINER_PIPELINE": "host", "INDELMINER_HOST_CHUNK_RECS": "1"}], seeds={20003}) == 0
