@@ -791,6 +791,81 @@ int im_pairlink_count(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kind,
 int im_pairlink_reset(im_ctx* ctx, void* stream);
 int im_pairlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
 
+/* Mate links, the read pairs whose reads lie on TWO contigs (-T).  Everything above stops at the contig's edge: the pile pairs are of
+ * one contig and a pair link needs mtid == tid.  A junction between two contigs -- a translocation -- leaves a clip pile on either
+ * contig and a bundle of pairs with one read near each.  A third keyed table, beside the clip-tail and the pair-link table, keeps one
+ * link per READ of such a pair, and a query asks where the mates of the reads around a position lie: without it every pile would have
+ * to be tried against every pile of every other contig.
+ *
+ * WHICH RECORDS STORE A LINK.  With q = min_mapq a delivered record is a MATE LINK iff all of
+ *   flag & 0x1 is set and none of 0x4 | 0x8 | 0x100 | 0x200 | 0x400 | 0x800 is;
+ *   0 <= tid < n_contigs, 0 <= mtid < n_contigs and mtid != tid;
+ *   mapq >= q (the record's own mapping quality; its mate's is not known);
+ *   0 <= pos <= length[tid] and 0 <= mpos <= length[mtid]
+ * hold.  EVERY such record stores one link at its own contig: there is no leftmost-read rule, the two reads of a pair store one link
+ * each, and a query from either contig finds the pair.  kind = r | m << 1 with r = (flag >> 4) & 1 (this read reverse) and
+ * m = (flag >> 5) & 1 (its mate reverse): four kinds, 0 .. 3.  A link is (tid, kind, pos, mtid, mpos).  Only the 32-byte core of the
+ * record is read, so both delivered record forms are taken (im_dev_records); no read group is looked up.
+ *
+ * A PARTNER QUERY is (kind, a0, a1) on contig tid.  The interval is inclusive and is clipped to [0, length]; a1 - a0 above 65 535 before
+ * the clip is IM_E_ARG, and so is a kind outside 0 .. 3.
+ *   L = the stored links of contig tid and that kind with a0 <= pos <= a1;
+ *   the CELL of a link is (mtid, mpos >> 10);
+ *   score(mtid, c) = the number of links of L in the cells (mtid, c) and (mtid, c + 1);
+ *   the WINNER is the (mtid, c) of the largest score; among equals the smallest mtid wins, then the smallest c.
+ * Two neighbouring cells span 2 048 bases, so a bundle of mates within some 1 000 bases of each other is always inside one pair of
+ * cells, wherever the cell borders fall.  The answer per query is n_links = |L|, mtid, n_partner = the winner's score, and lo, hi = the
+ * smallest and the largest mpos among the winner's links (those of L in its two cells).  |L| = 0 answers mtid = -1 and zeros.  A query
+ * keeps at most IM_MATELINK_CELLS = 256 distinct cells: one whose links lie in more answers mtid = -2, n_partner = lo = hi = 0, with
+ * n_links still exact -- no answer, not a wrong one (a pile in a repeat, whose mates scatter over the genome).  Whether that happens
+ * depends on the set of links alone; no output depends on the order in which the links arrived.
+ *
+ * THE TABLE has 2^log2_slots slots of 16 bytes (6 <= log2_slots <= 30), the design of the other two: a multimap with open addressing;
+ * the home slot of a link is (key * 0x9E3779B97F4A7C15) >> (64 - log2_slots) with key = 1 << 63 | tid << 26 | (pos >> 8) << 2 | kind, so
+ * all links of one (tid, 256-base bucket, kind) lie on one probe run; the payload is (pos & 255) | mtid << 8 | mpos << 32; probing is
+ * linear and wraps past the last slot.  Only half of the slots are ever taken: the number of links stored is exactly
+ * min(links asked for, 2^log2_slots / 2) and the rest are counted as dropped.  Once dropped > 0 an answer could miss links, so
+ * im_matelink_partner then returns IM_OK and fills EVERY output of the call with 0xFFFFFFFF (mtid, lo, hi: -1): no answer, not a wrong
+ * one.  A query walks one probe run per bucket of [a0, a1], at most 257.
+ *
+ * im_matelink_enable allocates the table (16 << log2_slots bytes of HBM, on this call only; the reference must be set, at most 2^24
+ * contigs) and fixes min_mapq: a second call with other values is refused.  A new reference frees it with the other two tables.
+ * im_dev_matelink_scatter adds the links of a chunk of delivered records (one launch of its own, asynchronous); without
+ * im_matelink_enable it is IM_E_ARG with a message.  im_matelink_add adds n links of contig tid the caller names as pos, mtid, mpos and
+ * kind 0 .. 3; it applies the rule's range checks itself: a link with mtid outside [0, n_contigs), mtid == tid or a position outside
+ * [0, length] of its contig is dropped without counting; synchronous.  im_matelink_partner answers nq queries of contig tid;
+ * synchronous, on the context's stream.  im_matelink_reset puts all slots and both counters back to zero.  im_matelink_stats gives the
+ * links stored and dropped since the last reset; synchronous. */
+#define IM_MATELINK_CELLS 256
+int im_matelink_enable(im_ctx* ctx, int32_t min_mapq, int32_t log2_slots);
+int im_dev_matelink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream);
+int im_matelink_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, const int32_t* mtid, const int32_t* mpos, const uint8_t* kind);
+int im_matelink_partner(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kind, const int32_t* a0, const int32_t* a1, uint32_t* n_links,
+                        int32_t* mtid_out, uint32_t* n_partner, int32_t* lo, int32_t* hi);
+int im_matelink_reset(im_ctx* ctx, void* stream);
+int im_matelink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
+
+/* Junctions, the clip tails of one pile against ANOTHER CONTIG (-T), and the one statement of the four verify rules above.  A query is
+ * two ends (tid1, p1, side1) and (tid2, p2, side2) with max_shift S, 0 <= S <= 32; a side is 0 = the right clips piled up at the
+ * position, 1 = the left clips.  The two contigs may be the same, and there is NO condition on the order of the positions.
+ * An entry at end A, of n bases, base 0 nearest the junction, is compared with the reference at the OTHER end (tidB, pB, sideB): for a
+ * shift s = 0 .. S its base i is expected to be
+ *   sideB = 1:  refB[pB + s + i]          (the other end's reads were clipped on their left: its contig goes on forwards from pB)
+ *   sideB = 0:  refB[pB - 1 - s - i]      (clipped on their right: its contig runs backwards from the base in front of pB)
+ * and, iff sideA == sideB, the COMPLEMENT of that reference byte (two piles of one side join the two strands).  The entry MATCHES iff
+ * at most n >> 4 of its n bases differ from what is expected; a position outside [0, length[tidB]) and a reference byte other than
+ * A, C, G, T (the resident reference is upper-cased ASCII) are mismatches.  v1(s), v2(s) are the matching entries at end 1 and end 2;
+ * the chosen s has the largest v1(s) + v2(s) over 0 .. S, the smallest s among equals.  The answer is v1, v2 and s of that shift and
+ * stored1, stored2, the numbers of entries stored at the two keys, whatever their bases; a best sum of 0 answers 0, 0, -1; an end whose
+ * position lies outside [0, length] has no entry.  Once the clip-tail table has dropped entries every output of the call is
+ * 0xFFFFFFFF (shift: -1).
+ * With tid1 == tid2 this is, to the letter: im_cliptail_verify for (pr, 0) and (pl, 1) with pl > pr; the crossed rule for (pr, 0) and
+ * (pl, 1) with pl < pr; the inverted rules for (x, sigma) and (y, sigma).  A contig outside 0 .. n_contigs - 1, a side other than 0 and
+ * 1, S outside 0 .. 32, a negative nq or a null array with nq >= 1 is IM_E_ARG; so are a table that is not enabled and a reference that
+ * is not set.  Synchronous, on the context's stream. */
+int im_cliptail_junction(im_ctx* ctx, int32_t nq, const int32_t* tid1, const int32_t* p1, const uint8_t* side1, const int32_t* tid2, const int32_t* p2,
+                         const uint8_t* side2, int32_t max_shift, uint32_t* v1, uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

@@ -250,6 +250,13 @@ def lib():
         L.im_pairlink_count.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.im_pairlink_reset.argtypes = [C.c_void_p, C.c_void_p]
         L.im_pairlink_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.im_matelink_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.im_dev_matelink_scatter.argtypes = [C.c_void_p, C.POINTER(DevRecords), C.c_void_p]
+        L.im_matelink_add.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_matelink_partner.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 8
+        L.im_matelink_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.im_matelink_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.im_cliptail_junction.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 5
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.im_capture_begin.argtypes = [C.c_void_p, C.c_void_p]
@@ -728,6 +735,55 @@ class Context:
         stored, dropped = C.c_uint64(0), C.c_uint64(0)
         self._check(lib().im_pairlink_stats(self.h, C.byref(stored), C.byref(dropped)))
         return int(stored.value), int(dropped.value)
+
+    def matelink_enable(self, min_mapq, log2_slots):
+        """the keyed table of mate links (-T): 2^log2_slots slots of 16 bytes, half of them usable"""
+        self._check(lib().im_matelink_enable(self.h, int(min_mapq), int(log2_slots)))
+
+    def matelink_scatter(self, recs, stream=None):
+        """DevRecords -> one link per record of a pair whose mate lies on another contig (asynchronous)"""
+        self._check(lib().im_dev_matelink_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
+
+    def matelink_add(self, tid, pos, mtid, mpos, kind):
+        """links of contig tid as the caller found them: pos, mtid, mpos, kind (read reverse | mate reverse << 1)"""
+        pos, mtid, mpos = (np.ascontiguousarray(x, dtype=np.int32) for x in (pos, mtid, mpos))
+        kind = np.ascontiguousarray(kind, dtype=np.uint8)
+        assert len(pos) == len(mtid) == len(mpos) == len(kind)
+        self._check(lib().im_matelink_add(self.h, int(tid), len(pos), _ptr(pos), _ptr(mtid), _ptr(mpos), _ptr(kind)))
+
+    def matelink_partner(self, tid, kind, a0, a1):
+        """per query (kind, [a0, a1]) on contig tid: (n_links, mtid, n_partner, lo, hi) -- the links of that kind inside the interval,
+        the contig most of their mates lie on within two neighbouring 1 024-base cells, their number and their mates' range; mtid -1: no
+        link, -2: more than 256 cells; after an overflow every value is 0xFFFFFFFF (mtid, lo, hi: -1)"""
+        kind = np.ascontiguousarray(kind, dtype=np.uint8)
+        a0, a1 = (np.ascontiguousarray(x, dtype=np.int32) for x in (a0, a1))
+        n = len(kind)
+        assert len(a0) == len(a1) == n
+        out = [np.zeros(max(n, 1), dtype=np.uint32 if k in (0, 2) else np.int32) for k in range(5)]
+        self._check(lib().im_matelink_partner(self.h, int(tid), n, _ptr(kind), _ptr(a0), _ptr(a1), *[_ptr(o) for o in out]))
+        return tuple(o[:n] for o in out)
+
+    def matelink_reset(self, stream=None):
+        self._check(lib().im_matelink_reset(self.h, self.stream if stream is None else stream))
+
+    def matelink_stats(self):
+        """(links stored, links dropped) since the last reset"""
+        stored, dropped = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().im_matelink_stats(self.h, C.byref(stored), C.byref(dropped)))
+        return int(stored.value), int(dropped.value)
+
+    def cliptail_junction(self, tid1, p1, side1, tid2, p2, side2, max_shift=32):
+        """per query of two ends (tid, position, side 0: right clips, 1: left clips): (v1, v2, shift, stored1, stored2) -- the entries of
+        either end that continue in the other end's contig at the best shift; after an overflow every value is 0xFFFFFFFF and every
+        shift -1"""
+        tid1, p1, tid2, p2 = (np.ascontiguousarray(x, dtype=np.int32) for x in (tid1, p1, tid2, p2))
+        side1, side2 = (np.ascontiguousarray(x, dtype=np.uint8) for x in (side1, side2))
+        n = len(tid1)
+        assert len(p1) == len(side1) == len(tid2) == len(p2) == len(side2) == n
+        out = [np.zeros(max(n, 1), dtype=np.int32 if k == 2 else np.uint32) for k in range(5)]
+        self._check(lib().im_cliptail_junction(self.h, n, _ptr(tid1), _ptr(p1), _ptr(side1), _ptr(tid2), _ptr(p2), _ptr(side2), int(max_shift),
+                                               *[_ptr(o) for o in out]))
+        return tuple(o[:n] for o in out)
 
     _CROSSED = (np.int32, np.int32, np.uint32, np.uint32, np.uint32, np.uint32, np.int32, np.uint32, np.uint32)
 

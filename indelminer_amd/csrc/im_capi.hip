@@ -69,6 +69,9 @@ struct im_ctx {
     // -M: the keyed table of pair links (im_pairlink_enable), an allocation of its own; slots null: not enabled
     im::KeyedTable link = {nullptr, nullptr, 0};
     int32_t link_min_mapq = 0;
+    // -T: the keyed table of mate links (im_matelink_enable), a third allocation; slots null: not enabled
+    im::KeyedTable mate = {nullptr, nullptr, 0};
+    int32_t mate_min_mapq = 0;
     // the median queries' histograms of queries of several slabs (im::launch_depth_median): zeros between calls, sized by the call that
     // needed the most; med_dirty: a call did not get to its end, the next one clears them
     uint32_t* med_scratch = nullptr;
@@ -158,15 +161,15 @@ void free_reference(im_ctx* ctx)
         g->data = nullptr; g->sums = nullptr;
     }
     ctx->h_asc_off.clear(); ctx->h_len.clear(); ctx->ref_total = 0;
-    // the clip-tail table and the pair-link table are keyed by the contigs of the reference that goes
-    for (im::KeyedTable* t : {&ctx->tail, &ctx->link}) {
+    // the clip-tail table, the pair-link table and the mate-link table are keyed by the contigs of the reference that goes
+    for (im::KeyedTable* t : {&ctx->tail, &ctx->link, &ctx->mate}) {
         if (t->slots) (void)hipFree(t->slots);
         if (t->counters) (void)hipFree(t->counters);
         *t = {nullptr, nullptr, 0};
     }
 }
 
-// ---- the keyed table (im_keyed.hpp) behind the clip tails (im_ctx::tail) and the pair links (im_ctx::link) ----------
+// ---- the keyed table (im_keyed.hpp) behind the clip tails (im_ctx::tail), the pair links (im_ctx::link) and the mate links (im_ctx::mate) ----------
 
 // The checks both tables share; then, unless the member is enabled already -- which the caller has looked at, and compares its own
 // parameters for -- its slots and counters allocated, cleared and waited for.  who: the entry point, for the messages.
@@ -1641,6 +1644,123 @@ int im_pairlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped)
 {
     if (!ctx || !ctx->link.slots || !stored || !dropped) return IM_E_ARG;
     return keyed_stats(ctx, ctx->link, stored, dropped);
+}
+
+// ---- mate links: the read pairs whose mate lies on another contig, asked where the mates of a window lie (-T) ----------
+
+int im_matelink_enable(im_ctx* ctx, int32_t min_mapq, int32_t log2_slots)
+{
+    if (!ctx) return IM_E_ARG;
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    const bool enabled = ctx->mate.slots;
+    const int rc = keyed_enable(ctx, &im_ctx::mate, "im_matelink_enable", log2_slots);
+    if (rc) return rc;
+    if (enabled && (min_mapq != ctx->mate_min_mapq || log2_slots != ctx->mate.log2_slots)) {
+        set_err(ctx, "im_matelink_enable: already enabled with min_mapq %d, log2_slots %d", ctx->mate_min_mapq, ctx->mate.log2_slots);
+        return IM_E_ARG;
+    }
+    ctx->mate_min_mapq = min_mapq;
+    return IM_OK;
+}
+
+int im_dev_matelink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
+{
+    if (!ctx || !recs) return IM_E_ARG;
+    if (!ctx->mate.slots) { set_err(ctx, "im_matelink_enable has not been called"); return IM_E_ARG; }
+    if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, im::launch_matelink_scatter(ref_dev(ctx), ctx->mate_min_mapq, *recs, ctx->mate, (hipStream_t)stream));
+    return IM_OK;
+}
+
+// the host names the links: checked here, staged through the workspace, one lane inserts each, wait
+int im_matelink_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, const int32_t* mtid, const int32_t* mpos, const uint8_t* kind)
+{
+    if (!ctx || n < 0 || (n > 0 && (!pos || !mtid || !mpos || !kind))) return IM_E_ARG;
+    if (!ctx->mate.slots) { set_err(ctx, "im_matelink_enable has not been called"); return IM_E_ARG; }
+    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    for (int32_t i = 0; i < n; i++)
+        if (kind[i] > 3) { set_err(ctx, "im_matelink_add: link %d: kind %d, must be 0 .. 3 (read reverse | mate reverse << 1)", i, (int)kind[i]); return IM_E_ARG; }
+    if (n == 0) return IM_OK;
+    WsColumns C;                                                    // pos, mtid, mpos, kind
+    int rc = ws_columns(ctx, n, 4, &C);
+    if (rc || (rc = C.down(0, pos, 4)) || (rc = C.down(1, mtid, 4)) || (rc = C.down(2, mpos, 4)) || (rc = C.down(3, kind, 1))) return rc;
+    HIP_TRY(ctx, im::launch_matelink_add(ref_dev(ctx), n, tid, C.at<int32_t>(0), C.at<int32_t>(1), C.at<int32_t>(2), C.at<uint8_t>(3), ctx->mate, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+// [kind][a0][a1] in, one launch, the five answers and the two counters back, one wait; after an overflow every answer is "none"
+int im_matelink_partner(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kind, const int32_t* a0, const int32_t* a1, uint32_t* n_links,
+                        int32_t* mtid_out, uint32_t* n_partner, int32_t* lo, int32_t* hi)
+{
+    if (!ctx || nq < 0) return IM_E_ARG;
+    if (!ctx->mate.slots) { set_err(ctx, "im_matelink_enable has not been called"); return IM_E_ARG; }
+    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    if (nq == 0) return IM_OK;
+    if (!kind || !a0 || !a1 || !n_links || !mtid_out || !n_partner || !lo || !hi) return IM_E_ARG;
+    for (int32_t q = 0; q < nq; q++) {
+        if (kind[q] > 3) { set_err(ctx, "im_matelink_partner: query %d: kind %d, must be 0 .. 3 (read reverse | mate reverse << 1)", q, (int)kind[q]); return IM_E_ARG; }
+        // the wave walks one probe run per 256-base bucket of [a0, a1]: 257 at the most
+        if ((int64_t)a1[q] - (int64_t)a0[q] > 65535) { set_err(ctx, "im_matelink_partner: query %d: a1 - a0 = %lld, must be <= 65535", q, (long long)a1[q] - (long long)a0[q]); return IM_E_ARG; }
+    }
+    WsColumns C;                                                    // a0, a1, kind, then the five answers
+    int rc = ws_columns(ctx, nq, 8, &C);
+    if (rc || (rc = C.down(0, a0, 4)) || (rc = C.down(1, a1, 4)) || (rc = C.down(2, kind, 1))) return rc;
+    HIP_TRY(ctx, im::launch_matelink_partner(nq, tid, C.at<uint8_t>(2), C.at<int32_t>(0), C.at<int32_t>(1), ctx->h_len[tid], ctx->mate, C.at<uint32_t>(3),
+                                             C.at<int32_t>(4), C.at<uint32_t>(5), C.at<int32_t>(6), C.at<int32_t>(7), ctx->stream));
+    void* const h_out[5] = {n_links, mtid_out, n_partner, lo, hi};
+    for (int k = 0; k < 5 && !rc; k++) rc = C.up(3 + k, h_out[k], 4);
+    bool over = false;
+    if (rc || (rc = keyed_overflowed(ctx, ctx->mate, &over))) return rc;
+    if (over) for (int k = 0; k < 5; k++) memset(h_out[k], 0xFF, sizeof(uint32_t) * (size_t)nq);
+    return IM_OK;
+}
+
+int im_matelink_reset(im_ctx* ctx, void* stream)
+{
+    if (!ctx || !ctx->mate.slots) return IM_E_ARG;
+    return keyed_reset(ctx, ctx->mate, stream);
+}
+
+int im_matelink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped)
+{
+    if (!ctx || !ctx->mate.slots || !stored || !dropped) return IM_E_ARG;
+    return keyed_stats(ctx, ctx->mate, stored, dropped);
+}
+
+// six columns in, one launch, the five answers and the two counters back, one wait; after an overflow every answer is "none"
+int im_cliptail_junction(im_ctx* ctx, int32_t nq, const int32_t* tid1, const int32_t* p1, const uint8_t* side1, const int32_t* tid2, const int32_t* p2,
+                         const uint8_t* side2, int32_t max_shift, uint32_t* v1, uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2)
+{
+    if (!ctx || nq < 0) return IM_E_ARG;
+    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
+    if (max_shift < 0 || max_shift > 32) { set_err(ctx, "im_cliptail_junction: max_shift %d, must be 0 .. 32", max_shift); return IM_E_ARG; }
+    if (nq == 0) return IM_OK;
+    if (!tid1 || !p1 || !side1 || !tid2 || !p2 || !side2 || !v1 || !v2 || !shift || !stored1 || !stored2) return IM_E_ARG;
+    for (int32_t q = 0; q < nq; q++) {
+        if (tid1[q] < 0 || tid1[q] >= ctx->n_contigs || tid2[q] < 0 || tid2[q] >= ctx->n_contigs) {
+            set_err(ctx, "im_cliptail_junction: query %d: contigs %d and %d, must be 0 .. %d", q, tid1[q], tid2[q], ctx->n_contigs - 1);
+            return IM_E_ARG;
+        }
+        if (side1[q] > 1 || side2[q] > 1) { set_err(ctx, "im_cliptail_junction: query %d: sides %d and %d, must be 0 (right) or 1 (left)", q, (int)side1[q], (int)side2[q]); return IM_E_ARG; }
+    }
+    WsColumns C;                                                    // tid1, p1, tid2, p2, side1, side2, then the five answers
+    int rc = ws_columns(ctx, nq, 11, &C);
+    const int32_t* h_in[4] = {tid1, p1, tid2, p2};
+    for (int k = 0; k < 4 && !rc; k++) rc = C.down(k, h_in[k], 4);
+    if (rc || (rc = C.down(4, side1, 1)) || (rc = C.down(5, side2, 1))) return rc;
+    im::TailJunctionArgs A;
+    A.nq = nq; A.max_shift = max_shift; A.tid1 = C.at<int32_t>(0); A.p1 = C.at<int32_t>(1); A.tid2 = C.at<int32_t>(2); A.p2 = C.at<int32_t>(3);
+    A.side1 = C.at<uint8_t>(4); A.side2 = C.at<uint8_t>(5); A.ref = ref_dev(ctx); A.tab = ctx->tail;
+    A.v1 = C.at<uint32_t>(6); A.v2 = C.at<uint32_t>(7); A.shift = C.at<int32_t>(8); A.stored1 = C.at<uint32_t>(9); A.stored2 = C.at<uint32_t>(10);
+    HIP_TRY(ctx, im::launch_cliptail_junction(A, ctx->stream));
+    void* const h_out[5] = {v1, v2, shift, stored1, stored2};
+    for (int k = 0; k < 5 && !rc; k++) rc = C.up(6 + k, h_out[k], 4);
+    bool over = false;
+    if (rc || (rc = keyed_overflowed(ctx, ctx->tail, &over))) return rc;
+    if (over) for (int k = 0; k < 5; k++) memset(h_out[k], 0xFF, sizeof(uint32_t) * (size_t)nq);
+    return IM_OK;
 }
 
 int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64_t* t_off,

@@ -311,6 +311,39 @@ __global__ __launch_bounds__(kTailWaveBlock) void cliptail_verify_kernel(TailVer
     }
 }
 
+// Junctions (include/indelminer_amd.h, seam 5, "Junctions"): one wave per query (tid1, p1, side1, tid2, p2, side2), the two ends on
+// contigs of their own or on one, in any order.  The entries of an end are expected to hold the OTHER end's contig: forwards from its
+// position when that end's pile is of left clips, backwards from the base in front of it when it is of right clips, the other strand
+// when the two sides are equal -- tail_expected_window with the other contig's bases and length, one 64-base window per end, fetched
+// once.  The chosen shift: tail_best_shift.  The contigs' offsets are 64-bit, as everywhere.
+__global__ __launch_bounds__(kTailWaveBlock) void cliptail_junction_kernel(TailJunctionArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int q = wave; q < A.nq; q += nwaves) {
+        const int32_t t1 = A.tid1[q], t2 = A.tid2[q];
+        const int64_t p1 = A.p1[q], p2 = A.p2[q];
+        const uint32_t s1 = A.side1[q], s2 = A.side2[q];
+        const int64_t clen1 = A.ref.len[t1], clen2 = A.ref.len[t2];
+        const uint8_t* __restrict__ ref1 = A.ref.ascii + A.ref.asc_off[t1];
+        const uint8_t* __restrict__ ref2 = A.ref.ascii + A.ref.asc_off[t2];
+        const bool inverted = s1 == s2;
+        const TailWindow W1 = tail_expected_window(ref2, clen2, p2, s1, inverted, lane);
+        const TailWindow W2 = tail_expected_window(ref1, clen1, p1, s2, inverted, lane);
+        uint32_t v1, v2;
+        const uint32_t st1 = tail_side(A.tab, t1, p1, s1, clen1, W1, true, A.max_shift, lane, &v1);
+        const uint32_t st2 = tail_side(A.tab, t2, p2, s2, clen2, W2, true, A.max_shift, lane, &v2);
+        int best;
+        uint32_t b1, b2;
+        const bool found = tail_best_shift(v1, v2, A.max_shift, lane, &best, &b1, &b2);
+        if (lane == 0) {
+            A.v1[q] = found ? b1 : 0u; A.v2[q] = found ? b2 : 0u; A.shift[q] = found ? best : -1;
+            A.stored1[q] = st1; A.stored2[q] = st2;
+        }
+    }
+}
+
 // the first index of the ascending list at which pos[i] >= x (n when there is none): every lane runs the same search
 __device__ __forceinline__ int32_t first_at_or_behind(const int32_t* __restrict__ pos, int32_t n, int64_t x)
 {
@@ -494,6 +527,13 @@ hipError_t launch_cliptail_verify(int32_t nq, int32_t tid, const int32_t* pr, co
     A.nq = nq; A.tid = tid; A.max_shift = max_shift; A.pr = pr; A.pl = pl; A.ref = ref; A.clen = clen; A.tab = tab;
     A.v_right = v_right; A.v_left = v_left; A.shift = shift; A.stored_right = stored_right; A.stored_left = stored_left;
     hipLaunchKernelGGL(cliptail_verify_kernel, dim3(wave_grid(nq)), dim3(kTailWaveBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_cliptail_junction(const TailJunctionArgs& A, hipStream_t stream)
+{
+    if (A.nq <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cliptail_junction_kernel, dim3(wave_grid(A.nq)), dim3(kTailWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 

@@ -193,6 +193,29 @@ hipError_t launch_pairlink_add(int32_t n, int32_t tid, int64_t clen, const int32
 // in the first, mpos in the second and mpos - pos >= min_sep; the caller holds a1 - a0 to 65 535
 hipError_t launch_pairlink_count(int32_t nq, int32_t tid, const uint8_t* kind, const int32_t* a0, const int32_t* a1, const int32_t* b0,
                                  const int32_t* b1, int32_t min_sep, int64_t clen, const KeyedTable& tab, uint32_t* count, hipStream_t stream);
+// im_matelink.hip: the read pairs whose mate lies on another contig in a keyed table of its own (-T)
+// the records that are a link under the record rule (include/indelminer_amd.h, "Mate links") -> one entry each
+hipError_t launch_matelink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream);
+// one entry per host-named (pos, mtid, mpos, kind 0 .. 3) of contig tid; a link that fails the rule's range checks is dropped
+hipError_t launch_matelink_add(const RefDev& ref, int32_t n, int32_t tid, const int32_t* pos, const int32_t* mtid, const int32_t* mpos,
+                               const uint8_t* kind, const KeyedTable& tab, hipStream_t stream);
+// per query (kind, [a0, a1]) on contig tid, the interval inclusive and clipped to [0, clen]: the links of that kind inside it, the contig
+// and the two neighbouring 1 024-base cells most of their mates lie in, their number and their mates' range (mtid -1: no link, -2: more
+// than IM_MATELINK_CELLS cells); the caller holds a1 - a0 to 65 535
+hipError_t launch_matelink_partner(int32_t nq, int32_t tid, const uint8_t* kind, const int32_t* a0, const int32_t* a1, int64_t clen,
+                                   const KeyedTable& tab, uint32_t* n_links, int32_t* mtid, uint32_t* n_partner, int32_t* lo, int32_t* hi,
+                                   hipStream_t stream);
+// per query (tid1, p1, side1, tid2, p2, side2): the entries at either end that continue in the OTHER end's contig at the best shift
+// 0 .. max_shift <= 32 (include/indelminer_amd.h, "Junctions"), that shift (-1: none matched), and the entries stored at the two keys
+struct TailJunctionArgs {
+    int32_t nq, max_shift;
+    const int32_t* tid1; const int32_t* p1; const uint8_t* side1;
+    const int32_t* tid2; const int32_t* p2; const uint8_t* side2;
+    RefDev ref;
+    KeyedTable tab;
+    uint32_t* v1; uint32_t* v2; int32_t* shift; uint32_t* stored1; uint32_t* stored2;
+};
+hipError_t launch_cliptail_junction(const TailJunctionArgs& A, hipStream_t stream);
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);

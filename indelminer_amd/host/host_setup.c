@@ -352,7 +352,7 @@ static int evidence_table_log2(const driver* d)
 }
 
 #define GPU2(drv, call) do { if ((call) != IM_OK) fatalf("%s: %s", #call, im_last_error((drv)->gpu)); } while (0)
-#define EVIDENCE_ON (SPAN_ON || PAIR_ON || CLIP_ON || PAIRLINK_ON)     /* -V needs -C */
+#define EVIDENCE_ON (SPAN_ON || PAIR_ON || CLIP_ON || PAIRLINK_ON || MATELINK_ON)     /* -V needs -C */
 
 /* Once per run, on either path, when the reference is on the device and the insert lengths are known: what the evidence options
  * keep on the device.  Genome-wide arrays and tables keyed by contig: nothing is reset between contigs. */
@@ -373,6 +373,8 @@ static void evidence_enable(driver* d)
     if (CLIPTAIL_ON) GPU2(d, im_cliptail_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, evidence_table_log2(d)));
     /* -M: and the table of pair links, -V's rule with one sixteenth of its slots (LINK_EV_SLOTS_SHIFT says what that assumes) */
     if (PAIRLINK_ON) GPU2(d, im_pairlink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
+    /* -T: and the table of mate links, of the same size on the same assumption, which nobody has measured here either */
+    if (MATELINK_ON) GPU2(d, im_matelink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
 }
 
 /* a chunk of records on the device, as they are in the file: each option's record rule is its scatter kernel's, on either path */
@@ -383,6 +385,7 @@ static void evidence_scatter(driver* d, const im_dev_records* recs, void* stream
     if (CLIP_ON) GPU2(d, im_dev_clip_scatter(d->gpu, recs, stream));            /* -C: one more, only then; these arrays need no scan */
     if (CLIPTAIL_ON) GPU2(d, im_dev_cliptail_scatter(d->gpu, recs, stream));    /* -V: and one behind it, only then */
     if (PAIRLINK_ON) GPU2(d, im_dev_pairlink_scatter(d->gpu, recs, stream));    /* -M: and one behind that, only then */
+    if (MATELINK_ON) GPU2(d, im_dev_matelink_scatter(d->gpu, recs, stream));    /* -T: and one behind that, only then */
 }
 
 /* The chunks of both paths: the pipelined walk's ring has up to PIPE_NCHUNK of them per walker (host_pipeline.c), the record-at-a-time
@@ -740,6 +743,169 @@ static void inv_contig(driver* d, int32_t tid, FILE* f)
         fprintf(f, "\n");
     }
     free(pe); free(P.pos); free(P.cnt); free(P.side);
+}
+
+/* -T: the FILE's ##ALT, ##INFO and description lines; the rule with its constants, as ##inversion= has it */
+static void bnd_describe(FILE* f)
+{
+    fprintf(f, "##ALT=<ID=BND,Description=\"Breakend: reads clipped at POS continue on contig CHR2 at POS2\">\n");
+    fprintf(f, "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n");
+    fprintf(f, "##INFO=<ID=CHR2,Number=1,Type=String,Description=\"The contig of the second pile of clipped reads\">\n");
+    fprintf(f, "##INFO=<ID=POS2,Number=1,Type=Integer,Description=\"The second pile of clipped reads (POS: the first, on the contig that comes first in the reference)\">\n");
+    fprintf(f, "##INFO=<ID=CT,Number=1,Type=String,Description=\"Junction: 3 for a pile of reads that stop aligning with a clip, 5 for a pile of reads that start aligning with one; POS, then POS2\">\n");
+    fprintf(f, "##INFO=<ID=HOMLEN,Number=1,Type=Integer,Description=\"Bases by which the clipped reads continue behind the other breakpoint (micro-homology the aligner extended into, both piles together)\">\n");
+    fprintf(f, "##INFO=<ID=CR,Number=2,Type=Integer,Description=\"Clipped reads at POS, clipped reads at POS2\">\n");
+    fprintf(f, "##INFO=<ID=CN,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases were kept, either pile\">\n");
+    fprintf(f, "##INFO=<ID=CV,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases are the other contig's at the other pile\">\n");
+    fprintf(f, "##INFO=<ID=PE,Number=2,Type=Integer,Description=\"Read pairs that led from POS to POS2, read pairs that led from POS2 to POS: one read near the pile, its mate within two neighbouring cells of %d bases of the other contig; 0 where that pile's pairs point elsewhere or nowhere\">\n", BND_EV_CELL_BASES);
+    fprintf(f, "##interContig=\"a record per pair of positions POS and POS2 on two contigs at each of which at least %d reads of mapping quality >= -q stop aligning (3) "
+               "or start aligning (5) with a soft clip of at least %d bases, more than at any of the %d positions in front and no fewer than at any of the %d behind, "
+               "when at least %d read pairs lead from one to the other and for one shift s in 0 .. %d at least %d of the reads at POS and at least %d of the reads at "
+               "POS2 continue with the other contig at the other position, forwards from its base + s when that pile is of 5 reads and backwards from its base - 1 - s "
+               "when it is of 3 reads, complemented when both piles are of one kind, in up to 32 clipped bases per read with at most 1 difference in 16 (HOMLEN: the s "
+               "with the most such reads, the smallest among equals; CV: those reads); read pairs: paired, both reads mapped, neither secondary, supplementary, "
+               "duplicate nor failing quality control, the mate on another contig, the read of mapping quality >= -q and on the strand of its pile (forward at 3, "
+               "reverse at 5), starting within %d bases from the pile towards where its reads lie and %d the other way; the mates of one strand vote for the contig and "
+               "the two neighbouring cells of %d bases most of them start in (at most %d cells: a pile whose mates scatter further has no partner), and the piles "
+               "of that contig within %d and %d bases of those mates are tried; no genotype; the two junctions of a reciprocal translocation are two records; the "
+               "mate's mapping quality is unknown; the file has no records once the clip-tail or the mate-link table has overflowed (stderr says so); POS 0 and "
+               "POS2 0 are skipped\"\n",
+            DUP_EV_MIN_READS, CLIP_EV_MIN_CLIP, DUP_EV_REACH, DUP_EV_REACH, BND_EV_MIN_LINKS, CLIPTAIL_MAX_SHIFT, BND_EV_MIN_VERIFIED, BND_EV_MIN_VERIFIED,
+            LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT, BND_EV_CELL_BASES, IM_MATELINK_CELLS, LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT);
+}
+
+/* the peaks of one clip array of one contig, ascending */
+typedef struct bnd_peaks { int32_t n; int32_t* pos; uint32_t* cnt; int32_t* mtid; uint32_t* np; int32_t* lo; int32_t* hi; } bnd_peaks;
+/* a junction: end 1 is the lower (tid, position); n1, n2: the pairs that led to it from either end */
+typedef struct bnd_junction { int32_t tid1, p1, tid2, p2; uint8_t s1, s2; uint32_t c1, c2, n1, n2; } bnd_junction;
+
+static int bnd_cmp(const void* a, const void* b)
+{
+    const bnd_junction* x = a; const bnd_junction* y = b;
+    if (x->tid1 != y->tid1) return x->tid1 < y->tid1 ? -1 : 1;
+    if (x->p1 != y->p1) return x->p1 < y->p1 ? -1 : 1;
+    if (x->tid2 != y->tid2) return x->tid2 < y->tid2 ? -1 : 1;
+    if (x->p2 != y->p2) return x->p2 < y->p2 ? -1 : 1;
+    if (x->s1 != y->s1) return x->s1 < y->s1 ? -1 : 1;
+    if (x->s2 != y->s2) return x->s2 < y->s2 ? -1 : 1;
+    return 0;
+}
+
+/* -T: every contig's peaks, their partner queries, the candidates those name, the junction verify, FILE.  Once per run, on either
+ * path, when every scatter has completed: the clip arrays are genome-wide and the tables are keyed by contig.  The lists are small
+ * and stay on the host; every device call is under g_query_mu. */
+static void bnd_search(driver* d)
+{
+    FILE* f = fopen(g_bnd_file, "w");
+    if (!f) fatalf("cannot write %s", g_bnd_file);
+    fprintf(f, "##fileformat=VCFv4.1\n");
+    bnd_describe(f);
+    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
+    gpu_wait(d);
+    uint64_t stored = 0, dropped_tail = 0, dropped_mate = 0;
+    pthread_mutex_lock(&g_query_mu);
+    if (im_cliptail_stats(d->gpu, &stored, &dropped_tail) != IM_OK) fatalf("im_cliptail_stats: %s", im_last_error(d->gpu));
+    if (im_matelink_stats(d->gpu, &stored, &dropped_mate) != IM_OK) fatalf("im_matelink_stats: %s", im_last_error(d->gpu));
+    pthread_mutex_unlock(&g_query_mu);
+    const int32_t nt = d->hdr->n_targets;
+    if (dropped_tail == 0 && dropped_mate == 0 && nt > 1) {
+        /* 1, 2: the peaks of both arrays, and per peak the partner of its reads' mates on either strand (m = 0, then m = 1) */
+        bnd_peaks* P = xcalloc(2 * (size_t)nt, sizeof(bnd_peaks));
+        for (int32_t tid = 0; tid < nt; tid++) {
+            for (int side = 0; side < 2; side++) {
+                bnd_peaks* p = &P[2 * tid + side];
+                int32_t cap = 4096, found = 0;
+                pthread_mutex_lock(&g_query_mu);
+                for (;; cap = found) {
+                    p->pos = xrealloc(p->pos, sizeof(int32_t) * (size_t)cap); p->cnt = xrealloc(p->cnt, sizeof(uint32_t) * (size_t)cap);
+                    if (im_clip_peaks_tid(d->gpu, tid, side, DUP_EV_MIN_READS, DUP_EV_REACH, cap, p->pos, p->cnt, &found) != IM_OK)
+                        fatalf("im_clip_peaks_tid: %s", im_last_error(d->gpu));
+                    if (found <= cap) break;
+                }
+                p->n = found > 0 ? found : 0;
+                if (p->n > 0) {
+                    const size_t n = (size_t)p->n;
+                    uint8_t* kind = xmalloc(2 * n); int32_t* win = xmalloc(sizeof(int32_t) * 4 * n); uint32_t* nl = xmalloc(sizeof(uint32_t) * 2 * n);
+                    p->mtid = xmalloc(sizeof(int32_t) * 2 * n); p->np = xmalloc(sizeof(uint32_t) * 2 * n);
+                    p->lo = xmalloc(sizeof(int32_t) * 2 * n); p->hi = xmalloc(sizeof(int32_t) * 2 * n);
+                    for (size_t k = 0; k < 2 * n; k++) {
+                        const int64_t at = p->pos[k % n];
+                        const int m = k >= n;
+                        kind[k] = (uint8_t)(side | m << 1);
+                        win[k] = link_clamp(at - (side ? CLIPTAIL_MAX_SHIFT : LINK_EV_WINDOW));
+                        win[2 * n + k] = link_clamp(at + (side ? LINK_EV_WINDOW : CLIPTAIL_MAX_SHIFT));
+                    }
+                    if (im_matelink_partner(d->gpu, tid, (int32_t)(2 * n), kind, win, win + 2 * n, nl, p->mtid, p->np, p->lo, p->hi) != IM_OK)
+                        fatalf("im_matelink_partner: %s", im_last_error(d->gpu));
+                    free(kind); free(win); free(nl);
+                }
+                pthread_mutex_unlock(&g_query_mu);
+            }
+        }
+        /* 3: the candidates -- the peaks of array side2 = m on the partner contig inside the window around its mates; each junction once,
+         * with the pairs that led to it from either end */
+        bnd_junction* J = NULL; size_t nj = 0, capj = 0;
+        for (int32_t tid = 0; tid < nt; tid++) {
+            for (int side = 0; side < 2; side++) {
+                const bnd_peaks* p = &P[2 * tid + side];
+                for (int32_t k = 0; k < 2 * p->n; k++) {
+                    const int m = k >= p->n;
+                    const int32_t at = k % p->n, mt = p->mtid[k];
+                    if (mt < 0 || mt >= nt || p->np[k] < BND_EV_MIN_LINKS) continue;
+                    const bnd_peaks* o = &P[2 * mt + m];
+                    const int64_t w0 = (int64_t)p->lo[k] - (m ? LINK_EV_WINDOW : CLIPTAIL_MAX_SHIFT), w1 = (int64_t)p->hi[k] + (m ? CLIPTAIL_MAX_SHIFT : LINK_EV_WINDOW);
+                    for (int32_t j = 0; j < o->n; j++) {
+                        if (o->pos[j] < w0 || o->pos[j] > w1) continue;
+                        bnd_junction x;
+                        const int first = tid < mt;         /* mt != tid: a mate link names another contig */
+                        x.tid1 = first ? tid : mt; x.p1 = first ? p->pos[at] : o->pos[j]; x.s1 = (uint8_t)(first ? side : m); x.c1 = first ? p->cnt[at] : o->cnt[j];
+                        x.tid2 = first ? mt : tid; x.p2 = first ? o->pos[j] : p->pos[at]; x.s2 = (uint8_t)(first ? m : side); x.c2 = first ? o->cnt[j] : p->cnt[at];
+                        x.n1 = first ? p->np[k] : 0; x.n2 = first ? 0 : p->np[k];
+                        size_t e = 0;
+                        while (e < nj && bnd_cmp(&J[e], &x) != 0) e++;
+                        if (e < nj) { J[e].n1 += x.n1; J[e].n2 += x.n2; continue; }     /* found from the other end: one query per end leads here */
+                        if (nj == capj) { capj = capj ? 2 * capj : 64; J = xrealloc(J, sizeof(bnd_junction) * capj); }
+                        J[nj++] = x;
+                    }
+                }
+            }
+        }
+        /* 4 .. 6: verify, keep, sort, print */
+        if (nj > 0) {
+            qsort(J, nj, sizeof(bnd_junction), bnd_cmp);
+            int32_t* q = xmalloc(sizeof(int32_t) * 5 * nj); uint8_t* qs = xmalloc(2 * nj); uint32_t* a = xmalloc(sizeof(uint32_t) * 4 * nj);
+            for (size_t k = 0; k < nj; k++) {
+                q[k] = J[k].tid1; q[nj + k] = J[k].p1; q[2 * nj + k] = J[k].tid2; q[3 * nj + k] = J[k].p2; qs[k] = J[k].s1; qs[nj + k] = J[k].s2;
+            }
+            pthread_mutex_lock(&g_query_mu);
+            const int rc = im_cliptail_junction(d->gpu, (int32_t)nj, q, q + nj, qs, q + 2 * nj, q + 3 * nj, qs + nj, CLIPTAIL_MAX_SHIFT, a, a + nj, q + 4 * nj,
+                                                a + 2 * nj, a + 3 * nj);
+            pthread_mutex_unlock(&g_query_mu);
+            if (rc != IM_OK) fatalf("im_cliptail_junction: %s", im_last_error(d->gpu));
+            static const char* const ct[2][2] = {{"3to3", "3to5"}, {"5to3", "5to5"}};
+            for (size_t k = 0; k < nj; k++) {
+                const bnd_junction* x = &J[k];
+                const uint32_t v1 = a[k], v2 = a[nj + k];
+                if (v1 == CLIPTAIL_NONE || v1 < BND_EV_MIN_VERIFIED || v2 < BND_EV_MIN_VERIFIED) continue;
+                if (x->p1 == 0 || x->p2 == 0) continue;    /* nothing in front to anchor on */
+                const char* c1 = d->hdr->target_name[x->tid1]; const char* c2 = d->hdr->target_name[x->tid2];
+                const int ref = toupper((unsigned char)d->sequences[x->tid1][x->p1 - 1]);
+                fprintf(f, "%s\t%d\t.\t%c\t", c1, x->p1, ref);
+                if (!x->s1 && x->s2) fprintf(f, "%c[%s:%d[", ref, c2, x->p2);
+                else if (x->s1 && !x->s2) fprintf(f, "]%s:%d]%c", c2, x->p2, ref);
+                else if (!x->s1) fprintf(f, "%c]%s:%d]", ref, c2, x->p2);
+                else fprintf(f, "[%s:%d[%c", c2, x->p2, ref);
+                fprintf(f, "\t.\t.\tSVTYPE=BND;CHR2=%s;POS2=%d;CT=%s;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u;PE=%u,%u\n", c2, x->p2, ct[x->s1][x->s2], q[4 * nj + k],
+                        x->c1, x->c2, a[2 * nj + k], a[3 * nj + k], v1, v2, x->n1, x->n2);
+            }
+            free(q); free(qs); free(a);
+        }
+        free(J);
+        for (int32_t k = 0; k < 2 * nt; k++) { free(P[k].pos); free(P[k].cnt); free(P[k].mtid); free(P[k].np); free(P[k].lo); free(P[k].hi); }
+        free(P);
+    }
+    if (fclose(f) != 0) fatalf("cannot write %s", g_bnd_file);
+    phase_time("inter-contig breakpoint evidence (device)");
 }
 
 static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_reader* r)

@@ -227,6 +227,31 @@ extern int im_pairlink_stats(im_ctx*, uint64_t*, uint64_t*) __attribute__((weak)
                                     * (a chimeric or mis-oriented pair against a clipped read), which nobody has measured on real data */
 #define PAIRLINK_NONE 0xFFFFFFFFu  /* what the device answers after its table has overflowed */
 enum { LINK_EVERTED = 0, LINK_FORWARD = 1, LINK_REVERSE = 2 };
+/* -T FILE, with -G -C -V: breakpoints between TWO contigs, the one event the files above cannot show -- a peak of either clip array
+ * whose neighbouring reads have at least BND_EV_MIN_LINKS mates within two neighbouring cells of another contig (the device's keyed
+ * table of mate links and its partner query), paired with the peaks of that contig where those mates point, kept when at least
+ * BND_EV_MIN_VERIFIED clipped reads of either pile continue in the other contig (the device's junction verify, over the clip-tail
+ * table).  A small VCF of its own in breakend notation, written to FILE once, behind -N's.  stdout, stderr and the other FILEs stay
+ * as they are.  It needs none of -U, -N and -M.  Not an option of the reference; referenced weakly. */
+static const char* g_bnd_file = NULL;
+extern int im_matelink_enable(im_ctx*, int32_t, int32_t) __attribute__((weak));
+extern int im_dev_matelink_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
+extern int im_matelink_add(im_ctx*, int32_t, int32_t, const int32_t*, const int32_t*, const int32_t*, const uint8_t*) __attribute__((weak));
+extern int im_matelink_partner(im_ctx*, int32_t, int32_t, const uint8_t*, const int32_t*, const int32_t*, uint32_t*, int32_t*, uint32_t*, int32_t*, int32_t*) __attribute__((weak));
+extern int im_matelink_reset(im_ctx*, void*) __attribute__((weak));
+extern int im_matelink_stats(im_ctx*, uint64_t*, uint64_t*) __attribute__((weak));
+extern int im_cliptail_junction(im_ctx*, int32_t, const int32_t*, const int32_t*, const uint8_t*, const int32_t*, const int32_t*, const uint8_t*, int32_t,
+                                uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*) __attribute__((weak));
+extern int im_clip_peaks_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t*, uint32_t*, int32_t*) __attribute__((weak));
+#define MATELINK_ON (g_bnd_file != NULL)           /* the walk also keeps the mate links */
+#define MATELINK_API_PRESENT (im_matelink_enable && im_dev_matelink_scatter && im_matelink_add && im_matelink_partner && im_matelink_reset && \
+                              im_matelink_stats && im_cliptail_junction && im_clip_peaks_tid)
+#define BND_EV_MIN_LINKS 2         /* mates of a pile's reads inside the winning pair of cells: a junction fewer pairs span is not searched for */
+#define BND_EV_MIN_VERIFIED 2      /* clipped reads of either pile that continue in the other contig */
+#define BND_EV_CELL_BASES 1024     /* a cell of the partner query (the header's mpos >> 10): two neighbours hold a junction's bundle */
+/* the peaks are -U's (DUP_EV_MIN_READS, DUP_EV_REACH), the windows -M's (LINK_EV_WINDOW towards where the pairs lie, CLIPTAIL_MAX_SHIFT
+ * the other way), and the table has the pair-link table's size: LINK_EV_SLOTS_SHIFT says what that ASSUMES, and nobody has measured
+ * the rate of inter-contig pairs against clipped reads on real data either */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that
