@@ -445,7 +445,10 @@ size_t im_dev_flushgroup_scratch_bytes(int32_t n_slots_cap, int32_t n_flushes_ca
 int im_dev_flushgroup_scratch_init(im_ctx* ctx, int32_t n_slots_cap, int32_t n_flushes_cap, void* scratch, size_t scratch_bytes, void* stream);
 int im_dev_flush_groupby(im_ctx* ctx, const im_flush_desc* desc_dev, int32_t n_flushes,
                          const int32_t* cls, const int32_t* b1, const int32_t* b2, int32_t* consumed,
-                         const int32_t* cand_rec, const int32_t* n_cand_dev, int32_t cand_cap /* also the launch bound */,
+                         const int32_t* cand_rec, const int32_t* n_cand_dev,
+                         int32_t cand_cap /* also the launch bound.  cand_rec, cls, b1 and b2 must be READABLE up to cand_cap candidates
+                                             (IM_MAX_EV slots each), whatever *n_cand_dev says: the kernels load a candidate beside the
+                                             count and drop it when it lies behind it.  What stands there does not matter. */,
                          int32_t pe_base, int32_t pe_count, int32_t tie_desc,
                          int32_t* order, int32_t* cl_key, int32_t* cl_first, int32_t* cl_count, int32_t* counts,
                          void* scratch, size_t scratch_bytes, void* stream);

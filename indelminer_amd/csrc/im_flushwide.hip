@@ -21,21 +21,25 @@
 //                                  consumed split-read slot enters the cluster table keyed (flush, class, b1, b2): a 64-bit
 //                                  CAS of (flush id | representative slot), a count and the smallest member slot per entry
 //   launch 3  flushw_emit_kernel   the smallest member of each cluster takes the cluster's record and its run of order[] (one
-//                                  64-bit atomicAdd per WAVE for all its clusters) and the wave collects the members in slot
+//                                  64-bit atomicAdd per WORKGROUP for all its clusters) and the wave collects the members in slot
 //                                  order = arrival order: members of a cluster arrive within a few hundred slots
 //                                  of each other, so that is a handful of coalesced 64-slot sweeps -- no placement pass, no
 //                                  ordering pass, no offsets scan.  The table and the tree leave clean for the next call.
 //
-// HBM streaming: 16 B per candidate and array read twice, 32 B written, 4 B per slot read once more; the table is touched by
-// consumed slots only.
+// HBM streaming: 16 B per candidate and array read twice, 32 B written, 4 B per slot read once more (five times from L2: a wave
+// of launch 3 fetches the 256 slots behind its own with them); the table is touched by consumed slots only.
 
 #include "im_device.hpp"
 
 namespace im {
 namespace {
 
-constexpr int kWin = 64;                 // flush descriptors a workgroup keeps in LDS (a workgroup's candidates span 1-2 flushes)
+constexpr int kWin = 64;                 // flush descriptors a workgroup keeps in LDS: the whole list up to here, a window of a longer one
 constexpr int kWideBlock = 256;
+constexpr int kEmitBlock = 256;           // launch 3: its waves share one atomic on the output counters.  512 and 1024 lanes are faster
+                                         // alone and slower in the overlapped step: a large workgroup waits for a whole CU's room
+static_assert(kEmitBlock % 64 == 0 && kEmitBlock / 64 <= 16, "sum16 adds up the totals of at most sixteen waves");
+constexpr int kAhead = 4;                // 64-slot stretches behind its own that a wave of launch 3 fetches with them
 
 __device__ __forceinline__ uint64_t cut_key(int32_t b1, int32_t b2) { return ((uint64_t)(uint32_t)b1 << 32) | (uint32_t)b2; }
 
@@ -56,11 +60,12 @@ struct WideArgs {
     WideScratch s;
 };
 
-// the flush list through a workgroup's LDS window
-struct FlushView {
+// the flush list through a workgroup's LDS window; kWhole: the window is the list (n_fl <= kWin), every read is an LDS read
+template <bool kWhole>
+struct FlushViewT {
     const im_flush_desc* g; int32_t n_fl;
     const im_flush_desc* w; int32_t lo, n;
-    __device__ __forceinline__ bool in(int32_t f) const { return (uint32_t)(f - lo) < (uint32_t)n; }
+    __device__ __forceinline__ bool in(int32_t f) const { return kWhole || (uint32_t)(f - lo) < (uint32_t)n; }
     __device__ __forceinline__ int32_t rec1(int32_t f) const { return in(f) ? w[f - lo].rec1 : g[f].rec1; }
     __device__ __forceinline__ int32_t marker(int32_t f) const { return in(f) ? w[f - lo].marker : g[f].marker; }
     __device__ __forceinline__ int32_t id(int32_t f) const { return in(f) ? w[f - lo].id : g[f].id; }
@@ -70,6 +75,8 @@ struct FlushView {
         return l < f ? f : (l >= n_fl ? n_fl - 1 : l);
     }
 };
+using FlushView = FlushViewT<false>;
+using FlushList = FlushViewT<true>;
 
 __device__ __forceinline__ int32_t first_flush_rec(const im_flush_desc* d, int32_t n, int32_t rec)     // first f with rec1 > rec
 {
@@ -86,7 +93,8 @@ __device__ __forceinline__ int32_t first_flush_pe(const im_flush_desc* d, int32_
 
 // the flushes entry (arrival fa, b2) is a cutting candidate of: [fa, fh); fh = the first flush of the contig whose marker
 // exceeds b2 (monotone markers: a binary search), fa itself when it is a candidate of none
-__device__ __forceinline__ int32_t run_end(const FlushView& V, int32_t fa, int32_t last, int32_t vb2)
+template <class View>
+__device__ __forceinline__ int32_t run_end(const View& V, int32_t fa, int32_t last, int32_t vb2)
 {
     if (V.marker(fa) > vb2) return fa;
     int32_t lo = fa + 1, hi = last + 1;
@@ -119,6 +127,18 @@ __device__ __forceinline__ uint64_t wave_min64(uint64_t v)
         if (ov < v) v = ov;
     }
     return v;
+}
+
+// the sum over lanes 0..15 (clusters in the low word, nodes in the high word: neither sum reaches 2^32), in every lane
+__device__ __forceinline__ unsigned long long sum16(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, 0), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), 0);
+    return ((unsigned long long)hi << 32) | lo;
 }
 
 // one wave-wide step of launch 1: lanes with `live` give key to the cuts of [fa, fh).  A wave whose live lanes share the run
@@ -155,57 +175,109 @@ __device__ __forceinline__ int32_t stage_window(const WideArgs& A, im_flush_desc
     return flo;
 }
 
+// A list of at most kWin flushes (every list but a long contig's READCHUNK list) is in every workgroup's LDS whole, and
+// then nothing a lane loads first has an address that waits for another load: the list, the candidate count, the lane's
+// candidate (block-strided over cand_cap, dropped when it lies behind the count) and its paired-read entry go out together
+// at kernel entry, one round trip instead of count -> record -> search -> window -> candidate.
+struct CandLoad { int32_t rec; int4 vc, v1, v2; };
+struct PeLoad { int32_t cls, b1, b2; };
+
+__device__ __forceinline__ CandLoad load_cand(const WideArgs& A, int32_t c, bool in)
+{
+    CandLoad L = { 0, make_int4(-1, -1, -1, -1), make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0) };
+    if (in) {
+        L.rec = A.cand_rec[c];
+        L.vc = reinterpret_cast<const int4*>(A.cls)[c]; L.v1 = reinterpret_cast<const int4*>(A.b1)[c]; L.v2 = reinterpret_cast<const int4*>(A.b2)[c];
+    }
+    return L;
+}
+__device__ __forceinline__ PeLoad load_pe(const WideArgs& A, int32_t i)
+{
+    PeLoad P = { -1, 0, 0 };
+    if (i < A.pe_count) { const int32_t sl = A.pe_base + i; P.cls = A.cls[sl]; P.b1 = A.b1[sl]; P.b2 = A.b2[sl]; }
+    return P;
+}
+__device__ __forceinline__ int4 list_fetch(const WideArgs& A, int t)
+{
+    return t < 2 * A.n_fl ? reinterpret_cast<const int4*>(A.desc)[t] : make_int4(0, 0, 0, 0);
+}
+__device__ __forceinline__ void list_store(const WideArgs& A, im_flush_desc* s_desc, int t, int4 v)
+{
+    if (t < 2 * A.n_fl) reinterpret_cast<int4*>(s_desc)[t] = v;
+}
+
+// launch 1 for one candidate per lane.  kWhole: the whole list is the window, the arrival flush by a search in LDS
+template <bool kWhole>
+__device__ __forceinline__ void cut_cand(const WideArgs& A, const FlushViewT<kWhole>& V, bool have, const CandLoad& L, int lane)
+{
+    int32_t fa = A.n_fl, last = 0;
+    if (have) {
+        if (kWhole) fa = first_flush_rec(V.w, V.n, L.rec);
+        else { fa = V.lo; while (fa < A.n_fl && V.rec1(fa) <= L.rec) fa++; }
+        if (fa < A.n_fl) last = V.last(fa);
+    }
+    const bool ok = have && fa < A.n_fl;
+    const int32_t sc[4] = { L.vc.x, L.vc.y, L.vc.z, L.vc.w }, s1[4] = { L.v1.x, L.v1.y, L.v1.z, L.v1.w }, s2[4] = { L.v2.x, L.v2.y, L.v2.z, L.v2.w };
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        bool live = ok && sc[j] >= 0;
+        int32_t fh = fa;
+        if (live) { fh = run_end(V, fa, last, s2[j]); live = fh > fa; }
+        give_keys(A, live, fa, fh, cut_key(s1[j], s2[j]), lane);
+    }
+}
+
+// the paired-read entries (a few per thousand reads): the same, each through its own look-up.  G: the list as the lane reads it
+// (the LDS copy when it is whole, global memory otherwise)
+template <bool kWhole>
+__device__ __forceinline__ void cut_pe(const WideArgs& A, const FlushViewT<kWhole>& G, int32_t i, const PeLoad& P, int lane)
+{
+    bool live = false;
+    int32_t fa = 0, fh = 0; uint64_t key = ~0ull;
+    if (i < A.pe_count) {
+        fa = first_flush_pe(kWhole ? G.w : A.desc, A.n_fl, i);
+        if (fa < A.n_fl && P.cls >= 0) {
+            fh = run_end(G, fa, G.last(fa), P.b2);
+            live = fh > fa; key = cut_key(P.b1, P.b2);
+        }
+    }
+    give_keys(A, live, fa, fh, key, lane);
+}
+
 __global__ __launch_bounds__(kWideBlock) void flushw_cut_kernel(WideArgs A, int32_t* __restrict__ counts)
 {
     __shared__ __attribute__((aligned(16))) im_flush_desc s_desc[kWin];
     __shared__ int32_t s_flo;
     const int t = threadIdx.x, lane = t & 63;
     if (blockIdx.x == 0 && t == 0) { counts[0] = 0; counts[1] = 0; }       // launch 3 counts clusters and nodes up from here
+    const int32_t stride = gridDim.x * kWideBlock, npe_round = (A.pe_count + 63) & ~63;
+    if (A.n_fl <= kWin) {
+        const int4 dv = list_fetch(A, t);
+        int32_t base = blockIdx.x * kWideBlock, i = base + t;
+        CandLoad L = load_cand(A, base + t, base + t < A.cand_cap);
+        PeLoad P = load_pe(A, i);
+        const int32_t ncand = min(*A.n_cand, A.cand_cap);
+        list_store(A, s_desc, t, dv);
+        __syncthreads();
+        const FlushList V = { A.desc, A.n_fl, s_desc, 0, A.n_fl };
+        for (;;) {                                                            // wave-uniform: give_keys is a wave's step
+            cut_cand<true>(A, V, base + t < ncand, L, lane);
+            base += stride;
+            if (base >= ncand) break;
+            L = load_cand(A, base + t, base + t < A.cand_cap);
+        }
+        for (; i < npe_round; i += stride, P = load_pe(A, i)) cut_pe<true>(A, V, i, P, lane);
+        return;
+    }
     int32_t c0, c1, nst;
     const int32_t flo = stage_window(A, s_desc, &s_flo, c0, c1, nst);
     const FlushView V = { A.desc, A.n_fl, s_desc, flo, nst };
-    const int4* cls4 = reinterpret_cast<const int4*>(A.cls);
-    const int4* b14 = reinterpret_cast<const int4*>(A.b1);
-    const int4* b24 = reinterpret_cast<const int4*>(A.b2);
     for (int32_t base = c0; base < c1; base += kWideBlock) {
-        const int32_t c = base + t;
-        const bool have = c < c1;
-        int32_t fa = A.n_fl, last = 0;
-        int4 vc = make_int4(-1, -1, -1, -1), v1 = make_int4(0, 0, 0, 0), v2 = v1;
-        if (have) {
-            const int32_t rec = A.cand_rec[c];
-            vc = cls4[c]; v1 = b14[c]; v2 = b24[c];
-            fa = flo;
-            while (fa < A.n_fl && V.rec1(fa) <= rec) fa++;
-            if (fa < A.n_fl) last = V.last(fa);
-        }
-        const bool ok = have && fa < A.n_fl;
-        const int32_t sc[4] = { vc.x, vc.y, vc.z, vc.w }, s1[4] = { v1.x, v1.y, v1.z, v1.w }, s2[4] = { v2.x, v2.y, v2.z, v2.w };
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            bool live = ok && sc[j] >= 0;
-            int32_t fh = fa;
-            if (live) { fh = run_end(V, fa, last, s2[j]); live = fh > fa; }
-            give_keys(A, live, fa, fh, cut_key(s1[j], s2[j]), lane);
-        }
+        const bool have = base + t < c1;
+        cut_cand<false>(A, V, have, load_cand(A, base + t, have), lane);
     }
-    // the paired-read entries (a few per thousand reads): the same, each through its own look-up
-    const int32_t npe_round = (A.pe_count + 63) & ~63;
-    for (int32_t i = blockIdx.x * kWideBlock + t; i < npe_round; i += gridDim.x * kWideBlock) {
-        bool live = false;
-        int32_t fa = 0, fh = 0; uint64_t key = ~0ull;
-        if (i < A.pe_count) {
-            const int32_t sl = A.pe_base + i;
-            fa = first_flush_pe(A.desc, A.n_fl, i);
-            if (fa < A.n_fl && A.cls[sl] >= 0) {
-                const int32_t vb1 = A.b1[sl], vb2 = A.b2[sl];
-                const FlushView G = { A.desc, A.n_fl, s_desc, 0, 0 };
-                fh = run_end(G, fa, G.last(fa), vb2);
-                live = fh > fa; key = cut_key(vb1, vb2);
-            }
-        }
-        give_keys(A, live, fa, fh, key, lane);
-    }
+    const FlushView G = { A.desc, A.n_fl, s_desc, 0, 0 };
+    for (int32_t i = blockIdx.x * kWideBlock + t; i < npe_round; i += stride) cut_pe<false>(A, G, i, load_pe(A, i), lane);
 }
 
 __device__ __forceinline__ uint32_t mix32(uint32_t f, uint32_t c, uint32_t x1, uint32_t x2)
@@ -217,11 +289,79 @@ __device__ __forceinline__ uint32_t mix32(uint32_t f, uint32_t c, uint32_t x1, u
 }
 
 // the flush that consumes an entry: the first f of [fh, last] with key < cut(f); 0 when none does
-template <class CutOf>
-__device__ __forceinline__ int32_t consuming_flush(const FlushView& V, int32_t fh, int32_t last, uint64_t key, CutOf cut_of)
+template <class View, class CutOf>
+__device__ __forceinline__ int32_t consuming_flush(const View& V, int32_t fh, int32_t last, uint64_t key, CutOf cut_of)
 {
     for (int32_t f = fh; f <= last; f++) if (key < cut_of(f)) return V.id(f);
     return 0;
+}
+
+// the cut of flush f of a list of at most kWin flushes (at most 7 levels): every level's load goes out at once -- the loop of
+// tree_get waits for each node before it asks for its parent.  Levels above the root read the root again.
+__device__ __forceinline__ uint64_t tree_get_short(const unsigned long long* T, uint32_t F2, int32_t f)
+{
+    const uint32_t i = (uint32_t)f + F2;
+    uint64_t v[7];
+#pragma unroll
+    for (int k = 0; k < 7; k++) { const uint32_t ik = i >> k; v[k] = T[ik ? ik : 1u]; }
+    uint64_t m = v[0];
+#pragma unroll
+    for (int k = 1; k < 7; k++) if (v[k] < m) m = v[k];
+    return m;
+}
+
+// launch 2 for candidate c
+template <bool kWhole, class CutOf>
+__device__ __forceinline__ void mark_cand(const WideArgs& A, const FlushViewT<kWhole>& V, CutOf cut_of, int32_t c, const CandLoad& L)
+{
+    int32_t fa;
+    if (kWhole) fa = first_flush_rec(V.w, V.n, L.rec);
+    else { fa = V.lo; while (fa < A.n_fl && V.rec1(fa) <= L.rec) fa++; }
+    const bool ok = fa < A.n_fl;
+    const int32_t last = ok ? V.last(fa) : 0;
+    const int32_t sc[4] = { L.vc.x, L.vc.y, L.vc.z, L.vc.w }, s1[4] = { L.v1.x, L.v1.y, L.v1.z, L.v1.w }, s2[4] = { L.v2.x, L.v2.y, L.v2.z, L.v2.w };
+    int32_t ids[4]; uint32_t hs[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        ids[j] = 0; hs[j] = 0xFFFFFFFFu;
+        if (!ok || sc[j] < 0) continue;
+        const uint64_t key = cut_key(s1[j], s2[j]);
+        const int32_t id = consuming_flush(V, run_end(V, fa, last, s2[j]), last, key, cut_of);
+        ids[j] = id;
+        if (id <= 0 || sc[j] >= 2) continue;
+        // the cluster table: one entry per distinct (flush, class, b1, b2); the entry names a representative slot, whose
+        // class / b1 / b2 are compared through the slot arrays, and carries the flush id itself (consumed[] of another
+        // slot is being written by this very launch)
+        const uint32_t slot = (uint32_t)c * IM_MAX_EV + (uint32_t)j;
+        const unsigned long long mine = ((unsigned long long)(uint32_t)id << 32) | (slot + 1u);
+        uint32_t h = mix32((uint32_t)id, (uint32_t)sc[j], (uint32_t)s1[j], (uint32_t)s2[j]) & (A.s.H - 1u);
+        for (;;) {
+            const unsigned long long old = atomicCAS(&A.s.head[h], 0ull, mine);
+            if (old == 0ull) break;
+            if ((uint32_t)(old >> 32) == (uint32_t)id) {
+                const uint32_t rep = (uint32_t)old - 1u;
+                if (A.cls[rep] == sc[j] && A.b1[rep] == s1[j] && A.b2[rep] == s2[j]) break;
+            }
+            h = (h + 1u) & (A.s.H - 1u);
+        }
+        atomicAdd(&A.s.cnt[h], 1u);
+        atomicMin(&A.s.first_slot[h], slot);
+        hs[j] = h;
+    }
+    reinterpret_cast<int4*>(A.consumed)[c] = make_int4(ids[0], ids[1], ids[2], ids[3]);
+    reinterpret_cast<uint4*>(A.s.slot_h)[c] = make_uint4(hs[0], hs[1], hs[2], hs[3]);
+}
+
+template <bool kWhole, class CutOf>
+__device__ __forceinline__ void mark_pe(const WideArgs& A, const FlushViewT<kWhole>& G, CutOf cut_of, int32_t i, const PeLoad& P)
+{
+    int32_t id = 0;
+    const int32_t fa = first_flush_pe(kWhole ? G.w : A.desc, A.n_fl, i);
+    if (fa < A.n_fl && P.cls >= 0) {
+        const int32_t last = G.last(fa);
+        id = consuming_flush(G, run_end(G, fa, last, P.b2), last, cut_key(P.b1, P.b2), cut_of);
+    }
+    A.consumed[A.pe_base + i] = id;
 }
 
 __global__ __launch_bounds__(kWideBlock) void flushw_mark_kernel(WideArgs A)
@@ -230,122 +370,126 @@ __global__ __launch_bounds__(kWideBlock) void flushw_mark_kernel(WideArgs A)
     __shared__ unsigned long long s_cut[kWin];
     __shared__ int32_t s_flo;
     const int t = threadIdx.x;
+    const int32_t stride = gridDim.x * kWideBlock;
+    if (A.n_fl <= kWin) {
+        // as in launch 1, and the cuts' tree nodes with them: their addresses follow from F2 alone
+        const int4 dv = list_fetch(A, t);
+        const uint64_t cv = t < A.n_fl ? tree_get_short(A.s.tree, A.F2, t) : ~0ull;
+        int32_t c = blockIdx.x * kWideBlock + t, i = c;
+        CandLoad L = load_cand(A, c, c < A.cand_cap);
+        PeLoad P = load_pe(A, i);
+        const int32_t ncand = min(*A.n_cand, A.cand_cap);
+        list_store(A, s_desc, t, dv);
+        if (t < A.n_fl) s_cut[t] = cv;
+        __syncthreads();
+        const FlushList V = { A.desc, A.n_fl, s_desc, 0, A.n_fl };
+        auto cut_of = [&](int32_t f) -> uint64_t { return (uint64_t)s_cut[f]; };
+        while (c < ncand) {
+            mark_cand<true>(A, V, cut_of, c, L);
+            c += stride;
+            if (c < ncand) L = load_cand(A, c, true);
+        }
+        while (i < A.pe_count) {
+            mark_pe<true>(A, V, cut_of, i, P);
+            i += stride;
+            P = load_pe(A, i);
+        }
+        return;
+    }
     int32_t c0, c1, nst;
     const int32_t flo = stage_window(A, s_desc, &s_flo, c0, c1, nst);
     if (t < nst) s_cut[t] = tree_get(A.s.tree, A.F2, flo + t);
     __syncthreads();
     const FlushView V = { A.desc, A.n_fl, s_desc, flo, nst };
-    auto cut_of = [&](int32_t f) -> uint64_t { return V.in(f) ? (uint64_t)s_cut[f - flo] : tree_get(A.s.tree, A.F2, f); };
-    const int4* cls4 = reinterpret_cast<const int4*>(A.cls);
-    const int4* b14 = reinterpret_cast<const int4*>(A.b1);
-    const int4* b24 = reinterpret_cast<const int4*>(A.b2);
-    for (int32_t c = c0 + t; c < c1; c += kWideBlock) {
-        const int32_t rec = A.cand_rec[c];
-        const int4 vc = cls4[c], v1 = b14[c], v2 = b24[c];
-        int32_t fa = flo;
-        while (fa < A.n_fl && V.rec1(fa) <= rec) fa++;
-        const bool ok = fa < A.n_fl;
-        const int32_t last = ok ? V.last(fa) : 0;
-        const int32_t sc[4] = { vc.x, vc.y, vc.z, vc.w }, s1[4] = { v1.x, v1.y, v1.z, v1.w }, s2[4] = { v2.x, v2.y, v2.z, v2.w };
-        int32_t ids[4]; uint32_t hs[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            ids[j] = 0; hs[j] = 0xFFFFFFFFu;
-            if (!ok || sc[j] < 0) continue;
-            const uint64_t key = cut_key(s1[j], s2[j]);
-            const int32_t id = consuming_flush(V, run_end(V, fa, last, s2[j]), last, key, cut_of);
-            ids[j] = id;
-            if (id <= 0 || sc[j] >= 2) continue;
-            // the cluster table: one entry per distinct (flush, class, b1, b2); the entry names a representative slot, whose
-            // class / b1 / b2 are compared through the slot arrays, and carries the flush id itself (consumed[] of another
-            // slot is being written by this very launch)
-            const uint32_t slot = (uint32_t)c * IM_MAX_EV + (uint32_t)j;
-            const unsigned long long mine = ((unsigned long long)(uint32_t)id << 32) | (slot + 1u);
-            uint32_t h = mix32((uint32_t)id, (uint32_t)sc[j], (uint32_t)s1[j], (uint32_t)s2[j]) & (A.s.H - 1u);
-            for (;;) {
-                const unsigned long long old = atomicCAS(&A.s.head[h], 0ull, mine);
-                if (old == 0ull) break;
-                if ((uint32_t)(old >> 32) == (uint32_t)id) {
-                    const uint32_t rep = (uint32_t)old - 1u;
-                    if (A.cls[rep] == sc[j] && A.b1[rep] == s1[j] && A.b2[rep] == s2[j]) break;
-                }
-                h = (h + 1u) & (A.s.H - 1u);
-            }
-            atomicAdd(&A.s.cnt[h], 1u);
-            atomicMin(&A.s.first_slot[h], slot);
-            hs[j] = h;
-        }
-        reinterpret_cast<int4*>(A.consumed)[c] = make_int4(ids[0], ids[1], ids[2], ids[3]);
-        reinterpret_cast<uint4*>(A.s.slot_h)[c] = make_uint4(hs[0], hs[1], hs[2], hs[3]);
-    }
-    for (int32_t i = blockIdx.x * kWideBlock + t; i < A.pe_count; i += gridDim.x * kWideBlock) {
-        const int32_t sl = A.pe_base + i;
-        int32_t id = 0;
-        const int32_t fa = first_flush_pe(A.desc, A.n_fl, i);
-        if (fa < A.n_fl && A.cls[sl] >= 0) {
-            const FlushView G = { A.desc, A.n_fl, s_desc, 0, 0 };
-            const int32_t vb1 = A.b1[sl], vb2 = A.b2[sl], last = G.last(fa);
-            id = consuming_flush(G, run_end(G, fa, last, vb2), last, cut_key(vb1, vb2),
-                                 [&](int32_t f) -> uint64_t { return tree_get(A.s.tree, A.F2, f); });
-        }
-        A.consumed[sl] = id;
-    }
+    for (int32_t c = c0 + t; c < c1; c += kWideBlock)
+        mark_cand<false>(A, V, [&](int32_t f) -> uint64_t { return V.in(f) ? (uint64_t)s_cut[f - flo] : tree_get(A.s.tree, A.F2, f); }, c, load_cand(A, c, true));
+    const FlushView G = { A.desc, A.n_fl, s_desc, 0, 0 };
+    for (int32_t i = blockIdx.x * kWideBlock + t; i < A.pe_count; i += stride)
+        mark_pe<false>(A, G, [&](int32_t f) -> uint64_t { return tree_get(A.s.tree, A.F2, f); }, i, load_pe(A, i));
 }
 
-__global__ __launch_bounds__(kWideBlock) void flushw_emit_kernel(WideArgs A, int32_t tie_desc, int32_t* __restrict__ order, int32_t* __restrict__ cl_key,
+__global__ __launch_bounds__(kEmitBlock) void flushw_emit_kernel(WideArgs A, int32_t tie_desc, int32_t* __restrict__ order, int32_t* __restrict__ cl_key,
                                                                 int32_t* __restrict__ cl_first, int32_t* __restrict__ cl_count,
                                                                 unsigned long long* __restrict__ counts64)
 {
-    const int t = threadIdx.x, lane = t & 63;
-    const int64_t gtid = (int64_t)blockIdx.x * kWideBlock + t, gstride = (int64_t)gridDim.x * kWideBlock;
-    // the cuts are done with: the tree is all ones again for the next call
-    for (int64_t i = gtid; i < 2 * (int64_t)A.F2; i += gstride) A.s.tree[i] = ~0ull;
-    const int64_t nc = min(*A.n_cand, A.cand_cap);
-    const int64_t n_slots = nc * IM_MAX_EV;
+    __shared__ unsigned long long s_wave[kEmitBlock / 64], s_got;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t gtid = (int64_t)blockIdx.x * kEmitBlock + t, gstride = (int64_t)gridDim.x * kEmitBlock;
+    const int64_t cap_slots = (int64_t)A.cand_cap * IM_MAX_EV;
     const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    for (int64_t base = gtid - lane; base < n_slots; base += gstride) {         // wave-uniform
+    for (int64_t wg_base = gtid - t; wg_base < cap_slots; wg_base += gstride) { // workgroup-uniform: the waves meet at two barriers
+        const int64_t base = wg_base + 64 * wave;
+        // the wave's own 64 slots and the kAhead * 64 behind them, where the members of its clusters lie, go out together and
+        // beside the candidate count: slot_h is laid out for cand_cap candidates, what lies behind the count is dropped
         const int64_t i = base + lane;
-        const uint32_t h = i < n_slots ? A.s.slot_h[i] : 0xFFFFFFFFu;
-        const bool isfirst = h != 0xFFFFFFFFu && A.s.first_slot[h] == (uint32_t)i;
+        uint32_t h = i < cap_slots ? A.s.slot_h[i] : 0xFFFFFFFFu;
+        uint32_t ahead[kAhead];
+#pragma unroll
+        for (int k = 0; k < kAhead; k++) { const int64_t j = i + 64 * (k + 1); ahead[k] = j < cap_slots ? A.s.slot_h[j] : 0xFFFFFFFFu; }
+        const int64_t n_slots = (int64_t)min(*A.n_cand, A.cand_cap) * IM_MAX_EV;
+        if (wg_base >= n_slots) break;
+        if (i >= n_slots) h = 0xFFFFFFFFu;
+#pragma unroll
+        for (int k = 0; k < kAhead; k++) if (i + 64 * (k + 1) >= n_slots) ahead[k] = 0xFFFFFFFFu;
+        // everything a table position addresses in one round trip, the slot's own key beside it (only a cluster's first keeps it)
+        uint32_t fs = 0xFFFFFFFFu, cn = 0u; unsigned long long hd = 0ull; int32_t kc = 0, k1 = 0, k2 = 0;
+        if (h != 0xFFFFFFFFu) { fs = A.s.first_slot[h]; cn = A.s.cnt[h]; hd = A.s.head[h]; kc = A.cls[i]; k1 = A.b1[i]; k2 = A.b2[i]; }
+        const bool isfirst = h != 0xFFFFFFFFu && fs == (uint32_t)i;
         const uint64_t mask = __ballot(isfirst);
-        if (mask == 0ull) continue;
-        const uint32_t cnt = isfirst ? A.s.cnt[h] : 0u;
+        const uint32_t cnt = isfirst ? cn : 0u;
         uint32_t incl = cnt;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, o); if (lane >= o) incl += y; }
         const uint32_t tot = (uint32_t)__shfl((int)incl, 63);
         const uint32_t ncl = (uint32_t)__popcll((unsigned long long)mask);
-        // the wave's clusters and their runs of order[] in one atomic: low word = clusters, high word = nodes (= counts[0], counts[1])
-        unsigned long long got = 0ull;
-        if (lane == 0) got = atomicAdd(counts64, ((unsigned long long)tot << 32) | ncl);
-        const uint32_t u0 = (uint32_t)__shfl((int)(uint32_t)got, 0), n0 = (uint32_t)__shfl((int)(uint32_t)(got >> 32), 0);
+        // the WORKGROUP's clusters and their runs of order[] in one atomic: low word = clusters, high word = nodes (= counts[0],
+        // counts[1]).  Returning atomics on one word are served one after the other, some 9 ns each: one per wave was most of
+        // this launch's time (764 of them at 12 k candidates, 4 000 at 73 k); one per workgroup is a quarter of that.
+        if (lane == 0) s_wave[wave] = ((unsigned long long)tot << 32) | ncl;
+        __syncthreads();
+        const unsigned long long w = lane < kEmitBlock / 64 ? s_wave[lane] : 0ull;
+        const unsigned long long all = sum16(w), before = sum16(lane < wave ? w : 0ull);
+        if (t == 0 && all != 0ull) s_got = atomicAdd(counts64, all);
+        __syncthreads();
+        if (mask == 0ull) continue;
+        const unsigned long long got = s_got + before;
+        const uint32_t u0 = (uint32_t)got, n0 = (uint32_t)(got >> 32);
         const uint32_t my_first = n0 + incl - cnt;
         if (isfirst) {
             const uint32_t u = u0 + (uint32_t)__popcll((unsigned long long)(mask & below));
             cl_first[u] = (int32_t)my_first; cl_count[u] = (int32_t)cnt;
-            reinterpret_cast<int4*>(cl_key)[u] = make_int4((int32_t)(A.s.head[h] >> 32), A.cls[i], A.b1[i], A.b2[i]);
-            // the table cleans itself: only this lane still looks at the entry
+            reinterpret_cast<int4*>(cl_key)[u] = make_int4((int32_t)(hd >> 32), kc, k1, k2);
+            // the table cleans itself: the cluster's other members may still be reading the entry, and drop what they read
             A.s.head[h] = 0ull; A.s.cnt[h] = 0u; A.s.first_slot[h] = 0xFFFFFFFFu;
         }
-        // the members of each of the wave's clusters, in slot order: 64-slot sweeps from the smallest member on
+        // the members of each of the wave's clusters, in slot order.  No member lies in front of the first, so the 64-slot
+        // stretches from `base` on hold them all: the wave's own and the kAhead behind it are in registers and serve every
+        // first of the wave; only a cluster that reaches further goes on with one load per stretch
         uint64_t m = mask;
         while (m != 0ull) {
             const int L = __ffsll((unsigned long long)m) - 1;
             m &= m - 1ull;
             const uint32_t hL = (uint32_t)__shfl((int)h, L), cL = (uint32_t)__shfl((int)cnt, L), fL = (uint32_t)__shfl((int)my_first, L);
             uint32_t found = 0;
-            for (int64_t j0 = base + L; found < cL && j0 < n_slots; j0 += 64) {
-                const int64_t j = j0 + lane;
-                const bool hit = j < n_slots && A.s.slot_h[j] == hL;
+            auto take = [&](bool hit, int64_t j) {
                 const uint64_t bal = __ballot(hit);
                 if (hit) {
                     const uint32_t k = found + (uint32_t)__popcll((unsigned long long)(bal & below));
                     order[fL + (tie_desc ? cL - 1u - k : k)] = (int32_t)j;
                 }
                 found += (uint32_t)__popcll((unsigned long long)bal);
+            };
+            take(h == hL, i);
+#pragma unroll
+            for (int k = 0; k < kAhead; k++) take(ahead[k] == hL, i + 64 * (k + 1));
+            for (int64_t j0 = base + 64 * (kAhead + 1); found < cL && j0 < n_slots; j0 += 64) {
+                const int64_t j = j0 + lane;
+                take(j < n_slots && A.s.slot_h[j] == hL, j);
             }
         }
     }
+    // the cuts are done with: the tree is all ones again for the next call
+    for (int64_t i = gtid; i < 2 * (int64_t)A.F2; i += gstride) A.s.tree[i] = ~0ull;
 }
 
 inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
@@ -404,7 +548,7 @@ hipError_t launch_flush_groupby(int32_t n_slots_layout, int32_t n_fl_layout, con
     const int g = grid_of(work, kWideBlock, 2048);
     hipLaunchKernelGGL(flushw_cut_kernel, dim3(g), dim3(kWideBlock), 0, stream, A, counts);
     hipLaunchKernelGGL(flushw_mark_kernel, dim3(g), dim3(kWideBlock), 0, stream, A);
-    hipLaunchKernelGGL(flushw_emit_kernel, dim3(grid_of((int64_t)cand_cap * IM_MAX_EV, kWideBlock, 4096)), dim3(kWideBlock), 0, stream, A, tie_desc,
+    hipLaunchKernelGGL(flushw_emit_kernel, dim3(grid_of((int64_t)cand_cap * IM_MAX_EV, kEmitBlock, 4096 * kWideBlock / kEmitBlock)), dim3(kEmitBlock), 0, stream, A, tie_desc,
                        order, cl_key, cl_first, cl_count, reinterpret_cast<unsigned long long*>(counts));
     return hipGetLastError();
 }
