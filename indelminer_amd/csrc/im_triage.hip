@@ -11,27 +11,50 @@
 //
 // Shape.  HBM streaming: every byte of a record is read once (core, CIGAR, aux by the record's
 // own lane; the packed bases of the ~4 % candidates by the whole wave), nothing is staged.
-// Three launches per chunk, one lane per record:
-//   classify   class + read-group range per record, per-workgroup candidate / byte totals,
-//              pileup segments scattered into the genome-wide difference array; 64-record (one-wave) workgroups
-//   scan       one workgroup: exclusive scan of the workgroup totals on top of the running
+// Four launches per chunk on the caller's stream (capturable: no memset, no allocation, no synchronisation):
+//   classify   one lane per record, 64-record (one-wave) workgroups: class + read-group range per record,
+//              pileup segments scattered into the genome-wide difference array, and the workgroup's
+//              candidate / byte / counted / error totals as ONE plain store -- then the wave ends
+//   scan       one workgroup of 256 lanes, a lane per group of 32 classify workgroups: exclusive scan of those totals on top of the running
 //              candidate / byte counters (candidates are appended in RECORD ORDER -- arrival
-//              order decides tie order inside clusters)
-//   emit       candidate index = running base + position in the workgroup; the owner lane
-//              writes the per-read scalars and the CIGAR-derived evidence slots, then the wave
-//              decodes each of its candidates' bases together, four bases per lane
+//              order decides tie order inside clusters); one base entry per emit
+//              workgroup, the running counters, the chunk's first candidate
+//   emit       one lane per record: candidate index = its workgroup's base entry + position in the
+//              workgroup; the owner lane writes the per-read scalars and the CIGAR-derived evidence slots
+//   decode     32 lanes per candidate: the packed bases to ASCII, four bases per lane and pass
+// What one launch leaves for the next is visible at the kernel boundary on the stream; no kernel
+// here waits for another workgroup or reads what another workgroup of its own launch wrote.
 // Algorithmic bytes: the record bytes in + (4-byte padded read + 24 B of scalars + 48 B of
 // slots) per candidate out + 1 B class per record.
 
 #include "im_device.hpp"
 #include "im_rg.hpp"
+#include "im_wave.hpp"
+
+// Diagnostic build only (-DIM_STAMPS, `python indelminer_amd/build.py --stamps`): where a classify wave's life goes.  Six readings
+// of the shader clock per wave -- entry, core arrived, CIGAR / aux / sweep arrived, classification done, window written out,
+// publication done -- one 64-byte record per workgroup (at blockIdx.x, launches write over each other), read back through
+// im_debug_tri_stamps_read by profiles/triage_stamps.py.  The product library is built without it and contains no stamp.
+#ifdef IM_STAMPS
+constexpr int kTriStampCap = 32768;
+__device__ unsigned long long im_tri_stamp_rec[kTriStampCap][8];
+#define IM_TRI_STAMP_DECL unsigned long long tri_t_[6]; tri_t_[0] = __builtin_amdgcn_s_memtime(); \
+                          tri_t_[1] = tri_t_[2] = tri_t_[3] = tri_t_[4] = tri_t_[5] = tri_t_[0];
+// v: a value the phase ends with -- the clock is read once it is in a register
+#define IM_TRI_STAMP(k, v) do { asm volatile("" :: "v"(v)); tri_t_[k] = __builtin_amdgcn_s_memtime(); } while (0)
+#define IM_TRI_STAMP_OUT(lane) do { if ((lane) < 6) { const int l_ = (lane); \
+        im_tri_stamp_rec[blockIdx.x % kTriStampCap][l_] = l_ == 0 ? tri_t_[0] : l_ == 1 ? tri_t_[1] : l_ == 2 ? tri_t_[2] : l_ == 3 ? tri_t_[3] : l_ == 4 ? tri_t_[4] : tri_t_[5]; } } while (0)
+#else
+#define IM_TRI_STAMP_DECL
+#define IM_TRI_STAMP(k, v)
+#define IM_TRI_STAMP_OUT(lane)
+#endif
 
 namespace im {
 namespace {
 
 constexpr int kTriBlock = 256;          // records of an emit workgroup
-constexpr int kTriGroup = 32;           // classify workgroups that count their publication into one word (see the classify kernel's tail)
-constexpr int kTriGroupsMax = 2048;
+constexpr int kTriGroup = 32;           // classify workgroups of a group: 256 bytes of blk[], what one lane of the scan takes a pass
 
 __device__ __forceinline__ uint32_t ld_u16(const uint8_t* p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
 
@@ -256,12 +279,8 @@ struct TriageArgs {
     int32_t* depth_diff;    // genome-wide difference array (index = ascii offset of the position) or null
     uint32_t* info;         // [n] class | revcomp << 8
     int32_t* rmax;          // [n]
-    uint2* blk;             // [classify workgroups] one packed word per workgroup: padded read bytes << 32 | candidates | counted << 9 | errors << 18
-    uint32_t* blocks_done;  // [1] zero between launches: groups of workgroups that are complete; the group that comes last scans grp[]
-    uint32_t* grp_done;     // [kTriGroupsMax] zero between launches: workgroups of a group that have published their totals (group g at grp_done_slot(g))
-    unsigned long long* grp;// [2 * groups] a group's totals: bytes << 32 | candidates, counted << 32 | errors
-    uint2* grp_base;        // [groups] candidates / bytes in front of a group (running counters included), written by the last group
-    int32_t group_size;     // classify workgroups per group
+    uint2* blk;             // [classify workgroups, padded to whole groups of kTriGroup] one packed word per workgroup: x = candidates | counted << 9 | errors << 18, y = padded read bytes
+    uint2* wg_base;         // [emit workgroups] candidates / bytes in front of an emit workgroup (running counters included), written by the scan
     uint32_t* seq_at;       // [cap_cand] byte offset of a candidate's packed bases in recs.raw, | 1 << 31 = reverse complement
     int32_t* chunk_base;    // [1] candidates before this chunk (written by the scan)
 };
@@ -278,13 +297,8 @@ constexpr int kDepthWin = 1024;     // positions of the depth difference array a
                                     // 16 per record.  Events outside it go to memory directly, so results do not depend on it.
 constexpr int kClsRgLds = 448;      // an insert-length table up to this size (a handful of read groups) is copied to LDS
 static_assert(kTriBlock % kClsBlock == 0 && kTriGroup % (kTriBlock / kClsBlock) == 0, "an emit workgroup's classify blocks lie in one group");
+static_assert(kClsBlock < 512, "a workgroup's candidate, counted and error counts take nine bits each of its packed word");
 static_assert(kClsBlock * kAuxWin + kClsBlock * 4 + kDepthWin * 4 + kClsRgLds <= kClsLdsBudget, "classify must fit the hole a realign wave leaves");
-
-// Where group g counts its workgroups in grp_done[kTriGroupsMax]: neighbouring groups 128 bytes apart.  Atomics on ONE cache line are
-// served one after the other like atomics on one word: with the groups' words side by side, 4 688 workgroups counting into five
-// lines took 8 us of the step, and groups of 128 (two lines) 28 (profiles/README.md, "classify beside realign").
-static_assert(kTriGroupsMax == 64 * 32, "grp_done_slot: 64 lines of 32 words");
-__device__ __forceinline__ int32_t grp_done_slot(int32_t g) { return (g & 63) * 32 + (g >> 6); }
 
 // LDS written by one lane and read by another of the same wave: the wave's LDS operations complete in order, so only the
 // compiler has to keep them in order.  Wavefront scope: no barrier, no cache operation.
@@ -301,6 +315,7 @@ __global__ __launch_bounds__(kClsBlock, 6) void triage_classify_kernel(TriageArg
     __shared__ int32_t s_dd[kDepthWin];
     __shared__ uint32_t s_fb[kClsBlock];
     const int lane = threadIdx.x;
+    IM_TRI_STAMP_DECL
     const int64_t i = (int64_t)blockIdx.x * kClsBlock + lane;
     if (A.depth_diff) {
         int4* z = reinterpret_cast<int4*>(s_dd);
@@ -315,6 +330,7 @@ __global__ __launch_bounds__(kClsBlock, 6) void triage_classify_kernel(TriageArg
     const bool rg_lds = A.rg.bytes <= kClsRgLds;
     if (rg_lds) for (int k = lane; 4 * k < A.rg.bytes; k += kClsBlock) s_rg[k] = reinterpret_cast<const uint32_t*>(A.rg.blob)[k];
     if (i < A.recs.n) r = view_record(A.recs.raw, A.recs.rec_off[i], A.recs.rec_off[i + 1]);
+    IM_TRI_STAMP(1, r.flag);
     const uint32_t sw_lim = reaches_new_readaln(r) ? (uint32_t)r.l_seq : 0u;   // r.ok: the packed bases lie inside the record
     const uint32_t sw_so = sw_lim ? (uint32_t)(r.p - A.recs.raw) + r.o_seq : 0u;
     BaseSweep S;
@@ -340,6 +356,7 @@ __global__ __launch_bounds__(kClsBlock, 6) void triage_classify_kernel(TriageArg
         dd_pos = fp < 0 ? 0 : fp; dd_tid = mp ? ft : -1;
     }
     wave_lds_order();                                                           // the table, the sweep's minima and the zeroed window are in
+    IM_TRI_STAMP(2, r.cig[3]);
     const RgView T = rg_view(rg_lds ? reinterpret_cast<const uint8_t*>(s_rg) : A.rg.blob, A.rg.n);
 
     uint32_t cls = IM_REC_SKIP, bytes = 0;
@@ -375,6 +392,7 @@ __global__ __launch_bounds__(kClsBlock, 6) void triage_classify_kernel(TriageArg
             }
         }
     }
+    IM_TRI_STAMP(3, cls);
     // workgroup totals
     const uint64_t mc = __ballot(cand);
     uint32_t wb = bytes;
@@ -393,90 +411,114 @@ __global__ __launch_bounds__(kClsBlock, 6) void triage_classify_kernel(TriageArg
             if (v != 0 && idx < room) atomicAdd(&dst[idx], v);
         }
     }
-    // Publication.  A workgroup's totals go out with a RETURNING agent-scope atomic and are counted only once the return is
-    // in: the count cannot overtake the totals, and no fence is needed (an agent-scope fence is a whole-L2 write-back per
-    // workgroup on this chip, profiles/README.md).  The counting is in two levels: a thousand workgroups adding to ONE word
-    // took 12 of the kernel's 36 us (same-address atomics are served one after the other, ~9 ns each; measured by leaving the
-    // tail out, profiles/r04_d_*), so a workgroup counts into its GROUP's word, the workgroup that completes a group adds the
-    // group's totals up and counts the group, and the workgroup that completes the last group scans the groups.  No workgroup
-    // waits for another.
-    const int32_t n_blocks = (int32_t)gridDim.x;
-    const int32_t gsz = A.group_size, g = (int32_t)blockIdx.x / gsz, g_first = g * gsz;
-    const int32_t g_n = min(gsz, n_blocks - g_first), n_groups = (n_blocks + gsz - 1) / gsz;
-    uint32_t role = 0;
-    if (lane == 0) {
-        // one word per workgroup: padded read bytes | candidates, counted records and error records (each <= 64; 9 bits each)
-        unsigned long long seen = atomicExch(reinterpret_cast<unsigned long long*>(&A.blk[blockIdx.x]),
-                                             ((unsigned long long)wb << 32) | (uint32_t)__popcll(mc) | ((uint32_t)__popcll(mk) << 9) | ((uint32_t)__popcll(me) << 18));
-        asm volatile("" :: "v"(seen));
-        role = atomicAdd(&A.grp_done[grp_done_slot(g)], 1u) == (uint32_t)g_n - 1u ? 1u : 0u;
-    }
-    role = (uint32_t)__shfl((int)role, 0);
-    if (!role) return;
-    // last workgroup of its group: the group's totals (the members' words come back through the atomic path they went out on)
-    {
-        unsigned long long cb = 0, ke = 0;
-        for (int32_t j = lane; j < g_n; j += 64) {
-            const unsigned long long pv = atomicAdd(reinterpret_cast<unsigned long long*>(&A.blk[g_first + j]), 0ull);
-            cb += (pv & 0xFFFFFFFF00000000ull) | ((uint32_t)pv & 511u);
-            ke += ((unsigned long long)(((uint32_t)pv >> 9) & 511u) << 32) | (((uint32_t)pv >> 18) & 511u);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            cb += ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(cb >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)cb, o);
-            ke += ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(ke >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)ke, o);
-        }
-        role = 0;
-        if (lane == 0) {
-            unsigned long long s0 = atomicExch(&A.grp[2 * g], cb), s1 = atomicExch(&A.grp[2 * g + 1], ke);
-            asm volatile("" :: "v"(s0), "v"(s1));
-            atomicExch(&A.grp_done[grp_done_slot(g)], 0u);                      // ready for the next launch
-            role = atomicAdd(A.blocks_done, 1u) == (uint32_t)n_groups - 1u ? 2u : 0u;
-        }
-        role = (uint32_t)__shfl((int)role, 0);
-    }
-    if (role != 2u) return;
-    // Last group to complete: exclusive scan of the groups' totals on top of the running counters (candidates are appended in
-    // record order), 64 groups a round; the emit kernel adds the workgroups in front of it inside its group.
+    IM_TRI_STAMP(4, wb);
+    // Publication: the workgroup's totals in one packed word, one plain store by lane 0, and the wave ends -- it holds its registers
+    // and its LDS for no round trip after its last store.  The scan launch behind this one on the stream reads the words; the kernel
+    // boundary makes them visible.  (Until the scan had a launch of its own again, every wave counted itself into its group with two
+    // dependent returning atomics, and the last wave of the launch scanned: profiles/README.md, "the scan out of classify's waves".)
+    // x: candidates, counted records and error records (each <= 64; 9 bits each); y: padded read bytes
+    if (lane == 0) A.blk[blockIdx.x] = make_uint2((uint32_t)__popcll(mc) | ((uint32_t)__popcll(mk) << 9) | ((uint32_t)__popcll(me) << 18), wb);
+    IM_TRI_STAMP(5, wb);
+    IM_TRI_STAMP_OUT(lane);
+}
+
+// The scan: ONE workgroup of kScanLanes lanes, two levels.  A lane takes one GROUP of kTriGroup classify workgroups a pass: the
+// kAhead emit workgroups they make, kScanPerLane words each, 256 consecutive bytes of blk[] as sixteen loads that are in flight
+// together.  It adds them up per emit workgroup, the groups' totals are scanned across the workgroup (DPP steps inside a wave, the
+// waves' totals through LDS, one barrier), and the lane walks its emit workgroups again, writing each one's base where
+// triage_emit_kernel takes it with one load.  A pass covers kScanLanes groups = 8 192 classify workgroups = 524 288 records, so the
+// launches of the product's chunks are one pass.  A longer launch takes pass after pass; fetching the next pass's words before the
+// current pass is scanned was built and measured, and did not pay (143 registers against 94, and no faster on a launch of four
+// passes: profiles/README.md).  At most 256 lanes: a wider workgroup starts only where a CU has room for all of its waves, and
+// beside the other streams' one-wave workgroups that took up to 58 us (profiles/README.md).
+constexpr int kScanLanes = 256;
+constexpr int kScanPerLane = kTriBlock / kClsBlock;
+constexpr int kAhead = 8;
+static_assert(kScanPerLane == 4, "an emit workgroup's words are two 16-byte loads");
+static_assert(kAhead * kScanPerLane == kTriGroup, "a lane's kAhead emit workgroups are one group");
+static_assert(kTriGroup * sizeof(uint2) == 256, "blk[] is padded to 256 bytes: whole groups");
+static_assert(kScanLanes % 64 == 0 && kScanLanes <= 256, "whole waves, and no wider than fits beside the other streams' workgroups");
+
+__global__ __launch_bounds__(kScanLanes) void triage_scan_kernel(TriageArgs A)
+{
+    constexpr int kWaves = kScanLanes / 64;
+    __shared__ uint2 s_tot[2][kWaves];              // the waves' totals of a pass; passes alternate between the two rows (one barrier a pass)
+    __shared__ uint2 s_ke[kWaves];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int32_t n_blocks = (int32_t)(((int64_t)A.recs.n + kClsBlock - 1) / kClsBlock);
+    const int32_t n_emit = (n_blocks + kScanPerLane - 1) / kScanPerLane;
+    const int32_t n_groups = (n_blocks + kTriGroup - 1) / kTriGroup;
+    const int32_t n_passes = (n_groups + kScanLanes - 1) / kScanLanes;
     // restart: this launch opens a new batch -- the running counters count as zero whatever they hold (no memset in front)
     const bool fresh = A.tp.restart != 0;
     uint32_t carry_c = fresh ? 0u : (uint32_t)A.out.counters[0], carry_b = fresh ? 0u : (uint32_t)A.out.counters[1];
-    if (lane == 0) A.chunk_base[0] = (int32_t)carry_c;
+    const uint32_t chunk_first = carry_c;
+    const uint4* src = reinterpret_cast<const uint4*>(A.blk);           // two workgroups' words a load
+    uint4 buf[2 * kAhead];
+    // blk[] is allocated in whole groups (256 bytes).  A lane behind the launch's last group loads that group again -- the loads
+    // stay unconditional -- and counts none of it
+    auto fetch = [&](int32_t pass) {
+        const int64_t g = (int64_t)pass * kScanLanes + t;
+        const uint4* p = src + (g < n_groups ? g : (int64_t)n_groups - 1) * (2 * kAhead);
+#pragma unroll
+        for (int i = 0; i < 2 * kAhead; i++) buf[i] = p[i];
+    };
     uint32_t sum_k = 0, sum_e = 0;
-    // rounds whose totals are fetched together: a round's loads do not wait for the round before.  One wave scans where four did: with
-    // two rounds a fetch the 916 groups of a 1.875 M-record launch were eight fetches one after the other, +23 us on that launch
-    constexpr int kAhead = 8;
-    for (int32_t base = 0; base < n_groups; base += kAhead * 64) {
-        unsigned long long cbv[kAhead], kev[kAhead];
+    for (int32_t pass = 0; pass < n_passes; pass++) {
+        fetch(pass);
+        const int64_t g = (int64_t)pass * kScanLanes + t;
+        // classify and emit workgroups of the launch inside this lane's group
+        const int64_t left_b = (int64_t)n_blocks - g * kTriGroup, left_e = (int64_t)n_emit - g * kAhead;
+        const int nb = left_b < 0 ? 0 : left_b > kTriGroup ? kTriGroup : (int)left_b, ne = left_e < 0 ? 0 : left_e > kAhead ? kAhead : (int)left_e;
+        // the lane's emit workgroups: candidates and bytes of each.  Words of classify workgroups behind the launch's last one are
+        // whatever an earlier, larger launch left there: they count as zero
+        uint32_t oc[kAhead], ob[kAhead], own_c = 0, own_b = 0;
 #pragma unroll
-        for (int q = 0; q < kAhead; q++) {
-            const int32_t j = base + 64 * q + lane;
-            cbv[q] = 0ull; kev[q] = 0ull;
-            if (j < n_groups) { cbv[q] = atomicAdd(&A.grp[2 * j], 0ull); kev[q] = atomicAdd(&A.grp[2 * j + 1], 0ull); }
-        }
+        for (int j = 0; j < kAhead; j++) {
+            const uint4 d0 = buf[2 * j], d1 = buf[2 * j + 1];
+            const uint32_t wx[4] = { d0.x, d0.z, d1.x, d1.z }, wy[4] = { d0.y, d0.w, d1.y, d1.w };
+            oc[j] = 0u; ob[j] = 0u;
 #pragma unroll
-        for (int q = 0; q < kAhead; q++) {
-            const int32_t j = base + 64 * q + lane;
-            const uint32_t vx = (uint32_t)cbv[q], vy = (uint32_t)(cbv[q] >> 32);
-            sum_k += (uint32_t)(kev[q] >> 32); sum_e += (uint32_t)kev[q];
-            uint32_t c = vx, b = vy;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t tc = (uint32_t)__shfl_up((int)c, o), tb = (uint32_t)__shfl_up((int)b, o);
-                if (lane >= o) { c += tc; b += tb; }
+            for (int k = 0; k < kScanPerLane; k++) {
+                const bool in = j * kScanPerLane + k < nb;
+                const uint32_t x = in ? wx[k] : 0u;
+                oc[j] += x & 511u; ob[j] += in ? wy[k] : 0u;
+                sum_k += (x >> 9) & 511u; sum_e += (x >> 18) & 511u;
             }
-            if (j < n_groups) A.grp_base[j] = make_uint2(carry_c + c - vx, carry_b + b - vy);
-            carry_c += (uint32_t)__shfl((int)c, 63); carry_b += (uint32_t)__shfl((int)b, 63);
+            own_c += oc[j]; own_b += ob[j];
         }
-    }
+        const uint32_t c = (uint32_t)wave_scan_add((int)own_c, lane), b = (uint32_t)wave_scan_add((int)own_b, lane);
+        uint2* tot = s_tot[pass & 1];
+        if (lane == 63) tot[wave] = make_uint2(c, b);
+        __syncthreads();
+        uint32_t front_c = 0, front_b = 0, all_c = 0, all_b = 0;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sum_k += (uint32_t)__shfl_xor((int)sum_k, o); sum_e += (uint32_t)__shfl_xor((int)sum_e, o); }
-    if (lane == 0) {
+        for (int w = 0; w < kWaves; w++) {
+            const uint2 v = tot[w];
+            if (w < wave) { front_c += v.x; front_b += v.y; }
+            all_c += v.x; all_b += v.y;
+        }
+        uint32_t at_c = carry_c + front_c + c - own_c, at_b = carry_b + front_b + b - own_b;
+#pragma unroll
+        for (int j = 0; j < kAhead; j++) {
+            if (j < ne) A.wg_base[g * kAhead + j] = make_uint2(at_c, at_b);
+            at_c += oc[j]; at_b += ob[j];
+        }
+        carry_c += all_c; carry_b += all_b;
+    }
+    sum_k = (uint32_t)wave_sum((int)sum_k); sum_e = (uint32_t)wave_sum((int)sum_e);
+    if (lane == 0) s_ke[wave] = make_uint2(sum_k, sum_e);
+    __syncthreads();
+    if (t == 0) {
+        uint32_t k = 0, e = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; w++) { k += s_ke[w].x; e += s_ke[w].y; }
+        A.chunk_base[0] = (int32_t)chunk_first;
+        const int32_t k0 = fresh ? 0 : A.out.counters[2], e0 = fresh ? 0 : A.out.counters[3];
         A.out.counters[0] = (int32_t)carry_c; A.out.counters[1] = (int32_t)carry_b;
-        A.out.counters[2] = (fresh ? 0 : A.out.counters[2]) + (int32_t)sum_k;          // records counted
-        A.out.counters[3] = (fresh ? 0 : A.out.counters[3]) + (int32_t)sum_e;          // error records (emit / decode add theirs later)
+        A.out.counters[2] = k0 + (int32_t)k;                                           // records counted
+        A.out.counters[3] = e0 + (int32_t)e;                                           // error records (emit / decode add theirs later)
         if (fresh) A.out.counters[4] = 0;                                              // overflows: counted by the emit kernel
-        *A.blocks_done = 0u;
     }
 }
 
@@ -514,23 +556,11 @@ __global__ __launch_bounds__(kTriBlock) void triage_emit_kernel(TriageArgs A)
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const uint32_t tb = (uint32_t)__shfl_up((int)ib, o); if (lane >= o) ib += tb; }
     if (lane == 63) { s_cnt[wave] = (uint32_t)__popcll(mc); s_bytes[wave] = ib; }
-    // candidates / bytes in front of this workgroup: its group's base (the classify kernel's scan) + the classify workgroups of the
-    // group in front (this workgroup's records are kTriBlock / kClsBlock classify workgroups; a group holds a multiple of that)
-    __shared__ uint2 s_base;
-    if (t < 64) {
-        const int32_t mine0 = (int32_t)blockIdx.x * (kTriBlock / kClsBlock);
-        const int32_t gsz = A.group_size, g = mine0 / gsz, g_first = g * gsz, mine = mine0 - g_first;
-        uint32_t fc = 0, fb = 0;
-        for (int32_t j = t; j < mine; j += 64) { const uint2 pv = A.blk[g_first + j]; fc += pv.x & 511u; fb += pv.y; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { fc += (uint32_t)__shfl_xor((int)fc, o); fb += (uint32_t)__shfl_xor((int)fb, o); }
-        if (t == 0) { const uint2 gb = A.grp_base[g]; s_base = make_uint2(gb.x + fc, gb.y + fb); }
-    }
     __syncthreads();
     if (!cand) return;
     uint32_t oc = 0, ob = 0;
     for (int w = 0; w < wave; w++) { oc += s_cnt[w]; ob += s_bytes[w]; }
-    const uint2 base = s_base;
+    const uint2 base = A.wg_base[blockIdx.x];           // candidates / bytes in front of this workgroup, running counters included (the scan)
     const uint32_t ci = base.x + oc + below;
     const uint32_t bo = base.y + ob + ib - bytes;
     const im_dev_batch& B = A.out.batch;
@@ -656,25 +686,38 @@ __global__ __launch_bounds__(256) void triage_decode_kernel(TriageArgs A)
 
 }  // namespace
 
-// fixed words at the head of the scratch: chunk_base (256 B), blocks_done (256 B), grp_done (zero between launches), grp, grp_base
-constexpr size_t kTriFixedZero = 512 + 4 * (size_t)kTriGroupsMax;
-constexpr size_t kTriFixed = kTriFixedZero + 16 * (size_t)kTriGroupsMax + 8 * (size_t)kTriGroupsMax;
+// fixed words at the head of the scratch: chunk_base (256 B)
+constexpr size_t kTriFixed = 256;
 
 size_t triage_scratch_bytes(int32_t n_records)
 {
     const size_t n = (size_t)(n_records > 0 ? n_records : 1);
-    const size_t blocks = (n + kClsBlock - 1) / kClsBlock;       // blk[]: one word per classify workgroup
+    const size_t emits = (n + kTriBlock - 1) / kTriBlock;        // blk[]: one word per classify workgroup, whole emit workgroups; wg_base[]: one per emit workgroup
     auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    return up(n * 4) + up(n * 4) + up(blocks * 8) + up(n * 4) + kTriFixed;
+    return up(n * 4) + up(n * 4) + up(emits * (kTriBlock / kClsBlock) * 8) + up(emits * 8) + up(n * 4) + kTriFixed;
 }
 
-// offset of the words that must be zero before the first launch on a scratch buffer
+// No word of the scratch has to hold anything before the first launch: every launch writes what it reads.  The entry point stays for
+// the callers that have it; it clears the fixed words.
 size_t triage_scratch_zero_offset(int32_t n_records, size_t* bytes)
 {
     (void)n_records;
-    *bytes = kTriFixedZero;
+    *bytes = kTriFixed;
     return 0;
 }
+
+#ifdef IM_STAMPS
+extern "C" int im_debug_tri_stamps_read(unsigned long long* out, int n_rec, int reset)
+{
+    if (n_rec < 0 || n_rec > kTriStampCap) return -1;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(out, HIP_SYMBOL(im_tri_stamp_rec), (size_t)n_rec * 64);
+    void* sym = nullptr;
+    if (e == hipSuccess && reset) e = hipGetSymbolAddress(&sym, HIP_SYMBOL(im_tri_stamp_rec));
+    if (e == hipSuccess && reset) e = hipMemset(sym, 0, sizeof(im_tri_stamp_rec));
+    return e == hipSuccess ? 0 : -1;
+}
+#endif
 
 hipError_t launch_triage(const RefDev& ref, const RgTable& rg, int32_t* depth_diff, const im_triage_params& tp,
                          const im_dev_records& recs, const im_dev_cands& out, void* scratch, hipStream_t stream)
@@ -689,17 +732,13 @@ hipError_t launch_triage(const RefDev& ref, const RgTable& rg, int32_t* depth_di
     // fixed words first (their place must not depend on the launch's record count), then the per-record arrays
     char* s = static_cast<char*>(scratch);
     A.chunk_base = reinterpret_cast<int32_t*>(s); s += 256;
-    A.blocks_done = reinterpret_cast<uint32_t*>(s); s += 256;      // zeroed by im_dev_triage_scratch_init, left zero by every launch
-    A.grp_done = reinterpret_cast<uint32_t*>(s); s += 4 * (size_t)kTriGroupsMax;       // likewise
-    A.grp = reinterpret_cast<unsigned long long*>(s); s += 16 * (size_t)kTriGroupsMax;
-    A.grp_base = reinterpret_cast<uint2*>(s); s += 8 * (size_t)kTriGroupsMax;
-    A.group_size = kTriGroup;
-    while ((cls_blocks + A.group_size - 1) / A.group_size > kTriGroupsMax) A.group_size *= 2;
     A.info = reinterpret_cast<uint32_t*>(s); s += up(n * 4);
     A.rmax = reinterpret_cast<int32_t*>(s); s += up(n * 4);
-    A.blk = reinterpret_cast<uint2*>(s); s += up((size_t)cls_blocks * 8);
+    A.blk = reinterpret_cast<uint2*>(s); s += up((size_t)blocks * (kTriBlock / kClsBlock) * 8);      // whole groups of kTriGroup words: up()'s 256 bytes
+    A.wg_base = reinterpret_cast<uint2*>(s); s += up((size_t)blocks * 8);
     A.seq_at = reinterpret_cast<uint32_t*>(s);
     hipLaunchKernelGGL(triage_classify_kernel, dim3(cls_blocks), dim3(kClsBlock), 0, stream, A);
+    hipLaunchKernelGGL(triage_scan_kernel, dim3(1), dim3(kScanLanes), 0, stream, A);
     hipLaunchKernelGGL(triage_emit_kernel, dim3(blocks), dim3(kTriBlock), 0, stream, A);
     int dgrid = (int)((n + 63) / 64);           // one 32-lane group per candidate, 8 per workgroup; ~1/8 of the records at most pays off
     if (dgrid > 16384) dgrid = 16384;           // a candidate per 32-lane group while that stays a sane grid: a group's candidates are a chain of dependent loads each
