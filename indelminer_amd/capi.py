@@ -474,6 +474,21 @@ class Context:
     def _query_tid(self, fn, tid, beg, end):
         return self._query(fn, beg, end, tid)
 
+    # one body per operation of the keyed tables (clip tails, pair links, mate links); fn is the library function of the table
+    def _keyed_enable(self, fn, *params):
+        self._check(fn(self.h, *[int(p) for p in params]))
+
+    def _keyed_scatter(self, fn, recs, stream):
+        self._check(fn(self.h, C.byref(recs), self.stream if stream is None else stream))
+
+    def _keyed_reset(self, fn, stream):
+        self._check(fn(self.h, self.stream if stream is None else stream))
+
+    def _keyed_stats(self, fn):
+        stored, dropped = C.c_uint64(0), C.c_uint64(0)
+        self._check(fn(self.h, C.byref(stored), C.byref(dropped)))
+        return int(stored.value), int(dropped.value)
+
     def depth_build(self, contig_len, seg_start, seg_len):
         self._build(lib().im_depth_build, contig_len, seg_start, seg_len)
 
@@ -613,11 +628,11 @@ class Context:
 
     def cliptail_enable(self, min_clip, min_mapq, log2_slots):
         """the keyed table of clipped bases (-V): 2^log2_slots slots of 16 bytes, half of them usable"""
-        self._check(lib().im_cliptail_enable(self.h, int(min_clip), int(min_mapq), int(log2_slots)))
+        self._keyed_enable(lib().im_cliptail_enable, min_clip, min_mapq, log2_slots)
 
     def cliptail_scatter(self, recs, stream=None):
         """DevRecords -> one entry per clipping end of the chunk's clipped reads (asynchronous)"""
-        self._check(lib().im_dev_cliptail_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
+        self._keyed_scatter(lib().im_dev_cliptail_scatter, recs, stream)
 
     def cliptail_add(self, tid, pos, side, nbases, planes):
         """entries of contig tid as the caller found them: position, side (0: right, 1: left), bases 1 .. 32, planes[i] = (low bits, high bits)"""
@@ -640,13 +655,11 @@ class Context:
         return tuple(o[:n] for o in out)
 
     def cliptail_reset(self, stream=None):
-        self._check(lib().im_cliptail_reset(self.h, self.stream if stream is None else stream))
+        self._keyed_reset(lib().im_cliptail_reset, stream)
 
     def cliptail_stats(self):
         """(entries stored, entries dropped) since the last reset"""
-        stored, dropped = C.c_uint64(0), C.c_uint64(0)
-        self._check(lib().im_cliptail_stats(self.h, C.byref(stored), C.byref(dropped)))
-        return int(stored.value), int(dropped.value)
+        return self._keyed_stats(lib().im_cliptail_stats)
 
     def _clip_facing(self, fn, min_reads, max_overlap, cap, *tid):
         """(pr, pl, cr, cl) of the facing piles, sorted by pr; asks again with a larger cap when there are more than cap"""
@@ -702,11 +715,11 @@ class Context:
 
     def pairlink_enable(self, min_mapq, log2_slots):
         """the keyed table of pair links (-M): 2^log2_slots slots of 16 bytes, half of them usable"""
-        self._check(lib().im_pairlink_enable(self.h, int(min_mapq), int(log2_slots)))
+        self._keyed_enable(lib().im_pairlink_enable, min_mapq, log2_slots)
 
     def pairlink_scatter(self, recs, stream=None):
         """DevRecords -> one link per leftmost record of a pair in an abnormal orientation (asynchronous)"""
-        self._check(lib().im_dev_pairlink_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
+        self._keyed_scatter(lib().im_dev_pairlink_scatter, recs, stream)
 
     def pairlink_add(self, tid, pos, mpos, kind):
         """links of contig tid as the caller found them: pos, mpos, kind (0: everted, 1: both forward, 2: both reverse)"""
@@ -728,21 +741,19 @@ class Context:
         return out[:n]
 
     def pairlink_reset(self, stream=None):
-        self._check(lib().im_pairlink_reset(self.h, self.stream if stream is None else stream))
+        self._keyed_reset(lib().im_pairlink_reset, stream)
 
     def pairlink_stats(self):
         """(links stored, links dropped) since the last reset"""
-        stored, dropped = C.c_uint64(0), C.c_uint64(0)
-        self._check(lib().im_pairlink_stats(self.h, C.byref(stored), C.byref(dropped)))
-        return int(stored.value), int(dropped.value)
+        return self._keyed_stats(lib().im_pairlink_stats)
 
     def matelink_enable(self, min_mapq, log2_slots):
         """the keyed table of mate links (-T): 2^log2_slots slots of 16 bytes, half of them usable"""
-        self._check(lib().im_matelink_enable(self.h, int(min_mapq), int(log2_slots)))
+        self._keyed_enable(lib().im_matelink_enable, min_mapq, log2_slots)
 
     def matelink_scatter(self, recs, stream=None):
         """DevRecords -> one link per record of a pair whose mate lies on another contig (asynchronous)"""
-        self._check(lib().im_dev_matelink_scatter(self.h, C.byref(recs), self.stream if stream is None else stream))
+        self._keyed_scatter(lib().im_dev_matelink_scatter, recs, stream)
 
     def matelink_add(self, tid, pos, mtid, mpos, kind):
         """links of contig tid as the caller found them: pos, mtid, mpos, kind (read reverse | mate reverse << 1)"""
@@ -764,13 +775,11 @@ class Context:
         return tuple(o[:n] for o in out)
 
     def matelink_reset(self, stream=None):
-        self._check(lib().im_matelink_reset(self.h, self.stream if stream is None else stream))
+        self._keyed_reset(lib().im_matelink_reset, stream)
 
     def matelink_stats(self):
         """(links stored, links dropped) since the last reset"""
-        stored, dropped = C.c_uint64(0), C.c_uint64(0)
-        self._check(lib().im_matelink_stats(self.h, C.byref(stored), C.byref(dropped)))
-        return int(stored.value), int(dropped.value)
+        return self._keyed_stats(lib().im_matelink_stats)
 
     def cliptail_junction(self, tid1, p1, side1, tid2, p2, side2, max_shift=32):
         """per query of two ends (tid, position, side 0: right clips, 1: left clips): (v1, v2, shift, stored1, stored2) -- the entries of

@@ -30,6 +30,14 @@ struct GenomeArray {
     int32_t flank = 0, min_mapq = 0;
 };
 
+// One keyed table (im_keyed.hpp) with what its scatter counts by (min_clip: the clip tails'; 0 elsewhere) and the entry point that
+// enables it, for the messages; slots null: not enabled
+struct KeyedMember : im::KeyedTable {
+    const char* enable;
+    int32_t min_clip = 0, min_mapq = 0;
+    explicit KeyedMember(const char* enable_) : im::KeyedTable{nullptr, nullptr, 0}, enable(enable_) {}
+};
+
 struct im_ctx {
     int device = -1;
     int n_cu = 0;
@@ -63,15 +71,8 @@ struct im_ctx {
     GenomeArray all_depth, all_span, all_pair;
     // genome-wide clipped-read counts, right and left (im_clip_enable): flank holds min_clip; never scanned, their sums stay null
     GenomeArray all_clip_r, all_clip_l;
-    // -V: the keyed table of clipped bases (im_cliptail_enable); slots null: not enabled.  min_clip and min_mapq are its scatter's
-    im::KeyedTable tail = {nullptr, nullptr, 0};
-    int32_t tail_min_clip = 0, tail_min_mapq = 0;
-    // -M: the keyed table of pair links (im_pairlink_enable), an allocation of its own; slots null: not enabled
-    im::KeyedTable link = {nullptr, nullptr, 0};
-    int32_t link_min_mapq = 0;
-    // -T: the keyed table of mate links (im_matelink_enable), a third allocation; slots null: not enabled
-    im::KeyedTable mate = {nullptr, nullptr, 0};
-    int32_t mate_min_mapq = 0;
+    // the keyed tables, an allocation each: -V the clipped bases, -M the pair links, -T the mate links
+    KeyedMember tail{"im_cliptail_enable"}, link{"im_pairlink_enable"}, mate{"im_matelink_enable"};
     // the median queries' histograms of queries of several slabs (im::launch_depth_median): zeros between calls, sized by the call that
     // needed the most; med_dirty: a call did not get to its end, the next one clears them
     uint32_t* med_scratch = nullptr;
@@ -162,37 +163,58 @@ void free_reference(im_ctx* ctx)
     }
     ctx->h_asc_off.clear(); ctx->h_len.clear(); ctx->ref_total = 0;
     // the clip-tail table, the pair-link table and the mate-link table are keyed by the contigs of the reference that goes
-    for (im::KeyedTable* t : {&ctx->tail, &ctx->link, &ctx->mate}) {
+    for (KeyedMember* t : {&ctx->tail, &ctx->link, &ctx->mate}) {
         if (t->slots) (void)hipFree(t->slots);
         if (t->counters) (void)hipFree(t->counters);
-        *t = {nullptr, nullptr, 0};
+        *t = KeyedMember(t->enable);
     }
 }
 
 // ---- the keyed table (im_keyed.hpp) behind the clip tails (im_ctx::tail), the pair links (im_ctx::link) and the mate links (im_ctx::mate) ----------
 
-// The checks both tables share; then, unless the member is enabled already -- which the caller has looked at, and compares its own
-// parameters for -- its slots and counters allocated, cleared and waited for.  who: the entry point, for the messages.
-int keyed_enable(im_ctx* ctx, im::KeyedTable im_ctx::*which, const char* who, int32_t log2_slots)
+// An enable call from its first check to its last.  min_clip: null for the families that have none.  A member that is enabled already
+// takes the same parameters again and no others; otherwise its slots and counters are allocated, cleared and waited for.
+int keyed_enable(im_ctx* ctx, KeyedMember im_ctx::*which, const int32_t* min_clip, int32_t min_mapq, int32_t log2_slots)
 {
-    if (log2_slots < 6 || log2_slots > 30) { set_err(ctx, "%s: log2_slots %d, must be 6 .. 30", who, log2_slots); return IM_E_ARG; }
-    if (ctx->n_contigs > (1 << 24)) { set_err(ctx, "%s: more than 2^24 contigs", who); return IM_E_ARG; }
-    if ((ctx->*which).slots) return IM_OK;
+    if (!ctx) return IM_E_ARG;
+    KeyedMember& T = ctx->*which;
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    if (min_clip && *min_clip < 1) { set_err(ctx, "%s: min_clip %d, must be >= 1", T.enable, *min_clip); return IM_E_ARG; }
+    if (log2_slots < 6 || log2_slots > 30) { set_err(ctx, "%s: log2_slots %d, must be 6 .. 30", T.enable, log2_slots); return IM_E_ARG; }
+    if (ctx->n_contigs > (1 << 24)) { set_err(ctx, "%s: more than 2^24 contigs", T.enable); return IM_E_ARG; }
+    const int32_t clip = min_clip ? *min_clip : 0;
+    if (T.slots) {
+        if (clip == T.min_clip && min_mapq == T.min_mapq && log2_slots == T.log2_slots) return IM_OK;
+        char clipped[32] = "";
+        if (min_clip) snprintf(clipped, sizeof clipped, "min_clip %d, ", T.min_clip);
+        set_err(ctx, "%s: already enabled with %smin_mapq %d, log2_slots %d", T.enable, clipped, T.min_mapq, T.log2_slots);
+        return IM_E_ARG;
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t bytes = (size_t)16 << log2_slots;
     unsigned long long* slots = nullptr;
     unsigned long long* counters = nullptr;
     HIP_TRY(ctx, hipMalloc((void**)&slots, bytes));
-    if (hipMalloc((void**)&counters, 2 * sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(slots); set_err(ctx, "%s: out of device memory", who); return IM_E_HIP; }
-    ctx->*which = {slots, counters, log2_slots};
+    if (hipMalloc((void**)&counters, 2 * sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(slots); set_err(ctx, "%s: out of device memory", T.enable); return IM_E_HIP; }
+    T.slots = slots; T.counters = counters; T.log2_slots = log2_slots; T.min_clip = clip; T.min_mapq = min_mapq;
     HIP_TRY(ctx, hipMemsetAsync(slots, 0, bytes, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return IM_OK;
 }
 
-int keyed_reset(im_ctx* ctx, const im::KeyedTable& T, void* stream)
+// What every other entry point asks first: the table enabled and, where the call names one (tid non-null), a contig of the reference
+int keyed_ready(im_ctx* ctx, const KeyedMember& T, const int32_t* tid)
 {
+    if (!T.slots) { set_err(ctx, "%s has not been called", T.enable); return IM_E_ARG; }
+    if (tid && (*tid < 0 || *tid >= ctx->n_contigs)) return IM_E_ARG;
+    return IM_OK;
+}
+
+int keyed_reset(im_ctx* ctx, KeyedMember im_ctx::*which, void* stream)
+{
+    if (!ctx || !(ctx->*which).slots) return IM_E_ARG;
+    const im::KeyedTable& T = ctx->*which;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemsetAsync(T.slots, 0, (size_t)16 << T.log2_slots, (hipStream_t)stream));
     HIP_TRY(ctx, hipMemsetAsync(T.counters, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream));
@@ -216,8 +238,10 @@ int keyed_overflowed(im_ctx* ctx, const im::KeyedTable& T, bool* over)
     return rc;
 }
 
-int keyed_stats(im_ctx* ctx, const im::KeyedTable& T, uint64_t* stored, uint64_t* dropped)
+int keyed_stats(im_ctx* ctx, KeyedMember im_ctx::*which, uint64_t* stored, uint64_t* dropped)
 {
+    if (!ctx || !(ctx->*which).slots || !stored || !dropped) return IM_E_ARG;
+    const im::KeyedTable& T = ctx->*which;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     unsigned long long counters[2] = {0, 0};
     const int rc = keyed_counters(ctx, T, counters);
@@ -227,7 +251,7 @@ int keyed_stats(im_ctx* ctx, const im::KeyedTable& T, uint64_t* stored, uint64_t
     return IM_OK;
 }
 
-// The workspace as columns of n elements for the entry points of either table: column k at k * up256(4 n) bytes (a column of 8-byte
+// The workspace as columns of n elements for the entry points of the three tables: column k at k * up256(4 n) bytes (a column of 8-byte
 // elements takes two), host -> device and back on the context's stream.
 struct WsColumns {
     im_ctx* ctx;
@@ -242,6 +266,38 @@ int ws_columns(im_ctx* ctx, int32_t n, int k, WsColumns* C)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *C = {ctx, (size_t)n, up256(sizeof(int32_t) * (size_t)n)};
     return ensure_ws(ctx, k * C->sb);
+}
+
+// The end of a query: its answers, in columns from `first` on (one of 8-byte elements takes two), up to the host behind the launch, the
+// table's counters with them and the ONE wait; after an overflow every answer is 0xFF bytes -- "none", not a wrong one
+struct Answer { void* host; size_t elem; };
+
+int keyed_answers(im_ctx* ctx, const im::KeyedTable& T, const WsColumns& C, int first, std::initializer_list<Answer> answers)
+{
+    int rc = IM_OK, k = first;
+    for (const Answer& a : answers) {
+        if ((rc = C.up(k, a.host, a.elem))) return rc;
+        k += a.elem > 4 ? 2 : 1;
+    }
+    bool over = false;
+    if ((rc = keyed_overflowed(ctx, T, &over))) return rc;
+    if (over) for (const Answer& a : answers) memset(a.host, 0xFF, a.elem * C.n);
+    return IM_OK;
+}
+
+// What the add and query calls of both link families check per link or query (what: "link", "query"): its kind, and -- a0 non-null --
+// that the wave walks 257 buckets at the most, one probe run per 256-base bucket of [a0, a1]
+struct LinkKinds { uint8_t max; const char* words; };
+constexpr LinkKinds kPairKinds = {2, "0 (everted), 1 (forward) or 2 (reverse)"}, kMateKinds = {3, "0 .. 3 (read reverse | mate reverse << 1)"};
+
+int link_args(im_ctx* ctx, const char* who, const char* what, const LinkKinds& K, int32_t n, const uint8_t* kind, const int32_t* a0, const int32_t* a1)
+{
+    for (int32_t i = 0; i < n; i++) {
+        if (kind[i] > K.max) { set_err(ctx, "%s: %s %d: kind %d, must be %s", who, what, i, (int)kind[i], K.words); return IM_E_ARG; }
+        const long long span = a0 ? (long long)a1[i] - (long long)a0[i] : 0;
+        if (span > 65535) { set_err(ctx, "%s: %s %d: a1 - a0 = %lld, must be <= 65535", who, what, i, span); return IM_E_ARG; }
+    }
+    return IM_OK;
 }
 
 void free_array(ContigArray& a)
@@ -491,6 +547,26 @@ im::RefDev ref_dev(const im_ctx* ctx)
     ref.ascii = ctx->ref_ascii; ref.pk = reinterpret_cast<const uint8_t*>(ctx->ref_pk);
     ref.asc_off = ctx->d_asc_off; ref.pk_off = ctx->d_pk_off; ref.len = ctx->d_len; ref.n_contigs = ctx->n_contigs;
     return ref;
+}
+
+// A scatter call: the table of *which filled from the records by launch(reference, member, records, stream), nothing waited for
+template <class Launch>
+int keyed_scatter(im_ctx* ctx, KeyedMember im_ctx::*which, const im_dev_records* recs, void* stream, Launch launch)
+{
+    if (!ctx || !recs) return IM_E_ARG;
+    const int rc = keyed_ready(ctx, ctx->*which, nullptr);
+    if (rc) return rc;
+    if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch(ref_dev(ctx), ctx->*which, *recs, (hipStream_t)stream));
+    return IM_OK;
+}
+
+// both link scatters take (reference, min_mapq, records, table, stream)
+int link_scatter(im_ctx* ctx, KeyedMember im_ctx::*which, const im_dev_records* recs, void* stream, decltype(&im::launch_pairlink_scatter) launch)
+{
+    return keyed_scatter(ctx, which, recs, stream, [launch](const im::RefDev& ref, const KeyedMember& T, const im_dev_records& r, hipStream_t st) {
+        return launch(ref, T.min_mapq, r, T, st); });
 }
 
 }  // namespace
@@ -1259,45 +1335,27 @@ int im_clip_facing(im_ctx* ctx, int32_t min_reads, int32_t max_overlap, int32_t 
 
 // ---- clip tails: the clipped bases of clipped reads against the reference behind the partner breakpoint ----------
 
-int im_cliptail_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq, int32_t log2_slots)
-{
-    if (!ctx) return IM_E_ARG;
-    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
-    if (min_clip < 1) { set_err(ctx, "im_cliptail_enable: min_clip %d, must be >= 1", min_clip); return IM_E_ARG; }
-    const bool enabled = ctx->tail.slots;
-    const int rc = keyed_enable(ctx, &im_ctx::tail, "im_cliptail_enable", log2_slots);
-    if (rc) return rc;
-    if (enabled && (min_clip != ctx->tail_min_clip || min_mapq != ctx->tail_min_mapq || log2_slots != ctx->tail.log2_slots)) {
-        set_err(ctx, "im_cliptail_enable: already enabled with min_clip %d, min_mapq %d, log2_slots %d", ctx->tail_min_clip, ctx->tail_min_mapq, ctx->tail.log2_slots);
-        return IM_E_ARG;
-    }
-    ctx->tail_min_clip = min_clip; ctx->tail_min_mapq = min_mapq;
-    return IM_OK;
-}
+int im_cliptail_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq, int32_t log2_slots) { return keyed_enable(ctx, &im_ctx::tail, &min_clip, min_mapq, log2_slots); }
 
 int im_dev_cliptail_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
 {
-    if (!ctx || !recs) return IM_E_ARG;
-    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
-    if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_cliptail_scatter(ref_dev(ctx), ctx->tail_min_clip, ctx->tail_min_mapq, *recs, ctx->tail, (hipStream_t)stream));
-    return IM_OK;
+    return keyed_scatter(ctx, &im_ctx::tail, recs, stream, [](const im::RefDev& ref, const KeyedMember& T, const im_dev_records& r, hipStream_t st) {
+        return im::launch_cliptail_scatter(ref, T.min_clip, T.min_mapq, r, T, st); });
 }
 
 // the host names the entries: checked here, staged through the workspace, one lane inserts each, wait
 int im_cliptail_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, const uint8_t* side, const uint8_t* nbases, const uint32_t* planes)
 {
     if (!ctx || n < 0 || (n > 0 && (!pos || !side || !nbases || !planes))) return IM_E_ARG;
-    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
-    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->tail, &tid);
+    if (rc) return rc;
     for (int32_t i = 0; i < n; i++) {
         if (side[i] > 1) { set_err(ctx, "im_cliptail_add: entry %d: side %d, must be 0 (right) or 1 (left)", i, (int)side[i]); return IM_E_ARG; }
         if (nbases[i] < 1 || nbases[i] > 32) { set_err(ctx, "im_cliptail_add: entry %d: %d bases, must be 1 .. 32", i, (int)nbases[i]); return IM_E_ARG; }
     }
     if (n == 0) return IM_OK;
     WsColumns C;                                                    // pos, planes (two words per entry: two columns), side, bases
-    int rc = ws_columns(ctx, n, 5, &C);
+    rc = ws_columns(ctx, n, 5, &C);
     if (rc || (rc = C.down(0, pos, 4)) || (rc = C.down(1, planes, 8)) || (rc = C.down(3, side, 1)) || (rc = C.down(4, nbases, 1))) return rc;
     HIP_TRY(ctx, im::launch_cliptail_add(n, tid, ctx->h_len[tid], C.at<int32_t>(0), C.at<uint8_t>(3), C.at<uint8_t>(4), C.at<uint32_t>(1), ctx->tail, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1309,22 +1367,17 @@ int im_cliptail_verify(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* pr, 
                        uint32_t* v_left, int32_t* shift, uint32_t* stored_right, uint32_t* stored_left)
 {
     if (!ctx || nq < 0) return IM_E_ARG;
-    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
-    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->tail, &tid);
+    if (rc) return rc;
     if (max_shift < 0 || max_shift > 32) { set_err(ctx, "im_cliptail_verify: max_shift %d, must be 0 .. 32", max_shift); return IM_E_ARG; }
     if (nq == 0) return IM_OK;
     if (!pr || !pl || !v_right || !v_left || !shift || !stored_right || !stored_left) return IM_E_ARG;
     WsColumns C;                                                    // pr, pl, then the five answers
-    int rc = ws_columns(ctx, nq, 7, &C);
+    rc = ws_columns(ctx, nq, 7, &C);
     if (rc || (rc = C.down(0, pr, 4)) || (rc = C.down(1, pl, 4))) return rc;
     HIP_TRY(ctx, im::launch_cliptail_verify(nq, tid, C.at<int32_t>(0), C.at<int32_t>(1), max_shift, ctx->ref_ascii + ctx->h_asc_off[tid], ctx->h_len[tid], ctx->tail,
                                             C.at<uint32_t>(2), C.at<uint32_t>(3), C.at<int32_t>(4), C.at<uint32_t>(5), C.at<uint32_t>(6), ctx->stream));
-    void* const h_out[5] = {v_right, v_left, shift, stored_right, stored_left};
-    for (int k = 0; k < 5 && !rc; k++) rc = C.up(2 + k, h_out[k], 4);
-    bool over = false;
-    if (rc || (rc = keyed_overflowed(ctx, ctx->tail, &over))) return rc;
-    if (over) for (int k = 0; k < 5; k++) memset(h_out[k], 0xFF, sizeof(uint32_t) * (size_t)nq);
-    return IM_OK;
+    return keyed_answers(ctx, ctx->tail, C, 2, {{v_right, 4}, {v_left, 4}, {shift, 4}, {stored_right, 4}, {stored_left, 4}});
 }
 
 // [pos][side] in, one launch, the five words per query and the two counters back, one wait; after an overflow every answer is "none"
@@ -1332,25 +1385,18 @@ int im_cliptail_consensus(im_ctx* ctx, int32_t tid, int32_t nq, const int32_t* p
                           uint32_t* len, uint32_t* planes, uint32_t* agree)
 {
     if (!ctx || nq < 0) return IM_E_ARG;
-    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
-    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->tail, &tid);
+    if (rc) return rc;
     if (min_cover < 1) { set_err(ctx, "im_cliptail_consensus: min_cover %d, must be >= 1", min_cover); return IM_E_ARG; }
     if (nq == 0) return IM_OK;
     if (!pos || !side || !entries || !len || !planes || !agree) return IM_E_ARG;
     for (int32_t q = 0; q < nq; q++) if (side[q] > 1) { set_err(ctx, "im_cliptail_consensus: query %d: side %d, must be 0 (right) or 1 (left)", q, (int)side[q]); return IM_E_ARG; }
     WsColumns C;                                                    // pos, side, entries, len, agree, planes (two words per query)
-    int rc = ws_columns(ctx, nq, 7, &C);
+    rc = ws_columns(ctx, nq, 7, &C);
     if (rc || (rc = C.down(0, pos, 4)) || (rc = C.down(1, side, 1))) return rc;
     HIP_TRY(ctx, im::launch_cliptail_consensus(nq, tid, C.at<int32_t>(0), C.at<uint8_t>(1), min_cover, ctx->h_len[tid], ctx->tail, C.at<uint32_t>(2),
                                                C.at<uint32_t>(3), C.at<uint32_t>(5), C.at<uint32_t>(4), ctx->stream));
-    bool over = false;
-    if ((rc = C.up(2, entries, 4)) || (rc = C.up(3, len, 4)) || (rc = C.up(4, agree, 4)) || (rc = C.up(5, planes, 8)) ||
-        (rc = keyed_overflowed(ctx, ctx->tail, &over))) return rc;
-    if (over) {
-        memset(entries, 0xFF, sizeof(uint32_t) * (size_t)nq); memset(len, 0xFF, sizeof(uint32_t) * (size_t)nq);
-        memset(agree, 0xFF, sizeof(uint32_t) * (size_t)nq); memset(planes, 0xFF, 2 * sizeof(uint32_t) * (size_t)nq);
-    }
-    return IM_OK;
+    return keyed_answers(ctx, ctx->tail, C, 2, {{entries, 4}, {len, 4}, {agree, 4}, {planes, 8}});
 }
 
 // ---- the peaks of either clip array, which the searches for pairs of piles start from ----------
@@ -1460,10 +1506,10 @@ static int sort_peak_lists(im_ctx* ctx, const PeakLists& P, void* d_list[4], std
 static int pile_pairs_arrays(im_ctx* ctx, const char* who, bool inverted, const ClipArrays& C, int32_t tid, int32_t min_reads, int32_t reach, int32_t min_len,
                              int32_t max_len, int32_t max_shift, int32_t min_verified, int32_t cap, uint8_t* side, void* const out[9], int32_t* n_found)
 {
-    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
-    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
-    int rc = peaks_args(ctx, who, min_reads, reach, cap);
+    int rc = keyed_ready(ctx, ctx->tail, nullptr);
     if (rc) return rc;
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    if ((rc = peaks_args(ctx, who, min_reads, reach, cap))) return rc;
     if (min_len < 1) { set_err(ctx, "%s: min_len %d, must be >= 1", who, min_len); return IM_E_ARG; }
     if (max_len < min_len) { set_err(ctx, "%s: max_len %d, must be >= min_len %d", who, max_len, min_len); return IM_E_ARG; }
     if (max_shift < 0 || max_shift > 32) { set_err(ctx, "%s: max_shift %d, must be 0 .. 32", who, max_shift); return IM_E_ARG; }
@@ -1550,56 +1596,26 @@ int im_clip_inverted(im_ctx* ctx, int32_t tid, int32_t min_reads, int32_t reach,
     return rc ? rc : pile_pairs_arrays(ctx, "im_clip_inverted", true, A, tid, min_reads, reach, min_len, max_len, max_shift, min_verified, cap, side, out, n_found);
 }
 
-int im_cliptail_reset(im_ctx* ctx, void* stream)
-{
-    if (!ctx || !ctx->tail.slots) return IM_E_ARG;
-    return keyed_reset(ctx, ctx->tail, stream);
-}
-
-int im_cliptail_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped)
-{
-    if (!ctx || !ctx->tail.slots || !stored || !dropped) return IM_E_ARG;
-    return keyed_stats(ctx, ctx->tail, stored, dropped);
-}
+int im_cliptail_reset(im_ctx* ctx, void* stream) { return keyed_reset(ctx, &im_ctx::tail, stream); }
+int im_cliptail_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped) { return keyed_stats(ctx, &im_ctx::tail, stored, dropped); }
 
 // ---- pair links: the read pairs of an abnormal orientation, counted between two windows (-M) ----------
 
-int im_pairlink_enable(im_ctx* ctx, int32_t min_mapq, int32_t log2_slots)
-{
-    if (!ctx) return IM_E_ARG;
-    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
-    const bool enabled = ctx->link.slots;
-    const int rc = keyed_enable(ctx, &im_ctx::link, "im_pairlink_enable", log2_slots);
-    if (rc) return rc;
-    if (enabled && (min_mapq != ctx->link_min_mapq || log2_slots != ctx->link.log2_slots)) {
-        set_err(ctx, "im_pairlink_enable: already enabled with min_mapq %d, log2_slots %d", ctx->link_min_mapq, ctx->link.log2_slots);
-        return IM_E_ARG;
-    }
-    ctx->link_min_mapq = min_mapq;
-    return IM_OK;
-}
+int im_pairlink_enable(im_ctx* ctx, int32_t min_mapq, int32_t log2_slots) { return keyed_enable(ctx, &im_ctx::link, nullptr, min_mapq, log2_slots); }
+int im_pairlink_reset(im_ctx* ctx, void* stream) { return keyed_reset(ctx, &im_ctx::link, stream); }
+int im_pairlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped) { return keyed_stats(ctx, &im_ctx::link, stored, dropped); }
 
-int im_dev_pairlink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
-{
-    if (!ctx || !recs) return IM_E_ARG;
-    if (!ctx->link.slots) { set_err(ctx, "im_pairlink_enable has not been called"); return IM_E_ARG; }
-    if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_pairlink_scatter(ref_dev(ctx), ctx->link_min_mapq, *recs, ctx->link, (hipStream_t)stream));
-    return IM_OK;
-}
+int im_dev_pairlink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream) { return link_scatter(ctx, &im_ctx::link, recs, stream, im::launch_pairlink_scatter); }
 
 // the host names the links: checked here, staged through the workspace, one lane inserts each, wait
 int im_pairlink_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, const int32_t* mpos, const uint8_t* kind)
 {
     if (!ctx || n < 0 || (n > 0 && (!pos || !mpos || !kind))) return IM_E_ARG;
-    if (!ctx->link.slots) { set_err(ctx, "im_pairlink_enable has not been called"); return IM_E_ARG; }
-    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    for (int32_t i = 0; i < n; i++)
-        if (kind[i] > 2) { set_err(ctx, "im_pairlink_add: link %d: kind %d, must be 0 (everted), 1 (forward) or 2 (reverse)", i, (int)kind[i]); return IM_E_ARG; }
+    int rc = keyed_ready(ctx, ctx->link, &tid);
+    if (rc || (rc = link_args(ctx, "im_pairlink_add", "link", kPairKinds, n, kind, nullptr, nullptr))) return rc;
     if (n == 0) return IM_OK;
     WsColumns C;                                                    // pos, mpos, kind
-    int rc = ws_columns(ctx, n, 3, &C);
+    rc = ws_columns(ctx, n, 3, &C);
     if (rc || (rc = C.down(0, pos, 4)) || (rc = C.down(1, mpos, 4)) || (rc = C.down(2, kind, 1))) return rc;
     HIP_TRY(ctx, im::launch_pairlink_add(n, tid, ctx->h_len[tid], C.at<int32_t>(0), C.at<int32_t>(1), C.at<uint8_t>(2), ctx->link, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1611,79 +1627,38 @@ int im_pairlink_count(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kind,
                       const int32_t* b1, int32_t min_sep, uint32_t* count_out)
 {
     if (!ctx || nq < 0) return IM_E_ARG;
-    if (!ctx->link.slots) { set_err(ctx, "im_pairlink_enable has not been called"); return IM_E_ARG; }
-    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->link, &tid);
+    if (rc) return rc;
     if (min_sep < 0) { set_err(ctx, "im_pairlink_count: min_sep %d, must be >= 0", min_sep); return IM_E_ARG; }
     if (nq == 0) return IM_OK;
     if (!kind || !a0 || !a1 || !b0 || !b1 || !count_out) return IM_E_ARG;
-    for (int32_t q = 0; q < nq; q++) {
-        if (kind[q] > 2) { set_err(ctx, "im_pairlink_count: query %d: kind %d, must be 0 (everted), 1 (forward) or 2 (reverse)", q, (int)kind[q]); return IM_E_ARG; }
-        // the wave walks one probe run per 256-base bucket of [a0, a1]: 257 at the most
-        if ((int64_t)a1[q] - (int64_t)a0[q] > 65535) { set_err(ctx, "im_pairlink_count: query %d: a1 - a0 = %lld, must be <= 65535", q, (long long)a1[q] - (long long)a0[q]); return IM_E_ARG; }
-    }
+    if ((rc = link_args(ctx, "im_pairlink_count", "query", kPairKinds, nq, kind, a0, a1))) return rc;
     WsColumns C;                                                    // a0, a1, b0, b1, kind, the counts
-    int rc = ws_columns(ctx, nq, 6, &C);
+    rc = ws_columns(ctx, nq, 6, &C);
     const int32_t* h_in[4] = {a0, a1, b0, b1};
     for (int k = 0; k < 4 && !rc; k++) rc = C.down(k, h_in[k], 4);
     if (rc || (rc = C.down(4, kind, 1))) return rc;
     HIP_TRY(ctx, im::launch_pairlink_count(nq, tid, C.at<uint8_t>(4), C.at<int32_t>(0), C.at<int32_t>(1), C.at<int32_t>(2), C.at<int32_t>(3), min_sep, ctx->h_len[tid],
                                            ctx->link, C.at<uint32_t>(5), ctx->stream));
-    bool over = false;
-    if ((rc = C.up(5, count_out, 4)) || (rc = keyed_overflowed(ctx, ctx->link, &over))) return rc;
-    if (over) memset(count_out, 0xFF, sizeof(uint32_t) * (size_t)nq);
-    return IM_OK;
-}
-
-int im_pairlink_reset(im_ctx* ctx, void* stream)
-{
-    if (!ctx || !ctx->link.slots) return IM_E_ARG;
-    return keyed_reset(ctx, ctx->link, stream);
-}
-
-int im_pairlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped)
-{
-    if (!ctx || !ctx->link.slots || !stored || !dropped) return IM_E_ARG;
-    return keyed_stats(ctx, ctx->link, stored, dropped);
+    return keyed_answers(ctx, ctx->link, C, 5, {{count_out, 4}});
 }
 
 // ---- mate links: the read pairs whose mate lies on another contig, asked where the mates of a window lie (-T) ----------
 
-int im_matelink_enable(im_ctx* ctx, int32_t min_mapq, int32_t log2_slots)
-{
-    if (!ctx) return IM_E_ARG;
-    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
-    const bool enabled = ctx->mate.slots;
-    const int rc = keyed_enable(ctx, &im_ctx::mate, "im_matelink_enable", log2_slots);
-    if (rc) return rc;
-    if (enabled && (min_mapq != ctx->mate_min_mapq || log2_slots != ctx->mate.log2_slots)) {
-        set_err(ctx, "im_matelink_enable: already enabled with min_mapq %d, log2_slots %d", ctx->mate_min_mapq, ctx->mate.log2_slots);
-        return IM_E_ARG;
-    }
-    ctx->mate_min_mapq = min_mapq;
-    return IM_OK;
-}
-
-int im_dev_matelink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
-{
-    if (!ctx || !recs) return IM_E_ARG;
-    if (!ctx->mate.slots) { set_err(ctx, "im_matelink_enable has not been called"); return IM_E_ARG; }
-    if (recs->n < 0) { set_err(ctx, "negative record count"); return IM_E_ARG; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, im::launch_matelink_scatter(ref_dev(ctx), ctx->mate_min_mapq, *recs, ctx->mate, (hipStream_t)stream));
-    return IM_OK;
-}
+int im_matelink_enable(im_ctx* ctx, int32_t min_mapq, int32_t log2_slots) { return keyed_enable(ctx, &im_ctx::mate, nullptr, min_mapq, log2_slots); }
+int im_matelink_reset(im_ctx* ctx, void* stream) { return keyed_reset(ctx, &im_ctx::mate, stream); }
+int im_matelink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped) { return keyed_stats(ctx, &im_ctx::mate, stored, dropped); }
+int im_dev_matelink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream) { return link_scatter(ctx, &im_ctx::mate, recs, stream, im::launch_matelink_scatter); }
 
 // the host names the links: checked here, staged through the workspace, one lane inserts each, wait
 int im_matelink_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, const int32_t* mtid, const int32_t* mpos, const uint8_t* kind)
 {
     if (!ctx || n < 0 || (n > 0 && (!pos || !mtid || !mpos || !kind))) return IM_E_ARG;
-    if (!ctx->mate.slots) { set_err(ctx, "im_matelink_enable has not been called"); return IM_E_ARG; }
-    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
-    for (int32_t i = 0; i < n; i++)
-        if (kind[i] > 3) { set_err(ctx, "im_matelink_add: link %d: kind %d, must be 0 .. 3 (read reverse | mate reverse << 1)", i, (int)kind[i]); return IM_E_ARG; }
+    int rc = keyed_ready(ctx, ctx->mate, &tid);
+    if (rc || (rc = link_args(ctx, "im_matelink_add", "link", kMateKinds, n, kind, nullptr, nullptr))) return rc;
     if (n == 0) return IM_OK;
     WsColumns C;                                                    // pos, mtid, mpos, kind
-    int rc = ws_columns(ctx, n, 4, &C);
+    rc = ws_columns(ctx, n, 4, &C);
     if (rc || (rc = C.down(0, pos, 4)) || (rc = C.down(1, mtid, 4)) || (rc = C.down(2, mpos, 4)) || (rc = C.down(3, kind, 1))) return rc;
     HIP_TRY(ctx, im::launch_matelink_add(ref_dev(ctx), n, tid, C.at<int32_t>(0), C.at<int32_t>(1), C.at<int32_t>(2), C.at<uint8_t>(3), ctx->mate, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1695,38 +1670,17 @@ int im_matelink_partner(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kin
                         int32_t* mtid_out, uint32_t* n_partner, int32_t* lo, int32_t* hi)
 {
     if (!ctx || nq < 0) return IM_E_ARG;
-    if (!ctx->mate.slots) { set_err(ctx, "im_matelink_enable has not been called"); return IM_E_ARG; }
-    if (tid < 0 || tid >= ctx->n_contigs) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->mate, &tid);
+    if (rc) return rc;
     if (nq == 0) return IM_OK;
     if (!kind || !a0 || !a1 || !n_links || !mtid_out || !n_partner || !lo || !hi) return IM_E_ARG;
-    for (int32_t q = 0; q < nq; q++) {
-        if (kind[q] > 3) { set_err(ctx, "im_matelink_partner: query %d: kind %d, must be 0 .. 3 (read reverse | mate reverse << 1)", q, (int)kind[q]); return IM_E_ARG; }
-        // the wave walks one probe run per 256-base bucket of [a0, a1]: 257 at the most
-        if ((int64_t)a1[q] - (int64_t)a0[q] > 65535) { set_err(ctx, "im_matelink_partner: query %d: a1 - a0 = %lld, must be <= 65535", q, (long long)a1[q] - (long long)a0[q]); return IM_E_ARG; }
-    }
+    if ((rc = link_args(ctx, "im_matelink_partner", "query", kMateKinds, nq, kind, a0, a1))) return rc;
     WsColumns C;                                                    // a0, a1, kind, then the five answers
-    int rc = ws_columns(ctx, nq, 8, &C);
+    rc = ws_columns(ctx, nq, 8, &C);
     if (rc || (rc = C.down(0, a0, 4)) || (rc = C.down(1, a1, 4)) || (rc = C.down(2, kind, 1))) return rc;
     HIP_TRY(ctx, im::launch_matelink_partner(nq, tid, C.at<uint8_t>(2), C.at<int32_t>(0), C.at<int32_t>(1), ctx->h_len[tid], ctx->mate, C.at<uint32_t>(3),
                                              C.at<int32_t>(4), C.at<uint32_t>(5), C.at<int32_t>(6), C.at<int32_t>(7), ctx->stream));
-    void* const h_out[5] = {n_links, mtid_out, n_partner, lo, hi};
-    for (int k = 0; k < 5 && !rc; k++) rc = C.up(3 + k, h_out[k], 4);
-    bool over = false;
-    if (rc || (rc = keyed_overflowed(ctx, ctx->mate, &over))) return rc;
-    if (over) for (int k = 0; k < 5; k++) memset(h_out[k], 0xFF, sizeof(uint32_t) * (size_t)nq);
-    return IM_OK;
-}
-
-int im_matelink_reset(im_ctx* ctx, void* stream)
-{
-    if (!ctx || !ctx->mate.slots) return IM_E_ARG;
-    return keyed_reset(ctx, ctx->mate, stream);
-}
-
-int im_matelink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped)
-{
-    if (!ctx || !ctx->mate.slots || !stored || !dropped) return IM_E_ARG;
-    return keyed_stats(ctx, ctx->mate, stored, dropped);
+    return keyed_answers(ctx, ctx->mate, C, 3, {{n_links, 4}, {mtid_out, 4}, {n_partner, 4}, {lo, 4}, {hi, 4}});
 }
 
 // six columns in, one launch, the five answers and the two counters back, one wait; after an overflow every answer is "none"
@@ -1734,7 +1688,8 @@ int im_cliptail_junction(im_ctx* ctx, int32_t nq, const int32_t* tid1, const int
                          const uint8_t* side2, int32_t max_shift, uint32_t* v1, uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2)
 {
     if (!ctx || nq < 0) return IM_E_ARG;
-    if (!ctx->tail.slots) { set_err(ctx, "im_cliptail_enable has not been called"); return IM_E_ARG; }
+    int rc = keyed_ready(ctx, ctx->tail, nullptr);
+    if (rc) return rc;
     if (max_shift < 0 || max_shift > 32) { set_err(ctx, "im_cliptail_junction: max_shift %d, must be 0 .. 32", max_shift); return IM_E_ARG; }
     if (nq == 0) return IM_OK;
     if (!tid1 || !p1 || !side1 || !tid2 || !p2 || !side2 || !v1 || !v2 || !shift || !stored1 || !stored2) return IM_E_ARG;
@@ -1746,7 +1701,7 @@ int im_cliptail_junction(im_ctx* ctx, int32_t nq, const int32_t* tid1, const int
         if (side1[q] > 1 || side2[q] > 1) { set_err(ctx, "im_cliptail_junction: query %d: sides %d and %d, must be 0 (right) or 1 (left)", q, (int)side1[q], (int)side2[q]); return IM_E_ARG; }
     }
     WsColumns C;                                                    // tid1, p1, tid2, p2, side1, side2, then the five answers
-    int rc = ws_columns(ctx, nq, 11, &C);
+    rc = ws_columns(ctx, nq, 11, &C);
     const int32_t* h_in[4] = {tid1, p1, tid2, p2};
     for (int k = 0; k < 4 && !rc; k++) rc = C.down(k, h_in[k], 4);
     if (rc || (rc = C.down(4, side1, 1)) || (rc = C.down(5, side2, 1))) return rc;
@@ -1755,12 +1710,7 @@ int im_cliptail_junction(im_ctx* ctx, int32_t nq, const int32_t* tid1, const int
     A.side1 = C.at<uint8_t>(4); A.side2 = C.at<uint8_t>(5); A.ref = ref_dev(ctx); A.tab = ctx->tail;
     A.v1 = C.at<uint32_t>(6); A.v2 = C.at<uint32_t>(7); A.shift = C.at<int32_t>(8); A.stored1 = C.at<uint32_t>(9); A.stored2 = C.at<uint32_t>(10);
     HIP_TRY(ctx, im::launch_cliptail_junction(A, ctx->stream));
-    void* const h_out[5] = {v1, v2, shift, stored1, stored2};
-    for (int k = 0; k < 5 && !rc; k++) rc = C.up(6 + k, h_out[k], 4);
-    bool over = false;
-    if (rc || (rc = keyed_overflowed(ctx, ctx->tail, &over))) return rc;
-    if (over) for (int k = 0; k < 5; k++) memset(h_out[k], 0xFF, sizeof(uint32_t) * (size_t)nq);
-    return IM_OK;
+    return keyed_answers(ctx, ctx->tail, C, 6, {{v1, 4}, {v2, 4}, {shift, 4}, {stored1, 4}, {stored2, 4}});
 }
 
 int im_support_batch(im_ctx* ctx, int32_t n, const uint8_t* targets, const int64_t* t_off,

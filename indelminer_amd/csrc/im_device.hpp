@@ -139,7 +139,7 @@ hipError_t launch_clip_facing(const int32_t* right, const int32_t* left, int64_t
 // written, in no particular order
 hipError_t launch_clip_peaks(const int32_t* arr, int64_t clen, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count,
                              uint32_t* n_found, hipStream_t stream);
-// The keyed table behind the clip tails (-V) and the pair links (-M), an allocation each; im_keyed.hpp has its definition.  slots:
+// The keyed table behind the clip tails (-V), the pair links (-M) and the mate links (-T), an allocation each; im_keyed.hpp has its definition.  slots:
 // 2^log2_slots pairs (key, payload) of 64-bit words, zeros = empty; counters[0]: inserts asked for, counters[1]: those dropped because
 // half of the slots were taken
 struct KeyedTable {
@@ -183,7 +183,7 @@ struct TailPairsArgs {
     uint32_t* n_found;
 };
 hipError_t launch_cliptail_pairs(bool inverted, TailPairsArgs A, hipStream_t stream);
-// im_pairlink.hip: the read pairs of an abnormal orientation in a keyed table of its own (-M)
+// im_links.hip: the read pairs of an abnormal orientation in a keyed table of its own (-M)
 // the records that are a link under the record rule (include/indelminer_amd.h, "Pair links") -> one entry each
 hipError_t launch_pairlink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream);
 // one entry per host-named (pos, mpos, kind 0 .. 2) of contig tid; a position outside [0, clen] drops the link
@@ -193,7 +193,7 @@ hipError_t launch_pairlink_add(int32_t n, int32_t tid, int64_t clen, const int32
 // in the first, mpos in the second and mpos - pos >= min_sep; the caller holds a1 - a0 to 65 535
 hipError_t launch_pairlink_count(int32_t nq, int32_t tid, const uint8_t* kind, const int32_t* a0, const int32_t* a1, const int32_t* b0,
                                  const int32_t* b1, int32_t min_sep, int64_t clen, const KeyedTable& tab, uint32_t* count, hipStream_t stream);
-// im_matelink.hip: the read pairs whose mate lies on another contig in a keyed table of its own (-T)
+// im_links.hip: the read pairs whose mate lies on another contig in a keyed table of its own (-T)
 // the records that are a link under the record rule (include/indelminer_amd.h, "Mate links") -> one entry each
 hipError_t launch_matelink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream);
 // one entry per host-named (pos, mtid, mpos, kind 0 .. 3) of contig tid; a link that fails the rule's range checks is dropped

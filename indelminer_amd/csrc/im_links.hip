@@ -1,0 +1,394 @@
+// im_links.hip -- the two families of read pairs kept as links in keyed tables of their own (gfx950):
+//   the PAIR LINKS (-M): the read pairs whose orientation says "junction", counted between two windows.  The definition is in
+//     include/indelminer_amd.h (seam 5, "Pair links"); DESIGN.md 4.5j has the cost.
+//   the MATE LINKS (-T): the read pairs whose mate lies on ANOTHER contig, asked where the mates of the reads around a position lie.
+//     The definition is in include/indelminer_amd.h (seam 5, "Mate links"); DESIGN.md 4.5k has the cost.
+//
+// PAIR LINKS  A delivered record that is the leftmost of a pair on one contig, both reads mapped, neither read in the normal orientation
+// (forward in front of reverse), stores ONE LINK (tid, kind, pos, mpos): kind 0 EVERTED (this read reverse, its mate forward: a tandem
+// duplication's pairs), 1 FORWARD (both forward: an inversion's left junction), 2 REVERSE (both reverse: its right junction).
+//
+// MATE LINKS  A delivered record that is paired, both reads mapped, its mate on another contig, stores ONE LINK (tid, kind, pos, mtid,
+// mpos) at its own contig: kind = r | m << 1, r = this read reverse, m = its mate reverse.  Both reads of a pair store one each.
+//
+// THE TABLES are keyed tables of im_keyed.hpp (slots, tickets, claim, walk), an allocation each, with
+//   word 0   the key, BOTH FAMILIES': bit 63 set (an empty slot is 0) | tid << 26 | (pos >> 8) << 2 | kind   (tid < 2^24, pos < 2^31)
+//   word 1   the payload, the family's own:   pair links  pos | mpos << 32        mate links  pos & 255 | mtid << 8 | mpos << 32
+// The whole key enters the hash: every link of one (tid, 256-base bucket, kind) lies on one probe run.
+//
+// SHARED: the key, the bucket, the block sizes, the scatter (link_scatter<Rule>: the front of the record rule, the tickets, the insert)
+// and the interval and the bucket loop of the queries (link_clip, link_walk).  PER FAMILY: the payload, the rest of the record rule, the add kernel's range checks
+// and what a query does with the links it is handed.
+//
+//   pairlink_scatter, matelink_scatter   one lane per delivered record; the lanes that hold a link insert it, on tickets their
+//                                        workgroup draws with one atomic add
+//   pairlink_add, matelink_add           one lane per link, for callers that name the events themselves
+//   pairlink_count     one wave per query (kind, a0, a1, b0, b1): the links with pos in [a0, a1], mpos in [b0, b1], mpos - pos >= min_sep
+//   matelink_partner   one wave per query (kind, a0, a1): the links with pos in [a0, a1] vote for the cell (mtid, mpos >> 10) of their
+//                      mate in a table in LDS; the pair of neighbouring cells with the most links wins
+
+#include "im_keyed.hpp"
+#include "im_rg.hpp"
+#include "im_wave.hpp"
+
+namespace im {
+namespace {
+
+constexpr int kLinkBlock = 1024;      // records of a scatter workgroup: one ticket draw each
+constexpr int kLinkWaveBlock = 256;   // threads of the add and query kernels
+constexpr int kLinkBucketShift = 8;   // a bucket is 256 bases: a query window of 1 000 bases walks 4 or 5 probe runs
+constexpr int kMateCellShift = 10;    // a cell is 1 024 bases of the mate's contig
+constexpr int kMateCells = IM_MATELINK_CELLS;
+static_assert(kMateCells == 256, "a cell's slot is the top 8 bits of its hash, and a lane owns kMateCells / 64 slots");
+
+__device__ __forceinline__ uint64_t link_key(int32_t tid, int64_t bucket, uint32_t kind)
+{
+    return kKeyedUsed | ((uint64_t)(uint32_t)tid << 26) | ((uint64_t)bucket << 2) | kind;
+}
+
+__device__ __forceinline__ uint64_t pair_payload(int64_t pos, int64_t mpos) { return (uint64_t)(uint32_t)pos | ((uint64_t)(uint32_t)mpos << 32); }
+
+__device__ __forceinline__ uint64_t mate_payload(int64_t pos, int32_t mtid, int64_t mpos)
+{
+    return (uint64_t)((uint32_t)pos & 255u) | ((uint64_t)(uint32_t)mtid << 8) | ((uint64_t)(uint32_t)mpos << 32);
+}
+
+struct LinkScatterArgs {
+    im_dev_records recs;
+    const int32_t* len;
+    int32_t n_contigs, min_mapq;
+    KeyedTable tab;
+};
+
+// The record rules, on the 32-byte core alone.  A rule says whether a record that has passed the front both share (link_of_record)
+// stores a link; *kind, *payload: what it stores, under the key of (r.tid, r.pos's bucket, *kind).  The front has held r.tid to
+// [0, n_contigs): len[r.tid] may be read; len[r.mtid] only behind the rule's own check of r.mtid.
+struct PairRule {
+    static __device__ __forceinline__ bool link(const LinkScatterArgs& A, const RecView& r, uint32_t* kind, uint64_t* payload)
+    {
+        if (r.mtid != r.tid) return false;
+        if (!(r.pos < r.mpos || (r.pos == r.mpos && (r.flag & 0x40u)))) return false;      // each pair once, at its leftmost record
+        const uint32_t rev = (r.flag >> 4) & 1u, mrev = (r.flag >> 5) & 1u;
+        if (!rev && mrev) return false;                                 // the normal orientation is no link, whatever its insert size
+        if (r.pos < 0 || r.mpos > A.len[r.tid]) return false;          // pos <= mpos behind the leftmost test: both lie in [0, len[tid]]
+        *kind = rev ? (mrev ? 2u : 0u) : 1u;
+        *payload = pair_payload(r.pos, r.mpos);
+        return true;
+    }
+};
+
+struct MateRule {
+    static __device__ __forceinline__ bool link(const LinkScatterArgs& A, const RecView& r, uint32_t* kind, uint64_t* payload)
+    {
+        if (r.mtid < 0 || r.mtid >= A.n_contigs || r.mtid == r.tid) return false;
+        if (r.pos < 0 || r.pos > A.len[r.tid] || r.mpos < 0 || r.mpos > A.len[r.mtid]) return false;
+        *kind = ((r.flag >> 4) & 1u) | (((r.flag >> 5) & 1u) << 1);
+        *payload = mate_payload(r.pos, r.mtid, r.mpos);
+        return true;
+    }
+};
+
+// Whether record i stores a link; *key, *payload: what it stores.  The front of both rules: a whole core, paired, this read and its
+// mate mapped, primary, no duplicate, no failure, on a contig of the reference, at min_mapq or above.
+template <class Rule>
+__device__ __forceinline__ bool link_of_record(const LinkScatterArgs& A, int64_t i, uint64_t* key, uint64_t* payload)
+{
+    if (i >= A.recs.n) return false;
+    const RecView r = view_record(A.recs.raw, A.recs.rec_off[i], A.recs.rec_off[i + 1]);
+    if (r.len < 32u) return false;
+    if ((int32_t)r.mapq < A.min_mapq) return false;
+    if (!(r.flag & 0x1u) || (r.flag & (0x4u | 0x8u | 0x100u | 0x200u | 0x400u | 0x800u))) return false;
+    if (r.tid < 0 || r.tid >= A.n_contigs) return false;
+    uint32_t kind;
+    if (!Rule::link(A, r, &kind, payload)) return false;
+    *key = link_key(r.tid, r.pos >> kLinkBucketShift, kind);
+    return true;
+}
+
+// One lane per record; one ticket draw per workgroup (keyed_block_tickets has the reason); a workgroup without a link -- most of
+// them -- ends there.
+template <class Rule>
+__device__ __forceinline__ void link_scatter(const LinkScatterArgs& A)
+{
+    uint64_t key = 0, payload = 0;
+    const bool has = link_of_record<Rule>(A, (int64_t)blockIdx.x * kLinkBlock + threadIdx.x, &key, &payload);
+    unsigned long long ticket;
+    if (!keyed_block_tickets<kLinkBlock, 1>(A.tab, has ? 1u : 0u, &ticket)) return;
+    if (has && keyed_admit(A.tab, ticket)) keyed_place(A.tab, keyed_home(key, A.tab.log2_slots), key, payload);
+}
+
+__global__ __launch_bounds__(kLinkBlock) void pairlink_scatter_kernel(LinkScatterArgs A) { link_scatter<PairRule>(A); }
+__global__ __launch_bounds__(kLinkBlock) void matelink_scatter_kernel(LinkScatterArgs A) { link_scatter<MateRule>(A); }
+
+// for callers that name the events themselves: one lane per link; positions outside [0, clen] are dropped (no ticket)
+__global__ __launch_bounds__(kLinkWaveBlock) void pairlink_add_kernel(int32_t n, int32_t tid, int64_t clen, const int32_t* __restrict__ pos,
+                                                                      const int32_t* __restrict__ mpos, const uint8_t* __restrict__ kind, KeyedTable tab)
+{
+    const int64_t i = (int64_t)blockIdx.x * kLinkWaveBlock + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = pos[i], m = mpos[i];
+    if (p < 0 || p > clen || m < 0 || m > clen) return;
+    const uint64_t key = link_key(tid, p >> kLinkBucketShift, kind[i]);
+    keyed_insert(tab, keyed_home(key, tab.log2_slots), key, pair_payload(p, m));
+}
+
+// the same for the mate links; a link that fails the rule's range checks is dropped (no ticket)
+__global__ __launch_bounds__(kLinkWaveBlock) void matelink_add_kernel(int32_t n, int32_t tid, const int32_t* __restrict__ len, int32_t n_contigs,
+                                                                      const int32_t* __restrict__ pos, const int32_t* __restrict__ mtid,
+                                                                      const int32_t* __restrict__ mpos, const uint8_t* __restrict__ kind, KeyedTable tab)
+{
+    const int64_t i = (int64_t)blockIdx.x * kLinkWaveBlock + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = pos[i], m = mpos[i];
+    const int32_t mt = mtid[i];
+    if (mt < 0 || mt >= n_contigs || mt == tid) return;
+    if (p < 0 || p > len[tid] || m < 0 || m > len[mt]) return;
+    const uint64_t key = link_key(tid, p >> kLinkBucketShift, kind[i]);
+    keyed_insert(tab, keyed_home(key, tab.log2_slots), key, mate_payload(p, mt, m));
+}
+
+// What both queries do with an interval, by the whole wave.  link_clip: [*lo, *hi] clipped to [0, clen], in place; whether anything is
+// left of it.  link_walk, for a pos interval that link_clip has left something of: for every bucket of it (at most 257: the caller
+// holds a1 - a0 to 65 535) the wave walks the bucket's probe run (keyed_walk) for the slots whose key is the bucket's, and
+// each(has, bucket, payload) is called for every batch that holds one: has says whether this lane's slot does, and payload is that
+// slot's (0 without).  Every branch is on values the whole wave shares; both loops are bounded, by the bucket count and the slot count.
+__device__ __forceinline__ bool link_clip(int64_t* lo, int64_t* hi, int64_t clen)
+{
+    *lo = *lo < 0 ? 0 : *lo;
+    *hi = *hi > clen ? clen : *hi;
+    return *lo <= *hi;
+}
+
+template <class Each>
+__device__ __forceinline__ void link_walk(const KeyedTable& T, int32_t tid, uint32_t kind, int64_t a0, int64_t a1, int lane, Each each)
+{
+    for (int64_t bucket = a0 >> kLinkBucketShift; bucket <= (a1 >> kLinkBucketShift); bucket++) {
+        const uint64_t want = link_key(tid, bucket, kind);
+        (void)keyed_walk(T, keyed_home(want, T.log2_slots), [want](uint64_t key) { return key == want; }, lane,
+                         [&](bool has, uint64_t, uint64_t s) { each(has, bucket, has ? T.slots[2ull * s + 1ull] : 0ull); });
+    }
+}
+
+struct LinkCountArgs {
+    int32_t nq, tid, min_sep;
+    const uint8_t* kind;
+    const int32_t* a0;
+    const int32_t* a1;
+    const int32_t* b0;
+    const int32_t* b1;
+    int64_t clen;
+    KeyedTable tab;
+    uint32_t* count;
+};
+
+// One wave per query.  Both intervals are clipped to [0, clen].  A lane's link counts when its payload passes the three tests; the wave
+// sums by ballot and popcount.
+__global__ __launch_bounds__(kLinkWaveBlock) void pairlink_count_kernel(LinkCountArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int q = wave; q < A.nq; q += nwaves) {
+        int64_t a0 = A.a0[q], a1 = A.a1[q], b0 = A.b0[q], b1 = A.b1[q];
+        const uint32_t kind = A.kind[q];
+        const bool in_a = link_clip(&a0, &a1, A.clen), in_b = link_clip(&b0, &b1, A.clen);
+        uint32_t n = 0;
+        if (in_a && in_b) {
+            link_walk(A.tab, A.tid, kind, a0, a1, lane, [&](bool has, int64_t, uint64_t payload) {
+                const int64_t pos = (int64_t)(uint32_t)payload, mpos = (int64_t)(uint32_t)(payload >> 32);
+                const bool counts = has && pos >= a0 && pos <= a1 && mpos >= b0 && mpos <= b1 && mpos - pos >= (int64_t)A.min_sep;
+                n += (uint32_t)__builtin_popcountll(__ballot(counts));
+            });
+        }
+        if (lane == 0) A.count[q] = n;
+    }
+}
+
+// The cells of one query, one table per wave: open addressing over kMateCells slots of 20 bytes, ALL of which may be taken -- a 257th
+// distinct cell finds no slot on its way round, and that is the cap of the definition.
+//   key   bit 63 set (an empty slot is 0) | mtid << 32 | mpos >> 10: the right neighbour of a cell is key + 1 (mpos >> 10 < 2^21)
+struct MateCellTable {
+    unsigned long long key[kMateCells];
+    uint32_t cnt[kMateCells], lo[kMateCells], hi[kMateCells];
+};
+static_assert(sizeof(MateCellTable) == 20 * kMateCells, "20 bytes a cell: 5 KB per wave");
+
+__device__ __forceinline__ uint32_t cell_home(unsigned long long cell) { return (uint32_t)((cell * kKeyedHashMul) >> 56); }
+
+// The slot that holds `cell`, or kMateCells when the table does not: the lanes with want set probe from the cell's home until they see
+// the cell or an empty slot; the loop is the wave's, bounded by the slot count.
+__device__ __forceinline__ uint32_t cell_find(const MateCellTable& C, unsigned long long cell, bool want)
+{
+    uint32_t s = cell_home(cell), found = (uint32_t)kMateCells;
+    for (int step = 0; step < kMateCells; step++) {
+        if (!__ballot(want)) break;                                 // wave-uniform
+        if (want) {
+            const unsigned long long k = C.key[s];
+            if (k == cell) { found = s; want = false; }
+            else if (k == 0ull) want = false;
+            else s = (s + 1u) & (uint32_t)(kMateCells - 1);
+        }
+    }
+    return found;
+}
+
+struct MatePartnerArgs {
+    int32_t nq, tid;
+    const uint8_t* kind;
+    const int32_t* a0;
+    const int32_t* a1;
+    int64_t clen;
+    KeyedTable tab;
+    uint32_t* n_links;
+    int32_t* mtid;
+    uint32_t* n_partner;
+    int32_t* lo;
+    int32_t* hi;
+};
+
+// One wave per query.  A lane whose slot holds a link of the interval (link_walk) claims the link's cell in the wave's LDS table with a
+// 64-bit compare-and-swap and adds the link to the cell's count, minimum and maximum with LDS atomics: sums, minima and maxima, so
+// nothing depends on the order of arrival, and a cell finds no slot only when 256 others hold them all.  Then every lane takes four
+// slots: an occupied one looks up its right neighbour, its score is the two counts, and the wave reduces (score, the smallest cell key
+// among equals -- mtid in the high word, the cell in the low one).  A cell (mtid, c) that holds no link while (mtid, c + 1) does need
+// not stand: its links are those of (mtid, c + 1) or fewer, and the answer names links, not c.  Every branch is on values the whole
+// wave shares; every loop is bounded, by the bucket count, the slot count or kMateCells.  The LDS one lane writes and another reads is
+// ordered by wave_lds_sync (im_wave.hpp): LDS executes a wave's instructions in order.
+__global__ __launch_bounds__(kLinkWaveBlock) void matelink_partner_kernel(MatePartnerArgs A)
+{
+    __shared__ MateCellTable s_cells[kLinkWaveBlock / 64];
+    const int lane = threadIdx.x & 63;
+    MateCellTable& C = s_cells[threadIdx.x >> 6];
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int q = wave; q < A.nq; q += nwaves) {
+        int64_t a0 = A.a0[q], a1 = A.a1[q];
+        const uint32_t kind = A.kind[q];
+        const bool any = link_clip(&a0, &a1, A.clen);
+#pragma unroll
+        for (int j = 0; j < kMateCells / 64; j++) {
+            const int s = lane + 64 * j;
+            C.key[s] = 0ull; C.cnt[s] = 0u; C.lo[s] = 0xFFFFFFFFu; C.hi[s] = 0u;
+        }
+        wave_lds_sync();
+        uint32_t n = 0;
+        bool over = false;
+        if (any) link_walk(A.tab, A.tid, kind, a0, a1, lane, [&](bool has, int64_t bucket, uint64_t payload) {
+            const int64_t pos = (bucket << kLinkBucketShift) | (int64_t)(payload & 255ull);
+            bool pending = has && pos >= a0 && pos <= a1;
+            n += (uint32_t)__builtin_popcountll(__ballot(pending));
+            const uint32_t mpos = (uint32_t)(payload >> 32);
+            const unsigned long long cell = kKeyedUsed | ((unsigned long long)(((uint32_t)payload >> 8) & 0xFFFFFFu) << 32) | (mpos >> kMateCellShift);
+            uint32_t c = cell_home(cell);
+            for (int step = 0; step < kMateCells; step++) {
+                if (!__ballot(pending)) break;              // wave-uniform
+                if (pending) {
+                    const unsigned long long prev = atomicCAS(&C.key[c], 0ull, cell);
+                    if (prev == 0ull || prev == cell) {
+                        atomicAdd(&C.cnt[c], 1u); atomicMin(&C.lo[c], mpos); atomicMax(&C.hi[c], mpos);
+                        pending = false;
+                    } else {
+                        c = (c + 1u) & (uint32_t)(kMateCells - 1);
+                    }
+                }
+            }
+            over = over || __ballot(pending) != 0ull;
+        });
+        wave_lds_sync();
+        // this lane's best of its four slots: the larger score, the smaller cell key among equals
+        uint32_t best_score = 0;
+        unsigned long long best_cell = ~0ull;
+#pragma unroll
+        for (int j = 0; j < kMateCells / 64; j++) {
+            const int s = lane + 64 * j;
+            const unsigned long long cell = C.key[s];
+            const uint32_t right = cell_find(C, cell + 1ull, cell != 0ull);
+            const uint32_t score = cell != 0ull ? C.cnt[s] + (right < (uint32_t)kMateCells ? C.cnt[right] : 0u) : 0u;
+            if (score > best_score || (score == best_score && score != 0u && cell < best_cell)) { best_score = score; best_cell = cell; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t sc = (uint32_t)__shfl_xor((int)best_score, o);
+            const uint32_t chi = (uint32_t)__shfl_xor((int)(uint32_t)(best_cell >> 32), o), clo = (uint32_t)__shfl_xor((int)(uint32_t)best_cell, o);
+            const unsigned long long cell = ((unsigned long long)chi << 32) | clo;
+            if (sc > best_score || (sc == best_score && cell < best_cell)) { best_score = sc; best_cell = cell; }
+        }
+        // the winner's links: its own cell and the right neighbour, looked up by the whole wave (one address: a broadcast)
+        int32_t mtid = -1, lo = 0, hi = 0;
+        uint32_t n_partner = 0;
+        if (over) {
+            mtid = -2;
+        } else if (best_score != 0u) {                              // wave-uniform
+            const uint32_t own = cell_find(C, best_cell, true), right = cell_find(C, best_cell + 1ull, true);
+            uint32_t l = 0xFFFFFFFFu, h = 0u;
+            if (own < (uint32_t)kMateCells) { l = C.lo[own]; h = C.hi[own]; }
+            if (right < (uint32_t)kMateCells) { l = l < C.lo[right] ? l : C.lo[right]; h = h > C.hi[right] ? h : C.hi[right]; }
+            mtid = (int32_t)((uint32_t)(best_cell >> 32) & 0xFFFFFFu); n_partner = best_score; lo = (int32_t)l; hi = (int32_t)h;
+        }
+        if (lane == 0) { A.n_links[q] = n; A.mtid[q] = mtid; A.n_partner[q] = n_partner; A.lo[q] = lo; A.hi[q] = hi; }
+        wave_lds_sync();                                            // the next query clears what this one has read
+    }
+}
+
+template <class Kernel>
+hipError_t launch_link_scatter(Kernel kernel, const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)
+{
+    if (recs.n <= 0) return hipSuccess;
+    LinkScatterArgs A;
+    A.recs = recs; A.len = ref.len; A.n_contigs = ref.n_contigs; A.min_mapq = min_mapq; A.tab = tab;
+    hipLaunchKernelGGL(kernel, dim3((recs.n + kLinkBlock - 1) / kLinkBlock), dim3(kLinkBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_pairlink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)
+{
+    return launch_link_scatter(pairlink_scatter_kernel, ref, min_mapq, recs, tab, stream);
+}
+
+hipError_t launch_matelink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)
+{
+    return launch_link_scatter(matelink_scatter_kernel, ref, min_mapq, recs, tab, stream);
+}
+
+hipError_t launch_pairlink_add(int32_t n, int32_t tid, int64_t clen, const int32_t* pos, const int32_t* mpos, const uint8_t* kind,
+                               const KeyedTable& tab, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pairlink_add_kernel, dim3((n + kLinkWaveBlock - 1) / kLinkWaveBlock), dim3(kLinkWaveBlock), 0, stream, n, tid, clen, pos, mpos, kind, tab);
+    return hipGetLastError();
+}
+
+hipError_t launch_matelink_add(const RefDev& ref, int32_t n, int32_t tid, const int32_t* pos, const int32_t* mtid, const int32_t* mpos,
+                               const uint8_t* kind, const KeyedTable& tab, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(matelink_add_kernel, dim3((n + kLinkWaveBlock - 1) / kLinkWaveBlock), dim3(kLinkWaveBlock), 0, stream, n, tid, ref.len, ref.n_contigs,
+                       pos, mtid, mpos, kind, tab);
+    return hipGetLastError();
+}
+
+hipError_t launch_pairlink_count(int32_t nq, int32_t tid, const uint8_t* kind, const int32_t* a0, const int32_t* a1, const int32_t* b0,
+                                 const int32_t* b1, int32_t min_sep, int64_t clen, const KeyedTable& tab, uint32_t* count, hipStream_t stream)
+{
+    if (nq <= 0) return hipSuccess;
+    LinkCountArgs A;
+    A.nq = nq; A.tid = tid; A.min_sep = min_sep; A.kind = kind; A.a0 = a0; A.a1 = a1; A.b0 = b0; A.b1 = b1; A.clen = clen; A.tab = tab; A.count = count;
+    hipLaunchKernelGGL(pairlink_count_kernel, dim3(wave_grid(nq)), dim3(kLinkWaveBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_matelink_partner(int32_t nq, int32_t tid, const uint8_t* kind, const int32_t* a0, const int32_t* a1, int64_t clen,
+                                   const KeyedTable& tab, uint32_t* n_links, int32_t* mtid, uint32_t* n_partner, int32_t* lo, int32_t* hi,
+                                   hipStream_t stream)
+{
+    if (nq <= 0) return hipSuccess;
+    MatePartnerArgs A;
+    A.nq = nq; A.tid = tid; A.kind = kind; A.a0 = a0; A.a1 = a1; A.clen = clen; A.tab = tab;
+    A.n_links = n_links; A.mtid = mtid; A.n_partner = n_partner; A.lo = lo; A.hi = hi;
+    hipLaunchKernelGGL(matelink_partner_kernel, dim3(wave_grid(nq)), dim3(kLinkWaveBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace im

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""matelink_scatter_kernel's time per chunk (-T, im_matelink.hip) next to pairlink_scatter_kernel's in the same process, and
+"""matelink_scatter_kernel's time per chunk (-T, im_links.hip) next to pairlink_scatter_kernel's in the same process, and
 im_matelink_partner and im_cliptail_junction for the planted queries.
 
 Scatter: the configs[1] chunk (synth seed 1, 1 Mb at 30x, 300 000 records as the product's walkers deliver them).  It has one contig, so

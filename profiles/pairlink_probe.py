@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""pairlink_scatter_kernel's time per chunk (-M, im_pairlink.hip) next to cliptail_scatter_kernel's in the same process,
+"""pairlink_scatter_kernel's time per chunk (-M, im_links.hip) next to cliptail_scatter_kernel's in the same process,
 im_pairlink_count for the planted queries, and the product with -M next to the product without it.
 
 Scatter: the configs[1] chunk (synth seed 1, 1 Mb at 30x, 300 000 records as the product's walkers deliver them).  Its pairs are all in

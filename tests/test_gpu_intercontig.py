@@ -1,4 +1,4 @@
-"""Breakpoints between contigs (-T): the scatter, add and partner kernels of im_matelink.hip behind the six im_matelink_* entries, the
+"""Breakpoints between contigs (-T): the scatter, add and partner kernels of im_links.hip behind the six im_matelink_* entries, the
 junction kernel of im_cliptail.hip behind im_cliptail_junction, and what the host driver makes of them (-T's FILE).
 
 The yardstick is the plain restatement in tests/support/intercontig.py, written from the definitions in include/indelminer_amd.h (seam 5,

@@ -1,4 +1,4 @@
-"""Pair links (-M): the scatter, add and count kernels of im_pairlink.hip behind the six im_pairlink_* entries, and what the host driver
+"""Pair links (-M): the scatter, add and count kernels of im_links.hip behind the six im_pairlink_* entries, and what the host driver
 makes of them (PE= in -U's and -N's FILE).
 
 The yardstick is the plain restatement in tests/support/pairlinks.py, written from the definition in include/indelminer_amd.h (seam 5,

@@ -273,4 +273,4 @@ def test_entry_points_are_declared_bound_and_exported():
     shim = open(os.path.join(ROOT, "tests", "shim", "im_shim.c")).read()
     assert "im_matelink" not in shim and "im_cliptail_junction" not in shim           # additive: the shim stays without the entries
     from indelminer_amd import build
-    assert "im_matelink.hip" in build.SOURCES
+    assert "im_links.hip" in build.SOURCES and "im_matelink.hip" not in build.SOURCES

@@ -117,7 +117,7 @@ def test_pair_link_entry_points_are_declared_bound_and_exported():
     assert C.sizeof(capi.TriageParams) == 24 and C.sizeof(capi.DevRecords) == 32
     shim = open(os.path.join(ROOT, "tests", "shim", "im_shim.c")).read()
     assert "im_pairlink" not in shim and "im_dev_pairlink" not in shim
-    assert "im_pairlink.hip" in build.SOURCES
+    assert "im_links.hip" in build.SOURCES and "im_pairlink.hip" not in build.SOURCES
 
 
 def test_pair_link_restatement_on_cases_worked_by_hand():
