@@ -53,13 +53,8 @@ __device__ __forceinline__ RecView view_record(const uint8_t* raw, uint32_t off,
 
 __device__ __forceinline__ int aux_size(uint32_t t)
 {
-    switch (t) {
-    case 'A': case 'c': case 'C': return 1;
-    case 's': case 'S': return 2;
-    case 'i': case 'I': case 'f': return 4;
-    case 'd': return 8;
-    default: return 0;
-    }
+    // selects, not a switch: the tag walk calls it in straight-line code
+    return (t == 'A' || t == 'c' || t == 'C') ? 1 : (t == 's' || t == 'S') ? 2 : (t == 'i' || t == 'I' || t == 'f') ? 4 : t == 'd' ? 8 : 0;
 }
 
 // a byte of the record at offset o: the lane's aux window (LDS) when it covers o, memory otherwise
@@ -69,15 +64,20 @@ __device__ __forceinline__ uint32_t rec_byte(const RecView& r, const AuxWin& w, 
     const uint32_t d = o - w.o0;
     return d < (uint32_t)kAuxWin ? reinterpret_cast<const uint8_t*>(w.lds)[d] : r.p[o];
 }
-// The window moved to offset o: six dword loads by the lane that needs them.  What an aligner writes in front of RG and MQ
-// (NM MD AS XS MC ...: 30-100 bytes) used to be walked through memory byte by byte behind the first 24 -- every byte a 64-line
-// gather: records with such fields took classify from 25 to 77 us per 300 000 (profiles/r04_m_*).  Reads past the record stay
-// inside the chunk buffer (>= 64 spare bytes behind the last record).
+// The window moved to offset o: six dword loads by the lane that needs them, issued together and waited for once -- the values
+// are held in registers until all six are under way, then written (a load and its LDS write per dword made six round trips one
+// after the other).  What an aligner writes in front of RG and MQ (NM MD AS XS MC ...: 30-100 bytes) used to be walked through
+// memory byte by byte behind the first 24 -- every byte a 64-line gather: records with such fields took classify from 25 to 77 us
+// per 300 000 (profiles/r04_m_*).  Reads past the record stay inside the chunk buffer (>= 64 spare bytes behind the last record):
+// o < r.len wherever the window is moved, so the last byte read is at most 23 behind the record's end.
 __device__ __forceinline__ void aux_slide(const RecView& r, AuxWin& w, uint32_t o)
 {
     w.o0 = o;
+    uint32_t v[kAuxWin / 4];
 #pragma unroll
-    for (int k = 0; k < kAuxWin / 4; k++) w.lds[k] = ld_u32(r.p + o + 4u * k);
+    for (int k = 0; k < kAuxWin / 4; k++) v[k] = ld_u32(r.p + o + 4u * k);
+#pragma unroll
+    for (int k = 0; k < kAuxWin / 4; k++) w.lds[k] = v[k];
 }
 // the byte at o for a walk that only moves forward: the window follows
 __device__ __forceinline__ uint32_t walk_byte(const RecView& r, AuxWin& w, uint32_t o)
@@ -86,38 +86,66 @@ __device__ __forceinline__ uint32_t walk_byte(const RecView& r, AuxWin& w, uint3
     return reinterpret_cast<const uint8_t*>(w.lds)[o - w.o0];
 }
 // [o, o + need) inside the window (need <= kAuxWin)
+__device__ __forceinline__ bool aux_covers(const AuxWin& w, uint32_t o, uint32_t need)
+{
+    return o >= w.o0 && o + need <= w.o0 + (uint32_t)kAuxWin;
+}
 __device__ __forceinline__ void aux_cover(const RecView& r, AuxWin& w, uint32_t o, uint32_t need)
 {
-    if (!(o >= w.o0 && o + need <= w.o0 + (uint32_t)kAuxWin)) aux_slide(r, w, o);
+    if (!aux_covers(w, o, need)) aux_slide(r, w, o);
+}
+// a byte the window is known to cover; a lane that is not `on` reads the window's first byte and makes nothing of it
+__device__ __forceinline__ uint32_t win_byte(const AuxWin& w, uint32_t o, bool on)
+{
+    return reinterpret_cast<const uint8_t*>(w.lds)[on ? o - w.o0 : 0u];
 }
 
 // bam_aux_get for RG and MQ in one walk (bam_aux.c:27-54): offsets of the TYPE byte of the first
 // occurrence, 0 = absent.  The walk stops where samtools' would (unknown type, truncated B array).
-__device__ __forceinline__ void find_rg_mq(const RecView& r, AuxWin& w, uint32_t& o_rg, uint32_t& o_mq)
+// The loops are the WAVE's: a pass per field while any lane of the caller still walks, the lanes that are done (or that do not
+// walk at all: `walk` false) predicated, and what few fields need -- a window that has to move, a string, a B array -- behind a
+// test on the whole wave.  A wave of records with fixed-size fields inside the first window runs no lane-divergent region.
+__device__ __forceinline__ void find_rg_mq(const RecView& r, AuxWin& w, uint32_t& o_rg, uint32_t& o_mq, bool walk = true)
 {
     o_rg = 0; o_mq = 0;
     uint32_t s = r.o_aux;
     const uint32_t end = r.len;
-    while (s + 4u <= end) {      // a tail of < 4 bytes is alignment padding (include/indelminer_amd.h, im_dev_records)
-        aux_cover(r, w, s, 8u);  // tag, type and what a B array's header takes
-        const uint32_t t0 = rec_byte(r, w, s), t1 = rec_byte(r, w, s + 1), type = rec_byte(r, w, s + 2);
-        if (t0 == 'R' && t1 == 'G' && !o_rg) o_rg = s + 2u;
-        if (t0 == 'M' && t1 == 'Q' && !o_mq) o_mq = s + 2u;
-        if (o_rg && o_mq) return;
+    bool on = walk && s + 4u <= end;     // a tail of < 4 bytes is alignment padding (include/indelminer_amd.h, im_dev_records)
+    while (__ballot(on) != 0ull) {
+        // tag, type and what a B array's header takes
+        const bool move = on && !aux_covers(w, s, 8u);
+        if (__ballot(move) != 0ull) { if (move) aux_slide(r, w, s); }
+        const uint32_t t0 = win_byte(w, s, on), t1 = win_byte(w, s + 1u, on), type = win_byte(w, s + 2u, on);
+        if (on && t0 == 'R' && t1 == 'G' && !o_rg) o_rg = s + 2u;
+        if (on && t0 == 'M' && t1 == 'Q' && !o_mq) o_mq = s + 2u;
+        on = on && !(o_rg && o_mq);
         s += 3u;
-        if (type == 'Z' || type == 'H') { while (s < end && walk_byte(r, w, s)) s++; s++; }
-        else if (type == 'B') {
-            if (s + 5u > end) return;
-            const int sz = aux_size(rec_byte(r, w, s));
-            const uint32_t cnt = rec_byte(r, w, s + 1) | (rec_byte(r, w, s + 2) << 8) | (rec_byte(r, w, s + 3) << 16) | (rec_byte(r, w, s + 4) << 24);
-            const uint64_t ns = (uint64_t)s + 5u + (uint64_t)sz * cnt;
-            if (ns > end) return;
-            s = (uint32_t)ns;
-        } else {
-            const int sz = aux_size(type);
-            if (sz == 0) return;
-            s += (uint32_t)sz;
+        const bool str = on && (type == 'Z' || type == 'H'), arr = on && type == 'B';
+        const uint32_t sz = (uint32_t)aux_size(type);
+        if (on && !str && !arr) { on = sz != 0u; s += sz; }
+        if (__ballot(str) != 0ull) {
+            // while (s < end && byte(s)) s++; s++;
+            bool go = str;
+            for (;;) {
+                go = go && s < end;
+                const bool mv = go && s - w.o0 >= (uint32_t)kAuxWin;
+                if (__ballot(mv) != 0ull) { if (mv) aux_slide(r, w, s); }
+                go = go && win_byte(w, s, go) != 0u;
+                if (__ballot(go) == 0ull) break;
+                s += go ? 1u : 0u;
+            }
+            s += str ? 1u : 0u;
         }
+        if (__ballot(arr) != 0ull) {
+            // the header's five bytes lie in the window: it covers eight bytes from the tag on
+            const bool hdr = arr && s + 5u <= end;
+            const uint32_t esz = (uint32_t)aux_size(win_byte(w, s, hdr));
+            const uint32_t cnt = win_byte(w, s + 1u, hdr) | (win_byte(w, s + 2u, hdr) << 8) | (win_byte(w, s + 3u, hdr) << 16) | (win_byte(w, s + 4u, hdr) << 24);
+            const uint64_t ns = (uint64_t)s + 5u + (uint64_t)esz * cnt;        // 64 bits: count * size can pass 2^32
+            const bool fits = hdr && ns <= end;
+            if (arr) { on = fits; s = fits ? (uint32_t)ns : s; }
+        }
+        on = on && s + 4u <= end;
     }
 }
 

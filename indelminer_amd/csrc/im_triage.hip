@@ -92,19 +92,6 @@ __device__ __forceinline__ bool reaches_new_readaln(const RecView& r)
     return r.ok && !(f & (0x100u | 0x200u | 0x400u | 0x800u)) && (f & 0x1u) && (f & 0x2u) && !(f & (0x4u | 0x8u)) && r.tid == r.mtid;
 }
 
-// How many read bases new_readaln decodes: the query bases of the CIGAR, taken where the CIGAR says -- also past l_seq --
-// but not past the record.
-__device__ __forceinline__ uint32_t bases_in_cigar_reach(const RecView& r)
-{
-    uint64_t qtot = 0;
-    for (uint32_t i = 0; i < r.n_cigar; i++) {
-        const uint32_t cw = cigar_word(r, i), op = cw & 15u;
-        if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) qtot += cw >> 4;
-    }
-    const uint64_t avail = 2ull * (r.len - r.o_seq);
-    return (uint32_t)(qtot < avail ? qtot : avail);
-}
-
 // Of eight packed bases (one dword): bit 4 p set where nibble p holds a code bit2char takes.  A popcount per nibble (the
 // codes of A C G T have one bit, N has four), then "count is 1 or 4" on its three bits.
 __device__ __forceinline__ uint32_t good_codes(uint32_t x)
@@ -184,92 +171,22 @@ __device__ __forceinline__ void sweep_finish(const BaseSweep& S, const uint8_t* 
     }
 }
 
-struct Verdict {
-    uint32_t cls;           // IM_REC_*
-    bool revcomp;
-    int32_t range_max;
+// CIGAR ops as bits of 1 << op: what new_readseg_bam refuses (N H P and op > 8), what carries read bases (M I S = X), what the
+// pileup counts (M = X) and what moves along the reference (M D N = X)
+constexpr uint32_t kOpsRefused = 0xFE68u, kOpsQuery = 0x193u, kOpsMatch = 0x181u, kOpsRef = 0x18Du;
+
+// A 32-bit running sum that stops at 2^32 - 1.  A CIGAR has up to 65 535 ops of up to 2^28 - 1 each, so sums of lengths reach
+// 2^44; every use below compares the sum with a value below 2^32 - 1, and for that the stopped sum answers as the 64-bit one does.
+__device__ __forceinline__ uint32_t add_sat(uint32_t a, uint32_t b) { const uint32_t s = a + b; return s < a ? 0xFFFFFFFFu : s; }
+
+// What the ONE walk over a record's CIGAR leaves for the rule cascade (the pileup's events go out during the walk)
+struct CigarFacts {
+    uint32_t seen;      // 1 << op of every op, or-ed
+    uint32_t qtot;      // read bases of all ops: what new_readaln decodes, before the record's end cuts it (add_sat)
+    uint32_t q0;        // read bases in front of the first refused op (add_sat)
+    uint32_t nclip;     // soft clips
+    bool three;         // a soft clip at the read's 3' end: the last op of a forward read, the first of a reverse one
 };
-
-// generic_ok / generic_range: the lookup of "generic" (records without an RG tag, src/indelminer.c:370), done once per workgroup
-__device__ __forceinline__ Verdict classify(const RecView& r, AuxWin w, const im_triage_params& tp, const RgView& T,
-                                            bool generic_ok, int32_t generic_range, uint32_t fb)
-{
-    Verdict v; v.cls = IM_REC_SKIP; v.revcomp = false; v.range_max = 0;
-    if (!r.ok) { v.cls = IM_REC_ERR_LIMIT; return v; }
-    const uint32_t flag = r.flag;
-    if (flag & (0x100u | 0x200u | 0x400u | 0x800u)) return v;                  // 348-351
-    const bool aligned = !(flag & 0x4u), mate_aligned = !(flag & 0x8u);
-    const bool proper = (flag & 0x2u) != 0, is_rc = (flag & 0x10u) != 0, mate_rc = (flag & 0x20u) != 0;
-    if (!(flag & 0x1u)) return v;                                              // 361
-    if (aligned && mate_aligned && r.tid != r.mtid) return v;                  // 364-366
-    v.cls = IM_REC_COUNTED;
-
-    uint32_t o_rg, o_mq;
-    find_rg_mq(r, w, o_rg, o_mq);
-    if (tp.defer_ranges) {
-        // the table is still being estimated: only what does not need it is checked (a read-group tag of a type bam_aux2Z refuses)
-        if (o_rg) { const uint32_t type = rec_byte(r, w, o_rg); if (!(type == 'Z' || type == 'H')) { v.cls = IM_REC_ERR_RG; return v; } }
-        v.range_max = 0;
-    } else if (!o_rg) {
-        if (!generic_ok) { v.cls = IM_REC_ERR_RG; return v; }
-        v.range_max = generic_range;
-    } else {
-        if (!rg_tag_range(r, w, o_rg, T, v.range_max)) { v.cls = IM_REC_ERR_RG; return v; }
-    }
-
-    if (aligned && !mate_aligned) return v;                                    // 384-385
-    if (!aligned && mate_aligned) {                                            // 386-424
-        int32_t mmq = (int32_t)r.mapq;
-        if (o_mq) {
-            aux_cover(r, w, o_mq, 5u);
-            const uint32_t t = rec_byte(r, w, o_mq);
-            if (!(t == 'I' || t == 'i' || t == 'C' || t == 'c' || t == 'S' || t == 's')) { v.cls = IM_REC_ERR_MQ; return v; }
-            mmq = aux_int(r, w, o_mq);
-        }
-        if (mmq >= tp.qthreshold) { v.cls = IM_REC_CAND_UNMAPPED; v.revcomp = !mate_rc; }
-        return v;
-    }
-    if (aligned && mate_aligned && proper) {                                   // 425-515
-        // new_readaln (src/readaln.c:186-240) builds the segment list of EVERY proper pair first, op by op: N / H / P and
-        // unknown ops are fatal (163-182), and so is a base code other than A C G T N in an op that carries read bases
-        // (bit2char, 4-16) -- whichever comes first along the CIGAR.  fb comes in as the first bad base among the l_seq
-        // bases of the read (the wave's cooperative sweep); only what lies inside the CIGAR's reach counts, and a CIGAR
-        // that reaches past l_seq has the bytes behind the packed bases looked at here.  Then the ops are walked: a bad op
-        // at read offset q loses to a bad base in front of it.
-        const uint32_t lim = bases_in_cigar_reach(r);
-        if (fb >= lim) {
-            fb = 0xFFFFFFFFu;
-            for (uint32_t j = (uint32_t)r.l_seq; j < lim; j++) {
-                const uint32_t code = (r.p[r.o_seq + (j >> 1)] >> ((~j & 1u) << 2)) & 15u;
-                if (!(code == 1u || code == 2u || code == 4u || code == 8u || code == 15u)) { fb = j; break; }
-            }
-        }
-        uint32_t ndel = 0, nins = 0, nclip = 0; bool three = false;
-        uint64_t q = 0;
-        for (uint32_t i = 0; i < r.n_cigar; i++) {
-            const uint32_t cw = cigar_word(r, i), op = cw & 15u;
-            if (op == 3u || op == 5u || op == 6u || op > 8u) { v.cls = (uint64_t)fb < q ? IM_REC_ERR_BASE : IM_REC_ERR_CIGAR; return v; }   // new_readseg_bam
-            if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) q += cw >> 4;
-            ndel += op == 2u; nins += op == 1u; nclip += op == 4u;
-            if (op == 4u && ((!is_rc && i == r.n_cigar - 1u) || (is_rc && i == 0u))) three = true;
-        }
-        if (fb != 0xFFFFFFFFu) { v.cls = IM_REC_ERR_BASE; return v; }
-        if (ndel + nins + nclip == 0u) return v;
-        if ((nclip == 0u || (nclip == 1u && three)) && ndel == 0u && nins == 0u) return v;            // 457-460
-        if (o_mq) aux_cover(r, w, o_mq, 5u);
-        const int32_t mmq = o_mq ? aux_int(r, w, o_mq) : (int32_t)r.mapq;
-        if (mmq >= tp.qthreshold) { v.cls = IM_REC_CAND_PROPER; v.revcomp = is_rc == mate_rc; }
-        return v;
-    }
-    if (aligned && mate_aligned && !proper) {                                  // 516-521
-        const int64_t a = r.isize < 0 ? -(int64_t)r.isize : (int64_t)r.isize;
-        const uint32_t a32 = (uint32_t)(r.isize < 0 ? -r.isize : r.isize);     // abs() as int, compared with a uint
-        if (a > (int64_t)v.range_max && a32 < tp.maxpedelsize && is_rc != mate_rc) v.cls = IM_REC_PE;
-        return v;
-    }
-    return v;
-}
-
 struct TriageArgs {
     im_dev_records recs;
     im_dev_cands out;
@@ -325,72 +242,201 @@ __global__ __launch_bounds__(kClsBlock, 6) void triage_classify_kernel(TriageArg
 
     // the record: offsets, core, then CIGAR head + aux window + the wave's sweep over the packed bases in one round trip
     RecView r; r.ok = false; r.l_seq = 0; r.flag = 0; r.n_cigar = 0; r.tid = -1; r.pos = 0; r.o_cigar = 0; r.o_seq = 0; r.p = A.recs.raw; r.len = 0; r.o_aux = 0;
+    r.mtid = -1; r.isize = 0; r.mapq = 0;
     s_fb[lane] = 0xFFFFFFFFu;
     // the insert-length table: LDS copy when it is small (its loads go out with the record offsets')
     const bool rg_lds = A.rg.bytes <= kClsRgLds;
     if (rg_lds) for (int k = lane; 4 * k < A.rg.bytes; k += kClsBlock) s_rg[k] = reinterpret_cast<const uint32_t*>(A.rg.blob)[k];
-    if (i < A.recs.n) r = view_record(A.recs.raw, A.recs.rec_off[i], A.recs.rec_off[i + 1]);
+    const bool valid = i < A.recs.n;
+    if (valid) r = view_record(A.recs.raw, A.recs.rec_off[i], A.recs.rec_off[i + 1]);
     IM_TRI_STAMP(1, r.flag);
-    const uint32_t sw_lim = reaches_new_readaln(r) ? (uint32_t)r.l_seq : 0u;   // r.ok: the packed bases lie inside the record
+    const bool pp = reaches_new_readaln(r);                                     // r.ok: the packed bases lie inside the record
+    const uint32_t sw_lim = pp ? (uint32_t)r.l_seq : 0u;
     const uint32_t sw_so = sw_lim ? (uint32_t)(r.p - A.recs.raw) + r.o_seq : 0u;
     BaseSweep S;
     sweep_issue(S, A.recs.raw, sw_so, sw_lim, lane);
-    if (r.ok) {
-        // reads past the record stay inside the chunk buffer (>= 64 spare bytes behind the last record)
+    {
+        // The CIGAR head and the aux window: ten loads that go out together and are waited for once.  They are unconditional: a
+        // lane without a record takes the buffer's first bytes (the chunk holds >= 64), a record with a short aux area reads on
+        // behind it -- at most 24 bytes behind the record, inside the chunk buffer's >= 64 spare bytes -- and what lands in the
+        // window for bytes the aux area does not have is never looked at: every reader checks its offset against r.len first.
+        const uint8_t* pc = r.ok ? r.p + r.o_cigar : A.recs.raw;
+        const uint8_t* pa = r.ok ? r.p + r.o_aux : A.recs.raw;
+        uint32_t av[kAuxWin / 4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) r.cig[k] = ld_u32(r.p + r.o_cigar + 4u * k);
-        // the aux window: as many dwords as the record's aux area has (a record with the MQ tag alone: one or two)
-        const uint32_t aux_bytes = r.len - r.o_aux;
+        for (int k = 0; k < 4; k++) r.cig[k] = ld_u32(pc + 4u * k);
 #pragma unroll
-        for (int k = 0; k < kAuxWin / 4; k++) if (4u * k < aux_bytes) s_aux[lane][k] = ld_u32(r.p + r.o_aux + 4u * k);
+        for (int k = 0; k < kAuxWin / 4; k++) av[k] = ld_u32(pa + 4u * k);
+#pragma unroll
+        for (int k = 0; k < kAuxWin / 4; k++) s_aux[lane][k] = av[k];
     }
     wave_lds_order();                                                           // s_fb's ~0 before the sweep's minima
     sweep_finish(S, A.recs.raw, sw_so, sw_lim, s_fb, lane);
     // the depth window starts at the first pileup-eligible record of the workgroup (records are sorted inside a contig)
     const bool piles = A.depth_diff && r.ok && r.tid >= 0 && r.tid < A.ref.n_contigs && !(r.flag & (0x4u | 0x100u | 0x200u | 0x400u));
     int32_t dd_pos = 0, dd_tid = -1;
+    int64_t pl_base = 0;            // the lane's contig in the difference array
+    uint32_t pl_end = 0;            // and its length, as a biased position (below)
     if (A.depth_diff) {
         const uint64_t mp = __ballot(piles);
         const int first = mp ? (int)__builtin_ctzll(mp) : 0;
         const int fp = __shfl(r.pos, first), ft = __shfl(r.tid, first);
         dd_pos = fp < 0 ? 0 : fp; dd_tid = mp ? ft : -1;
+        if (mp) {
+            // a lane that does not pile up asks for the window's contig: the loads stay unconditional
+            const int32_t t = piles ? r.tid : dd_tid;
+            pl_base = A.ref.asc_off[t];
+            pl_end = (uint32_t)A.ref.len[t] ^ 0x80000000u;
+        }
     }
     wave_lds_order();                                                           // the table, the sweep's minima and the zeroed window are in
     IM_TRI_STAMP(2, r.cig[3]);
     const RgView T = rg_view(rg_lds ? reinterpret_cast<const uint8_t*>(s_rg) : A.rg.blob, A.rg.n);
 
-    uint32_t cls = IM_REC_SKIP, bytes = 0;
-    bool cand = false;
-    if (i < A.recs.n) {
-        AuxWin w; w.lds = s_aux[lane]; w.o0 = r.o_aux;
-        const Verdict v = classify(r, w, A.tp, T, A.rg.generic_ok != 0, A.rg.generic_range, s_fb[lane]);
-        cls = v.cls;
-        cand = cls == IM_REC_CAND_UNMAPPED || cls == IM_REC_CAND_PROPER;
-        if (cand) bytes = padded4(r.l_seq);
-        A.info[i] = cls | (v.revcomp ? 0x100u : 0u);
-        A.rmax[i] = v.range_max;
-        if (A.out.rec_class) A.out.rec_class[i] = (uint8_t)cls;
-        // what samtools' pileup counts (bam_pileup.c:171-172, 238-265): M/=/X of records that are mapped,
-        // primary, not QC-failed, not duplicates
-        if (piles) {
-            const int64_t base = A.ref.asc_off[r.tid];
-            const int64_t clen = A.ref.len[r.tid];
-            const bool here = r.tid == dd_tid;
-            int64_t x = r.pos;
-            for (uint32_t k = 0; k < r.n_cigar; k++) {
-                const uint32_t cw = cigar_word(r, k), op = cw & 15u;
-                const int64_t len = cw >> 4;
-                if (op == 0u || op == 7u || op == 8u) {
-                    int64_t a = x < 0 ? 0 : x, b = x + len > clen ? clen : x + len;
-                    if (a < b) {
-                        const int64_t ra = a - dd_pos, rb = b - dd_pos;
-                        if (here && ra >= 0 && ra < kDepthWin) atomicAdd(&s_dd[ra], 1); else atomicAdd(&A.depth_diff[base + a], 1);
-                        if (here && rb >= 0 && rb < kDepthWin) atomicAdd(&s_dd[rb], -1); else atomicAdd(&A.depth_diff[base + b], -1);
-                    }
-                    x += len;
-                } else if (op == 2u || op == 3u) x += len;
+    // ---- the rules' inputs (src/indelminer.c:348-366): computed by every lane, nothing branches on them
+    const uint32_t flag = r.flag;
+    const bool aligned = !(flag & 0x4u), mate_aligned = !(flag & 0x8u), both = aligned && mate_aligned;
+    const bool proper = (flag & 0x2u) != 0, is_rc = (flag & 0x10u) != 0, mate_rc = (flag & 0x20u) != 0;
+    // past the flag / pairing filters: the record counts, and its tags are looked at
+    const bool counted = r.ok && !(flag & (0x100u | 0x200u | 0x400u | 0x800u)) && (flag & 0x1u) && !(both && r.tid != r.mtid);
+
+    // ---- the ONE walk over the CIGAR: a loop of the wave's, to the longest CIGAR among the lanes that need theirs (proper pairs
+    // for new_readaln's census, pileup-eligible records for their match segments).  Per op a lane takes
+    //   seen, nclip, three   the census of src/indelminer.c:441-460
+    //   q / q0               read bases so far / in front of the first op new_readseg_bam refuses
+    //   u                    the reference position, and from it the pileup's +1 / -1 of an M = X run
+    // Value ranges.  q: add_sat (above).  u is the position x = pos + (lengths so far) as x + 2^31 in a uint32 with add_sat: pos is
+    // an int32, so the bias makes it non-negative, and a sum stopped at 2^32 - 1 stands for "x >= 2^31 - 1", which is at or
+    // behind every contig's end (len is an int32): max(x, 0) and min(x + len, clen) of the 64-bit form become max / min against
+    // the biased 0 and the biased clen, with the same outcome of a < b and the same a and b wherever a < b.
+    CigarFacts cf; cf.seen = 0u; cf.qtot = 0u; cf.q0 = 0u; cf.nclip = 0u; cf.three = false;
+    {
+        const uint32_t nc = (pp || piles) ? r.n_cigar : 0u;
+        const uint32_t nmax = (uint32_t)wave_max((int)nc);                      // n_cigar < 2^16
+        const uint32_t three_at = is_rc ? 0u : r.n_cigar - 1u;
+        const bool here = r.tid == dd_tid;
+        uint32_t u = (uint32_t)r.pos ^ 0x80000000u;
+        auto op_step = [&](uint32_t k, uint32_t cw) {
+            const uint32_t bit = k < nc ? 1u << (cw & 15u) : 0u, len = cw >> 4;
+            if ((bit & kOpsRefused) && !(cf.seen & kOpsRefused)) cf.q0 = cf.qtot;
+            cf.seen |= bit;
+            cf.qtot = add_sat(cf.qtot, (bit & kOpsQuery) ? len : 0u);
+            cf.nclip += (bit >> 4) & 1u;
+            cf.three = cf.three || ((bit & 16u) && k == three_at);
+            const uint32_t ue = add_sat(u, (bit & kOpsRef) ? len : 0u);
+            // what samtools' pileup counts (bam_pileup.c:171-172, 238-265): M/=/X of records that are mapped, primary, not
+            // QC-failed, not duplicates -- whatever class the record gets
+            const uint32_t au = u > 0x80000000u ? u : 0x80000000u, bu = ue < pl_end ? ue : pl_end;
+            if (piles && (bit & kOpsMatch) && au < bu) {
+                // 0 <= a < b <= clen < 2^31, dd_pos >= 0: the differences fit an int32, and as uint32 one compare is "0 <= . < window"
+                const int32_t a = (int32_t)(au ^ 0x80000000u), b = (int32_t)(bu ^ 0x80000000u);
+                const uint32_t ra = (uint32_t)(a - dd_pos), rb = (uint32_t)(b - dd_pos);
+                // the array index keeps 64 bits in its last addition
+                if (here && ra < (uint32_t)kDepthWin) atomicAdd(&s_dd[ra], 1); else atomicAdd(&A.depth_diff[pl_base + a], 1);
+                if (here && rb < (uint32_t)kDepthWin) atomicAdd(&s_dd[rb], -1); else atomicAdd(&A.depth_diff[pl_base + b], -1);
+            }
+            u = ue;
+        };
+        // the first four words travel in registers (one round trip with the aux window) ...
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) if (k < nmax) op_step(k, r.cig[k]);
+        // ... the rest come from memory, for the lanes that have them
+        for (uint32_t k = 4u; k < nmax; k++) {
+            uint32_t cw = 0u;
+            if (k < nc) cw = ld_u32(r.p + r.o_cigar + 4u * k);
+            op_step(k, cw);
+        }
+    }
+
+    // ---- the tags (369-376, and the MQ of 386-424 / 461): one walk of the wave's for RG and MQ
+    AuxWin w; w.lds = s_aux[lane]; w.o0 = r.o_aux;
+    uint32_t o_rg, o_mq;
+    find_rg_mq(r, w, o_rg, o_mq, counted);
+    // the read group's range.  No RG tag: "generic", looked up once per workgroup.  A tag: behind a test of the wave's
+    const bool defer = A.tp.defer_ranges != 0;      // the table is still being estimated: only what does not need it is checked
+    const bool has_rg = counted && o_rg != 0u;
+    const bool generic = counted && !has_rg && !defer;
+    bool rg_err = generic && A.rg.generic_ok == 0;
+    int32_t rmax = (generic && A.rg.generic_ok != 0) ? A.rg.generic_range : 0;
+    if (__ballot(has_rg) != 0ull) {
+        if (has_rg) {
+            if (defer) { const uint32_t type = rec_byte(r, w, o_rg); rg_err = !(type == 'Z' || type == 'H'); }   // a type bam_aux2Z refuses
+            else { int32_t rm = 0; if (rg_tag_range(r, w, o_rg, T, rm)) rmax = rm; else rg_err = true; }
+        }
+    }
+    const bool live = counted && !rg_err;
+    const bool um = live && !aligned && mate_aligned;                           // 386-424
+    const bool ppl = live && both && proper;                                    // 425-515
+    const bool pe = live && both && !proper;                                    // 516-521
+
+    // ---- proper pairs.  new_readaln (src/readaln.c:186-240) builds the segment list of EVERY proper pair first, op by op: N / H / P
+    // and unknown ops are fatal (163-182), and so is a base code other than A C G T N in an op that carries read bases (bit2char,
+    // 4-16) -- whichever comes first along the CIGAR.  s_fb holds the first bad base among the l_seq bases of the read (the wave's
+    // cooperative sweep); only what lies inside the CIGAR's reach counts -- the query bases of all ops, taken where the CIGAR says,
+    // also past l_seq, but not past the record -- and a CIGAR that reaches past l_seq has the bytes behind the packed bases looked
+    // at here.  A bad op at read offset q0 loses to a bad base in front of it.
+    // r.len < 2^31 (chunk offsets fit 31 bits: seq_at), so twice the bytes behind o_seq fit 32 bits; qtot stopped at 2^32 - 1 is
+    // above that, and the minimum is the 64-bit one
+    const uint32_t avail = 2u * (r.len - r.o_seq);
+    const uint32_t lim = cf.qtot < avail ? cf.qtot : avail;
+    uint32_t fb = s_fb[lane];
+    fb = fb >= lim ? 0xFFFFFFFFu : fb;
+    const bool behind = ppl && fb == 0xFFFFFFFFu && lim > (uint32_t)r.l_seq;
+    if (__ballot(behind) != 0ull) {
+        if (behind) {
+            for (uint32_t j = (uint32_t)r.l_seq; j < lim; j++) {
+                const uint32_t code = (r.p[r.o_seq + (j >> 1)] >> ((~j & 1u) << 2)) & 15u;
+                if (!(code == 1u || code == 2u || code == 4u || code == 8u || code == 15u)) { fb = j; break; }
             }
         }
+    }
+    // fb < lim < 2^32 - 1 or fb = ~0: against q0 stopped at 2^32 - 1 "a bad base in front of the op" is fb < q0 as it is in 64 bits,
+    // and "no bad base" (~0) is in front of nothing, also where the op lies 2^32 or more read bases in: IM_REC_ERR_CIGAR, as the
+    // reference has it
+    const uint32_t pp_err = (cf.seen & kOpsRefused) ? (fb < cf.q0 ? IM_REC_ERR_BASE : IM_REC_ERR_CIGAR) : fb != 0xFFFFFFFFu ? IM_REC_ERR_BASE : 0u;
+    // 441-460: an indel, or a clip other than the one clip at the 3' end
+    const bool variant = (cf.seen & 6u) != 0u || cf.nclip > 1u || (cf.nclip == 1u && !cf.three);
+
+    // ---- the mate's mapping quality: the MQ tag where there is one, for the records whose class hangs on it.  An MQ:C inside the
+    // window (what aligners write) is one LDS byte; any other type, or a tag the window has left, behind a test of the wave's
+    const bool need_mq = o_mq != 0u && (um || (ppl && pp_err == 0u && variant));
+    const bool mq_in = need_mq && aux_covers(w, o_mq, 2u);                      // o_mq + 1 < r.len: a field has at least four bytes
+    const uint32_t mq_type = win_byte(w, o_mq, mq_in), mq_byte = win_byte(w, o_mq + 1u, mq_in);
+    const bool mq_fast = mq_in && mq_type == 'C';
+    int32_t mmq = mq_fast ? (int32_t)mq_byte : (int32_t)r.mapq;
+    bool mq_err = false;
+    const bool mq_slow = need_mq && !mq_fast;
+    if (__ballot(mq_slow) != 0ull) {
+        if (mq_slow) {
+            aux_cover(r, w, o_mq, 5u);
+            const uint32_t t = rec_byte(r, w, o_mq);
+            // only the unmapped-read case checks the type (399-403); a proper pair takes bam_aux2i's 0
+            mq_err = um && !(t == 'I' || t == 'i' || t == 'C' || t == 'c' || t == 'S' || t == 's');
+            mmq = aux_int(r, w, o_mq);
+        }
+    }
+    const bool mq_pass = mmq >= A.tp.qthreshold;
+
+    // ---- the class, in the reference's order of precedence
+    // 516-521: abs(isize) as an int against range_max, as a uint against maxpedelsize.  |isize| <= 2^31 is exact in a uint32; a
+    // negative range_max is below it, and a non-negative one compares as a uint32 as it does in 64 bits
+    const uint32_t a32 = r.isize < 0 ? 0u - (uint32_t)r.isize : (uint32_t)r.isize;
+    const bool pe_hit = (rmax < 0 || a32 > (uint32_t)rmax) && a32 < A.tp.maxpedelsize && is_rc != mate_rc;
+    uint32_t cls = !valid ? IM_REC_SKIP : !r.ok ? IM_REC_ERR_LIMIT : !counted ? IM_REC_SKIP : rg_err ? IM_REC_ERR_RG : IM_REC_COUNTED;
+    bool revcomp = false;
+    if (um) { cls = mq_err ? IM_REC_ERR_MQ : mq_pass ? IM_REC_CAND_UNMAPPED : IM_REC_COUNTED; revcomp = !mq_err && mq_pass && !mate_rc; }
+    if (ppl) {
+        const bool hit = pp_err == 0u && variant && mq_pass;
+        cls = pp_err != 0u ? pp_err : hit ? IM_REC_CAND_PROPER : IM_REC_COUNTED;
+        revcomp = hit && is_rc == mate_rc;
+    }
+    if (pe && pe_hit) cls = IM_REC_PE;
+    const bool cand = cls == IM_REC_CAND_UNMAPPED || cls == IM_REC_CAND_PROPER;
+    const uint32_t bytes = cand ? padded4(r.l_seq) : 0u;
+    if (valid) {
+        A.info[i] = cls | (revcomp ? 0x100u : 0u);
+        A.rmax[i] = rmax;
+        if (A.out.rec_class) A.out.rec_class[i] = (uint8_t)cls;
     }
     IM_TRI_STAMP(3, cls);
     // workgroup totals
