@@ -119,7 +119,13 @@ typedef struct im_read_batch {
                                    complemented where the caller decided so
                                    (src/indelminer.c:404-409,479-484)                */
     const int64_t* base_off;    /* n+1 offsets into bases                            */
-    const int32_t* tid;         /* mate contig  (core.mtid)                          */
+    const int32_t* tid;         /* mate contig  (core.mtid), an index into the contigs
+                                   of im_set_reference.  A read whose tid lies outside
+                                   [0, n_contigs) touches no reference byte: its result
+                                   is IM_ST_ABORT with n_ev = 0 (the call returns
+                                   IM_E_ABORT), whatever its length and the parameters,
+                                   and the other reads of the batch are not affected.
+                                   The same holds for im_dev_batch.tid.              */
     const int32_t* anchor;      /* mate position (core.mpos)                         */
     const int32_t* range_max;   /* range[1] of the read group                        */
 } im_read_batch;
@@ -489,7 +495,10 @@ int im_depth_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, 
 /* the same, and per query the DEEPEST position of [beg - 1, end] (max_out, may be NULL).  The depth array counts every record; samtools'
  * pileup, which the reference's DP= comes from (src/shared.c:178-212), stops buffering records that start at the position it stands on
  * once 8000 are buffered (src/samtools-0.1.19/bam_pileup.c:172,244): the host driver asks the file, with that rule, about the queries
- * whose maximum says the rule may have applied. */
+ * whose maximum says the rule may have applied.
+ * With a = max(beg, 0) and b = min(end, contig length): sum_out = the sum of depth[a .. b - 1]; max_out = the largest depth[p] over
+ * p = (a > 0 ? a - 1 : a) .. (b < contig length ? b : b - 1).  A query with beg >= end, or one that does not meet the contig
+ * (a >= b), answers sum 0 and an UNSPECIFIED maximum. */
 int im_depth_query_max_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out, uint32_t* max_out);
 /* im_depth_median over contig tid's run of the genome-wide array, behind im_depth_scan: the lower median of min(depth, 4095)
  * over [beg, end) clipped to the contig, 0xFFFFFFFF for a query that is empty after the clip (the same definition, the same

@@ -209,6 +209,7 @@ def lib():
         L.im_depth_reset.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.im_depth_query_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_depth_median_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_depth_query_max_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_span_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.im_dev_span_scatter.argtypes = [C.c_void_p, C.POINTER(DevRecords), C.c_void_p]
         L.im_span_scan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
@@ -537,6 +538,17 @@ class Context:
 
     def depth_query_tid(self, tid, beg, end):
         return self._query_tid(lib().im_depth_query_tid, tid, beg, end)
+
+    def depth_query_max_tid(self, tid, beg, end):
+        """(sum, max) per query on contig tid (after depth_scan): the sum over [beg, end) as depth_query_tid gives it, and the deepest
+        position of [beg - 1, end], both clipped to the contig"""
+        beg = np.ascontiguousarray(beg, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        assert len(beg) == len(end)
+        n = len(beg)
+        total, deepest = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2))
+        self._check(lib().im_depth_query_max_tid(self.h, int(tid), n, _ptr(beg), _ptr(end), _ptr(total), _ptr(deepest)))
+        return total[:n], deepest[:n]
 
     def depth_median_tid(self, tid, beg, end):
         """depth_median over contig tid's run of the genome-wide array (after depth_scan)"""

@@ -924,7 +924,9 @@ __global__ __launch_bounds__(256) void any_pick_kernel(RealignArgs A, int all, i
             any_finish(out, (off & 3) ? IM_ST_UNSUPPORTED : bad ? IM_ST_ABORT : IM_ST_UNSUPPORTED, 0);
             if (bad) continue;
         }
-        if (out->status != IM_ST_UNSUPPORTED || (off & 3) || L <= 0 || tid < 0 || tid >= A.ref.n_contigs) continue;
+        if (out->status != IM_ST_UNSUPPORTED || (off & 3)) continue;
+        // a read the laid-out kernels left for its length before they looked at its contig: no contig, no window (im_read_batch.tid)
+        if (L <= 0 || tid < 0 || tid >= A.ref.n_contigs) { any_finish(out, IM_ST_ABORT, 0); continue; }
         const int clen = A.ref.len[tid], anchor = A.batch.anchor[c];
         const int64_t reach = (int64_t)A.batch.range_max[c] + (int64_t)A.P.maxdelsize;
         const int64_t lo = anchor >= reach ? anchor - reach : 0, hi = (int64_t)anchor + reach > clen ? clen : anchor + reach;
