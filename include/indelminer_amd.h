@@ -841,7 +841,7 @@ int im_pairlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
  * one.  A query walks one probe run per bucket of [a0, a1], at most 257.
  *
  * im_matelink_enable allocates the table (16 << log2_slots bytes of HBM, on this call only; the reference must be set, at most 2^24
- * contigs) and fixes min_mapq: a second call with other values is refused.  A new reference frees it with the other two tables.
+ * contigs) and fixes min_mapq: a second call with other values is refused.  A new reference frees it with the other keyed tables.
  * im_dev_matelink_scatter adds the links of a chunk of delivered records (one launch of its own, asynchronous); without
  * im_matelink_enable it is IM_E_ARG with a message.  im_matelink_add adds n links of contig tid the caller names as pos, mtid, mpos and
  * kind 0 .. 3; it applies the rule's range checks itself: a link with mtid outside [0, n_contigs), mtid == tid or a position outside
@@ -877,6 +877,81 @@ int im_matelink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
  * is not set.  Synchronous, on the context's stream. */
 int im_cliptail_junction(im_ctx* ctx, int32_t nq, const int32_t* tid1, const int32_t* p1, const uint8_t* side1, const int32_t* tid2, const int32_t* p2,
                          const uint8_t* side2, int32_t max_shift, uint32_t* v1, uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2);
+
+/* Split links, the reads an aligner has split at a junction (-S).  The piles and the pairs above are indirect: 32 clipped bases compared
+ * with the reference, and the orientation of pairs whose mate's mapping quality is not known.  A read that CROSSES a junction is written
+ * by a split aligner as a primary record with a soft clip, and its SA:Z tag says where the clipped part was placed: contig, position,
+ * strand, CIGAR and that placement's own mapping quality.  A fourth keyed table keeps one link per such record, from the junction end
+ * its clip marks to the junction end the tag names -- the ends (tid, position, side) of im_cliptail_junction -- and a query counts the
+ * links between two ends.
+ *
+ * WHICH RECORDS STORE A LINK.  With c = min_clip >= 1 and q = min_mapq a delivered record stores AT MOST ONE split link, iff all of
+ *   THE FRONT  the core is whole (32 bytes, l_seq >= 0, and the CIGAR and the start of the aux area inside the record); the flag has
+ *     none of 0x4 | 0x100 | 0x200 | 0x400 | 0x800 (each read once, at its primary record; paired or not does not matter);
+ *     0 <= tid < n_contigs; mapq >= q;
+ *   THE CIGAR  has at least one reference-consuming operation (-C's eligibility); first, last = its first and last operation that is
+ *     not H; refend = pos + the lengths of its M = X D N; L1, T1 = the total lengths of its leading and its trailing run of H and S;
+ *   THE TAG  the aux area holds an SA tag; the FIRST occurrence is taken, found by samtools' walk (bam_aux_get: fixed sizes for
+ *     A c C s S i I f d, Z and H to their NUL, B by its header; an unknown type or a field that runs out of the record ends the walk;
+ *     a tail of fewer than 4 bytes is padding); its type is Z; it is NUL-terminated inside the record; and its value is EXACTLY ONE
+ *     entry  rname,pos,strand,cigar,mapQ,NM  followed by ';' NUL or by NUL alone, with
+ *       rname   1 or more bytes, none of ',' ';' NUL
+ *       pos     1 to 10 decimal digits, value 1 .. 2^31 - 1 (1-based)
+ *       strand  '+' or '-'
+ *       cigar   one or more of (1 to 9 digits, then one of MIDNSHP=X)
+ *       mapQ    1 to 3 digits
+ *       NM      1 or more digits (value unused)
+ *     anything else -- a second entry, an empty field, a non-digit, a tag of another type -- stores nothing;
+ *   THE SA ALIGNMENT  tid2 = the contig whose name equals rname byte for byte over its whole length (no prefix match; an unknown name
+ *     stores nothing); p2 = pos - 1; span2 = the sum of its M = X D N lengths (64 bits), span2 >= 1; e2 = p2 + span2 <= length[tid2];
+ *     its mapQ >= q; L2, T2 = the length of its first and of its last operation when that is S or H, else 0;
+ *     same = ((strand == '-') == ((flag >> 4) & 1)); when !same, L2 and T2 are swapped (the entry's CIGAR is written for the other strand);
+ *   WHICH SIDE  BEHIND iff L2 > L1 and T2 < T1 (the other part holds the read's bases behind the primary's); FRONT iff L2 < L1 and
+ *     T2 > T1; neither (a tie in either) stores nothing;
+ *   END A, the primary's   BEHIND: last is S of >= c bases and 0 <= refend <= length[tid]: A = (tid, refend, 0), -C's RIGHT CLIP;
+ *                          FRONT:  first is S of >= c bases and 0 <= pos <= length[tid]:   A = (tid, pos, 1),    -C's LEFT CLIP;
+ *     so a split link always sits on a position and side that clipR or clipL counted;
+ *   END B, the other part's            same strand       other strand
+ *                          BEHIND      (tid2, p2, 1)     (tid2, e2, 0)
+ *                          FRONT       (tid2, e2, 0)     (tid2, p2, 1)
+ * hold.  The link is (tidA, pA, sideA, tidB, pB, sideB), kind = sideA | sideB << 1; tidB == tidA is allowed.  Both delivered record
+ * forms are taken (im_dev_records).
+ *
+ * WORKED EXAMPLES, a read of 100 bases whose primary record is forward on contig tid at x (0-based), the other part on ctgB:
+ *   60M40S, SA:Z:ctgB,p,+,60S40M,60,0;   BEHIND, same strand:   A = (tid, x + 60, 0)  B = (ctgB, p - 1, 1)       kind 2  ("3to5": a deletion, a duplication)
+ *   60M40S, SA:Z:ctgB,p,-,40M60S,60,0;   BEHIND, other strand:  A = (tid, x + 60, 0)  B = (ctgB, p - 1 + 40, 0)  kind 0  ("3to3": an inversion's left junction)
+ *   40S60M, SA:Z:ctgB,p,+,40M60S,60,0;   FRONT, same strand:    A = (tid, x, 1)       B = (ctgB, p - 1 + 40, 0)  kind 1  ("5to3")
+ *   40S60M, SA:Z:ctgB,p,-,60S40M,60,0;   FRONT, other strand:   A = (tid, x, 1)       B = (ctgB, p - 1, 1)       kind 3  ("5to5": an inversion's right junction)
+ *
+ * A QUERY is (tid1, side1, a0, a1, tid2, side2, b0, b1).  Both intervals are inclusive and are clipped to [0, length] of their contig.
+ * The answer is the number of stored links with tidA == tid1, kind == side1 | side2 << 1, a0 <= pA <= a1, tidB == tid2 and
+ * b0 <= pB <= b1; an interval that is empty after the clip answers 0.  a1 - a0 above 65 535 before the clip, a side other than 0 or 1,
+ * a contig outside the reference, or a null array with nq >= 1 is IM_E_ARG.  No answer depends on the order in which the links arrived.
+ *
+ * THE TABLE has 2^log2_slots slots of 16 bytes (6 <= log2_slots <= 30), the design of the other three: a multimap with open addressing;
+ * the home slot of a link is (key * 0x9E3779B97F4A7C15) >> (64 - log2_slots) with key = 1 << 63 | tidA << 26 | (pA >> 8) << 2 | kind, so
+ * all links of one (tidA, 256-base bucket, kind) lie on one probe run; the payload is (pA & 255) | tidB << 8 | pB << 32; probing is
+ * linear and wraps.  Only half of the slots are ever taken: the number stored is exactly min(links asked for, 2^log2_slots / 2) and the
+ * rest are counted as dropped.  Once dropped > 0 im_splitlink_count returns IM_OK and fills every count of the call with 0xFFFFFFFF:
+ * no answer, not a wrong one.  A query walks one probe run per bucket of [a0, a1], at most 257.
+ *
+ * im_splitlink_enable allocates the table (16 << log2_slots bytes of HBM, on this call only) and fixes min_clip, min_mapq and the contig
+ * names: the reference must be set, n_names must equal its number of contigs, and names[i] is contig i's name as the BAM header spells
+ * it.  A null or empty name, two equal names, min_clip < 1 and log2_slots outside 6 .. 30 are IM_E_ARG with a message; a second call
+ * with other values is refused.  A new reference frees the table with the other three.  im_dev_splitlink_scatter adds the links of a
+ * chunk of delivered records (one launch of its own, asynchronous); without im_splitlink_enable it is IM_E_ARG with a message.
+ * im_splitlink_add adds n links the caller names as six columns; it applies the rule's range checks itself: a link with a contig
+ * outside the reference or a position outside [0, length] of its contig is dropped without counting (a side other than 0 or 1 is
+ * IM_E_ARG); synchronous.  im_splitlink_count answers nq queries; synchronous, on the context's stream.  im_splitlink_reset puts all
+ * slots and both counters back to zero.  im_splitlink_stats gives the links stored and dropped since the last reset; synchronous. */
+int im_splitlink_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq, int32_t log2_slots, int32_t n_names, const char* const* names);
+int im_dev_splitlink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream);
+int im_splitlink_add(im_ctx* ctx, int32_t n, const int32_t* tid, const int32_t* pos, const uint8_t* side, const int32_t* tid2, const int32_t* pos2,
+                     const uint8_t* side2);
+int im_splitlink_count(im_ctx* ctx, int32_t nq, const int32_t* tid1, const uint8_t* side1, const int32_t* a0, const int32_t* a1,
+                       const int32_t* tid2, const uint8_t* side2, const int32_t* b0, const int32_t* b1, uint32_t* count_out);
+int im_splitlink_reset(im_ctx* ctx, void* stream);
+int im_splitlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
 
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 

@@ -257,6 +257,12 @@ def lib():
         L.im_matelink_partner.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 8
         L.im_matelink_reset.argtypes = [C.c_void_p, C.c_void_p]
         L.im_matelink_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.im_splitlink_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_char_p)]
+        L.im_dev_splitlink_scatter.argtypes = [C.c_void_p, C.POINTER(DevRecords), C.c_void_p]
+        L.im_splitlink_add.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+        L.im_splitlink_count.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
+        L.im_splitlink_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.im_splitlink_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.im_cliptail_junction.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 5
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -792,6 +798,42 @@ class Context:
     def matelink_stats(self):
         """(links stored, links dropped) since the last reset"""
         return self._keyed_stats(lib().im_matelink_stats)
+
+    def splitlink_enable(self, min_clip, min_mapq, log2_slots, names):
+        """the keyed table of split links (-S): 2^log2_slots slots of 16 bytes, half of them usable; names: the contigs' names as the
+        BAM header spells them (str or bytes; None stands for a null pointer), in tid order"""
+        names = [n.encode() if isinstance(n, str) else n for n in names]
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        self._check(lib().im_splitlink_enable(self.h, int(min_clip), int(min_mapq), int(log2_slots), len(names), arr))
+
+    def splitlink_scatter(self, recs, stream=None):
+        """DevRecords -> one link per soft-clipped primary record whose SA:Z tag holds one entry (asynchronous)"""
+        self._keyed_scatter(lib().im_dev_splitlink_scatter, recs, stream)
+
+    def splitlink_add(self, tid, pos, side, tid2, pos2, side2):
+        """links as the caller found them, six columns: end A (tid, pos, side) and end B (tid2, pos2, side2)"""
+        tid, pos, tid2, pos2 = (np.ascontiguousarray(x, dtype=np.int32) for x in (tid, pos, tid2, pos2))
+        side, side2 = (np.ascontiguousarray(x, dtype=np.uint8) for x in (side, side2))
+        assert len(tid) == len(pos) == len(side) == len(tid2) == len(pos2) == len(side2)
+        self._check(lib().im_splitlink_add(self.h, len(tid), _ptr(tid), _ptr(pos), _ptr(side), _ptr(tid2), _ptr(pos2), _ptr(side2)))
+
+    def splitlink_count(self, tid1, side1, a0, a1, tid2, side2, b0, b1):
+        """per query (tid1, side1, [a0, a1], tid2, side2, [b0, b1]): the links from the first end to the second; after an overflow
+        every count is 0xFFFFFFFF"""
+        tid1, a0, a1, tid2, b0, b1 = (np.ascontiguousarray(x, dtype=np.int32) for x in (tid1, a0, a1, tid2, b0, b1))
+        side1, side2 = (np.ascontiguousarray(x, dtype=np.uint8) for x in (side1, side2))
+        n = len(tid1)
+        assert len(side1) == len(a0) == len(a1) == len(tid2) == len(side2) == len(b0) == len(b1) == n
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(lib().im_splitlink_count(self.h, n, _ptr(tid1), _ptr(side1), _ptr(a0), _ptr(a1), _ptr(tid2), _ptr(side2), _ptr(b0), _ptr(b1), _ptr(out)))
+        return out[:n]
+
+    def splitlink_reset(self, stream=None):
+        self._keyed_reset(lib().im_splitlink_reset, stream)
+
+    def splitlink_stats(self):
+        """(links stored, links dropped) since the last reset"""
+        return self._keyed_stats(lib().im_splitlink_stats)
 
     def cliptail_junction(self, tid1, p1, side1, tid2, p2, side2, max_shift=32):
         """per query of two ends (tid, position, side 0: right clips, 1: left clips): (v1, v2, shift, stored1, stored2) -- the entries of

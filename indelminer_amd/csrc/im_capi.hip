@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 #include <unordered_map>
 #include <mutex>
@@ -71,8 +72,11 @@ struct im_ctx {
     GenomeArray all_depth, all_span, all_pair;
     // genome-wide clipped-read counts, right and left (im_clip_enable): flank holds min_clip; never scanned, their sums stay null
     GenomeArray all_clip_r, all_clip_l;
-    // the keyed tables, an allocation each: -V the clipped bases, -M the pair links, -T the mate links
-    KeyedMember tail{"im_cliptail_enable"}, link{"im_pairlink_enable"}, mate{"im_matelink_enable"};
+    // the keyed tables, an allocation each: -V the clipped bases, -M the pair links, -T the mate links, -S the split links
+    KeyedMember tail{"im_cliptail_enable"}, link{"im_pairlink_enable"}, mate{"im_matelink_enable"}, split{"im_splitlink_enable"};
+    // the contig names im_splitlink_enable was given, and their blob on the device (im_links.hip has the layout)
+    std::vector<std::string> split_names;
+    uint8_t* split_blob = nullptr;
     // the median queries' histograms of queries of several slabs (im::launch_depth_median): zeros between calls, sized by the call that
     // needed the most; med_dirty: a call did not get to its end, the next one clears them
     uint32_t* med_scratch = nullptr;
@@ -162,15 +166,17 @@ void free_reference(im_ctx* ctx)
         g->data = nullptr; g->sums = nullptr;
     }
     ctx->h_asc_off.clear(); ctx->h_len.clear(); ctx->ref_total = 0;
-    // the clip-tail table, the pair-link table and the mate-link table are keyed by the contigs of the reference that goes
-    for (KeyedMember* t : {&ctx->tail, &ctx->link, &ctx->mate}) {
+    // the clip-tail table and the three link tables are keyed by the contigs of the reference that goes
+    for (KeyedMember* t : {&ctx->tail, &ctx->link, &ctx->mate, &ctx->split}) {
         if (t->slots) (void)hipFree(t->slots);
         if (t->counters) (void)hipFree(t->counters);
         *t = KeyedMember(t->enable);
     }
+    if (ctx->split_blob) (void)hipFree(ctx->split_blob);
+    ctx->split_blob = nullptr; ctx->split_names.clear();
 }
 
-// ---- the keyed table (im_keyed.hpp) behind the clip tails (im_ctx::tail), the pair links (im_ctx::link) and the mate links (im_ctx::mate) ----------
+// ---- the keyed table (im_keyed.hpp) behind the clip tails (im_ctx::tail), the pair links (im_ctx::link), the mate links (im_ctx::mate) and the split links (im_ctx::split) ----------
 
 // An enable call from its first check to its last.  min_clip: null for the families that have none.  A member that is enabled already
 // takes the same parameters again and no others; otherwise its slots and counters are allocated, cleared and waited for.
@@ -251,7 +257,7 @@ int keyed_stats(im_ctx* ctx, KeyedMember im_ctx::*which, uint64_t* stored, uint6
     return IM_OK;
 }
 
-// The workspace as columns of n elements for the entry points of the three tables: column k at k * up256(4 n) bytes (a column of 8-byte
+// The workspace as columns of n elements for the entry points of the four tables: column k at k * up256(4 n) bytes (a column of 8-byte
 // elements takes two), host -> device and back on the context's stream.
 struct WsColumns {
     im_ctx* ctx;
@@ -567,6 +573,48 @@ int link_scatter(im_ctx* ctx, KeyedMember im_ctx::*which, const im_dev_records* 
 {
     return keyed_scatter(ctx, which, recs, stream, [launch](const im::RefDev& ref, const KeyedMember& T, const im_dev_records& r, hipStream_t st) {
         return launch(ref, T.min_mapq, r, T, st); });
+}
+
+// The names as the blob contig_of_name (im_links.hip) reads: [bins][n][bin_start bins + 1][tid n][name_off n][name_len n][names], the
+// entries in bin order; the bin of a name is its 32-bit FNV-1a hash & (bins - 1)
+std::vector<uint8_t> split_name_blob(const std::vector<std::string>& names)
+{
+    const int32_t n = (int32_t)names.size();
+    int32_t bins = 16;
+    while (bins < n && bins < (1 << 20)) bins <<= 1;
+    std::vector<uint32_t> bin(n);
+    std::vector<int32_t> start(bins + 1, 0);
+    for (int32_t i = 0; i < n; i++) {
+        uint32_t h = 2166136261u;
+        for (unsigned char c : names[i]) h = (h ^ c) * 16777619u;
+        bin[i] = h & (uint32_t)(bins - 1);
+        start[bin[i] + 1]++;
+    }
+    for (int32_t b = 0; b < bins; b++) start[b + 1] += start[b];
+    std::vector<int32_t> at(start.begin(), start.end() - 1), e_tid(n), e_off(n), e_len(n);
+    std::string bytes;
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t e = at[bin[i]]++;
+        e_tid[e] = i; e_off[e] = (int32_t)bytes.size(); e_len[e] = (int32_t)names[i].size();
+        bytes += names[i];
+    }
+    std::vector<int32_t> words = {bins, n};
+    words.insert(words.end(), start.begin(), start.end());
+    words.insert(words.end(), e_tid.begin(), e_tid.end());
+    words.insert(words.end(), e_off.begin(), e_off.end());
+    words.insert(words.end(), e_len.begin(), e_len.end());
+    std::vector<uint8_t> blob(words.size() * 4 + bytes.size());
+    memcpy(blob.data(), words.data(), words.size() * 4);
+    memcpy(blob.data() + words.size() * 4, bytes.data(), bytes.size());
+    return blob;
+}
+
+// the sides of the add and the count calls (what: "link", "query")
+int split_sides(im_ctx* ctx, const char* who, const char* what, int32_t n, const uint8_t* side1, const uint8_t* side2)
+{
+    for (int32_t i = 0; i < n; i++)
+        if (side1[i] > 1 || side2[i] > 1) { set_err(ctx, "%s: %s %d: sides %d and %d, must be 0 (right) or 1 (left)", who, what, i, (int)side1[i], (int)side2[i]); return IM_E_ARG; }
+    return IM_OK;
 }
 
 }  // namespace
@@ -1681,6 +1729,99 @@ int im_matelink_partner(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kin
     HIP_TRY(ctx, im::launch_matelink_partner(nq, tid, C.at<uint8_t>(2), C.at<int32_t>(0), C.at<int32_t>(1), ctx->h_len[tid], ctx->mate, C.at<uint32_t>(3),
                                              C.at<int32_t>(4), C.at<uint32_t>(5), C.at<int32_t>(6), C.at<int32_t>(7), ctx->stream));
     return keyed_answers(ctx, ctx->mate, C, 3, {{n_links, 4}, {mtid_out, 4}, {n_partner, 4}, {lo, 4}, {hi, 4}});
+}
+
+// ---- split links: the soft-clipped primary records whose SA:Z tag places the clipped part, counted between two junction ends (-S) ----------
+
+int im_splitlink_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq, int32_t log2_slots, int32_t n_names, const char* const* names)
+{
+    if (!ctx) return IM_E_ARG;
+    if (!ctx->ref_ascii) { set_err(ctx, "im_set_reference has not been called"); return IM_E_ARG; }
+    if (n_names != ctx->n_contigs || !names) { set_err(ctx, "im_splitlink_enable: %d names for %d contigs", names ? n_names : 0, ctx->n_contigs); return IM_E_ARG; }
+    std::vector<std::string> list;
+    std::unordered_map<std::string, int32_t> seen;
+    for (int32_t i = 0; i < n_names; i++) {
+        if (!names[i] || !names[i][0]) { set_err(ctx, "im_splitlink_enable: name %d is null or empty", i); return IM_E_ARG; }
+        const auto ins = seen.emplace(names[i], i);
+        if (!ins.second) { set_err(ctx, "im_splitlink_enable: names %d and %d are equal (%s)", ins.first->second, i, names[i]); return IM_E_ARG; }
+        list.emplace_back(names[i]);
+    }
+    if (ctx->split.slots) {
+        if (list != ctx->split_names) { set_err(ctx, "im_splitlink_enable: already enabled with other contig names"); return IM_E_ARG; }
+        return keyed_enable(ctx, &im_ctx::split, &min_clip, min_mapq, log2_slots);      // the same values again, or the refusal
+    }
+    const int rc = keyed_enable(ctx, &im_ctx::split, &min_clip, min_mapq, log2_slots);
+    if (rc) return rc;
+    const std::vector<uint8_t> blob = split_name_blob(list);
+    hipError_t e = hipMalloc((void**)&ctx->split_blob, blob.size());
+    if (e == hipSuccess) e = hipMemcpy(ctx->split_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        // no table without its names
+        if (ctx->split_blob) (void)hipFree(ctx->split_blob);
+        (void)hipFree(ctx->split.slots); (void)hipFree(ctx->split.counters);
+        ctx->split = KeyedMember(ctx->split.enable); ctx->split_blob = nullptr;
+        set_err(ctx, "im_splitlink_enable: the name table: %s", hipGetErrorString(e));
+        return IM_E_HIP;
+    }
+    ctx->split_names = list;
+    return IM_OK;
+}
+
+int im_splitlink_reset(im_ctx* ctx, void* stream) { return keyed_reset(ctx, &im_ctx::split, stream); }
+int im_splitlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped) { return keyed_stats(ctx, &im_ctx::split, stored, dropped); }
+
+int im_dev_splitlink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
+{
+    const uint8_t* names = ctx ? ctx->split_blob : nullptr;
+    return keyed_scatter(ctx, &im_ctx::split, recs, stream, [names](const im::RefDev& ref, const KeyedMember& T, const im_dev_records& r, hipStream_t st) {
+        return im::launch_splitlink_scatter(ref, T.min_clip, T.min_mapq, names, r, T, st); });
+}
+
+// the host names the links: checked here, staged through the workspace, one lane inserts each, wait
+int im_splitlink_add(im_ctx* ctx, int32_t n, const int32_t* tid, const int32_t* pos, const uint8_t* side, const int32_t* tid2, const int32_t* pos2,
+                     const uint8_t* side2)
+{
+    if (!ctx || n < 0 || (n > 0 && (!tid || !pos || !side || !tid2 || !pos2 || !side2))) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->split, nullptr);
+    if (rc || (rc = split_sides(ctx, "im_splitlink_add", "link", n, side, side2))) return rc;
+    if (n == 0) return IM_OK;
+    WsColumns C;                                                    // tid, pos, tid2, pos2, side, side2
+    rc = ws_columns(ctx, n, 6, &C);
+    const int32_t* h_in[4] = {tid, pos, tid2, pos2};
+    for (int k = 0; k < 4 && !rc; k++) rc = C.down(k, h_in[k], 4);
+    if (rc || (rc = C.down(4, side, 1)) || (rc = C.down(5, side2, 1))) return rc;
+    HIP_TRY(ctx, im::launch_splitlink_add(ref_dev(ctx), n, C.at<int32_t>(0), C.at<int32_t>(1), C.at<uint8_t>(4), C.at<int32_t>(2), C.at<int32_t>(3),
+                                          C.at<uint8_t>(5), ctx->split, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+// eight columns in, one launch, the counts and the two counters back, one wait; after an overflow every answer is "none"
+int im_splitlink_count(im_ctx* ctx, int32_t nq, const int32_t* tid1, const uint8_t* side1, const int32_t* a0, const int32_t* a1, const int32_t* tid2,
+                       const uint8_t* side2, const int32_t* b0, const int32_t* b1, uint32_t* count_out)
+{
+    if (!ctx || nq < 0) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->split, nullptr);
+    if (rc) return rc;
+    if (nq == 0) return IM_OK;
+    if (!tid1 || !side1 || !a0 || !a1 || !tid2 || !side2 || !b0 || !b1 || !count_out) return IM_E_ARG;
+    if ((rc = split_sides(ctx, "im_splitlink_count", "query", nq, side1, side2))) return rc;
+    for (int32_t q = 0; q < nq; q++) {
+        if (tid1[q] < 0 || tid1[q] >= ctx->n_contigs || tid2[q] < 0 || tid2[q] >= ctx->n_contigs) {
+            set_err(ctx, "im_splitlink_count: query %d: contigs %d and %d, must be 0 .. %d", q, tid1[q], tid2[q], ctx->n_contigs - 1);
+            return IM_E_ARG;
+        }
+        const long long span = (long long)a1[q] - (long long)a0[q];
+        if (span > 65535) { set_err(ctx, "im_splitlink_count: query %d: a1 - a0 = %lld, must be <= 65535", q, span); return IM_E_ARG; }
+    }
+    WsColumns C;                                                    // tid1, a0, a1, tid2, b0, b1, side1, side2, the counts
+    rc = ws_columns(ctx, nq, 9, &C);
+    const int32_t* h_in[6] = {tid1, a0, a1, tid2, b0, b1};
+    for (int k = 0; k < 6 && !rc; k++) rc = C.down(k, h_in[k], 4);
+    if (rc || (rc = C.down(6, side1, 1)) || (rc = C.down(7, side2, 1))) return rc;
+    HIP_TRY(ctx, im::launch_splitlink_count(ref_dev(ctx), nq, C.at<int32_t>(0), C.at<uint8_t>(6), C.at<int32_t>(1), C.at<int32_t>(2), C.at<int32_t>(3),
+                                            C.at<uint8_t>(7), C.at<int32_t>(4), C.at<int32_t>(5), ctx->split, C.at<uint32_t>(8), ctx->stream));
+    return keyed_answers(ctx, ctx->split, C, 8, {{count_out, 4}});
 }
 
 // six columns in, one launch, the five answers and the two counters back, one wait; after an overflow every answer is "none"

@@ -139,7 +139,7 @@ hipError_t launch_clip_facing(const int32_t* right, const int32_t* left, int64_t
 // written, in no particular order
 hipError_t launch_clip_peaks(const int32_t* arr, int64_t clen, int32_t min_reads, int32_t reach, int32_t cap, int32_t* pos, uint32_t* count,
                              uint32_t* n_found, hipStream_t stream);
-// The keyed table behind the clip tails (-V), the pair links (-M) and the mate links (-T), an allocation each; im_keyed.hpp has its definition.  slots:
+// The keyed table behind the clip tails (-V), the pair links (-M), the mate links (-T) and the split links (-S), an allocation each; im_keyed.hpp has its definition.  slots:
 // 2^log2_slots pairs (key, payload) of 64-bit words, zeros = empty; counters[0]: inserts asked for, counters[1]: those dropped because
 // half of the slots were taken
 struct KeyedTable {
@@ -205,6 +205,20 @@ hipError_t launch_matelink_add(const RefDev& ref, int32_t n, int32_t tid, const 
 hipError_t launch_matelink_partner(int32_t nq, int32_t tid, const uint8_t* kind, const int32_t* a0, const int32_t* a1, int64_t clen,
                                    const KeyedTable& tab, uint32_t* n_links, int32_t* mtid, uint32_t* n_partner, int32_t* lo, int32_t* hi,
                                    hipStream_t stream);
+// im_links.hip: the split reads (a soft-clipped primary record and its SA:Z tag) in a keyed table of its own (-S)
+// the records that are a link under the record rule (include/indelminer_amd.h, "Split links") -> one entry each; names: the contig-name
+// blob of im_splitlink_enable
+hipError_t launch_splitlink_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const uint8_t* names, const im_dev_records& recs,
+                                    const KeyedTable& tab, hipStream_t stream);
+// one entry per host-named (tid, pos, side, tid2, pos2, side2); a link that fails the rule's range checks is dropped
+hipError_t launch_splitlink_add(const RefDev& ref, int32_t n, const int32_t* tid, const int32_t* pos, const uint8_t* side, const int32_t* tid2,
+                                const int32_t* pos2, const uint8_t* side2, const KeyedTable& tab, hipStream_t stream);
+// per query (tid1, side1, [a0, a1], tid2, side2, [b0, b1]), both intervals inclusive and clipped to [0, length] of their contig: the
+// links of kind side1 | side2 << 1 from the first to the second; the caller holds the contigs to the reference, the sides to 0 and 1
+// and a1 - a0 to 65 535
+hipError_t launch_splitlink_count(const RefDev& ref, int32_t nq, const int32_t* tid1, const uint8_t* side1, const int32_t* a0, const int32_t* a1,
+                                  const int32_t* tid2, const uint8_t* side2, const int32_t* b0, const int32_t* b1, const KeyedTable& tab,
+                                  uint32_t* count, hipStream_t stream);
 // per query (tid1, p1, side1, tid2, p2, side2): the entries at either end that continue in the OTHER end's contig at the best shift
 // 0 .. max_shift <= 32 (include/indelminer_amd.h, "Junctions"), that shift (-1: none matched), and the entries stored at the two keys
 struct TailJunctionArgs {

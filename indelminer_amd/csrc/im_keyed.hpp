@@ -1,6 +1,6 @@
-// im_keyed.hpp -- the keyed table behind the clip tails (-V, im_cliptail.hip), the pair links (-M) and the mate links (-T, both
-// im_links.hip): its one definition (gfx950).  DESIGN.md 4.5f has the cost.  The three users keep their key and payload layouts and what
-// they do with an entry.
+// im_keyed.hpp -- the keyed table behind the clip tails (-V, im_cliptail.hip), the pair links (-M), the mate links (-T) and the split
+// links (-S, all three im_links.hip): its one definition (gfx950).  DESIGN.md 4.5f has the cost.  The four users keep their key and
+// payload layouts and what they do with an entry.
 //
 // THE TABLE (KeyedTable, im_device.hpp): 2^k slots of 16 bytes in HBM, open addressing, a multimap.
 //   word 0   the key: bit 63 set, so that an empty slot is 0; the other bits are the user's

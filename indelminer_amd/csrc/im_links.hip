@@ -1,8 +1,10 @@
-// im_links.hip -- the two families of read pairs kept as links in keyed tables of their own (gfx950):
+// im_links.hip -- the three families of links kept in keyed tables of their own (gfx950): two of read pairs, one of split reads:
 //   the PAIR LINKS (-M): the read pairs whose orientation says "junction", counted between two windows.  The definition is in
 //     include/indelminer_amd.h (seam 5, "Pair links"); DESIGN.md 4.5j has the cost.
 //   the MATE LINKS (-T): the read pairs whose mate lies on ANOTHER contig, asked where the mates of the reads around a position lie.
 //     The definition is in include/indelminer_amd.h (seam 5, "Mate links"); DESIGN.md 4.5k has the cost.
+//   the SPLIT LINKS (-S): the primary records whose SA:Z tag places their clipped part elsewhere, counted between two junction ends.
+//     The definition is in include/indelminer_amd.h (seam 5, "Split links"); DESIGN.md 4.5l has the rest.
 //
 // PAIR LINKS  A delivered record that is the leftmost of a pair on one contig, both reads mapped, neither read in the normal orientation
 // (forward in front of reverse), stores ONE LINK (tid, kind, pos, mpos): kind 0 EVERTED (this read reverse, its mate forward: a tandem
@@ -11,9 +13,15 @@
 // MATE LINKS  A delivered record that is paired, both reads mapped, its mate on another contig, stores ONE LINK (tid, kind, pos, mtid,
 // mpos) at its own contig: kind = r | m << 1, r = this read reverse, m = its mate reverse.  Both reads of a pair store one each.
 //
+// SPLIT LINKS  A delivered primary record with a qualifying soft clip whose SA:Z tag holds exactly one entry stores ONE LINK
+// (tidA, pA, sideA, tidB, pB, sideB): end A is the clip's (-C's position and side), end B where the entry's alignment continues;
+// kind = sideA | sideB << 1.  The front of its rule differs from the pairs' (paired or not does not matter) and it reads the CIGAR
+// and the aux area, so it has a scatter kernel of its own; the key, the tickets, the insert and the bucket walk are the shared ones.
+//
 // THE TABLES are keyed tables of im_keyed.hpp (slots, tickets, claim, walk), an allocation each, with
-//   word 0   the key, BOTH FAMILIES': bit 63 set (an empty slot is 0) | tid << 26 | (pos >> 8) << 2 | kind   (tid < 2^24, pos < 2^31)
+//   word 0   the key, EVERY FAMILY'S: bit 63 set (an empty slot is 0) | tid << 26 | (pos >> 8) << 2 | kind   (tid < 2^24, pos < 2^31)
 //   word 1   the payload, the family's own:   pair links  pos | mpos << 32        mate links  pos & 255 | mtid << 8 | mpos << 32
+//                                                       split links  pA & 255 | tidB << 8 | pB << 32   (the key: tidA, pA >> 8)
 // The whole key enters the hash: every link of one (tid, 256-base bucket, kind) lies on one probe run.
 //
 // SHARED: the key, the bucket, the block sizes, the scatter (link_scatter<Rule>: the front of the record rule, the tickets, the insert)
@@ -26,6 +34,10 @@
 //   pairlink_count     one wave per query (kind, a0, a1, b0, b1): the links with pos in [a0, a1], mpos in [b0, b1], mpos - pos >= min_sep
 //   matelink_partner   one wave per query (kind, a0, a1): the links with pos in [a0, a1] vote for the cell (mtid, mpos >> 10) of their
 //                      mate in a table in LDS; the pair of neighbouring cells with the most links wins
+//   splitlink_scatter  one lane per delivered record: front, CIGAR ends, then -- the few lanes with a qualifying clip -- the walk to
+//                      SA:Z (find_tag, im_rg.hpp), the parse of its one entry and the contig-name look-up; tickets as above
+//   splitlink_add      one lane per link the caller names, as six columns
+//   splitlink_count    one wave per query (tid1, side1, [a0, a1], tid2, side2, [b0, b1]): the links between the two ends
 
 #include "im_keyed.hpp"
 #include "im_rg.hpp"
@@ -330,6 +342,241 @@ __global__ __launch_bounds__(kLinkWaveBlock) void matelink_partner_kernel(MatePa
     }
 }
 
+// ---- the split links (-S) ----------
+
+__device__ __forceinline__ uint64_t split_payload(int64_t pa, int32_t tidb, int64_t pb)
+{
+    return (uint64_t)((uint32_t)pa & 255u) | ((uint64_t)(uint32_t)tidb << 8) | ((uint64_t)(uint32_t)pb << 32);
+}
+
+// The contig names as one blob, the layout idea of RgView (im_rg.hpp), built by im_splitlink_enable:
+//   int32 [0] bins (a power of two)  [1] n   [2 .. 2 + bins] bin_start   then tid[n], name_off[n], name_len[n] in bin order, then the names
+// The bin of a name is its 32-bit FNV-1a hash & (bins - 1).  The compare is exact, over the whole length: ctg1 is not ctg10.
+__device__ __forceinline__ uint32_t name_hash_step(uint32_t h, uint32_t byte) { return (h ^ byte) * 16777619u; }
+constexpr uint32_t kNameHashSeed = 2166136261u;
+
+__device__ __forceinline__ int32_t contig_of_name(const uint8_t* blob, const uint8_t* name, uint32_t len, uint32_t hash)
+{
+    const int32_t* w = reinterpret_cast<const int32_t*>(blob);
+    const int32_t bins = w[0], n = w[1];
+    const int32_t* bin_start = w + 2;
+    const int32_t* e_tid = bin_start + bins + 1;
+    const int32_t* e_off = e_tid + n;
+    const int32_t* e_len = e_off + n;
+    const uint8_t* names = reinterpret_cast<const uint8_t*>(e_len + n);
+    const uint32_t bin = hash & (uint32_t)(bins - 1);
+    for (int32_t e = bin_start[bin]; e < bin_start[bin + 1]; e++) {
+        if ((uint32_t)e_len[e] != len) continue;
+        const uint8_t* en = names + e_off[e];
+        bool same = true;
+        for (uint32_t i = 0; i < len && same; i++) same = en[i] == name[i];
+        if (same) return e_tid[e];
+    }
+    return -1;
+}
+
+// What the one entry of an SA:Z value says (include/indelminer_amd.h, "Split links", the table of fields)
+struct SaEntry {
+    uint32_t o_name, name_len, name_hash;
+    int64_t pos;            // 1-based, 1 .. 2^31 - 1
+    int64_t span;           // its M = X D N lengths
+    uint32_t lead, trail;   // its first / last operation's length when that is S or H, else 0
+    uint32_t mapq;
+    bool minus;
+};
+
+// The value from offset o on, a byte per pass: the loop is the WAVE's, the lanes that are done (or never parse: `on` false)
+// predicated; a pass ends at the record's end at the latest (o < r.len wherever a byte is read or the window moved).  true iff the
+// value is exactly one well-formed entry followed by ';' NUL or by NUL.
+__device__ __forceinline__ bool parse_sa(const RecView& r, AuxWin& w, uint32_t o, bool on, SaEntry* e)
+{
+    e->o_name = o; e->name_len = 0; e->name_hash = kNameHashSeed; e->pos = 0; e->span = 0; e->lead = e->trail = 0; e->mapq = 0; e->minus = false;
+    // st: 0 rname, 1 pos, 2 strand, 3 the comma behind it, 4 cigar, 5 mapQ, 6 NM, 7 behind ';'
+    uint32_t st = 0, nd = 0, nops = 0;
+    uint64_t val = 0;
+    bool ok = false;
+    for (;;) {
+        on = on && o < r.len;
+        if (__ballot(on) == 0ull) break;
+        const bool mv = on && o - w.o0 >= (uint32_t)kAuxWin;
+        if (__ballot(mv) != 0ull) { if (mv) aux_slide(r, w, o); }
+        if (on) {
+            const uint32_t b = win_byte(w, o, true), d = b - (uint32_t)'0';
+            const bool dig = d < 10u;
+            o++;
+            if (st == 0u) {
+                if (b == ',') { on = e->name_len >= 1u; st = 1u; }
+                else if (b == ';' || b == 0u) on = false;
+                else { e->name_hash = name_hash_step(e->name_hash, b); e->name_len++; }
+            } else if (st == 1u) {
+                if (dig) { nd++; val = val * 10ull + d; on = nd <= 10u; }
+                else { on = b == ',' && nd >= 1u && val >= 1ull && val <= 0x7FFFFFFFull; e->pos = (int64_t)val; st = 2u; }
+            } else if (st == 2u) {
+                on = b == '+' || b == '-'; e->minus = b == '-'; st = 3u;
+            } else if (st == 3u) {
+                on = b == ','; st = 4u; nd = 0u; val = 0ull;
+            } else if (st == 4u) {
+                if (dig) { nd++; val = val * 10ull + d; on = nd <= 9u; }
+                else if (nd >= 1u) {
+                    // MIDNSHP=X
+                    const bool refc = b == 'M' || b == 'D' || b == 'N' || b == '=' || b == 'X', clip = b == 'S' || b == 'H';
+                    on = refc || clip || b == 'I' || b == 'P';
+                    if (refc) e->span += (int64_t)val;
+                    e->trail = clip ? (uint32_t)val : 0u;
+                    if (nops == 0u) e->lead = e->trail;
+                    nops++; nd = 0u; val = 0ull;
+                } else { on = b == ',' && nops >= 1u; st = 5u; }
+            } else if (st == 5u) {
+                if (dig) { nd++; val = val * 10ull + d; on = nd <= 3u; }
+                else { on = b == ',' && nd >= 1u; e->mapq = (uint32_t)val; st = 6u; nd = 0u; }
+            } else if (st == 6u) {
+                if (dig) nd = 1u;
+                else if (nd >= 1u && b == ';') st = 7u;
+                else { ok = nd >= 1u && b == 0u; on = false; }
+            } else {
+                ok = b == 0u; on = false;
+            }
+        }
+    }
+    return ok;
+}
+
+struct SplitScatterArgs {
+    im_dev_records recs;
+    const int32_t* len;
+    int32_t n_contigs, min_clip, min_mapq;
+    const uint8_t* names;       // the contig-name blob
+    KeyedTable tab;
+};
+
+// One lane per record.  The front and the CIGAR ends first; a lane whose record has a qualifying clip (almost none of a usual chunk)
+// walks its CIGAR, and only such lanes send their wave into the tag walk and the parse.  One ticket draw per workgroup; a workgroup
+// without a link ends in front of it.
+__global__ __launch_bounds__(kLinkBlock) void splitlink_scatter_kernel(SplitScatterArgs A)
+{
+    __shared__ uint32_t s_aux[kLinkBlock][kAuxWin / 4];
+    const int64_t i = (int64_t)blockIdx.x * kLinkBlock + threadIdx.x;
+    RecView r = view_record(A.recs.raw, 0u, 0u);
+    if (i < A.recs.n) r = view_record(A.recs.raw, A.recs.rec_off[i], A.recs.rec_off[i + 1]);
+    // the front (r.ok: a whole core, and the CIGAR and the start of the aux area inside the record)
+    const bool front = r.ok && !(r.flag & (0x4u | 0x100u | 0x200u | 0x400u | 0x800u)) && r.tid >= 0 && r.tid < A.n_contigs && (int32_t)r.mapq >= A.min_mapq;
+    const uint32_t n = front ? r.n_cigar : 0u;
+    const uint8_t* cig = r.p + r.o_cigar;
+    // `first` and `last`, the operations that are not H: which ends are soft clips of min_clip bases
+    bool left = false, right = false;
+    if (n >= 2u) {
+        uint32_t kf = 0, kl = n - 1u;
+        while (kf < n && (ld_u32(cig + 4u * kf) & 15u) == 5u) kf++;
+        while (kl > kf && (ld_u32(cig + 4u * kl) & 15u) == 5u) kl--;
+        if (kf < kl) {
+            const uint32_t wf = ld_u32(cig + 4u * kf), wl = ld_u32(cig + 4u * kl);
+            left = (wf & 15u) == 4u && (int64_t)(wf >> 4) >= A.min_clip;
+            right = (wl & 15u) == 4u && (int64_t)(wl >> 4) >= A.min_clip;
+        }
+    }
+    // refend, and L1 / T1: the leading and the trailing run of S and H
+    bool cand = left || right;
+    int64_t refend = r.pos, l1 = 0, t1 = 0;
+    if (cand) {
+        bool consumes = false, lead = true;
+        for (uint32_t k = 0; k < n; k++) {
+            const uint32_t cw = ld_u32(cig + 4u * k), op = cw & 15u;
+            const int64_t ln = (int64_t)(cw >> 4);
+            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) { consumes = true; refend += ln; }
+            if (op == 4u || op == 5u) { t1 += ln; l1 += lead ? ln : 0; }
+            else { lead = false; t1 = 0; }
+        }
+        cand = consumes;
+    }
+    // the tag and its one entry
+    AuxWin w; w.lds = s_aux[threadIdx.x]; w.o0 = 0u;
+    uint32_t type = 0;
+    const uint32_t o_sa = find_tag(r, w, 'S', 'A', cand, &type);
+    SaEntry e;
+    bool has = parse_sa(r, w, o_sa + 1u, cand && o_sa != 0u && type == 'Z', &e);
+    uint64_t key = 0, payload = 0;
+    if (has) {
+        has = false;
+        const int32_t tid2 = contig_of_name(A.names, r.p + e.o_name, e.name_len, e.name_hash);
+        if (tid2 >= 0 && (int32_t)e.mapq >= A.min_mapq && e.span >= 1) {
+            const int64_t p2 = e.pos - 1, e2 = p2 + e.span;
+            const bool same = e.minus == (((r.flag >> 4) & 1u) != 0u);
+            const int64_t l2 = same ? e.lead : e.trail, t2 = same ? e.trail : e.lead;
+            const bool behind = l2 > l1 && t2 < t1, infront = l2 < l1 && t2 > t1;
+            const int64_t clen = A.len[r.tid];
+            int64_t pa = 0;
+            uint32_t side_a = 0;
+            bool end_a = false;
+            if (behind) { end_a = right && refend >= 0 && refend <= clen; pa = refend; side_a = 0u; }
+            if (infront) { end_a = left && r.pos >= 0 && r.pos <= clen; pa = r.pos; side_a = 1u; }
+            if (end_a && e2 <= (int64_t)A.len[tid2]) {
+                // behind on the same strand and in front on the other one continue at the part's start; the other two at its end
+                const bool at_start = behind == same;
+                const int64_t pb = at_start ? p2 : e2;
+                const uint32_t kind = side_a | ((at_start ? 1u : 0u) << 1);
+                key = link_key(r.tid, pa >> kLinkBucketShift, kind);
+                payload = split_payload(pa, tid2, pb);
+                has = true;
+            }
+        }
+    }
+    unsigned long long ticket;
+    if (!keyed_block_tickets<kLinkBlock, 1>(A.tab, has ? 1u : 0u, &ticket)) return;
+    if (has && keyed_admit(A.tab, ticket)) keyed_place(A.tab, keyed_home(key, A.tab.log2_slots), key, payload);
+}
+
+// for callers that name the links themselves, as six columns; a link that fails the rule's range checks is dropped (no ticket)
+__global__ __launch_bounds__(kLinkWaveBlock) void splitlink_add_kernel(int32_t n, const int32_t* __restrict__ len, int32_t n_contigs,
+                                                                       const int32_t* __restrict__ tid, const int32_t* __restrict__ pos,
+                                                                       const uint8_t* __restrict__ side, const int32_t* __restrict__ tid2,
+                                                                       const int32_t* __restrict__ pos2, const uint8_t* __restrict__ side2, KeyedTable tab)
+{
+    const int64_t i = (int64_t)blockIdx.x * kLinkWaveBlock + threadIdx.x;
+    if (i >= n) return;
+    const int32_t ta = tid[i], tb = tid2[i];
+    const int64_t pa = pos[i], pb = pos2[i];
+    const uint32_t sa = side[i], sb = side2[i];
+    if (ta < 0 || ta >= n_contigs || tb < 0 || tb >= n_contigs || sa > 1u || sb > 1u) return;
+    if (pa < 0 || pa > len[ta] || pb < 0 || pb > len[tb]) return;
+    const uint64_t key = link_key(ta, pa >> kLinkBucketShift, sa | (sb << 1));
+    keyed_insert(tab, keyed_home(key, tab.log2_slots), key, split_payload(pa, tb, pb));
+}
+
+struct SplitCountArgs {
+    int32_t nq;
+    const int32_t* tid1; const uint8_t* side1; const int32_t* a0; const int32_t* a1;
+    const int32_t* tid2; const uint8_t* side2; const int32_t* b0; const int32_t* b1;
+    const int32_t* len;
+    KeyedTable tab;
+    uint32_t* count;
+};
+
+// One wave per query (the entry point has held its contigs to the reference and its sides to 0 and 1).  Both intervals are clipped to
+// [0, length] of their contig.  A lane's link counts when its payload passes the tidB and the two position tests; the wave sums by
+// ballot and popcount.
+__global__ __launch_bounds__(kLinkWaveBlock) void splitlink_count_kernel(SplitCountArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int q = wave; q < A.nq; q += nwaves) {
+        const int32_t tid1 = A.tid1[q], tid2 = A.tid2[q];
+        int64_t a0 = A.a0[q], a1 = A.a1[q], b0 = A.b0[q], b1 = A.b1[q];
+        const uint32_t kind = (uint32_t)A.side1[q] | ((uint32_t)A.side2[q] << 1);
+        const bool in_a = link_clip(&a0, &a1, A.len[tid1]), in_b = link_clip(&b0, &b1, A.len[tid2]);
+        uint32_t n = 0;
+        if (in_a && in_b) {
+            link_walk(A.tab, tid1, kind, a0, a1, lane, [&](bool has, int64_t bucket, uint64_t payload) {
+                const int64_t pa = (bucket << kLinkBucketShift) | (int64_t)(payload & 255ull), pb = (int64_t)(uint32_t)(payload >> 32);
+                const int32_t tb = (int32_t)(((uint32_t)payload >> 8) & 0xFFFFFFu);
+                const bool counts = has && pa >= a0 && pa <= a1 && tb == tid2 && pb >= b0 && pb <= b1;
+                n += (uint32_t)__builtin_popcountll(__ballot(counts));
+            });
+        }
+        if (lane == 0) A.count[q] = n;
+    }
+}
+
 template <class Kernel>
 hipError_t launch_link_scatter(Kernel kernel, const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)
 {
@@ -388,6 +635,37 @@ hipError_t launch_matelink_partner(int32_t nq, int32_t tid, const uint8_t* kind,
     A.nq = nq; A.tid = tid; A.kind = kind; A.a0 = a0; A.a1 = a1; A.clen = clen; A.tab = tab;
     A.n_links = n_links; A.mtid = mtid; A.n_partner = n_partner; A.lo = lo; A.hi = hi;
     hipLaunchKernelGGL(matelink_partner_kernel, dim3(wave_grid(nq)), dim3(kLinkWaveBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_splitlink_scatter(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const uint8_t* names, const im_dev_records& recs,
+                                    const KeyedTable& tab, hipStream_t stream)
+{
+    if (recs.n <= 0) return hipSuccess;
+    SplitScatterArgs A;
+    A.recs = recs; A.len = ref.len; A.n_contigs = ref.n_contigs; A.min_clip = min_clip; A.min_mapq = min_mapq; A.names = names; A.tab = tab;
+    hipLaunchKernelGGL(splitlink_scatter_kernel, dim3((recs.n + kLinkBlock - 1) / kLinkBlock), dim3(kLinkBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_splitlink_add(const RefDev& ref, int32_t n, const int32_t* tid, const int32_t* pos, const uint8_t* side, const int32_t* tid2,
+                                const int32_t* pos2, const uint8_t* side2, const KeyedTable& tab, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(splitlink_add_kernel, dim3((n + kLinkWaveBlock - 1) / kLinkWaveBlock), dim3(kLinkWaveBlock), 0, stream, n, ref.len, ref.n_contigs,
+                       tid, pos, side, tid2, pos2, side2, tab);
+    return hipGetLastError();
+}
+
+hipError_t launch_splitlink_count(const RefDev& ref, int32_t nq, const int32_t* tid1, const uint8_t* side1, const int32_t* a0, const int32_t* a1,
+                                  const int32_t* tid2, const uint8_t* side2, const int32_t* b0, const int32_t* b1, const KeyedTable& tab,
+                                  uint32_t* count, hipStream_t stream)
+{
+    if (nq <= 0) return hipSuccess;
+    SplitCountArgs A;
+    A.nq = nq; A.tid1 = tid1; A.side1 = side1; A.a0 = a0; A.a1 = a1; A.tid2 = tid2; A.side2 = side2; A.b0 = b0; A.b1 = b1; A.len = ref.len;
+    A.tab = tab; A.count = count;
+    hipLaunchKernelGGL(splitlink_count_kernel, dim3(wave_grid(nq)), dim3(kLinkWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 

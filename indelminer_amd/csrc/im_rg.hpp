@@ -149,6 +149,52 @@ __device__ __forceinline__ void find_rg_mq(const RecView& r, AuxWin& w, uint32_t
     }
 }
 
+// bam_aux_get for ONE tag (t0, t1), by find_rg_mq's walk rules and in its shape -- the loops are the wave's, the lanes that do not
+// walk (`walk` false) or are done predicated: the offset of the TYPE byte of the first occurrence (0 = absent) and, in *type, that
+// byte.  A lane that walks moves its window itself (o0 = 0 covers no aux byte: an aux area starts behind the 32-byte core), so the
+// caller loads nothing for the lanes that do not walk.  Used by the split-link scatter (im_links.hip); the classify kernel does not
+// call it.
+__device__ __forceinline__ uint32_t find_tag(const RecView& r, AuxWin& w, uint32_t t0, uint32_t t1, bool walk, uint32_t* type_out)
+{
+    uint32_t found = 0;
+    *type_out = 0;
+    uint32_t s = r.o_aux;
+    const uint32_t end = r.len;
+    bool on = walk && s + 4u <= end;
+    while (__ballot(on) != 0ull) {
+        const bool move = on && !aux_covers(w, s, 8u);
+        if (__ballot(move) != 0ull) { if (move) aux_slide(r, w, s); }
+        const uint32_t b0 = win_byte(w, s, on), b1 = win_byte(w, s + 1u, on), type = win_byte(w, s + 2u, on);
+        if (on && b0 == t0 && b1 == t1) { found = s + 2u; *type_out = type; on = false; }
+        s += 3u;
+        const bool str = on && (type == 'Z' || type == 'H'), arr = on && type == 'B';
+        const uint32_t sz = (uint32_t)aux_size(type);
+        if (on && !str && !arr) { on = sz != 0u; s += sz; }
+        if (__ballot(str) != 0ull) {
+            bool go = str;
+            for (;;) {
+                go = go && s < end;
+                const bool mv = go && s - w.o0 >= (uint32_t)kAuxWin;
+                if (__ballot(mv) != 0ull) { if (mv) aux_slide(r, w, s); }
+                go = go && win_byte(w, s, go) != 0u;
+                if (__ballot(go) == 0ull) break;
+                s += go ? 1u : 0u;
+            }
+            s += str ? 1u : 0u;
+        }
+        if (__ballot(arr) != 0ull) {
+            const bool hdr = arr && s + 5u <= end;
+            const uint32_t esz = (uint32_t)aux_size(win_byte(w, s, hdr));
+            const uint32_t cnt = win_byte(w, s + 1u, hdr) | (win_byte(w, s + 2u, hdr) << 8) | (win_byte(w, s + 3u, hdr) << 16) | (win_byte(w, s + 4u, hdr) << 24);
+            const uint64_t ns = (uint64_t)s + 5u + (uint64_t)esz * cnt;
+            const bool fits = hdr && ns <= end;
+            if (arr) { on = fits; s = fits ? (uint32_t)ns : s; }
+        }
+        on = on && s + 4u <= end;
+    }
+    return found;
+}
+
 // The insert-length table as one blob (LDS copy when it is small, else the device original):
 // [bin_start 17][name_off n][name_len n][range_max n][names]
 struct RgView {

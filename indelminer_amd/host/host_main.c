@@ -54,6 +54,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    is the junction's (everted; both forward; both reverse) between two windows at the breakpoints\n");
     fprintf(file, "\t-T, with -G -C -V: write breakpoints between two contigs to this file, a VCF of its own\n");
     fprintf(file, "\t    (a pile of clipped reads on either contig that continue in the other, found through the read pairs that span them)\n");
+    fprintf(file, "\t-S, with -U, -N or -T: add SR= to their records, the split reads (a soft-clipped\n");
+    fprintf(file, "\t    primary record whose SA tag places the clipped part at the other breakpoint), from either end\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -111,7 +113,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:MT:")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:MT:S")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -146,6 +148,7 @@ int main(int argc, char** argv)
         case 'N': g_inv_file = optarg; break;                       /* not an option of the reference */
         case 'M': g_pair_links = 1; break;                          /* not an option of the reference */
         case 'T': g_bnd_file = optarg; break;                       /* not an option of the reference */
+        case 'S': g_split_links = 1; break;                         /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -255,11 +258,18 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: breakpoints between contigs (-T) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -S: behind -T's refusals; every other refusal reaches it through -U, -N or -T, that is through -G, -C and -V */
+    if (g_split_links) {
+        if (!g_dup_file && !g_inv_file && !g_bnd_file) { fprintf(stderr, "indelminer: -S needs -U, -N or -T\n"); return EXIT_FAILURE; }
+        if (!SPLITLINK_API_PRESENT) {
+            fprintf(stderr, "indelminer: split links (-S) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = 0; g_ins_file = g_dup_file = g_inv_file = g_bnd_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
+        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = g_split_links = 0; g_ins_file = g_dup_file = g_inv_file = g_bnd_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {
@@ -416,6 +426,7 @@ int main(int argc, char** argv)
     if (CLIPTAIL_ON) say_overflow(d.gpu, im_cliptail_stats, "indelminer: -V: the clip-tail table overflowed (%llu entries stored, %llu dropped): CV and CH are . from there on\n");
     if (PAIRLINK_ON) say_overflow(d.gpu, im_pairlink_stats, "indelminer: -M: the pair-link table overflowed (%llu links stored, %llu dropped): PE is . in the files of -U and -N\n");
     if (MATELINK_ON) say_overflow(d.gpu, im_matelink_stats, "indelminer: -T: the mate-link table overflowed (%llu links stored, %llu dropped): its file has no records\n");
+    if (SPLITLINK_ON) say_overflow(d.gpu, im_splitlink_stats, "indelminer: -S: the split-link table overflowed (%llu links stored, %llu dropped): SR is . in the files of -U, -N and -T\n");
     if (t_out) fflush(t_out);
     if (g_vcfname != NULL) cpu_report();            /* annotate mode has no replay workers: its report comes here */
     if (!getenv("INDELMINER_TIDY_EXIT")) {

@@ -352,7 +352,7 @@ static int evidence_table_log2(const driver* d)
 }
 
 #define GPU2(drv, call) do { if ((call) != IM_OK) fatalf("%s: %s", #call, im_last_error((drv)->gpu)); } while (0)
-#define EVIDENCE_ON (SPAN_ON || PAIR_ON || CLIP_ON || PAIRLINK_ON || MATELINK_ON)     /* -V needs -C */
+#define EVIDENCE_ON (SPAN_ON || PAIR_ON || CLIP_ON || PAIRLINK_ON || MATELINK_ON || SPLITLINK_ON)     /* -V needs -C */
 
 /* Once per run, on either path, when the reference is on the device and the insert lengths are known: what the evidence options
  * keep on the device.  Genome-wide arrays and tables keyed by contig: nothing is reset between contigs. */
@@ -375,6 +375,10 @@ static void evidence_enable(driver* d)
     if (PAIRLINK_ON) GPU2(d, im_pairlink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
     /* -T: and the table of mate links, of the same size on the same assumption, which nobody has measured here either */
     if (MATELINK_ON) GPU2(d, im_matelink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
+    /* -S: and the table of split links, -C's clip and -q, the contig names as the BAM header spells them, in tid order; the same size
+     * on an assumption of its own (SPLIT_EV_SLOTS_SHIFT), which nobody has measured either */
+    if (SPLITLINK_ON) GPU2(d, im_splitlink_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, evidence_table_log2(d) - SPLIT_EV_SLOTS_SHIFT, d->hdr->n_targets,
+                                                  (const char* const*)d->hdr->target_name));
 }
 
 /* a chunk of records on the device, as they are in the file: each option's record rule is its scatter kernel's, on either path */
@@ -386,6 +390,7 @@ static void evidence_scatter(driver* d, const im_dev_records* recs, void* stream
     if (CLIPTAIL_ON) GPU2(d, im_dev_cliptail_scatter(d->gpu, recs, stream));    /* -V: and one behind it, only then */
     if (PAIRLINK_ON) GPU2(d, im_dev_pairlink_scatter(d->gpu, recs, stream));    /* -M: and one behind that, only then */
     if (MATELINK_ON) GPU2(d, im_dev_matelink_scatter(d->gpu, recs, stream));    /* -T: and one behind that, only then */
+    if (SPLITLINK_ON) GPU2(d, im_dev_splitlink_scatter(d->gpu, recs, stream));  /* -S: and one behind that, only then */
 }
 
 /* The chunks of both paths: the pipelined walk's ring has up to PIPE_NCHUNK of them per walker (host_pipeline.c), the record-at-a-time
@@ -581,6 +586,62 @@ static void fprint_pe(FILE* f, uint32_t pe)
     if (pe == PAIRLINK_NONE) fprintf(f, ";PE=."); else fprintf(f, ";PE=%u", pe);
 }
 
+/* -S: the ##INFO line of SR and the ##splitLinks line, the rule and its constants, the same in the three FILEs */
+static void sr_info(FILE* f)
+{
+    fprintf(f, "##INFO=<ID=SR,Number=2,Type=Integer,Description=\"Split reads whose primary part is clipped within %d bases of the record's first breakpoint and whose SA tag "
+               "places the clipped part within %d bases of its second breakpoint, and the same from the second to the first\">\n", SPLIT_EV_WINDOW, SPLIT_EV_WINDOW);
+}
+static void sr_describe(FILE* f)
+{
+    fprintf(f, "##splitLinks=\"SR counts primary records (neither unmapped, secondary, supplementary, duplicate nor failing quality control; paired or not) of mapping "
+               "quality >= -q with a soft clip of at least %d bases on the side of the breakpoint whose SA tag holds exactly one entry, of mapping quality >= -q, "
+               "inside the contig it names, that places the clipped part of the read: the primary part ends at one breakpoint of the record, on the side the "
+               "record's pile is clipped on, and the other part ends at the other, both within %d bases; the first number counts the reads whose primary record "
+               "lies at the record's first breakpoint, the second those at its second; a tag with several entries is not counted; SR is . once the split-link "
+               "table has overflowed (stderr says so)\"\n", CLIP_EV_MIN_CLIP, SPLIT_EV_WINDOW);
+}
+
+/* -S: SR of n records, two queries each: from the first end (tid1, p1, side1) to the second (tid2, p2, side2), and back; windows of
+ * SPLIT_EV_WINDOW bases around either position (the device clips them to the contig; what an int32 does not hold is clipped here).
+ * sr[k], sr[n + k]: the two counts of record k. */
+static uint32_t* split_links_query(driver* d, int32_t n, const int32_t* tid1, const int32_t* p1, const uint8_t* side1, const int32_t* tid2, const int32_t* p2,
+                                   const uint8_t* side2)
+{
+    const size_t m = 2 * (size_t)(n > 0 ? n : 1);
+    uint32_t* sr = xmalloc(sizeof(uint32_t) * m);
+    int32_t* q = xmalloc(sizeof(int32_t) * 6 * m); uint8_t* qs = xmalloc(2 * m);
+    int32_t* ta = q; int32_t* a0 = q + m; int32_t* a1 = q + 2 * m; int32_t* tb = q + 3 * m; int32_t* b0 = q + 4 * m; int32_t* b1 = q + 5 * m;
+    for (int32_t k = 0; k < 2 * n; k++) {
+        const int back = k >= n;
+        const int32_t j = k % n;
+        const int64_t pa = back ? p2[j] : p1[j], pb = back ? p1[j] : p2[j];
+        ta[k] = back ? tid2[j] : tid1[j]; tb[k] = back ? tid1[j] : tid2[j];
+        qs[k] = back ? side2[j] : side1[j]; qs[m + k] = back ? side1[j] : side2[j];
+        a0[k] = link_clamp(pa - SPLIT_EV_WINDOW); a1[k] = link_clamp(pa + SPLIT_EV_WINDOW);
+        b0[k] = link_clamp(pb - SPLIT_EV_WINDOW); b1[k] = link_clamp(pb + SPLIT_EV_WINDOW);
+    }
+    pthread_mutex_lock(&g_query_mu);
+    const int rc = im_splitlink_count(d->gpu, 2 * n, ta, qs, a0, a1, tb, qs + m, b0, b1, sr);
+    pthread_mutex_unlock(&g_query_mu);
+    if (rc != IM_OK) fatalf("im_splitlink_count: %s", im_last_error(d->gpu));
+    free(q); free(qs);
+    return sr;
+}
+static void fprint_sr(FILE* f, uint32_t n1, uint32_t n2)
+{
+    if (n1 == SPLITLINK_NONE) fprintf(f, ";SR=."); else fprintf(f, ";SR=%u,%u", n1, n2);
+}
+/* the same for the pile pairs of one contig: the ends' positions are columns a and b of pos, the sides s1 and s2 (side: per pair, or null) */
+static uint32_t* split_links_pairs(driver* d, int32_t tid, int32_t n, const int32_t* pa, const int32_t* pb, const uint8_t* side, uint8_t s1, uint8_t s2)
+{
+    int32_t* t = xmalloc(sizeof(int32_t) * (size_t)n); uint8_t* s = xmalloc(2 * (size_t)n);
+    for (int32_t k = 0; k < n; k++) { t[k] = tid; s[k] = side ? side[k] : s1; s[n + k] = side ? side[k] : s2; }
+    uint32_t* sr = split_links_query(d, n, t, pa, s, t, pb, s + n);
+    free(t); free(s);
+    return sr;
+}
+
 static void dup_describe(FILE* f)
 {
     fprintf(f, "##ALT=<ID=DUP:TANDEM,Description=\"Tandem duplication: reads clipped at its end continue at its start\">\n");
@@ -598,6 +659,7 @@ static void dup_describe(FILE* f)
     if (PAIRLINK_ON)
         fprintf(f, "##INFO=<ID=PE,Number=1,Type=Integer,Description=\"everted read pairs (the leftmost read reverse, its mate forward) that start within POS - %d .. POS + %d "
                    "and whose mate starts within END - %d .. END + %d, at least %d bases apart\">\n", CLIPTAIL_MAX_SHIFT, LINK_EV_WINDOW, LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT, LINK_EV_MIN_SEP);
+    if (SPLITLINK_ON) sr_info(f);
     fprintf(f, "##tandemDuplication=\"a record per pair of positions END and POS, %d <= END - POS <= %d, where END is a position at which at least %d reads of mapping "
                "quality >= -q stop aligning with a soft clip of at least %d bases, more than at any of the %d positions in front and no fewer than at any of the %d "
                "behind, and POS is such a position of the reads that start aligning with such a clip, when for one shift s in 0 .. %d at least %d of the reads at END "
@@ -606,6 +668,7 @@ static void dup_describe(FILE* f)
                "the file has no records once the clip-tail table has overflowed (stderr says so); POS 0 is skipped\"\n",
             DUP_EV_MIN_LEN, DUP_EV_MAX_LEN, DUP_EV_MIN_READS, CLIP_EV_MIN_CLIP, DUP_EV_REACH, DUP_EV_REACH, CLIPTAIL_MAX_SHIFT, DUP_EV_MIN_VERIFIED, DUP_EV_MIN_VERIFIED);
     if (PAIRLINK_ON) pe_describe(f);
+    if (SPLITLINK_ON) sr_describe(f);
 }
 
 /* The pairs of piles of one contig, crossed (-U) or inverted (-N).  Columns of cap: pos = p1 p2 shift | cnt = c1 c2 v1 v2 stored at p1,
@@ -672,6 +735,8 @@ static void dup_contig(driver* d, int32_t tid, FILE* f)
         pe = pair_links_query(d, tid, found, kind, win);
         free(kind); free(win);
     }
+    /* -S: from (pl, the left clips) to (pr, the right clips), and back */
+    uint32_t* sr = found > 0 && SPLITLINK_ON ? split_links_pairs(d, tid, found, pos + cap, pos, NULL, 1, 0) : NULL;
     const char* seq = d->sequences[tid];
     for (int32_t k = 0; k < found; k++) {
         const int32_t pr = pos[k], pl = pos[cap + k];
@@ -681,9 +746,10 @@ static void dup_contig(driver* d, int32_t tid, FILE* f)
                 cnt[2 * cap + k], cnt[3 * cap + k]);
         if (med) fprint_depth_values(f, med + 3 * k, ";DM=", ";DFC=");
         if (pe) fprint_pe(f, pe[k]);
+        if (sr) fprint_sr(f, sr[k], sr[found + k]);
         fprintf(f, "\n");
     }
-    free(med); free(pe); free(P.pos); free(P.cnt);
+    free(med); free(pe); free(sr); free(P.pos); free(P.cnt);
 }
 
 static void inv_describe(FILE* f)
@@ -700,6 +766,7 @@ static void inv_describe(FILE* f)
     if (PAIRLINK_ON)
         fprintf(f, "##INFO=<ID=PE,Number=1,Type=Integer,Description=\"read pairs with both reads forward (CT=3to3: both start within %d bases in front of and %d behind POS "
                    "and END) or both reverse (CT=5to5: within %d in front of and %d behind), at least %d bases apart\">\n", LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT, CLIPTAIL_MAX_SHIFT, LINK_EV_WINDOW, LINK_EV_MIN_SEP);
+    if (SPLITLINK_ON) sr_info(f);
     fprintf(f, "##inversion=\"a record per pair of positions POS < END, %d <= END - POS <= %d, at both of which at least %d reads of mapping quality >= -q stop aligning "
                "(CT=3to3) or at both of which such reads start aligning (CT=5to5) with a soft clip of at least %d bases, more than at any of the %d positions in front "
                "and no fewer than at any of the %d behind, when for one shift s in 0 .. %d at least %d of the reads at POS and at least %d of the reads at END "
@@ -709,6 +776,7 @@ static void inv_describe(FILE* f)
                "(stderr says so); POS 0 is skipped\"\n",
             INV_EV_MIN_LEN, INV_EV_MAX_LEN, INV_EV_MIN_READS, CLIP_EV_MIN_CLIP, INV_EV_REACH, INV_EV_REACH, CLIPTAIL_MAX_SHIFT, INV_EV_MIN_VERIFIED, INV_EV_MIN_VERIFIED);
     if (PAIRLINK_ON) pe_describe(f);
+    if (SPLITLINK_ON) sr_describe(f);
 }
 
 /* -N: one contig's inverted piles into FILE.  No depth fields with -D: an inversion changes no depth. */
@@ -732,6 +800,8 @@ static void inv_contig(driver* d, int32_t tid, FILE* f)
         pe = pair_links_query(d, tid, n, kind, win);
         free(kind); free(win);
     }
+    /* -S: from (x, the pair's side) to (y, the same side), and back */
+    uint32_t* sr = P.found > 0 && SPLITLINK_ON ? split_links_pairs(d, tid, P.found, pos, pos + cap, P.side, 0, 0) : NULL;
     const char* seq = d->sequences[tid];
     for (int32_t k = 0; k < P.found; k++) {
         const int32_t x = pos[k], y = pos[cap + k];
@@ -740,9 +810,10 @@ static void inv_contig(driver* d, int32_t tid, FILE* f)
                 toupper((unsigned char)seq[x - 1]), y, y - x, P.side[k] ? "5to5" : "3to3", pos[2 * cap + k], cnt[k], cnt[cap + k], cnt[4 * cap + k],
                 cnt[5 * cap + k], cnt[2 * cap + k], cnt[3 * cap + k]);
         if (pe) fprint_pe(f, pe[k]);
+        if (sr) fprint_sr(f, sr[k], sr[P.found + k]);
         fprintf(f, "\n");
     }
-    free(pe); free(P.pos); free(P.cnt); free(P.side);
+    free(pe); free(sr); free(P.pos); free(P.cnt); free(P.side);
 }
 
 /* -T: the FILE's ##ALT, ##INFO and description lines; the rule with its constants, as ##inversion= has it */
@@ -758,6 +829,7 @@ static void bnd_describe(FILE* f)
     fprintf(f, "##INFO=<ID=CN,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases were kept, either pile\">\n");
     fprintf(f, "##INFO=<ID=CV,Number=2,Type=Integer,Description=\"Of those, the reads whose clipped bases are the other contig's at the other pile\">\n");
     fprintf(f, "##INFO=<ID=PE,Number=2,Type=Integer,Description=\"Read pairs that led from POS to POS2, read pairs that led from POS2 to POS: one read near the pile, its mate within two neighbouring cells of %d bases of the other contig; 0 where that pile's pairs point elsewhere or nowhere\">\n", BND_EV_CELL_BASES);
+    if (SPLITLINK_ON) sr_info(f);
     fprintf(f, "##interContig=\"a record per pair of positions POS and POS2 on two contigs at each of which at least %d reads of mapping quality >= -q stop aligning (3) "
                "or start aligning (5) with a soft clip of at least %d bases, more than at any of the %d positions in front and no fewer than at any of the %d behind, "
                "when at least %d read pairs lead from one to the other and for one shift s in 0 .. %d at least %d of the reads at POS and at least %d of the reads at "
@@ -772,6 +844,7 @@ static void bnd_describe(FILE* f)
                "POS2 0 are skipped\"\n",
             DUP_EV_MIN_READS, CLIP_EV_MIN_CLIP, DUP_EV_REACH, DUP_EV_REACH, BND_EV_MIN_LINKS, CLIPTAIL_MAX_SHIFT, BND_EV_MIN_VERIFIED, BND_EV_MIN_VERIFIED,
             LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT, BND_EV_CELL_BASES, IM_MATELINK_CELLS, LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT);
+    if (SPLITLINK_ON) sr_describe(f);
 }
 
 /* the peaks of one clip array of one contig, ascending */
@@ -882,6 +955,8 @@ static void bnd_search(driver* d)
                                                 a + 2 * nj, a + 3 * nj);
             pthread_mutex_unlock(&g_query_mu);
             if (rc != IM_OK) fatalf("im_cliptail_junction: %s", im_last_error(d->gpu));
+            /* -S: from end 1 to end 2 of every junction, and back: one call for the FILE */
+            uint32_t* sr = SPLITLINK_ON ? split_links_query(d, (int32_t)nj, q, q + nj, qs, q + 2 * nj, q + 3 * nj, qs + nj) : NULL;
             static const char* const ct[2][2] = {{"3to3", "3to5"}, {"5to3", "5to5"}};
             for (size_t k = 0; k < nj; k++) {
                 const bnd_junction* x = &J[k];
@@ -895,10 +970,12 @@ static void bnd_search(driver* d)
                 else if (x->s1 && !x->s2) fprintf(f, "]%s:%d]%c", c2, x->p2, ref);
                 else if (!x->s1) fprintf(f, "%c]%s:%d]", ref, c2, x->p2);
                 else fprintf(f, "[%s:%d[%c", c2, x->p2, ref);
-                fprintf(f, "\t.\t.\tSVTYPE=BND;CHR2=%s;POS2=%d;CT=%s;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u;PE=%u,%u\n", c2, x->p2, ct[x->s1][x->s2], q[4 * nj + k],
+                fprintf(f, "\t.\t.\tSVTYPE=BND;CHR2=%s;POS2=%d;CT=%s;HOMLEN=%d;CR=%u,%u;CN=%u,%u;CV=%u,%u;PE=%u,%u", c2, x->p2, ct[x->s1][x->s2], q[4 * nj + k],
                         x->c1, x->c2, a[2 * nj + k], a[3 * nj + k], v1, v2, x->n1, x->n2);
+                if (sr) fprint_sr(f, sr[k], sr[nj + k]);
+                fprintf(f, "\n");
             }
-            free(q); free(qs); free(a);
+            free(q); free(qs); free(a); free(sr);
         }
         free(J);
         for (int32_t k = 0; k < 2 * nt; k++) { free(P[k].pos); free(P[k].cnt); free(P[k].mtid); free(P[k].np); free(P[k].lo); free(P[k].hi); }

@@ -252,6 +252,26 @@ extern int im_clip_peaks_tid(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_
 /* the peaks are -U's (DUP_EV_MIN_READS, DUP_EV_REACH), the windows -M's (LINK_EV_WINDOW towards where the pairs lie, CLIPTAIL_MAX_SHIFT
  * the other way), and the table has the pair-link table's size: LINK_EV_SLOTS_SHIFT says what that ASSUMES, and nobody has measured
  * the rate of inter-contig pairs against clipped reads on real data either */
+/* -S, with -U, -N or -T: the records of their FILEs gain SR=n1,n2, the split reads between the record's two ends: primary records with
+ * a soft clip whose SA:Z tag places the clipped part at the other end (the device's keyed table of split links and its count query),
+ * n1 those whose primary part lies at the first end, n2 those at the second.  Evidence that uses every clipped base and carries a
+ * mapping quality for the far side; nothing is filtered by it.  stdout, stderr and -I's FILE stay as they are.  Not an option of the
+ * reference; referenced weakly. */
+static int g_split_links = 0;
+extern int im_splitlink_enable(im_ctx*, int32_t, int32_t, int32_t, int32_t, const char* const*) __attribute__((weak));
+extern int im_dev_splitlink_scatter(im_ctx*, const im_dev_records*, void*) __attribute__((weak));
+extern int im_splitlink_add(im_ctx*, int32_t, const int32_t*, const int32_t*, const uint8_t*, const int32_t*, const int32_t*, const uint8_t*) __attribute__((weak));
+extern int im_splitlink_count(im_ctx*, int32_t, const int32_t*, const uint8_t*, const int32_t*, const int32_t*, const int32_t*, const uint8_t*,
+                              const int32_t*, const int32_t*, uint32_t*) __attribute__((weak));
+extern int im_splitlink_reset(im_ctx*, void*) __attribute__((weak));
+extern int im_splitlink_stats(im_ctx*, uint64_t*, uint64_t*) __attribute__((weak));
+#define SPLITLINK_ON (g_split_links)               /* the walk also keeps the split links */
+#define SPLITLINK_API_PRESENT (im_splitlink_enable && im_dev_splitlink_scatter && im_splitlink_add && im_splitlink_count && im_splitlink_reset && \
+                               im_splitlink_stats)
+#define SPLIT_EV_WINDOW CLIPTAIL_MAX_SHIFT         /* bases around either end: the slack by which micro-homology moves a pile or an aligner's split */
+#define SPLIT_EV_SLOTS_SHIFT LINK_EV_SLOTS_SHIFT   /* the pair-link table's size: split reads are ASSUMED rarer than clipped reads by the same
+                                                    * factor, which nobody has measured on real data -- a library with long reads splits more */
+#define SPLITLINK_NONE 0xFFFFFFFFu                 /* what the device answers after its table has overflowed */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that
