@@ -41,7 +41,25 @@ extern "C" {
 #define IM_ST_NONE        0     /* attempt_pe_alignment returned NULL                */
 #define IM_ST_EVIDENCE    1     /* segment list + n_ev >= 1 evidence records valid   */
 #define IM_ST_ABORT      -1     /* the reference would have exited on this read      */
-#define IM_ST_OVERFLOW   -2
+#define IM_ST_OVERFLOW   -2     /* the read's result is beyond IM_MAX_OPS or IM_MAX_EV (the reference has neither bound).
+                                 * The rule, with (n_ops, n_ev) what the reference's attempt_pe_alignment leaves for the read:
+                                 *   n_ops <= IM_MAX_OPS and n_ev <= IM_MAX_EV   IM_ST_EVIDENCE, every field as the reference has it
+                                 *                                                (a list of exactly 64 words, 4 indels: they fit)
+                                 *   n_ops >  IM_MAX_OPS or  n_ev >  IM_MAX_EV   IM_ST_OVERFLOW
+                                 * One case the rule leaves open: a final list that fits while the CIGAR of one of the two band
+                                 * alignments it is cut from is beyond IM_MAX_OPS words -- IM_ST_OVERFLOW today.
+                                 * An overflow record holds n_ev = n_ops = ref_start = 0 (like every status but IM_ST_EVIDENCE),
+                                 * n_band and band[] as for a read that fitted (both band searches were done; band[1] is zero when the
+                                 * FIRST alignment's CIGAR was the one too long, n_band = 1 then), nothing valid in ev[] and ops[], and
+                                 * nothing outside its 512 bytes.  Its evidence slots (im_dev_batch.ev_cls/b1/b2): cls = -1, b1 = b2 = 0
+                                 * in all IM_MAX_EV of them from im_dev_realign; untouched by im_dev_realign_keep (and
+                                 * im_dev_realign_n with keep_slots = 1), like those of a read without realigned evidence.
+                                 * im_realign_batch returns IM_E_OVERFLOW when a read of the batch overflowed (every record is
+                                 * written, im_last_error names the first such read); im_dev_compact_results does not pack it.
+                                 * Which kernel can meet which bound: a list grows by at most 2 words per ~12 read bases, so the
+                                 * segment bound takes a read of some 450 bases or more -- the long-read kernel and the general
+                                 * pass; numgaps == 0 leaves one indel per read, so the indel bound takes numgaps > 0 -- the band
+                                 * kernel and the general pass.  tests/test_gpu_record_bounds.py holds all of this. */
 #define IM_ST_UNSUPPORTED -3    /* a read beyond 255 bases when im_expect_read_length was not told of it; base_off not a multiple of 4 */
 
 /* CIGAR op codes in packed words (len<<4|op): samtools bam.h + src/readaln.h:10-11 */
@@ -57,8 +75,8 @@ extern "C" {
                                    see im_expect_read_length */
 #define IM_MAX_SW_TARGET 4095   /* longest annotate-mode window (reference span + variant) of im_support_batch's LDS form; longer
                                    windows and queries beyond IM_MAX_READ run in its second form */
-#define IM_MAX_OPS   64         /* packed segment words per realigned read           */
-#define IM_MAX_EV    4          /* indel segments (= evidence) per realigned read    */
+#define IM_MAX_OPS   64         /* packed segment words per realigned read: 64 fit, 65 are IM_ST_OVERFLOW (see there) */
+#define IM_MAX_EV    4          /* indel segments (= evidence) per realigned read: 4 fit, 5 are IM_ST_OVERFLOW         */
 
 #define IM_CLS_INSERTION 0      /* varianttype, src/evidence.h:13-17                 */
 #define IM_CLS_DELETION  1

@@ -1162,7 +1162,7 @@ int im_realign_batch(im_ctx* ctx, const im_params* params, const im_read_batch* 
     for (int32_t i = 0; i < n; i++) {
         const int st = out[i].status;
         if (st == IM_ST_ABORT && worst == IM_OK) { worst = IM_E_ABORT; set_err(ctx, "read %d: the reference would abort on this input", i); }
-        else if (st == IM_ST_OVERFLOW && worst == IM_OK) { worst = IM_E_OVERFLOW; set_err(ctx, "read %d: segment list longer than IM_MAX_OPS", i); }
+        else if (st == IM_ST_OVERFLOW && worst == IM_OK) { worst = IM_E_OVERFLOW; set_err(ctx, "read %d: more than IM_MAX_OPS segments or IM_MAX_EV indels", i); }
         else if (st == IM_ST_UNSUPPORTED && worst == IM_OK) { worst = IM_E_UNSUPPORTED; set_err(ctx, "read %d: longer than IM_MAX_READ=%d%s", i, IM_MAX_READ, params->numgaps ? ", or than 255 with numgaps > 0" : ""); }
     }
     return worst;

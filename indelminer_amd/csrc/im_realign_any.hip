@@ -494,6 +494,8 @@ __device__ AnyAln any_band_alignment(const AR& a, const AnyLayout& Y, gbytes con
         }
     }
     if (score <= 0) return r;                                                         // src/alignment.c:365-372
+    // the alignment's corners are known before its CIGAR is: a piece whose CIGAR overflows leaves them in the record's band
+    r.r1 = startj + w0 - 1; r.r2 = endj + w0; r.q1 = starti + p0 - 1; r.q2 = endi + p0;    // 385-388
     // fetch_cigar (507-604): [AP S] runs [tail S]; deletion lengths count into the consumed total as there (541-595)
     {
         const int pos0 = starti - 1;
@@ -516,7 +518,6 @@ __device__ AnyAln any_band_alignment(const AR& a, const AnyLayout& Y, gbytes con
         if (over) { r.st = IM_ST_OVERFLOW; return r; }
         r.n_ops = n;
     }
-    r.r1 = startj + w0 - 1; r.r2 = endj + w0; r.q1 = starti + p0 - 1; r.q2 = endi + p0;    // 385-388
     return r;
 }
 

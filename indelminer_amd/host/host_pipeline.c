@@ -930,7 +930,7 @@ static void stage_run_group(ppipe* P, pgroup* G)
         if (st >= 0) continue;
         if ((st == IM_ST_ABORT || st == IM_ST_OVERFLOW || st == IM_ST_UNSUPPORTED) && g_handoff_pool) pipeline_handoff();
         if (st == IM_ST_ABORT) fatalf("im_dev_realign: read %d: the reference would abort on this input", i);
-        if (st == IM_ST_OVERFLOW) fatalf("im_dev_realign: read %d: segment list longer than IM_MAX_OPS", i);
+        if (st == IM_ST_OVERFLOW) fatalf("im_dev_realign: read %d: more than IM_MAX_OPS segments or IM_MAX_EV indels", i);
         if (st == IM_ST_UNSUPPORTED) fatalf("im_dev_realign: read %d: left unrealigned (the context was not told of its length)", i);
     }
     free(rstat);

@@ -65,7 +65,7 @@ int im_realign_batch(im_ctx* c, const im_params* p, const im_read_batch* b, im_r
         o->status = st == IMO_OK ? IM_ST_EVIDENCE : st == IMO_NONE ? IM_ST_NONE : st == IMO_ABORT ? IM_ST_ABORT : IM_ST_OVERFLOW;
         if (st == IMO_ABORT) { worst = IM_E_ABORT; snprintf(c->err, sizeof c->err, "read %d: the reference would abort", i); }
         if (st != IMO_OK) continue;
-        if (r->n_ops > IM_MAX_OPS || r->n_ev > IM_MAX_EV) { o->status = IM_ST_OVERFLOW; worst = IM_E_OVERFLOW; continue; }
+        if (r->n_ops > IM_MAX_OPS || r->n_ev > IM_MAX_EV) { o->status = IM_ST_OVERFLOW; worst = IM_E_OVERFLOW; snprintf(c->err, sizeof c->err, "read %d: more than IM_MAX_OPS segments or IM_MAX_EV indels", i); continue; }
         o->ref_start = r->ref_start; o->n_ops = r->n_ops; o->n_ev = r->n_ev; o->n_band = r->n_band;
         memcpy(o->ops, r->ops, sizeof(uint32_t) * (size_t)r->n_ops);
         for (int k = 0; k < r->n_ev; k++) {

@@ -372,6 +372,47 @@ def test_host_read_with_more_indels_than_the_kernels_hold(tmp_path):
     _many_indels_in_one_read(_build_shim(), tmp_path, ({}, {"INDELMINER_CLAIM_BASES": "1", "INDELMINER_WALKERS": "3"}))
 
 
+def _longer_list_than_the_kernels_hold(binary, tmp_path, envs):
+    """Three realign candidates support one 45-base deletion; the segment list of one of them has 65 words
+    (tests/support/recordbounds.py product_dataset).  The reference has no bound and prints the deletion with NS=3
+    (tests/golden/vcf/record_bounds_65_segments.vcf, from the compiled reference: neither the product nor the CPU shim can make
+    these bytes, the result record of both holds IM_MAX_OPS = 64 words).  The realign kernels answer IM_ST_OVERFLOW, the
+    pipeline hands the run to the record-at-a-time child (host_pipeline.c, pipeline_handoff) -- whose im_realign_batch meets
+    the same read and the same bound (host_setup.c).  Held to: EITHER the expected bytes, OR a non-zero exit status with the
+    limit named on stderr and a byte-for-byte prefix of the expected output on stdout; never other bytes with status 0.
+    Returns what the runs did, "whole" or "stopped" per env."""
+    from tests.support import recordbounds as rb
+    d = str(tmp_path)
+    infos, b1 = rb.product_dataset(d)
+    assert [i.n_ops for i in infos] == [65, 63, 61]
+    want = _golden("record_bounds_65_segments")
+    line = [l for l in want.split(b"\n") if l.startswith(b"ctg0\t%d\t" % b1)]
+    assert len(line) == 1 and b"DELETION;SPLIT_READ;NS=3;" in line[0]           # the read beyond the bound counts
+    ref_bin = os.path.join(ROOT, "oracle", "_ref", "indelminer")
+    if os.path.exists(ref_bin):
+        assert _run(ref_bin, rb.PRODUCT_FLAGS, d, ref="ref.fa", bam="aln.bam") == want
+    did = []
+    for env in envs:
+        r = subprocess.run([binary] + rb.PRODUCT_FLAGS + ["ref.fa", "s=aln.bam"], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           env=dict(os.environ, **env))
+        if r.returncode == 0:
+            assert r.stdout == want, (env, r.stderr.decode()[-1500:])
+            did.append("whole")
+        else:
+            assert b"IM_MAX_OPS" in r.stderr, (env, r.returncode, r.stderr.decode()[-1500:])
+            assert want.startswith(r.stdout), (env, len(r.stdout), len(want))
+            did.append("stopped")
+    return did
+
+
+def test_host_read_with_a_longer_list_than_the_kernels_hold(tmp_path):
+    """the CPU shim holds the record's bounds in its im_realign_batch as the kernels do (tests/shim/im_shim.c): every form of
+    the host driver above it stops at the read, the limit named"""
+    did = _longer_list_than_the_kernels_hold(_build_shim(), tmp_path, ({}, {"INDELMINER_CLAIM_BASES": "1", "INDELMINER_WALKERS": "3"},
+                                                                       {"INDELMINER_PIPELINE": "host"}))
+    assert did == ["stopped"] * 3, did
+
+
 def test_host_leaked_handoff_variable_drops_nothing(synth_small):
     """INDELMINER_SKIP_STDOUT is how a hand-over child learns how many bytes its parent has printed; found in the environment of a
     run that nobody handed anything to (no INDELMINER_HANDOFF_PARENT naming the parent process), it must not eat output"""
@@ -981,6 +1022,15 @@ def test_product_runs_beyond_the_laid_out_kernels(tmp_path):
 @pytest.mark.gpu
 def test_product_read_with_more_indels_than_the_kernels_hold(tmp_path):
     _many_indels_in_one_read(_product(), tmp_path, ({}, {"INDELMINER_CLAIM_BASES": "1", "INDELMINER_WALKERS": "3"}, {"INDELMINER_ONEPASS": "0"}), expect_handoff=True)
+
+
+@pytest.mark.gpu
+def test_product_read_with_a_longer_list_than_the_kernels_hold(tmp_path):
+    """What the product does today: it stops.  The pipeline hands the run over, and the record-at-a-time child turns the
+    IM_E_OVERFLOW of its im_realign_batch into a fatal error (host_setup.c) -- the limit named on stderr, what was printed
+    until then a prefix of the reference's output.  It does not finish the run, in either form."""
+    did = _longer_list_than_the_kernels_hold(_product(), tmp_path, ({}, {"INDELMINER_ONEPASS": "0"}, {"INDELMINER_PIPELINE": "host"}))
+    assert did == ["stopped"] * 3, did
 
 
 @pytest.mark.gpu
