@@ -208,6 +208,10 @@ int im_cluster_sr(im_ctx* ctx, int32_t n,
 int im_depth_build(im_ctx* ctx, int64_t contig_len, int32_t n_seg,
                    const int32_t* seg_start, const int32_t* seg_len);
 int im_depth_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out);
+/* the same, and per query the DEEPEST position of [beg - 1, end] (max_out, may be NULL): what im_depth_query_max_tid answers on the
+ * genome-wide array (same definition, same edges), here on what im_depth_build left.  The record-at-a-time path of the host driver
+ * decides with it, like the pipelined path, whether samtools' pileup cap may have applied to a DP=. */
+int im_depth_query_max(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out, uint32_t* max_out);
 /* Seam 3's order statistic (no reference counterpart: calculate_cov_params only ever sums, src/shared.c:178-212), over what
  * im_depth_build left.  Per query [beg, end), clipped to [0, contig_len), the LOWER MEDIAN of the depths of its n positions: the
  * smallest d such that at least (n + 1) / 2 of them have depth <= d.  A position with depth >= 4095 counts as 4095 -- the

@@ -146,6 +146,7 @@ def lib():
         L.im_comm_last_error.restype = C.c_char_p
         L.im_depth_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.im_depth_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_depth_query_max.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_depth_median.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_support_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_support_count.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
@@ -501,6 +502,17 @@ class Context:
 
     def depth_query(self, beg, end):
         return self._query(lib().im_depth_query, beg, end)
+
+    def depth_query_max(self, beg, end):
+        """(sum, max) per query on what depth_build left: the sum over [beg, end) as depth_query gives it, and the deepest position
+        of [beg - 1, end], both clipped to the contig"""
+        beg = np.ascontiguousarray(beg, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        assert len(beg) == len(end)
+        n = len(beg)
+        total, deepest = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2))
+        self._check(lib().im_depth_query_max(self.h, n, _ptr(beg), _ptr(end), _ptr(total), _ptr(deepest)))
+        return total[:n], deepest[:n]
 
     def depth_median(self, beg, end):
         """per query the lower median of min(depth, 4095) over [beg, end); 0xFFFFFFFF for an interval that is empty after the clip"""

@@ -476,16 +476,16 @@ int query_array(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, 
     return IM_OK;
 }
 
-// im_depth_query / im_depth_median / im_span_query / im_pairspan_query / im_clip_query
+// im_depth_query_max / im_depth_median / im_span_query / im_pairspan_query / im_clip_query
 int query_contig_array(im_ctx* ctx, ContigArray im_ctx::*which, const char* family, int32_t n, const int32_t* beg, const int32_t* end, Reduce what,
-                       uint32_t* out, const ArgMaxSide* argmax = nullptr)
+                       uint32_t* out, const ArgMaxSide* argmax = nullptr, uint32_t* max_out = nullptr)
 {
     if (!ctx || n < 0) return IM_E_ARG;
     const ContigArray& a = ctx->*which;
     if (a.len < 0) { set_err(ctx, "%s_build has not been called", family); return IM_E_ARG; }
     if (n == 0) return IM_OK;
     if (!beg || !end || !out) return IM_E_ARG;
-    return query_array(ctx, n, beg, end, a.data, a.sums, a.len, what, out, nullptr, argmax);
+    return query_array(ctx, n, beg, end, a.data, a.sums, a.len, what, out, max_out, argmax);
 }
 
 // im_depth_enable / im_span_enable / im_pairspan_enable / im_clip_enable: a genome-wide array and its sums, zeroed.  Each contig has its own
@@ -1171,8 +1171,11 @@ int im_realign_batch(im_ctx* ctx, const im_params* params, const im_read_batch* 
 int im_depth_build(im_ctx* ctx, int64_t contig_len, int32_t n_seg, const int32_t* seg_start, const int32_t* seg_len)
 { return build_array(ctx, &im_ctx::depth, "im_depth", contig_len, n_seg, seg_start, seg_len, nullptr); }
 
+int im_depth_query_max(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out, uint32_t* max_out)
+{ return query_contig_array(ctx, &im_ctx::depth, "im_depth", n, beg, end, kSum, sum_out, nullptr, max_out); }
+
 int im_depth_query(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out)
-{ return query_contig_array(ctx, &im_ctx::depth, "im_depth", n, beg, end, kSum, sum_out); }
+{ return im_depth_query_max(ctx, n, beg, end, sum_out, nullptr); }
 
 int im_depth_median(im_ctx* ctx, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* med_out)
 { return query_contig_array(ctx, &im_ctx::depth, "im_depth", n, beg, end, kMedian, med_out); }

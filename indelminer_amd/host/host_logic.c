@@ -813,26 +813,73 @@ static void merge_variants(variant_list* pvs, const char* reference, int64_t ref
 /* Loci at which samtools' pileup, the reference's source of DP= (src/shared.c:178-212), may have stopped taking records: a record
  * is left out when it starts at the position the iterator stands on and more than 8000 nodes are allocated
  * (src/samtools-0.1.19/bam_pileup.c:172,244).  The device's depth array counts every record, so a query whose deepest position
- * reaches this bound is answered from the file with that rule (region_depth_from_bam). */
+ * reaches this bound is answered from the file with that rule (region_depth_from_bam).
+ * Where the deepest position is looked for: the pileup buffers every record that bam_fetch returns for the window, and such a
+ * record starts up to a record's reference span in front of the window and may cross it in a D or N, where it adds nothing to the
+ * M/=/X depth.  Every record adds to the depth at its first aligned base, though: the bound is held against
+ * [beg - 1 - the longest reference span any record has shown so far, end] (depth_sum_deepest).  A pile of records whose starts all
+ * differ and that cross the window in gaps alone can still pass below it; nothing else can. */
 #define DP_DEEP_LOCUS 4000
 
+/* the longest reference span among the records the pileup does not skip, over everything the run has read (either path; several
+ * ranks: it travels with the walked groups) */
+static volatile int32_t g_longest_span = 0;
+static void note_span(int32_t span)
+{
+    int32_t cur = __atomic_load_n(&g_longest_span, __ATOMIC_RELAXED);
+    while (span > cur && !__atomic_compare_exchange_n(&g_longest_span, &cur, span, 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+}
+/* INDELMINER_TIMING: the DP= windows asked of the device, and those among them that were then answered from the file */
+static int64_t g_dp_queries = 0, g_dp_from_file = 0;
+
 static uint32_t region_depth_from_bam(driver* d, int32_t tid, int32_t start, int32_t stop);
+
+/* m DP= windows of contig tid (the one whose depth array the device holds) in ONE device call: per window the sum over [beg, end)
+ * and the deepest position of [beg - 1 - longest span, end].  The call carries every window twice, once as it is for the sum and
+ * once drawn out to the front for the maximum.  On either path: the genome-wide array of the pipeline, or what im_depth_build left. */
+static void depth_sum_deepest(driver* d, int32_t tid, int m, const int32_t* beg, const int32_t* end, uint32_t* sum, uint32_t* deepest)
+{
+    const int32_t back = __atomic_load_n(&g_longest_span, __ATOMIC_RELAXED);
+    int32_t* qb = xmalloc(sizeof(int32_t) * 2 * (size_t)m);
+    int32_t* qe = xmalloc(sizeof(int32_t) * 2 * (size_t)m);
+    uint32_t* qs = xmalloc(sizeof(uint32_t) * 2 * (size_t)m);
+    uint32_t* qm = xmalloc(sizeof(uint32_t) * 2 * (size_t)m);
+    for (int q = 0; q < m; q++) {
+        qb[q] = beg[q]; qe[q] = end[q];
+        qb[m + q] = beg[q] > back ? beg[q] - back : 0; qe[m + q] = end[q];
+        qm[q] = qm[m + q] = 0;
+    }
+    gpu_wait(d);
+    pthread_mutex_lock(&g_query_mu);
+    const int qrc = d->pipe_mode ? im_depth_query_max_tid(d->gpu, tid, 2 * m, qb, qe, qs, qm)
+                  : im_depth_query_max ? im_depth_query_max(d->gpu, 2 * m, qb, qe, qs, qm)
+                  : im_depth_query(d->gpu, m, qb, qe, qs);         /* a library from before im_depth_query_max: no maximum, qm stays 0 */
+    pthread_mutex_unlock(&g_query_mu);
+    if (qrc != IM_OK)
+        fatalf("im_depth_query: %s", im_last_error(d->gpu));
+    for (int q = 0; q < m; q++) { sum[q] = qs[q]; deepest[q] = qm[m + q]; }
+    __atomic_fetch_add(&g_dp_queries, m, __ATOMIC_RELAXED);
+    free(qb); free(qe); free(qs); free(qm);
+}
+
+/* DP= of one window from the sum and the deepest position the device gave */
+static uint32_t depth_or_file(driver* d, int32_t tid, int32_t start, int32_t stop, uint32_t sum, uint32_t deepest)
+{
+    if (deepest >= DP_DEEP_LOCUS) {         /* the pileup's cap may have applied */
+        __atomic_fetch_add(&g_dp_from_file, 1, __ATOMIC_RELAXED);
+        return region_depth_from_bam(d, tid, start, stop);
+    }
+    return (uint32_t)floor(sum * 1.0 / (uint32_t)(stop - start));
+}
 
 static uint32_t region_depth(driver* d, int32_t tid, int32_t start, int32_t stop)
 {
     if (stop <= start) return 0;
     if (d->depth_tid == tid) {
         /* the device holds the contig's depth array (im_depth_build in run_contig) */
-        uint32_t sum = 0;
-        gpu_wait(d);
-        pthread_mutex_lock(&g_query_mu);
-        uint32_t deepest = 0;
-        const int qrc = d->pipe_mode ? im_depth_query_max_tid(d->gpu, tid, 1, &start, &stop, &sum, &deepest) : im_depth_query(d->gpu, 1, &start, &stop, &sum);
-        pthread_mutex_unlock(&g_query_mu);
-        if (qrc != IM_OK)
-            fatalf("im_depth_query: %s", im_last_error(d->gpu));
-        if (deepest >= DP_DEEP_LOCUS) return region_depth_from_bam(d, tid, start, stop);      /* the pileup's cap may have applied */
-        return (uint32_t)floor(sum * 1.0 / (uint32_t)(stop - start));
+        uint32_t sum = 0, deepest = 0;
+        depth_sum_deepest(d, tid, 1, &start, &stop, &sum, &deepest);
+        return depth_or_file(d, tid, start, stop, sum, deepest);
     }
     /* region runs (-c): the reference pileups the whole BAM around the variant, which can reach
      * outside the analysed region -- go to the file like it does */
@@ -1276,17 +1323,10 @@ static void print_variants(driver* d, variant_list* vs)
             beg[m] = start; end[m] = stop; who[m] = i; m++;
         }
         if (m > 0) {
-            gpu_wait(d);
-            pthread_mutex_lock(&g_query_mu);
-            for (int q = 0; q < m; q++) deepest[q] = 0;
-            const int qrc = d->pipe_mode ? im_depth_query_max_tid(d->gpu, d->depth_tid, m, beg, end, sum, deepest) : im_depth_query(d->gpu, m, beg, end, sum);
-            pthread_mutex_unlock(&g_query_mu);
-            if (qrc != IM_OK)
-                fatalf("im_depth_query: %s", im_last_error(d->gpu));
+            depth_sum_deepest(d, d->depth_tid, m, beg, end, sum, deepest);
             for (int q = 0; q < m; q++) {
                 variant_t* v = out.v[who[q]];
-                v->dp_cached = deepest[q] >= DP_DEEP_LOCUS ? (int32_t)region_depth_from_bam(d, d->depth_tid, beg[q], end[q])      /* the pileup's cap may have applied */
-                                                           : (int32_t)(uint32_t)floor(sum[q] * 1.0 / (uint32_t)(end[q] - beg[q]));
+                v->dp_cached = (int32_t)depth_or_file(d, d->depth_tid, beg[q], end[q], sum[q], deepest[q]);
                 v->dp_valid = 1;
             }
         }

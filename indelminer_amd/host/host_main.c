@@ -428,6 +428,8 @@ int main(int argc, char** argv)
     if (MATELINK_ON) say_overflow(d.gpu, im_matelink_stats, "indelminer: -T: the mate-link table overflowed (%llu links stored, %llu dropped): its file has no records\n");
     if (SPLITLINK_ON) say_overflow(d.gpu, im_splitlink_stats, "indelminer: -S: the split-link table overflowed (%llu links stored, %llu dropped): SR is . in the files of -U, -N and -T\n");
     if (t_out) fflush(t_out);
+    if (g_timing) fprintf(stderr, "[timing] DP=: %ld windows asked of the device, %ld of them answered from the file (a position of %d records or more within %d bases in front)\n",
+                          (long)g_dp_queries, (long)g_dp_from_file, DP_DEEP_LOCUS, (int)g_longest_span);
     if (g_vcfname != NULL) cpu_report();            /* annotate mode has no replay workers: its report comes here */
     if (!getenv("INDELMINER_TIDY_EXIT")) {
         /* everything is printed: the GPU context, the pinned rings and the device arrays go with the process -- tearing the

@@ -825,7 +825,7 @@ static void group_park_device(ppipe* P, pgroup* G)
  * device allocation.  Both travel device to device in ONE RCCL send / receive group when every rank has walked what it walks
  * (mg_ship_groups); `aborted` = the walk met a record the reference dies on. */
 #define PKG_MAGIC 0x504b4734
-typedef struct { int32_t magic, aborted, n_ctg, n_fp, n_npp, n_cand, sv_n, longest_read, has_range, pad; int64_t n_rec, npp_len, craw_len, sv_bytes; } pkg_head;
+typedef struct { int32_t magic, aborted, n_ctg, n_fp, n_npp, n_cand, sv_n, longest_read, has_range, longest_span; int64_t n_rec, npp_len, craw_len, sv_bytes; } pkg_head;
 typedef struct { char* blob; size_t blob_len; void* slab; size_t slab_bytes; int aborted, walked; } mg_parcel;     /* a walked group on its way */
 static mg_parcel* g_parcel = NULL;            /* [claims] filled by this rank's walkers for the claims other ranks own */
 
@@ -851,7 +851,7 @@ static void package_pack(int ci, pgroup* G, int aborted)
     memset(&h, 0, sizeof h);
     h.magic = PKG_MAGIC; h.aborted = aborted;
     if (!aborted) {
-        h.n_ctg = G->n_ctg; h.n_fp = G->n_fp; h.n_npp = G->n_npp; h.n_cand = G->n_cand; h.sv_n = G->sv_n; h.longest_read = g_longest_read; h.has_range = G->sv_range != NULL;
+        h.n_ctg = G->n_ctg; h.n_fp = G->n_fp; h.n_npp = G->n_npp; h.n_cand = G->n_cand; h.sv_n = G->sv_n; h.longest_read = g_longest_read; h.longest_span = g_longest_span; h.has_range = G->sv_range != NULL;
         h.n_rec = G->n_rec; h.npp_len = G->npp_len; h.craw_len = G->craw_len; h.sv_bytes = G->sv_bytes;
     }
     pkg_put(fp, &h, sizeof h);
@@ -881,6 +881,7 @@ static pgroup* package_unpack(driver* d, const char* blob, size_t len, void* sla
     if (h.magic != PKG_MAGIC) fatalf("what arrived is not a walked group of this run");
     if (h.aborted) { fclose(fp); return NULL; }
     if (h.longest_read > g_longest_read) note_long_read(d, h.longest_read);      /* this rank's realign launches must know of reads beyond 255 bases too */
+    if (h.longest_span > g_longest_span) note_span(h.longest_span);              /* and its DP= queries of the longest record any rank has walked */
     pgroup* G = xcalloc(1, sizeof(pgroup));
     G->from_package = 1;
     G->n_ctg = G->cap_ctg = h.n_ctg; G->n_fp = G->cap_fp = h.n_fp; G->n_npp = G->cap_npp = h.n_npp; G->n_cand = G->cap_cand = h.n_cand; G->sv_n = h.sv_n;

@@ -546,6 +546,11 @@ static void pipe_host_record(driver* d, pgroup* G, const bam_record* b)
         if (!G->cov.sum) cov_init(&G->cov, d->hdr->n_targets);
         cov_record(&G->cov, b);
     }
+    if (b->tid >= 0 && !(flag & (0x4 | 0x100 | 0x200 | 0x400))) {
+        /* a record the pileup takes: how far in front of a DP= window the deepest position is looked for (region_depth) */
+        const int32_t span = bam_record_end(b) - b->pos;
+        if (span > g_longest_span) note_span(span);
+    }
     if (flag & (0x100 | 0x200 | 0x400 | 0x800)) return;
     if ((flag & 0x1) == 0) return;
     if (b->l_seq > g_longest_read) note_long_read(d, b->l_seq);

@@ -1011,6 +1011,7 @@ static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_re
                     x += len;
                 } else if (op == OP_D || op == OP_N) x += len;
             }
+            if (x - b.pos > g_longest_span) note_span(x - b.pos);       /* how far in front of a DP= window the deepest position is looked for */
         }
         dispatch_record(d, &b);
     }

@@ -367,6 +367,8 @@ static walkpool_t* walkpool_start(driver* d)
             pc->index = o->n_pieces - 1;
         }
     }
+    if (g_timing) for (int k = 0; k < o->n_pieces; k++)         /* the piece table: where the contigs were cut */
+        fprintf(stderr, "[timing] piece %d: contig %d [%d, %d)\n", k, (int)o->pieces[k].tid, (int)o->pieces[k].beg, (int)o->pieces[k].end);
     /* claims: a piece of a cut contig on its own; whole small contigs together up to about a piece's worth (the stage and the
      * replay have fixed costs per group) */
     int64_t claim_len = total_len / (4 * (int64_t)nw);

@@ -106,6 +106,10 @@ static __thread FILE* t_out;
 #define OUT (t_out ? t_out : stdout)
 #define printf(...) fprintf(OUT, __VA_ARGS__)
 static pthread_mutex_t g_query_mu = PTHREAD_MUTEX_INITIALIZER;     /* depth queries share the context's workspace and stream */
+/* DP= on the record-at-a-time path: the sum and the deepest position of a window of the one-contig depth array (region_depth,
+ * host_logic.c).  Referenced weakly like the optional families below: an implementation of the C ABI from before this entry
+ * point still links, and that path then sums with im_depth_query and cannot tell a locus at samtools' pileup cap, as before. */
+extern int im_depth_query_max(im_ctx*, int32_t, const int32_t*, const int32_t*, uint32_t*, uint32_t*) __attribute__((weak));
 /* -G: genotype columns (FORMAT GT:AD:GQ) from the device's reference-spanning read counts.  The reference has no such option
  * (its getopt string has no G).  The entry points are referenced weakly: an implementation of the C ABI without them (the CPU
  * stand-in the host tests link this driver against) still links, and -G then says what it needs. */

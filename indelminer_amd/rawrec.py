@@ -75,9 +75,10 @@ def build(rd, lo=0, hi=None, qname_prefix="r", align=4, block_size_word=False, r
     raw = np.zeros(int(off[-1]), dtype=np.uint8)
     start = off[:-1] + pre
 
+    mapq = rd.mapq[sl] if isinstance(rd.mapq, np.ndarray) else rd.mapq        # one per row, or one for the data set
     core = np.zeros(n, dtype=CORE_DTYPE)
     core["tid"] = rd.tid[sl]; core["pos"] = pos; core["l_qname"] = qlen
-    core["mapq"] = np.where(unm, 0, rd.mapq); core["bin"] = reg2bin_vec(pos, end)
+    core["mapq"] = np.where(unm, 0, mapq); core["bin"] = reg2bin_vec(pos, end)
     core["n_cigar"] = ncig; core["flag"] = flag; core["l_seq"] = L
     core["mtid"] = rd.tid[sl]; core["mpos"] = rd.mpos[sl]; core["isize"] = rd.isize[sl]
     raw[(start[:, None] + np.arange(32)[None, :]).reshape(-1)] = core.view(np.uint8).reshape(-1)
@@ -114,7 +115,7 @@ def build(rd, lo=0, hi=None, qname_prefix="r", align=4, block_size_word=False, r
         ab = np.frombuffer(bytes(aux_prefix), dtype=np.uint8)
         raw[(o_tag[:, None] + np.arange(len(ab))[None, :]).reshape(-1)] = np.tile(ab, n)
         o_tag = o_tag + len(ab)
-    mq = np.where((flag & 0x8) != 0, 0, rd.mapq).astype(np.uint8)
+    mq = np.where((flag & 0x8) != 0, 0, mapq).astype(np.uint8)
     tag = np.zeros((n, 4), dtype=np.uint8)
     tag[:, 0] = ord("M"); tag[:, 1] = ord("Q"); tag[:, 2] = ord("C"); tag[:, 3] = mq
     raw[(o_tag[:, None] + np.arange(4)[None, :]).reshape(-1)] = tag.reshape(-1)

@@ -104,16 +104,36 @@ int im_depth_build(im_ctx* c, int64_t contig_len, int32_t n_seg, const int32_t* 
     return IM_OK;
 }
 
-int im_depth_query(im_ctx* c, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out)
+/* the sum over [beg, end) and (max_out, may be NULL) the deepest position of [beg - 1, end], both clipped to the contig: one restatement
+ * behind im_depth_query_max and im_depth_query_max_tid, as one kernel is behind both in the product */
+static void depth_sum_max(const int32_t* depth, int64_t len, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out, uint32_t* max_out)
 {
     for (int32_t q = 0; q < n; q++) {
         int64_t a = beg[q], b = end[q];
         if (a < 0) a = 0;
-        if (b > c->depth_len) b = c->depth_len;
-        uint32_t s = 0;
-        for (int64_t p = a; p < b; p++) s += (uint32_t)c->depth[p];
+        if (b > len) b = len;
+        uint32_t s = 0, mx = 0;
+        for (int64_t p = a > 0 ? a - 1 : a; p < (b < len ? b + 1 : b); p++) {
+            const uint32_t v = (uint32_t)depth[p];
+            if (p >= a && p < b) s += v;
+            if (v > mx) mx = v;
+        }
         sum_out[q] = s;
+        if (max_out) max_out[q] = mx;
     }
+}
+
+#ifndef IM_SHIM_WITHOUT_DEPTH_QUERY_MAX        /* defined by the test of a driver linked against a library from before the entry point */
+int im_depth_query_max(im_ctx* c, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out, uint32_t* max_out)
+{
+    depth_sum_max(c->depth, c->depth_len, n, beg, end, sum_out, max_out);
+    return IM_OK;
+}
+#endif
+
+int im_depth_query(im_ctx* c, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out)
+{
+    depth_sum_max(c->depth, c->depth_len, n, beg, end, sum_out, NULL);
     return IM_OK;
 }
 
@@ -167,19 +187,7 @@ int im_depth_reset(im_ctx* c, int32_t tid, void* stream)
 }
 int im_depth_query_max_tid(im_ctx* c, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out, uint32_t* max_out)
 {
-    for (int32_t q = 0; q < n; q++) {
-        int64_t a = beg[q], b = end[q];
-        if (a < 0) a = 0;
-        if (b > c->lens[tid]) b = c->lens[tid];
-        uint32_t s = 0, mx = 0;
-        for (int64_t p = a > 0 ? a - 1 : a; p < (b < c->lens[tid] ? b + 1 : b); p++) {
-            const uint32_t v = (uint32_t)g_gdepth[tid][p];
-            if (p >= a && p < b) s += v;
-            if (v > mx) mx = v;
-        }
-        sum_out[q] = s;
-        if (max_out) max_out[q] = mx;
-    }
+    depth_sum_max(g_gdepth[tid], c->lens[tid], n, beg, end, sum_out, max_out);
     return IM_OK;
 }
 int im_depth_query_tid(im_ctx* c, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* sum_out)

@@ -1,6 +1,8 @@
-"""Inputs and yardstick for im_depth_query_max_tid: the sum over [beg, end) and the DEEPEST position of [beg - 1, end], the query the
-host driver makes for every printed variant in pipeline mode (host_logic.c, region_depth); its maximum decides whether DP= is
-re-derived from the file (deepest >= 4000).  A maximum that comes out too low is silent everywhere but at a deep locus.
+"""Inputs and yardstick for im_depth_query_max_tid and im_depth_query_max: the sum over [beg, end) and the DEEPEST position of
+[beg - 1, end], the query the host driver makes for every printed variant (host_logic.c, depth_sum_deepest: on the genome-wide array in
+pipeline mode, on what im_depth_build left on the record-at-a-time path); its maximum decides whether DP= is re-derived from the
+file (deepest >= 4000).  A maximum that comes out too low is silent everywhere but at a deep locus.  The driver sends every window
+twice: as it is, and drawn out to the front by the longest reference span it has seen (lookback_queries).
 
 Records: plain matching reads of matchrecs.BASES bases on the two contigs of tests/test_gpu_depth_scan_shapes.py's genome-wide test, a
 random background, and SPIKES -- k records starting at one position p, which raise the depth on [p, p + BASES) by k.  A query with
@@ -23,14 +25,21 @@ SPIKES = [(0, 3 * TILE + 100, DEEP), (0, 5 * TILE - BASES, K), (0, 7 * TILE, K +
           (1, 1000, 4100), (1, CLENS[1] - BASES, K), (1, 3000, K + 3)]
 
 
-def records(seed=33):
-    """(raw, rec_off, depth): the records sorted by (tid, pos) and per contig depth[0 .. clen - 1] by the difference array's cumsum"""
+def positions(seed=33):
+    """per contig the sorted start positions of its records"""
     rng = np.random.default_rng(seed)
-    tid, pos, depth = [], [], []
+    pos = []
     for t, clen in enumerate(CLENS):
         p = [rng.integers(0, clen, 6000 if t == 0 else 500)]
         p += [np.full(k, at) for tt, at, k in SPIKES if tt == t]
-        p = np.sort(np.concatenate(p))
+        pos.append(np.sort(np.concatenate(p)))
+    return pos
+
+
+def records(seed=33):
+    """(raw, rec_off, depth): the records sorted by (tid, pos) and per contig depth[0 .. clen - 1] by the difference array's cumsum"""
+    tid, pos, depth = [], [], []
+    for t, (clen, p) in enumerate(zip(CLENS, positions(seed))):
         tid.append(np.full(len(p), t)); pos.append(p)
         diff = np.zeros(clen + 1, np.int64)
         np.add.at(diff, p, 1); np.add.at(diff, np.minimum(p + BASES, clen), -1)
@@ -58,6 +67,19 @@ def queries(t):
     q += [(-5, 3), (-5, clen + 9), (clen - 1, clen), (clen - 1, clen + 9), (clen - 2, clen - 1)]
     q = [(b, e) for b, e in q if b < e and max(b, 0) < min(e, clen)]
     return np.array([b for b, e in q], np.int32), np.array([e for b, e in q], np.int32)
+
+
+BACKS = (260, TILE + 1000)        # a record with a gap; a record longer than a tile of the scan
+
+
+def lookback_queries(t):
+    """the second half of the driver's call: every query of queries(t) with beg drawn out to the front by `back` bases, not below 0
+    (as depth_sum_deepest does) -- across tile edges, and at beg - back < 0"""
+    beg, end = queries(t)
+    b = np.concatenate([np.where(beg > back, beg - back, 0) for back in BACKS]).astype(np.int32)
+    crossing = int(((b // TILE) != (np.concatenate([beg, beg]) // TILE)).sum())          # the second contig is one tile long
+    assert (b == 0).sum() > 10 and (b > 0).sum() > 10 and (crossing > 10 or CLENS[t] <= TILE)
+    return b, np.concatenate([end, end]).astype(np.int32)
 
 
 def model(depth, beg, end):

@@ -70,5 +70,24 @@ def test_shim_matches_the_numpy_statement():
             bad = np.nonzero((got_sum != want_sum) | (got_max != want_max))[0]
             assert len(bad) == 0, (t, [(int(beg[i]), int(end[i]), int(got_sum[i]), int(want_sum[i]), int(got_max[i]), int(want_max[i])) for i in bad[:6]])
             assert np.array_equal(plain, want_sum)
+            # the windows drawn out to the front, as the driver sends them beside the plain ones
+            beg, end = dm.lookback_queries(t)
+            want_sum, want_max = dm.model(depth[t], beg, end)
+            got_sum, got_max = (np.zeros(len(beg), np.uint32) for _ in range(2))
+            assert L.im_depth_query_max_tid(h, t, len(beg), beg.ctypes.data, end.ctypes.data, got_sum.ctypes.data, got_max.ctypes.data) == 0
+            assert np.array_equal(got_sum, want_sum) and np.array_equal(got_max, want_max), t
+        # im_depth_query_max: the same statement on what im_depth_build left (the record-at-a-time path), each contig in turn
+        L.im_depth_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+        L.im_depth_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_depth_query_max.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for t, (clen, pos) in enumerate(zip(dm.CLENS, dm.positions())):
+            start, length = pos.astype(np.int32), np.full(len(pos), dm.BASES, np.int32)
+            assert L.im_depth_build(h, clen, len(start), start.ctypes.data, length.ctypes.data) == 0
+            beg, end = (np.concatenate(x) for x in zip(dm.queries(t), dm.lookback_queries(t)))
+            want_sum, want_max = dm.model(depth[t], beg, end)
+            got_sum, got_max, plain = (np.zeros(len(beg), np.uint32) for _ in range(3))
+            assert L.im_depth_query_max(h, len(beg), beg.ctypes.data, end.ctypes.data, got_sum.ctypes.data, got_max.ctypes.data) == 0
+            assert L.im_depth_query(h, len(beg), beg.ctypes.data, end.ctypes.data, plain.ctypes.data) == 0
+            assert np.array_equal(got_sum, want_sum) and np.array_equal(got_max, want_max) and np.array_equal(plain, want_sum), t
     finally:
         L.im_ctx_destroy(h)

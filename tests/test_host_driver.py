@@ -1129,7 +1129,8 @@ def test_product_multi_gpu_path_one_rank(synth_small, tmp_path):
 def _deep_locus(binary, tmp_path):
     """DP= at a locus deeper than samtools' pileup buffers (bam_pileup.c:172,244): 9000 plain pairs stacked on the base in front
     of a called deletion -- the reference's pileup stops taking the stack's records at 8000 nodes and prints DP=365 where a plain
-    depth count gives 409; 7900 stacked pairs stay below the cap.  Goldens: the compiled reference (make_golden_deep.py)."""
+    depth count gives 410; 7900 stacked pairs stay below the cap.  Goldens: the compiled reference (make_golden_deep.py).
+    The other geometries and the other routes: tests/test_deep_locus_routes.py."""
     from tests.support import deeplocus
     for name, depth in (("deep_locus_9000", 9000), ("deep_locus_7900", 7900)):
         d = tmp_path / name
