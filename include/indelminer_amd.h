@@ -975,6 +975,47 @@ int im_splitlink_count(im_ctx* ctx, int32_t nq, const int32_t* tid1, const uint8
 int im_splitlink_reset(im_ctx* ctx, void* stream);
 int im_splitlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
 
+/* Split junctions, the junctions the split links name BY THEMSELVES (-J).  Every search above starts from two piles of clipped reads
+ * on one position each and compares clipped bases with the reference; im_splitlink_count only counts links for a record found that
+ * way.  A junction with inserted bases, with more micro-homology than 32 bases, or whose reads were clipped at scattered positions has
+ * no such record, though every read across it stores a link that names both ends to the base.  This search reads the table alone.
+ *
+ * A stored link is L = (tA, pA, sA, tB, pB, sB).  rev(L) = (tB, pB, sB, tA, pA, sA).  can(L) = L when (tA, pA, sA) <= (tB, pB, sB)
+ * in lexicographic order, rev(L) otherwise; a canonical tuple is written (t1, p1, s1, t2, p2, s2).  With W = window (0 .. 255),
+ * min_span >= 0 and min_links >= 1:
+ *   1. CANDIDATES  a stored link is a candidate iff tA != tB or |pA - pB| >= min_span (a smaller event is an indel: stdout's); a
+ *      candidate junction is a distinct value c = can(L) of a candidate link;
+ *   2. EXACT SUPPORT  E(c) = the number of stored links equal to c or to rev(c) (a link equal to both counts once);
+ *   3. NEAR  two candidate junctions c, c' are near iff t1, s1, t2, s2 are equal and |p1 - p1'| <= W and |p2 - p2'| <= W;
+ *   4. PEAK  c is a peak iff no near candidate junction c' BEATS it; c' beats c on the larger E, among equal E on the smaller p1, then
+ *      on the smaller p2.  This is non-maximum suppression, the peak rule of "Crossed piles" in two dimensions, and like it NOT
+ *      transitive: a candidate suppressed by a neighbour that is itself suppressed stays suppressed;
+ *   5. COUNTS  n1 of a peak is, by definition, what im_splitlink_count answers for (t1, s1, p1 - W, p1 + W, t2, s2, p2 - W, p2 + W) and
+ *      n2 what it answers with the two ends exchanged; EVERY stored link counts, candidate or not;
+ *   6. THRESHOLD  a peak with n1 + n2 < min_links is dropped, after the suppression: it un-suppresses nothing;
+ *   7. ORDER  the answer is the remaining peaks, each once, sorted by (t1, p1, t2, p2, s1, s2).
+ * No answer depends on the order in which the links arrived or on the slots that hold them.
+ *
+ * WORKED EXAMPLE, W = 32, min_span = 50, min_links = 3, the links stored (contig 0 throughout):
+ *   3 x (0, 1000, 0, 0, 5000, 1)   2 x (0, 5000, 1, 0, 1000, 0)   2 x (0, 1020, 0, 0, 5010, 1)   1 x (0, 1040, 0, 0, 5030, 1)
+ *   1 x (0, 1010, 0, 0, 1030, 1)
+ * The last link spans 20 bases: no candidate.  The second group is the reverse of the first: c1 = (0, 1000, 0, 0, 5000, 1) has
+ * E = 5; c2 = (0, 1020, 0, 0, 5010, 1) has E = 2; c3 = (0, 1040, 0, 0, 5030, 1) has E = 1.  c1 and c2 are near (20, 10), c2 and c3 are
+ * near (20, 20), c1 and c3 are not (40 > W).  c1 beats c2, c2 beats c3: c1 is the one peak, and c3 stays suppressed although the
+ * junction that beats it is suppressed itself.  n1 of c1 counts the links from [968, 1032] side 0 to [4968, 5032] side 1: 3 + 2 = 5 (the
+ * short link ends at 1030, outside); n2 counts those from [4968, 5032] side 1 to [968, 1032] side 0: 2.  The answer is the one row
+ * (0, 1000, 0, 0, 5000, 1), E = 5, n1 = 5, n2 = 2.
+ *
+ * im_splitlink_junctions answers the whole table in one call: synchronous, on the context's stream, behind what is queued there.
+ * *found is ALWAYS the number of junctions; when it exceeds cap nothing is written and the caller asks again with a larger cap (the
+ * idiom of im_clip_peaks_tid).  Once the table has dropped links *found = -1, nothing is written and the call returns IM_OK: no
+ * answer, not a wrong one.  window outside 0 .. 255, min_links < 1, min_span < 0, cap < 0, a null found, a null column with cap >= 1
+ * and a table that im_splitlink_enable has not made are IM_E_ARG with a message.  The call allocates its workspace (12 bytes per
+ * stored link, 4 per slot of the table, the columns) and frees it: it is meant to be made once per run.  A site with n links is n
+ * walks of a probe run of n. */
+int im_splitlink_junctions(im_ctx* ctx, int32_t window, int32_t min_links, int32_t min_span, int32_t cap, int32_t* tid1, int32_t* pos1, uint8_t* side1,
+                           int32_t* tid2, int32_t* pos2, uint8_t* side2, uint32_t* exact, uint32_t* n1, uint32_t* n2, int32_t* found);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

@@ -264,6 +264,7 @@ def lib():
         L.im_splitlink_count.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
         L.im_splitlink_reset.argtypes = [C.c_void_p, C.c_void_p]
         L.im_splitlink_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.im_splitlink_junctions.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 9 + [C.POINTER(C.c_int32)]
         L.im_cliptail_junction.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 5
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -846,6 +847,14 @@ class Context:
     def splitlink_stats(self):
         """(links stored, links dropped) since the last reset"""
         return self._keyed_stats(lib().im_splitlink_stats)
+
+    _JUNCTIONS = (np.int32, np.int32, np.uint8, np.int32, np.int32, np.uint8, np.uint32, np.uint32, np.uint32)
+
+    def splitlink_junctions(self, window, min_links, min_span, cap=65536):
+        """(tid1, pos1, side1, tid2, pos2, side2, exact, n1, n2) of the junctions the split links name by themselves (-J), sorted by
+        (tid1, pos1, tid2, pos2, side1, side2): the distinct end pairs min_span apart that no pair within window at both ends beats
+        on exact support, with min_links links between their windows; None once the table has overflowed"""
+        return self._clip_search(lib().im_splitlink_junctions, self._JUNCTIONS, cap, window, min_links, min_span)
 
     def cliptail_junction(self, tid1, p1, side1, tid2, p2, side2, max_shift=32):
         """per query of two ends (tid, position, side 0: right clips, 1: left clips): (v1, v2, shift, stored1, stored2) -- the entries of

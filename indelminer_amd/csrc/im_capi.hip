@@ -1827,6 +1827,69 @@ int im_splitlink_count(im_ctx* ctx, int32_t nq, const int32_t* tid1, const uint8
     return keyed_answers(ctx, ctx->split, C, 8, {{count_out, 4}});
 }
 
+// The junctions of the table alone.  The table's counters first: after an overflow there is no answer, and counters[0] is the list's
+// length.  The workspace is this call's own (12 bytes per stored link, 4 per slot, the nine columns), allocated here and freed here: the
+// call is made once per run.  Three launches, the count back, then -- when it fits cap -- the columns, sorted here by (tid1, pos1, tid2,
+// pos2, side1, side2).
+int im_splitlink_junctions(im_ctx* ctx, int32_t window, int32_t min_links, int32_t min_span, int32_t cap, int32_t* tid1, int32_t* pos1, uint8_t* side1,
+                           int32_t* tid2, int32_t* pos2, uint8_t* side2, uint32_t* exact, uint32_t* n1, uint32_t* n2, int32_t* found)
+{
+    if (!ctx) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->split, nullptr);
+    if (rc) return rc;
+    const char* who = "im_splitlink_junctions";
+    if (window < 0 || window > 255) { set_err(ctx, "%s: window %d, must be 0 .. 255", who, window); return IM_E_ARG; }
+    if (min_links < 1) { set_err(ctx, "%s: min_links %d, must be >= 1", who, min_links); return IM_E_ARG; }
+    if (min_span < 0) { set_err(ctx, "%s: min_span %d, must be >= 0", who, min_span); return IM_E_ARG; }
+    if (cap < 0) { set_err(ctx, "%s: cap %d, must be >= 0", who, cap); return IM_E_ARG; }
+    if (!found) { set_err(ctx, "%s: found is null", who); return IM_E_ARG; }
+    if (cap > 0 && (!tid1 || !pos1 || !side1 || !tid2 || !pos2 || !side2 || !exact || !n1 || !n2)) { set_err(ctx, "%s: a null column with cap %d", who, cap); return IM_E_ARG; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long counters[2] = {0, 0};
+    if ((rc = keyed_counters(ctx, ctx->split, counters))) return rc;
+    if (counters[1] > 0) { *found = -1; return IM_OK; }
+    *found = 0;
+    if (counters[0] == 0) return IM_OK;
+    const size_t n_list = (size_t)counters[0], slots = (size_t)1 << ctx->split.log2_slots;
+    const size_t lb = up256(sizeof(uint32_t) * n_list), eb = up256(sizeof(uint32_t) * slots), cb = up256(sizeof(uint32_t) * (size_t)(cap ? cap : 1));
+    char* ws = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&ws, 256 + 3 * lb + eb + 9 * cb));
+    im::SplitJuncArgs A;
+    A.tab = ctx->split; A.len = ctx->d_len; A.window = window; A.min_links = min_links; A.min_span = min_span; A.cap = cap; A.n_list = (uint32_t)n_list;
+    A.counters = (unsigned long long*)ws;
+    A.list = (uint32_t*)(ws + 256); A.n_own = (uint32_t*)(ws + 256 + lb); A.n_far = (uint32_t*)(ws + 256 + 2 * lb); A.exact = (uint32_t*)(ws + 256 + 3 * lb);
+    for (int k = 0; k < 9; k++) A.col[k] = (uint32_t*)(ws + 256 + 3 * lb + eb + k * cb);
+    unsigned long long got[2] = {0, 0};
+    hipError_t e = im::launch_splitlink_junctions(A, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(got, A.counters, sizeof got, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    const size_t n = (size_t)got[1];
+    std::vector<uint32_t> h(n <= (size_t)cap ? 9 * n : 0);
+    if (e == hipSuccess && n > 0 && n <= (size_t)cap) {
+        for (int k = 0; k < 9 && e == hipSuccess; k++) e = hipMemcpyAsync(h.data() + k * n, A.col[k], sizeof(uint32_t) * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    const hipError_t ef = hipFree(ws);
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) { set_err(ctx, "%s: %s", who, hipGetErrorString(e)); return IM_E_HIP; }
+    *found = (int32_t)n;
+    if (n == 0 || n > (size_t)cap) return IM_OK;
+    std::vector<uint32_t> order(n);
+    for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+    const int by[6] = {0, 1, 3, 4, 2, 5};                           // the driver's record order: tid1, pos1, tid2, pos2, side1, side2
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        for (int k : by) if (h[k * n + a] != h[k * n + b]) return h[k * n + a] < h[k * n + b];
+        return false;
+    });
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t r = order[i];
+        tid1[i] = (int32_t)h[r]; pos1[i] = (int32_t)h[n + r]; side1[i] = (uint8_t)h[2 * n + r];
+        tid2[i] = (int32_t)h[3 * n + r]; pos2[i] = (int32_t)h[4 * n + r]; side2[i] = (uint8_t)h[5 * n + r];
+        exact[i] = h[6 * n + r]; n1[i] = h[7 * n + r]; n2[i] = h[8 * n + r];
+    }
+    return IM_OK;
+}
+
 // six columns in, one launch, the five answers and the two counters back, one wait; after an overflow every answer is "none"
 int im_cliptail_junction(im_ctx* ctx, int32_t nq, const int32_t* tid1, const int32_t* p1, const uint8_t* side1, const int32_t* tid2, const int32_t* p2,
                          const uint8_t* side2, int32_t max_shift, uint32_t* v1, uint32_t* v2, int32_t* shift, uint32_t* stored1, uint32_t* stored2)

@@ -219,6 +219,23 @@ hipError_t launch_splitlink_add(const RefDev& ref, int32_t n, const int32_t* tid
 hipError_t launch_splitlink_count(const RefDev& ref, int32_t nq, const int32_t* tid1, const uint8_t* side1, const int32_t* a0, const int32_t* a1,
                                   const int32_t* tid2, const uint8_t* side2, const int32_t* b0, const int32_t* b1, const KeyedTable& tab,
                                   uint32_t* count, hipStream_t stream);
+// The junctions of the split links alone (include/indelminer_amd.h, "Split junctions"): a sweep lists the occupied slots, a wave per
+// listed link counts E and the two windows, a wave per 64 of them decides the peaks.  The caller provides the workspace (counters: two
+// words; list, n_own, n_far: n_list words each; exact: a word per SLOT) and nine columns of max(cap, 1) words; the launch clears the
+// counters.  counters[1] is the number of junctions, of which the first cap that take a row are written, in no particular order.
+struct SplitJuncArgs {
+    KeyedTable tab;
+    const int32_t* len;
+    int32_t window, min_links, min_span, cap;
+    uint32_t n_list;                    // the list's length: the links stored (the ticket rule makes it exact)
+    unsigned long long* counters;       // [0] the slots listed, [1] the junctions found
+    uint32_t* list;                     // n_list: a listed link's slot; bit 31: it is the emitter among its equals
+    uint32_t* exact;                    // per SLOT: E of the candidate link it holds
+    uint32_t* n_own;                    // n_list: the links from the window around its own end to the window around its far end
+    uint32_t* n_far;                    // n_list: the same with the ends exchanged
+    uint32_t* col[9];                   // tid1, pos1, side1, tid2, pos2, side2, exact, n1, n2
+};
+hipError_t launch_splitlink_junctions(const SplitJuncArgs& A, hipStream_t stream);
 // per query (tid1, p1, side1, tid2, p2, side2): the entries at either end that continue in the OTHER end's contig at the best shift
 // 0 .. max_shift <= 32 (include/indelminer_amd.h, "Junctions"), that shift (-1: none matched), and the entries stored at the two keys
 struct TailJunctionArgs {

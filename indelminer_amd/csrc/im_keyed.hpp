@@ -65,8 +65,10 @@ __device__ __forceinline__ void keyed_insert(const KeyedTable& T, uint64_t home,
 // one-entry form does not carry the second) and 64 bytes of LDS, thread 0 adds the workgroup's total to counters[0], and the lane's
 // tickets are *first_ticket .. *first_ticket + mine - 1.  Returns false, for the whole workgroup and before the atomic, when the
 // workgroup has nothing to insert -- most workgroups of a chunk.  Every thread of the workgroup calls it, once per kernel.
+// block_tickets is that draw on the counter it is given (the split-junction sweep of im_links.hip ranks the slots it lists with it);
+// keyed_block_tickets, behind it, is the table's.
 template <int kBlock, int kMaxPerLane>
-__device__ __forceinline__ bool keyed_block_tickets(const KeyedTable& T, uint32_t mine, unsigned long long* first_ticket)
+__device__ __forceinline__ bool block_tickets(unsigned long long* counter, uint32_t mine, unsigned long long* first_ticket)
 {
     static_assert(kBlock % 64 == 0 && (kMaxPerLane == 1 || kMaxPerLane == 2), "whole waves; one ballot per entry a lane may hold");
     __shared__ uint32_t s_wave[kBlock / 64];
@@ -85,10 +87,16 @@ __device__ __forceinline__ bool keyed_block_tickets(const KeyedTable& T, uint32_
 #pragma unroll
     for (int w = 0; w < kBlock / 64; w++) { before += w < wave ? s_wave[w] : 0u; total += s_wave[w]; }
     if (total == 0u) return false;                                  // uniform over the workgroup
-    if (t == 0) s_base = atomicAdd(&T.counters[0], (unsigned long long)total);
+    if (t == 0) s_base = atomicAdd(counter, (unsigned long long)total);
     __syncthreads();
     *first_ticket = s_base + before + rank;
     return true;
+}
+
+template <int kBlock, int kMaxPerLane>
+__device__ __forceinline__ bool keyed_block_tickets(const KeyedTable& T, uint32_t mine, unsigned long long* first_ticket)
+{
+    return block_tickets<kBlock, kMaxPerLane>(&T.counters[0], mine, first_ticket);
 }
 
 // The walk every query shares: the wave goes along the probe run that starts at home 64 slots at a time until a batch shows an empty

@@ -38,6 +38,12 @@
 //                      SA:Z (find_tag, im_rg.hpp), the parse of its one entry and the contig-name look-up; tickets as above
 //   splitlink_add      one lane per link the caller names, as six columns
 //   splitlink_count    one wave per query (tid1, side1, [a0, a1], tid2, side2, [b0, b1]): the links between the two ends
+//
+// THE SPLIT JUNCTIONS (-J): the junctions the stored split links name by themselves, searched in the table alone.  The rule is in
+// include/indelminer_amd.h (seam 5, "Split junctions"); DESIGN.md 4.5m has the rest.  Three launches of one call, made once per run:
+//   splitjunc_sweep    one lane per slot: the occupied slots into a list, on ranks the workgroup draws with one atomic add
+//   splitjunc_count    one wave per listed link: E, the two window counts and the one emitter among equal links
+//   splitjunc_peak     one wave per 64 listed links: an emitter's neighbours' E decide the peak; rows through one ballot and one atomic add
 
 #include "im_keyed.hpp"
 #include "im_rg.hpp"
@@ -577,6 +583,177 @@ __global__ __launch_bounds__(kLinkWaveBlock) void splitlink_count_kernel(SplitCo
     }
 }
 
+// ---- the junctions of the split links alone (-J): include/indelminer_amd.h, "Split junctions", has the rule ----------
+
+// A stored link, out of its slot's two words
+struct SplitLink {
+    int32_t ta, tb;
+    int64_t pa, pb;
+    uint32_t sa, sb;
+};
+
+__device__ __forceinline__ SplitLink split_decode(uint64_t key, uint64_t payload)
+{
+    SplitLink l;
+    l.ta = (int32_t)((key >> 26) & 0xFFFFFFull); l.tb = (int32_t)(((uint32_t)payload >> 8) & 0xFFFFFFu);
+    l.pa = (int64_t)(((key >> 2) & 0xFFFFFFull) << kLinkBucketShift) | (int64_t)(payload & 255ull); l.pb = (int64_t)(uint32_t)(payload >> 32);
+    l.sa = (uint32_t)key & 1u; l.sb = ((uint32_t)key >> 1) & 1u;
+    return l;
+}
+
+// rev, can and the candidate test of the rule
+__device__ __forceinline__ SplitLink split_rev(const SplitLink& l) { return SplitLink{l.tb, l.ta, l.pb, l.pa, l.sb, l.sa}; }
+
+__device__ __forceinline__ bool split_is_can(const SplitLink& l)
+{
+    if (l.ta != l.tb) return l.ta < l.tb;
+    if (l.pa != l.pb) return l.pa < l.pb;
+    return l.sa <= l.sb;
+}
+
+__device__ __forceinline__ SplitLink split_can(const SplitLink& l) { return split_is_can(l) ? l : split_rev(l); }
+
+__device__ __forceinline__ bool split_candidate(const SplitLink& l, int64_t min_span)
+{
+    const int64_t d = l.pa > l.pb ? l.pa - l.pb : l.pb - l.pa;
+    return l.ta != l.tb || d >= min_span;
+}
+
+constexpr uint32_t kJuncEmitter = 1u << 31;     // a slot index is below 2^30
+
+// The links from end A = (ta, sa, pa +- window) to end B = (tb, sb, pb +- window), by the whole wave: the one to three buckets of A's
+// window, both windows clipped to their contig (what splitlink_count_kernel does with a query).  each(has, slot, l) is called for
+// every batch that holds a link of A's buckets and kind; has says whether this lane's slot does, l is that link (zeros without), and
+// the link is INSIDE both windows iff in(l).  Every branch is the wave's; the loops are bounded by the bucket and the slot count.
+struct SplitEnds {
+    int32_t ta, tb;
+    uint32_t kind;
+    int64_t a0, a1, b0, b1;
+    __device__ __forceinline__ bool in(const SplitLink& l) const { return l.pa >= a0 && l.pa <= a1 && l.tb == tb && l.pb >= b0 && l.pb <= b1; }
+};
+
+__device__ __forceinline__ SplitEnds split_ends(const SplitJuncArgs& A, int32_t ta, int64_t pa, uint32_t sa, int32_t tb, int64_t pb, uint32_t sb)
+{
+    SplitEnds e;
+    e.ta = ta; e.tb = tb; e.kind = sa | (sb << 1);
+    e.a0 = pa - A.window; e.a1 = pa + A.window; e.b0 = pb - A.window; e.b1 = pb + A.window;
+    (void)link_clip(&e.a0, &e.a1, A.len[ta]);       // a stored position lies in [0, length]: something is left of both
+    (void)link_clip(&e.b0, &e.b1, A.len[tb]);
+    return e;
+}
+
+template <class Each>
+__device__ __forceinline__ void split_walk(const KeyedTable& T, const SplitEnds& e, int lane, Each each)
+{
+    for (int64_t bucket = e.a0 >> kLinkBucketShift; bucket <= (e.a1 >> kLinkBucketShift); bucket++) {
+        const uint64_t want = link_key(e.ta, bucket, e.kind);
+        (void)keyed_walk(T, keyed_home(want, T.log2_slots), [want](uint64_t key) { return key == want; }, lane,
+                         [&](bool has, uint64_t key, uint64_t s) { each(has, (uint32_t)s, split_decode(has ? key : 0ull, has ? T.slots[2ull * s + 1ull] : 0ull)); });
+    }
+}
+
+// 1. The sweep: one lane per slot; the occupied ones take a place in the list, on ranks their workgroup draws with one atomic add.
+__global__ __launch_bounds__(kLinkBlock) void splitjunc_sweep_kernel(SplitJuncArgs A)
+{
+    const uint64_t s = (uint64_t)blockIdx.x * kLinkBlock + threadIdx.x;
+    const bool used = s < (1ull << A.tab.log2_slots) && A.tab.slots[2ull * s] != 0ull;
+    unsigned long long at;
+    if (!block_tickets<kLinkBlock, 1>(&A.counters[0], used ? 1u : 0u, &at)) return;
+    if (used && at < (unsigned long long)A.n_list) A.list[at] = (uint32_t)s;
+}
+
+// 2. One wave per listed link.  A link that is no candidate is done at once.  The others walk the buckets around their own end and,
+// under the swapped kind, around their far end, and leave E at their slot, the two window counts at their place in the list, and --
+// one link per distinct junction -- the emitter mark: among the links equal to it, the one in the lowest slot; a link that is not
+// canonical only while no link equal to its reverse is stored.
+__global__ __launch_bounds__(kLinkWaveBlock) void splitjunc_count_kernel(SplitJuncArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+    const unsigned long long listed = A.counters[0];
+    const uint32_t n = listed < (unsigned long long)A.n_list ? (uint32_t)listed : A.n_list;
+    for (uint32_t i = wave; i < n; i += nwaves) {
+        const uint32_t s = A.list[i];
+        const SplitLink l = split_decode(A.tab.slots[2ull * s], A.tab.slots[2ull * s + 1ull]);
+        if (!split_candidate(l, A.min_span)) continue;                 // the wave's: every lane holds the same link
+        uint32_t n_own = 0, n_far = 0, eq_own = 0, eq_far = 0, lower = 0;
+        const SplitEnds own = split_ends(A, l.ta, l.pa, l.sa, l.tb, l.pb, l.sb), far = split_ends(A, l.tb, l.pb, l.sb, l.ta, l.pa, l.sa);
+        split_walk(A.tab, own, lane, [&](bool has, uint32_t slot, const SplitLink& m) {
+            const bool eq = has && m.pa == l.pa && m.tb == l.tb && m.pb == l.pb;
+            n_own += (uint32_t)__builtin_popcountll(__ballot(has && own.in(m)));
+            eq_own += (uint32_t)__builtin_popcountll(__ballot(eq));
+            lower += (uint32_t)__builtin_popcountll(__ballot(eq && slot < s));
+        });
+        split_walk(A.tab, far, lane, [&](bool has, uint32_t, const SplitLink& m) {
+            n_far += (uint32_t)__builtin_popcountll(__ballot(has && far.in(m)));
+            eq_far += (uint32_t)__builtin_popcountll(__ballot(has && m.pa == l.pb && m.tb == l.ta && m.pb == l.pa));
+        });
+        const bool own_rev = l.ta == l.tb && l.pa == l.pb && l.sa == l.sb;      // rev(l) == l: the second walk met the first one's links
+        const bool emits = lower == 0u && (split_is_can(l) || eq_far == 0u);
+        if (lane == 0) {
+            A.exact[s] = own_rev ? eq_own : eq_own + eq_far;
+            A.n_own[i] = n_own; A.n_far[i] = n_far;
+            if (emits) A.list[i] = s | kJuncEmitter;
+        }
+    }
+}
+
+// 3. One wave per 64 places of the list, a lane each: the emitters whose counts reach min_links are taken one by one.  The wave walks
+// the same runs again for the candidates near the emitter's junction, reads their E and decides the peak; the surviving lanes take
+// their rows through one ballot and one atomic add.  An emitter below min_links needs no walk: it is dropped whatever the walk says,
+// and the others find its E at its slot all the same.
+__global__ __launch_bounds__(kLinkWaveBlock) void splitjunc_peak_kernel(SplitJuncArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+    const unsigned long long listed = A.counters[0];
+    const uint32_t n = listed < (unsigned long long)A.n_list ? (uint32_t)listed : A.n_list;
+    const int64_t w = A.window;
+    for (uint32_t base = wave * 64u; base < n; base += nwaves * 64u) {
+        const uint32_t i = base + (uint32_t)lane;
+        const uint32_t mark = i < n ? A.list[i] : 0u, s = mark & ~kJuncEmitter;
+        SplitLink c = SplitLink{0, 0, 0, 0, 0u, 0u};
+        uint32_t e = 0, n1 = 0, n2 = 0;
+        if (mark & kJuncEmitter) {
+            const SplitLink l = split_decode(A.tab.slots[2ull * s], A.tab.slots[2ull * s + 1ull]);
+            const bool is_can = split_is_can(l);
+            c = split_can(l); e = A.exact[s];
+            n1 = is_can ? A.n_own[i] : A.n_far[i]; n2 = is_can ? A.n_far[i] : A.n_own[i];
+        }
+        uint64_t todo = __ballot((mark & kJuncEmitter) != 0u && (uint64_t)n1 + (uint64_t)n2 >= (uint64_t)A.min_links), peaks = 0ull;
+        for (int turn = 0; turn < 64 && todo; turn++) {                 // the wave's: todo is a ballot
+            const int j = (int)__builtin_ctzll(todo);
+            todo &= todo - 1ull;
+            SplitLink x;
+            x.ta = __shfl(c.ta, j); x.tb = __shfl(c.tb, j); x.sa = (uint32_t)__shfl((int)c.sa, j); x.sb = (uint32_t)__shfl((int)c.sb, j);
+            x.pa = (int64_t)(uint32_t)__shfl((int)(uint32_t)c.pa, j); x.pb = (int64_t)(uint32_t)__shfl((int)(uint32_t)c.pb, j);
+            const uint32_t xe = (uint32_t)__shfl((int)e, j);
+            bool beaten = false;
+            const auto meet = [&](bool has, uint32_t slot, const SplitLink& m) {
+                const SplitLink y = split_can(m);
+                const bool near_x = has && split_candidate(m, A.min_span) && y.ta == x.ta && y.sa == x.sa && y.tb == x.tb && y.sb == x.sb &&
+                                    y.pa >= x.pa - w && y.pa <= x.pa + w && y.pb >= x.pb - w && y.pb <= x.pb + w;
+                const uint32_t ye = near_x ? A.exact[slot] : 0u;
+                const bool beats = near_x && (ye > xe || (ye == xe && (y.pa < x.pa || (y.pa == x.pa && y.pb < x.pb))));
+                beaten = beaten || __ballot(beats) != 0ull;
+            };
+            split_walk(A.tab, split_ends(A, x.ta, x.pa, x.sa, x.tb, x.pb, x.sb), lane, meet);
+            split_walk(A.tab, split_ends(A, x.tb, x.pb, x.sb, x.ta, x.pa, x.sa), lane, meet);
+            if (!beaten) peaks |= 1ull << j;
+        }
+        if (!peaks) continue;                                           // the wave's
+        unsigned long long first = 0ull;
+        if (lane == 0) first = atomicAdd(&A.counters[1], (unsigned long long)__builtin_popcountll(peaks));
+        first = (unsigned long long)(uint64_t)uni64((int64_t)first);
+        const unsigned long long row = first + (unsigned long long)__builtin_popcountll(peaks & ((1ull << lane) - 1ull));
+        if (((peaks >> lane) & 1ull) && row < (unsigned long long)A.cap) {
+            A.col[0][row] = (uint32_t)c.ta; A.col[1][row] = (uint32_t)c.pa; A.col[2][row] = c.sa;
+            A.col[3][row] = (uint32_t)c.tb; A.col[4][row] = (uint32_t)c.pb; A.col[5][row] = c.sb;
+            A.col[6][row] = e; A.col[7][row] = n1; A.col[8][row] = n2;
+        }
+    }
+}
+
 template <class Kernel>
 hipError_t launch_link_scatter(Kernel kernel, const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)
 {
@@ -666,6 +843,19 @@ hipError_t launch_splitlink_count(const RefDev& ref, int32_t nq, const int32_t* 
     A.nq = nq; A.tid1 = tid1; A.side1 = side1; A.a0 = a0; A.a1 = a1; A.tid2 = tid2; A.side2 = side2; A.b0 = b0; A.b1 = b1; A.len = ref.len;
     A.tab = tab; A.count = count;
     hipLaunchKernelGGL(splitlink_count_kernel, dim3(wave_grid(nq)), dim3(kLinkWaveBlock), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_splitlink_junctions(const SplitJuncArgs& A, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(A.counters, 0, 2 * sizeof(unsigned long long), stream);
+    if (e != hipSuccess || A.n_list == 0u) return e;
+    const uint64_t slots = 1ull << A.tab.log2_slots;
+    hipLaunchKernelGGL(splitjunc_sweep_kernel, dim3((unsigned)((slots + kLinkBlock - 1) / kLinkBlock)), dim3(kLinkBlock), 0, stream, A);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(splitjunc_count_kernel, dim3(wave_grid(A.n_list)), dim3(kLinkWaveBlock), 0, stream, A);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(splitjunc_peak_kernel, dim3(wave_grid(((int64_t)A.n_list + 63) / 64)), dim3(kLinkWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 

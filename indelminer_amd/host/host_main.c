@@ -56,6 +56,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    (a pile of clipped reads on either contig that continue in the other, found through the read pairs that span them)\n");
     fprintf(file, "\t-S, with -U, -N or -T: add SR= to their records, the split reads (a soft-clipped\n");
     fprintf(file, "\t    primary record whose SA tag places the clipped part at the other breakpoint), from either end\n");
+    fprintf(file, "\t-J, with -G: write the junctions the split reads name by themselves to this file, a VCF of its own\n");
+    fprintf(file, "\t    (no clip pile and no verified bases needed: insertions at the junction, long micro-homology, scattered clips)\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -113,7 +115,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:MT:S")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:MT:SJ:")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -149,6 +151,7 @@ int main(int argc, char** argv)
         case 'M': g_pair_links = 1; break;                          /* not an option of the reference */
         case 'T': g_bnd_file = optarg; break;                       /* not an option of the reference */
         case 'S': g_split_links = 1; break;                         /* not an option of the reference */
+        case 'J': g_junc_file = optarg; break;                      /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -265,11 +268,20 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: split links (-S) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -J: behind -S's refusals; it needs -G alone (annotate mode and more than one rank are refused through it) and none of the others */
+    if (g_junc_file) {
+        if (!g_genotype) { fprintf(stderr, "indelminer: -J needs -G\n"); return EXIT_FAILURE; }
+        /* a junction's far end, and the reads there that name it from the other side, lie outside a walked stretch */
+        if (O.region != NULL) { fprintf(stderr, "indelminer: -J is not available with -c\n"); return EXIT_FAILURE; }
+        if (!SPLITJUNC_API_PRESENT) {
+            fprintf(stderr, "indelminer: split-link junctions (-J) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = g_split_links = 0; g_ins_file = g_dup_file = g_inv_file = g_bnd_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
+        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = g_split_links = 0; g_ins_file = g_dup_file = g_inv_file = g_bnd_file = g_junc_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {
@@ -423,10 +435,13 @@ int main(int argc, char** argv)
     }
     /* -T: once, behind -N's FILE, on either path: a junction has its two piles on two contigs */
     if (MATELINK_ON) bnd_search(&d);
+    /* -J: once, behind -T's FILE, on either path: the table is keyed by contig and holds every chunk's links by now */
+    if (SPLITJUNC_ON) junc_search(&d);
     if (CLIPTAIL_ON) say_overflow(d.gpu, im_cliptail_stats, "indelminer: -V: the clip-tail table overflowed (%llu entries stored, %llu dropped): CV and CH are . from there on\n");
     if (PAIRLINK_ON) say_overflow(d.gpu, im_pairlink_stats, "indelminer: -M: the pair-link table overflowed (%llu links stored, %llu dropped): PE is . in the files of -U and -N\n");
     if (MATELINK_ON) say_overflow(d.gpu, im_matelink_stats, "indelminer: -T: the mate-link table overflowed (%llu links stored, %llu dropped): its file has no records\n");
     if (SPLITLINK_ON) say_overflow(d.gpu, im_splitlink_stats, "indelminer: -S: the split-link table overflowed (%llu links stored, %llu dropped): SR is . in the files of -U, -N and -T\n");
+    if (SPLITJUNC_ON) say_overflow(d.gpu, im_splitlink_stats, "indelminer: -J: the split-link table overflowed (%llu links stored, %llu dropped): its file has no records\n");
     if (t_out) fflush(t_out);
     if (g_timing) fprintf(stderr, "[timing] DP=: %ld windows asked of the device, %ld of them answered from the file (a position of %d records or more within %d bases in front)\n",
                           (long)g_dp_queries, (long)g_dp_from_file, DP_DEEP_LOCUS, (int)g_longest_span);

@@ -352,7 +352,7 @@ static int evidence_table_log2(const driver* d)
 }
 
 #define GPU2(drv, call) do { if ((call) != IM_OK) fatalf("%s: %s", #call, im_last_error((drv)->gpu)); } while (0)
-#define EVIDENCE_ON (SPAN_ON || PAIR_ON || CLIP_ON || PAIRLINK_ON || MATELINK_ON || SPLITLINK_ON)     /* -V needs -C */
+#define EVIDENCE_ON (SPAN_ON || PAIR_ON || CLIP_ON || PAIRLINK_ON || MATELINK_ON || SPLITTABLE_ON)     /* -V needs -C */
 
 /* Once per run, on either path, when the reference is on the device and the insert lengths are known: what the evidence options
  * keep on the device.  Genome-wide arrays and tables keyed by contig: nothing is reset between contigs. */
@@ -375,9 +375,9 @@ static void evidence_enable(driver* d)
     if (PAIRLINK_ON) GPU2(d, im_pairlink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
     /* -T: and the table of mate links, of the same size on the same assumption, which nobody has measured here either */
     if (MATELINK_ON) GPU2(d, im_matelink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
-    /* -S: and the table of split links, -C's clip and -q, the contig names as the BAM header spells them, in tid order; the same size
+    /* -S, -J: and the table of split links, -C's clip and -q, the contig names as the BAM header spells them, in tid order; the same size
      * on an assumption of its own (SPLIT_EV_SLOTS_SHIFT), which nobody has measured either */
-    if (SPLITLINK_ON) GPU2(d, im_splitlink_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, evidence_table_log2(d) - SPLIT_EV_SLOTS_SHIFT, d->hdr->n_targets,
+    if (SPLITTABLE_ON) GPU2(d, im_splitlink_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, evidence_table_log2(d) - SPLIT_EV_SLOTS_SHIFT, d->hdr->n_targets,
                                                   (const char* const*)d->hdr->target_name));
 }
 
@@ -390,7 +390,7 @@ static void evidence_scatter(driver* d, const im_dev_records* recs, void* stream
     if (CLIPTAIL_ON) GPU2(d, im_dev_cliptail_scatter(d->gpu, recs, stream));    /* -V: and one behind it, only then */
     if (PAIRLINK_ON) GPU2(d, im_dev_pairlink_scatter(d->gpu, recs, stream));    /* -M: and one behind that, only then */
     if (MATELINK_ON) GPU2(d, im_dev_matelink_scatter(d->gpu, recs, stream));    /* -T: and one behind that, only then */
-    if (SPLITLINK_ON) GPU2(d, im_dev_splitlink_scatter(d->gpu, recs, stream));  /* -S: and one behind that, only then */
+    if (SPLITTABLE_ON) GPU2(d, im_dev_splitlink_scatter(d->gpu, recs, stream)); /* -S, -J: and one behind that, only then */
 }
 
 /* The chunks of both paths: the pipelined walk's ring has up to PIPE_NCHUNK of them per walker (host_pipeline.c), the record-at-a-time
@@ -983,6 +983,76 @@ static void bnd_search(driver* d)
     }
     if (fclose(f) != 0) fatalf("cannot write %s", g_bnd_file);
     phase_time("inter-contig breakpoint evidence (device)");
+}
+
+/* -J's header: a line per INFO key, and the whole rule with its constants */
+static void junc_describe(FILE* f)
+{
+    fprintf(f, "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant: BND, one junction between two ends\">\n"
+               "##INFO=<ID=CHR2,Number=1,Type=String,Description=\"Contig of the second end\">\n"
+               "##INFO=<ID=POS2,Number=1,Type=Integer,Description=\"Position of the second end\">\n"
+               "##INFO=<ID=CT,Number=1,Type=String,Description=\"Which side of either end the junction joins: 3 = the reads there are clipped on their right, 5 = on their left\">\n"
+               "##INFO=<ID=JT,Number=1,Type=String,Description=\"What a junction of this CT on these contigs is read as: TRA on two contigs; on one, DEL for 3to5, DUP for 5to3, "
+               "INV for 3to3 and 5to5\">\n"
+               "##INFO=<ID=SVLEN,Number=1,Type=Integer,Description=\"POS2 - POS, on one contig only\">\n"
+               "##INFO=<ID=SE,Number=1,Type=Integer,Description=\"Split reads that name exactly these two ends, from either\">\n");
+    fprintf(f, "##INFO=<ID=SR,Number=2,Type=Integer,Description=\"Split reads whose primary part ends within %d bases of the first end and whose SA tag "
+               "places the clipped part within %d bases of the second, and the same from the second to the first\">\n", SPLIT_EV_WINDOW, SPLIT_EV_WINDOW);
+    fprintf(f, "##splitJunctions=\"junctions from split reads alone: a split read is a primary record at or above -q whose soft clip at either end has %d bases "
+               "or more and whose SA tag holds exactly one entry, itself at or above -q, that continues the read; it names two ends (contig, position, side); "
+               "an end pair on two contigs, or on one contig %d bases or more apart, is a candidate, its read count SE the reads that name exactly its two ends from "
+               "either; a candidate is kept when no candidate of the same contigs and sides within %d bases at both ends has a larger SE, or the same SE and a "
+               "smaller POS, then a smaller POS2 (a candidate that loses stays lost when its winner loses to a third); SR counts every split read between the "
+               "windows of %d bases around the two ends, from the first and from the second; a kept candidate needs SR of %d in sum; no clip pile and no "
+               "comparison with the reference is needed, so a junction with inserted bases, with micro-homology above %d bases or with reads clipped at "
+               "scattered positions is reported; nothing is merged with or filtered against the records of -U, -N and -T; no genotype; a tag with several "
+               "entries stores nothing; the file has no records once the split-link table has overflowed (stderr says so); POS 0 and POS2 0 are skipped\"\n",
+            CLIP_EV_MIN_CLIP, JUNC_EV_MIN_SPAN, SPLIT_EV_WINDOW, SPLIT_EV_WINDOW, JUNC_EV_MIN_LINKS, CLIPTAIL_MAX_SHIFT);
+}
+
+/* -J: the device's search over the table of split links, FILE.  Once per run, on either path, when every scatter has completed.  One
+ * call under g_query_mu, asked again with the cap it names while that exceeds the one it was given. */
+static void junc_search(driver* d)
+{
+    FILE* f = fopen(g_junc_file, "w");
+    if (!f) fatalf("cannot write %s", g_junc_file);
+    fprintf(f, "##fileformat=VCFv4.1\n");
+    junc_describe(f);
+    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
+    gpu_wait(d);
+    int32_t cap = 4096, found = 0;
+    int32_t* q = NULL; uint8_t* qs = NULL; uint32_t* a = NULL;
+    pthread_mutex_lock(&g_query_mu);
+    for (;; cap = found) {
+        const size_t n = (size_t)cap;
+        q = xrealloc(q, sizeof(int32_t) * 4 * n); qs = xrealloc(qs, 2 * n); a = xrealloc(a, sizeof(uint32_t) * 3 * n);
+        if (im_splitlink_junctions(d->gpu, SPLIT_EV_WINDOW, JUNC_EV_MIN_LINKS, JUNC_EV_MIN_SPAN, cap, q, q + n, qs, q + 2 * n, q + 3 * n, qs + n, a, a + n, a + 2 * n,
+                                   &found) != IM_OK)
+            fatalf("im_splitlink_junctions: %s", im_last_error(d->gpu));
+        if (found <= cap) break;
+    }
+    pthread_mutex_unlock(&g_query_mu);
+    static const char* const ct[2][2] = {{"3to3", "3to5"}, {"5to3", "5to5"}};
+    const size_t n = (size_t)cap;
+    for (int32_t k = 0; k < found; k++) {                       /* found = -1: the table has overflowed, the header alone */
+        const int32_t tid1 = q[k], p1 = q[n + k], tid2 = q[2 * n + k], p2 = q[3 * n + k];
+        const int s1 = qs[k], s2 = qs[n + k];
+        if (p1 == 0 || p2 == 0) continue;                       /* nothing in front to anchor on */
+        const char* c1 = d->hdr->target_name[tid1]; const char* c2 = d->hdr->target_name[tid2];
+        const int ref = toupper((unsigned char)d->sequences[tid1][p1 - 1]);
+        fprintf(f, "%s\t%d\t.\t%c\t", c1, p1, ref);
+        if (!s1 && s2) fprintf(f, "%c[%s:%d[", ref, c2, p2);
+        else if (s1 && !s2) fprintf(f, "]%s:%d]%c", c2, p2, ref);
+        else if (!s1) fprintf(f, "%c]%s:%d]", ref, c2, p2);
+        else fprintf(f, "[%s:%d[%c", c2, p2, ref);
+        const char* jt = tid1 != tid2 ? "TRA" : s1 == s2 ? "INV" : s1 ? "DUP" : "DEL";
+        fprintf(f, "\t.\t.\tSVTYPE=BND;CHR2=%s;POS2=%d;CT=%s;JT=%s", c2, p2, ct[s1][s2], jt);
+        if (tid1 == tid2) fprintf(f, ";SVLEN=%d", p2 - p1);
+        fprintf(f, ";SE=%u;SR=%u,%u\n", a[k], a[n + k], a[2 * n + k]);
+    }
+    free(q); free(qs); free(a);
+    if (fclose(f) != 0) fatalf("cannot write %s", g_junc_file);
+    phase_time("split-link junctions (device)");
 }
 
 static void run_contig(driver* d, int32_t tid, int32_t beg, int32_t end, bgzf_reader* r)

@@ -276,6 +276,20 @@ extern int im_splitlink_stats(im_ctx*, uint64_t*, uint64_t*) __attribute__((weak
 #define SPLIT_EV_SLOTS_SHIFT LINK_EV_SLOTS_SHIFT   /* the pair-link table's size: split reads are ASSUMED rarer than clipped reads by the same
                                                     * factor, which nobody has measured on real data -- a library with long reads splits more */
 #define SPLITLINK_NONE 0xFFFFFFFFu                 /* what the device answers after its table has overflowed */
+/* -J FILE, with -G: the junctions the split links name BY THEMSELVES (the device's search over the table of split links:
+ * include/indelminer_amd.h, "Split junctions").  -U, -N and -T need two piles of three clipped reads on one position each whose clipped
+ * bases continue in the reference at the other pile; a junction with inserted bases, with more micro-homology than CLIPTAIL_MAX_SHIFT,
+ * or whose reads were clipped at scattered positions has none, though every read across it names both ends.  A small VCF of its own in
+ * breakend notation, written to FILE once, behind -T's.  It keeps the table of split links on its own and needs none of -C, -V, -U, -N,
+ * -T, -M and -S; stdout, stderr and the other FILEs stay as they are.  Not an option of the reference; referenced weakly. */
+static const char* g_junc_file = NULL;
+extern int im_splitlink_junctions(im_ctx*, int32_t, int32_t, int32_t, int32_t, int32_t*, int32_t*, uint8_t*, int32_t*, int32_t*, uint8_t*, uint32_t*,
+                                  uint32_t*, uint32_t*, int32_t*) __attribute__((weak));
+#define SPLITJUNC_ON (g_junc_file != NULL)
+#define SPLITTABLE_ON (SPLITLINK_ON || SPLITJUNC_ON)    /* the walk keeps the split links: the table, its scatter, its overflow line; SPLITLINK_ON is SR= alone */
+#define SPLITJUNC_API_PRESENT (SPLITLINK_API_PRESENT && im_splitlink_junctions)
+#define JUNC_EV_MIN_SPAN DUP_EV_MIN_LEN            /* the two ends of one contig at least this far apart: a smaller event is stdout's indel */
+#define JUNC_EV_MIN_LINKS DUP_EV_MIN_READS         /* split reads between the windows around the two ends, from either: the clip peak's read count */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that
