@@ -1016,6 +1016,42 @@ int im_splitlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped);
 int im_splitlink_junctions(im_ctx* ctx, int32_t window, int32_t min_links, int32_t min_span, int32_t cap, int32_t* tid1, int32_t* pos1, uint8_t* side1,
                            int32_t* tid2, int32_t* pos2, uint8_t* side2, uint32_t* exact, uint32_t* n1, uint32_t* n2, int32_t* found);
 
+/* Junction genotypes (-K): a junction of im_splitlink_junctions against the reads that run through its two ends on the reference allele.
+ * Both halves are on the device already.  For a junction (t1, p1, s1, t2, p2, s2, E, n1, n2), in array coordinates:
+ *   ALT = n1 + n2.  A read stores ONE link, at its primary record's end, so the two window counts are disjoint sets of reads: their sum
+ *     is the number of reads of the junction allele.
+ *   RS1 = span[t1][p1] and RS2 = span[t2][p2], of the genome-wide array of this seam's first family (im_span_enable's flank and
+ *     min_mapq).  The boundary in front of base p is where a right clip at refend = p and a left clip at pos = p both put the junction:
+ *     span[p] counts the runs with `flank` matched bases on either side of exactly that boundary.  A split read's own run ends there,
+ *     so it is in neither.
+ *   RS = min(RS1, RS2), except for a tandem duplication (JT=DUP: one contig, s1 = 1, s2 = 0), where RS = max(0, min(RS1, RS2) - ALT).
+ *     A tandem duplication leaves both outer boundaries of the duplicated segment intact ON THE DUPLICATED ALLELE: every copy of that
+ *     allele adds reference-looking reads at p1 and at p2 at the rate at which it adds junction reads.  Uncorrected, a homozygous
+ *     duplication shows RS ~ ALT and could never be called 1/1; the correction takes away as many reads as the junction has.
+ *   (GT, GQ) are the genotype columns' own integers from (RS, ALT): in thousandths of a phred L(0/0) = ALT * 20000 + RS * 44,
+ *     L(0/1) = (ALT + RS) * 3010, L(1/1) = ALT * 44 + RS * 20000; GT is the smallest (the lower index wins a tie), GQ the distance to
+ *     the second smallest, rounded to whole phreds, at most 99.
+ *
+ * WORKED EXAMPLE, 10 reads per allele copy.  A heterozygous deletion junction (0, 1000, 0, 0, 1500, 1) with n1 = 5, n2 = 5 and
+ * span[1000] = 10, span[1500] = 12: ALT = 10, RS = min(10, 12) = 10, L = (200440, 60200, 200440): GT 0/1, GQ 99.  A homozygous tandem
+ * duplication (0, 3000, 1, 0, 3400, 0) with n1 = 10, n2 = 10 and span[3000] = span[3400] = 20 (both copies of the allele, reads through
+ * either outer boundary): ALT = 20, RS = max(0, 20 - 20) = 0, L = (400000, 60200, 880): GT 1/1, GQ 59.  Without the correction RS would
+ * be 20 and L = (400880, 120400, 400880): 0/1 at GQ 99, for a sample that has no reference allele at all.
+ *
+ * im_span_query_ends answers the reference side for a whole file of junctions in one launch: for every k, min_out[k] is the minimum of
+ * span[p] of contig tid[k] over [pos[k] - slack, pos[k] + slack] clipped to [0, length] -- by definition what
+ * im_span_query_tid(ctx, tid[k], 1, &beg, &end, ..) answers for that interval, which takes one contig per call.  Synchronous, on the
+ * context's stream, behind what is queued there; every contig asked about must have been through im_span_scan (a contig that no record
+ * was scattered to answers 0 scanned or not).  n == 0 is IM_OK without a launch.  n < 0, slack outside 0 .. 255, a null column with
+ * n > 0, a tid outside the reference, a pos outside [0, length] and an array that im_span_enable has not made are IM_E_ARG with a
+ * message that names the first offending end; the ranges are checked on the host before anything is copied.
+ *
+ * Limits of the genotype: a reference read must hold `flank` bases on either side while a split read needs a clip of min_clip bases and
+ * a placed remainder, so the two alleles are not equally detectable and nothing corrects for it; RS is exact for one position while
+ * micro-homology lets an aligner place the split anywhere inside it; span[] counts runs, so a read with an indel near the end may count
+ * on neither side; the two junctions of an inversion or of a reciprocal translocation are genotyped independently. */
+int im_span_query_ends(im_ctx* ctx, int32_t n, const int32_t* tid, const int32_t* pos, int32_t slack, uint32_t* min_out);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

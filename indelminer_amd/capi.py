@@ -216,6 +216,7 @@ def lib():
         L.im_span_scan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.im_span_reset.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.im_span_query_tid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.im_span_query_ends.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.im_span_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         L.im_span_query.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.im_pairspan_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
@@ -590,6 +591,16 @@ class Context:
     def span_query_tid(self, tid, beg, end):
         """per query the minimum of span[p] over [beg, end] inclusive"""
         return self._query_tid(lib().im_span_query_tid, tid, beg, end)
+
+    def span_query_ends(self, tid, pos, slack=0):
+        """per end (tid, pos), each on its own contig, the minimum of span[p] over [pos - slack, pos + slack] clipped to the contig: one
+        launch for all of them (-K)"""
+        tid = np.ascontiguousarray(tid, dtype=np.int32)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        assert len(tid) == len(pos)
+        out = np.zeros(max(len(tid), 1), dtype=np.uint32)
+        self._check(lib().im_span_query_ends(self.h, len(tid), _ptr(tid), _ptr(pos), int(slack), _ptr(out)))
+        return out[:len(tid)]
 
     def span_build(self, contig_len, run_start, run_len, flank):
         self._build(lib().im_span_build, contig_len, run_start, run_len, flank)

@@ -1201,6 +1201,37 @@ int im_span_reset(im_ctx* ctx, int32_t tid, void* stream) { return reset_genome_
 int im_span_query_tid(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* beg, const int32_t* end, uint32_t* min_out)
 { return query_genome_array(ctx, &im_ctx::all_span, tid, n, beg, end, kMinimum, min_out, nullptr); }
 
+// A list of ends, each on its own contig: every range is checked here, before anything is copied.  [tid][pos][sums_off, 8 bytes] in, one
+// launch, out back, one wait.  The kernel finds a contig's run of the array through the reference's device columns; where the contig
+// keeps its tile offsets is known on the host alone (h_sums_off), so it travels as a column per end.
+int im_span_query_ends(im_ctx* ctx, int32_t n, const int32_t* tid, const int32_t* pos, int32_t slack, uint32_t* min_out)
+{
+    if (!ctx) return IM_E_ARG;
+    const char* who = "im_span_query_ends";
+    const GenomeArray& g = ctx->all_span;
+    if (!g.data) { set_err(ctx, "%s: im_span_enable has not been called", who); return IM_E_ARG; }
+    if (n < 0) { set_err(ctx, "%s: n %d, must be >= 0", who, n); return IM_E_ARG; }
+    if (slack < 0 || slack > 255) { set_err(ctx, "%s: slack %d, must be 0 .. 255", who, slack); return IM_E_ARG; }
+    if (n == 0) return IM_OK;
+    if (!tid || !pos || !min_out) { set_err(ctx, "%s: a null column with n %d", who, n); return IM_E_ARG; }
+    std::vector<int64_t> sums_off((size_t)n);
+    for (int32_t k = 0; k < n; k++) {
+        if (tid[k] < 0 || tid[k] >= ctx->n_contigs) { set_err(ctx, "%s: end %d: tid %d, the reference has %d contigs", who, k, tid[k], ctx->n_contigs); return IM_E_ARG; }
+        if (pos[k] < 0 || pos[k] > ctx->h_len[tid[k]]) { set_err(ctx, "%s: end %d: pos %d, must be 0 .. %d on contig %d", who, k, pos[k], ctx->h_len[tid[k]], tid[k]); return IM_E_ARG; }
+        sums_off[k] = ctx->h_sums_off[tid[k]];
+    }
+    WsColumns C;
+    int rc = ws_columns(ctx, n, 5, &C);
+    if (rc || (rc = C.down(0, tid, 4)) || (rc = C.down(1, pos, 4)) || (rc = C.down(2, sums_off.data(), 8))) return rc;
+    im::SpanEndsArgs A;
+    A.n = n; A.slack = slack; A.tid = C.at<int32_t>(0); A.pos = C.at<int32_t>(1); A.sums_off = C.at<int64_t>(2);
+    A.asc_off = ctx->d_asc_off; A.len = ctx->d_len; A.n_contigs = ctx->n_contigs; A.span = g.data; A.sums = g.sums; A.out = C.at<uint32_t>(4);
+    HIP_TRY(ctx, im::launch_span_query_ends(A, ctx->stream));
+    if ((rc = C.up(4, min_out, 4))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
 int im_span_build(im_ctx* ctx, int64_t contig_len, int32_t n_run, const int32_t* run_start, const int32_t* run_len, int32_t flank)
 { return build_array(ctx, &im_ctx::span, "im_span", contig_len, n_run, run_start, run_len, &flank); }
 

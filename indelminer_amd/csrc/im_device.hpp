@@ -250,6 +250,21 @@ hipError_t launch_cliptail_junction(const TailJunctionArgs& A, hipStream_t strea
 // minimum over [beg, end] inclusive of a scanned array (0 for an interval that is empty after the clip to [0, clen])
 hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end, const int32_t* span, const int32_t* sums,
                              int64_t clen, uint32_t* out, hipStream_t stream);
+// the same minimum for a list of ENDS, each on its own contig (include/indelminer_amd.h, "Junction genotypes"): per end the interval
+// [pos - slack, pos + slack] clipped to its contig, one lane per end, one launch for all n
+struct SpanEndsArgs {
+    int32_t n, slack;                   // slack 0 .. 255
+    const int32_t* tid;                 // [n]
+    const int32_t* pos;                 // [n]
+    const int64_t* sums_off;            // [n] where the end's contig keeps its run of tile offsets in sums
+    const int64_t* asc_off;             // [n_contigs] where a contig's run starts in span (RefDev's)
+    const int32_t* len;                 // [n_contigs]
+    int32_t n_contigs;
+    const int32_t* span;                // the genome-wide array, scanned contig by contig
+    const int32_t* sums;                // the tile offsets of those scans
+    uint32_t* out;                      // [n]
+};
+hipError_t launch_span_query_ends(const SpanEndsArgs& A, hipStream_t stream);
 
 // tasks within IM_MAX_SW_TARGET / IM_MAX_READ run in the LDS form; when the batch holds longer ones (big_grid > 0) a second launch
 // with its boundary rows in big_scratch (support_big_scratch_bytes) takes those

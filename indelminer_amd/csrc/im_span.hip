@@ -12,6 +12,7 @@
 //   span_scatter   one lane per delivered record: runs -> events, gathered in an LDS window, written out with vector atomics
 //   (scan)         launch_depth_scan_tiled, as it is
 //   span_query     one wave per query: minimum of span[p] over [beg, end] inclusive
+//   span_ends      one lane per end, each on its own contig: the same minimum over [pos - slack, pos + slack] (-K)
 // The build form, for callers that name the events themselves, takes (start, length) runs instead of records:
 // launch_depth_build(lo = m, hi = m - 1) makes the same events from them.
 //
@@ -472,6 +473,34 @@ __global__ __launch_bounds__(256) void span_query_kernel(int32_t nq, const int32
     }
 }
 
+// One LANE per end (-K): the minimum of span[p] of contig tid[k] over [pos[k] - slack, pos[k] + slack], clipped to [0, len[tid[k]]]:
+// what span_query_kernel answers for that interval of that contig.  The ends of a call lie on any contigs, so every lane finds its own
+// contig's run in the genome-wide array through asc_off (the scatter's 64-bit offsets) and its contig's run of tile offsets through
+// sums_off[k], which the entry point names per end.  The driver asks with slack 0: one load of the array and one of the offsets per
+// lane, no cross-lane operation, nothing divergent to wait for.  The loop has 2 slack + 1 <= 511 turns for any input.  An end whose
+// contig is not one of the reference's answers 0 and reads nothing (the entry point has refused it before).
+constexpr int kEndsBlock = 256;
+
+__global__ __launch_bounds__(kEndsBlock) void span_ends_kernel(SpanEndsArgs A)
+{
+    const int64_t k = (int64_t)blockIdx.x * kEndsBlock + threadIdx.x;
+    if (k >= A.n) return;
+    const int32_t t = A.tid[k];
+    if (t < 0 || t >= A.n_contigs) { A.out[k] = 0u; return; }
+    const int64_t clen = A.len[t], lo = (int64_t)A.pos[k] - A.slack;
+    const int32_t* __restrict__ data = A.span + A.asc_off[t];
+    const int32_t* __restrict__ offs = A.sums + A.sums_off[k];
+    uint32_t mn = 0xFFFFFFFFu;
+    bool any = false;
+    for (int32_t j = 0; j <= 2 * A.slack; j++) {
+        const int64_t p = lo + j;
+        if (p < 0 || p > clen) continue;
+        mn = min(mn, (uint32_t)(data[p] + offs[p / kScanTile]));
+        any = true;
+    }
+    A.out[k] = any ? mn : 0u;
+}
+
 hipError_t launch_scatter(void (*kernel)(ScatterArgs), const RefDev& ref, const RgTable& rg, int32_t flank, int32_t min_mapq, const im_dev_records& recs,
                           int32_t* diff, hipStream_t stream)
 {
@@ -559,6 +588,14 @@ hipError_t launch_span_query(int32_t nq, const int32_t* beg, const int32_t* end,
     int b = (nq + 3) / 4;
     if (b > 2048) b = 2048;
     hipLaunchKernelGGL(span_query_kernel, dim3(b), dim3(256), 0, stream, nq, beg, end, span, sums, clen, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_span_query_ends(const SpanEndsArgs& A, hipStream_t stream)
+{
+    if (A.n <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)(((int64_t)A.n + kEndsBlock - 1) / kEndsBlock);
+    hipLaunchKernelGGL(span_ends_kernel, dim3(blocks), dim3(kEndsBlock), 0, stream, A);
     return hipGetLastError();
 }
 

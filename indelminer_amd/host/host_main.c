@@ -58,6 +58,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    primary record whose SA tag places the clipped part at the other breakpoint), from either end\n");
     fprintf(file, "\t-J, with -G: write the junctions the split reads name by themselves to this file, a VCF of its own\n");
     fprintf(file, "\t    (no clip pile and no verified bases needed: insertions at the junction, long micro-homology, scattered clips)\n");
+    fprintf(file, "\t-K, with -J: genotype its junctions (FORMAT GT:AD:GQ:RB), the split reads against\n");
+    fprintf(file, "\t    the reads that run through either end on the reference allele\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -115,7 +117,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:MT:SJ:")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:MT:SJ:K")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -152,6 +154,7 @@ int main(int argc, char** argv)
         case 'T': g_bnd_file = optarg; break;                       /* not an option of the reference */
         case 'S': g_split_links = 1; break;                         /* not an option of the reference */
         case 'J': g_junc_file = optarg; break;                      /* not an option of the reference */
+        case 'K': g_junc_genotype = 1; break;                       /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -277,11 +280,18 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: split-link junctions (-J) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -K: behind -J's refusals; every other refusal reaches it through -J and -G */
+    if (g_junc_genotype) {
+        if (!g_junc_file) { fprintf(stderr, "indelminer: -K needs -J\n"); return EXIT_FAILURE; }
+        if (!SPANENDS_API_PRESENT) {
+            fprintf(stderr, "indelminer: junction genotypes (-K) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = g_split_links = 0; g_ins_file = g_dup_file = g_inv_file = g_bnd_file = g_junc_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
+        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = g_split_links = g_junc_genotype = 0; g_ins_file = g_dup_file = g_inv_file = g_bnd_file = g_junc_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {

@@ -998,6 +998,13 @@ static void junc_describe(FILE* f)
                "##INFO=<ID=SE,Number=1,Type=Integer,Description=\"Split reads that name exactly these two ends, from either\">\n");
     fprintf(f, "##INFO=<ID=SR,Number=2,Type=Integer,Description=\"Split reads whose primary part ends within %d bases of the first end and whose SA tag "
                "places the clipped part within %d bases of the second, and the same from the second to the first\">\n", SPLIT_EV_WINDOW, SPLIT_EV_WINDOW);
+    if (JUNCGT_ON)
+        fprintf(f, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype of the junction, the most likely of 0/0, 0/1, 1/1 given AD\">\n"
+                   "##FORMAT=<ID=AD,Number=2,Type=Integer,Description=\"Read support of the reference and the junction allele: RS, the smaller number of RB (for JT=DUP "
+                   "less the second number here, not below 0), and the sum of the two numbers of SR\">\n"
+                   "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred-scaled distance to the second most likely genotype, at most 99\">\n"
+                   "##FORMAT=<ID=RB,Number=2,Type=Integer,Description=\"Alignments that match the reference for the -n distance on both sides of the boundary behind "
+                   "base POS, and of the one behind base POS2\">\n");
     fprintf(f, "##splitJunctions=\"junctions from split reads alone: a split read is a primary record at or above -q whose soft clip at either end has %d bases "
                "or more and whose SA tag holds exactly one entry, itself at or above -q, that continues the read; it names two ends (contig, position, side); "
                "an end pair on two contigs, or on one contig %d bases or more apart, is a candidate, its read count SE the reads that name exactly its two ends from "
@@ -1005,9 +1012,22 @@ static void junc_describe(FILE* f)
                "smaller POS, then a smaller POS2 (a candidate that loses stays lost when its winner loses to a third); SR counts every split read between the "
                "windows of %d bases around the two ends, from the first and from the second; a kept candidate needs SR of %d in sum; no clip pile and no "
                "comparison with the reference is needed, so a junction with inserted bases, with micro-homology above %d bases or with reads clipped at "
-               "scattered positions is reported; nothing is merged with or filtered against the records of -U, -N and -T; no genotype; a tag with several "
+               "scattered positions is reported; nothing is merged with or filtered against the records of -U, -N and -T; %s; a tag with several "
                "entries stores nothing; the file has no records once the split-link table has overflowed (stderr says so); POS 0 and POS2 0 are skipped\"\n",
-            CLIP_EV_MIN_CLIP, JUNC_EV_MIN_SPAN, SPLIT_EV_WINDOW, SPLIT_EV_WINDOW, JUNC_EV_MIN_LINKS, CLIPTAIL_MAX_SHIFT);
+            CLIP_EV_MIN_CLIP, JUNC_EV_MIN_SPAN, SPLIT_EV_WINDOW, SPLIT_EV_WINDOW, JUNC_EV_MIN_LINKS, CLIPTAIL_MAX_SHIFT,
+            JUNCGT_ON ? "the genotype is that of ##junctionGenotype" : "no genotype");
+    if (JUNCGT_ON)
+        fprintf(f, "##junctionGenotype=\"every junction against the reads that run through its two ends on the reference allele: ALT is the sum of the two numbers of SR "
+                   "(a split read stores one link, at its primary record, so the two are disjoint sets of reads); RB=RS1,RS2 are -G's count of alignments at or above -q "
+                   "that match the reference for the -n distance on both sides, the smallest within %d bases of the boundary behind base POS and of the one behind "
+                   "base POS2, which is where a clip on either side puts the junction (a split read's own alignment ends there and is in neither); RS is the "
+                   "smaller of RS1 and RS2, except for JT=DUP, where RS is that less ALT and not below 0: a tandem duplication keeps both outer boundaries of the "
+                   "duplicated segment intact on the duplicated allele, so every copy of that allele adds reference-looking reads at POS and at POS2 at the rate at which "
+                   "it adds split reads, and a homozygous duplication would show RS about ALT and never be called 1/1; GT and GQ are -G's, the same integers from AD=RS,ALT; "
+                   "a reference read must hold -n bases on either side while a split read needs a clip of %d bases and a placed remainder, so the two alleles are not "
+                   "equally detectable and nothing corrects for it; RS is exact for one position while micro-homology lets an aligner place the split anywhere inside it; "
+                   "a read with an indel near an end may count on neither side; the two junctions of an inversion or of a reciprocal translocation are genotyped "
+                   "independently; the records of -U, -N and -T have no genotype\"\n", JUNC_GT_SLACK, CLIP_EV_MIN_CLIP);
 }
 
 /* -J: the device's search over the table of split links, FILE.  Once per run, on either path, when every scatter has completed.  One
@@ -1018,10 +1038,11 @@ static void junc_search(driver* d)
     if (!f) fatalf("cannot write %s", g_junc_file);
     fprintf(f, "##fileformat=VCFv4.1\n");
     junc_describe(f);
-    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
+    if (JUNCGT_ON) fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", g_sample_name);
+    else fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
     gpu_wait(d);
     int32_t cap = 4096, found = 0;
-    int32_t* q = NULL; uint8_t* qs = NULL; uint32_t* a = NULL;
+    int32_t* q = NULL; uint8_t* qs = NULL; uint32_t* a = NULL; uint32_t* rb = NULL;
     pthread_mutex_lock(&g_query_mu);
     for (;; cap = found) {
         const size_t n = (size_t)cap;
@@ -1030,6 +1051,18 @@ static void junc_search(driver* d)
                                    &found) != IM_OK)
             fatalf("im_splitlink_junctions: %s", im_last_error(d->gpu));
         if (found <= cap) break;
+    }
+    /* -K: the reference side of every end, the first ends then the second ones, in one call behind the search.  Every contig's run of
+     * span[] holds counts by now: either path scans a contig when its last record has been scattered, and this runs behind both */
+    if (JUNCGT_ON && found > 0) {
+        const size_t n = (size_t)cap, m = (size_t)found;
+        int32_t* et = xmalloc(sizeof(int32_t) * 4 * m);
+        rb = xmalloc(sizeof(uint32_t) * 2 * m);
+        memcpy(et, q, sizeof(int32_t) * m); memcpy(et + m, q + 2 * n, sizeof(int32_t) * m);                     /* tid1, tid2 */
+        memcpy(et + 2 * m, q + n, sizeof(int32_t) * m); memcpy(et + 3 * m, q + 3 * n, sizeof(int32_t) * m);     /* pos1, pos2 */
+        if (im_span_query_ends(d->gpu, (int32_t)(2 * m), et, et + 2 * m, JUNC_GT_SLACK, rb) != IM_OK)
+            fatalf("im_span_query_ends: %s", im_last_error(d->gpu));
+        free(et);
     }
     pthread_mutex_unlock(&g_query_mu);
     static const char* const ct[2][2] = {{"3to3", "3to5"}, {"5to3", "5to5"}};
@@ -1048,9 +1081,20 @@ static void junc_search(driver* d)
         const char* jt = tid1 != tid2 ? "TRA" : s1 == s2 ? "INV" : s1 ? "DUP" : "DEL";
         fprintf(f, "\t.\t.\tSVTYPE=BND;CHR2=%s;POS2=%d;CT=%s;JT=%s", c2, p2, ct[s1][s2], jt);
         if (tid1 == tid2) fprintf(f, ";SVLEN=%d", p2 - p1);
-        fprintf(f, ";SE=%u;SR=%u,%u\n", a[k], a[n + k], a[2 * n + k]);
+        fprintf(f, ";SE=%u;SR=%u,%u", a[k], a[n + k], a[2 * n + k]);
+        if (JUNCGT_ON) {
+            /* "Junction genotypes": the smaller of the two ends; a tandem duplication's own reads run through both, so they come off */
+            const int64_t rs1 = rb[k], rs2 = rb[found + k], alt = (int64_t)a[n + k] + a[2 * n + k];
+            int64_t rs = rs1 < rs2 ? rs1 : rs2;
+            if (tid1 == tid2 && s1 && !s2) rs = rs > alt ? rs - alt : 0;
+            int best, gq;
+            genotype_of(rs, alt, &best, &gq);
+            fprintf(f, "\tGT:AD:GQ:RB\t%s:%lld,%lld:%d:%lld,%lld", best == 0 ? "0/0" : best == 1 ? "0/1" : "1/1", (long long)rs, (long long)alt, gq,
+                    (long long)rs1, (long long)rs2);
+        }
+        fprintf(f, "\n");
     }
-    free(q); free(qs); free(a);
+    free(q); free(qs); free(a); free(rb);
     if (fclose(f) != 0) fatalf("cannot write %s", g_junc_file);
     phase_time("split-link junctions (device)");
 }

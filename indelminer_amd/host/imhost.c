@@ -290,6 +290,15 @@ extern int im_splitlink_junctions(im_ctx*, int32_t, int32_t, int32_t, int32_t, i
 #define SPLITJUNC_API_PRESENT (SPLITLINK_API_PRESENT && im_splitlink_junctions)
 #define JUNC_EV_MIN_SPAN DUP_EV_MIN_LEN            /* the two ends of one contig at least this far apart: a smaller event is stdout's indel */
 #define JUNC_EV_MIN_LINKS DUP_EV_MIN_READS         /* split reads between the windows around the two ends, from either: the clip peak's read count */
+/* -K, with -J: a sample column on -J's records (FORMAT GT:AD:GQ:RB), the junction's split reads against the reads that run through its
+ * two ends on the reference allele (include/indelminer_amd.h, "Junction genotypes").  -J needs -G, so the genome-wide span array is
+ * resident and scanned when FILE is written; one call answers every end of every junction.  Without -K FILE is what it was; stdout,
+ * stderr and the other FILEs never change.  Not an option of the reference; referenced weakly. */
+static int g_junc_genotype = 0;
+extern int im_span_query_ends(im_ctx*, int32_t, const int32_t*, const int32_t*, int32_t, uint32_t*) __attribute__((weak));
+#define JUNCGT_ON (g_junc_genotype && SPLITJUNC_ON)
+#define SPANENDS_API_PRESENT (SPAN_API_PRESENT && im_span_query_ends)
+#define JUNC_GT_SLACK 0                            /* RS1 and RS2 are span[] at the one position of either end */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that
