@@ -1052,6 +1052,61 @@ int im_splitlink_junctions(im_ctx* ctx, int32_t window, int32_t min_links, int32
  * on neither side; the two junctions of an inversion or of a reciprocal translocation are genotyped independently. */
 int im_span_query_ends(im_ctx* ctx, int32_t n, const int32_t* tid, const int32_t* pos, int32_t slack, uint32_t* min_out);
 
+/* Junction overlap (-H): how many read bases the two parts of a split read share, or how many lie between them.  A junction of
+ * im_splitlink_junctions says where its two ends are; what sets it apart from the junctions the pile searches report -- inserted or
+ * non-templated bases, micro-homology beyond 32 bases -- is in no column of it.  Yet every read it counts carries that number exactly,
+ * in the two CIGARs a split link is made from.  The table's 16-byte slot is full, so the number lives in an array of its own beside the
+ * table: one uint16_t per slot, 0 = unknown, otherwise d + 32768.
+ *
+ * THE OVERLAP d OF A SPLIT LINK, in the names of "Split links" (L1, T1 the primary's clipped runs; L2, T2 the entry's, AFTER the swap
+ * for the other strand):
+ *   Q1 = L1 + T1 + the lengths of the primary CIGAR's M I = X operations   (the read's length as the primary record states it)
+ *   Q2 = the lengths of the entry's M I S H = X operations                 (the same as the SA entry states it)
+ *   Q1 != Q2:  d is unknown (the two do not describe one read)
+ *   BEHIND:    d = (Q1 - T1) - L2   (the primary's part ends at read base Q1 - T1, the other part starts at L2)
+ *   FRONT:     d = (Q1 - T2) - L1   (the other part ends at read base Q1 - T2, the primary's starts at L1)
+ *   d outside -32767 .. 32767:  d is unknown
+ * d > 0: the two parts share d read bases (micro-homology); d < 0: -d read bases belong to neither part (inserted bases); d = 0: a
+ * clean junction.  I counts as read bases, D and N and P do not.  d is what the aligner says: nothing is compared with the reference.
+ *
+ * WORKED EXAMPLES, a read of 100 bases (primary CIGAR, SA entry, d):
+ *   60M40S   ctgB,p,+,60S40M,60,0;   d = 0
+ *   65M35S   ctgB,p,+,60S40M,60,0;   d = 5
+ *   55M45S   ctgB,p,+,65S35M,60,0;   d = -10
+ *   40S60M   ctgB,p,+,40M60S,60,0;   d = 0
+ *   60M40S   ctgB,p,-,40M60S,60,0;   d = 0
+ * (the last one on the other strand: L2, T2 = 60, 40 after the swap).
+ *
+ * im_splitlink_overlap_enable allocates the array (2 << log2_slots bytes of HBM) and clears it.  It comes behind im_splitlink_enable and
+ * in front of the first link -- or behind im_splitlink_reset: while the table's counter of links asked for is not 0 it is IM_E_ARG with
+ * a message.  A second call is IM_OK.  A new reference frees the array together with the table; im_splitlink_reset clears it.  From then
+ * on im_dev_splitlink_scatter writes every link's d to the slot the link claimed.  WHICH links are stored and both
+ * counters do not depend on the array: im_splitlink_stats, im_splitlink_count and im_splitlink_junctions answer what they answer without.
+ * im_splitlink_add_overlap is im_splitlink_add with a seventh column: d[i] in -32767 .. 32767, or -32768 for unknown; IM_E_ARG with a
+ * message when the array is not enabled.  A link added through im_splitlink_add has no d: it stays unknown.
+ *
+ * im_splitlink_overlap sums the array up for n junctions, the rows of im_splitlink_junctions.  For row k let D be the known d of every
+ * stored link that the two count queries of rule 5 of "Split junctions" count: the links im_splitlink_count counts for
+ * (tid1, side1, pos1 - window, pos1 + window, tid2, side2, pos2 - window, pos2 + window) and for the same with the two ends exchanged,
+ * intervals clipped as it clips them; a link that both queries count (they can meet only where both ends share contig and side and the
+ * windows overlap) is taken once.  Then
+ *   known[k]  = |D|
+ *   median[k] = the LOWER median: the element of index (|D| - 1) / 2 of D sorted in ascending order; 0 when D is empty
+ *   agree[k]  = the number of elements of D equal to median[k] (0 when D is empty)
+ * exactly, for any number of links.  Once the table has dropped links all three columns are filled with 0xFF bytes and the call returns
+ * IM_OK: no answer, not a wrong one.  n == 0 is IM_OK without a launch.  n < 0, window outside 0 .. 255, a null column with n > 0, a side
+ * other than 0 or 1, a contig outside the reference, a table that im_splitlink_enable has not made and an array that
+ * im_splitlink_overlap_enable has not made are IM_E_ARG.  One launch, a wave per junction; synchronous, on the context's stream, behind
+ * what is queued there.  No answer depends on the order in which the links arrived or on the slots that hold them.
+ *
+ * Limits: no inserted sequence (that needs read bases, which the table does not keep); no confidence interval; a read with an indel or
+ * a mismatch inside the micro-homology is given whatever split its aligner chose. */
+int im_splitlink_overlap_enable(im_ctx* ctx);
+int im_splitlink_add_overlap(im_ctx* ctx, int32_t n, const int32_t* tid, const int32_t* pos, const uint8_t* side, const int32_t* tid2, const int32_t* pos2,
+                             const uint8_t* side2, const int16_t* d);
+int im_splitlink_overlap(im_ctx* ctx, int32_t n, const int32_t* tid1, const int32_t* pos1, const uint8_t* side1, const int32_t* tid2, const int32_t* pos2,
+                         const uint8_t* side2, int32_t window, uint32_t* known, int32_t* median, uint32_t* agree);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

@@ -266,6 +266,9 @@ def lib():
         L.im_splitlink_reset.argtypes = [C.c_void_p, C.c_void_p]
         L.im_splitlink_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.im_splitlink_junctions.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 9 + [C.POINTER(C.c_int32)]
+        L.im_splitlink_overlap_enable.argtypes = [C.c_void_p]
+        L.im_splitlink_add_overlap.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7
+        L.im_splitlink_overlap.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3
         L.im_cliptail_junction.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 5
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -866,6 +869,30 @@ class Context:
         (tid1, pos1, tid2, pos2, side1, side2): the distinct end pairs min_span apart that no pair within window at both ends beats
         on exact support, with min_links links between their windows; None once the table has overflowed"""
         return self._clip_search(lib().im_splitlink_junctions, self._JUNCTIONS, cap, window, min_links, min_span)
+
+    def splitlink_overlap_enable(self):
+        """the overlap array beside the split-link table (-H): 2 bytes per slot; behind splitlink_enable, in front of the first link"""
+        self._check(lib().im_splitlink_overlap_enable(self.h))
+
+    def splitlink_add_overlap(self, tid, pos, side, tid2, pos2, side2, d):
+        """splitlink_add with a seventh column: the overlap d of every link (-32767 .. 32767; -32768: unknown)"""
+        tid, pos, tid2, pos2 = (np.ascontiguousarray(x, dtype=np.int32) for x in (tid, pos, tid2, pos2))
+        side, side2 = (np.ascontiguousarray(x, dtype=np.uint8) for x in (side, side2))
+        d = np.ascontiguousarray(d, dtype=np.int16)
+        assert len(tid) == len(pos) == len(side) == len(tid2) == len(pos2) == len(side2) == len(d)
+        self._check(lib().im_splitlink_add_overlap(self.h, len(tid), _ptr(tid), _ptr(pos), _ptr(side), _ptr(tid2), _ptr(pos2), _ptr(side2), _ptr(d)))
+
+    def splitlink_overlap(self, tid1, pos1, side1, tid2, pos2, side2, window):
+        """per junction (tid1, pos1, side1, tid2, pos2, side2), the rows of splitlink_junctions: (known, median, agree) of the overlaps of
+        the links between the windows around its two ends, from either; after an overflow every value is all ones (median -1)"""
+        tid1, pos1, tid2, pos2 = (np.ascontiguousarray(x, dtype=np.int32) for x in (tid1, pos1, tid2, pos2))
+        side1, side2 = (np.ascontiguousarray(x, dtype=np.uint8) for x in (side1, side2))
+        n = len(tid1)
+        assert len(pos1) == len(side1) == len(tid2) == len(pos2) == len(side2) == n
+        known, median, agree = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint32)
+        self._check(lib().im_splitlink_overlap(self.h, n, _ptr(tid1), _ptr(pos1), _ptr(side1), _ptr(tid2), _ptr(pos2), _ptr(side2), int(window),
+                                               _ptr(known), _ptr(median), _ptr(agree)))
+        return known[:n], median[:n], agree[:n]
 
     def cliptail_junction(self, tid1, p1, side1, tid2, p2, side2, max_shift=32):
         """per query of two ends (tid, position, side 0: right clips, 1: left clips): (v1, v2, shift, stored1, stored2) -- the entries of

@@ -77,6 +77,8 @@ struct im_ctx {
     // the contig names im_splitlink_enable was given, and their blob on the device (im_links.hip has the layout)
     std::vector<std::string> split_names;
     uint8_t* split_blob = nullptr;
+    // -H: the overlap of every stored split link, a 16-bit code per slot of the split table (im_splitlink_overlap_enable); null: off
+    uint16_t* split_ovl = nullptr;
     // the median queries' histograms of queries of several slabs (im::launch_depth_median): zeros between calls, sized by the call that
     // needed the most; med_dirty: a call did not get to its end, the next one clears them
     uint32_t* med_scratch = nullptr;
@@ -174,6 +176,8 @@ void free_reference(im_ctx* ctx)
     }
     if (ctx->split_blob) (void)hipFree(ctx->split_blob);
     ctx->split_blob = nullptr; ctx->split_names.clear();
+    if (ctx->split_ovl) (void)hipFree(ctx->split_ovl);
+    ctx->split_ovl = nullptr;
 }
 
 // ---- the keyed table (im_keyed.hpp) behind the clip tails (im_ctx::tail), the pair links (im_ctx::link), the mate links (im_ctx::mate) and the split links (im_ctx::split) ----------
@@ -1801,14 +1805,25 @@ int im_splitlink_enable(im_ctx* ctx, int32_t min_clip, int32_t min_mapq, int32_t
     return IM_OK;
 }
 
-int im_splitlink_reset(im_ctx* ctx, void* stream) { return keyed_reset(ctx, &im_ctx::split, stream); }
+// the overlap array goes back to "unknown" with the slots it belongs to
+int im_splitlink_reset(im_ctx* ctx, void* stream)
+{
+    const int rc = keyed_reset(ctx, &im_ctx::split, stream);
+    if (rc || !ctx->split_ovl) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->split_ovl, 0, (size_t)2 << ctx->split.log2_slots, (hipStream_t)stream));
+    return IM_OK;
+}
+
 int im_splitlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped) { return keyed_stats(ctx, &im_ctx::split, stored, dropped); }
 
+// with the overlap array on, the kernel instantiation that fills it; without, the one there was
 int im_dev_splitlink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
 {
     const uint8_t* names = ctx ? ctx->split_blob : nullptr;
-    return keyed_scatter(ctx, &im_ctx::split, recs, stream, [names](const im::RefDev& ref, const KeyedMember& T, const im_dev_records& r, hipStream_t st) {
-        return im::launch_splitlink_scatter(ref, T.min_clip, T.min_mapq, names, r, T, st); });
+    uint16_t* ovl = ctx ? ctx->split_ovl : nullptr;
+    return keyed_scatter(ctx, &im_ctx::split, recs, stream, [names, ovl](const im::RefDev& ref, const KeyedMember& T, const im_dev_records& r, hipStream_t st) {
+        return ovl ? im::launch_splitlink_scatter_overlap(ref, T.min_clip, T.min_mapq, names, r, T, ovl, st)
+                   : im::launch_splitlink_scatter(ref, T.min_clip, T.min_mapq, names, r, T, st); });
 }
 
 // the host names the links: checked here, staged through the workspace, one lane inserts each, wait
@@ -1919,6 +1934,85 @@ int im_splitlink_junctions(im_ctx* ctx, int32_t window, int32_t min_links, int32
         exact[i] = h[6 * n + r]; n1[i] = h[7 * n + r]; n2[i] = h[8 * n + r];
     }
     return IM_OK;
+}
+
+// ---- junction overlap: micro-homology and inserted bases of the split links, summed up per junction (-H) ----------
+
+// The array beside the table: a 16-bit code per slot, zero = unknown.  Behind im_splitlink_enable and in front of the first link: a
+// link stored earlier would have no d although its record had one.
+int im_splitlink_overlap_enable(im_ctx* ctx)
+{
+    if (!ctx) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->split, nullptr);
+    if (rc) return rc;
+    if (ctx->split_ovl) return IM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long counters[2] = {0, 0};
+    if ((rc = keyed_counters(ctx, ctx->split, counters))) return rc;
+    if (counters[0] > 0) {
+        set_err(ctx, "im_splitlink_overlap_enable: %llu links have been asked for already; enable in front of the first (or behind im_splitlink_reset)", counters[0]);
+        return IM_E_ARG;
+    }
+    const size_t bytes = (size_t)2 << ctx->split.log2_slots;
+    uint16_t* ovl = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&ovl, bytes));
+    hipError_t e = hipMemsetAsync(ovl, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(ovl); set_err(ctx, "im_splitlink_overlap_enable: %s", hipGetErrorString(e)); return IM_E_HIP; }
+    ctx->split_ovl = ovl;
+    return IM_OK;
+}
+
+// im_splitlink_add with a seventh column
+int im_splitlink_add_overlap(im_ctx* ctx, int32_t n, const int32_t* tid, const int32_t* pos, const uint8_t* side, const int32_t* tid2, const int32_t* pos2,
+                             const uint8_t* side2, const int16_t* d)
+{
+    if (!ctx || n < 0 || (n > 0 && (!tid || !pos || !side || !tid2 || !pos2 || !side2 || !d))) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->split, nullptr);
+    if (rc) return rc;
+    if (!ctx->split_ovl) { set_err(ctx, "im_splitlink_overlap_enable has not been called"); return IM_E_ARG; }
+    if ((rc = split_sides(ctx, "im_splitlink_add_overlap", "link", n, side, side2))) return rc;
+    if (n == 0) return IM_OK;
+    WsColumns C;                                                    // tid, pos, tid2, pos2, side, side2, d
+    rc = ws_columns(ctx, n, 7, &C);
+    const int32_t* h_in[4] = {tid, pos, tid2, pos2};
+    for (int k = 0; k < 4 && !rc; k++) rc = C.down(k, h_in[k], 4);
+    if (rc || (rc = C.down(4, side, 1)) || (rc = C.down(5, side2, 1)) || (rc = C.down(6, d, 2))) return rc;
+    HIP_TRY(ctx, im::launch_splitlink_add_overlap(ref_dev(ctx), n, C.at<int32_t>(0), C.at<int32_t>(1), C.at<uint8_t>(4), C.at<int32_t>(2), C.at<int32_t>(3),
+                                                  C.at<uint8_t>(5), C.at<int16_t>(6), ctx->split, ctx->split_ovl, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return IM_OK;
+}
+
+// six columns in, one launch, the three answers and the two counters back, one wait; after an overflow every answer is "none"
+int im_splitlink_overlap(im_ctx* ctx, int32_t n, const int32_t* tid1, const int32_t* pos1, const uint8_t* side1, const int32_t* tid2, const int32_t* pos2,
+                         const uint8_t* side2, int32_t window, uint32_t* known, int32_t* median, uint32_t* agree)
+{
+    if (!ctx || n < 0) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->split, nullptr);
+    if (rc) return rc;
+    const char* who = "im_splitlink_overlap";
+    if (!ctx->split_ovl) { set_err(ctx, "im_splitlink_overlap_enable has not been called"); return IM_E_ARG; }
+    if (window < 0 || window > 255) { set_err(ctx, "%s: window %d, must be 0 .. 255", who, window); return IM_E_ARG; }
+    if (n == 0) return IM_OK;
+    if (!tid1 || !pos1 || !side1 || !tid2 || !pos2 || !side2 || !known || !median || !agree) return IM_E_ARG;
+    if ((rc = split_sides(ctx, who, "junction", n, side1, side2))) return rc;
+    for (int32_t k = 0; k < n; k++)
+        if (tid1[k] < 0 || tid1[k] >= ctx->n_contigs || tid2[k] < 0 || tid2[k] >= ctx->n_contigs) {
+            set_err(ctx, "%s: junction %d: contigs %d and %d, must be 0 .. %d", who, k, tid1[k], tid2[k], ctx->n_contigs - 1);
+            return IM_E_ARG;
+        }
+    WsColumns C;                                                    // tid1, pos1, tid2, pos2, side1, side2, then the three answers
+    rc = ws_columns(ctx, n, 9, &C);
+    const int32_t* h_in[4] = {tid1, pos1, tid2, pos2};
+    for (int k = 0; k < 4 && !rc; k++) rc = C.down(k, h_in[k], 4);
+    if (rc || (rc = C.down(4, side1, 1)) || (rc = C.down(5, side2, 1))) return rc;
+    im::SplitOverlapArgs A;
+    A.nq = n; A.window = window; A.tid1 = C.at<int32_t>(0); A.pos1 = C.at<int32_t>(1); A.side1 = C.at<uint8_t>(4);
+    A.tid2 = C.at<int32_t>(2); A.pos2 = C.at<int32_t>(3); A.side2 = C.at<uint8_t>(5); A.len = ctx->d_len; A.tab = ctx->split; A.ovl = ctx->split_ovl;
+    A.known = C.at<uint32_t>(6); A.median = C.at<int32_t>(7); A.agree = C.at<uint32_t>(8);
+    HIP_TRY(ctx, im::launch_splitlink_overlap(A, ctx->stream));
+    return keyed_answers(ctx, ctx->split, C, 6, {{known, 4}, {median, 4}, {agree, 4}});
 }
 
 // six columns in, one launch, the five answers and the two counters back, one wait; after an overflow every answer is "none"

@@ -236,6 +236,27 @@ struct SplitJuncArgs {
     uint32_t* col[9];                   // tid1, pos1, side1, tid2, pos2, side2, exact, n1, n2
 };
 hipError_t launch_splitlink_junctions(const SplitJuncArgs& A, hipStream_t stream);
+// The overlap of the split links (include/indelminer_amd.h, "Junction overlap"): ovl is one 16-bit code per SLOT of the table, d + 32768
+// or 0 for unknown, written behind the claim of the slot.  The scatter and the add with it store the links, and draw the tickets, that
+// the forms without it do.
+hipError_t launch_splitlink_scatter_overlap(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const uint8_t* names, const im_dev_records& recs,
+                                            const KeyedTable& tab, uint16_t* ovl, hipStream_t stream);
+hipError_t launch_splitlink_add_overlap(const RefDev& ref, int32_t n, const int32_t* tid, const int32_t* pos, const uint8_t* side, const int32_t* tid2,
+                                        const int32_t* pos2, const uint8_t* side2, const int16_t* d, const KeyedTable& tab, uint16_t* ovl,
+                                        hipStream_t stream);
+// per junction (tid1, pos1, side1, tid2, pos2, side2): the known codes of the links between the windows of `window` bases around its two
+// ends, from either -- their number, their lower median as d, and how many equal it; the caller holds the contigs to the reference, the
+// sides to 0 and 1 and window to 0 .. 255
+struct SplitOverlapArgs {
+    int32_t nq, window;
+    const int32_t* tid1; const int32_t* pos1; const uint8_t* side1;
+    const int32_t* tid2; const int32_t* pos2; const uint8_t* side2;
+    const int32_t* len;
+    KeyedTable tab;
+    const uint16_t* ovl;
+    uint32_t* known; int32_t* median; uint32_t* agree;
+};
+hipError_t launch_splitlink_overlap(const SplitOverlapArgs& A, hipStream_t stream);
 // per query (tid1, p1, side1, tid2, p2, side2): the entries at either end that continue in the OTHER end's contig at the best shift
 // 0 .. max_shift <= 32 (include/indelminer_amd.h, "Junctions"), that shift (-1: none matched), and the entries stored at the two keys
 struct TailJunctionArgs {

@@ -53,6 +53,21 @@ __device__ __forceinline__ void keyed_place(const KeyedTable& T, uint64_t home, 
     }
 }
 
+// The same, for a user that keeps something of its own beside a slot (the split links' overlap array, im_links.hip): returns the slot
+// the entry claimed, or the slot count when the run held none (it always holds one: the ticket rule).  The other users keep keyed_place,
+// which is not written on top of this one: forwarding changed the instructions the compiler makes for their kernels.
+__device__ __forceinline__ uint64_t keyed_place_at(const KeyedTable& T, uint64_t home, uint64_t key, uint64_t payload)
+{
+    const uint64_t slots = 1ull << T.log2_slots, mask = slots - 1ull;
+    uint64_t s = home;
+    for (uint64_t step = 0; step < slots; step++, s = (s + 1ull) & mask) {
+        unsigned long long* k = &T.slots[2ull * s];
+        if (step != 0ull && __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) continue;
+        if (atomicCAS(k, 0ull, (unsigned long long)key) == 0ull) { T.slots[2ull * s + 1ull] = payload; return s; }
+    }
+    return slots;
+}
+
 // One entry in, the ticket drawn by the lane itself (counters[0]: inserts): the form for callers that name the events themselves.
 __device__ __forceinline__ void keyed_insert(const KeyedTable& T, uint64_t home, uint64_t key, uint64_t payload)
 {

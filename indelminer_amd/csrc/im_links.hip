@@ -44,6 +44,13 @@
 //   splitjunc_sweep    one lane per slot: the occupied slots into a list, on ranks the workgroup draws with one atomic add
 //   splitjunc_count    one wave per listed link: E, the two window counts and the one emitter among equal links
 //   splitjunc_peak     one wave per 64 listed links: an emitter's neighbours' E decide the peak; rows through one ballot and one atomic add
+//
+// THE JUNCTION OVERLAP (-H): the read bases the two parts of a split read share, or that lie between them, as a 16-bit code per SLOT in
+// an array beside the split-link table.  The rule is in include/indelminer_amd.h (seam 5, "Junction overlap"); DESIGN.md 4.5o has the rest.
+//   splitlink_scatter_overlap, splitlink_add_overlap   the scatter and the add, which also leave the link's code at the slot it claimed
+//                                                      (keyed_place_at); the links stored and the tickets are those of the forms without
+//   splitlink_overlap  one wave per junction: the known codes of the links between its two windows, from either end -- their number,
+//                      their lower median by bisection over the code (18 walks of the same probe runs, no memory), and how many equal it
 
 #include "im_keyed.hpp"
 #include "im_rg.hpp"
@@ -386,6 +393,7 @@ struct SaEntry {
     uint32_t o_name, name_len, name_hash;
     int64_t pos;            // 1-based, 1 .. 2^31 - 1
     int64_t span;           // its M = X D N lengths
+    int64_t qlen;           // Q2 of "Junction overlap": its M I S H = X lengths
     uint32_t lead, trail;   // its first / last operation's length when that is S or H, else 0
     uint32_t mapq;
     bool minus;
@@ -396,7 +404,7 @@ struct SaEntry {
 // value is exactly one well-formed entry followed by ';' NUL or by NUL.
 __device__ __forceinline__ bool parse_sa(const RecView& r, AuxWin& w, uint32_t o, bool on, SaEntry* e)
 {
-    e->o_name = o; e->name_len = 0; e->name_hash = kNameHashSeed; e->pos = 0; e->span = 0; e->lead = e->trail = 0; e->mapq = 0; e->minus = false;
+    e->o_name = o; e->name_len = 0; e->name_hash = kNameHashSeed; e->pos = 0; e->span = 0; e->qlen = 0; e->lead = e->trail = 0; e->mapq = 0; e->minus = false;
     // st: 0 rname, 1 pos, 2 strand, 3 the comma behind it, 4 cigar, 5 mapQ, 6 NM, 7 behind ';'
     uint32_t st = 0, nd = 0, nops = 0;
     uint64_t val = 0;
@@ -428,6 +436,7 @@ __device__ __forceinline__ bool parse_sa(const RecView& r, AuxWin& w, uint32_t o
                     const bool refc = b == 'M' || b == 'D' || b == 'N' || b == '=' || b == 'X', clip = b == 'S' || b == 'H';
                     on = refc || clip || b == 'I' || b == 'P';
                     if (refc) e->span += (int64_t)val;
+                    if (b == 'M' || b == 'I' || b == '=' || b == 'X' || clip) e->qlen += (int64_t)val;
                     e->trail = clip ? (uint32_t)val : 0u;
                     if (nops == 0u) e->lead = e->trail;
                     nops++; nd = 0u; val = 0ull;
@@ -458,7 +467,14 @@ struct SplitScatterArgs {
 // One lane per record.  The front and the CIGAR ends first; a lane whose record has a qualifying clip (almost none of a usual chunk)
 // walks its CIGAR, and only such lanes send their wave into the tag walk and the parse.  One ticket draw per workgroup; a workgroup
 // without a link ends in front of it.
-__global__ __launch_bounds__(kLinkBlock) void splitlink_scatter_kernel(SplitScatterArgs A)
+//
+// kOverlap (-H; include/indelminer_amd.h, "Junction overlap"): the lane also sums Q1 on its CIGAR walk, makes d from Q1, the entry's Q2
+// and the clips it holds already, and leaves d's code in ovl[] at the slot its link claimed.  Which links are stored, and the tickets,
+// are the same in either form; the form without is the kernel as it was.
+constexpr int64_t kOverlapMax = 32767;          // |d| beyond it is unknown; the code is d + 32768, 0 = unknown
+
+template <bool kOverlap>
+__device__ __forceinline__ void splitlink_scatter(const SplitScatterArgs& A, uint16_t* ovl)
 {
     __shared__ uint32_t s_aux[kLinkBlock][kAuxWin / 4];
     const int64_t i = (int64_t)blockIdx.x * kLinkBlock + threadIdx.x;
@@ -482,13 +498,14 @@ __global__ __launch_bounds__(kLinkBlock) void splitlink_scatter_kernel(SplitScat
     }
     // refend, and L1 / T1: the leading and the trailing run of S and H
     bool cand = left || right;
-    int64_t refend = r.pos, l1 = 0, t1 = 0;
+    int64_t refend = r.pos, l1 = 0, t1 = 0, q1 = 0;
     if (cand) {
         bool consumes = false, lead = true;
         for (uint32_t k = 0; k < n; k++) {
             const uint32_t cw = ld_u32(cig + 4u * k), op = cw & 15u;
             const int64_t ln = (int64_t)(cw >> 4);
             if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) { consumes = true; refend += ln; }
+            if constexpr (kOverlap) q1 += (op == 0u || op == 1u || op == 7u || op == 8u) ? ln : 0;
             if (op == 4u || op == 5u) { t1 += ln; l1 += lead ? ln : 0; }
             else { lead = false; t1 = 0; }
         }
@@ -501,6 +518,7 @@ __global__ __launch_bounds__(kLinkBlock) void splitlink_scatter_kernel(SplitScat
     SaEntry e;
     bool has = parse_sa(r, w, o_sa + 1u, cand && o_sa != 0u && type == 'Z', &e);
     uint64_t key = 0, payload = 0;
+    uint32_t code = 0;
     if (has) {
         has = false;
         const int32_t tid2 = contig_of_name(A.names, r.p + e.o_name, e.name_len, e.name_hash);
@@ -523,13 +541,29 @@ __global__ __launch_bounds__(kLinkBlock) void splitlink_scatter_kernel(SplitScat
                 key = link_key(r.tid, pa >> kLinkBucketShift, kind);
                 payload = split_payload(pa, tid2, pb);
                 has = true;
+                if constexpr (kOverlap) {
+                    // Q1 == Q2: both records describe one read.  BEHIND: the primary's part ends at read base Q1 - T1, the other
+                    // starts at L2; FRONT: the other ends at Q1 - T2, the primary starts at L1
+                    const int64_t d = behind ? (q1 + l1) - l2 : (q1 + l1 + t1 - t2) - l1;
+                    if (q1 + l1 + t1 == e.qlen && d >= -kOverlapMax && d <= kOverlapMax) code = (uint32_t)(d + kOverlapMax + 1);
+                }
             }
         }
     }
     unsigned long long ticket;
     if (!keyed_block_tickets<kLinkBlock, 1>(A.tab, has ? 1u : 0u, &ticket)) return;
-    if (has && keyed_admit(A.tab, ticket)) keyed_place(A.tab, keyed_home(key, A.tab.log2_slots), key, payload);
+    if (has && keyed_admit(A.tab, ticket)) {
+        if constexpr (kOverlap) {
+            const uint64_t s = keyed_place_at(A.tab, keyed_home(key, A.tab.log2_slots), key, payload);
+            if (s < (1ull << A.tab.log2_slots)) ovl[s] = (uint16_t)code;
+        } else {
+            keyed_place(A.tab, keyed_home(key, A.tab.log2_slots), key, payload);
+        }
+    }
 }
+
+__global__ __launch_bounds__(kLinkBlock) void splitlink_scatter_kernel(SplitScatterArgs A) { splitlink_scatter<false>(A, nullptr); }
+__global__ __launch_bounds__(kLinkBlock) void splitlink_scatter_overlap_kernel(SplitScatterArgs A, uint16_t* ovl) { splitlink_scatter<true>(A, ovl); }
 
 // for callers that name the links themselves, as six columns; a link that fails the rule's range checks is dropped (no ticket)
 __global__ __launch_bounds__(kLinkWaveBlock) void splitlink_add_kernel(int32_t n, const int32_t* __restrict__ len, int32_t n_contigs,
@@ -546,6 +580,26 @@ __global__ __launch_bounds__(kLinkWaveBlock) void splitlink_add_kernel(int32_t n
     if (pa < 0 || pa > len[ta] || pb < 0 || pb > len[tb]) return;
     const uint64_t key = link_key(ta, pa >> kLinkBucketShift, sa | (sb << 1));
     keyed_insert(tab, keyed_home(key, tab.log2_slots), key, split_payload(pa, tb, pb));
+}
+
+// the same with a seventh column, d (-32768: unknown, which is code 0 as it stands), into ovl[] at the slot the link claimed
+__global__ __launch_bounds__(kLinkWaveBlock) void splitlink_add_overlap_kernel(int32_t n, const int32_t* __restrict__ len, int32_t n_contigs,
+                                                                               const int32_t* __restrict__ tid, const int32_t* __restrict__ pos,
+                                                                               const uint8_t* __restrict__ side, const int32_t* __restrict__ tid2,
+                                                                               const int32_t* __restrict__ pos2, const uint8_t* __restrict__ side2,
+                                                                               const int16_t* __restrict__ d, KeyedTable tab, uint16_t* __restrict__ ovl)
+{
+    const int64_t i = (int64_t)blockIdx.x * kLinkWaveBlock + threadIdx.x;
+    if (i >= n) return;
+    const int32_t ta = tid[i], tb = tid2[i];
+    const int64_t pa = pos[i], pb = pos2[i];
+    const uint32_t sa = side[i], sb = side2[i];
+    if (ta < 0 || ta >= n_contigs || tb < 0 || tb >= n_contigs || sa > 1u || sb > 1u) return;
+    if (pa < 0 || pa > len[ta] || pb < 0 || pb > len[tb]) return;
+    const uint64_t key = link_key(ta, pa >> kLinkBucketShift, sa | (sb << 1));
+    if (!keyed_admit(tab, atomicAdd(&tab.counters[0], 1ull))) return;
+    const uint64_t s = keyed_place_at(tab, keyed_home(key, tab.log2_slots), key, split_payload(pa, tb, pb));
+    if (s < (1ull << tab.log2_slots)) ovl[s] = (uint16_t)((int32_t)d[i] + (int32_t)kOverlapMax + 1);
 }
 
 struct SplitCountArgs {
@@ -754,6 +808,57 @@ __global__ __launch_bounds__(kLinkWaveBlock) void splitjunc_peak_kernel(SplitJun
     }
 }
 
+// ---- the overlap of a junction's links (-H): include/indelminer_amd.h, "Junction overlap", has the rule ----------
+
+// One wave per junction.  D is the codes (ovl[]: d + 32768, 0 = unknown) of the links that the two window counts of rule 5 count: those
+// from the window around end 1 to the one around end 2 and those the other way round, a link that both count taken once.  The lower
+// median is found by bisection over the 16-bit code, not by sorting: a pass walks the same probe runs again and counts the codes in
+// [from, to] by ballot and popcount, so a site of thousands of links needs no memory at all.  Pass 0 counts D; passes 1 .. 16 halve
+// [lo, hi] around the smallest code c with #(codes <= c) >= (|D| - 1) / 2 + 1; pass 17 counts the codes equal to it.  Every branch is
+// on values the whole wave shares; the loops are bounded by the pass, the bucket and the slot count.
+__global__ __launch_bounds__(kLinkWaveBlock) void splitlink_overlap_kernel(SplitOverlapArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int q = wave; q < A.nq; q += nwaves) {
+        const int32_t t1 = A.tid1[q], t2 = A.tid2[q];
+        const int64_t p1 = A.pos1[q], p2 = A.pos2[q];
+        const uint32_t s1 = A.side1[q], s2 = A.side2[q];
+        SplitEnds fwd, bwd;
+        fwd.ta = t1; fwd.tb = t2; fwd.kind = s1 | (s2 << 1);
+        fwd.a0 = p1 - A.window; fwd.a1 = p1 + A.window; fwd.b0 = p2 - A.window; fwd.b1 = p2 + A.window;
+        // both are one test: the second query's intervals are the first one's, exchanged
+        const bool any = link_clip(&fwd.a0, &fwd.a1, A.len[t1]) && link_clip(&fwd.b0, &fwd.b1, A.len[t2]);
+        bwd.ta = t2; bwd.tb = t1; bwd.kind = s2 | (s1 << 1);
+        bwd.a0 = fwd.b0; bwd.a1 = fwd.b1; bwd.b0 = fwd.a0; bwd.b1 = fwd.a1;
+        const bool twice = bwd.ta == fwd.ta && bwd.kind == fwd.kind;       // only then can a link be one of both queries
+        uint32_t known = 0, need = 0, agree = 0, lo = 1u, hi = 65535u;
+        for (int pass = 0; any && pass < 18; pass++) {
+            if (pass >= 1 && pass <= 16 && lo == hi) continue;
+            const uint32_t from = pass == 17 ? lo : 1u, to = pass == 0 ? 65535u : pass == 17 ? lo : (lo + hi) >> 1;
+            uint32_t n = 0;
+            split_walk(A.tab, fwd, lane, [&](bool has, uint32_t slot, const SplitLink& m) {
+                const uint32_t code = has && fwd.in(m) ? (uint32_t)A.ovl[slot] : 0u;
+                n += (uint32_t)__builtin_popcountll(__ballot(code >= from && code <= to));
+            });
+            split_walk(A.tab, bwd, lane, [&](bool has, uint32_t slot, const SplitLink& m) {
+                const uint32_t code = has && bwd.in(m) && !(twice && fwd.in(m)) ? (uint32_t)A.ovl[slot] : 0u;
+                n += (uint32_t)__builtin_popcountll(__ballot(code >= from && code <= to));
+            });
+            if (pass == 0) {
+                known = n; need = (n - 1u) / 2u + 1u;
+                if (n == 0u) break;
+            } else if (pass <= 16) {
+                if (n >= need) hi = to; else lo = to + 1u;
+            } else {
+                agree = n;
+            }
+        }
+        if (lane == 0) { A.known[q] = known; A.median[q] = known ? (int32_t)lo - 32768 : 0; A.agree[q] = agree; }
+    }
+}
+
 template <class Kernel>
 hipError_t launch_link_scatter(Kernel kernel, const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)
 {
@@ -831,6 +936,33 @@ hipError_t launch_splitlink_add(const RefDev& ref, int32_t n, const int32_t* tid
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(splitlink_add_kernel, dim3((n + kLinkWaveBlock - 1) / kLinkWaveBlock), dim3(kLinkWaveBlock), 0, stream, n, ref.len, ref.n_contigs,
                        tid, pos, side, tid2, pos2, side2, tab);
+    return hipGetLastError();
+}
+
+hipError_t launch_splitlink_scatter_overlap(const RefDev& ref, int32_t min_clip, int32_t min_mapq, const uint8_t* names, const im_dev_records& recs,
+                                            const KeyedTable& tab, uint16_t* ovl, hipStream_t stream)
+{
+    if (recs.n <= 0) return hipSuccess;
+    SplitScatterArgs A;
+    A.recs = recs; A.len = ref.len; A.n_contigs = ref.n_contigs; A.min_clip = min_clip; A.min_mapq = min_mapq; A.names = names; A.tab = tab;
+    hipLaunchKernelGGL(splitlink_scatter_overlap_kernel, dim3((recs.n + kLinkBlock - 1) / kLinkBlock), dim3(kLinkBlock), 0, stream, A, ovl);
+    return hipGetLastError();
+}
+
+hipError_t launch_splitlink_add_overlap(const RefDev& ref, int32_t n, const int32_t* tid, const int32_t* pos, const uint8_t* side, const int32_t* tid2,
+                                        const int32_t* pos2, const uint8_t* side2, const int16_t* d, const KeyedTable& tab, uint16_t* ovl,
+                                        hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(splitlink_add_overlap_kernel, dim3((n + kLinkWaveBlock - 1) / kLinkWaveBlock), dim3(kLinkWaveBlock), 0, stream, n, ref.len,
+                       ref.n_contigs, tid, pos, side, tid2, pos2, side2, d, tab, ovl);
+    return hipGetLastError();
+}
+
+hipError_t launch_splitlink_overlap(const SplitOverlapArgs& A, hipStream_t stream)
+{
+    if (A.nq <= 0) return hipSuccess;
+    hipLaunchKernelGGL(splitlink_overlap_kernel, dim3(wave_grid(A.nq)), dim3(kLinkWaveBlock), 0, stream, A);
     return hipGetLastError();
 }
 

@@ -60,6 +60,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    (no clip pile and no verified bases needed: insertions at the junction, long micro-homology, scattered clips)\n");
     fprintf(file, "\t-K, with -J: genotype its junctions (FORMAT GT:AD:GQ:RB), the split reads against\n");
     fprintf(file, "\t    the reads that run through either end on the reference allele\n");
+    fprintf(file, "\t-H, with -J: add HOMLEN, INSLEN and OA to its records, the micro-homology or the inserted bases\n");
+    fprintf(file, "\t    that the split reads' own two alignments state, their median and how many reads agree on it\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -117,7 +119,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:MT:SJ:K")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:MT:SJ:KH")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -155,6 +157,7 @@ int main(int argc, char** argv)
         case 'S': g_split_links = 1; break;                         /* not an option of the reference */
         case 'J': g_junc_file = optarg; break;                      /* not an option of the reference */
         case 'K': g_junc_genotype = 1; break;                       /* not an option of the reference */
+        case 'H': g_junc_overlap = 1; break;                        /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -287,11 +290,18 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: junction genotypes (-K) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -H: behind -K's refusals; every other refusal reaches it through -J and -G */
+    if (g_junc_overlap) {
+        if (!g_junc_file) { fprintf(stderr, "indelminer: -H needs -J\n"); return EXIT_FAILURE; }
+        if (!SPLITOVERLAP_API_PRESENT) {
+            fprintf(stderr, "indelminer: junction overlap (-H) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = g_split_links = g_junc_genotype = 0; g_ins_file = g_dup_file = g_inv_file = g_bnd_file = g_junc_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
+        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = g_split_links = g_junc_genotype = g_junc_overlap = 0; g_ins_file = g_dup_file = g_inv_file = g_bnd_file = g_junc_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {

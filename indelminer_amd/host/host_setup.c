@@ -379,6 +379,8 @@ static void evidence_enable(driver* d)
      * on an assumption of its own (SPLIT_EV_SLOTS_SHIFT), which nobody has measured either */
     if (SPLITTABLE_ON) GPU2(d, im_splitlink_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, evidence_table_log2(d) - SPLIT_EV_SLOTS_SHIFT, d->hdr->n_targets,
                                                   (const char* const*)d->hdr->target_name));
+    /* -H: and the overlap array beside it, two bytes per slot, in front of the first scatter */
+    if (JUNCOVL_ON) GPU2(d, im_splitlink_overlap_enable(d->gpu));
 }
 
 /* a chunk of records on the device, as they are in the file: each option's record rule is its scatter kernel's, on either path */
@@ -998,6 +1000,13 @@ static void junc_describe(FILE* f)
                "##INFO=<ID=SE,Number=1,Type=Integer,Description=\"Split reads that name exactly these two ends, from either\">\n");
     fprintf(f, "##INFO=<ID=SR,Number=2,Type=Integer,Description=\"Split reads whose primary part ends within %d bases of the first end and whose SA tag "
                "places the clipped part within %d bases of the second, and the same from the second to the first\">\n", SPLIT_EV_WINDOW, SPLIT_EV_WINDOW);
+    if (JUNCOVL_ON)
+        fprintf(f, "##INFO=<ID=HOMLEN,Number=1,Type=Integer,Description=\"Micro-homology at the junction: the read bases that both parts of a split read align, "
+                   "the lower median over the reads of SR that state it; 0 when that median is an insertion\">\n"
+                   "##INFO=<ID=INSLEN,Number=1,Type=Integer,Description=\"Inserted bases at the junction: the read bases between the two parts of a split read that "
+                   "neither aligns, from the same median; 0 when it is a homology\">\n"
+                   "##INFO=<ID=OA,Number=2,Type=Integer,Description=\"Overlap agreement: the reads of SR whose own overlap equals that median, and the reads of SR "
+                   "that state one\">\n");
     if (JUNCGT_ON)
         fprintf(f, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype of the junction, the most likely of 0/0, 0/1, 1/1 given AD\">\n"
                    "##FORMAT=<ID=AD,Number=2,Type=Integer,Description=\"Read support of the reference and the junction allele: RS, the smaller number of RB (for JT=DUP "
@@ -1028,6 +1037,17 @@ static void junc_describe(FILE* f)
                    "equally detectable and nothing corrects for it; RS is exact for one position while micro-homology lets an aligner place the split anywhere inside it; "
                    "a read with an indel near an end may count on neither side; the two junctions of an inversion or of a reciprocal translocation are genotyped "
                    "independently; the records of -U, -N and -T have no genotype\"\n", JUNC_GT_SLACK, CLIP_EV_MIN_CLIP);
+    if (JUNCOVL_ON)
+        fprintf(f, "##junctionOverlap=\"every split read states its own overlap d in its two CIGARs: with L1, T1 the clipped bases (S and H) in front of and behind "
+                   "the primary alignment, L2, T2 those of the SA entry (exchanged when the entry is on the other strand), Q1 = L1 + T1 + the primary's M, I, = and X "
+                   "bases and Q2 the entry's M, I, S, H, = and X bases, d = Q1 - T1 - L2 when the entry aligns the bases behind the primary's and d = Q1 - T2 - L1 "
+                   "when it aligns those in front; d above 0 is that many read bases aligned by both parts (micro-homology), d below 0 that many aligned by "
+                   "neither (inserted bases), 0 a clean junction; a read with Q1 other than Q2 or with d outside -%d .. %d states none; over the reads of "
+                   "SR, from either end, within %d bases at both ends, that state one, OA=agree,known gives their number and how many equal their lower "
+                   "median (the element of index (known - 1) / 2 in ascending order), HOMLEN is that median when above 0 and INSLEN its negative when below, "
+                   "each 0 otherwise; HOMLEN=.;INSLEN=.;OA=0,0 when no read states one; no inserted sequence is printed (that needs read bases), there is "
+                   "no CIPOS, d is what the aligner says and is not compared with the reference, so a junction above %d bases of homology is described as well; "
+                   "the records of -U, -N and -T are not touched\"\n", 32767, 32767, SPLIT_EV_WINDOW, CLIPTAIL_MAX_SHIFT);
 }
 
 /* -J: the device's search over the table of split links, FILE.  Once per run, on either path, when every scatter has completed.  One
@@ -1064,6 +1084,14 @@ static void junc_search(driver* d)
             fatalf("im_span_query_ends: %s", im_last_error(d->gpu));
         free(et);
     }
+    /* -H: the overlaps of every junction's links, in one call behind the search: known, median, agree */
+    uint32_t* ov = NULL;
+    if (JUNCOVL_ON && found > 0) {
+        const size_t n = (size_t)cap, m = (size_t)found;
+        ov = xmalloc(sizeof(uint32_t) * 3 * m);
+        if (im_splitlink_overlap(d->gpu, found, q, q + n, qs, q + 2 * n, q + 3 * n, qs + n, SPLIT_EV_WINDOW, ov, (int32_t*)(ov + m), ov + 2 * m) != IM_OK)
+            fatalf("im_splitlink_overlap: %s", im_last_error(d->gpu));
+    }
     pthread_mutex_unlock(&g_query_mu);
     static const char* const ct[2][2] = {{"3to3", "3to5"}, {"5to3", "5to5"}};
     const size_t n = (size_t)cap;
@@ -1082,6 +1110,13 @@ static void junc_search(driver* d)
         fprintf(f, "\t.\t.\tSVTYPE=BND;CHR2=%s;POS2=%d;CT=%s;JT=%s", c2, p2, ct[s1][s2], jt);
         if (tid1 == tid2) fprintf(f, ";SVLEN=%d", p2 - p1);
         fprintf(f, ";SE=%u;SR=%u,%u", a[k], a[n + k], a[2 * n + k]);
+        if (JUNCOVL_ON) {
+            /* "Junction overlap": the lower median of the reads that state one; above 0 a homology, below 0 an insertion */
+            const uint32_t known = ov[k], agree = ov[2 * (size_t)found + k];
+            const int32_t med = (int32_t)ov[(size_t)found + k];
+            if (known == 0) fprintf(f, ";HOMLEN=.;INSLEN=.;OA=0,0");
+            else fprintf(f, ";HOMLEN=%d;INSLEN=%d;OA=%u,%u", med > 0 ? med : 0, med < 0 ? -med : 0, agree, known);
+        }
         if (JUNCGT_ON) {
             /* "Junction genotypes": the smaller of the two ends; a tandem duplication's own reads run through both, so they come off */
             const int64_t rs1 = rb[k], rs2 = rb[found + k], alt = (int64_t)a[n + k] + a[2 * n + k];
@@ -1094,7 +1129,7 @@ static void junc_search(driver* d)
         }
         fprintf(f, "\n");
     }
-    free(q); free(qs); free(a); free(rb);
+    free(q); free(qs); free(a); free(rb); free(ov);
     if (fclose(f) != 0) fatalf("cannot write %s", g_junc_file);
     phase_time("split-link junctions (device)");
 }

@@ -299,6 +299,18 @@ extern int im_span_query_ends(im_ctx*, int32_t, const int32_t*, const int32_t*, 
 #define JUNCGT_ON (g_junc_genotype && SPLITJUNC_ON)
 #define SPANENDS_API_PRESENT (SPAN_API_PRESENT && im_span_query_ends)
 #define JUNC_GT_SLACK 0                            /* RS1 and RS2 are span[] at the one position of either end */
+/* -H, with -J: HOMLEN, INSLEN and OA on -J's records, from the overlap d that every split read's two CIGARs state exactly (shared read
+ * bases: micro-homology; read bases in neither part: inserted ones), kept beside the split-link table by its scatter and summed up per
+ * junction in one call (include/indelminer_amd.h, "Junction overlap").  Without -H FILE is what it was; stdout, stderr and the other
+ * FILEs never change.  Not an option of the reference; referenced weakly. */
+static int g_junc_overlap = 0;
+extern int im_splitlink_overlap_enable(im_ctx*) __attribute__((weak));
+extern int im_splitlink_add_overlap(im_ctx*, int32_t, const int32_t*, const int32_t*, const uint8_t*, const int32_t*, const int32_t*, const uint8_t*,
+                                    const int16_t*) __attribute__((weak));
+extern int im_splitlink_overlap(im_ctx*, int32_t, const int32_t*, const int32_t*, const uint8_t*, const int32_t*, const int32_t*, const uint8_t*, int32_t,
+                                uint32_t*, int32_t*, uint32_t*) __attribute__((weak));
+#define JUNCOVL_ON (g_junc_overlap && SPLITJUNC_ON)
+#define SPLITOVERLAP_API_PRESENT (SPLITJUNC_API_PRESENT && im_splitlink_overlap_enable && im_splitlink_add_overlap && im_splitlink_overlap)
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that
