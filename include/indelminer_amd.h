@@ -1107,6 +1107,62 @@ int im_splitlink_add_overlap(im_ctx* ctx, int32_t n, const int32_t* tid, const i
 int im_splitlink_overlap(im_ctx* ctx, int32_t n, const int32_t* tid1, const int32_t* pos1, const uint8_t* side1, const int32_t* tid2, const int32_t* pos2,
                          const uint8_t* side2, int32_t window, uint32_t* known, int32_t* median, uint32_t* agree);
 
+/* Junction pairs (-E): the read pairs on either side of a junction of im_splitlink_junctions.  Its SE and SR are both counted from the
+ * same split reads; a chimeric read or an aligner artefact gives the same picture.  The read pairs whose insert spans the junction
+ * come from other molecules: an independent kind of evidence.  Both pair tables are on the device already ("Pair links", "Mate links");
+ * two things were missing.  The commonest junction, a deletion's, leaves pairs in the NORMAL orientation that are too far apart, which
+ * the pair links drop; and no query answers junctions with ends on arbitrary contigs in one call.
+ *
+ * THE STRETCHED PAIRS, kind 3 of the pair-link table.  The key's kind field has two bits and value 3 was free: the layout of the table
+ * is what it was.  A delivered record is a link of kind 3, STRETCHED, iff it passes every line of WHICH RECORDS STORE A LINK of "Pair
+ * links" down to the positions (paired, none of 0x4 0x8 0x100 0x200 0x400 0x800, mtid == tid, the leftmost-record rule, mapq >= q, both
+ * starts in [0, length]), its orientation is (r, m) = (0, 1), and flag & 0x2 (proper pair) is CLEAR.  Only the 32-byte core is read;
+ * no read group and no insert range is looked up: the aligner's own verdict stands in for the insert-size test.  A deletion shorter
+ * than the spread of the library's insert size therefore leaves proper pairs and no link.
+ *
+ * im_pairlink_stretched_enable switches the rule on.  It comes behind im_pairlink_enable and in front of the first link -- or behind
+ * im_pairlink_reset: while the table's links stored + dropped is not 0 it is IM_E_ARG with a message.  A second call is IM_OK.
+ * im_pairlink_reset keeps the switch; a new reference drops it with the table.  From then on im_dev_pairlink_scatter stores the kind-3
+ * links as well, and im_pairlink_add and im_pairlink_count take kind 3; without the switch kind 3 is the IM_E_ARG it was.  The links
+ * of kinds 0 .. 2, the contents of their slots and both counters do not depend on the switch, but for the tickets the kind-3 links take.
+ *
+ * AN END is (t, p, s), s as everywhere: 0 = right clips (the reads lie in front of p, on the forward strand), 1 = left clips (the reads
+ * lie behind p, on the reverse strand).  Its WINDOW is W(p, s) = s ? [p - back, p + reach] : [p - reach, p + back], inclusive, clipped
+ * to [0, length[t]]: the windows of -M and -T.  A read that supports the end starts inside W and has strand s.
+ *
+ * im_junction_pairs answers n junctions (tid1, pos1, side1, tid2, pos2, side2), the rows of im_splitlink_junctions:
+ *   tid1 == tid2   out of the pair-link table.  lo is the end with the smaller position (end 1 on a tie), hi the other;
+ *                  kind = K(s_lo, s_hi) with K(1,0) = 0, K(0,0) = 1, K(1,1) = 2, K(0,1) = 3;
+ *                  pe1 = the stored links of that kind with pos in W(lo), mpos in W(hi) and mpos - pos >= min_sep; pe2 = 0.
+ *                  For kinds 0 .. 2 this is, to the letter, what im_pairlink_count answers for the same windows.
+ *   tid1 != tid2   out of the mate-link table.  pe1 = the links stored at tid1 of kind s1 | s2 << 1 with pos in W(end 1), mtid == tid2
+ *                  and mpos in W(end 2); pe2 = the same from end 2, kind s2 | s1 << 1.  min_sep does not apply.
+ * An end whose window is empty after the clip answers 0.  Once the pair-link table has dropped links every answer of the call with
+ * tid1 == tid2 is 0xFFFFFFFF in both columns, and once the mate-link table has, every answer with tid1 != tid2: per table, no answer,
+ * not a wrong one; the other class still answers.
+ *
+ * WORKED EXAMPLES, reach 1000, back 32, min_sep 50, on contigs of 100 000 bases (junction; the pairs that count, as the leftmost
+ * record's strand and start -> its mate's):
+ *   DEL       (0, 5000, 0, 0, 5400, 1)   kind K(0,1) = 3: forward in [4000, 5032] -> reverse in [5368, 6400], flag 0x2 clear, >= 50 apart
+ *   DUP       (0, 5000, 1, 0, 5400, 0)   kind K(1,0) = 0: reverse in [4968, 6000] -> forward in [4400, 5432], >= 50 apart
+ *   INV 3to3  (0, 5000, 0, 0, 9000, 0)   kind K(0,0) = 1: forward in [4000, 5032] -> forward in [8000, 9032]
+ *   INV 5to5  (0, 5000, 1, 0, 9000, 1)   kind K(1,1) = 2: reverse in [4968, 6000] -> reverse in [8968, 10000]
+ *   TRA       (0, 5000, 0, 1, 7000, 1)   pe1: at contig 0, kind 0 | 1 << 1 = 2, forward in [4000, 5032], mate on contig 1 in [6968, 8000];
+ *                                        pe2: at contig 1, kind 1 | 0 << 1 = 1, reverse in [6968, 8000], mate on contig 0 in [4000, 5032]
+ * (one pair of the TRA junction stores a mate link at either contig, so it is counted in pe1 by one record and in pe2 by the other).
+ *
+ * IM_E_ARG with a message that names the junction's index: a contig outside the reference, a side other than 0 and 1; with a message:
+ * reach < 0 or back < 0, reach + back > 65 535, min_sep < 0, n < 0, a null array with n >= 1, a pair-link table that is not enabled or
+ * not in the stretched form, a mate-link table that is not enabled.  n == 0 is IM_OK without a launch.  One launch, a wave per
+ * junction; synchronous, on the context's stream, behind what is queued there.  No answer depends on the order in which the links
+ * arrived or on the slots that hold them.
+ *
+ * Limits: the proper-pair flag is the aligner's; the mate's mapping quality is not known; a duplication or an inversion shorter than a
+ * read leaves no such pair; nothing is compared with an insert-size distribution. */
+int im_pairlink_stretched_enable(im_ctx* ctx);
+int im_junction_pairs(im_ctx* ctx, int32_t n, const int32_t* tid1, const int32_t* pos1, const uint8_t* side1, const int32_t* tid2, const int32_t* pos2,
+                      const uint8_t* side2, int32_t reach, int32_t back, int32_t min_sep, uint32_t* pe1, uint32_t* pe2);
+
 /* ---- multi-GPU: one collective ------------------------------------------------ */
 
 /* Contigs are independent (the reference's own parallel mode is one process per -c

@@ -269,6 +269,8 @@ def lib():
         L.im_splitlink_overlap_enable.argtypes = [C.c_void_p]
         L.im_splitlink_add_overlap.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7
         L.im_splitlink_overlap.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3
+        L.im_pairlink_stretched_enable.argtypes = [C.c_void_p]
+        L.im_junction_pairs.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p] * 2
         L.im_cliptail_junction.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 5
         L.im_dev_memset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.im_dev_copy_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -893,6 +895,24 @@ class Context:
         self._check(lib().im_splitlink_overlap(self.h, n, _ptr(tid1), _ptr(pos1), _ptr(side1), _ptr(tid2), _ptr(pos2), _ptr(side2), int(window),
                                                _ptr(known), _ptr(median), _ptr(agree)))
         return known[:n], median[:n], agree[:n]
+
+    def pairlink_stretched_enable(self):
+        """the fourth kind of the pair links (-E), 3 STRETCHED: the normal orientation without the proper-pair flag; behind
+        pairlink_enable, in front of the first link"""
+        self._check(lib().im_pairlink_stretched_enable(self.h))
+
+    def junction_pairs(self, tid1, pos1, side1, tid2, pos2, side2, reach, back, min_sep):
+        """per junction (tid1, pos1, side1, tid2, pos2, side2), the rows of splitlink_junctions: (pe1, pe2), the read pairs between the
+        windows of its two ends -- one contig: the pair links, pe2 = 0; two contigs: the mate links from either end; a junction whose
+        table has overflowed answers 0xFFFFFFFF twice"""
+        tid1, pos1, tid2, pos2 = (np.ascontiguousarray(x, dtype=np.int32) for x in (tid1, pos1, tid2, pos2))
+        side1, side2 = (np.ascontiguousarray(x, dtype=np.uint8) for x in (side1, side2))
+        n = len(tid1)
+        assert len(pos1) == len(side1) == len(tid2) == len(pos2) == len(side2) == n
+        pe1, pe2 = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        self._check(lib().im_junction_pairs(self.h, n, _ptr(tid1), _ptr(pos1), _ptr(side1), _ptr(tid2), _ptr(pos2), _ptr(side2), int(reach), int(back),
+                                            int(min_sep), _ptr(pe1), _ptr(pe2)))
+        return pe1[:n], pe2[:n]
 
     def cliptail_junction(self, tid1, p1, side1, tid2, p2, side2, max_shift=32):
         """per query of two ends (tid, position, side 0: right clips, 1: left clips): (v1, v2, shift, stored1, stored2) -- the entries of

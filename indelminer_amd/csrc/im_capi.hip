@@ -79,6 +79,8 @@ struct im_ctx {
     uint8_t* split_blob = nullptr;
     // -H: the overlap of every stored split link, a 16-bit code per slot of the split table (im_splitlink_overlap_enable); null: off
     uint16_t* split_ovl = nullptr;
+    // -E: the pair-link table also takes kind 3, the stretched pairs (im_pairlink_stretched_enable); goes with the table
+    bool link_stretched = false;
     // the median queries' histograms of queries of several slabs (im::launch_depth_median): zeros between calls, sized by the call that
     // needed the most; med_dirty: a call did not get to its end, the next one clears them
     uint32_t* med_scratch = nullptr;
@@ -178,6 +180,7 @@ void free_reference(im_ctx* ctx)
     ctx->split_blob = nullptr; ctx->split_names.clear();
     if (ctx->split_ovl) (void)hipFree(ctx->split_ovl);
     ctx->split_ovl = nullptr;
+    ctx->link_stretched = false;
 }
 
 // ---- the keyed table (im_keyed.hpp) behind the clip tails (im_ctx::tail), the pair links (im_ctx::link), the mate links (im_ctx::mate) and the split links (im_ctx::split) ----------
@@ -298,7 +301,7 @@ int keyed_answers(im_ctx* ctx, const im::KeyedTable& T, const WsColumns& C, int 
 // What the add and query calls of both link families check per link or query (what: "link", "query"): its kind, and -- a0 non-null --
 // that the wave walks 257 buckets at the most, one probe run per 256-base bucket of [a0, a1]
 struct LinkKinds { uint8_t max; const char* words; };
-constexpr LinkKinds kPairKinds = {2, "0 (everted), 1 (forward) or 2 (reverse)"}, kMateKinds = {3, "0 .. 3 (read reverse | mate reverse << 1)"};
+constexpr LinkKinds kPairKinds = {2, "0 (everted), 1 (forward) or 2 (reverse)"}, kPairKindsStretched = {3, "0 (everted), 1 (forward), 2 (reverse) or 3 (stretched)"}, kMateKinds = {3, "0 .. 3 (read reverse | mate reverse << 1)"};
 
 int link_args(im_ctx* ctx, const char* who, const char* what, const LinkKinds& K, int32_t n, const uint8_t* kind, const int32_t* a0, const int32_t* a1)
 {
@@ -1691,14 +1694,18 @@ int im_pairlink_enable(im_ctx* ctx, int32_t min_mapq, int32_t log2_slots) { retu
 int im_pairlink_reset(im_ctx* ctx, void* stream) { return keyed_reset(ctx, &im_ctx::link, stream); }
 int im_pairlink_stats(im_ctx* ctx, uint64_t* stored, uint64_t* dropped) { return keyed_stats(ctx, &im_ctx::link, stored, dropped); }
 
-int im_dev_pairlink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream) { return link_scatter(ctx, &im_ctx::link, recs, stream, im::launch_pairlink_scatter); }
+// in the stretched form, the kernel instantiation with the fourth kind; without, the one there was
+int im_dev_pairlink_scatter(im_ctx* ctx, const im_dev_records* recs, void* stream)
+{
+    return link_scatter(ctx, &im_ctx::link, recs, stream, ctx && ctx->link_stretched ? im::launch_pairlink_scatter_stretched : im::launch_pairlink_scatter);
+}
 
 // the host names the links: checked here, staged through the workspace, one lane inserts each, wait
 int im_pairlink_add(im_ctx* ctx, int32_t tid, int32_t n, const int32_t* pos, const int32_t* mpos, const uint8_t* kind)
 {
     if (!ctx || n < 0 || (n > 0 && (!pos || !mpos || !kind))) return IM_E_ARG;
     int rc = keyed_ready(ctx, ctx->link, &tid);
-    if (rc || (rc = link_args(ctx, "im_pairlink_add", "link", kPairKinds, n, kind, nullptr, nullptr))) return rc;
+    if (rc || (rc = link_args(ctx, "im_pairlink_add", "link", ctx->link_stretched ? kPairKindsStretched : kPairKinds, n, kind, nullptr, nullptr))) return rc;
     if (n == 0) return IM_OK;
     WsColumns C;                                                    // pos, mpos, kind
     rc = ws_columns(ctx, n, 3, &C);
@@ -1718,7 +1725,7 @@ int im_pairlink_count(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kind,
     if (min_sep < 0) { set_err(ctx, "im_pairlink_count: min_sep %d, must be >= 0", min_sep); return IM_E_ARG; }
     if (nq == 0) return IM_OK;
     if (!kind || !a0 || !a1 || !b0 || !b1 || !count_out) return IM_E_ARG;
-    if ((rc = link_args(ctx, "im_pairlink_count", "query", kPairKinds, nq, kind, a0, a1))) return rc;
+    if ((rc = link_args(ctx, "im_pairlink_count", "query", ctx->link_stretched ? kPairKindsStretched : kPairKinds, nq, kind, a0, a1))) return rc;
     WsColumns C;                                                    // a0, a1, b0, b1, kind, the counts
     rc = ws_columns(ctx, nq, 6, &C);
     const int32_t* h_in[4] = {a0, a1, b0, b1};
@@ -1727,6 +1734,25 @@ int im_pairlink_count(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kind,
     HIP_TRY(ctx, im::launch_pairlink_count(nq, tid, C.at<uint8_t>(4), C.at<int32_t>(0), C.at<int32_t>(1), C.at<int32_t>(2), C.at<int32_t>(3), min_sep, ctx->h_len[tid],
                                            ctx->link, C.at<uint32_t>(5), ctx->stream));
     return keyed_answers(ctx, ctx->link, C, 5, {{count_out, 4}});
+}
+
+// The fourth kind of the pair links (-E).  Behind im_pairlink_enable and in front of the first link: a pair delivered earlier would
+// have stored no link although the rule now gives it one.
+int im_pairlink_stretched_enable(im_ctx* ctx)
+{
+    if (!ctx) return IM_E_ARG;
+    int rc = keyed_ready(ctx, ctx->link, nullptr);
+    if (rc) return rc;
+    if (ctx->link_stretched) return IM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long counters[2] = {0, 0};
+    if ((rc = keyed_counters(ctx, ctx->link, counters))) return rc;
+    if (counters[0] > 0) {
+        set_err(ctx, "im_pairlink_stretched_enable: %llu links have been asked for already; enable in front of the first (or behind im_pairlink_reset)", counters[0]);
+        return IM_E_ARG;
+    }
+    ctx->link_stretched = true;
+    return IM_OK;
 }
 
 // ---- mate links: the read pairs whose mate lies on another contig, asked where the mates of a window lie (-T) ----------
@@ -1767,6 +1793,53 @@ int im_matelink_partner(im_ctx* ctx, int32_t tid, int32_t nq, const uint8_t* kin
     HIP_TRY(ctx, im::launch_matelink_partner(nq, tid, C.at<uint8_t>(2), C.at<int32_t>(0), C.at<int32_t>(1), ctx->h_len[tid], ctx->mate, C.at<uint32_t>(3),
                                              C.at<int32_t>(4), C.at<uint32_t>(5), C.at<int32_t>(6), C.at<int32_t>(7), ctx->stream));
     return keyed_answers(ctx, ctx->mate, C, 3, {{n_links, 4}, {mtid_out, 4}, {n_partner, 4}, {lo, 4}, {hi, 4}});
+}
+
+// ---- junction pairs: the read pairs on either side of a junction, out of both tables in one launch (-E) ----------
+
+// six columns in, one launch, the two answers and both tables' counters back, one wait; a junction whose table has dropped links is "none"
+int im_junction_pairs(im_ctx* ctx, int32_t n, const int32_t* tid1, const int32_t* pos1, const uint8_t* side1, const int32_t* tid2, const int32_t* pos2,
+                      const uint8_t* side2, int32_t reach, int32_t back, int32_t min_sep, uint32_t* pe1, uint32_t* pe2)
+{
+    if (!ctx) return IM_E_ARG;
+    const char* who = "im_junction_pairs";
+    if (n < 0) { set_err(ctx, "%s: n %d, must be >= 0", who, n); return IM_E_ARG; }
+    int rc = keyed_ready(ctx, ctx->link, nullptr);
+    if (rc || (rc = keyed_ready(ctx, ctx->mate, nullptr))) return rc;
+    if (!ctx->link_stretched) { set_err(ctx, "im_pairlink_stretched_enable has not been called"); return IM_E_ARG; }
+    if (reach < 0 || back < 0 || (long long)reach + back > 65535) {
+        set_err(ctx, "%s: reach %d, back %d, must be >= 0 and reach + back <= 65535", who, reach, back);
+        return IM_E_ARG;
+    }
+    if (min_sep < 0) { set_err(ctx, "%s: min_sep %d, must be >= 0", who, min_sep); return IM_E_ARG; }
+    if (n == 0) return IM_OK;
+    if (!tid1 || !pos1 || !side1 || !tid2 || !pos2 || !side2 || !pe1 || !pe2) { set_err(ctx, "%s: junction 0: a null column with n %d", who, n); return IM_E_ARG; }
+    if ((rc = split_sides(ctx, who, "junction", n, side1, side2))) return rc;
+    for (int32_t k = 0; k < n; k++)
+        if (tid1[k] < 0 || tid1[k] >= ctx->n_contigs || tid2[k] < 0 || tid2[k] >= ctx->n_contigs) {
+            set_err(ctx, "%s: junction %d: contigs %d and %d, must be 0 .. %d", who, k, tid1[k], tid2[k], ctx->n_contigs - 1);
+            return IM_E_ARG;
+        }
+    WsColumns C;                                                    // tid1, pos1, tid2, pos2, side1, side2, then the two answers
+    rc = ws_columns(ctx, n, 8, &C);
+    const int32_t* h_in[4] = {tid1, pos1, tid2, pos2};
+    for (int k = 0; k < 4 && !rc; k++) rc = C.down(k, h_in[k], 4);
+    if (rc || (rc = C.down(4, side1, 1)) || (rc = C.down(5, side2, 1))) return rc;
+    im::JuncPairArgs A;
+    A.nq = n; A.reach = reach; A.back = back; A.min_sep = min_sep; A.tid1 = C.at<int32_t>(0); A.pos1 = C.at<int32_t>(1); A.side1 = C.at<uint8_t>(4);
+    A.tid2 = C.at<int32_t>(2); A.pos2 = C.at<int32_t>(3); A.side2 = C.at<uint8_t>(5); A.len = ctx->d_len; A.pair = ctx->link; A.mate = ctx->mate;
+    A.pe1 = C.at<uint32_t>(6); A.pe2 = C.at<uint32_t>(7);
+    HIP_TRY(ctx, im::launch_junction_pairs(A, ctx->stream));
+    // the answers and the counters of both tables behind the launch, one wait; the overflow is per table: a junction on one contig is
+    // blanked by the pair links' drops, one on two contigs by the mate links'
+    unsigned long long pair_counters[2] = {0, 0}, mate_counters[2] = {0, 0};
+    if ((rc = C.up(6, pe1, 4)) || (rc = C.up(7, pe2, 4))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(pair_counters, ctx->link.counters, sizeof pair_counters, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = keyed_counters(ctx, ctx->mate, mate_counters))) return rc;
+    const bool pair_over = pair_counters[1] > 0, mate_over = mate_counters[1] > 0;
+    for (int32_t k = 0; k < n && (pair_over || mate_over); k++)
+        if (tid1[k] == tid2[k] ? pair_over : mate_over) pe1[k] = pe2[k] = 0xFFFFFFFFu;
+    return IM_OK;
 }
 
 // ---- split links: the soft-clipped primary records whose SA:Z tag places the clipped part, counted between two junction ends (-S) ----------

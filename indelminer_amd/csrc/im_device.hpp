@@ -193,6 +193,22 @@ hipError_t launch_pairlink_add(int32_t n, int32_t tid, int64_t clen, const int32
 // in the first, mpos in the second and mpos - pos >= min_sep; the caller holds a1 - a0 to 65 535
 hipError_t launch_pairlink_count(int32_t nq, int32_t tid, const uint8_t* kind, const int32_t* a0, const int32_t* a1, const int32_t* b0,
                                  const int32_t* b1, int32_t min_sep, int64_t clen, const KeyedTable& tab, uint32_t* count, hipStream_t stream);
+// the same with the fourth kind of "Junction pairs" (3 STRETCHED: the normal orientation, not flagged a proper pair); the links of
+// kinds 0 .. 2 are those of the form above
+hipError_t launch_pairlink_scatter_stretched(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream);
+// per junction (tid1, pos1, side1, tid2, pos2, side2): the read pairs between the windows of its two ends (include/indelminer_amd.h,
+// "Junction pairs") -- on one contig pe1 out of the pair-link table and pe2 = 0, on two contigs pe1 and pe2 out of the mate-link table,
+// from either end; the caller holds the contigs to the reference, the sides to 0 and 1, reach, back and min_sep to >= 0 and
+// reach + back to 65 535
+struct JuncPairArgs {
+    int32_t nq, reach, back, min_sep;
+    const int32_t* tid1; const int32_t* pos1; const uint8_t* side1;
+    const int32_t* tid2; const int32_t* pos2; const uint8_t* side2;
+    const int32_t* len;
+    KeyedTable pair, mate;
+    uint32_t* pe1; uint32_t* pe2;
+};
+hipError_t launch_junction_pairs(const JuncPairArgs& A, hipStream_t stream);
 // im_links.hip: the read pairs whose mate lies on another contig in a keyed table of its own (-T)
 // the records that are a link under the record rule (include/indelminer_amd.h, "Mate links") -> one entry each
 hipError_t launch_matelink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream);

@@ -51,6 +51,13 @@
 //                                                      (keyed_place_at); the links stored and the tickets are those of the forms without
 //   splitlink_overlap  one wave per junction: the known codes of the links between its two windows, from either end -- their number,
 //                      their lower median by bisection over the code (18 walks of the same probe runs, no memory), and how many equal it
+//
+// THE JUNCTION PAIRS (-E): the read pairs on either side of a junction, out of the two pair tables.  The rule is in
+// include/indelminer_amd.h (seam 5, "Junction pairs"); DESIGN.md 4.5p has the rest.
+//   pairlink_scatter_stretched   the pair links' scatter with a fourth kind, 3 STRETCHED: the normal orientation that the aligner has
+//                                NOT flagged a proper pair (a deletion's pairs); the links of kinds 0 .. 2 are those of the form without
+//   junction_pairs     one wave per junction, ends on any contigs: one contig -- the pair links of the kind the two sides name between
+//                      the two windows; two contigs -- the mate links from either end's window into the other's
 
 #include "im_keyed.hpp"
 #include "im_rg.hpp"
@@ -88,15 +95,24 @@ struct LinkScatterArgs {
 // The record rules, on the 32-byte core alone.  A rule says whether a record that has passed the front both share (link_of_record)
 // stores a link; *kind, *payload: what it stores, under the key of (r.tid, r.pos's bucket, *kind).  The front has held r.tid to
 // [0, n_contigs): len[r.tid] may be read; len[r.mtid] only behind the rule's own check of r.mtid.
+//
+// kStretched (-E; include/indelminer_amd.h, "Junction pairs"): the normal orientation is a link of kind 3 when the aligner has not
+// flagged the pair proper (0x2 clear).  The links of kinds 0 .. 2 are the same in either form; the form without is the rule as it was.
+template <bool kStretched>
 struct PairRule {
     static __device__ __forceinline__ bool link(const LinkScatterArgs& A, const RecView& r, uint32_t* kind, uint64_t* payload)
     {
         if (r.mtid != r.tid) return false;
         if (!(r.pos < r.mpos || (r.pos == r.mpos && (r.flag & 0x40u)))) return false;      // each pair once, at its leftmost record
         const uint32_t rev = (r.flag >> 4) & 1u, mrev = (r.flag >> 5) & 1u;
-        if (!rev && mrev) return false;                                 // the normal orientation is no link, whatever its insert size
+        if constexpr (kStretched) {
+            if (!rev && mrev && (r.flag & 0x2u)) return false;          // a proper pair is no link: the aligner's verdict on its insert size
+        } else {
+            if (!rev && mrev) return false;                             // the normal orientation is no link, whatever its insert size
+        }
         if (r.pos < 0 || r.mpos > A.len[r.tid]) return false;          // pos <= mpos behind the leftmost test: both lie in [0, len[tid]]
-        *kind = rev ? (mrev ? 2u : 0u) : 1u;
+        if constexpr (kStretched) *kind = rev ? (mrev ? 2u : 0u) : (mrev ? 3u : 1u);
+        else *kind = rev ? (mrev ? 2u : 0u) : 1u;
         *payload = pair_payload(r.pos, r.mpos);
         return true;
     }
@@ -142,7 +158,8 @@ __device__ __forceinline__ void link_scatter(const LinkScatterArgs& A)
     if (has && keyed_admit(A.tab, ticket)) keyed_place(A.tab, keyed_home(key, A.tab.log2_slots), key, payload);
 }
 
-__global__ __launch_bounds__(kLinkBlock) void pairlink_scatter_kernel(LinkScatterArgs A) { link_scatter<PairRule>(A); }
+__global__ __launch_bounds__(kLinkBlock) void pairlink_scatter_kernel(LinkScatterArgs A) { link_scatter<PairRule<false>>(A); }
+__global__ __launch_bounds__(kLinkBlock) void pairlink_scatter_stretched_kernel(LinkScatterArgs A) { link_scatter<PairRule<true>>(A); }
 __global__ __launch_bounds__(kLinkBlock) void matelink_scatter_kernel(LinkScatterArgs A) { link_scatter<MateRule>(A); }
 
 // for callers that name the events themselves: one lane per link; positions outside [0, clen] are dropped (no ticket)
@@ -859,6 +876,72 @@ __global__ __launch_bounds__(kLinkWaveBlock) void splitlink_overlap_kernel(Split
     }
 }
 
+// ---- the read pairs on either side of a junction (-E): include/indelminer_amd.h, "Junction pairs", has the rule ----------
+
+// The window of an end (p, side) on a contig of clen bases: the reads that support it start inside, in front of p for right clips
+// (side 0) and behind it for left clips (side 1); whether anything is left of it behind the clip
+__device__ __forceinline__ bool junc_window(int64_t p, uint32_t side, int64_t reach, int64_t back, int64_t clen, int64_t* w0, int64_t* w1)
+{
+    *w0 = side ? p - back : p - reach;
+    *w1 = side ? p + reach : p + back;
+    return link_clip(w0, w1, clen);
+}
+
+// One wave per junction.  Both ends on one contig: the pair links (payload pos | mpos << 32) of the kind that the sides of the lower
+// and the upper end name, pos in the lower end's window, mpos in the upper end's, min_sep apart; pe2 = 0.  Ends on two contigs: the
+// mate links (pos = bucket << 8 | payload & 255; mtid, mpos in the payload) stored at end 1's contig that lie in end 1's window and
+// point into end 2's, and the same from end 2.  Which table a junction reads is the wave's (every lane holds the same junction), and so
+// is every branch around a ballot; the loops are bounded by the bucket count (reach + back <= 65 535: 257 at the most) and the slot
+// count.  The sums are by ballot and popcount; lane 0 stores.
+__global__ __launch_bounds__(kLinkWaveBlock) void junction_pairs_kernel(JuncPairArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int q = wave; q < A.nq; q += nwaves) {
+        const int32_t t1 = A.tid1[q], t2 = A.tid2[q];
+        const int64_t p1 = A.pos1[q], p2 = A.pos2[q];
+        const uint32_t s1 = A.side1[q], s2 = A.side2[q];
+        uint32_t n1 = 0, n2 = 0;
+        if (t1 == t2) {
+            // lo: the end with the smaller position, end 1 on a tie
+            const bool first = p1 <= p2;
+            const int64_t plo = first ? p1 : p2, phi = first ? p2 : p1;
+            const uint32_t slo = first ? s1 : s2, shi = first ? s2 : s1;
+            const uint32_t kind = slo ? (shi ? 2u : 0u) : (shi ? 3u : 1u);
+            int64_t a0, a1, b0, b1;
+            const bool in_a = junc_window(plo, slo, A.reach, A.back, A.len[t1], &a0, &a1);
+            const bool in_b = junc_window(phi, shi, A.reach, A.back, A.len[t1], &b0, &b1);
+            if (in_a && in_b) {
+                link_walk(A.pair, t1, kind, a0, a1, lane, [&](bool has, int64_t, uint64_t payload) {
+                    const int64_t pos = (int64_t)(uint32_t)payload, mpos = (int64_t)(uint32_t)(payload >> 32);
+                    const bool counts = has && pos >= a0 && pos <= a1 && mpos >= b0 && mpos <= b1 && mpos - pos >= (int64_t)A.min_sep;
+                    n1 += (uint32_t)__builtin_popcountll(__ballot(counts));
+                });
+            }
+        } else {
+            int64_t a0, a1, b0, b1;
+            const bool in_a = junc_window(p1, s1, A.reach, A.back, A.len[t1], &a0, &a1);
+            const bool in_b = junc_window(p2, s2, A.reach, A.back, A.len[t2], &b0, &b1);
+            if (in_a && in_b) {
+                link_walk(A.mate, t1, s1 | (s2 << 1), a0, a1, lane, [&](bool has, int64_t bucket, uint64_t payload) {
+                    const int64_t pos = (bucket << kLinkBucketShift) | (int64_t)(payload & 255ull), mpos = (int64_t)(uint32_t)(payload >> 32);
+                    const int32_t mt = (int32_t)(((uint32_t)payload >> 8) & 0xFFFFFFu);
+                    const bool counts = has && pos >= a0 && pos <= a1 && mt == t2 && mpos >= b0 && mpos <= b1;
+                    n1 += (uint32_t)__builtin_popcountll(__ballot(counts));
+                });
+                link_walk(A.mate, t2, s2 | (s1 << 1), b0, b1, lane, [&](bool has, int64_t bucket, uint64_t payload) {
+                    const int64_t pos = (bucket << kLinkBucketShift) | (int64_t)(payload & 255ull), mpos = (int64_t)(uint32_t)(payload >> 32);
+                    const int32_t mt = (int32_t)(((uint32_t)payload >> 8) & 0xFFFFFFu);
+                    const bool counts = has && pos >= b0 && pos <= b1 && mt == t1 && mpos >= a0 && mpos <= a1;
+                    n2 += (uint32_t)__builtin_popcountll(__ballot(counts));
+                });
+            }
+        }
+        if (lane == 0) { A.pe1[q] = n1; A.pe2[q] = n2; }
+    }
+}
+
 template <class Kernel>
 hipError_t launch_link_scatter(Kernel kernel, const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)
 {
@@ -874,6 +957,18 @@ hipError_t launch_link_scatter(Kernel kernel, const RefDev& ref, int32_t min_map
 hipError_t launch_pairlink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)
 {
     return launch_link_scatter(pairlink_scatter_kernel, ref, min_mapq, recs, tab, stream);
+}
+
+hipError_t launch_pairlink_scatter_stretched(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)
+{
+    return launch_link_scatter(pairlink_scatter_stretched_kernel, ref, min_mapq, recs, tab, stream);
+}
+
+hipError_t launch_junction_pairs(const JuncPairArgs& A, hipStream_t stream)
+{
+    if (A.nq <= 0) return hipSuccess;
+    hipLaunchKernelGGL(junction_pairs_kernel, dim3(wave_grid(A.nq)), dim3(kLinkWaveBlock), 0, stream, A);
+    return hipGetLastError();
 }
 
 hipError_t launch_matelink_scatter(const RefDev& ref, int32_t min_mapq, const im_dev_records& recs, const KeyedTable& tab, hipStream_t stream)

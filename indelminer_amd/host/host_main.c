@@ -62,6 +62,8 @@ static void print_help(FILE* file)
     fprintf(file, "\t    the reads that run through either end on the reference allele\n");
     fprintf(file, "\t-H, with -J: add HOMLEN, INSLEN and OA to its records, the micro-homology or the inserted bases\n");
     fprintf(file, "\t    that the split reads' own two alignments state, their median and how many reads agree on it\n");
+    fprintf(file, "\t-E, with -J: add PE to its records, the read pairs on either side of the junction (for a deletion\n");
+    fprintf(file, "\t    the pairs in the normal orientation that the aligner has not flagged as proper pairs)\n");
     fprintf(file, "\n");
     fprintf(file, "Assumptions:\n");
     fprintf(file, "\tThe BAM file is coordinate sorted\n");
@@ -119,7 +121,7 @@ int main(int argc, char** argv)
     O.tie_desc = (tie_env && strcmp(tie_env, "expected") == 0) ? 1 : 0;
 
     int c;
-    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:MT:SJ:KH")) != -1) {
+    while ((c = getopt(argc, argv, "dl:hc:e:o:k:g:x:i:s:p:tn:q:af:b:GAPDCVI:U:N:MT:SJ:KHE")) != -1) {
         switch (c) {
         case 'd': O.debug = 1; break;
         case 'l': break;
@@ -158,6 +160,7 @@ int main(int argc, char** argv)
         case 'J': g_junc_file = optarg; break;                      /* not an option of the reference */
         case 'K': g_junc_genotype = 1; break;                       /* not an option of the reference */
         case 'H': g_junc_overlap = 1; break;                        /* not an option of the reference */
+        case 'E': g_junc_pairs = 1; break;                          /* not an option of the reference */
         case '?': break;
         default: print_help(stderr); return EXIT_FAILURE;
         }
@@ -297,11 +300,18 @@ int main(int argc, char** argv)
             fprintf(stderr, "indelminer: junction overlap (-H) needs the device library\n"); return EXIT_FAILURE;
         }
     }
+    /* -E: behind -H's refusals; every other refusal reaches it through -J and -G */
+    if (g_junc_pairs) {
+        if (!g_junc_file) { fprintf(stderr, "indelminer: -E needs -J\n"); return EXIT_FAILURE; }
+        if (!JUNCPAIR_API_PRESENT) {
+            fprintf(stderr, "indelminer: junction pairs (-E) needs the device library\n"); return EXIT_FAILURE;
+        }
+    }
     if (g_genotype) {
         if (!SPAN_API_PRESENT) {
             fprintf(stderr, "indelminer: genotyping (-G) needs the device library\n"); return EXIT_FAILURE;
         }
-        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = g_split_links = g_junc_genotype = g_junc_overlap = 0; g_ins_file = g_dup_file = g_inv_file = g_bnd_file = g_junc_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
+        if (strcmp(O.outputformat, "detailed") == 0) { g_genotype = g_pair_counts = g_depth_evidence = g_clip_evidence = g_clip_verify = g_pair_links = g_split_links = g_junc_genotype = g_junc_overlap = g_junc_pairs = 0; g_ins_file = g_dup_file = g_inv_file = g_bnd_file = g_junc_file = NULL; }    /* -o detailed has no columns to add to, and builds no clip arrays to search */
     }
     if (g_known_counts) {
         if (!im_support_count || !SPAN_API_PRESENT) {
@@ -462,6 +472,8 @@ int main(int argc, char** argv)
     if (MATELINK_ON) say_overflow(d.gpu, im_matelink_stats, "indelminer: -T: the mate-link table overflowed (%llu links stored, %llu dropped): its file has no records\n");
     if (SPLITLINK_ON) say_overflow(d.gpu, im_splitlink_stats, "indelminer: -S: the split-link table overflowed (%llu links stored, %llu dropped): SR is . in the files of -U, -N and -T\n");
     if (SPLITJUNC_ON) say_overflow(d.gpu, im_splitlink_stats, "indelminer: -J: the split-link table overflowed (%llu links stored, %llu dropped): its file has no records\n");
+    if (JUNCPAIR_ON) say_overflow(d.gpu, im_pairlink_stats, "indelminer: -E: the pair-link table overflowed (%llu links stored, %llu dropped): PE is . on one contig in the file of -J\n");
+    if (JUNCPAIR_ON) say_overflow(d.gpu, im_matelink_stats, "indelminer: -E: the mate-link table overflowed (%llu links stored, %llu dropped): PE is .,. on two contigs in the file of -J\n");
     if (t_out) fflush(t_out);
     if (g_timing) fprintf(stderr, "[timing] DP=: %ld windows asked of the device, %ld of them answered from the file (a position of %d records or more within %d bases in front)\n",
                           (long)g_dp_queries, (long)g_dp_from_file, DP_DEEP_LOCUS, (int)g_longest_span);

@@ -352,7 +352,7 @@ static int evidence_table_log2(const driver* d)
 }
 
 #define GPU2(drv, call) do { if ((call) != IM_OK) fatalf("%s: %s", #call, im_last_error((drv)->gpu)); } while (0)
-#define EVIDENCE_ON (SPAN_ON || PAIR_ON || CLIP_ON || PAIRLINK_ON || MATELINK_ON || SPLITTABLE_ON)     /* -V needs -C */
+#define EVIDENCE_ON (SPAN_ON || PAIR_ON || CLIP_ON || PAIRTABLE_ON || MATETABLE_ON || SPLITTABLE_ON)     /* -V needs -C */
 
 /* Once per run, on either path, when the reference is on the device and the insert lengths are known: what the evidence options
  * keep on the device.  Genome-wide arrays and tables keyed by contig: nothing is reset between contigs. */
@@ -372,9 +372,11 @@ static void evidence_enable(driver* d)
     /* -V: and the table of their clipped bases */
     if (CLIPTAIL_ON) GPU2(d, im_cliptail_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, evidence_table_log2(d)));
     /* -M: and the table of pair links, -V's rule with one sixteenth of its slots (LINK_EV_SLOTS_SHIFT says what that assumes) */
-    if (PAIRLINK_ON) GPU2(d, im_pairlink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
+    if (PAIRTABLE_ON) GPU2(d, im_pairlink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
+    /* -E: with its fourth kind, the stretched pairs, in front of the first scatter */
+    if (JUNCPAIR_ON) GPU2(d, im_pairlink_stretched_enable(d->gpu));
     /* -T: and the table of mate links, of the same size on the same assumption, which nobody has measured here either */
-    if (MATELINK_ON) GPU2(d, im_matelink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
+    if (MATETABLE_ON) GPU2(d, im_matelink_enable(d->gpu, O.qthreshold, evidence_table_log2(d) - LINK_EV_SLOTS_SHIFT));
     /* -S, -J: and the table of split links, -C's clip and -q, the contig names as the BAM header spells them, in tid order; the same size
      * on an assumption of its own (SPLIT_EV_SLOTS_SHIFT), which nobody has measured either */
     if (SPLITTABLE_ON) GPU2(d, im_splitlink_enable(d->gpu, CLIP_EV_MIN_CLIP, O.qthreshold, evidence_table_log2(d) - SPLIT_EV_SLOTS_SHIFT, d->hdr->n_targets,
@@ -390,8 +392,8 @@ static void evidence_scatter(driver* d, const im_dev_records* recs, void* stream
     if (PAIR_ON) GPU2(d, im_dev_pairspan_scatter(d->gpu, recs, stream));        /* -P: one more, only then */
     if (CLIP_ON) GPU2(d, im_dev_clip_scatter(d->gpu, recs, stream));            /* -C: one more, only then; these arrays need no scan */
     if (CLIPTAIL_ON) GPU2(d, im_dev_cliptail_scatter(d->gpu, recs, stream));    /* -V: and one behind it, only then */
-    if (PAIRLINK_ON) GPU2(d, im_dev_pairlink_scatter(d->gpu, recs, stream));    /* -M: and one behind that, only then */
-    if (MATELINK_ON) GPU2(d, im_dev_matelink_scatter(d->gpu, recs, stream));    /* -T: and one behind that, only then */
+    if (PAIRTABLE_ON) GPU2(d, im_dev_pairlink_scatter(d->gpu, recs, stream));   /* -M, -E: and one behind that, only then */
+    if (MATETABLE_ON) GPU2(d, im_dev_matelink_scatter(d->gpu, recs, stream));   /* -T, -E: and one behind that, only then */
     if (SPLITTABLE_ON) GPU2(d, im_dev_splitlink_scatter(d->gpu, recs, stream)); /* -S, -J: and one behind that, only then */
 }
 
@@ -1007,6 +1009,9 @@ static void junc_describe(FILE* f)
                    "neither aligns, from the same median; 0 when it is a homology\">\n"
                    "##INFO=<ID=OA,Number=2,Type=Integer,Description=\"Overlap agreement: the reads of SR whose own overlap equals that median, and the reads of SR "
                    "that state one\">\n");
+    if (JUNCPAIR_ON)
+        fprintf(f, "##INFO=<ID=PE,Number=.,Type=Integer,Description=\"Read pairs across the junction: on one contig the pairs of the junction's orientation with "
+                   "one read at either end; on two contigs the pairs counted from the first end and from the second\">\n");
     if (JUNCGT_ON)
         fprintf(f, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype of the junction, the most likely of 0/0, 0/1, 1/1 given AD\">\n"
                    "##FORMAT=<ID=AD,Number=2,Type=Integer,Description=\"Read support of the reference and the junction allele: RS, the smaller number of RB (for JT=DUP "
@@ -1048,6 +1053,19 @@ static void junc_describe(FILE* f)
                    "each 0 otherwise; HOMLEN=.;INSLEN=.;OA=0,0 when no read states one; no inserted sequence is printed (that needs read bases), there is "
                    "no CIPOS, d is what the aligner says and is not compared with the reference, so a junction above %d bases of homology is described as well; "
                    "the records of -U, -N and -T are not touched\"\n", 32767, 32767, SPLIT_EV_WINDOW, CLIPTAIL_MAX_SHIFT);
+    if (JUNCPAIR_ON)
+        fprintf(f, "##junctionPairs=\"every junction against the read pairs on either side of it, which come from other molecules than the split reads of SE and SR: "
+                   "a record counts when it is paired, mapped with a mapped mate, primary, no duplicate and no failure, at or above -q (its mate's quality is not "
+                   "known); an end with CT 3 is supported by forward reads that start from %d bases in front of it to %d behind, an end with CT 5 by reverse reads "
+                   "that start from %d in front of it to %d behind; on one contig PE=n counts the pairs whose leftmost read supports the end with the smaller position "
+                   "(POS on a tie) and whose mate supports the other, their starts at least %d bases apart: JT=DUP reverse then forward, JT=INV both forward (3to3) "
+                   "or both reverse (5to5), and JT=DEL forward then reverse, the normal orientation, only when the aligner has NOT flagged the pair a proper pair "
+                   "(flag 0x2 clear) -- its verdict stands in for an insert-size test, so a deletion shorter than the spread of the library's insert size leaves "
+                   "proper pairs and PE=0 is expected there; on two contigs PE=n1,n2 counts the pairs with a read that supports the first end and its mate "
+                   "supporting the second, at the record of the first end's read and at that of the second end's; PE=. or PE=.,. once that table has "
+                   "overflowed (stderr says so); a duplication or an inversion shorter than a read leaves no such pair; nothing is filtered by PE, and the "
+                   "ALT of ##junctionGenotype stays the split reads alone; the records of -U, -N and -T are not touched\"\n",
+                LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT, CLIPTAIL_MAX_SHIFT, LINK_EV_WINDOW, LINK_EV_MIN_SEP);
 }
 
 /* -J: the device's search over the table of split links, FILE.  Once per run, on either path, when every scatter has completed.  One
@@ -1092,6 +1110,14 @@ static void junc_search(driver* d)
         if (im_splitlink_overlap(d->gpu, found, q, q + n, qs, q + 2 * n, q + 3 * n, qs + n, SPLIT_EV_WINDOW, ov, (int32_t*)(ov + m), ov + 2 * m) != IM_OK)
             fatalf("im_splitlink_overlap: %s", im_last_error(d->gpu));
     }
+    /* -E: the read pairs on either side of every junction, out of both pair tables in one call behind that: pe1, pe2 */
+    uint32_t* pe = NULL;
+    if (JUNCPAIR_ON && found > 0) {
+        const size_t n = (size_t)cap, m = (size_t)found;
+        pe = xmalloc(sizeof(uint32_t) * 2 * m);
+        if (im_junction_pairs(d->gpu, found, q, q + n, qs, q + 2 * n, q + 3 * n, qs + n, LINK_EV_WINDOW, CLIPTAIL_MAX_SHIFT, LINK_EV_MIN_SEP, pe, pe + m) != IM_OK)
+            fatalf("im_junction_pairs: %s", im_last_error(d->gpu));
+    }
     pthread_mutex_unlock(&g_query_mu);
     static const char* const ct[2][2] = {{"3to3", "3to5"}, {"5to3", "5to5"}};
     const size_t n = (size_t)cap;
@@ -1117,6 +1143,13 @@ static void junc_search(driver* d)
             if (known == 0) fprintf(f, ";HOMLEN=.;INSLEN=.;OA=0,0");
             else fprintf(f, ";HOMLEN=%d;INSLEN=%d;OA=%u,%u", med > 0 ? med : 0, med < 0 ? -med : 0, agree, known);
         }
+        if (JUNCPAIR_ON) {
+            /* "Junction pairs": one number on one contig, one from either end on two; the table's overflow blanks both */
+            const uint32_t n1 = pe[k], n2 = pe[(size_t)found + k];
+            if (tid1 == tid2) { if (n1 == JUNCPAIR_NONE) fprintf(f, ";PE=."); else fprintf(f, ";PE=%u", n1); }
+            else if (n1 == JUNCPAIR_NONE) fprintf(f, ";PE=.,.");
+            else fprintf(f, ";PE=%u,%u", n1, n2);
+        }
         if (JUNCGT_ON) {
             /* "Junction genotypes": the smaller of the two ends; a tandem duplication's own reads run through both, so they come off */
             const int64_t rs1 = rb[k], rs2 = rb[found + k], alt = (int64_t)a[n + k] + a[2 * n + k];
@@ -1129,7 +1162,7 @@ static void junc_search(driver* d)
         }
         fprintf(f, "\n");
     }
-    free(q); free(qs); free(a); free(rb); free(ov);
+    free(q); free(qs); free(a); free(rb); free(ov); free(pe);
     if (fclose(f) != 0) fatalf("cannot write %s", g_junc_file);
     phase_time("split-link junctions (device)");
 }

@@ -311,6 +311,23 @@ extern int im_splitlink_overlap(im_ctx*, int32_t, const int32_t*, const int32_t*
                                 uint32_t*, int32_t*, uint32_t*) __attribute__((weak));
 #define JUNCOVL_ON (g_junc_overlap && SPLITJUNC_ON)
 #define SPLITOVERLAP_API_PRESENT (SPLITJUNC_API_PRESENT && im_splitlink_overlap_enable && im_splitlink_add_overlap && im_splitlink_overlap)
+/* -E, with -J: PE= on -J's records, the read pairs on either side of the junction -- evidence from other molecules than the split reads
+ * that SE and SR count.  Ends on one contig: the pair links of the kind the two sides name, a deletion's being the fourth kind that -E
+ * switches on (normal orientation, not flagged a proper pair); ends on two: the mate links from either end (include/indelminer_amd.h,
+ * "Junction pairs").  It keeps both tables on its own, at -M's and -T's sizes and windows, and needs none of -C, -V, -U, -N, -T, -M and
+ * -S; one call answers every junction.  Without -E every output is what it was; with it stdout, stderr and the other FILEs stay as
+ * they are -- but for one thing: with -M the stretched links share -M's table and can bring its overflow forward.  Not an option of
+ * the reference; referenced weakly. */
+static int g_junc_pairs = 0;
+extern int im_pairlink_stretched_enable(im_ctx*) __attribute__((weak));
+extern int im_junction_pairs(im_ctx*, int32_t, const int32_t*, const int32_t*, const uint8_t*, const int32_t*, const int32_t*, const uint8_t*, int32_t, int32_t,
+                             int32_t, uint32_t*, uint32_t*) __attribute__((weak));
+#define JUNCPAIR_ON (g_junc_pairs && SPLITJUNC_ON)
+#define JUNCPAIR_API_PRESENT (SPLITJUNC_API_PRESENT && PAIRLINK_API_PRESENT && im_matelink_enable && im_dev_matelink_scatter && im_matelink_stats && \
+                              im_pairlink_stretched_enable && im_junction_pairs)
+#define PAIRTABLE_ON (PAIRLINK_ON || JUNCPAIR_ON)  /* the walk keeps the pair links: the table and its scatter; PAIRLINK_ON is -M's PE= alone */
+#define MATETABLE_ON (MATELINK_ON || JUNCPAIR_ON)  /* the walk keeps the mate links: the table and its scatter; MATELINK_ON is -T's search alone */
+#define JUNCPAIR_NONE 0xFFFFFFFFu                  /* what the device answers after the junction's table has overflowed */
 
 /* Runs the reference aborts.  The device pipeline finds the record the reference would die on during the walk (or in the device
  * stage), when only the groups in front of it have been printed; the reference has by then also printed the flushes of that
