@@ -405,10 +405,11 @@ def test_support_sw_hand_made_ties(gpu_ctx):
     assert indels[6:10] == [6, 6, 6, 6], indels
 
 
-@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1000, 50001])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1000, 50001, 600_001])
 def test_compact_results_packs_exactly_the_records_with_evidence(gpu_ctx, n):
     """im_dev_compact_results: status and place of every read, the records with status == IM_ST_EVIDENCE and n_ev > 0 packed whole
-    (any order), nothing else; also with the batch size read from device memory"""
+    (any order), nothing else; also with the batch size read from device memory.  600 001 is more than the 8 x 256 CUs x 256 records of
+    one grid: compact_results_kernel's workgroups take a second tile in their loop"""
     import ctypes as C
     from indelminer_amd import capi
     L = capi.lib()
